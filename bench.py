@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
 """Decode-GEMV benchmark for the VPTQ hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--hidden 8192] [--mode ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--hidden 8192] [--mode ...] [--dump-outputs DIR] [--full]
 
 N = 1 (default): BASELINE.json configs[1] at the hidden size the north-star target is quoted on:
 one VQuantLinear H x H, vector_len 8, k = 256 + 256 residual centroids (2 bits / weight),
 enable_norm, batch = 1, seq = 1, fp16.  A *step* is one decode token through a RING of R
 distinct layers (R x packed-index bytes >= 512 MiB, so neither the 32 MiB of L2 nor the 256 MiB
 Infinity Cache can hold the weights between uses): R fused dequant + GEMV launches through the
-C ABI, captured once in a hipGraph and replayed.  After W warm-up steps, `--regions` (5) timed
-regions of EXACTLY K steps each are run, every one bracketed by a barrier + synchronize; the
-line reports the MEDIAN region (all of them are listed under "regions_ms_per_step").
+C ABI, captured once in a hipGraph and replayed.  After W warm-up steps, EXACTLY K timed steps
+are run, cut into `--regions` (5) regions, every one bracketed by a barrier + synchronize; the
+line reports the MEDIAN region's rate (all of them are listed under "regions_ms_per_step").
   --mode chain   : the ring as ONE persistent launch that walks its layers one after the other
                    (vptq_quant_gemv_chain, independent layers: the next layer's codebooks, activations
                    and first index words are requested while the current one streams)     [N = 1 default]
@@ -25,8 +25,11 @@ line reports the MEDIAN region (all of them are listed under "regions_ms_per_ste
   --mode tp      : output rows split over the ranks, RCCL all-gather per layer (strong scaling)
   --mode rings   : every rank its own ring of independent layers, no collective (weak scaling);
                    with N > 1 this line is also attached to the tp_row line as "weak_scaling"
-Extras (N = 1, unless --no-extras): one launch per layer, the dependent chain, hidden 4096 (BASELINE
-configs[0/1]; chain and single), the reference's roundings (VPTQ_GEMV_EXACT), grouped x4, 16 tokens
+A plain run does only that: set up, warm up, time the K steps, write the outputs of the last step
+(--dump-outputs DIR: DIR/<name>.npy, float32) and print the line.  Everything else is measured or
+checked with --full: CPU baselines and parity against the C oracle, clocks and power, a soak,
+committed PMC traffic, and the extras (N = 1, unless --no-extras; most of them with --extras):
+one launch per layer, the dependent chain, hidden 4096 (BASELINE configs[0/1]; chain and single), the reference's roundings (VPTQ_GEMV_EXACT), grouped x4, 16 tokens
 (batched-decode kernel), the k = 8192 + 256 format (LDS-resident codebooks), tp_row on one GPU (the
 strong-scaling baseline), each a short ring of its own; the prefill configuration (BASELINE configs[3]:
 batch 4 x seq 2048 through 4096x4096 and 14336x4096, bf16, TFLOP/s of both routes) and the
@@ -347,11 +350,11 @@ class SclkSampler:
     """Shader clock of this GPU during the timed regions (rule DVFS in or out as the box-to-box
     spread): a thread reads the current level of pp_dpm_sclk every 20 ms.  None where sysfs does not offer it."""
 
-    def __init__(self, dev_index=0):
+    def __init__(self, dev_index=0, enabled=True):
         import glob
         # the measured shader clock (hwmon freq1_input, Hz) where the driver offers it; else the DPM level table
         # (pp_dpm_sclk: the starred level - on MI300-class parts that is a coarse state, not the live clock)
-        self.card = sysfs_card_of_device(dev_index)   # (matched by PCI address: the node's other GPUs are in /sys too)
+        self.card = sysfs_card_of_device(dev_index) if enabled else None   # (matched by PCI address: the node's other GPUs are in /sys too)
         hw = sorted(glob.glob(os.path.join(self.card, "hwmon", "hwmon*", "freq1_input"))) if self.card else []
         self.path = hw[0] if hw else (os.path.join(self.card, "pp_dpm_sclk") if self.card else None)
         self.kind = "hwmon freq1_input" if hw else "pp_dpm_sclk (starred level)"
@@ -590,9 +593,12 @@ def compute_floor(kname, H):
 
 
 class Timer:
-    """hipGraph capture of `one_pass`, W warm-up replays, then `regions` timed regions of exactly
-    `steps` replays, each bracketed by a barrier + synchronize; HIP events on the launch stream;
-    max over ranks."""
+    """hipGraph capture of `one_pass`, W warm-up replays, then exactly `steps` timed steps cut into (up to) `regions`
+    regions, each bracketed by a barrier + synchronize; HIP events on the launch stream; max over ranks.  Per-step
+    figures of the median region, scaled back to `steps` steps."""
+
+    # --full only: after the timed steps, the same number of steps once more as one-step graph replays
+    ONE_STEP_PER_GRAPH_PASS = True
 
     def __init__(self, dev, dist=None, allow_eager=False):
         self.dev, self.dist, self.allow_eager = dev, dist, allow_eager
@@ -631,6 +637,7 @@ class Timer:
 
         p = max(d for d in range(1, max(1, self.MAX_STEPS_PER_GRAPH) + 1) if steps % d == 0)
         res = []
+        rsteps = []   # steps of each timed region: together exactly `steps`
         with torch.cuda.stream(self.stream):
             one_pass()
             torch.cuda.synchronize()
@@ -683,7 +690,10 @@ class Timer:
                     torch.cuda.synchronize()
             for _ in range(warmup):
                 graph1.replay()
-            for _ in range(regions):
+            replays = steps // p
+            nreg = max(1, min(regions, replays))
+            rsteps = [p * (replays // nreg + (1 if i < replays % nreg else 0)) for i in range(nreg)]
+            for n in rsteps:
                 torch.cuda.synchronize()
                 if dist is not None:
                     dist.barrier()
@@ -692,7 +702,7 @@ class Timer:
                 e1 = torch.cuda.Event(enable_timing=True)
                 t0 = time.perf_counter()
                 e0.record(self.stream)
-                for _ in range(steps // p):
+                for _ in range(n // p):
                     graph.replay()
                 e1.record(self.stream)
                 torch.cuda.synchronize()
@@ -700,11 +710,12 @@ class Timer:
                     dist.barrier()
                 torch.cuda.synchronize()
                 wall = time.perf_counter() - t0
-                res.append(reduce_times(wall, e0.elapsed_time(e1), dist, self.dev))
+                wall, ev = reduce_times(wall, e0.elapsed_time(e1), dist, self.dev)
+                res.append((wall / n, ev / n))     # per step
             # the same K steps once more as K replays of the ONE-step graph (the rounds 1 - 3 methodology: every step pays the
             # ~8 us between two graph launches), so that numbers stay comparable across rounds; never the headline
             one_step_ms = None
-            if captured and p > 1 and dist is None:
+            if captured and p > 1 and dist is None and self.ONE_STEP_PER_GRAPH_PASS:
                 torch.cuda.synchronize()
                 e0 = torch.cuda.Event(enable_timing=True)
                 e1 = torch.cuda.Event(enable_timing=True)
@@ -718,8 +729,10 @@ class Timer:
         self.last_steps_per_graph = p
         res.sort(key=lambda r: r[0])
         med = res[len(res) // 2]
-        return dict(wall_s=med[0], event_ms=med[1], captured=captured, steps_per_graph=p, conditioning_s=cond,
-                    regions_ms_per_step=[r[0] * 1e3 / steps for r in res], ms_per_step_one_step_per_graph=one_step_ms)
+        # (wall_s / event_ms: the median region's per-step figures x `steps`, what `steps` steps take at that rate)
+        return dict(wall_s=med[0] * steps, event_ms=med[1] * steps, captured=captured, steps_per_graph=p, conditioning_s=cond,
+                    regions_ms_per_step=[r[0] * 1e3 for r in res], region_steps=rsteps,
+                    ms_per_step_one_step_per_graph=one_step_ms)
 
 
 def bench_ring(lib, B, dev, timer, H, mode, flags, steps, warmup, regions, rank=0, world=1, group=4,
@@ -812,7 +825,7 @@ def bench_ring(lib, B, dev, timer, H, mode, flags, steps, warmup, regions, rank=
                kernel=kname, ring=R, launches_per_step=launches, hipgraph=t["captured"],
                us_per_layer=t["event_ms"] * 1e3 / (steps * R),
                regions_ms_per_step=t["regions_ms_per_step"], idx_mib=R * idx_bytes >> 20,
-               steps_per_graph=t["steps_per_graph"], conditioning_s=t["conditioning_s"],
+               steps_per_graph=t["steps_per_graph"], conditioning_s=t["conditioning_s"], region_steps=t["region_steps"],
                ms_per_step_one_step_per_graph=t["ms_per_step_one_step_per_graph"])
     return res, layers, x, ys, keeps
 
@@ -824,7 +837,7 @@ def llama70b_projections():
 
 
 def bench_tp_row(lib, B, dev, timer, rank, world, n_layers, flags, steps, warmup, regions, check=True,
-                 fuse_siblings=True, pair=False):
+                 fuse_siblings=True, pair=False, outputs=None):
     """BASELINE config #5 (see the module docstring).  Every rank builds the SAME full projections
     (common seed; the permutation is already absorbed: enable_perm = False) and keeps its slice of
     the input columns; per projection: fused GEMV of the slice with fp32 partial output
@@ -836,7 +849,8 @@ def bench_tp_row(lib, B, dev, timer, rank, world, n_layers, flags, steps, warmup
     pair (--mode tp_pair): the Megatron pairing SURVEY 8(e) describes - q / k / v / gate / up cut
     COLUMN-parallel (output rows, shard_out_features: disjoint output slices, no collective; their
     consumers o / down are row-parallel over the same split), o / down row-parallel as above: 2
-    all-reduces per decoder layer instead of 4."""
+    all-reduces per decoder layer instead of 4.
+    outputs: a list that receives every call's output tensor (what the timed step computes)."""
     from vptq_amd.utils.shard import shard_in_features, shard_out_features
     col_names = ("q_proj", "k_proj", "v_proj", "gate_proj", "up_proj") if pair else ()
     dist = timer.dist
@@ -901,6 +915,8 @@ def bench_tp_row(lib, B, dev, timer, rank, world, n_layers, flags, steps, warmup
                 dist.all_reduce(part)           # fp32 partial sums over the ranks
             y.copy_(part)                       # the ONE rounding (reference: F.linear's)
     t = timer.run(one_pass, steps, warmup, regions)
+    if outputs is not None:
+        outputs.extend(y for (*_, y) in calls)
     ab = sum(alg_bytes(I, O) for (_, O, I) in projs) * n_layers
     per_layer = len(groups)
     n_reduce = sum(1 for grp in groups if projs[grp[0]][0] not in col_names)
@@ -1016,12 +1032,33 @@ def write_full(out, path=None):
     return rel
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs DIR: what the timed path computed in its last step, one DIR/<name>.npy per array, float32
+    (fp16 / bf16 widen exactly).  Above `limit` bytes in all, every array is cut to the same fixed, seeded sample
+    of its flat elements (DIR/<name>.npy) and their flat positions (DIR/<name>_index.npy, float64)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total <= limit:
+            np.save(os.path.join(path, name + ".npy"), a)
+            continue
+        n = max(1, int(a.size * limit / (3 * total)))   # 4 bytes of value + 8 of position per sampled element
+        idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+        np.save(os.path.join(path, name + ".npy"), a.reshape(-1)[idx])
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+    return sorted(arrs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of K steps; the median is reported")
+    ap.add_argument("--regions", type=int, default=5, help="the K timed steps are cut into this many regions; the median is reported")
     ap.add_argument("--hidden", type=int, default=8192)
     ap.add_argument("--ring", type=int, default=0)
     ap.add_argument("--mode", choices=["auto", "chain", "chain_dep", "single", "grouped", "tp", "tp_row", "tp_pair", "rings"], default="auto")
@@ -1037,19 +1074,28 @@ def main():
     ap.add_argument("--arithmetic", choices=["reference", "selective", "folded"], default=None,
                     help="the headline's arithmetic (default: reference = the product default; selective / folded = the opt-in forms, "
                          "vptq_amd.set_arithmetic)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline too: CPU baselines and parity against the C oracle, clocks / power during the "
+                         "timed steps and a soak after them, the one-step-per-graph pass, the committed PMC traffic, the module-path and "
+                         "opt-in rows of the compact line (extras), with N > 1 the tp_pair and weak-scaling lines; the whole result "
+                         "to a JSON file + stderr.  Default: set up, warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and their parity check")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extras")
     ap.add_argument("--extras", action="store_true",
-                    help="measure every other route too (folded opt-in, grouped, tokens, k8192, wide layers, tp_row on one GPU, prefill, the "
-                         "Llama-3-8B-shaped decode loop: ~60 s more).  Default: only the module-path rows of the compact line "
-                         "(one launch per layer at 8192^2 and 4096^2, the large-codebook formats' default route)")
+                    help="(implies --full) measure every other route too (folded opt-in, grouped, tokens, k8192, wide layers, tp_row on one "
+                         "GPU, prefill, the Llama-3-8B-shaped decode loop: ~60 s more).  --full alone: only the module-path rows of the "
+                         "compact line (one launch per layer at 8192^2 and 4096^2, the large-codebook formats' default route)")
     ap.add_argument("--prefetch", action="store_true")
     ap.add_argument("--steps-per-graph", type=int, default=0,
                     help="steps captured per hipGraph (0 = as many as divide K, up to 10; 1 = the rounds 1 - 3 methodology: "
                          "one graph launch per step)")
     a = ap.parse_args()
+    a.full = a.full or a.extras
     if a.steps_per_graph > 0:
         Timer.MAX_STEPS_PER_GRAPH = a.steps_per_graph
+    Timer.ONE_STEP_PER_GRAPH_PASS = a.full
 
     # stdout carries exactly ONE line, the JSON: everything else written to file descriptor 1 - RCCL prints
     # its version banner there, hipBLASLt / MIOpen may warn - goes to stderr
@@ -1058,8 +1104,9 @@ def main():
     os.dup2(2, 1)
 
     def emit(obj):
-        # the full result to gpurun_out/bench_full.json + stderr, the compact line (LAST thing on stdout) to the driver
-        obj["full"] = write_full(obj)
+        # --full: the whole result to a JSON file + stderr (write_full); the compact line (LAST thing on stdout) to the caller
+        if a.full:
+            obj["full"] = write_full(obj)
         sys.stdout.flush()
         sys.stderr.flush()
         os.write(json_fd, (compact_line(obj) + "\n").encode())
@@ -1118,8 +1165,12 @@ def main():
                   "checkpoint-like layers with massive-channel / sparse activations (profiles/r05/gate_count_*)")
 
     if mode in ("tp_row", "tp_pair"):
+        ys = []
         r = bench_tp_row(lib, B, dev, timer, rank, world, a.tp_layers, flags, a.steps, a.warmup, a.regions,
-                         pair=mode == "tp_pair")
+                         pair=mode == "tp_pair", check=a.full, outputs=ys)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {f"y_call{i:03d}": y for i, y in enumerate(ys)})
+        del ys
         out = {
             "metric": "decode GEMV effective GB/s (VQuantLinear 2-bit, batch 1)",
             "value": r["value"], "unit": "GB/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -1142,12 +1193,12 @@ def main():
             "process": {"rank": rank, "local_rank": local_rank, "world": world, "device": torch.cuda.current_device(),
                         "collective_backend": None if dist is None else dist.get_backend()},
         }
-        if world > 1 and not a.no_extras and mode == "tp_row":
+        if world > 1 and a.full and not a.no_extras and mode == "tp_row":
             # the Megatron pairing (2 all-reduces per decoder layer instead of 4) on the same layers
             pr = bench_tp_row(lib, B, dev, Timer(dev, dist, allow_eager=True), rank, world, a.tp_layers, flags,
                               max(5, a.steps // 4), 5, 3, pair=True)
             out["tp_pair"] = {k: v for k, v in pr.items() if k != "regions_ms_per_step"}
-        if world > 1 and not a.no_extras:
+        if world > 1 and a.full and not a.no_extras:
             w, *_ = bench_ring(lib, B, dev, Timer(dev, dist), H, "single", flags, max(5, a.steps // 4), 5, 3,
                                rank=rank, world=world)
             out["weak_scaling"] = {"what": f"{world} x independent rings of 8192^2 layers, no collective",
@@ -1162,12 +1213,15 @@ def main():
     tp_split = "out" if mode == "tp" else None
     if mode == "tp" and H // 8 % world:
         raise SystemExit("tp mode needs the vector-row count divisible by the world size")
-    with SclkSampler(local_rank) as sclk:
+    with SclkSampler(local_rank, enabled=a.full) as sclk:
         r, layers, x, ys, keeps = bench_ring(lib, B, dev, timer, H, mode if mode in ("grouped", "chain", "chain_dep") else "single",
                                              flags, a.steps, a.warmup, a.regions, rank=rank, world=world, group=a.group,
                                              ring=a.ring, tp_split=tp_split, prefetch=a.prefetch, chain=a.chain)
+    if a.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dump_outputs(a.dump_outputs, {"y": torch.stack([y.reshape(y.shape[-2:]) for y in ys])})   # [ring, tokens, out]
     soak = None
-    if rank == 0 and world == 1 and os.environ.get("VPTQ_BENCH_SOAK", "1") != "0":
+    if a.full and rank == 0 and world == 1 and os.environ.get("VPTQ_BENCH_SOAK", "1") != "0":
         # what the package draws and where the shader clock settles while this workload runs back to back for 1.5 s
         with SclkSampler(local_rank) as sk:
             us_replay = timer.soak(1.5)
@@ -1197,8 +1251,9 @@ def main():
                    "us_per_layer": r["us_per_layer"],
                    "kernel": r["kernel"], "arithmetic": arithmetic,
                    "read_ahead_next_layer": bool(a.prefetch), "hipgraph": r["hipgraph"],
-                   "timing": (f"median of {a.regions} regions of {a.steps} steps; a region = {a.steps // r['steps_per_graph']} replays of a "
-                              f"hipGraph holding {r['steps_per_graph']} steps; before the {a.warmup} warm-up steps the workload is replayed "
+                   "timing": (f"{a.steps} timed steps in {len(r['region_steps'])} region(s) of {'/'.join(str(n) for n in sorted(set(r['region_steps'])))} "
+                              f"steps, the median region's rate; a region = replays of a hipGraph holding {r['steps_per_graph']} steps; "
+                              f"before the {a.warmup} warm-up steps the workload is replayed "
                               f"for {r['conditioning_s']:g} s so that clocks and package power are in their sustained state (an idle "
                               "MI355X sits at 160 MHz; bursts of a few ms run faster than the sustained rate)"),
                    "parallelism": (f"tp{world}: output rows of every layer split over {world} ranks, "
@@ -1250,14 +1305,14 @@ def main():
     for rd in reversed(rounds):
         cand = os.path.join(ROOT, "profiles", rd, f"bench_h{H}_{'chain' if chain_mode else mode}"
                             f"{'_exact' if a.exact else '_selective' if a.arithmetic == 'selective' else ''}_pmc_summary.json")
-        if os.path.exists(cand) and not a.prefetch:
+        if a.full and os.path.exists(cand) and not a.prefetch:
             # HBM bytes per launch from a separate rocprofv3 --pmc run of this same command
             # (FETCH_SIZE x2 gfx950 correction + WRITE_SIZE); see the file's _note
             out["roofline"]["traffic"] = json.load(open(cand)).get("hbm_bytes_corrected")
             out["roofline"]["traffic_source"] = os.path.relpath(cand, ROOT)
             out["roofline"]["traffic_from_committed_profile"] = True   # NOT measured in this run: a PMC pass cannot share a process with the timing
             break
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and mode in ("single", "grouped", "chain", "chain_dep"):
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and mode in ("single", "grouped", "chain", "chain_dep"):
         torch.cuda.synchronize()
         # parity on the LAST layer of the ring (of the chain), against the C oracle on the same bits
         x_last = ys[-2] if mode == "chain_dep" else x
@@ -1276,7 +1331,7 @@ def main():
                     assert checked[i] <= 1e-3, f"layer {i}: GPU result differs from the CPU oracle: {checked[i]}"
         out["parity_checked_on"] = {"layers_of_the_ring": sorted(checked), "rel_err_vs_cpu_oracle": [checked[i] for i in sorted(checked)],
                                     "bar": 1e-3, "every_layer": "tests/test_chain_gpu.py::test_chain_of_32_distinct_8192_layers_every_output"}
-    if world == 1 and not a.no_extras and mode in ("single", "chain") and a.exact:
+    if a.full and world == 1 and not a.no_extras and mode in ("single", "chain") and a.exact:
         del layers, ys, keeps
         torch.cuda.empty_cache()
         ex = {}

@@ -9,6 +9,8 @@ from oracle import vptq_oracle as vo
 from _proc import proc_values
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# what the reference itself computed / declared, recorded by tests/golden/gen_golden_recorded.py
+RECORDED_DIR = os.path.join(GOLDEN_DIR, "recorded")
 
 
 def golden_names():
@@ -22,9 +24,9 @@ def _proc_codebook(spec, dtype):
     return vo.from_f32(v, dtype)
 
 
-def load_golden(name):
+def load_golden(name, directory=None):
     """-> (LayerSpec, x_bits [1,T,I], y_bits [1,T,O], cfg dict, W_head)"""
-    z = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+    z = np.load(os.path.join(directory or GOLDEN_DIR, name + ".npz"))
     cfg = json.loads(bytes(z["config"]).decode())
     dt = cfg["dtype"]
     C, k, kr, v = (cfg["num_codebooks"], cfg["num_centroids"],

@@ -13,7 +13,6 @@ from vptq_amd.utils.pack import pack_index, unpack_index_tensor
 from oracle import vptq_oracle as vo
 from _cases import golden_names, load_golden
 from _gpu_util import spec_to_module
-from _refshim import reference_available
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -336,26 +335,28 @@ def test_module_state_dict_contract(name):
     assert ("bias" in sd) == (L.bias is not None)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted")
 def test_module_matches_reference_state_dict_and_meta_init():
+    """Built on the meta device, our VQuantLinear has the reference module's state-dict keys (in order), shapes and
+    dtypes and its derived attributes, for every golden configuration (the reference's side recorded in
+    tests/golden/recorded/reference_modules.json by tests/golden/gen_golden_recorded.py)."""
+    import json
     import gen_golden as gg
-    from _refshim import load_reference
-    ref = load_reference()
+    from _cases import RECORDED_DIR
+    rec = json.load(open(os.path.join(RECORDED_DIR, "reference_modules.json")))
+    assert sorted(rec) == sorted(c[0] for c in gg.CASES)
     for name, I, O, kw, dtype, tokens, dist in gg.CASES:
         C, S = kw["group_num"], kw["outlier_size"]
         G = (I - S) // C
         common = dict(group_size=G, indices_as_float=False, is_indice_packed=True,
                       dtype=gg.TORCH_DT[dtype], enable_proxy_error=False, **kw)
-        rm = ref.VQuantLinear(I, O, **common)
         with torch.device("meta"):
             mm = vptq_amd.VQuantLinear(I, O, **common)
-        rs, ms = rm.state_dict(), mm.state_dict()
-        assert list(rs) == list(ms), name
-        for k in rs:
-            assert rs[k].shape == ms[k].shape and rs[k].dtype == ms[k].dtype, (name, k)
-        for attr in ("padding", "num_indices", "outlier_padding", "vector_len", "num_codebooks",
-                     "num_centroids", "num_res_centroids", "enable_outlier", "enable_residual"):
-            assert getattr(rm, attr) == getattr(mm, attr), (name, attr)
+        rs, ms = rec[name]["state_dict"], mm.state_dict()
+        assert [k for k, _, _ in rs] == list(ms), name
+        for k, shape, dt in rs:
+            assert list(ms[k].shape) == shape and str(ms[k].dtype) == dt, (name, k)
+        for attr, v in rec[name]["attrs"].items():
+            assert getattr(mm, attr) == v, (name, attr)
 
 
 def test_derived_state_cache_follows_the_tensor_not_the_address():
@@ -468,8 +469,8 @@ def test_product_never_imports_oracle():
 
 
 def test_command_line_options_match_the_reference():
-    """`python -m vptq`: same options and defaults as the reference's parser (vptq/app_utils.py:17-53);
-    compared live when the reference is mounted, against its documented set otherwise."""
+    """`python -m vptq`: same options and defaults as the reference's parser (vptq/app_utils.py:17-53); its long
+    options as recorded in tests/golden/recorded/reference_cli_flags.json, its defaults as documented."""
     import importlib.util
     import sys
     import vptq_amd.app_utils as app
@@ -487,13 +488,11 @@ def test_command_line_options_match_the_reference():
             "chat_system_prompt": "you are a math teacher."}
     ours = {a.dest: a.default for a in app.define_basic_args()._actions if a.dest != "help"}
     assert ours == want
-    ref_file = "/root/reference/vptq/app_utils.py"
-    if os.path.exists(ref_file):
-        import re
-        src = open(ref_file).read()
-        flags = set(re.findall(r'"(--[a-z-]+)"', src))
-        mine = {s for a in app.define_basic_args()._actions for s in a.option_strings if s.startswith("--")}
-        assert flags == mine - {"--help"}, (flags, mine)
+    import json
+    from _cases import RECORDED_DIR
+    flags = set(json.load(open(os.path.join(RECORDED_DIR, "reference_cli_flags.json"))))
+    mine = {s for a in app.define_basic_args()._actions for s in a.option_strings if s.startswith("--")}
+    assert flags == mine - {"--help"}, (flags, mine)
     ns = app.define_basic_args().parse_args(["--model", "m", "--chat", "--chat-system-prompt", "s"])
     assert ns.model == "m" and ns.chat and ns.chat_system_prompt == "s" and ns.tokenizer == ""
     with pytest.raises(SystemExit):

@@ -1,13 +1,14 @@
-"""Pin the oracle against the real reference (golden vectors + live import)."""
+"""Pin the oracle against the real reference (golden vectors and recorded results of the reference)."""
 import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
 
 from oracle import vptq_oracle as vo
 from _cases import (golden_names, load_golden, rel_err, bit_identical_frac, big_names, load_big, fmt_names, load_fmt, stored_rows,
-                    v2_names, load_v2)
-from _refshim import reference_available
+                    v2_names, load_v2, RECORDED_DIR)
 
 # fp16: 1 ulp ~ 4.9e-4 relative; bf16: 3.9e-3.  The reference's F.linear and the
 # oracle's float64 dot differ only by summation order -> <= ~1 output ulp.
@@ -62,40 +63,16 @@ def test_residual_mask_quirk_documented():
     assert (rc == r).all() and (rq == (r & 3)).all()
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted (GPU box)")
 def test_oracle_vs_live_reference_random_layers():
-    import torch
-    from _refshim import load_reference
-    import gen_golden as gg
-    vptq = load_reference()
-    cases = [
-        ("r1", 640, 136, dict(vector_lens=[-1, 8], num_centroids=[-1, 256], num_res_centroids=[-1, 256], group_num=1, outlier_size=0, enable_norm=True, enable_perm=True, bias=True), "f16", 2, "ref-test"),
-        ("r2", 8 + 3 * 64, 70, dict(vector_lens=[2, 10], num_centroids=[16, 512], num_res_centroids=[-1, 64], group_num=3, outlier_size=8, enable_norm=True, enable_perm=False, bias=False), "bf16", 1, "llm"),
-        ("r3", 192, 66, dict(vector_lens=[-1, 2], num_centroids=[-1, 16], num_res_centroids=[-1, -1], group_num=1, outlier_size=0, enable_norm=False, enable_perm=True, bias=False), "f16", 4, "ref-test"),
-    ]
-    for ci, (name, I, O, kw, dtype, tokens, dist) in enumerate(cases):
-        m, x, proc = gg.build(vptq, name, I, O, kw, dtype, tokens, dist, seed=99 + ci)
-        with torch.no_grad():
-            W = gg.ref_dequant(vptq, m)
-            y = m(x)
-        L = vo.LayerSpec(I, O, m.vector_len, m.num_centroids, m.num_res_centroids, m.num_codebooks,
-                         m.group_size, m.outlier_size, m.outlier_vector_len, m.num_outlier_centroids, dtype)
-        L.indices = gg.bits(m.indices)
-        L.centroids = gg.bits(m.centroids.weight).reshape(m.num_codebooks, m.num_centroids, m.vector_len)
-        if m.enable_residual:
-            L.res_centroids = gg.bits(m.res_centroids.weight).reshape(m.num_codebooks, m.num_res_centroids, m.vector_len)
-        if m.enable_outlier:
-            L.outlier_indices = gg.bits(m.outlier_indices)
-            L.outlier_centroids = gg.bits(m.outlier_centroids.weight)
-        if m.enable_perm:
-            L.perm = gg.bits(m.perm)
-        if m.enable_norm:
-            L.weight_scale = gg.bits(m.weight_scale); L.weight_bias = gg.bits(m.weight_bias)
-        if m.bias is not None:
-            L.bias = gg.bits(m.bias)
-        assert (vo.dequant(L) == gg.bits(W)).all(), name
-        out = vo.forward(L, gg.bits(x))
-        assert rel_err(out, gg.bits(y), dtype) <= Y_TOL[dtype], name
+    """Three seeded random layers built as the reference's own VQuantLinear (outliers, three codebooks, perm, bias,
+    bf16, vector lengths 2 / 8 / 10): the numpy oracle rebuilds the reference's whole dense W bit for bit and its
+    forward output (tests/golden/recorded/oracle_r*.npz, written by tests/golden/gen_golden_recorded.py)."""
+    for name in ("r1", "r2", "r3"):
+        L, x, y, cfg, _ = load_golden("oracle_" + name, RECORDED_DIR)
+        W = np.load(os.path.join(RECORDED_DIR, f"oracle_{name}.npz"))["W"]
+        assert (vo.dequant(L) == W).all(), name
+        out = vo.forward(L, x)
+        assert rel_err(out, y, cfg["dtype"]) <= Y_TOL[cfg["dtype"]], name
 
 
 # ---------------------------------------------------------------- BASELINE sizes
@@ -167,52 +144,32 @@ def test_v2_oracle_vs_reference_ground_truth_fixture(name):
     assert bit_identical_frac(out, d["y"]) >= 0.98
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted (GPU box)")
 def test_v2_oracle_vs_live_reference_ground_truth():
-    import torch
-    import gen_golden as gg
-    import gen_golden_v2 as g2
-    rt = g2.load_reference_test_module()
-    for dtype, k, kr, I, O, T in (("bf16", 512, 256, 128, 64, 1), ("f16", 1024, 512, 256, 32, 3)):
-        cfg = dict(in_features=I, out_features=O, num_centroids=k, num_res_centroids=kr, length=T,
-                   vector_length=8, device=torch.device("cpu"), dtype=gg.TORCH_DT[dtype])
-        d = rt.create_test_data(cfg)
-        y = rt.ground_truth(x=d["x"], bias=None, indices=d["indices"], centroids=d["centroids"],
-                            res_indices=d["residual_indices"], res_centroids=d["residual_centroids"],
-                            scale_weights=d["scale_weights"], scale_bias=d["scale_bias"],
-                            vector_len=8, out_features=O)
+    """`gemv_v2_ground_truth` bit for bit against the reference test file's `ground_truth` on two small inputs of
+    its `create_test_data` (bf16 and fp16, 1 and 3 tokens; tests/golden/recorded/v2_*.npz)."""
+    for dtype in ("bf16", "f16"):
+        z = np.load(os.path.join(RECORDED_DIR, f"v2_{dtype}.npz"))
+        c = json.loads(bytes(z["config"]).decode())
         out = vo.gemv_v2_ground_truth(
-            gg.bits(d["x"]), None, d["indices"].numpy().astype(np.int64), gg.bits(d["centroids"]),
-            d["residual_indices"].numpy().astype(np.int64), gg.bits(d["residual_centroids"]),
-            gg.bits(d["scale_weights"]), gg.bits(d["scale_bias"]), 8, O, dtype)
-        assert (out.reshape(-1) == gg.bits(y).reshape(-1)).all(), (dtype, k, kr)
+            z["x"], None, z["indices"], z["centroids"], z["res_indices"], z["res_centroids"],
+            z["scale_weights"], z["scale_bias"], 8, c["out_features"], dtype)
+        assert (out.reshape(-1) == z["y"].reshape(-1)).all(), (dtype, c["num_centroids"], c["num_res_centroids"])
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted (GPU box)")
 def test_reference_test_file_binds_to_this_package():
-    """The reference's kernel test (tests/test_quant_gemv.py), loaded UNMODIFIED with `vptq`
-    resolving to this repo's alias package: it imports, and the keyword set it passes to
-    `vptq.ops.quant_gemv_v2(**test_data)` (:236) binds to our signature.  (Running it needs a
-    GPU and the reference tree on the same box - there is no such box; the GPU test
-    `test_quant_gemv_v2_reference_fixture` replays its data and its comparison instead.)"""
-    import importlib.util
+    """The reference's kernel test (tests/test_quant_gemv.py) passes the dict of its `create_test_data` to
+    `vptq.ops.quant_gemv_v2(**test_data)` (:236): with `vptq` resolving to this repo's alias package, that keyword
+    set (recorded in tests/golden/recorded/reference_test_file.json) binds to our signature.  (The GPU test
+    `test_quant_gemv_v2_reference_fixture` replays its data and its comparison.)"""
     import inspect
-    import os
     import sys
-    import torch
-    from _refshim import REFERENCE_PATH
+    rec = json.load(open(os.path.join(RECORDED_DIR, "reference_test_file.json")))
+    assert rec["test_configs"] and rec["has_test_quant_gemv"]
     saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k == "vptq" or k.startswith("vptq.")}
     try:
         import vptq  # the alias at the repo root
         assert "vptq_amd" in vptq.VQuantLinear.__module__
-        spec = importlib.util.spec_from_file_location(
-            "ref_test_quant_gemv_alias", os.path.join(REFERENCE_PATH, "tests", "test_quant_gemv.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        d = mod.create_test_data(dict(in_features=64, out_features=64, num_centroids=64,
-                                      num_res_centroids=16, device=torch.device("cpu")))
-        inspect.signature(vptq.ops.quant_gemv_v2).bind(**d)   # TypeError on a mismatch
-        assert mod.test_configs and callable(mod.test_quant_gemv)
+        inspect.signature(vptq.ops.quant_gemv_v2).bind(**{k: None for k in rec["create_test_data_keys"]})   # TypeError on a mismatch
     finally:
         for k in [k for k in sys.modules if k == "vptq" or k.startswith("vptq.")]:
             del sys.modules[k]

@@ -1,15 +1,12 @@
 """Offline packing of an unpacked checkpoint: `vptq_amd.utils.pack.pack_state_dict` against the
 reference's `pack_model` (vptq/utils/pack.py:142-283) run on a stand-in model, and against the
 oracle's bit-stream packer."""
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import vptq_oracle as vo
 from vptq_amd.utils.pack import pack_layer_tensors, pack_state_dict, unpack_index_tensor
-from _refshim import reference_available
 
 LAYERS = {
     # name: (C, N, G, k, k_res, as_float, perm, outliers)
@@ -82,58 +79,24 @@ def test_pack_state_dict_whole_checkpoint():
         pack_state_dict({}, conf)
 
 
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not mounted (GPU box)")
 def test_pack_state_dict_equals_reference_pack_model():
-    from _refshim import load_reference
-    saved = {k: v for k, v in sys.modules.items() if k == "vptq" or k.startswith("vptq.")}
-    try:
-        for k in saved:
-            sys.modules.pop(k)
-        load_reference()
-        from vptq.utils.pack import convert_idx_dtype   # pack_model = this + a HF config fix-up
-
-        class VQuantLinear(torch.nn.Module):       # the reference finds layers by type name
-            pass
-
-        class Model(torch.nn.Module):
-            class config:                          # noqa: N801 - stands in for a HF config
-                pass
-
-        state, conf = _state_and_config()
-        model = Model()
-        mods = {}
-        for name, (C, N, G, k, kr, as_f, perm, outl) in LAYERS.items():
-            m = VQuantLinear()
-            for key in ("indices", "res_indices", "outlier_indices", "perm"):
-                t = state.get(f"{name}.{key}")
-                setattr(m, key, None if t is None else torch.nn.Parameter(t.clone(), requires_grad=False))
-            if m.perm is None:                      # the reference converts perm unconditionally
-                m.perm = torch.nn.Parameter(torch.arange(C * G), requires_grad=False)
-            m.num_centroids, m.num_res_centroids = k, (kr if kr else -1)
-            m.init_args = dict(conf[name])
-            mods[name] = m
-        # nest the modules under their dotted names
-        for name, m in mods.items():
-            parent = model
-            parts = name.split(".")
-            for p in parts[:-1]:
-                if not hasattr(parent, p):
-                    parent.add_module(p, torch.nn.Module())
-                parent = getattr(parent, p)
-            parent.add_module(parts[-1], m)
-        packed = convert_idx_dtype(model, torch.uint16, torch.uint16, torch.int16)
-        ref_conf = Model.config.quantization_config["config_for_layers"]
-    finally:
-        for k in [k for k in sys.modules if k == "vptq" or k.startswith("vptq.")]:
-            sys.modules.pop(k)
-        sys.modules.update(saved)
+    """The same unpacked checkpoint through the reference's `convert_idx_dtype` (pack_model without its HF config
+    fix-up) on a stand-in model: packed tensors and layer configs as recorded in tests/golden/recorded/pack_model.npz
+    (tests/golden/gen_golden_recorded.py)."""
+    import json
+    import os
+    from _cases import RECORDED_DIR
+    z = np.load(os.path.join(RECORDED_DIR, "pack_model.npz"))
+    rec = json.loads(bytes(z["config"]).decode())
+    ref_conf = rec["config_for_layers"]
+    state, conf = _state_and_config()
     new_state, new_conf = pack_state_dict(state, conf)
-    for name, m in mods.items():
-        assert torch.equal(m.indices.data, new_state[f"{name}.indices"]), name
-        assert m.res_indices is None
+    for name in LAYERS:
+        assert torch.equal(torch.from_numpy(z[f"{name}.indices"]), new_state[f"{name}.indices"]), name
+        assert rec["res_indices_is_none"][name]
         if state.get(f"{name}.perm") is not None:
-            assert torch.equal(m.perm.data, new_state[f"{name}.perm"])
+            assert torch.equal(torch.from_numpy(z[f"{name}.perm"]), new_state[f"{name}.perm"])
         if state.get(f"{name}.outlier_indices") is not None:
-            assert torch.equal(m.outlier_indices.data, new_state[f"{name}.outlier_indices"])
+            assert torch.equal(torch.from_numpy(z[f"{name}.outlier_indices"]), new_state[f"{name}.outlier_indices"])
         assert ref_conf[name]["is_indice_packed"] is True and new_conf[name] == ref_conf[name]
-    assert packed is model
+    assert rec["returns_the_model"]

@@ -1,6 +1,6 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; cd $R
 # 1. the default bench command (what the driver runs), then the same with every extra
-timeout 600 python bench.py > $O/bench_line_final.json 2> $O/bench_stderr.txt; cp $O/bench_full.json $O/bench_full_final.json 2>/dev/null
+timeout 600 python bench.py --full > $O/bench_line_final.json 2> $O/bench_stderr.txt; cp $O/bench_full.json $O/bench_full_final.json 2>/dev/null
 head -c 600 $O/bench_line_final.json; echo
 timeout 1500 python bench.py --extras > $O/bench_line_final_extras.json 2>/dev/null; cp $O/bench_full.json $O/bench_full_final_extras.json 2>/dev/null
 # 2. rocprofv3: kernel stats + PMC of the same command, default and selective

@@ -2,11 +2,11 @@
 # Produce the round's bench lines + rocprofv3 evidence under gpurun_out/round/ (copy into profiles/rNN/).
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/round; mkdir -p $OUT
 cd $R
-timeout 900 python bench.py 2>&1 | tail -1 > $OUT/bench_h8192_single.json
-timeout 600 python bench.py --mode grouped --no-cpu-baseline --no-extras 2>&1 | tail -1 > $OUT/bench_h8192_grouped.json
-timeout 600 python bench.py --hidden 4096 --no-extras 2>&1 | tail -1 > $OUT/bench_h4096_single.json
-timeout 600 python bench.py --exact --no-cpu-baseline --no-extras 2>&1 | tail -1 > $OUT/bench_h8192_single_exact.json
-timeout 600 python bench.py --mode tp_row --no-extras 2>&1 | tail -1 > $OUT/bench_tp_row_n1.json
+timeout 900 python bench.py --full 2>&1 | tail -1 > $OUT/bench_h8192_single.json
+timeout 600 python bench.py --full --mode grouped --no-cpu-baseline --no-extras 2>&1 | tail -1 > $OUT/bench_h8192_grouped.json
+timeout 600 python bench.py --full --hidden 4096 --no-extras 2>&1 | tail -1 > $OUT/bench_h4096_single.json
+timeout 600 python bench.py --full --exact --no-cpu-baseline --no-extras 2>&1 | tail -1 > $OUT/bench_h8192_single_exact.json
+timeout 600 python bench.py --full --mode tp_row --no-extras 2>&1 | tail -1 > $OUT/bench_tp_row_n1.json
 B="python $R/bench.py --no-cpu-baseline --no-extras --regions 1"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- $B --steps 20 --warmup 5 > /dev/null 2>&1
