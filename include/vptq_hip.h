@@ -87,7 +87,12 @@ enum {
   /* y is float32 [tokens, O]: the fp32 sums (output bias included when desc->bias is set) are
    * stored un-rounded.  For callers that combine several launches before the one rounding of
    * the reference's F.linear - the partial outputs of a row-parallel (input-column) shard,
-   * summed by an all-reduce.  Every kernel honours it (ABI >= 4). */
+   * summed by an all-reduce.  Every kernel honours it (ABI >= 4).
+   * Range of the sliced routes (vptq_quant_gemv_sliced*, whose arrivals - slices x tables x window / column parts - meet in a
+   * fixed-point accumulator word of 2^-30 units for fp16, 2^-28 for bf16): each arrival's partial sum must stay below
+   * 2^19 / arrivals (fp16) or 2^21 / arrivals (bf16) - 8 slices: 65536 / 262144; at worst (127 arrivals) ~4.1e3 / ~1.65e4 - so
+   * that the total fits the word; an output with a partial sum beyond that is NaN (even where the total itself would fit), never a
+   * wrong finite value.  Every other kernel sums in fp32 (range of fp32). */
   VPTQ_GEMV_OUT_F32 = 1 << 5,
   /* vptq_quant_gemv_chain only: layer i + 1 reads what layer i wrote (x[i + 1] aliases y[i]);
    * without it the layers of a chain must be independent of each other (ABI >= 6) */
@@ -386,6 +391,8 @@ VPTQ_API int vptq_quant_gemv_sliced_tokens_supported_for(const VptqLayerDesc* de
  * per (slice, row block), each staging its column windows alone and walking their part of every list (`wstart` needed) */
 VPTQ_API int vptq_quant_gemv_sliced_tokens_one_pass(const VptqLayerDesc* desc, int tokens, int flags);
 VPTQ_API size_t vptq_quant_gemv_sliced_tokens_workspace_bytes(const VptqLayerDesc* desc, int tokens);
+/* VPTQ_GEMV_SELECTIVE here (and on vptq_quant_gemv_sliced_grouped / _tokens_grouped, which have no selective form either) is taken
+ * as VPTQ_GEMV_EXACT: the layout must then be one of the EXACT slice count, otherwise the call returns VPTQ_E_UNSUPPORTED. */
 VPTQ_API int vptq_quant_gemv_sliced_tokens(const VptqLayerDesc* desc, const VptqSlicedLayout* layout, const void* x, void* y,
                                   int tokens, int flags, void* workspace, size_t workspace_bytes, void* stream);
 

@@ -595,11 +595,13 @@ int vptq_quant_gemv_sliced_tokens_supported(const VptqLayerDesc* d, const VptqSl
   return vptq_quant_gemv_sliced_tokens_supported_for(d, layout, tokens, 0);
 }
 int vptq_quant_gemv_sliced_tokens_supported_for(const VptqLayerDesc* d, const VptqSlicedLayout* layout, int tokens, int flags) {
+  flags = selective_as_exact(flags);
   if (flags & ~(VPTQ_GEMV_EXACT | VPTQ_GEMV_OUT_F32)) return 0;
   return validate_layer(d) == VPTQ_OK && layout && vptq::gemv_sliced_tok_eligible(*d, layout, tokens, (flags & VPTQ_GEMV_EXACT) != 0) ? 1 : 0;
 }
 
 int vptq_quant_gemv_sliced_tokens_one_pass(const VptqLayerDesc* d, int tokens, int flags) {
+  flags = selective_as_exact(flags);
   if (validate_layer(d) != VPTQ_OK || (flags & ~(VPTQ_GEMV_EXACT | VPTQ_GEMV_OUT_F32))) return 0;
   return vptq::gemv_sliced_tok_one_pass_parts(*d, tokens, (flags & VPTQ_GEMV_EXACT) != 0);
 }
@@ -611,6 +613,7 @@ size_t vptq_quant_gemv_sliced_tokens_workspace_bytes(const VptqLayerDesc* d, int
 
 int vptq_quant_gemv_sliced_tokens(const VptqLayerDesc* d, const VptqSlicedLayout* layout, const void* x, void* y, int tokens,
                                   int flags, void* workspace, size_t workspace_bytes, void* stream) {
+  flags = selective_as_exact(flags);   // (no selective form over several tokens: the reference's roundings)
   if (int rc = validate_layer(d)) return rc;
   if (!layout || !x || !y) return fail(VPTQ_E_NULL, "layout, x and y must be set");
   if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
@@ -628,6 +631,7 @@ int vptq_quant_gemv_sliced_tokens(const VptqLayerDesc* d, const VptqSlicedLayout
 
 int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, const void* x,
                                    void* const* y, int flags, void* const* workspaces, const size_t* workspace_bytes, void* stream) {
+  flags = selective_as_exact(flags);   // (the grouped launch has no selective form: the reference's roundings)
   if (!descs || !layouts || !x || !y || !workspaces || !workspace_bytes) return fail(VPTQ_E_NULL, "descs / layouts / x / y / workspaces is NULL");
   if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
   for (int i = 0; i < n; ++i) {
@@ -672,6 +676,7 @@ int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const VptqSlicedL
 int vptq_quant_gemv_sliced_tokens_grouped(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, const void* x,
                                           void* const* y, int tokens, int flags, void* const* workspaces, const size_t* workspace_bytes,
                                           void* stream) {
+  flags = selective_as_exact(flags);
   if (!descs || !layouts || !x || !y || !workspaces || !workspace_bytes) return fail(VPTQ_E_NULL, "descs / layouts / x / y / workspaces is NULL");
   if (n < 1 || n > 3) return fail(VPTQ_E_UNSUPPORTED, "a sliced group takes 1 .. 3 layers");
   for (int i = 0; i < n; ++i) {

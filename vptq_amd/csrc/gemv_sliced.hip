@@ -85,29 +85,38 @@ constexpr int kSLMaxGroup = 3;
 #define VPTQ_SLICED_PIPE 1
 #endif
 // accumulator word of one output: bits [0, 7) arrivals, [7, 14) arrivals whose partial sum could not be represented (NaN, infinite,
-// beyond the field), [14, 64) the sum in units of 2^-F as a 50-bit two's-complement number.  F = 30 for fp16 layers: partial sums up
-// to 2^17 (twice the type's range), resolution 9.3e-10 - a 16-bit output of magnitude 1e-4 still gets its sum to 1e-5 relative per
-// arrival; F = 28 for bf16 layers: partial sums up to 2^19 = 5.2e5 (no activation of a language model comes near; the type itself
-// goes to 3e38), resolution 3.7e-9 against an ulp of 4.8e-7 at 1e-4.  Truncation is towards zero (magnitude first, then the sign):
-// no bias.  Integer adds commute and wrap: the result is the same whoever arrives last, and a transient overflow of the field does
-// not matter as long as the final sum fits it (2 bits above the partial sums' limit).  A partial sum that cannot be represented
-// makes the OUTPUT NaN - loud - instead of saturating to a finite value.
+// beyond the field), [14, 64) the sum in units of 2^-F as a 50-bit two's-complement number: |sum| < 2^(49 - F).  F = 30 for fp16
+// layers: sums below 2^19, resolution 9.3e-10 - a 16-bit output of magnitude 1e-4 still gets its sum to 1e-5 relative per arrival;
+// F = 28 for bf16 layers: sums below 2^21 (no activation of a language model comes near; the type itself goes to 3e38),
+// resolution 3.7e-9 against an ulp of 4.8e-7 at 1e-4.  Truncation is towards zero (magnitude first, then the sign): no bias.
+// Integer adds commute and wrap: the result is the same whoever arrives last, and a transient overflow of the field does not
+// matter as long as the final sum fits it.  That is guaranteed per arrival: a partial sum of more than (2^49 - 1) / arrivals units
+// counts as unrepresentable - fp16 2^19 / arrivals: 8 slices 65536, 16 slices 32768, the most arrivals (127) ~4.1e3; bf16 4x that
+// (127 arrivals: ~1.65e4) - so the arrivals of an output can never add up to more than the field holds (a total beyond it would
+// wrap to a wrong finite value).  The price: an output whose total fits but one of whose partial sums is above its share is NaN
+// too.  A partial sum that cannot be represented makes the OUTPUT NaN - loud - instead of saturating to a finite value.
 // [Round 5: units of 2^-24 for every type, floor (a bias of up to 6e-8 per arrival, always downwards: 16 - 96 arrivals moved
 // outputs of magnitude 1e-3 by several fp16 ulps), clamp to +-3.3e7 - a finite bf16 value.  ADVICE r5.]
 constexpr int kSLFixShift = 14;
 template <typename DT> constexpr int sl_frac() { return std::is_same<DT, F16>::value ? 30 : 28; }
+// qmax = (2^49 - 1) / arrivals (sl_qmax): the most units one arrival may bring
+static __device__ __forceinline__ unsigned long long sl_qmax(int arrivals) {
+  return ((1ull << 49) - 1ull) / (unsigned long long)(arrivals > 0 ? arrivals : 1);
+}
 template <int F>
-static __device__ __forceinline__ unsigned long long sl_to_fixed(float v) {
+static __device__ __forceinline__ unsigned long long sl_to_fixed(float v, unsigned long long qmax) {
   // |v| 2^F as a 64-bit integer out of two 32-bit conversions (the compiler's float -> int64 is ~25 instructions, and a wave pays
-  // it at the end of every row): |v| = a + f with a = floor(|v|) < 2^25 and f = |v| - a in [0, 1), exact in fp32
-  constexpr float lim = (float)(1u << (49 - F - 2));   // fp16: 2^17; bf16: 2^19
+  // it at the end of every row): |v| = a + f with a = floor(|v|) < 2^21 and f = |v| - a in [0, 1), exact in fp32
+  constexpr float lim = (float)(1u << (49 - F));   // the field: fp16 2^19, bf16 2^21
   const float m = __builtin_fabsf(v);
-  const bool bad = !(m < lim);                       // NaN, infinite, beyond the field
+  bool bad = !(m < lim);                             // NaN, infinite, beyond the field
   const float c = bad ? 0.f : m;
   const float a = __builtin_floorf(c);
   const uint32_t ai = (uint32_t)a;
   const uint32_t fi = (uint32_t)((c - a) * (float)(1u << F));   // < 2^F: f <= 1 - 2^-24
   unsigned long long q = ((unsigned long long)ai << F) + (unsigned long long)fi;
+  bad = bad || q > qmax;                             // beyond this arrival's share of the field
+  if (bad) q = 0ull;
   if (v < 0.f) q = 0ull - q;
   return (q << kSLFixShift) + (bad ? 129ull : 1ull);
 }
@@ -558,6 +567,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
   // puts the word back to zero.  One returning atomic is the whole hand-over: nobody waits for anybody, nothing is read back.
   int pend_o = -1;
   unsigned long long pend_old[TOK][V / 4], pend_mine[TOK][V / 4];
+  const unsigned long long qmax = sl_qmax(GP.arrivals);
   auto finish_rows = [&]() __attribute__((always_inline)) {
     if (pend_o >= 0) {
 #pragma unroll
@@ -614,7 +624,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
         unsigned long long* const ap = (unsigned long long*)as_global(P.partial) + (TOK > 1 ? (size_t)t * P.acc_stride : 0) + pend_o;
 #pragma unroll
         for (int i = 0; i < V / 4; ++i) {
-          pend_mine[t][i] = sl_to_fixed<sl_frac<DT>()>(v[t][i] + bdot);
+          pend_mine[t][i] = sl_to_fixed<sl_frac<DT>()>(v[t][i] + bdot, qmax);
           pend_old[t][i] = __hip_atomic_fetch_add(ap + i, pend_mine[t][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       }
