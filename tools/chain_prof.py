@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-wave cycle accounting of the chain kernel (library built with -DVPTQ_K256C_PROF=1, run with
-VPTQ_K256C_PROF=1): one launch of `--layers` layers, averages over all waves.
-  VPTQ_HIP_LIB=tools/_build/libvptq_hip_prof.so VPTQ_K256C_PROF=1 python tools/chain_prof.py --hidden 8192"""
+VPTQ_K256C_PROF=1): one launch of `--layers` layers, averages over all waves.  --exact: the reference's roundings
+(VPTQ_GEMV_EXACT, the default arithmetic of bench.py) instead of the folded form.
+  VPTQ_HIP_LIB=tools/_build/libvptq_hip_prof.so VPTQ_TUNING=1 VPTQ_K256C_PROF=1 python tools/chain_prof.py --hidden 8192 [--exact]"""
 import argparse, ctypes as C, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,6 +16,7 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--waves", type=int, default=16, help="waves per workgroup of the build (VPTQ_K256C_WAVES)")
     ap.add_argument("--timeline", action="store_true", help="library built with -DVPTQ_K256C_PROF=2: who computes when")
+    ap.add_argument("--exact", action="store_true", help="the reference's roundings (VPTQ_GEMV_EXACT) instead of the folded form")
     a = ap.parse_args()
     import bench
     from vptq_amd import _backend as B
@@ -33,7 +35,7 @@ def main():
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        B.check(B.lib().vptq_quant_gemv_chain(descs, n, xp, yp, 1, 0, ws.data_ptr(), ws.numel() * 8,
+        B.check(B.lib().vptq_quant_gemv_chain(descs, n, xp, yp, 1, B.GEMV_EXACT if a.exact else 0, ws.data_ptr(), ws.numel() * 8,
                                               B.current_stream_ptr(dev)), "chain")
         e1.record()
         torch.cuda.synchronize()
@@ -41,6 +43,8 @@ def main():
     w = raw.double()
     us = e0.elapsed_time(e1) * 1e3
     tot = w[..., 5].mean().item()
+    name = B.lib().vptq_quant_gemv_chain_kernel_name(descs, n, 1, B.GEMV_EXACT if a.exact else 0).decode()
+    print(f"{name}, {'reference roundings' if a.exact else 'folded'}")
     print(f"launch {us:.1f} us = {us / n:.2f} us per layer; wave total {tot:.0f} clocks of s_memtime "
           f"({tot / us:.1f} per us)")
     names = ["wait for index words", "consume", "request next (+ fill request, issue-side row group / layer switch)",

@@ -600,10 +600,16 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
   uint32_t use = 0;            // how many layers this workgroup has entered before the current one
   uint32_t q_done = 0;         // row groups this workgroup has finished
   bool fill_pending = false;   // the next layer's image has not been requested yet
-  int land_steps = 0;          // > 0: a fill was requested D - land_steps step ends ago
+  // a fill is counted as landed kCLand step ends after it was requested: then only the kCLand youngest sweeps are younger
+  // than it, and everything older than them - sweeps requested at least kCLand steps ago - has landed as a rule (the
+  // step after next waits for them anyway).  (D step ends, the whole queue: every wave of the workgroup signals its part
+  // of the image one step later, and the fast waves wait for the slowest one's signal at the layer switch.)
+  constexpr int kCLand = 2;
+  static_assert(kCLand <= D, "the fill is older than the sweeps of one queue");
+  int land_steps = 0;          // > 0: a fill was requested kCLand - land_steps step ends ago
   // "everything but the youngest n sweeps' loads has landed".  vmcnt retires in order: at the end
-  // of the j-th step after a fill the fill is older than j + 1 sweeps; at j = D - 1 those are
-  // exactly the D sweeps in flight.
+  // of the j-th step after a fill the fill is older than j + 1 sweeps; at j = kCLand - 1 those are
+  // the kCLand youngest of the D sweeps in flight.
   auto wait_all_but = [&](int steps) __attribute__((always_inline)) {
     switch (steps) {
       case 1: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 1) : "memory"); break;
@@ -662,8 +668,12 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
         const int part = (64 * fin_pass) / kCOutW;             // row part whose waves hold these outputs
         const float* const pr = pr0 + part * (kCColWaves * kCOutW);
         // sum b x: one term per wave of the part (every part forms the same sum; lanes past the wave count add 0)
-        const float bpart = (ln & 15) < kCColWaves ? red_b[slot * kCWaves + part * kCColWaves + (ln & 15) % kCColWaves] : 0.f;
-        const float bdot = row16_allsum(bpart);
+        // (EXACT: the weights carry the bias, no sum b x was formed - the term is 0)
+        float bdot = 0.f;
+        if constexpr (!EXACT) {
+          const float bpart = (ln & 15) < kCColWaves ? red_b[slot * kCWaves + part * kCColWaves + (ln & 15) % kCColWaves] : 0.f;
+          bdot = row16_allsum(bpart);
+        }
         float sum;
         int ol;   // output (of this part of the row group) this lane stores
         bool mine;
@@ -760,8 +770,10 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
         *(f32x2*)&rs[q * 32 + (int)jrow * 8 + o8] = f32x2{v[0], v[1]};
       }
     }
-    const float sb = wave_sum(accb);
-    if (lane == 0) red_b[slot * kCWaves + wave] = sb;
+    if constexpr (!EXACT) {
+      const float sb = wave_sum(accb);
+      if (lane == 0) red_b[slot * kCWaves + wave] = sb;
+    }
 #if VPTQ_K256C_BALANCE
     // issue priority for the next row group by arrival order at the PREVIOUS one (its number has
     // come back by now): the early ones yield
@@ -825,7 +837,12 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
     const u32x4 xq = lds_load16(xq_addr);
     if constexpr (EXACT) { sq = lds_load16(xq_addr + 256u); bq = lds_load16(xq_addr + 512u); }
     // (bf16 reference roundings: 18 registers of rounding chains per index - one gather less in flight, or the loop spills)
-    constexpr int kUnits = 8 * kCSub, kAhead = (EXACT && std::is_same<DT, BF16>::value) ? 1 : VPTQ_K256C_AHEAD, kNB = kAhead + 1;
+    // fp16, reference roundings: the gathers of a whole index pair (column u + 1) are requested together, in front of the rounding
+    // block of column u, so that a pair's LDS round trip is covered by one pair of rounding chains (one unit ahead, the second
+    // gather of a pair was requested right in front of its first use)
+    constexpr bool kPairAhead = EXACT && std::is_same<DT, F16>::value;
+    constexpr int kUnits = 8 * kCSub, kAhead = (EXACT && std::is_same<DT, BF16>::value) ? 1 : kPairAhead ? 2 : VPTQ_K256C_AHEAD,
+                  kNB = kPairAhead ? 4 : kAhead + 1;
     u32x4 cv[kNB], rv[kNB];
     auto gather = [&](int t) {   // unit t = column t / kCSub of subgroup t % kCSub
       const int u = t / kCSub, q = t % kCSub;
@@ -852,7 +869,11 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
     for (int t = 0; t < kUnits; ++t) {
       // fenced: left alone, the scheduler sinks the gathers next to their use (LDS latency exposed)
       __builtin_amdgcn_sched_barrier(0);
-      if (t + kAhead < kUnits) gather(t + kAhead);
+      if constexpr (kPairAhead) {
+        if (t % 2 == 0 && t + 2 < kUnits) { gather(t + 2); gather(t + 3); }
+      } else {
+        if (t + kAhead < kUnits) gather(t + kAhead);
+      }
       __builtin_amdgcn_sched_barrier(0);
       const int u = t / kCSub, q = t % kCSub;
       if (q == 0)
@@ -890,10 +911,10 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
           uint32_t w[8];
 #pragma unroll
           for (int k = 0; k < 4; ++k) { w[k] = DT::add2(c[k], r[k]); w[4 + k] = DT::add2(c1[k], r1[k]); }
-          asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int k = 0; k < 8; ++k) w[k] = DT::mul2_bcast(w[k], sq[u >> 1], u & 1);
-          asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int k = 0; k < 8; ++k) w[k] = DT::add2_bcast(w[k], bq[u >> 1], u & 1);
           acc[q][0] = DT::mfma4(xo, u32x2{w[0], w[1]}, acc[q][0]);
@@ -985,8 +1006,8 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
   // ---- rare events, each behind one branch of the step
   // the next layer's image: requested as soon as its buffer is free (every wave has left the layer
   // before the current one), BEFORE the step's loads (a younger invisible load would make the next
-  // step's counted wait cover those too); D step ends later only the D sweeps in flight are younger
-  // than it, so it has landed once everything older has - which a wave that keeps pace has waited for
+  // step's counted wait cover those too); kCLand step ends later only the kCLand youngest sweeps in
+  // flight are younger than it, so it has landed once everything older has
   auto fill_events_before_issue = [&]() __attribute__((always_inline)) {
     const uint32_t nb = (use + 1u) & 1u;
     const uint32_t need = (uint32_t)kCWaves * ((use + 1u) >> 1);
@@ -994,12 +1015,12 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
       lds_acquire();
       fill_image(Lf, nb);
       fill_pending = false;
-      land_steps = D;
+      land_steps = kCLand;
     }
   };
   auto fill_events_after_issue = [&]() __attribute__((always_inline)) {
     if (--land_steps == 0) {
-      wait_all_but(D);
+      wait_all_but(kCLand);
       lds_inc(&ready_cnt[(use + 1u) & 1u]);
     }
   };
@@ -1031,8 +1052,8 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       lds_inc(&ready_cnt[nb]);
     } else if (land_steps > 0) {
-      // requested D - land_steps step ends ago: that many sweeps are younger than the fill
-      wait_all_but(D - land_steps);
+      // requested kCLand - land_steps step ends ago: that many sweeps are younger than the fill
+      wait_all_but(kCLand - land_steps);
       lds_inc(&ready_cnt[nb]);
       land_steps = 0;
     }
@@ -1344,28 +1365,34 @@ bool gemv_k256c_eligible(const VptqLayerDesc& d, int tokens) {
 
 // Row groups are dealt to the workgroups in blocks of consecutive ones, `rpw` per workgroup and
 // layer.  Independent layers: at least kCMinSteps sweeps per visit of a layer (the next layer's
-// image is requested at the start of the visit and lands D sweeps later; a layer that gives every
+// image is requested at the start of the visit and lands kCLand sweeps later; a layer that gives every
 // workgroup one short row group would make all of them wait for it), so a small layer occupies
 // only some of the workgroups and the next layers run beside it.  Dependent layers follow each
 // other anyway: every layer is spread over all workgroups.
+// Longer visits, up to kCMaxSteps sweeps, while the blocks still give every workgroup two: every visit ends in a layer
+// switch - the layer's last sums stored at once, its image buffer handed over, and the fast waves waiting at the next
+// layer for the slowest one's part of its image (tools/chain_prof.py --exact: ~22 % of the wave time at 8 sweeps per
+// visit).  Ring of 32 8192^2 layers, reference roundings: 8 -> 16 -> 32 sweeps per visit 6.2 -> 5.8 -> 5.7 us per layer.
 #ifndef VPTQ_K256C_MIN_STEPS
 #define VPTQ_K256C_MIN_STEPS 8
 #endif
 constexpr int kCMinSteps = VPTQ_K256C_MIN_STEPS;
+constexpr int kCMaxSteps = 4 * kCMinSteps;
 static int c_groups(const VptqLayerDesc& d) { return (d.num_indices + kCRows - 1) / kCRows; }
-static int c_rows_per_wg(const VptqLayerDesc& d, int cus, bool wide) {
+// visit = sweeps per visit a block is sized for (0: the layer's row groups spread over all workgroups)
+static int c_rows_per_wg(const VptqLayerDesc& d, int cus, int visit) {
   const int ng = c_groups(d), ns = (d.group_size + kCSweepCols - 1) / kCSweepCols;
   int rpw = (ng + cus - 1) / cus;
-  if (wide) {
-    const int want = (kCMinSteps + ns - 1) / ns;
+  if (visit > 0) {
+    const int want = (visit + ns - 1) / ns;
     rpw = want > rpw ? want : rpw;
   }
   return rpw < 1 ? 1 : rpw;
 }
-static long long c_blocks(const VptqLayerDesc* descs, int n, int cus, bool wide) {
+static long long c_blocks(const VptqLayerDesc* descs, int n, int cus, int visit) {
   long long total = 0;
   for (int i = 0; i < n; ++i) {
-    const int rpw = c_rows_per_wg(descs[i], cus, wide);
+    const int rpw = c_rows_per_wg(descs[i], cus, visit);
     total += (c_groups(descs[i]) + rpw - 1) / rpw;
   }
   return total;
@@ -1391,15 +1418,18 @@ static int c_workgroups(bool dependent) {
   return dependent && cus > kCFlagStride ? kCFlagStride : cus;
 }
 
-// wide blocks (>= kCMinSteps sweeps per visit) only while they still give every workgroup twice
-// its share of blocks, and never for a dependent chain
-static bool c_wide(const VptqLayerDesc* descs, int n, int cus, bool dependent) {
-  return !dependent && c_blocks(descs, n, cus, true) >= 2ll * cus;
+// wide blocks: the longest visit of kCMaxSteps, kCMaxSteps / 2, ... kCMinSteps sweeps whose blocks still give every
+// workgroup twice its share; 0 below that, and for a dependent chain
+static int c_visit(const VptqLayerDesc* descs, int n, int cus, bool dependent) {
+  if (dependent) return 0;
+  for (int v = kCMaxSteps; v >= kCMinSteps; v /= 2)
+    if (c_blocks(descs, n, cus, v) >= 2ll * cus) return v;
+  return 0;
 }
 // does one launch of these layers fill the device (>= 3/4 of the workgroups busy)?
 bool gemv_k256c_fills_device(const VptqLayerDesc* descs, int n, bool dependent) {
   const int cus = c_workgroups(dependent);
-  return 4 * c_blocks(descs, n, cus, c_wide(descs, n, cus, dependent)) >= 3ll * cus;
+  return 4 * c_blocks(descs, n, cus, c_visit(descs, n, cus, dependent)) >= 3ll * cus;
 }
 
 template <typename DT, bool DEP, int MODE = kCModeFolded>
@@ -1509,8 +1539,8 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
                              int flags, bool dependent, uint32_t* sync, hipStream_t st) {
   if (n < 1 || n > kMaxGroup) return hipErrorInvalidValue;
   const int cus = c_workgroups(dependent);
-  const bool wide = c_wide(descs, n, cus, dependent);
-  const long long total = c_blocks(descs, n, cus, wide);
+  const int visit = c_visit(descs, n, cus, dependent);
+  const long long total = c_blocks(descs, n, cus, visit);
   const int grid = (int)(total < cus ? total : cus);
   K256CParams P;
   P.n_layers = n;
@@ -1533,7 +1563,7 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
     Ly.G = d.group_size;
     Ly.O = d.out_features;
     Ly.row_words = d.row_words;
-    const int rpw = c_rows_per_wg(d, cus, wide);
+    const int rpw = c_rows_per_wg(d, cus, visit);
     const int ng = c_groups(d), ns = (d.group_size + kCSweepCols - 1) / kCSweepCols;
     if (rpw > 0xffff || ng > 0xffffff || ns > 0xff || grid > 0xffff) return hipErrorInvalidValue;
     Ly.wgs = (int)(first % grid);
