@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VPTQ_ABI_VERSION 10
+#define VPTQ_ABI_VERSION 11
 
 #if defined(__GNUC__)
 #define VPTQ_API __attribute__((visibility("default")))
@@ -272,6 +272,17 @@ VPTQ_API size_t vptq_quant_gemv_chain_workspace_bytes(int n, int flags);
 VPTQ_API size_t vptq_quant_gemv_chain_workspace_bytes_for(const VptqLayerDesc* descs, int n, int flags);
 VPTQ_API const char* vptq_quant_gemv_chain_kernel_name(const VptqLayerDesc* descs, int n, int tokens,
                                               int flags);
+/* Diagnostic (ABI >= 11): how ONE persistent chain launch of these n <= 32 layers (one token) deals its row groups of 8
+ * vector-rows to its workgroups - the numbers the launch itself uses.  workgroups = 0: what a call would use (the device's
+ * CUs; a dependent list at most 256); workgroups > 0: the plan for that many, no device needed.  Out: *visit = sweeps of
+ * 2048 columns a block is sized for (32, 16 or 8: the longest whose blocks number at least 2 x the workgroups; 0: every
+ * layer spread over all of them, and always for a dependent list), *grid = workgroups launched = min(blocks, workgroups),
+ * and per layer i first_wg[i] (the workgroup that owns block 0; block k goes to (first_wg[i] + k) mod *grid) and
+ * rows_per_wg[i] (row groups per block; the last block of a layer may be shorter).  Returns VPTQ_E_UNSUPPORTED for a list
+ * the persistent launch does not take with these flags (whether the chain call would pick it is
+ * vptq_quant_gemv_chain_kernel_name's answer). */
+VPTQ_API int vptq_quant_gemv_chain_plan(const VptqLayerDesc* descs, int n, int flags, int workgroups, int* visit,
+                                        int* grid, int* first_wg, int* rows_per_wg);
 
 /*
  * Many tokens (prefill): y[tokens, O] = x[tokens, I] @ W^T + bias with the dequantisation FUSED

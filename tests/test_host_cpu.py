@@ -22,7 +22,9 @@ def _declared_symbols():
     return sorted(set(re.findall(r"VPTQ_API[^;(]*?\b(vptq_\w+)\s*\(", hdr)))
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_at_abi_11():
+    """every symbol the header declares is exported and bound; ABI 11 (vptq_quant_gemv_chain_plan) in the header, the
+    library and the binding"""
     syms = _declared_symbols()
     assert len(syms) >= 8, syms
     assert os.path.exists(B.LIB_PATH), "build libvptq_hip.so first (__graft_entry__.build())"
@@ -31,7 +33,10 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, s), f"{s} declared in include/vptq_hip.h but not exported"
     assert sorted(B.EXPORTS) == syms, "python binding table out of sync with the header"
     lib.vptq_abi_version.restype = ctypes.c_int
-    assert lib.vptq_abi_version() == B.ABI_VERSION == 10
+    assert lib.vptq_abi_version() == B.ABI_VERSION == 11
+    hdr = open(os.path.join(ROOT, "include", "vptq_hip.h")).read()
+    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "11"
+    assert "vptq_quant_gemv_chain_plan" in syms
 
 
 def test_ctypes_struct_layout_matches_header():

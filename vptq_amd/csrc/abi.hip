@@ -307,7 +307,8 @@ int vptq_quant_gemv_grouped(const VptqLayerDesc* descs, int n, const void* const
 }
 
 // ---- chain: one persistent launch per <= 32 layers (gemv_k256c.hip), else layer by layer ----
-static bool chain_one_kernel(const VptqLayerDesc* descs, int n, const void* const* x, int tokens, int flags) {
+// can the persistent launch serve these layers with these flags (whether it is the faster route aside)?
+static bool chain_kernel_takes(const VptqLayerDesc* descs, int n, const void* const* x, int tokens, int flags) {
   if (tokens != 1 || (flags & (VPTQ_GEMV_FORCE_GENERIC | VPTQ_GEMV_FORCE_VALU))) return false;
   const bool exact = (flags & VPTQ_GEMV_EXACT) != 0, dep = (flags & VPTQ_GEMV_CHAIN_DEPENDENT) != 0;
   const bool sel = !exact && (flags & VPTQ_GEMV_SELECTIVE) != 0;
@@ -317,6 +318,10 @@ static bool chain_one_kernel(const VptqLayerDesc* descs, int n, const void* cons
     if (sel && !vptq::gemv_k256c_selective_ok(descs[i], dep)) return false;
     if (x && (((uintptr_t)x[i]) & 3) != 0) return false;
   }
+  return true;
+}
+static bool chain_one_kernel(const VptqLayerDesc* descs, int n, const void* const* x, int tokens, int flags) {
+  if (!chain_kernel_takes(descs, n, x, tokens, flags)) return false;
   // a chain that cannot keep the workgroups busy (one small layer, q / k / v of a small model) is better
   // served by the per-layer kernels; VPTQ_GEMV_FORCE_MFMA takes the chain kernel regardless (tests)
   if (!(flags & VPTQ_GEMV_FORCE_MFMA)) {
@@ -394,6 +399,24 @@ const char* vptq_quant_gemv_chain_kernel_name(const VptqLayerDesc* descs, int n,
     case kChainGrouped: return "grouped";
     default: return "per-layer";
   }
+}
+
+int vptq_quant_gemv_chain_plan(const VptqLayerDesc* descs, int n, int flags, int workgroups, int* visit, int* grid,
+                               int* first_wg, int* rows_per_wg) {
+  if (!descs || !visit || !grid || !first_wg || !rows_per_wg) return fail(VPTQ_E_NULL, "descs / visit / grid / first_wg / rows_per_wg is NULL");
+  if (n < 1 || n > 32) return fail(VPTQ_E_SHAPE, "n %d outside [1, 32] (one persistent launch)", n);
+  if (workgroups < 0) return fail(VPTQ_E_SHAPE, "workgroups %d < 0", workgroups);
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_layer(&descs[i]);
+    if (rc) return rc;
+  }
+  flags = drop_redundant_selective(flags);
+  if (!chain_kernel_takes(descs, n, nullptr, 1, flags))
+    return fail(VPTQ_E_UNSUPPORTED, "the persistent chain launch does not take these layers with flags 0x%x", flags);
+  const hipError_t e = vptq::gemv_k256c_plan(descs, n, (flags & VPTQ_GEMV_CHAIN_DEPENDENT) != 0, workgroups, visit, grid,
+                                             first_wg, rows_per_wg);
+  if (e != hipSuccess) return fail(VPTQ_E_UNSUPPORTED, "no persistent chain launch for these layers (%s)", hipGetErrorString(e));
+  return VPTQ_OK;
 }
 
 int vptq_quant_gemv_chain(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,

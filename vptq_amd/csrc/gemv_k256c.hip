@@ -1410,11 +1410,12 @@ static int c_device_cus() {
   return cus[dev];
 }
 
-static int c_workgroups(bool dependent) {
+// workgroups > 0: that many (a plan query); 0: what a launch uses
+static int c_workgroups(bool dependent, int workgroups = 0) {
   static std::atomic<int> forced_wgs{-1};  // VPTQ_K256C_WGS: tuning override of the workgroup count
   if (forced_wgs < 0) { const char* e = vptq::tune_env("VPTQ_K256C_WGS"); forced_wgs = e ? atoi(e) : 0; }
   const int fw = forced_wgs.load();
-  const int cus = fw > 0 ? fw : c_device_cus();
+  const int cus = workgroups > 0 ? workgroups : fw > 0 ? fw : c_device_cus();
   return dependent && cus > kCFlagStride ? kCFlagStride : cus;
 }
 
@@ -1533,20 +1534,48 @@ hipError_t launch_permute_x(const VptqLayerDesc* descs, int n, const void* const
   return hipGetLastError();
 }
 
+// How one launch deals its row groups: the grid, the visit length, and per layer the workgroup that owns block 0 and
+// the row groups per block (block k of layer i goes to workgroup (first[i] + k) mod grid).  The launch and the plan
+// query (gemv_k256c_plan) take their numbers from here.
+static hipError_t c_plan(const VptqLayerDesc* descs, int n, bool dependent, int cus, int* visit_out, int* grid_out,
+                         int* first_wg, int* rows_per_wg) {
+  if (n < 1 || n > kMaxGroup || cus < 1) return hipErrorInvalidValue;
+  const int visit = c_visit(descs, n, cus, dependent);
+  const long long total = c_blocks(descs, n, cus, visit);
+  const int grid = (int)(total < cus ? total : cus);
+  if (grid > 0xffff) return hipErrorInvalidValue;
+  long long first = 0;   // running total of blocks: the layers continue each other's round robin
+  for (int i = 0; i < n; ++i) {
+    const int rpw = c_rows_per_wg(descs[i], cus, visit);
+    const int ng = c_groups(descs[i]), ns = (descs[i].group_size + kCSweepCols - 1) / kCSweepCols;
+    if (rpw > 0xffff || ng > 0xffffff || ns > 0xff) return hipErrorInvalidValue;
+    first_wg[i] = (int)(first % grid);
+    rows_per_wg[i] = rpw;
+    // dependent chain: every layer starts at workgroup 0 (all of its row groups wait anyway)
+    first = dependent ? 0 : first + (ng + rpw - 1) / rpw;
+  }
+  *visit_out = visit;
+  *grid_out = grid;
+  return hipSuccess;
+}
+hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
+                           int* first_wg, int* rows_per_wg) {
+  return c_plan(descs, n, dependent, c_workgroups(dependent, workgroups), visit, grid, first_wg, rows_per_wg);
+}
+
 // n <= kMaxGroup layers, all gemv_k256c_eligible and of one dtype; sync = kCFlagStride flags per
 // layer (zeroed by the caller's memset node) when dependent
 hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
                              int flags, bool dependent, uint32_t* sync, hipStream_t st) {
-  if (n < 1 || n > kMaxGroup) return hipErrorInvalidValue;
-  const int cus = c_workgroups(dependent);
-  const int visit = c_visit(descs, n, cus, dependent);
-  const long long total = c_blocks(descs, n, cus, visit);
-  const int grid = (int)(total < cus ? total : cus);
+  int visit = 0, grid = 0, first_wg[kMaxGroup], rpws[kMaxGroup];
+  {
+    const hipError_t e = c_plan(descs, n, dependent, c_workgroups(dependent), &visit, &grid, first_wg, rpws);
+    if (e != hipSuccess) return e;
+  }
   K256CParams P;
   P.n_layers = n;
   P.tokens = 1 | ((flags & VPTQ_GEMV_OUT_F32) ? kOutF32Bit : 0);
   P.sync = sync;
-  long long first = 0;   // workgroup that owns block 0 of the layer
   for (int i = 0; i < kMaxGroup + kCHeadPad; ++i) P.head[i][0] = P.head[i][1] = 0u;
   for (int i = 0; i < n; ++i) {
     const VptqLayerDesc& d = descs[i];
@@ -1563,15 +1592,11 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
     Ly.G = d.group_size;
     Ly.O = d.out_features;
     Ly.row_words = d.row_words;
-    const int rpw = c_rows_per_wg(d, cus, visit);
     const int ng = c_groups(d), ns = (d.group_size + kCSweepCols - 1) / kCSweepCols;
-    if (rpw > 0xffff || ng > 0xffffff || ns > 0xff || grid > 0xffff) return hipErrorInvalidValue;
-    Ly.wgs = (int)(first % grid);
-    Ly.rpw = rpw;
-    P.head[i][0] = (uint32_t)Ly.wgs | ((uint32_t)rpw << 16);
+    Ly.wgs = first_wg[i];
+    Ly.rpw = rpws[i];
+    P.head[i][0] = (uint32_t)Ly.wgs | ((uint32_t)Ly.rpw << 16);
     P.head[i][1] = (uint32_t)ng | ((uint32_t)ns << 24);
-    // dependent chain: every layer starts at workgroup 0 (all of its row groups wait anyway)
-    first = dependent ? 0 : first + (ng + rpw - 1) / rpw;
   }
   const bool f16 = descs[0].dtype == VPTQ_DTYPE_F16;
   if ((flags & VPTQ_GEMV_SELECTIVE) && !(flags & VPTQ_GEMV_EXACT)) {

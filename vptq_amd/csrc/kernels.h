@@ -33,6 +33,9 @@ size_t gemv_k256c_perm_bytes(const VptqLayerDesc& d);
 hipError_t launch_permute_x(const VptqLayerDesc* descs, int n, const void* const* x, void* const* out, hipStream_t st);   // VPTQ_GEMV_EXACT inside the chain launch
 hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
                              int flags, bool dependent, uint32_t* sync, hipStream_t st);
+// how that launch deals its row groups (vptq_quant_gemv_chain_plan); workgroups = 0: what a launch uses
+hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
+                           int* first_wg, int* rows_per_wg);
 
 // gemv_gather.hip — v=8, k=65536 (+ residual 0 / 256 / 65536), C=1, no outliers:
 // centroid rows gathered from L2.
