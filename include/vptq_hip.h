@@ -430,6 +430,23 @@ VPTQ_API int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const Vp
                                    const void* x, void* const* y, int flags, void* const* workspaces,
                                    const size_t* workspace_bytes, void* stream);
 
+/* Rebuild a layer's packed int32 indices [1][N][row_words] from its EXACT sliced layout(s): `parts` consecutive structs,
+ * part p covering columns [p G / parts, (p + 1) G / parts) (1 part, or the 2 - 3 column parts of exact_column_parts).
+ * Output is bit-identical to the packed stream the layout was built from, with zero bits past G*T in each row's last word.
+ * desc is validated like the sliced entries': its `indices` must be non-NULL but is not read.
+ *
+ * Added within ABI 11; present when the symbol is.  An exact layout (vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT)
+ * slices, whole_table = 0) holds every bit of the packed stream: the element word gives the column (+ the part's first column)
+ * and the index inside the slice, the (slice, row) list it sits in the slice and the row - index = slice << (index_bits -
+ * log2(slices)) | local -, and `res` the residual index (uint8: v = 8 with 256 residual centroids; uint16: any other residual
+ * codebook).  Padding words (column = part width) are skipped.  So a layer served from such a layout needs no packed copy: the
+ * paths that read the stream (gather kernels, vptq_dequant) get it from here, into a scratch buffer.  Folded layouts (two
+ * tables, whole tables) are not taken.  Errors: NULL layouts / out (VPTQ_E_NULL), `parts` other than the layer's
+ * (VPTQ_E_SHAPE), a part's n_slices other than vptq_sliced_layout_supported_for(part, VPTQ_GEMV_EXACT) (VPTQ_E_SHAPE), an out
+ * pointer not 16-byte aligned (VPTQ_E_ALIGN); nothing is launched then.  One workgroup per row, the row assembled in LDS. */
+VPTQ_API int vptq_sliced_layout_repack(const VptqLayerDesc* desc, const VptqSlicedLayout* layouts, int parts, void* indices_out,
+                                       void* stream);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
 

@@ -10,6 +10,10 @@ which resolves to this repository's class (the `vptq` alias package).  Reports T
 captured in a hipGraph.
 
     python tools/llama_decode.py [--layers 32] [--prompt 128] [--new 256]
+
+--compact: `vptq_amd.compact_model(model)` after the build - large-codebook layers (--k 65536) keep their exact sliced layout as
+the only copy of their indices; the JSON line then also reports what that freed.  Every run reports the device memory held at
+the end (`torch.cuda.memory_allocated`) and the layers' index data (`VQuantLinear.resident_bytes`).
 """
 import argparse
 import json
@@ -112,6 +116,11 @@ def run(args):
         import vptq
         fused = vptq.layers.link_siblings(model)
         stage(f"{fused} sibling groups linked")
+    compact_rep = None
+    if args.compact:
+        import vptq_amd
+        compact_rep = vptq_amd.compact_model(model)
+        stage(f"{len(compact_rep['layers'])} layers compacted, {compact_rep['freed'] / 1e9:.2f} GB freed")
     torch.cuda.synchronize()
     stage("built")
     qbytes = sum(m.indices.numel() * 4 for m in qlayers)
@@ -227,6 +236,14 @@ def run(args):
         res["vqlinear_GBps"] = qbytes / vq_us / 1e3
         if isinstance(graph_tps, float):
             res["vqlinear_share_of_step"] = vq_us * 1e-6 * graph_tps / args.batch
+    torch.cuda.synchronize()
+    res["memory_allocated_GB"] = torch.cuda.memory_allocated(dev) / 1e9
+    rb = [m.resident_bytes() for m in qlayers]
+    res["index_resident_GB"] = {k: sum(r[k] for r in rb) / 1e9 for k in ("packed", "layout", "scratch", "total")}
+    if compact_rep is not None:
+        res["compacted_layers"] = len(compact_rep["layers"])
+        res["compact_freed_GB"] = compact_rep["freed"] / 1e9
+        res["compact_skipped"] = len(compact_rep["skipped"])
     print(json.dumps(res))
     if args.out:
         os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -245,5 +262,6 @@ if __name__ == "__main__":
     ap.add_argument("--fuse", action="store_true", help="link_siblings: q/k/v and gate/up share one grouped launch")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded together: every VQuantLinear call of a step sees that many tokens")
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"], help="dtype of the model and its VQuantLinear tensors")
+    ap.add_argument("--compact", action="store_true", help="vptq_amd.compact_model: exact sliced layouts as the only copy of the indices")
     ap.add_argument("--out", default="")
     run(ap.parse_args())

@@ -119,6 +119,8 @@ EXPORTS = {
     "vptq_quant_gemv_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
     "vptq_sliced_layout_supported_for": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemv_grouped_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
+    # (added within ABI 11) the packed index stream rebuilt from a layer's exact sliced layout(s): compact mode
+    "vptq_sliced_layout_repack": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, _vp, _vp]),
 }
 
 _lib = None
@@ -208,6 +210,31 @@ def gemv_workspace(dev_index: int, stream_ptr: int, nbytes: int):
         t = torch.empty(max(int(nbytes), 2 << 20), dtype=torch.uint8, device=torch.device("cuda", dev_index))
         _GEMV_WS[key] = t
     return t.data_ptr(), t.numel()
+
+
+_COMPACT_WS = {}        # (device index, stream handle) -> int32 tensor: compact mode's packed indices, rebuilt per launch
+_COMPACT_WS_RETIRED = []
+
+
+def compact_scratch(dev_index: int, stream_ptr: int, nbytes: int):
+    """16-byte aligned buffer of at least `nbytes` on this (device, stream) into which a compacted layer's packed indices are
+    rebuilt before a launch that reads them (`vptq_sliced_layout_repack`); one per stream, as `gemv_workspace`: calls on a
+    stream are ordered.  Sized to the largest compacted layer that used it.  Unlike the workspace it is also allocated inside
+    a stream capture (the graph's pool; the buffer is kept, so the graph's address stays valid)."""
+    key = (dev_index, stream_ptr)
+    t = _COMPACT_WS.get(key)
+    if t is None or t.numel() * 4 < nbytes:
+        if t is not None:
+            _COMPACT_WS_RETIRED.append(t)   # (a captured graph may still point at it)
+        t = torch.empty((int(nbytes) + 15) // 4, dtype=torch.int32, device=torch.device("cuda", dev_index))
+        _COMPACT_WS[key] = t
+    return t
+
+
+def compact_scratch_bytes(dev_index: int) -> int:
+    """bytes of compact-mode scratch held on a device (every stream, outgrown buffers included)"""
+    return sum(t.numel() * 4 for (d, _), t in _COMPACT_WS.items() if d == dev_index) + \
+        sum(t.numel() * 4 for t in _COMPACT_WS_RETIRED if t.device.index == dev_index)
 
 
 def current_stream_ptr(device) -> int:

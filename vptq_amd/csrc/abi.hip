@@ -604,6 +604,62 @@ int vptq_quant_gemv_sliced(const VptqLayerDesc* d, const VptqSlicedLayout* layou
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced launch");
 }
 
+// the column parts vptq_amd/utils/sliced.py:exact_column_parts serves the reference's roundings with (its VPTQ_SLICED_PARTS A/B knob
+// included): 1 where the layer fits in one piece, else 2 or 3 equal parts of a multiple of 8 columns; 0 = none
+static VptqLayerDesc repack_part_desc(const VptqLayerDesc& d, int parts, int p) {
+  VptqLayerDesc q = d;
+  const int w = d.group_size / parts;
+  q.in_features = q.group_size = w;
+  const size_t off = (size_t)2 * p * w;   // (16-bit column-order tensors)
+  if (q.weight_scale) q.weight_scale = (const char*)q.weight_scale + off;
+  if (q.weight_bias) q.weight_bias = (const char*)q.weight_bias + off;
+  if (q.perm) q.perm = (const uint16_t*)((const char*)q.perm + off);
+  if (q.scale_permuted) q.scale_permuted = (const char*)q.scale_permuted + off;
+  if (q.bias_permuted) q.bias_permuted = (const char*)q.bias_permuted + off;
+  return q;
+}
+static int repack_exact_parts(const VptqLayerDesc& d) {
+  const char* e = vptq::tune_env("VPTQ_SLICED_PARTS");
+  const int least = e && atoi(e) > 1 ? atoi(e) : 1;
+  const bool whole = vptq::gemv_sliced_eligible(d, true);
+  if (whole && least <= 1) return 1;
+  for (int parts = 2; parts <= 3; ++parts) {
+    if (parts < least || d.group_size % (8 * parts) != 0) continue;
+    const VptqLayerDesc q = repack_part_desc(d, parts, 0);
+    if (vptq::gemv_sliced_eligible(q, true) && vptq::gemv_sliced_slices(q, true) * parts <= 127) return parts;
+  }
+  return least > 1 && whole ? 1 : 0;
+}
+
+int vptq_sliced_layout_repack(const VptqLayerDesc* d, const VptqSlicedLayout* layouts, int parts, void* indices_out, void* stream) {
+  if (int rc = validate_layer(d)) return rc;
+  if (!layouts || !indices_out) return fail(VPTQ_E_NULL, "layouts / indices_out is NULL");
+  const int want = repack_exact_parts(*d);
+  if (want == 0)
+    return fail(VPTQ_E_UNSUPPORTED, "no exact sliced layout serves this layer (vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT), "
+                                    "or 2 / 3 column parts of it)");
+  if (parts != want) return fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", parts, want);
+  if ((((uintptr_t)indices_out) & 15) != 0) return fail(VPTQ_E_ALIGN, "indices_out must be 16-byte aligned");
+  if (vptq::sliced_repack_lds_bytes(*d) > 163840) return fail(VPTQ_E_UNSUPPORTED, "row_words %d: a row's image exceeds the LDS", d->row_words);
+  const int side = d->num_res_centroids == 0 ? 0 : (d->vector_len == 8 && d->num_res_centroids == 256 ? 1 : 2);
+  for (int p = 0; p < parts; ++p) {
+    const VptqSlicedLayout& L = layouts[p];
+    const int nsl = vptq::gemv_sliced_slices(repack_part_desc(*d, parts, p), true);
+    if (!L.elems || !L.blocks || !L.first) return fail(VPTQ_E_NULL, "layout %d: elems / blocks / first is NULL", p);
+    if (L.n_slices != nsl)
+      return fail(VPTQ_E_SHAPE, "layout %d: n_slices %d, the exact layout of this part has %d (vptq_sliced_layout_supported_for)", p,
+                  L.n_slices, nsl);
+    if (L.whole_table) return fail(VPTQ_E_UNSUPPORTED, "layout %d: whole-table layouts are folded-form layouts, not exact ones", p);
+    if ((side != 0) != (L.res != nullptr))
+      return fail(VPTQ_E_NULL, "layout %d: the `res` side stream must be set iff the layer has a residual codebook", p);
+    if ((((uintptr_t)L.elems) & 15) != 0 || (((uintptr_t)L.blocks | (uintptr_t)L.first) & 3) != 0 ||
+        (side && (((uintptr_t)L.res) & (side == 1 ? 3 : 7)) != 0))
+      return fail(VPTQ_E_ALIGN, "layout %d: elems 16-byte, blocks / first 4-byte, res 4- (uint8) / 8-byte (uint16) aligned", p);
+  }
+  const hipError_t e = vptq::launch_sliced_repack(*d, layouts, parts, indices_out, (hipStream_t)stream);
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "sliced_repack launch");
+}
+
 int vptq_quant_gemv_sliced_selective_supported(const VptqLayerDesc* d) {
   return validate_layer(d) == VPTQ_OK && vptq::gemv_hot_eligible(*d) ? 1 : 0;
 }

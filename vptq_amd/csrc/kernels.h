@@ -93,6 +93,9 @@ hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayo
 bool gemv_sliced_exact_tokens_ok(const VptqLayerDesc& d, int tokens);
 int gemv_sliced_exact_tokens_parts(const VptqLayerDesc& d, int tokens);   // 0: not served; 1: all columns staged; 2 / 4: window parts (needs wstart)
 size_t gemv_sliced_exact_tokens_workspace_bytes(const VptqLayerDesc& d, int tokens);
+// repack.hip - the packed index stream of a layer rebuilt from its exact sliced layout(s) (vptq_sliced_layout_repack)
+size_t sliced_repack_lds_bytes(const VptqLayerDesc& d);
+hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, void* out, hipStream_t st);
 // gemm_k256t.hip - canonical format, fp16 / bf16, up to 16 tokens in one pass over the indices (transposing
 // gather -> 16x16x32 MFMA with tokens as M; folded arithmetic; needs a workspace for the operand-ordered activations)
 bool gemm_k256t_eligible(const VptqLayerDesc& d, int tokens, int flags);

@@ -26,6 +26,7 @@ import math
 from typing import Sequence
 
 import os
+import weakref
 
 import torch
 import torch.nn as nn
@@ -69,6 +70,50 @@ _SLICED_ONE_LAUNCH = B.tune_env("VPTQ_SLICED_ONE_LAUNCH", "auto").strip().lower(
 
 _SLICED_SELECTIVE_MIN_ELEMENTS = 6 << 20   # selective roundings over the folded sliced layouts (two-table formats): from 6 M index elements on
 _SLICED_OOM_RETRY_CALLS = 256   # calls of a layer before a sliced-layout build that ran out of memory is tried again
+
+
+_COMPACTED = weakref.WeakSet()   # compacted layers (their share of the compact-mode scratch)
+
+
+def _compact_state_dict_hook(module, state_dict, prefix, local_metadata):
+    """state_dict() of a compacted layer: the packed indices, bit-identical, rebuilt from the layout"""
+    if "_compact" in module.__dict__ and prefix + "indices" in state_dict:
+        state_dict[prefix + "indices"] = module.packed_indices()
+    return state_dict
+
+
+def _compact_load_pre_hook(module, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+    """load_state_dict into a compacted layer: a real `indices` parameter again (torch does not load into a meta one), the
+    layout and the frozen descriptor dropped - the layer is uncompacted and routes as any other"""
+    cp = module.__dict__.get("_compact")
+    if cp is not None and prefix + "indices" in state_dict:
+        dev = cp["sl"].dev
+        module._parameters["indices"] = Parameter(torch.empty(cp["shape"], dtype=torch.int32, device=dev), requires_grad=False)
+        module._compact_drop()
+
+
+def compact_model(model: nn.Module, force: bool = False) -> dict:
+    """`VQuantLinear.compact(force)` over every layer of `model`, one at a time (the peak is one layer's build temporaries).
+    Returns {"layers": {name: {"before", "after", "freed"}}, "skipped": {name: reason}, "before", "after", "freed"} in bytes of
+    index data (`resident_bytes()["total"]`; scratch excluded)."""
+    rep = {"layers": {}, "skipped": {}, "before": 0, "after": 0, "freed": 0}
+    for name, m in model.named_modules():
+        if not isinstance(m, VQuantLinear):
+            continue
+        b0 = m.resident_bytes()
+        freed = m.compact(force)
+        b1 = m.resident_bytes()
+        before, after = b0["packed"] + b0["layout"], b1["packed"] + b1["layout"]
+        rep["before"] += before
+        rep["after"] += after
+        if m.is_compact() and freed:
+            rep["layers"][name] = {"before": before, "after": after, "freed": freed}
+            rep["freed"] += freed
+        else:
+            rep["skipped"][name] = m.__dict__.get("compact_skipped") or "already compacted"
+    if torch.cuda.is_available():
+        torch.cuda.empty_cache()
+    return rep
 
 
 class SiblingGroup:
@@ -149,6 +194,10 @@ class SiblingGroup:
                 any(m.in_features != layer.in_features for m in self.members):
             raise RuntimeError("sibling layers must share the device and the input width")
         key = tuple(c[6] for c in caches)  # descriptor generations: a rebuilt descriptor never matches
+        if (self._arrays is None or self._arrays[0] != key) and any("_compact" in m.__dict__ for m in self.members):
+            # a compacted member has no packed indices for the grouped launch to read: every member launches for itself (compacting
+            # or uncompacting a layer rebuilds its descriptor: a new key)
+            self._arrays = (key, None, None)
         if self._arrays is None or self._arrays[0] != key:
             import ctypes as C
             # one launch per ARITHMETIC: the members the load-time gate sends to the reference's roundings (VPTQ_GEMV_EXACT) go out as a
@@ -165,6 +214,8 @@ class SiblingGroup:
                                   (C.c_void_p * len(idx))(), fl))
             self._arrays = (key, parts, B.lib().vptq_quant_gemv_grouped)
         _, parts, fn = self._arrays
+        if parts is None:
+            return None
         ys = [torch.empty(xc.shape[:-1] + (m.out_features,), dtype=xc.dtype, device=dev)
               for m in self.members]
         dev_index = caches[0][8]
@@ -337,7 +388,7 @@ class VQuantLinear(nn.Module):
         return ops.quant_gemm(
             x,
             bias=self.bias,
-            indices=self.indices,
+            indices=self.packed_indices(),
             centroids=self.centroids.weight,
             outlier_indices=self.outlier_indices,
             outlier_centroids=self.outlier_centroids.weight if self.enable_outlier else None,
@@ -360,7 +411,7 @@ class VQuantLinear(nn.Module):
             padding=self.padding,
             outlier_padding=self.outlier_padding,
             vector_quant_dim=self.vector_quant_dim,
-            prefetch=None if self._prefetch_next is None else self._prefetch_next.indices,
+            prefetch=None if self._prefetch_next is None or "_compact" in self._prefetch_next.__dict__ else self._prefetch_next.indices,
         )
 
     def _descriptor(self):
@@ -387,6 +438,11 @@ class VQuantLinear(nn.Module):
             key += (B.tensor_version(perm), B.tensor_version(tensors[6]), B.tensor_version(tensors[7]))
         cache = self.__dict__.get("_desc_cache")
         if cache is None or cache[0] != key:
+            # compact mode (the meta `indices` of a compacted layer are part of the key with pointer 0): the descriptor's `indices` is the
+            # layout's stand-in, and there is no prefetch from or of a layer without packed indices
+            cp = self.__dict__.get("_compact")
+            if cp is not None or (nxt is not None and "_compact" in nxt.__dict__):
+                tensors = (tensors[0] if cp is None else cp["standin"],) + tensors[1:9] + (None,)
             dev = B.require_device(*[t for t in tensors if t is not None])
             desc, keep = B.make_layer_desc(
                 indices=tensors[0], centroids=tensors[1], res_centroids=tensors[2],
@@ -404,7 +460,9 @@ class VQuantLinear(nn.Module):
             cache = (key, desc, keep, dev, B.lib().vptq_quant_gemv,
                      B.lib().vptq_quant_gemv_max_tokens(desc), VQuantLinear._desc_generation,
                      tensors[1].dtype, dev.index if dev.index is not None else torch.cuda.current_device(),
-                     B.layer_arithmetic_flags(self._folded_form_is_safe(tensors, desc)),
+                     # (compact mode: the gate is frozen at "refused" - it would read index data -, i.e. the reference's roundings in every
+                     # arithmetic, the documented fallback of every route without a selective form)
+                     B.GEMV_EXACT if cp is not None else B.layer_arithmetic_flags(self._folded_form_is_safe(tensors, desc)),
                      B.lib().vptq_quant_gemv_workspace_bytes(desc, 16, 0))   # [10]: scratch bytes of the batched-decode kernel
             self.__dict__["_desc_cache"] = cache
         return cache
@@ -436,6 +494,8 @@ class VQuantLinear(nn.Module):
         state = dict(self.__dict__)
         for k in self._DERIVED_STATE:
             state.pop(k, None)
+        if state.pop("_compact", None) is not None:   # (a compacted layer is saved / copied with its packed indices, uncompacted)
+            state["_parameters"] = dict(state["_parameters"], indices=Parameter(self.packed_indices(), requires_grad=False))
         return state
 
     def __deepcopy__(self, memo):
@@ -443,8 +503,10 @@ class VQuantLinear(nn.Module):
         new = self.__class__.__new__(self.__class__)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k not in self._DERIVED_STATE:
+            if k not in self._DERIVED_STATE and k != "_compact":
                 new.__dict__[k] = copy.deepcopy(v, memo)
+        if "_compact" in self.__dict__:   # (the copy is uncompacted: it gets the packed indices, not a second layout)
+            new._parameters["indices"] = Parameter(self.packed_indices(), requires_grad=False)
         return new
 
     def enable_sliced_layout(self, enable: bool = True):
@@ -456,6 +518,14 @@ class VQuantLinear(nn.Module):
         self.__dict__.pop("_sliced", None)
 
     def _sliced_gemv(self):
+        cp = self.__dict__.get("_compact")
+        if cp is not None:
+            # compact mode: the exact layout is the only copy of the indices - served in every arithmetic, whatever
+            # VPTQ_SLICED_LAYOUT says, never rebuilt (a rebuilt descriptor is only re-attached)
+            cache = self._descriptor()
+            if cp["gen"] != cache[6]:
+                cp["sl"], cp["gen"] = cp["sl"].rebound(cache[1]), cache[6]
+            return cp["sl"]
         on = self.__dict__.get("_sliced_on")
         if on is None:
             on = _SLICED_LAYOUT_ENV
@@ -659,7 +729,8 @@ class VQuantLinear(nn.Module):
     def _gemv_cached(self, x: torch.Tensor, tokens: int) -> torch.Tensor:
         """Decode fast path: identical to `ops.quant_gemm` for 1..8 (canonical format: 16) tokens with a cached
         descriptor; layers linked by `link_siblings` share one grouped launch."""
-        if tokens <= _SLICED_MAX_TOKENS and self.__dict__.get("_sliced_cand", True) and (_SLICED_LAYOUT_ENV or "_sliced_on" in self.__dict__):
+        if tokens <= _SLICED_MAX_TOKENS and self.__dict__.get("_sliced_cand", True) and (_SLICED_LAYOUT_ENV or "_sliced_on" in self.__dict__ or
+                                                                                         "_compact" in self.__dict__):
             if "_sliced_cand" not in self.__dict__:
                 # (static module configuration: decided once, so that every other layer pays one dict look-up per call)
                 self.__dict__["_sliced_cand"] = bool(
@@ -721,13 +792,18 @@ class VQuantLinear(nn.Module):
         y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
         # the current stream of the layer's device as a raw handle (torch.cuda.current_stream builds a
         # Stream object per call: 4 us of the 15 this function took)
+        cp = self.__dict__.get("_compact")
         if torch.cuda.current_device() != dev_index:
             with torch.cuda.device(dev):
                 sp = B.current_stream_ptr(dev)
+                if cp is not None:
+                    desc = self._repacked_desc(desc, dev_index, sp)
                 ws, wsb = B.gemv_workspace(dev_index, sp, ws_bytes) if tokens > 1 else (None, 0)
                 rc = fn(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | safe_flags, ws, wsb, sp)
         else:
             sp = _raw_stream(dev_index)
+            if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
+                desc = self._repacked_desc(desc, dev_index, sp)
             # 2+ tokens of the canonical format: the one-pass batched-decode kernel wants scratch memory
             ws, wsb = B.gemv_workspace(dev_index, sp, ws_bytes) if tokens > 1 else (None, 0)
             rc = fn(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | safe_flags, ws, wsb, sp)
@@ -755,8 +831,9 @@ class VQuantLinear(nn.Module):
         dense = self.__dict__.get("_desc_dense")
         if dense is None or dense[0] != cache[6]:
             P, M = self._parameters, self._modules
+            cp = self.__dict__.get("_compact")
             desc, keep = B.make_layer_desc(
-                indices=P["indices"], centroids=M["centroids"]._parameters["weight"],
+                indices=P["indices"] if cp is None else cp["standin"], centroids=M["centroids"]._parameters["weight"],
                 res_centroids=M["res_centroids"]._parameters["weight"] if self.enable_residual else None,
                 outlier_indices=P.get("outlier_indices"),
                 outlier_centroids=M["outlier_centroids"]._parameters["weight"] if self.enable_outlier else None,
@@ -773,11 +850,14 @@ class VQuantLinear(nn.Module):
             dense = (cache[6], desc, keep, B.lib().vptq_dequant)
             self.__dict__["_desc_dense"] = dense
         W = torch.empty((self.out_features, self.in_features), dtype=wdtype, device=dev)
+        cp = self.__dict__.get("_compact")
         if torch.cuda.current_device() != dev_index:
             with torch.cuda.device(dev):
-                rc = dense[3](dense[1], W.data_ptr(), B.current_stream_ptr(dev))
+                sp = B.current_stream_ptr(dev)
+                rc = dense[3](dense[1] if cp is None else self._repacked_desc(dense[1], dev_index, sp), W.data_ptr(), sp)
         else:
-            rc = dense[3](dense[1], W.data_ptr(), _raw_stream(dev_index))
+            sp = _raw_stream(dev_index)
+            rc = dense[3](dense[1] if cp is None else self._repacked_desc(dense[1], dev_index, sp), W.data_ptr(), sp)
         if rc:
             B.check(rc, "vptq_dequant")
         return torch.nn.functional.linear(x, W, self._parameters.get("bias"))
@@ -786,7 +866,7 @@ class VQuantLinear(nn.Module):
         """Dense W[out_features, in_features] (what the reference calls
         `ops.dequant(...)` with this layer's fields)."""
         return ops.dequant(
-            indices=self.indices, centroids=self.centroids.weight,
+            indices=self.packed_indices(), centroids=self.centroids.weight,
             outlier_indices=self.outlier_indices,
             outlier_centroids=self.outlier_centroids.weight if self.enable_outlier else None,
             res_indices=None,
@@ -800,6 +880,145 @@ class VQuantLinear(nn.Module):
             outlier_padding=self.outlier_padding, num_codebooks=self.num_codebooks,
             group_size=self.group_size, outlier_size=self.outlier_size,
             vector_len=self.vector_len, outlier_vector_len=self.outlier_vector_len)
+
+    # ---- compact mode: the exact sliced layout as the ONLY copy of the indices ----------------------------------------------------
+    # The exact layout (vptq_amd/utils/sliced.py, SlicedGemv(exact=True)) holds every bit of the packed stream (include/vptq_hip.h,
+    # vptq_sliced_layout_repack), so a layer served from it at one token can drop its packed `indices`: about a third of the resident
+    # weights of the large-codebook formats.  1 - 4 tokens take the sliced kernels as before; every path that reads the packed stream
+    # (gather kernels, vptq_dequant, dequant(), state_dict(), shards, copies) gets it rebuilt by the repack kernel - into a per-stream
+    # scratch buffer for launches, into a fresh tensor otherwise.  `indices` is a meta-device parameter of the same shape meanwhile.
+
+    def compact(self, force: bool = False) -> int:
+        """Hold this layer's indices in its exact sliced layout only; returns the bytes freed (0: not compacted - the reason is
+        `layer.compact_skipped`).  Without `force`, only layers the product already serves from an exact layout at one token
+        (the reference arithmetic's rule in `_sliced_gemv`): their one-token speed is unchanged by construction.  Refused, the
+        layer untouched, for: formats without an exact layout, non-zero bits past G T in a row, a stream capture, a layout build
+        that runs out of device memory.  A compacted layer takes the reference's roundings in every arithmetic; `.to()` refuses
+        it (`uncompact()` first); `load_state_dict` uncompacts it."""
+        if "_compact" in self.__dict__:
+            return 0
+        why = self._compact_refusal(force)
+        if why is None:
+            why = self._compact_install()
+        self.__dict__["compact_skipped"] = why
+        return 0 if why else self.__dict__["_compact"]["packed_bytes"]
+
+    def _compact_refusal(self, force: bool):
+        """None, or why this layer cannot be compacted (nothing is changed here)"""
+        from vptq_amd.utils.sliced import exact_column_parts, tail_bits_clear
+        ind = self._parameters["indices"]
+        if not (self.num_centroids >= 16384 and self.vector_len in (8, 16) and self.num_codebooks == 1 and not self.enable_outlier and
+                self.enable_norm):
+            return "format has no exact sliced layout (v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no outliers, scale / bias)"
+        if not tail_bits_clear(ind.detach(), self.group_size, self.total_index_bits):
+            return "non-zero bits past group_size x index bits in a row of the packed indices: a layout cannot hold them"
+        if not ind.is_cuda:
+            return "indices are not on a ROCm device"
+        if torch.cuda.is_current_stream_capturing():
+            return "inside a stream capture"
+        cache = self._descriptor()
+        if not exact_column_parts(cache[1], self.group_size)[0]:
+            return "no exact sliced layout serves this layer (too wide, or the format's LDS budget)"
+        if not force:
+            n_el = ind.shape[1] * self.group_size
+            kr = self.num_res_centroids if self.enable_residual else 0
+            big = (kr >= 4096 and n_el >= _SLICED_EXACT_RG_MIN_ELEMENTS) if (kr > 0 and not (self.vector_len == 8 and kr == 256)) \
+                else n_el >= _SLICED_EXACT_MIN_ELEMENTS
+            if not big:
+                return "one token takes the gather kernel for this layer (smaller than the exact sliced route's threshold; force=True compacts it)"
+        return None
+
+    def _compact_install(self):
+        from vptq_amd.utils.sliced import SlicedGemv
+        ind = self._parameters["indices"]
+        cache = self._descriptor()
+        st = self.__dict__.get("_sliced")
+        sl = st[1] if st is not None and st[0] == (cache[6], B.tensor_version(ind)) else None
+        if sl is None or not sl.exact:
+            try:
+                sl = SlicedGemv(self, exact=True)
+            except torch.cuda.OutOfMemoryError as e:
+                torch.cuda.empty_cache()
+                return f"out of device memory building the exact layout ({str(e)[:120]})"
+        with torch.cuda.device(cache[3]):
+            same = torch.equal(sl.repack(), ind.detach())
+        if not same:
+            return "the repacked layout differs from the packed indices"
+        w = ind.shape[2]
+        packed_bytes = ind.numel() * ind.element_size()
+        # the descriptors' `indices`: the layout's element words (the sliced entries check the pointer, never read through it; every
+        # launch that reads the stream gets a copy pointing at a repack) - a [1, 1, row_words] view: the descriptor takes row_words
+        # from its last dimension
+        standin = sl.elems[:w].view(1, 1, w) if sl.elems.numel() >= w else torch.zeros(1, 1, w, dtype=torch.int32, device=sl.dev)
+        self.__dict__["_compact"] = {"sl": sl, "gen": -1, "standin": standin, "shape": tuple(ind.shape), "packed_bytes": packed_bytes}
+        self._parameters["indices"] = Parameter(torch.empty(ind.shape, dtype=ind.dtype, device="meta"), requires_grad=False)
+        for k in ("_desc_cache", "_desc_dense", "_sliced", "_sliced_oom"):
+            self.__dict__.pop(k, None)
+        del ind, st
+        if not self.__dict__.get("_compact_hooked"):
+            self._register_state_dict_hook(_compact_state_dict_hook)
+            self._register_load_state_dict_pre_hook(_compact_load_pre_hook, with_module=True)
+            self.__dict__["_compact_hooked"] = True
+        self._sliced_gemv()   # (the frozen descriptor: built over the layout's element words as the stand-in `indices` pointer)
+        _COMPACTED.add(self)
+        return None
+
+    def is_compact(self) -> bool:
+        return "_compact" in self.__dict__
+
+    def packed_indices(self) -> torch.Tensor:
+        """the packed int32 indices: the parameter itself, or (compacted) a fresh repack on the layer's device"""
+        cp = self.__dict__.get("_compact")
+        if cp is None:
+            return self._parameters["indices"]
+        return self._sliced_gemv().repack()
+
+    def _repacked_desc(self, desc, dev_index: int, sp: int):
+        """a copy of `desc` whose `indices` point at this stream's scratch, the packed stream rebuilt there (stream order)"""
+        cp = self.__dict__["_compact"]
+        sl = self._sliced_gemv()
+        buf = B.compact_scratch(dev_index, sp, cp["packed_bytes"])
+        B.check(B.lib().vptq_sliced_layout_repack(sl.desc, sl._lay_ref, sl.parts, buf.data_ptr(), sp), "vptq_sliced_layout_repack")
+        d = B.LayerDesc.from_buffer_copy(desc)
+        d.indices, d.prefetch, d.prefetch_bytes = buf.data_ptr(), None, 0
+        return d
+
+    def uncompact(self) -> None:
+        """restore the packed `indices` parameter (from a repack); the layer then routes as any other"""
+        cp = self.__dict__.get("_compact")
+        if cp is None:
+            return
+        self._parameters["indices"] = Parameter(self.packed_indices(), requires_grad=False)
+        self._compact_drop()
+
+    def _compact_drop(self):
+        for k in ("_compact", "_desc_cache", "_desc_dense", "_sliced", "_sliced_oom"):
+            self.__dict__.pop(k, None)
+        _COMPACTED.discard(self)
+
+    def resident_bytes(self) -> dict:
+        """device bytes of this layer's index data: packed indices, sliced layout tensors, its share of the compact-mode scratch
+        (the per-stream buffers of its device divided among the compacted layers there)"""
+        ind = self._parameters["indices"]
+        packed = 0 if ind.is_meta else ind.numel() * ind.element_size()
+        cp = self.__dict__.get("_compact")
+        st = self.__dict__.get("_sliced")
+        sl = cp["sl"] if cp is not None else (st[1] if st is not None else None)
+        layout = 0
+        if sl is not None:
+            layout = sum(t.numel() * t.element_size() for tup in sl._tensors for t in tup if t is not None)
+        scratch = 0
+        if cp is not None:
+            di = sl._dev_index
+            peers = sum(1 for m in list(_COMPACTED) if m.__dict__.get("_compact") is not None and m._sliced_gemv()._dev_index == di)
+            scratch = B.compact_scratch_bytes(di) // max(peers, 1)
+        return {"packed": packed, "layout": layout, "scratch": scratch, "total": packed + layout + scratch}
+
+    def _apply(self, fn, *args, **kwargs):
+        if "_compact" in self.__dict__:
+            raise RuntimeError("this VQuantLinear is compacted (its indices live in its sliced layout on its device): call "
+                               "layer.uncompact() before moving or converting it")
+        return super()._apply(fn, *args, **kwargs)
 
     def extra_repr(self) -> str:
         return (f"in_features={self.in_features}, out_features={self.out_features}, "

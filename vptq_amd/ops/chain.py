@@ -40,6 +40,9 @@ class GemvChain:
         caches = [m._descriptor() for m in self.layers]
         key = tuple(c[6] for c in caches)
         if self._state is None or self._state[0] != key:
+            # (compacting or uncompacting a layer rebuilds its descriptor: a new key)
+            if any("_compact" in m.__dict__ for m in self.layers):
+                raise ValueError("a chain reads every layer's packed indices: uncompact() compacted layers first")
             n = len(caches)
             dev = caches[0][3]
             if any(c[3] != dev for c in caches):

@@ -118,6 +118,8 @@ def absorb_perm_layer(layer) -> bool:
         return False
     if layer.group_num > 1 or getattr(layer, "enable_outlier", False):
         return False
+    if getattr(layer, "is_compact", lambda: False)():
+        layer.uncompact()   # (the rewritten stream needs a real parameter; the layer is not compacted again here)
     inv = torch.argsort(layer.perm.detach().view(torch.int16).to(torch.int64) & 0xFFFF)
     idx, ridx = unpack_index_tensor(layer.indices.detach(), layer.index_bits, layer.group_size,
                                     layer.res_index_bits, layer.group_size,

@@ -31,7 +31,7 @@ def _split(n: int, rank: int, world: int):
 
 def _clone_like(layer: VQuantLinear, in_features: int, out_features: int, group_size: int,
                 enable_perm: bool, bias: bool) -> VQuantLinear:
-    dev, dt = layer.indices.device, layer.centroids.weight.dtype
+    dev, dt = layer.centroids.weight.device, layer.centroids.weight.dtype
     with torch.device("meta"):
         new = VQuantLinear(
             in_features, out_features,
@@ -64,7 +64,7 @@ def shard_out_features(layer: VQuantLinear, rank: int, world: int) -> VQuantLine
         raise ValueError("outlier vectors straddle the shard boundary")
     new = _clone_like(layer, layer.in_features, o1 - o0, layer.group_size, layer.enable_perm,
                       layer.bias is not None)
-    new.indices.data = layer.indices.data[:, n0:n1, :].contiguous()
+    new.indices.data = layer.packed_indices().data[:, n0:n1, :].contiguous()
     if layer.enable_outlier:
         ov = layer.outlier_vector_len
         new.outlier_indices.data = layer.outlier_indices.data[:, o0 // ov:(o1 + ov - 1) // ov, :].contiguous()
@@ -95,7 +95,7 @@ def shard_in_features(layer: VQuantLinear, rank: int, world: int) -> VQuantLinea
     w0, w1 = g0 * T // 32, (g0 + Gs) * T // 32
     new = _clone_like(layer, Gs, layer.out_features, Gs, False,
                       layer.bias is not None and rank == 0)
-    new.indices.data = layer.indices.data[:, :, w0:w1].contiguous()
+    new.indices.data = layer.packed_indices().data[:, :, w0:w1].contiguous()
     if layer.enable_norm:
         new.weight_scale.data = layer.weight_scale.data[g0:g0 + Gs].contiguous()
         new.weight_bias.data = layer.weight_bias.data[g0:g0 + Gs].contiguous()

@@ -139,6 +139,48 @@ def layout_from_indices(idx: torch.Tensor, slices: int = 8, ridx: torch.Tensor =
     return elems32, blocks_sn.to(torch.int32).contiguous(), first_sn.to(torch.int32).contiguous(), res, wstart
 
 
+def repack_reference(layouts, group_size: int, index_bits: int, res_bits: int, row_words: int, slices: int) -> torch.Tensor:
+    """Pure-torch model of `vptq_sliced_layout_repack` (tests and docs only): the packed int32 indices [1, N, row_words] rebuilt from
+    the EXACT layout(s) `layout_from_indices` returned - one tuple (elems, blocks, first, res, wstart) per column part, part p
+    covering columns [p G / parts, (p + 1) G / parts).  An element word is `column | local << 16`; the (slice, row) list it sits in
+    gives index = slice << (index_bits - log2(slices)) | local; `res` (uint8, or int16 bit patterns) the residual index above it."""
+    G, parts = group_size, len(layouts)
+    T, w = index_bits + res_bits, group_size // len(layouts)
+    sb = index_bits - {8: 3, 16: 4, 32: 5}[slices]
+    N = layouts[0][1].shape[1]
+    dev = layouts[0][0].device
+    vals = torch.zeros(N, G, dtype=torch.int64, device=dev)
+    for p, (e, b, f, r, _) in enumerate(layouts):
+        # block k belongs to the (s, n) list with first[s, n] <= k < first[s, n] + blocks[s, n]: lists in (s, n) order
+        sn = torch.repeat_interleave(torch.arange(b.numel(), device=dev), b.reshape(-1).to(torch.int64))
+        sn = sn.repeat_interleave(64)
+        word = e[:sn.numel()].to(torch.int64) & 0xFFFFFFFF
+        col, local = word & 0xFFFF, word >> 16
+        val = ((sn // N) << sb) | local
+        if r is not None:
+            val |= (r[:sn.numel()].to(torch.int64) & (0xFF if r.dtype == torch.uint8 else 0xFFFF)) << index_bits
+        keep = col < w                       # (padding: column = part width)
+        vals[(sn % N)[keep], p * w + col[keep]] = val[keep]
+    bitpos = torch.arange(G, device=dev, dtype=torch.int64) * T
+    shifted = vals << (bitpos & 31)
+    flat = torch.zeros(N, row_words + 1, dtype=torch.int64, device=dev)
+    flat.index_add_(1, bitpos >> 5, shifted & 0xFFFFFFFF)
+    flat.index_add_(1, (bitpos >> 5) + 1, shifted >> 32)
+    out = flat[:, :row_words]
+    return torch.where(out >= 2**31, out - 2**32, out).to(torch.int32).reshape(1, N, row_words)
+
+
+def tail_bits_clear(indices: torch.Tensor, group_size: int, total_bits: int) -> bool:
+    """no bit past G T in any row of the packed indices (`pack_index` never writes one; a layout cannot hold one).  One device -> host read."""
+    nbits = group_size * total_bits
+    full, rem = nbits // 32, nbits % 32
+    rows = indices.reshape(-1, indices.shape[-1])
+    bad = rows[:, full + (1 if rem else 0):].ne(0).any()
+    if rem:
+        bad = bad | ((rows[:, full].to(torch.int64) & 0xFFFFFFFF) >> rem).ne(0).any()
+    return not bool(bad.item())
+
+
 def rows_per_wave_for(n_rows: int, slices: int = 8, workgroups: int = 256) -> int:
     """consecutive rows per wave so that slices x row blocks of 16 waves give about `workgroups` workgroups"""
     r = max(1, (n_rows * slices + 16 * workgroups - 1) // (16 * workgroups))
@@ -254,6 +296,30 @@ class SlicedGemv:
         self._dtype = cache[7]
         self._dev_index = cache[8]
         self.extra_bytes = sum(e.numel() * (4 + (r.element_size() if r is not None else 0)) + b.numel() * 8 for e, b, f, r, _ in self._tensors)
+
+    def repack(self, out: torch.Tensor = None) -> torch.Tensor:
+        """the layer's packed int32 indices rebuilt from this EXACT layout on the current stream (`vptq_sliced_layout_repack`): into
+        `out` (int32, the shape of `indices`, 16-byte aligned) or a fresh tensor"""
+        if not self.exact:
+            raise ValueError("only an exact layout holds the packed stream")
+        shape = (1, int(self.desc.num_indices), int(self.desc.row_words))
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.dev)
+        with torch.cuda.device(self.dev):
+            B.check(B.lib().vptq_sliced_layout_repack(self.desc, self._lay_ref, self.parts, out.data_ptr(),
+                                                      B.current_stream_ptr(self.dev)), "vptq_sliced_layout_repack")
+        return out
+
+    def rebound(self, desc) -> "SlicedGemv":
+        """a copy of this object over the same layout tensors and workspaces for another descriptor of the same layer (a compacted
+        layer's descriptor is rebuilt after set_arithmetic or a parameter change; its layout never is)"""
+        import copy
+        new = copy.copy(self)
+        new.desc = desc
+        if self.parts > 1:
+            w = self.layer.group_size // self.parts
+            new._part_descs = (B.LayerDesc * self.parts)(*[part_desc(desc, p * w, (p + 1) * w) for p in range(self.parts)])
+        return new
 
     def _workspace(self, stream_ptr: int):
         ws = self._ws.get(stream_ptr)
