@@ -107,11 +107,20 @@ enum {
    * arithmetic) on the activation columns that dominate the token - |f16(scale_g x_g)| >= 6 x the rms of f16(scale x) over the
    * layer's columns.  The folded form's distance to the reference is a sum of per-column rounding errors that average out over
    * thousands of columns when the activations are dense and do not when a handful of channels carry the token (massive
-   * activations): the blocks of 128 columns that hold such a column are rebuilt bit-exactly, the rest stays folded.  Kernels
+   * activations): the blocks of 128 columns that hold such a column are rebuilt bit-exactly, the rest stays folded.  The blocks
+   * (and the 512-column windows below) are those of the STORED column order - column c of the quantised matrix, which multiplies
+   * input feature perm[c]: the kernels stage x[perm] and look for the hot columns there; without a permutation the two orders
+   * are one.  The rule above is the chain launch's.  The persistent MFMA kernel of one-layer / grouped launches takes one
+   * threshold per wave, 6 x the rms over the columns that wave stages, columns past the last one counted as zeros: up to 8192
+   * columns that is window w = columns [512 w, 512 w + 512); from 8193 columns on (5 - 7 sweeps) the kernel stages in two phases
+   * of 8192 columns and a wave's threshold runs over its 512 columns of BOTH - windows w and w + 16, 1024 columns - so a window
+   * whose partner lies past the last column has a threshold lower by sqrt(2) and turns hot sooner (never later: more exact
+   * blocks, not fewer).  Kernels
    * that implement it (fp16 and bf16): the persistent chain launch (independent layers; needs the workspace
    * vptq_quant_gemv_chain_workspace_bytes_for(descs, n, flags) asks for - 16 bytes per layer + 4 per output: thresholds and
    * the hot blocks' exact products) and the persistent MFMA kernel of one-layer / grouped launches (1 token, up to
-   * 14336 columns, at most 16 row groups per workgroup; thresholds over the 512 columns a wave stages, then the 16 most dominant blocks);
+   * 14336 columns, at most 16 row groups per workgroup; thresholds over the 512 / 1024 columns a wave stages, as above, then the 16 most
+   * dominant blocks);
    * every other kernel / layer / token count takes VPTQ_GEMV_EXACT instead (always at least as close to the reference).
    * With VPTQ_GEMV_EXACT set as well, EXACT wins.  Not bit-equivalent (55 - 65 % of the outputs bit-identical); counted on
    * checkpoint-like layers: 2 of 12 300 above the 1e-3 bar at 1.00e-3 / 1.09e-3 through the chain launch (folded form: 30
@@ -460,6 +469,28 @@ VPTQ_API const char* vptq_quant_gemv_kernel_name(const VptqLayerDesc* desc, int 
  * when the group is not served by one launch */
 VPTQ_API const char* vptq_quant_gemv_grouped_kernel_name(const VptqLayerDesc* descs, int n, int tokens,
                                                 int flags);
+/* Diagnostic (added within ABI 11; present when the symbols are): WHICH INSTANTIATION of that kernel the call would launch.  A
+ * kernel name above is a family of separately compiled instantiations, picked by the layer's shape; these write the template
+ * arguments and launch-shape facts the dispatch decided into buf as one line of `name key=value ...`, stable and parseable,
+ * produced by the very host functions that pick the launch (nothing is decided twice).  Host logic: nothing is launched, no
+ * device is needed (without one the CU count is taken as 256).  One launch per line item; a call served by several launches
+ * joins them with " | " (a split grouped launch, the members of a group served one by one, launches of 32 chain layers).
+ *   gemv_k256m dt=f16|bf16 ns=1..7 nst=0|1|2 perm=0|1 fast=0|1 tok=1|2|4 sb=0|1 entry=0|1 slots=1..4 units=N sel=0|1
+ *       ns sweeps of 2048 columns, nst staging phases (0: the unstaged form beyond 14336 columns), tok token slots, sb scale and
+ *       bias staged in LDS, entry 1 = the preloaded-argument entry (one layer, one token), slots partial-sum slots, units the most
+ *       row groups (of 4 vector-rows) one workgroup walks, sel the selective corrections
+ *   gemv_k256 dt= rows=1|2 tok=1|2|4 sw=1|2 perm= fast= entry=
+ *   gemm_k256 dt= perm= tok=N passes=4+2+1      (the passes of 4 / 2 / 1 row groups the busiest workgroup runs)
+ *   gemm_k256t dt= perm= tok=N sweeps=N rgs=N    (rgs: the most row groups one workgroup walks)
+ *   gemv_k256c dt= dep=0|1 mode=folded|exact|selective layers=N sweeps=a,b,... perm=a,b,...   (per layer, in list order)
+ * vptq_quant_gemv_chain_instance puts "grouped: " / "per-layer: " in front where the chain call hands the list to those.  The
+ * other kernel families answer with their kernel name alone.  tokens beyond one launch's: the first launch.  Returns VPTQ_OK,
+ * the validation error of the call itself, or VPTQ_E_WORKSPACE when buf (bytes long, NUL included) is too small. */
+VPTQ_API int vptq_quant_gemv_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+VPTQ_API int vptq_quant_gemv_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf,
+                                              size_t bytes);
+VPTQ_API int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf,
+                                            size_t bytes);
 
 #ifdef __cplusplus
 }

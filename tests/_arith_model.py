@@ -7,7 +7,10 @@ arithmetic, output by output:
   exact      w = the reference's bits (vptq_dequant / vo.dequant), m = sum_j w_j x_j + bias
   folded     m = sum_j (c + r)_j r16(s_j x_j) + sum_j b_j x_j + bias      (c + r exact: separate products of c and r)
              m = sum_j r16(c + r)_j r16(s_j x_j) + ...                      (rounded=True: c + r rounded to 16 bits first)
-  selective  exact on the given blocks of 128 input columns, folded elsewhere
+  selective  exact on the given blocks of 128 columns, folded elsewhere.  The blocks are blocks of the STORED column order
+             (column c of the quantised matrix multiplies input feature perm[c]; without a permutation the two orders are
+             one): the kernels stage x[perm] and find the hot blocks there.  hot_cols = the same as a mask over the input
+             features (hot_mask_for)
   cols       a column range [c0, c1) of any of them (row-parallel shards, column parts); the output bias only where asked
 
 and with every model the magnitude a = sum_j |term_j| + |bias| that bounds an fp32 summation's error in any order:
@@ -101,9 +104,21 @@ def _hot_mask(I, hot_blocks):
     return mk
 
 
-def model(P, x_bits, arith="exact", *, rounded=False, round_sx=True, hot_blocks=(), cols=None, with_bias=True):
+def hot_mask_for(I, hot_blocks, perm=None):
+    """mask over the INPUT FEATURES of the blocks of 128 STORED columns `hot_blocks`: feature perm[c] for every stored column c of
+    a hot block (perm: the layer's uint16 permutation, None: stored order = input-feature order)"""
+    stored = _hot_mask(I, hot_blocks)
+    if perm is None:
+        return stored
+    mk = np.zeros(I, bool)
+    mk[np.ascontiguousarray(perm).view(np.uint16).astype(np.int64)[stored]] = True
+    return mk
+
+
+def model(P, x_bits, arith="exact", *, rounded=False, round_sx=True, hot_blocks=(), hot_cols=None, cols=None, with_bias=True):
     """-> (m, a), float64 [tokens, O].  P = pieces(L).
-    arith: "exact" | "folded" | "selective" (exact on hot_blocks, folded elsewhere).  rounded: the folded form with r16(c + r);
+    arith: "exact" | "folded" | "selective" (exact on hot_blocks - or on the input features hot_cols, a mask: a permuted layer's
+    blocks are blocks of its stored column order, hot_mask_for - folded elsewhere).  rounded: the folded form with r16(c + r);
     round_sx=False: the folded form with s x unrounded.  cols: [c0, c1) of the input columns (shards, column parts);
     with_bias: add the output bias (rank 0 of a row-parallel shard only)."""
     dt = P["dtype"]
@@ -115,7 +130,7 @@ def model(P, x_bits, arith="exact", *, rounded=False, round_sx=True, hot_blocks=
     elif arith == "folded":
         ex_cols, fo_cols = np.zeros(I, bool), inside
     elif arith == "selective":
-        hot = _hot_mask(I, hot_blocks)
+        hot = _hot_mask(I, hot_blocks) if hot_cols is None else np.asarray(hot_cols, bool)
         ex_cols, fo_cols = inside & hot, inside & ~hot
     else:
         raise ValueError(arith)

@@ -33,21 +33,24 @@ def _dense(I, tokens, dt, seed):
     return vo.from_f32(x.astype(np.float32), dt), ()
 
 
-def _planted(I, tokens, dt, seed, n=3):
-    """-> (x bits, hot blocks): the others within 2.5 (~2.5 x their rms), n columns of magnitude 60 in distinct 128-column blocks
+def _planted(I, tokens, dt, seed, n=3, perm=None, clip=2.5):
+    """-> (x bits, hot blocks): the others within `clip` = 2.5 (~2.5 x their rms), n columns of magnitude 60 in distinct 128-column blocks
     (the same columns for every token).  Where the last 512-column window is short of columns, one of them is planted too: the
     per-window rule (gemv_k256m.hip) counts the missing columns as zeros, so a short window's threshold is low and its own ordinary
-    columns could turn hot - with a planted column in it every rule has the same hot set (_hot_rules_agree)"""
+    columns could turn hot - with a planted column in it every rule has the same hot set (_hot_rules_agree).
+    perm (the layer's uint16 permutation): blocks and windows are those of the STORED column order - stored column c reads input
+    feature perm[c] - so the column planted for stored position c is x[..., perm[c]]"""
     rng = np.random.default_rng(seed)
-    x = np.clip(rng.standard_normal((1, tokens, I)), -2.5, 2.5)
+    x = np.clip(rng.standard_normal((1, tokens, I)), -clip, clip)
     nb = (I + 127) // 128
     blocks = set(int(b) for b in rng.choice(nb, min(n, nb), replace=False))
     if I % SEL_WINDOW and I % SEL_WINDOW < SEL_WINDOW // 2 and not any(b * 128 >= I - I % SEL_WINDOW for b in blocks):
         blocks.add(nb - 1)
     blocks = sorted(blocks)
+    feature = np.arange(I) if perm is None else np.ascontiguousarray(perm).view(np.uint16).astype(np.int64)
     for b in blocks:
         col = b * 128 + int(rng.integers(0, min(128, I - b * 128)))
-        x[..., col] = 60.0 * rng.choice([-1.0, 1.0], size=tokens)
+        x[..., feature[col]] = 60.0 * rng.choice([-1.0, 1.0], size=tokens)
     return vo.from_f32(x.astype(np.float32), dt), tuple(blocks)
 
 
@@ -55,16 +58,30 @@ XKIND = {"dense": _dense, "planted": _planted}
 SEL_WINDOW, SEL_KAPPA = 512, 6.0   # the hot-block rules: kappa x rms of f16(s x) over the layer / over each 512-column window
 
 
-def _hot_rules_agree(P, x, hot):
-    """the hot blocks by both documented rules - over the layer's columns (gemv_hot, the chain launch) and over each 512-column
-    window, missing columns counted as zeros (gemv_k256m) - are the planted ones, every column clear of either threshold by 25 %"""
+SEL_STAGE = 8192   # gemv_k256m stages 8192 columns per phase: beyond that a wave's rms runs over its 512 columns of BOTH phases
+
+
+def _hot_rules_agree(P, x, hot, perm=None):
+    """the hot blocks by every documented rule - over the layer's columns (gemv_hot, the chain launch), over each 512-column
+    window, missing columns counted as zeros (gemv_k256m up to 8192 columns) and, beyond 8192 columns, over the 1024 columns of
+    window w and window w + 16 together (gemv_k256m from 5 sweeps on: two staging phases, one threshold per wave) - are the
+    planted ones, every column clear of every threshold by 25 %.  Columns, blocks and windows are those of the STORED order
+    (perm: stored column c = input feature perm[c])"""
     dt = P["dtype"]
     I = P["W"].shape[1]
     sx = np.abs(vo.round_to((P["s"] * vo.to_f32(np.asarray(x), dt).reshape(-1, I)).astype(np.float32), dt).astype(np.float64))
+    if perm is not None:
+        sx = sx[:, np.ascontiguousarray(perm).view(np.uint16).astype(np.int64)]
     pad = np.concatenate([sx, np.zeros((sx.shape[0], (-I) % SEL_WINDOW))], axis=1)
-    win = np.sqrt((pad.reshape(sx.shape[0], -1, SEL_WINDOW) ** 2).mean(axis=2))
+    sq = (pad.reshape(sx.shape[0], -1, SEL_WINDOW) ** 2).mean(axis=2)
+    win = np.sqrt(sq)
     thresholds = {"layer": SEL_KAPPA * np.sqrt((sx ** 2).mean(axis=1, keepdims=True)),
                   "window": SEL_KAPPA * np.repeat(win, SEL_WINDOW, axis=1)[:, :I]}
+    if SEL_STAGE < I <= 2 * SEL_STAGE:   # (wider layers are not staged: no selective form in gemv_k256m)
+        per = SEL_STAGE // SEL_WINDOW
+        both = np.concatenate([sq, np.zeros((sq.shape[0], 2 * per - sq.shape[1]))], axis=1)
+        pair = np.sqrt((both[:, :per] + both[:, per:]) / 2)
+        thresholds["window pair"] = SEL_KAPPA * np.repeat(np.concatenate([pair, pair], axis=1), SEL_WINDOW, axis=1)[:, :I]
     for rule, thr in thresholds.items():
         ratio = sx / thr
         assert not ((ratio > 0.8) & (ratio < 1.25)).any(), f"{rule} rule: a column near the threshold"
@@ -80,9 +97,10 @@ def _check(y16, y32, L, x, e, hot, extra=0.0, P=None, what=""):
     """y16 / y32 (either None) against the entry's model; a failure names the models the output WOULD meet"""
     P = P or am.pieces(L)
     T = x.size // L.in_features
-    kw = dict(rounded=e.get("rounded", False), round_sx=e.get("round_sx", True), hot_blocks=hot if e["arith"] == "selective" else ())
+    kw = dict(rounded=e.get("rounded", False), round_sx=e.get("round_sx", True),
+              hot_cols=am.hot_mask_for(L.in_features, hot, L.perm) if e["arith"] == "selective" else None)
     if e["arith"] == "selective":
-        _hot_rules_agree(P, x, hot)
+        _hot_rules_agree(P, x, hot, L.perm)
     mm, aa = am.model(P, x, e["arith"], **kw)
     try:
         if y16 is not None:
@@ -94,7 +112,7 @@ def _check(y16, y32, L, x, e, hot, extra=0.0, P=None, what=""):
         for name, arith, kw2 in (("exact", "exact", {}), ("folded", "folded", {}), ("folded r16(c+r)", "folded", dict(rounded=True)),
                                  ("folded unrounded s x", "folded", dict(round_sx=False)),
                                  ("folded r16(c+r), unrounded s x", "folded", dict(rounded=True, round_sx=False)),
-                                 ("selective", "selective", dict(hot_blocks=hot))):
+                                 ("selective", "selective", dict(hot_cols=am.hot_mask_for(L.in_features, hot, L.perm)))):
             m2, a2 = am.model(P, x, arith, **kw2)
             y = y32 if y32 is not None else y16
             if not am.violations(y.reshape(T, -1), m2, a2, L.dtype, y is y32, extra)[0].any():
@@ -103,7 +121,9 @@ def _check(y16, y32, L, x, e, hot, extra=0.0, P=None, what=""):
 
 
 # ---------------------------------------------------------------------------------------------- the table of one-layer routes
-# layer: (I, O, make_layer kwargs); flags of the call; the kernel name vptq_quant_gemv_kernel_name must give; the model.
+# layer: (I, O, make_layer kwargs); flags of the call; the kernel name vptq_quant_gemv_kernel_name must give; the model; for the
+# canonical format's kernels the instance vptq_quant_gemv_instance must give (every instantiation of those kernels has its row in
+# tests/test_route_models_k256_gpu.py, which tests/test_instance_census_cpu.py holds to what the dispatch can produce).
 # Tail shapes: O not a multiple of v x row group (264, 1032, 72, 40, 8200), I not a multiple of the sweep / block (4104, 1000,
 # 520, 8192 + 512).
 def E(route, layer, dt, tokens, flags, arith, xkinds=("dense",), **kw):
@@ -119,32 +139,55 @@ VALU_FOLDED = dict(rounded=True, round_sx=False)
 LLM = dict(dist="llm")
 ONE_LAYER = [
     # VALU kernel of the canonical format: the reference's roundings; the folded form (fp16, 1 - 2 tokens)
-    E("gemv_k256_kernel", (4104, 264, dict(LLM, bias=True)), "f16", 1, EXACT, "exact", ("dense", "planted")),
-    E("gemv_k256_kernel", (4104, 264, dict(LLM)), "bf16", 3, EXACT, "exact"),
-    E("gemv_k256_kernel", (1024, 72, dict(LLM, bias=True)), "f16", 4, EXACT | VALU, "exact"),
-    E("gemv_k256_kernel<fast>", (4104, 264, dict(LLM, bias=True)), "f16", 1, 0, "folded", ("planted",), **VALU_FOLDED),
-    E("gemv_k256_kernel<fast>", (2048, 1032, dict(LLM)), "f16", 2, VALU, "folded", ("planted",), **VALU_FOLDED),
+    E("gemv_k256_kernel", (4104, 264, dict(LLM, bias=True)), "f16", 1, EXACT, "exact", ("dense", "planted"),
+      instance="gemv_k256 dt=f16 rows=1 tok=1 sw=2 perm=0 fast=0 entry=1"),
+    E("gemv_k256_kernel", (4104, 264, dict(LLM)), "bf16", 3, EXACT, "exact",
+      instance="gemv_k256 dt=bf16 rows=1 tok=4 sw=1 perm=0 fast=0 entry=0"),
+    E("gemv_k256_kernel", (1024, 72, dict(LLM, bias=True)), "f16", 4, EXACT | VALU, "exact",
+      instance="gemv_k256 dt=f16 rows=1 tok=4 sw=1 perm=0 fast=0 entry=0"),
+    E("gemv_k256_kernel<fast>", (4104, 264, dict(LLM, bias=True)), "f16", 1, 0, "folded", ("planted",), **VALU_FOLDED,
+      instance="gemv_k256 dt=f16 rows=1 tok=1 sw=2 perm=0 fast=1 entry=1"),
+    E("gemv_k256_kernel<fast>", (2048, 1032, dict(LLM)), "f16", 2, VALU, "folded", ("planted",), **VALU_FOLDED,
+      instance="gemv_k256 dt=f16 rows=1 tok=2 sw=1 perm=0 fast=1 entry=0"),
     # persistent MFMA kernel: exact / folded / selective, 1 - 4 tokens, fp16 and bf16
-    E("gemv_k256m_kernel", (2048, 4608, dict(LLM)), "f16", 1, EXACT | MFMA, "exact", ("dense", "planted")),
-    E("gemv_k256m_kernel", (2048, 1032, dict(LLM, bias=True)), "f16", 4, EXACT | MFMA, "exact"),
-    E("gemv_k256m_kernel", (8192 + 512, 40, dict(LLM)), "bf16", 1, EXACT | MFMA, "exact"),
-    E("gemv_k256m_kernel", (2048, 1032, dict(LLM, bias=True)), "bf16", 3, EXACT | MFMA, "exact"),
-    E("gemv_k256m_kernel<fast>", (4104, 264, dict(LLM, bias=True)), "f16", 1, MFMA, "folded", ("planted",)),
-    E("gemv_k256m_kernel<fast>", (2048, 1032, dict(LLM)), "f16", 2, MFMA, "folded", ("planted",)),
-    E("gemv_k256m_kernel<fast>", (4104, 264, dict(LLM)), "bf16", 1, MFMA, "folded", ("planted",)),
-    E("gemv_k256m_kernel<fast>", (2048, 1032, dict(LLM, bias=True)), "bf16", 4, MFMA, "folded", ("planted",)),
-    E("gemv_k256m_kernel<selective>", (4104, 264, dict(LLM, bias=True)), "f16", 1, SEL | MFMA, "selective", ("planted",)),
-    E("gemv_k256m_kernel<selective>", (2048, 4608, dict(LLM)), "f16", 1, SEL, "selective", ("planted",)),
-    E("gemv_k256m_kernel<selective>", (4104, 264, dict(LLM)), "bf16", 1, SEL | MFMA, "selective", ("planted",)),
-    E("gemv_k256m_kernel<selective>", (2048, 1032, dict(LLM)), "f16", 1, SEL | MFMA, "selective", ("planted",)),
+    E("gemv_k256m_kernel", (2048, 4608, dict(LLM)), "f16", 1, EXACT | MFMA, "exact", ("dense", "planted"),
+      instance="gemv_k256m dt=f16 ns=1 nst=1 perm=0 fast=0 tok=1 sb=0 entry=1 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel", (2048, 1032, dict(LLM, bias=True)), "f16", 4, EXACT | MFMA, "exact",
+      instance="gemv_k256m dt=f16 ns=1 nst=1 perm=0 fast=0 tok=4 sb=1 entry=0 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel", (8192 + 512, 40, dict(LLM)), "bf16", 1, EXACT | MFMA, "exact",
+      instance="gemv_k256m dt=bf16 ns=5 nst=2 perm=0 fast=0 tok=1 sb=1 entry=1 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel", (2048, 1032, dict(LLM, bias=True)), "bf16", 3, EXACT | MFMA, "exact",
+      instance="gemv_k256m dt=bf16 ns=1 nst=1 perm=0 fast=0 tok=4 sb=1 entry=0 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel<fast>", (4104, 264, dict(LLM, bias=True)), "f16", 1, MFMA, "folded", ("planted",),
+      instance="gemv_k256m dt=f16 ns=3 nst=1 perm=0 fast=1 tok=1 sb=0 entry=1 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel<fast>", (2048, 1032, dict(LLM)), "f16", 2, MFMA, "folded", ("planted",),
+      instance="gemv_k256m dt=f16 ns=1 nst=1 perm=0 fast=1 tok=2 sb=0 entry=0 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel<fast>", (4104, 264, dict(LLM)), "bf16", 1, MFMA, "folded", ("planted",),
+      instance="gemv_k256m dt=bf16 ns=3 nst=1 perm=0 fast=1 tok=1 sb=0 entry=1 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel<fast>", (2048, 1032, dict(LLM, bias=True)), "bf16", 4, MFMA, "folded", ("planted",),
+      instance="gemv_k256m dt=bf16 ns=1 nst=1 perm=0 fast=1 tok=4 sb=0 entry=0 slots=4 units=1 sel=0"),
+    E("gemv_k256m_kernel<selective>", (4104, 264, dict(LLM, bias=True)), "f16", 1, SEL | MFMA, "selective", ("planted",),
+      instance="gemv_k256m dt=f16 ns=3 nst=1 perm=0 fast=1 tok=1 sb=0 entry=1 slots=4 units=1 sel=1"),
+    E("gemv_k256m_kernel<selective>", (2048, 4608, dict(LLM)), "f16", 1, SEL, "selective", ("planted",),
+      instance="gemv_k256m dt=f16 ns=1 nst=1 perm=0 fast=1 tok=1 sb=0 entry=1 slots=4 units=1 sel=1"),
+    E("gemv_k256m_kernel<selective>", (4104, 264, dict(LLM)), "bf16", 1, SEL | MFMA, "selective", ("planted",),
+      instance="gemv_k256m dt=bf16 ns=3 nst=1 perm=0 fast=1 tok=1 sb=0 entry=1 slots=4 units=1 sel=1"),
+    E("gemv_k256m_kernel<selective>", (2048, 1032, dict(LLM)), "f16", 1, SEL | MFMA, "selective", ("planted",),
+      instance="gemv_k256m dt=f16 ns=1 nst=1 perm=0 fast=1 tok=1 sb=0 entry=1 slots=4 units=1 sel=1"),
     # the one-pass batched-decode kernel (folded form), 1 - 16 tokens
-    E("gemm_k256t_kernel", (4104, 264, dict(LLM, bias=True)), "f16", 1, BATCHED, "folded", ("planted",)),
-    E("gemm_k256t_kernel", (2048, 1032, dict(LLM)), "f16", 7, 0, "folded", ("planted",)),
-    E("gemm_k256t_kernel", (1000 + 24, 200, dict(LLM, bias=True)), "bf16", 16, 0, "folded", ("planted",)),
+    E("gemm_k256t_kernel", (4104, 264, dict(LLM, bias=True)), "f16", 1, BATCHED, "folded", ("planted",),
+      instance="gemm_k256t dt=f16 perm=0 tok=1 sweeps=3 rgs=1"),
+    E("gemm_k256t_kernel", (2048, 1032, dict(LLM)), "f16", 7, 0, "folded", ("planted",),
+      instance="gemm_k256t dt=f16 perm=0 tok=7 sweeps=1 rgs=1"),
+    E("gemm_k256t_kernel", (1000 + 24, 200, dict(LLM, bias=True)), "bf16", 16, 0, "folded", ("planted",),
+      instance="gemm_k256t dt=bf16 perm=0 tok=16 sweeps=1 rgs=1"),
     # the batched-decode kernel in the reference's roundings, 5 - 16 tokens
-    E("gemm_k256_kernel", (4104, 264, dict(LLM, bias=True)), "f16", 5, EXACT, "exact"),
-    E("gemm_k256_kernel", (2048, 1032, dict(LLM)), "f16", 16, EXACT, "exact"),
-    E("gemm_k256_kernel", (4104, 264, dict(LLM, bias=True)), "bf16", 9, EXACT, "exact"),
+    E("gemm_k256_kernel", (4104, 264, dict(LLM, bias=True)), "f16", 5, EXACT, "exact",
+      instance="gemm_k256 dt=f16 perm=0 tok=5 passes=1"),
+    E("gemm_k256_kernel", (2048, 1032, dict(LLM)), "f16", 16, EXACT, "exact",
+      instance="gemm_k256 dt=f16 perm=0 tok=16 passes=1"),
+    E("gemm_k256_kernel", (4104, 264, dict(LLM, bias=True)), "bf16", 9, EXACT, "exact",
+      instance="gemm_k256 dt=bf16 perm=0 tok=9 passes=1"),
     # LDS-resident codebooks (256 < k <= 8192): the reference's roundings; the matrix-pipe one-token kernel (folded)
     E("gemv_lds_kernel", (520, 136, dict(num_centroids=4096, num_res_centroids=512, enable_perm=True)), "f16", 3, 0, "exact"),
     E("gemv_lds_kernel", (4096 + 8, 264, dict(num_centroids=8192, num_res_centroids=512)), "f16", 1, 0, "exact"),
@@ -177,6 +220,9 @@ def test_one_layer_route_vs_its_model(e, dev):
     L = _layer(e)
     m = spec_to_module(L, dev)
     assert kernel_name(m, e["tokens"], e["flags"]) == e["route"]
+    if "instance" in e:   # (the canonical format's kernels: which instantiation, tests/test_route_models_k256_gpu.py)
+        from test_route_models_k256_gpu import instance_of
+        assert instance_of([module_desc(m)[0]], e["tokens"], e["flags"]) == e["instance"]
     P = am.pieces(L)
     for kind in e["xkinds"]:
         x, hot = XKIND[kind](L.in_features, e["tokens"], L.dtype, L.in_features + e["tokens"])

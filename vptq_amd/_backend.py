@@ -121,6 +121,10 @@ EXPORTS = {
     "vptq_quant_gemv_grouped_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
     # (added within ABI 11) the packed index stream rebuilt from a layer's exact sliced layout(s): compact mode
     "vptq_sliced_layout_repack": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, _vp, _vp]),
+    # (added within ABI 11) which instantiation a call would launch, as text: host logic, nothing is launched
+    "vptq_quant_gemv_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "vptq_quant_gemv_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "vptq_quant_gemv_chain_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

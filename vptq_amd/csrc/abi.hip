@@ -263,47 +263,159 @@ int vptq_quant_gemv(const VptqLayerDesc* d, const void* x, void* y, int tokens, 
   }
 }
 
+// How a grouped call is executed: ONE decision for vptq_quant_gemv_grouped and vptq_quant_gemv_grouped_instance (x = NULL
+// there: the activation pointers are assumed aligned).  flags: as the call has normalised them.
+enum GroupRoute { kGroupEachK256, kGroupLaunches, kGroupPerLayer };
+static GroupRoute group_route(const VptqLayerDesc* descs, int n, const void* const* x, int tokens, int flags) {
+  bool all_fast = !(flags & VPTQ_GEMV_FORCE_GENERIC);
+  bool same_perm = true;  // one instantiation serves the whole group
+  for (int i = 0; i < n; ++i) {
+    all_fast = all_fast && vptq::gemv_k256_eligible(descs[i], tokens) && (!x || (((uintptr_t)x[i]) & 15) == 0);
+    same_perm = same_perm && ((descs[i].perm != nullptr) == (descs[0].perm != nullptr));
+  }
+  if (all_fast && !same_perm) return kGroupEachK256;   // one launch of the canonical format's kernels per layer
+  return all_fast ? kGroupLaunches : kGroupPerLayer;   // one launch for up to 32 layers / vptq_quant_gemv per layer
+}
+static int group_flags(int tokens, int flags) {
+  return tokens == 1 ? drop_redundant_selective(flags) : selective_as_exact(flags);   // (one token: gemv_k256.hip:choose_kernel decides)
+}
+
 int vptq_quant_gemv_grouped(const VptqLayerDesc* descs, int n, const void* const* x,
                             void* const* y, int tokens, int flags, void* stream) {
   if (!descs || !x || !y) return fail(VPTQ_E_NULL, "descs / x / y is NULL");
   if (n < 1 || n > VPTQ_GROUP_MAX) return fail(VPTQ_E_SHAPE, "n %d outside [1, %d]", n, VPTQ_GROUP_MAX);
   if (tokens < 1 || tokens > VPTQ_GEMV_MAX_TOKENS_ANY)
     return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d]", tokens, VPTQ_GEMV_MAX_TOKENS_ANY);
-  flags = tokens == 1 ? drop_redundant_selective(flags) : selective_as_exact(flags);   // (one token: gemv_k256.hip:choose_kernel decides)
-  bool all_fast = !(flags & VPTQ_GEMV_FORCE_GENERIC);
-  bool same_perm = true;  // one instantiation serves the whole group
+  flags = group_flags(tokens, flags);
   for (int i = 0; i < n; ++i) {
     int rc = validate_layer(&descs[i]);
     if (rc) return rc;
     if (!x[i] || !y[i]) return fail(VPTQ_E_NULL, "x[%d] / y[%d] is NULL", i, i);
     if (descs[i].dtype != descs[0].dtype)
       return fail(VPTQ_E_UNSUPPORTED, "grouped layers must share one dtype");
-    all_fast = all_fast && vptq::gemv_k256_eligible(descs[i], tokens) &&
-               (((uintptr_t)x[i]) & 15) == 0;
-    same_perm = same_perm && ((descs[i].perm != nullptr) == (descs[0].perm != nullptr));
   }
   hipStream_t st = (hipStream_t)stream;
-  if (all_fast && !same_perm) {
-    for (int i = 0; i < n; ++i) {
-      hipError_t e = vptq::launch_gemv_k256(descs + i, 1, x + i, y + i, tokens, flags, st);
-      if (e != hipSuccess) return hip_fail(e, "gemv_k256 launch");
-    }
-    return VPTQ_OK;
-  }
-  if (all_fast) {
-    // one launch for up to 32 layers
-    for (int i0 = 0; i0 < n; i0 += 32) {
-      const int m = n - i0 < 32 ? n - i0 : 32;
-      hipError_t e = vptq::launch_gemv_k256(descs + i0, m, x + i0, y + i0, tokens, flags, st);
-      if (e != hipSuccess) return hip_fail(e, "gemv_k256 grouped launch");
-    }
-    return VPTQ_OK;
+  switch (group_route(descs, n, x, tokens, flags)) {
+    case kGroupEachK256:
+      for (int i = 0; i < n; ++i) {
+        hipError_t e = vptq::launch_gemv_k256(descs + i, 1, x + i, y + i, tokens, flags, st);
+        if (e != hipSuccess) return hip_fail(e, "gemv_k256 launch");
+      }
+      return VPTQ_OK;
+    case kGroupLaunches:
+      // one launch for up to 32 layers
+      for (int i0 = 0; i0 < n; i0 += 32) {
+        const int m = n - i0 < 32 ? n - i0 : 32;
+        hipError_t e = vptq::launch_gemv_k256(descs + i0, m, x + i0, y + i0, tokens, flags, st);
+        if (e != hipSuccess) return hip_fail(e, "gemv_k256 grouped launch");
+      }
+      return VPTQ_OK;
+    default:
+      break;
   }
   for (int i = 0; i < n; ++i) {
     const int rc = vptq_quant_gemv(&descs[i], x[i], y[i], tokens, flags, nullptr, 0, stream);
     if (rc) return rc;
   }
   return VPTQ_OK;
+}
+
+// ---- which instantiation a call would launch, as text (vptq_quant_gemv*_instance): the decisions above and the kernels' own
+// decide functions (gemv_k256.hip:k256_decide, gemv_k256m_decide, gemm_k256_decide, gemm_k256t_decide, gemv_k256c_mode), printed
+namespace {
+struct Text {
+  char* buf; size_t bytes, used; bool fits;
+  void add(const char* fmt, ...) {
+    if (!fits) return;
+    va_list ap;
+    va_start(ap, fmt);
+    const int w = vsnprintf(buf + used, bytes - used, fmt, ap);
+    va_end(ap);
+    if (w < 0 || (size_t)w >= bytes - used) { fits = false; return; }
+    used += (size_t)w;
+  }
+};
+int text_done(const Text& t) { return t.fits ? VPTQ_OK : fail(VPTQ_E_WORKSPACE, "instance: buffer of %zu bytes too small", t.bytes); }
+const char* dt_text(int dtype) { return dtype == VPTQ_DTYPE_F16 ? "f16" : "bf16"; }
+
+// launches of the canonical format's one-layer kernels for (descs, n, tokens): appended to t
+int add_k256(Text& t, const VptqLayerDesc* descs, int n, int tokens, int flags) {
+  char one[1024];
+  const int rc = vptq::gemv_k256_instance(descs, n, tokens, flags, one, sizeof(one));
+  if (rc == -2) { t.fits = false; return VPTQ_OK; }
+  if (rc) return fail(VPTQ_E_UNSUPPORTED, "instance: no gemv_k256 / gemv_k256m instantiation for this launch");
+  t.add("%s", one);
+  return VPTQ_OK;
+}
+
+// what vptq_quant_gemv(d, tokens, flags) launches (the first launch of a call that is served in several)
+int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
+  const int kflags = drop_redundant_selective(flags);
+  flags = selective_as_exact(flags);
+  const Route r = route_gemv(d, tokens, flags, nullptr, true);
+  switch (r) {
+    case kRouteGemmK256T: {
+      const vptq::GemmK256TDecision D = vptq::gemm_k256t_decide(d);
+      t.add("gemm_k256t dt=%s perm=%d tok=%d sweeps=%d rgs=%d", dt_text(d.dtype), (int)D.perm, tokens > 16 ? 16 : tokens, D.n_sweeps,
+            D.groups_per_wg);
+      return VPTQ_OK;
+    }
+    case kRouteGemmK256: {
+      const vptq::GemmK256Decision D = vptq::gemm_k256_decide(d);
+      t.add("gemm_k256 dt=%s perm=%d tok=%d passes=", dt_text(d.dtype), (int)D.perm, tokens > 16 ? 16 : tokens);
+      bool first = true;
+      for (int nrg = 4; nrg >= 1; nrg >>= 1)
+        if (D.passes & nrg) { t.add("%s%d", first ? "" : "+", nrg); first = false; }
+      return VPTQ_OK;
+    }
+    case kRouteK256: {
+      const VptqLayerDesc* dp = &d;
+      return add_k256(t, dp, 1, tokens > 4 ? 4 : tokens, tokens == 1 ? kflags : flags);
+    }
+    case kRouteNone:
+      return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d] for this layer", tokens, VPTQ_GEMV_MAX_TOKENS_ANY);
+    default: {   // the other families: their kernel's name (their instantiations are not reported yet)
+      const char* name = vptq_quant_gemv_kernel_name(&d, tokens, kflags);
+      t.add("%s", name ? name : "none");
+      return VPTQ_OK;
+    }
+  }
+}
+}  // namespace
+
+int vptq_quant_gemv_instance(const VptqLayerDesc* d, int tokens, int flags, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  int rc = validate_layer(d);
+  if (rc) return rc;
+  if (tokens < 1 || tokens > VPTQ_GEMV_MAX_TOKENS) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d]", tokens, VPTQ_GEMV_MAX_TOKENS);
+  Text t = {buf, bytes, 0, true};
+  rc = add_one(t, *d, tokens, flags);
+  return rc ? rc : text_done(t);
+}
+
+int vptq_quant_gemv_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes) {
+  if (!descs || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / buf is NULL");
+  buf[0] = 0;
+  if (n < 1 || n > VPTQ_GROUP_MAX) return fail(VPTQ_E_SHAPE, "n %d outside [1, %d]", n, VPTQ_GROUP_MAX);
+  if (tokens < 1 || tokens > VPTQ_GEMV_MAX_TOKENS_ANY)
+    return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d]", tokens, VPTQ_GEMV_MAX_TOKENS_ANY);
+  flags = group_flags(tokens, flags);
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_layer(&descs[i]);
+    if (rc) return rc;
+    if (descs[i].dtype != descs[0].dtype) return fail(VPTQ_E_UNSUPPORTED, "grouped layers must share one dtype");
+  }
+  Text t = {buf, bytes, 0, true};
+  const GroupRoute route = group_route(descs, n, nullptr, tokens, flags);
+  const int step = route == kGroupLaunches ? 32 : 1;
+  for (int i0 = 0; i0 < n; i0 += step) {
+    if (i0) t.add(" | ");
+    const int m = n - i0 < step ? n - i0 : step;
+    const int rc = route == kGroupPerLayer ? add_one(t, descs[i0], tokens, flags) : add_k256(t, descs + i0, m, tokens, flags);
+    if (rc) return rc;
+  }
+  return text_done(t);
 }
 
 // ---- chain: one persistent launch per <= 32 layers (gemv_k256c.hip), else layer by layer ----
@@ -375,6 +487,84 @@ static ChainRoute chain_route(const VptqLayerDesc* descs, int n, const void* con
   return persistent_ok ? kChainPersistent : kChainPerLayer;
 }
 
+// Layers with an input permutation in an independent one-token list: the persistent launch runs on (x[perm], scale_permuted,
+// bias_permuted) without a permutation.  dd = the descriptors it is given; 0: no layer has one, 1: all of them can, -1: not all
+static int chain_absorb_perms(const VptqLayerDesc* descs, int n, std::vector<VptqLayerDesc>& dd) {
+  dd.assign(descs, descs + n);
+  bool any = false, ok = true;
+  for (int i = 0; i < n; ++i) {
+    if (!dd[i].perm) continue;
+    any = true;
+    ok = ok && dd[i].scale_permuted && dd[i].bias_permuted && (dd[i].in_features % 8) == 0 && (((uintptr_t)dd[i].perm) & 15) == 0;
+    dd[i].weight_scale = dd[i].scale_permuted;
+    dd[i].weight_bias = dd[i].bias_permuted;
+    dd[i].perm = nullptr; dd[i].inv_perm = nullptr; dd[i].scale_permuted = nullptr; dd[i].bias_permuted = nullptr;
+  }
+  return !any ? 0 : ok ? 1 : -1;
+}
+
+// How a chain call is executed: ONE decision for vptq_quant_gemv_chain and vptq_quant_gemv_chain_instance.  The call hands over
+// its activation pointers and workspace; the query passes x = NULL and assume_ws (the workspace ..._workspace_bytes_for asks
+// for, aligned, as vptq_quant_gemv_chain_kernel_name assumes).
+struct ChainDecision {
+  int flags;            // normalised: SELECTIVE dropped beside EXACT, and turned into EXACT where the call cannot carry its thresholds
+  bool dependent;
+  size_t sel_bytes;     // > 0: the selective thresholds take the first sel_bytes of the workspace
+  ChainRoute route;
+  bool absorbed;        // persistent launch with the permuted layers on (x[perm], scale_permuted, bias_permuted): x[perm] is
+                        // gathered into the workspace (behind the thresholds) by one small launch in front
+  std::vector<VptqLayerDesc> run;   // absorbed: the descriptors the persistent launch is given
+  std::vector<const void*> xx;      // absorbed, x given: its activation pointers ...
+  std::vector<void*> xp;            // ... and where x[perm] of each permuted layer goes (NULL: no permutation)
+};
+static ChainDecision chain_decide(const VptqLayerDesc* descs, int n, const void* const* x, int tokens, int flags, bool assume_ws,
+                                  void* workspace, size_t workspace_bytes) {
+  ChainDecision D = {};
+  D.dependent = (flags & VPTQ_GEMV_CHAIN_DEPENDENT) != 0;
+  flags = drop_redundant_selective(flags);
+  char* ws = (char*)workspace;
+  auto ws_holds = [&](size_t need) { return assume_ws || (ws && workspace_bytes >= need && (((uintptr_t)ws) & 255) == 0); };
+  // SELECTIVE: the thresholds live in front of the workspace; without it (or for a dependent list) the call takes the
+  // reference's roundings everywhere
+  if (flags & VPTQ_GEMV_SELECTIVE) {
+    const size_t tb = chain_sel_bytes(descs, n, flags);
+    if (tb > 0 && ws_holds(tb)) {
+      D.sel_bytes = tb;
+      if (ws) { ws += tb; workspace_bytes -= tb; }
+    } else {
+      flags = selective_as_exact(flags);
+    }
+  }
+  D.flags = flags;
+  // Layers with an input permutation in an independent list: with enough workspace for x[perm] the list still runs in the
+  // persistent launch
+  if (!D.dependent && tokens == 1) {
+    size_t need = 0;
+    for (int i = 0; i < n; ++i) need += vptq::gemv_k256c_perm_bytes(descs[i]);
+    if (need > 0 && ws_holds(need) && chain_absorb_perms(descs, n, D.run) == 1) {
+      if (x) {
+        D.xx.assign(x, x + n);
+        D.xp.assign(n, nullptr);
+        char* w = ws;
+        for (int i = 0; i < n; ++i) {
+          if (!descs[i].perm) continue;
+          D.xp[i] = w;
+          D.xx[i] = w;
+          w += vptq::gemv_k256c_perm_bytes(descs[i]);
+        }
+      }
+      if (chain_route(D.run.data(), n, x ? D.xx.data() : nullptr, tokens, flags) == kChainPersistent) {
+        D.absorbed = true;
+        D.route = kChainPersistent;
+        return D;
+      }
+    }
+  }
+  D.run.clear();
+  D.route = chain_route(descs, n, x, tokens, flags);
+  return D;
+}
+
 const char* vptq_quant_gemv_chain_kernel_name(const VptqLayerDesc* descs, int n, int tokens, int flags) {
   if (!descs || n < 1 || n > VPTQ_CHAIN_MAX || tokens < 1 || tokens > VPTQ_GEMV_MAX_TOKENS) return nullptr;
   for (int i = 0; i < n; ++i)
@@ -382,17 +572,9 @@ const char* vptq_quant_gemv_chain_kernel_name(const VptqLayerDesc* descs, int n,
   if (!(flags & VPTQ_GEMV_CHAIN_DEPENDENT) && tokens == 1) {
     // (as vptq_quant_gemv_kernel_name: assuming the caller hands over the workspace ..._workspace_bytes_for asks for -
     // layers with an input permutation then stay in the persistent launch)
-    bool any = false, ok = true;
-    std::vector<VptqLayerDesc> dd(descs, descs + n);
-    for (int i = 0; i < n; ++i) {
-      if (!dd[i].perm) continue;
-      any = true;
-      ok = ok && dd[i].scale_permuted && dd[i].bias_permuted && (dd[i].in_features % 8) == 0 && (((uintptr_t)dd[i].perm) & 15) == 0;
-      dd[i].weight_scale = dd[i].scale_permuted;
-      dd[i].weight_bias = dd[i].bias_permuted;
-      dd[i].perm = nullptr; dd[i].inv_perm = nullptr; dd[i].scale_permuted = nullptr; dd[i].bias_permuted = nullptr;
-    }
-    if (any && ok && chain_route(dd.data(), n, nullptr, tokens, flags) == kChainPersistent) return "gemv_k256c_kernel";
+    std::vector<VptqLayerDesc> dd;
+    if (chain_absorb_perms(descs, n, dd) == 1 && chain_route(dd.data(), n, nullptr, tokens, flags) == kChainPersistent)
+      return "gemv_k256c_kernel";
   }
   switch (chain_route(descs, n, nullptr, tokens, flags)) {
     case kChainPersistent: return "gemv_k256c_kernel";
@@ -419,6 +601,52 @@ int vptq_quant_gemv_chain_plan(const VptqLayerDesc* descs, int n, int flags, int
   return VPTQ_OK;
 }
 
+// (chain_decide with the workspace ..._workspace_bytes_for asks for assumed, as vptq_quant_gemv_chain_kernel_name does)
+int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes) {
+  if (!descs || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / buf is NULL");
+  buf[0] = 0;
+  if (n < 1 || n > VPTQ_CHAIN_MAX) return fail(VPTQ_E_SHAPE, "n %d outside [1, %d]", n, VPTQ_CHAIN_MAX);
+  if (tokens < 1 || tokens > VPTQ_GEMV_MAX_TOKENS) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d]", tokens, VPTQ_GEMV_MAX_TOKENS);
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_layer(&descs[i]);
+    if (rc) return rc;
+  }
+  const ChainDecision D = chain_decide(descs, n, nullptr, tokens, flags, true, nullptr, 0);
+  const bool dependent = D.dependent;
+  flags = D.flags;
+  const int lflags = flags & ~VPTQ_GEMV_CHAIN_DEPENDENT;
+  Text t = {buf, bytes, 0, true};
+  const VptqLayerDesc* run = D.absorbed ? D.run.data() : descs;   // what the persistent launch is given
+  const ChainRoute route = D.route;
+  if (route == kChainGrouped) {
+    char one[2048];
+    const int rc = vptq_quant_gemv_grouped_instance(descs, n, tokens, lflags & ~VPTQ_GEMV_FORCE_MFMA, one, sizeof(one));
+    if (rc) return rc;
+    t.add("grouped: %s", one);
+    return text_done(t);
+  }
+  if (route == kChainPerLayer) {
+    t.add("per-layer: ");
+    for (int i = 0; i < n; ++i) {
+      if (i) t.add(" | ");
+      const int rc = add_one(t, descs[i], tokens, lflags & ~VPTQ_GEMV_FORCE_MFMA);
+      if (rc) return rc;
+    }
+    return text_done(t);
+  }
+  static const char* const mode_text[3] = {"folded", "exact", "selective"};
+  for (int i0 = 0; i0 < n; i0 += 32) {   // one persistent launch per <= 32 layers
+    const int m = n - i0 < 32 ? n - i0 : 32;
+    const int mode = vptq::gemv_k256c_mode(lflags, dependent);
+    if (mode < 0 || mode > 2) return fail(VPTQ_E_UNSUPPORTED, "instance: no gemv_k256c instantiation for flags 0x%x", flags);
+    t.add("%sgemv_k256c dt=%s dep=%d mode=%s layers=%d sweeps=", i0 ? " | " : "", dt_text(descs[0].dtype), (int)dependent, mode_text[mode], m);
+    for (int i = 0; i < m; ++i) t.add("%s%d", i ? "," : "", vptq::gemv_k256c_sweeps(run[i0 + i]));
+    t.add(" perm=");
+    for (int i = 0; i < m; ++i) t.add("%s%d", i ? "," : "", descs[i0 + i].perm ? 1 : 0);
+  }
+  return text_done(t);
+}
+
 int vptq_quant_gemv_chain(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
                           int tokens, int flags, void* workspace, size_t workspace_bytes, void* stream) {
   if (!descs || !x || !y) return fail(VPTQ_E_NULL, "descs / x / y is NULL");
@@ -430,60 +658,29 @@ int vptq_quant_gemv_chain(const VptqLayerDesc* descs, int n, const void* const* 
     if (rc) return rc;
     if (!x[i] || !y[i]) return fail(VPTQ_E_NULL, "x[%d] / y[%d] is NULL", i, i);
   }
-  const bool dependent = (flags & VPTQ_GEMV_CHAIN_DEPENDENT) != 0;
-  flags = drop_redundant_selective(flags);
-  // SELECTIVE: the thresholds live in the first chain_thr_bytes of the workspace; without it (or for a dependent list) the
-  // call takes the reference's roundings everywhere
+  const ChainDecision D = chain_decide(descs, n, x, tokens, flags, false, workspace, workspace_bytes);
+  const bool dependent = D.dependent;
+  flags = D.flags;
   char* thr_ws = nullptr;
-  {
-    const size_t tb = chain_sel_bytes(descs, n, flags);
-    if (flags & VPTQ_GEMV_SELECTIVE) {
-      if (tb > 0 && workspace && workspace_bytes >= tb && (((uintptr_t)workspace) & 255) == 0) {
-        thr_ws = (char*)workspace;
-        workspace = (char*)workspace + tb;
-        workspace_bytes -= tb;
-      } else {
-        flags = selective_as_exact(flags);
-      }
-    }
+  if (D.sel_bytes) {
+    thr_ws = (char*)workspace;
+    workspace = (char*)workspace + D.sel_bytes;
+    workspace_bytes -= D.sel_bytes;
   }
   const int lflags = flags & ~VPTQ_GEMV_CHAIN_DEPENDENT;
   hipStream_t st = (hipStream_t)stream;
-  // Layers with an input permutation in an independent list: with enough workspace for x[perm] the list still runs in the
-  // persistent launch - on (x[perm], scale_permuted, bias_permuted), gathered by one small launch in front of it.
-  if (!dependent && tokens == 1) {
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) need += vptq::gemv_k256c_perm_bytes(descs[i]);
-    if (need > 0 && workspace && workspace_bytes >= need && (((uintptr_t)workspace) & 255) == 0) {
-      std::vector<VptqLayerDesc> dd(descs, descs + n);
-      std::vector<const void*> xx(x, x + n);
-      std::vector<void*> xp(n, nullptr);
-      char* w = (char*)workspace;
-      bool ok = true;
-      for (int i = 0; i < n; ++i) {
-        if (!dd[i].perm) continue;
-        ok = ok && dd[i].scale_permuted && dd[i].bias_permuted && (dd[i].in_features % 8) == 0 && (((uintptr_t)dd[i].perm) & 15) == 0;
-        xp[i] = w;
-        xx[i] = w;
-        w += vptq::gemv_k256c_perm_bytes(dd[i]);
-        dd[i].weight_scale = dd[i].scale_permuted;
-        dd[i].weight_bias = dd[i].bias_permuted;
-        dd[i].perm = nullptr; dd[i].inv_perm = nullptr; dd[i].scale_permuted = nullptr; dd[i].bias_permuted = nullptr;
-      }
-      if (ok && chain_route(dd.data(), n, xx.data(), tokens, flags) == kChainPersistent) {
-        for (int i0 = 0; i0 < n; i0 += 32) {
-          const int m = n - i0 < 32 ? n - i0 : 32;
-          hipError_t e = vptq::launch_permute_x(descs + i0, m, x + i0, xp.data() + i0, st);
-          if (e != hipSuccess) return hip_fail(e, "permute_x launch");
-          e = vptq::launch_gemv_k256c(dd.data() + i0, m, xx.data() + i0, y + i0, lflags, false, (uint32_t*)thr_ws, st);
-          if (thr_ws) thr_ws += vptq::gemv_k256c_selective_bytes(dd.data() + i0, m);
-          if (e != hipSuccess) return hip_fail(e, "gemv_k256c launch");
-        }
-        return VPTQ_OK;
-      }
+  if (D.absorbed) {
+    for (int i0 = 0; i0 < n; i0 += 32) {
+      const int m = n - i0 < 32 ? n - i0 : 32;
+      hipError_t e = vptq::launch_permute_x(descs + i0, m, x + i0, D.xp.data() + i0, st);
+      if (e != hipSuccess) return hip_fail(e, "permute_x launch");
+      e = vptq::launch_gemv_k256c(D.run.data() + i0, m, D.xx.data() + i0, y + i0, lflags, false, (uint32_t*)thr_ws, st);
+      if (thr_ws) thr_ws += vptq::gemv_k256c_selective_bytes(D.run.data() + i0, m);
+      if (e != hipSuccess) return hip_fail(e, "gemv_k256c launch");
     }
+    return VPTQ_OK;
   }
-  const ChainRoute route = chain_route(descs, n, x, tokens, flags);
+  const ChainRoute route = D.route;
   if (route == kChainGrouped)   // independent layers, one launch (it serves members it has no kernel for one by one)
     return vptq_quant_gemv_grouped(descs, n, x, y, tokens, lflags & ~VPTQ_GEMV_FORCE_MFMA, stream);
   if (route == kChainPerLayer) {

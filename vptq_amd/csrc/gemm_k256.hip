@@ -294,8 +294,27 @@ bool gemm_k256_eligible(const VptqLayerDesc& d, int tokens, int flags) {
   return tokens >= 1 && tokens <= 16;
 }
 
+// The launch shape: row groups, grid, and the passes (NRG = 4, 2, 1: the instantiations of gemm_k256_pass) the busiest
+// workgroup - workgroup 0 - runs, as the kernel's pass loop takes them.
+GemmK256Decision gemm_k256_decide(const VptqLayerDesc& d) {
+  GemmK256Decision D = {};
+  D.f16 = d.dtype == VPTQ_DTYPE_F16;
+  D.perm = d.perm != nullptr;
+  D.n_groups = (d.num_indices + kGRows - 1) / kGRows;
+  const int ncu = device_cus();
+  D.grid = D.n_groups < ncu ? D.n_groups : ncu;
+  if (D.grid < 1) return D;
+  int left = (D.n_groups + D.grid - 1) / D.grid;   // (gemm_k256_kernel, blockIdx.x = 0)
+  if (left >= 4) { D.passes |= 4; left %= 4; }
+  if (left >= 2) { D.passes |= 2; left -= 2; }
+  if (left >= 1) D.passes |= 1;
+  return D;
+}
+
 hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
                             hipStream_t st) {
+  const GemmK256Decision D = gemm_k256_decide(d);
+  if (D.grid < 1) return hipErrorInvalidValue;
   GemmK256Params P = {};
   P.idx = (const uint32_t*)d.indices;
   P.cent = (const uint32_t*)d.centroids;
@@ -308,16 +327,10 @@ hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int 
   P.perm = d.perm;
   P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
   P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
-  P.n_groups = (d.num_indices + kGRows - 1) / kGRows;
+  P.n_groups = D.n_groups;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  static std::atomic<int> cus[64];
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  const int ncu = cus[dev].load();
-  const int grid = P.n_groups < ncu ? P.n_groups : ncu;
+  const int grid = D.grid;
   auto go = [&](auto kern, std::atomic<bool>& done) -> hipError_t {
     if (!done) {
       if (hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kGLds); e != hipSuccess) return e;
@@ -327,9 +340,9 @@ hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int 
     return hipGetLastError();
   };
   static std::atomic<bool> attr_set[4][64];
-  if (d.dtype == VPTQ_DTYPE_F16)
-    return d.perm ? go(gemm_k256_kernel<F16, true>, attr_set[0][dev]) : go(gemm_k256_kernel<F16, false>, attr_set[1][dev]);
-  return d.perm ? go(gemm_k256_kernel<BF16, true>, attr_set[2][dev]) : go(gemm_k256_kernel<BF16, false>, attr_set[3][dev]);
+  if (D.f16)
+    return D.perm ? go(gemm_k256_kernel<F16, true>, attr_set[0][dev]) : go(gemm_k256_kernel<F16, false>, attr_set[1][dev]);
+  return D.perm ? go(gemm_k256_kernel<BF16, true>, attr_set[2][dev]) : go(gemm_k256_kernel<BF16, false>, attr_set[3][dev]);
 }
 
 }  // namespace vptq

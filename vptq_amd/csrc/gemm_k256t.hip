@@ -435,10 +435,26 @@ static hipError_t launch_bt(const VptqLayerDesc& d, const GemmK256TParams& P, co
   return hipGetLastError();
 }
 
+// The launch shape: sweeps of 2048 columns (pre-pass grid.y, the main kernel's column loop), row groups of 4 vector-rows,
+// one workgroup per CU at most
+GemmK256TDecision gemm_k256t_decide(const VptqLayerDesc& d) {
+  GemmK256TDecision D = {};
+  D.f16 = d.dtype == VPTQ_DTYPE_F16;
+  D.perm = d.perm != nullptr;   // (the pre-pass reads x through it)
+  D.n_groups = (d.num_indices + kBTRows - 1) / kBTRows;
+  D.n_sweeps = (d.group_size + kBTSweepCols - 1) / kBTSweepCols;
+  const int ncu = device_cus();
+  D.grid = D.n_groups < ncu ? D.n_groups : ncu;
+  D.groups_per_wg = D.grid > 0 ? (D.n_groups + D.grid - 1) / D.grid : 0;
+  return D;
+}
+
 // 1 ... 16 tokens; ws = gemm_k256t_workspace_bytes(d) bytes, 16-byte aligned
 hipError_t launch_gemm_k256t(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, void* ws,
                              hipStream_t st) {
   if (tokens < 1 || tokens > kBTTokens || !ws || (((uintptr_t)ws) & 15)) return hipErrorInvalidValue;
+  const GemmK256TDecision D = gemm_k256t_decide(d);
+  if (D.grid < 1) return hipErrorInvalidValue;
   GemmK256TParams P = {};
   P.idx = (const uint32_t*)d.indices;
   P.cent = (const uint32_t*)d.centroids;
@@ -449,18 +465,9 @@ hipError_t launch_gemm_k256t(const VptqLayerDesc& d, const void* x, void* y, int
   P.bias = (const uint16_t*)d.bias;
   P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
   P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
-  P.n_groups = (d.num_indices + kBTRows - 1) / kBTRows;
-  P.n_sweeps = (d.group_size + kBTSweepCols - 1) / kBTSweepCols;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  static std::atomic<int> cus[64];
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  const int ncu = cus[dev].load();
-  const int grid = P.n_groups < ncu ? P.n_groups : ncu;
-  return d.dtype == VPTQ_DTYPE_F16 ? launch_bt<F16>(d, P, x, ws, grid, st) : launch_bt<BF16>(d, P, x, ws, grid, st);
+  P.n_groups = D.n_groups;
+  P.n_sweeps = D.n_sweeps;
+  return D.f16 ? launch_bt<F16>(d, P, x, ws, D.grid, st) : launch_bt<BF16>(d, P, x, ws, D.grid, st);
 }
 
 }  // namespace vptq

@@ -36,6 +36,8 @@
 //  * two entry points share the body: gemv_k256_kernel (layer = blockIdx.y, grouped
 //    launches, 2-4 tokens) and gemv_k256_kernel_1 (one layer, one token: the arguments the
 //    first loads need are preloaded into SGPRs at wave launch).
+#include <cstdio>
+
 #include "common.h"
 #include "kernels.h"
 #include "k256.h"
@@ -379,7 +381,7 @@ static int pick_rows(int n_rows_total, int tok, bool f16) {
 }
 
 template <typename DT, int ROWS, int TOK, int SW, bool PERM, bool FAST>
-static hipError_t launch_inst(const K256Params& P, int grid, hipStream_t st) {
+static hipError_t launch_inst(const K256Params& P, int grid, int entry, hipStream_t st) {
   constexpr int lds = kScratchOff + kWaves * (TOK * ROWS * 8 + TOK) * 4;
   // > 64 KiB of dynamic LDS must be enabled once per device (benign race: idempotent)
   int dev = 0;
@@ -391,7 +393,8 @@ static hipError_t launch_inst(const K256Params& P, int grid, hipStream_t st) {
     return e;
   };
   if constexpr (TOK == 1) {
-    if (P.n_layers == 1) {  // the preloaded-argument entry point
+    if (entry == 1) {  // the preloaded-argument entry point
+      if (P.n_layers != 1) return hipErrorInvalidValue;
       auto kern = gemv_k256_kernel_1<DT, ROWS, SW, PERM, FAST>;
       static std::atomic<bool> attr_set[64];
       if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
@@ -401,6 +404,7 @@ static hipError_t launch_inst(const K256Params& P, int grid, hipStream_t st) {
       return hipGetLastError();
     }
   }
+  if (entry != 0) return hipErrorInvalidValue;
   auto kern = gemv_k256_kernel<DT, ROWS, TOK, SW, PERM, FAST>;
   static std::atomic<bool> attr_set[64];
   if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
@@ -409,25 +413,25 @@ static hipError_t launch_inst(const K256Params& P, int grid, hipStream_t st) {
 }
 
 template <typename DT, int ROWS, int TOK, bool FAST>
-static hipError_t launch_shape(const K256Params& P, int grid, int sw, bool perm, hipStream_t st) {
+static hipError_t launch_shape(const K256Params& P, int grid, int sw, bool perm, int entry, hipStream_t st) {
   if (sw == 1) {
-    return perm ? launch_inst<DT, ROWS, TOK, 1, true, FAST>(P, grid, st)
-                : launch_inst<DT, ROWS, TOK, 1, false, FAST>(P, grid, st);
+    return perm ? launch_inst<DT, ROWS, TOK, 1, true, FAST>(P, grid, entry, st)
+                : launch_inst<DT, ROWS, TOK, 1, false, FAST>(P, grid, entry, st);
   }
   if constexpr (TOK == 4) {
     return hipErrorInvalidValue;  // never chosen (launch_gemv_k256): two sweeps x 4 tokens spill
   } else {
-    return perm ? launch_inst<DT, ROWS, TOK, 2, true, FAST>(P, grid, st)
-                : launch_inst<DT, ROWS, TOK, 2, false, FAST>(P, grid, st);
+    return perm ? launch_inst<DT, ROWS, TOK, 2, true, FAST>(P, grid, entry, st)
+                : launch_inst<DT, ROWS, TOK, 2, false, FAST>(P, grid, entry, st);
   }
 }
 
 #define K256_CASE(DT, R, T, F) \
-  if (rows == R && tok == T && fast == F) return launch_shape<DT, R, T, F>(P, grid, sw, perm, st);
+  if (rows == R && tok == T && fast == F) return launch_shape<DT, R, T, F>(P, grid, sw, perm, entry, st);
 
 template <typename DT, bool ALLOW_FAST>
 static hipError_t dispatch(const K256Params& P, int grid, int rows, int tok, bool fast, int sw,
-                           bool perm, hipStream_t st) {
+                           bool perm, int entry, hipStream_t st) {
   K256_CASE(DT, 1, 1, false) K256_CASE(DT, 1, 2, false) K256_CASE(DT, 1, 4, false)
   if constexpr (ALLOW_FAST) {
     K256_CASE(DT, 2, 1, false)
@@ -558,51 +562,121 @@ static int best_split(const VptqLayerDesc* descs, int n, K256Choice c, int* part
   return best_parts;
 }
 
-static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, int flags,
-                                       hipStream_t st, bool may_split);
+// ---- decide, then launch.  One call = one launch, or (one token, 2 - 4 layers of the persistent kernel) the cheapest split
+// into launches (best_split).  k256_for_each_launch walks the launches of a call; k256_decide says what one launch is: the
+// kernel, the instantiation's template arguments and the launch shape.  launch_gemv_k256 launches exactly that and
+// gemv_k256_instance prints it, so the two cannot disagree.
+struct K256Decision {
+  K256Choice choice;
+  bool f16, perm;
+  int tok;        // token slots of the instantiation: 1, 2 or 4
+  int max_cols;
+  int rows, sw;   // VALU kernel: vector-rows per workgroup, sweeps per iteration
+  int entry;      // VALU kernel: 1 = gemv_k256_kernel_1 (one layer, one token), 0 = the grouped entry
+  K256MDecision m;   // the persistent MFMA kernel's (choice.mfma)
+};
 
-hipError_t launch_gemv_k256(const VptqLayerDesc* descs, int n, const void* const* x,
-                            void* const* y, int tokens, int flags, hipStream_t st) {
-  return launch_gemv_k256_one(descs, n, x, y, tokens, flags, st, true);
+static K256Decision k256_decide(const VptqLayerDesc* descs, int n, int tokens, int flags) {
+  K256Decision D = {};
+  D.choice = choose_kernel(descs, n, tokens, flags);
+  D.tok = tokens > 2 ? 4 : tokens;
+  D.f16 = descs[0].dtype == VPTQ_DTYPE_F16;
+  int total_rows = 0, n_rows[kMaxGroup];
+  for (int i = 0; i < n; ++i) {
+    total_rows += descs[i].num_indices;
+    n_rows[i] = descs[i].num_indices;
+    D.max_cols = descs[i].group_size > D.max_cols ? descs[i].group_size : D.max_cols;
+    D.perm = D.perm || descs[i].perm != nullptr;
+  }
+  // all layers of a group share one instantiation: widest column count decides the
+  // sweeps per iteration, any permutation selects the gather variant (grouped layers
+  // must agree on it, checked by the caller)
+  if (D.choice.mfma) {
+    D.rows = kMRows;
+    D.m = gemv_k256m_decide(n_rows, n, D.tok, D.f16, D.choice.fast, D.max_cols, D.perm, D.choice.sel);
+  } else {
+    D.rows = pick_rows(total_rows, D.tok, D.f16);
+    // two sweeps per iteration keep more loads in flight, but the 4-token instantiation
+    // only stays spill-free with one
+    D.sw = (D.max_cols > kSweepCols && D.tok != 4) ? 2 : 1;
+    D.entry = D.tok == 1 && n == 1 ? 1 : 0;
+  }
+  return D;
 }
 
-static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, int flags,
-                                       hipStream_t st, bool may_split) {
+// fn(descs of the launch, their count, their positions in the call's list, flags of the launch) per launch of the call
+template <typename F>
+static hipError_t k256_for_each_launch(const VptqLayerDesc* descs, int n, int tokens, int flags, F&& fn) {
   if (n < 1 || n > kMaxGroup) return hipErrorInvalidValue;
-  K256Params P;
-  P.n_layers = n;
-  P.tokens = tokens | ((flags & VPTQ_GEMV_OUT_F32) ? kOutF32Bit : 0);
-  int total_rows = 0;
-  for (int i = 0; i < n; ++i) total_rows += descs[i].num_indices;
-  const int tok = tokens > 2 ? 4 : tokens;
-  const bool f16 = descs[0].dtype == VPTQ_DTYPE_F16;
-  const K256Choice choice = choose_kernel(descs, n, tokens, flags);
-  const bool mfma = choice.mfma, fast = choice.fast;
-  if (may_split && tokens == 1) {
-    int part[4];
-    const int parts = best_split(descs, n, choice, part);
+  if (tokens == 1) {
+    int part[kMaxGroup];   // (best_split clears n entries)
+    const int parts = best_split(descs, n, choose_kernel(descs, n, tokens, flags), part);
     if (parts > 1) {
       // the same kernel and arithmetic as the group would have run (a part alone might fall under the row-group threshold)
       const int sub_flags = flags | VPTQ_GEMV_FORCE_MFMA;
       for (int q = 0; q < parts; ++q) {
         VptqLayerDesc d[4];
-        const void* xs[4];
-        void* ys[4];
-        int m = 0;
+        int at[4], m = 0;
         for (int i = 0; i < n; ++i)
-          if (part[i] == q) { d[m] = descs[i]; xs[m] = x[i]; ys[m] = y[i]; ++m; }
-        if (hipError_t e = launch_gemv_k256_one(d, m, xs, ys, tokens, sub_flags, st, false); e != hipSuccess) return e;
+          if (part[i] == q) { d[m] = descs[i]; at[m] = i; ++m; }
+        if (hipError_t e = fn(d, m, at, sub_flags); e != hipSuccess) return e;
       }
       return hipSuccess;
     }
   }
-  int maxG = 0;
-  bool perm = false;
-  for (int i = 0; i < n; ++i) {
-    maxG = descs[i].group_size > maxG ? descs[i].group_size : maxG;
-    perm = perm || descs[i].perm != nullptr;
-  }
-  const int rows = mfma ? kMRows : pick_rows(total_rows, tok, f16);
+  int at[kMaxGroup];
+  for (int i = 0; i < n; ++i) at[i] = i;
+  return fn(descs, n, at, flags);
+}
+
+static const char* dt_name(bool f16) { return f16 ? "f16" : "bf16"; }
+
+// the launches vptq_quant_gemv / _grouped make for these layers, one instance string per launch, joined by " | "
+int gemv_k256_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes) {
+  size_t used = 0;
+  bool fits = true;
+  const hipError_t e = k256_for_each_launch(descs, n, tokens, flags, [&](const VptqLayerDesc* d, int m, const int*, int fl) {
+    const K256Decision D = k256_decide(d, m, tokens, fl);
+    char one[192];
+    if (D.choice.mfma) {
+      if (!D.m.ok) return hipErrorInvalidValue;
+      snprintf(one, sizeof(one), "gemv_k256m dt=%s ns=%d nst=%d perm=%d fast=%d tok=%d sb=%d entry=%d slots=%d units=%d sel=%d",
+               dt_name(D.m.f16), D.m.ns, D.m.nst, (int)D.m.perm, (int)D.m.fast, D.m.tok, (int)D.m.sb, D.m.entry, D.m.slots, D.m.units,
+               (int)D.m.selective);
+    } else {
+      snprintf(one, sizeof(one), "gemv_k256 dt=%s rows=%d tok=%d sw=%d perm=%d fast=%d entry=%d", dt_name(D.f16), D.rows, D.tok, D.sw,
+               (int)D.perm, (int)D.choice.fast, D.entry);
+    }
+    const int w = snprintf(buf + used, bytes - used, "%s%s", used ? " | " : "", one);
+    if (w < 0 || (size_t)w >= bytes - used) { fits = false; return hipErrorInvalidValue; }
+    used += (size_t)w;
+    return hipSuccess;
+  });
+  return e == hipSuccess ? 0 : fits ? -1 : -2;
+}
+
+static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, int flags,
+                                       hipStream_t st);
+
+hipError_t launch_gemv_k256(const VptqLayerDesc* descs, int n, const void* const* x,
+                            void* const* y, int tokens, int flags, hipStream_t st) {
+  return k256_for_each_launch(descs, n, tokens, flags, [&](const VptqLayerDesc* d, int m, const int* at, int fl) {
+    const void* xs[kMaxGroup];
+    void* ys[kMaxGroup];
+    for (int i = 0; i < m; ++i) { xs[i] = x[at[i]]; ys[i] = y[at[i]]; }
+    return launch_gemv_k256_one(d, m, xs, ys, tokens, fl, st);
+  });
+}
+
+static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, int flags,
+                                       hipStream_t st) {
+  if (n < 1 || n > kMaxGroup) return hipErrorInvalidValue;
+  K256Params P;
+  P.n_layers = n;
+  P.tokens = tokens | ((flags & VPTQ_GEMV_OUT_F32) ? kOutF32Bit : 0);
+  const K256Decision D = k256_decide(descs, n, tokens, flags);
+  const bool mfma = D.choice.mfma;
+  const int rows = D.rows;
   const int wg_threads = mfma ? 1024 : kThreads;
   int grid = 0;
   for (int i = 0; i < n; ++i) {
@@ -637,15 +711,9 @@ static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const 
     Ly.slots = 0;
     grid = n_wg > grid ? n_wg : grid;  // grid.x; grid.y = layer
   }
-  // all layers of a group share one instantiation: widest column count decides the
-  // sweeps per iteration, any permutation selects the gather variant (grouped layers
-  // must agree on it, checked by the caller)
-  // two sweeps per iteration keep more loads in flight, but the 4-token instantiation
-  // only stays spill-free with one
-  if (mfma) return launch_gemv_k256m(P, tok, f16, fast, maxG, perm, st, choice.sel);
-  const int sw = (maxG > kSweepCols && tok != 4) ? 2 : 1;
-  return f16 ? dispatch<F16, true>(P, grid, rows, tok, fast, sw, perm, st)
-             : dispatch<BF16, false>(P, grid, rows, tok, false, sw, perm, st);
+  if (mfma) return launch_gemv_k256m(P, D.m, st);
+  return D.f16 ? dispatch<F16, true>(P, grid, rows, D.tok, D.choice.fast, D.sw, D.perm, D.entry, st)
+               : dispatch<BF16, false>(P, grid, rows, D.tok, false, D.sw, D.perm, D.entry, st);
 }
 
 }  // namespace vptq

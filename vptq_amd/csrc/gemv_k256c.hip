@@ -1379,9 +1379,11 @@ bool gemv_k256c_eligible(const VptqLayerDesc& d, int tokens) {
 constexpr int kCMinSteps = VPTQ_K256C_MIN_STEPS;
 constexpr int kCMaxSteps = 4 * kCMinSteps;
 static int c_groups(const VptqLayerDesc& d) { return (d.num_indices + kCRows - 1) / kCRows; }
+// sweeps of 2048 columns of one layer: the header field every wave's column loop runs to
+int gemv_k256c_sweeps(const VptqLayerDesc& d) { return (d.group_size + kCSweepCols - 1) / kCSweepCols; }
 // visit = sweeps per visit a block is sized for (0: the layer's row groups spread over all workgroups)
 static int c_rows_per_wg(const VptqLayerDesc& d, int cus, int visit) {
-  const int ng = c_groups(d), ns = (d.group_size + kCSweepCols - 1) / kCSweepCols;
+  const int ng = c_groups(d), ns = gemv_k256c_sweeps(d);
   int rpw = (ng + cus - 1) / cus;
   if (visit > 0) {
     const int want = (visit + ns - 1) / ns;
@@ -1398,24 +1400,12 @@ static long long c_blocks(const VptqLayerDesc* descs, int n, int cus, int visit)
   return total;
 }
 
-static int c_device_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0
-                   ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // workgroups > 0: that many (a plan query); 0: what a launch uses
 static int c_workgroups(bool dependent, int workgroups = 0) {
   static std::atomic<int> forced_wgs{-1};  // VPTQ_K256C_WGS: tuning override of the workgroup count
   if (forced_wgs < 0) { const char* e = vptq::tune_env("VPTQ_K256C_WGS"); forced_wgs = e ? atoi(e) : 0; }
   const int fw = forced_wgs.load();
-  const int cus = workgroups > 0 ? workgroups : fw > 0 ? fw : c_device_cus();
+  const int cus = workgroups > 0 ? workgroups : fw > 0 ? fw : device_cus();
   return dependent && cus > kCFlagStride ? kCFlagStride : cus;
 }
 
@@ -1456,7 +1446,7 @@ static hipError_t launch_c(const K256CParams& P, int grid, hipStream_t st) {
     if (!resident[dev]) {
       int per_cu = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kCThreads, lds) != hipSuccess) per_cu = 0;
-      resident[dev] = per_cu > 0 ? per_cu * c_device_cus() : -1;
+      resident[dev] = per_cu > 0 ? per_cu * device_cus() : -1;
     }
     if (resident[dev] < grid) return hipErrorCooperativeLaunchTooLarge;
   }
@@ -1547,7 +1537,7 @@ static hipError_t c_plan(const VptqLayerDesc* descs, int n, bool dependent, int 
   long long first = 0;   // running total of blocks: the layers continue each other's round robin
   for (int i = 0; i < n; ++i) {
     const int rpw = c_rows_per_wg(descs[i], cus, visit);
-    const int ng = c_groups(descs[i]), ns = (descs[i].group_size + kCSweepCols - 1) / kCSweepCols;
+    const int ng = c_groups(descs[i]), ns = gemv_k256c_sweeps(descs[i]);
     if (rpw > 0xffff || ng > 0xffffff || ns > 0xff) return hipErrorInvalidValue;
     first_wg[i] = (int)(first % grid);
     rows_per_wg[i] = rpw;
@@ -1561,6 +1551,14 @@ static hipError_t c_plan(const VptqLayerDesc* descs, int n, bool dependent, int 
 hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
                            int* first_wg, int* rows_per_wg) {
   return c_plan(descs, n, dependent, c_workgroups(dependent, workgroups), visit, grid, first_wg, rows_per_wg);
+}
+
+// MODE of the instantiation gemv_k256c_kernel<DT, DEP, MODE> a launch with these flags takes: 0 folded, 1 the reference's
+// roundings, 2 selective; -1: none (the caller routes such a list elsewhere)
+int gemv_k256c_mode(int flags, bool dependent) {
+  if ((flags & VPTQ_GEMV_SELECTIVE) && !(flags & VPTQ_GEMV_EXACT)) return !dependent && VPTQ_K256C_PROF == 0 ? kCModeSel : -1;
+  if (flags & VPTQ_GEMV_EXACT) return !dependent && VPTQ_K256C_PROF < 2 ? kCModeExact : -1;
+  return kCModeFolded;
 }
 
 // n <= kMaxGroup layers, all gemv_k256c_eligible and of one dtype; sync = kCFlagStride flags per
@@ -1592,16 +1590,18 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
     Ly.G = d.group_size;
     Ly.O = d.out_features;
     Ly.row_words = d.row_words;
-    const int ng = c_groups(d), ns = (d.group_size + kCSweepCols - 1) / kCSweepCols;
+    const int ng = c_groups(d), ns = gemv_k256c_sweeps(d);
     Ly.wgs = first_wg[i];
     Ly.rpw = rpws[i];
     P.head[i][0] = (uint32_t)Ly.wgs | ((uint32_t)Ly.rpw << 16);
     P.head[i][1] = (uint32_t)ng | ((uint32_t)ns << 24);
   }
   const bool f16 = descs[0].dtype == VPTQ_DTYPE_F16;
-  if ((flags & VPTQ_GEMV_SELECTIVE) && !(flags & VPTQ_GEMV_EXACT)) {
+  const int mode = gemv_k256c_mode(flags, dependent);
+  if (mode < 0) return hipErrorInvalidValue;   // (the caller routes those layer by layer / asks for EXACT)
+  if (mode == kCModeSel) {
     // sync = n thresholds, written by the launch in front of the chain launch (same stream)
-    if (dependent || !sync) return hipErrorInvalidValue;   // (the caller routes those layer by layer / asks for EXACT)
+    if (!sync) return hipErrorInvalidValue;
 #if VPTQ_K256C_PROF == 0
     CHotArgs H = {};
     size_t off = ((size_t)n * 16 + 255) / 256 * 256;
@@ -1622,8 +1622,7 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
     return hipErrorInvalidValue;
 #endif
   }
-  if (flags & VPTQ_GEMV_EXACT) {
-    if (dependent) return hipErrorInvalidValue;   // (the caller routes those layer by layer)
+  if (mode == kCModeExact) {
 #if VPTQ_K256C_PROF < 2
     return f16 ? launch_c<F16, false, kCModeExact>(P, grid, st) : launch_c<BF16, false, kCModeExact>(P, grid, st);
 #else

@@ -1087,18 +1087,6 @@ __global__ __launch_bounds__(kMThreads) void gemv_k256m_kernel_1(
 }
 
 // ---- host side -------------------------------------------------------------------
-static int device_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0
-                   ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // LDS bytes before the partial-sum slots: image + per token the staged activations (0 columns:
 // unstaged) and the per-wave sum b * x + slot counters
 // sb: scale and bias planes behind the activations (bf16 exact form)
@@ -1108,10 +1096,15 @@ static int lds_fixed_bytes(int staged_cols, int tok, bool sb) {
 }
 
 template <typename DT, int NS, int NST, bool PERM, bool FAST, int TOK>
-static hipError_t launch_m(const K256Params& P, int gx, int max_cols, hipStream_t st) {
-  const int fixed = lds_fixed_bytes(NST > 0 ? max_cols : 0, TOK, !FAST && (std::is_same<DT, BF16>::value || NS > 5 || TOK > 1 || VPTQ_K256M_SB_ALL));
-  const int slots = P.layer[0].slots & 0xff;  // set by launch_gemv_k256m (bit 8: selective roundings)
-  if (slots < 1 || slots > kMMaxSlots) return hipErrorInvalidValue;
+static hipError_t launch_m(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  // this instantiation is the one the decision names (kSB: the kernel's own rule, gemv_k256m_body)
+  constexpr bool kSB = !FAST && (std::is_same<DT, BF16>::value || NS > 5 || TOK > 1 || VPTQ_K256M_SB_ALL);
+  if (!D.ok || D.f16 != std::is_same<DT, F16>::value || D.ns != NS || D.nst != NST || D.perm != PERM || D.fast != FAST ||
+      D.tok != TOK || D.sb != kSB)
+    return hipErrorInvalidValue;
+  const int fixed = lds_fixed_bytes(NST > 0 ? D.max_cols : 0, TOK, kSB);
+  const int slots = D.slots;
+  if (slots < 1 || slots > kMMaxSlots || (P.layer[0].slots & 0xff) != slots) return hipErrorInvalidValue;
   const int lds = fixed + slots * kMRedSlot * TOK;
   if (lds > kMMaxLds) return hipErrorInvalidValue;
   int dev = 0;
@@ -1123,37 +1116,38 @@ static hipError_t launch_m(const K256Params& P, int gx, int max_cols, hipStream_
     return e;
   };
   if constexpr (TOK == 1) {
-    if (P.n_layers == 1) {  // the preloaded-argument entry point
+    if (D.entry == 1) {  // the preloaded-argument entry point
+      if (P.n_layers != 1) return hipErrorInvalidValue;
       auto kern = gemv_k256m_kernel_1<DT, NS, NST, PERM, FAST>;
       static std::atomic<bool> attr_set[64];
       if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
       const K256Layer& L0 = P.layer[0];
-      hipLaunchKernelGGL(kern, dim3(gx, 1), dim3(kMThreads), lds, st, L0.cent, L0.rcent, L0.x, L0.scale,
+      hipLaunchKernelGGL(kern, dim3(D.gx, 1), dim3(kMThreads), lds, st, L0.cent, L0.rcent, L0.x, L0.scale,
                          L0.N, L0.G, L0.O, L0.row_words, L0.wgs, L0.slots, P);
       return hipGetLastError();
     }
   }
+  if (D.entry != 0) return hipErrorInvalidValue;
   auto kern = gemv_k256m_kernel<DT, NS, NST, PERM, FAST, TOK>;
   static std::atomic<bool> attr_set[64];
   if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(gx, P.n_layers), dim3(kMThreads), lds, st, P);
+  hipLaunchKernelGGL(kern, dim3(D.gx, P.n_layers), dim3(kMThreads), lds, st, P);
   return hipGetLastError();
 }
 
+// the instantiation the decision names (gemv_k256m_decide: ns, nst, perm)
 template <typename DT, bool FAST, int TOK>
-static hipError_t launch_m_shape(const K256Params& P, int gx, bool perm, int max_cols,
-                                 hipStream_t st) {
-  if (max_cols > kMMaxCols) {
+static hipError_t launch_m_shape(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  if (D.nst == 0) {
     // wider than the LDS can stage: column blocks of 2 sweeps, scale and x through the queue
     if constexpr (FAST && TOK == 1) {
-      if (!perm) return launch_m<DT, 2, 0, false, true, 1>(P, gx, max_cols, st);
+      if (!D.perm && D.ns == 2) return launch_m<DT, 2, 0, false, true, 1>(P, D, st);
     }
     return hipErrorInvalidValue;
   }
-  const int ns = (max_cols + kMSweepCols - 1) / kMSweepCols;
-#define K256M_CASE(S, N)                                                               \
-  if (ns == S) return perm ? launch_m<DT, S, N, true, FAST, TOK>(P, gx, max_cols, st)  \
-                           : launch_m<DT, S, N, false, FAST, TOK>(P, gx, max_cols, st);
+#define K256M_CASE(S, N)                                                                             \
+  if (D.ns == S && D.nst == N) return D.perm ? launch_m<DT, S, N, true, FAST, TOK>(P, D, st)         \
+                                             : launch_m<DT, S, N, false, FAST, TOK>(P, D, st);
   K256M_CASE(1, 1) K256M_CASE(2, 1) K256M_CASE(3, 1) K256M_CASE(4, 1)
   K256M_CASE(5, 2) K256M_CASE(6, 2) K256M_CASE(7, 2)
 #undef K256M_CASE
@@ -1173,53 +1167,53 @@ static int lds_slots(int tok, int max_cols, bool sb) {
 #define VPTQ_K256M_PART 0
 #endif
 #define K256M_PART(n) (VPTQ_K256M_PART == 0 || VPTQ_K256M_PART == (n))
-hipError_t k256m_f16_fast(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_f16_exact(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_bf16(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_f16_tokens(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_bf16_tokens(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_bf16_exact(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_f16_tokens_exact(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st);
-hipError_t k256m_bf16_tokens_exact(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st);
+hipError_t k256m_f16_fast(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_f16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_bf16(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_f16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_bf16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_bf16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_f16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
+hipError_t k256m_bf16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
 
 #if K256M_PART(2)
-hipError_t k256m_f16_exact(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st) {
-  return launch_m_shape<F16, false, 1>(P, gx, perm, max_cols, st);
+hipError_t k256m_f16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return launch_m_shape<F16, false, 1>(P, D, st);
 }
-hipError_t k256m_bf16(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st) {
-  return launch_m_shape<BF16, true, 1>(P, gx, perm, max_cols, st);
+hipError_t k256m_bf16(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return launch_m_shape<BF16, true, 1>(P, D, st);
 }
 #endif
 #if K256M_PART(3)
-hipError_t k256m_f16_tokens(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st) {
-  return tok == 2 ? launch_m_shape<F16, true, 2>(P, gx, perm, max_cols, st)
-                  : launch_m_shape<F16, true, 4>(P, gx, perm, max_cols, st);
+hipError_t k256m_f16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return D.tok == 2 ? launch_m_shape<F16, true, 2>(P, D, st)
+                  : launch_m_shape<F16, true, 4>(P, D, st);
 }
 #endif
 #if K256M_PART(4)
-hipError_t k256m_bf16_tokens(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st) {
-  return tok == 2 ? launch_m_shape<BF16, true, 2>(P, gx, perm, max_cols, st)
-                  : launch_m_shape<BF16, true, 4>(P, gx, perm, max_cols, st);
+hipError_t k256m_bf16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return D.tok == 2 ? launch_m_shape<BF16, true, 2>(P, D, st)
+                  : launch_m_shape<BF16, true, 4>(P, D, st);
 }
-hipError_t k256m_bf16_exact(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st) {
-  return launch_m_shape<BF16, false, 1>(P, gx, perm, max_cols, st);
+hipError_t k256m_bf16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return launch_m_shape<BF16, false, 1>(P, D, st);
 }
 #endif
 #if K256M_PART(5)
-hipError_t k256m_f16_tokens_exact(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st) {
-  return tok == 2 ? launch_m_shape<F16, false, 2>(P, gx, perm, max_cols, st)
-                  : launch_m_shape<F16, false, 4>(P, gx, perm, max_cols, st);
+hipError_t k256m_f16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return D.tok == 2 ? launch_m_shape<F16, false, 2>(P, D, st)
+                  : launch_m_shape<F16, false, 4>(P, D, st);
 }
 #endif
 #if K256M_PART(6)
-hipError_t k256m_bf16_tokens_exact(const K256Params& P, int tok, int gx, bool perm, int max_cols, hipStream_t st) {
-  return tok == 2 ? launch_m_shape<BF16, false, 2>(P, gx, perm, max_cols, st)
-                  : launch_m_shape<BF16, false, 4>(P, gx, perm, max_cols, st);
+hipError_t k256m_bf16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return D.tok == 2 ? launch_m_shape<BF16, false, 2>(P, D, st)
+                  : launch_m_shape<BF16, false, 4>(P, D, st);
 }
 #endif
 #if K256M_PART(1)
-hipError_t k256m_f16_fast(const K256Params& P, int gx, bool perm, int max_cols, hipStream_t st) {
-  return launch_m_shape<F16, true, 1>(P, gx, perm, max_cols, st);
+hipError_t k256m_f16_fast(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return launch_m_shape<F16, true, 1>(P, D, st);
 }
 
 // exact form with scale and bias staged in LDS (kSB in the kernel): bf16, and fp16 from 6 sweeps on
@@ -1303,27 +1297,43 @@ bool gemv_k256m_selective_ok(const int* n_rows, int n, bool f16, int tok, int ma
   return true;
 }
 
-hipError_t launch_gemv_k256m(K256Params& P, int tok, bool f16, bool fast, int max_cols, bool perm,
-                             hipStream_t st, bool selective) {
-  if (!gemv_k256m_supported(tok, f16, fast, max_cols, perm)) return hipErrorInvalidValue;
-  if (selective && !(fast && tok == 1 && max_cols <= kMMaxCols)) return hipErrorInvalidValue;
-  if (P.n_layers > kMaxGroup) return hipErrorInvalidValue;
-  int groups[kMaxGroup], share[kMaxGroup];
-  for (int i = 0; i < P.n_layers; ++i) groups[i] = gemv_k256m_row_groups(P.layer[i].N);
-  m_shares(groups, P.n_layers, m_cus(), share);
-  int gx = 0;
+// The decision for one launch: which instantiation (launch_m_shape picks exactly it) and how the launch is shaped.  Host
+// arithmetic and the CU-count look-up only.
+K256MDecision gemv_k256m_decide(const int* n_rows, int n, int tok, bool f16, bool fast, int max_cols, bool perm, bool selective) {
+  K256MDecision D = {};
+  D.f16 = f16; D.fast = fast; D.perm = perm; D.selective = selective; D.tok = tok; D.max_cols = max_cols;
+  if (n < 1 || n > kMaxGroup || !gemv_k256m_supported(tok, f16, fast, max_cols, perm)) return D;
+  if (selective && !(fast && tok == 1 && max_cols <= kMMaxCols)) return D;
+  const bool wide = max_cols > kMMaxCols;   // unstaged: column blocks of 2 sweeps
+  D.ns = wide ? 2 : (max_cols + kMSweepCols - 1) / kMSweepCols;
+  D.nst = wide ? 0 : D.ns <= 4 ? 1 : 2;
+  D.sb = sb_staged(f16, fast, max_cols, tok);
+  D.slots = lds_slots(tok, max_cols, D.sb);
+  D.entry = tok == 1 && n == 1 ? 1 : 0;
+  int groups[kMaxGroup];
+  for (int i = 0; i < n; ++i) groups[i] = gemv_k256m_row_groups(n_rows[i]);
+  m_shares(groups, n, m_cus(), D.share);
+  for (int i = 0; i < n; ++i) {
+    const int u = (groups[i] + D.share[i] - 1) / D.share[i];
+    D.units = u > D.units ? u : D.units;
+    D.gx = D.share[i] > D.gx ? D.share[i] : D.gx;
+  }
+  D.ok = D.ns >= 1 && D.ns <= 7 && D.slots >= 1;
+  return D;
+}
+
+hipError_t launch_gemv_k256m(K256Params& P, const K256MDecision& D, hipStream_t st) {
+  if (!D.ok || P.n_layers < 1 || P.n_layers > kMaxGroup) return hipErrorInvalidValue;
   for (int i = 0; i < P.n_layers; ++i) {
-    P.layer[i].wgs = share[i];
-    P.layer[i].slots = lds_slots(tok, max_cols, sb_staged(f16, fast, max_cols, tok)) | (selective ? kMSelBit : 0);
-    gx = share[i] > gx ? share[i] : gx;
+    P.layer[i].wgs = D.share[i];
+    P.layer[i].slots = D.slots | (D.selective ? kMSelBit : 0);
   }
-  if (tok != 1) {
-    if (!fast) return f16 ? k256m_f16_tokens_exact(P, tok, gx, perm, max_cols, st) : k256m_bf16_tokens_exact(P, tok, gx, perm, max_cols, st);
-    return f16 ? k256m_f16_tokens(P, tok, gx, perm, max_cols, st)
-               : k256m_bf16_tokens(P, tok, gx, perm, max_cols, st);
+  if (D.tok != 1) {
+    if (!D.fast) return D.f16 ? k256m_f16_tokens_exact(P, D, st) : k256m_bf16_tokens_exact(P, D, st);
+    return D.f16 ? k256m_f16_tokens(P, D, st) : k256m_bf16_tokens(P, D, st);
   }
-  if (!f16) return fast ? k256m_bf16(P, gx, perm, max_cols, st) : k256m_bf16_exact(P, gx, perm, max_cols, st);
-  return fast ? k256m_f16_fast(P, gx, perm, max_cols, st) : k256m_f16_exact(P, gx, perm, max_cols, st);
+  if (!D.f16) return D.fast ? k256m_bf16(P, D, st) : k256m_bf16_exact(P, D, st);
+  return D.fast ? k256m_f16_fast(P, D, st) : k256m_f16_exact(P, D, st);
 }
 #endif  // part 1
 

@@ -102,8 +102,24 @@ static __device__ __forceinline__ K256Layer load_layer_args(int& tokens) {
 constexpr int kMRows = 4;  // vector-rows per workgroup of the MFMA kernel
 bool gemv_k256m_supported(int tok, bool f16, bool fast, int max_cols, bool perm);
 int gemv_k256m_row_groups(int n_rows);
-hipError_t launch_gemv_k256m(K256Params& P, int tok, bool f16, bool fast, int max_cols, bool perm,
-                             hipStream_t st, bool selective = false);
+// What one launch of the persistent MFMA kernel is: the template arguments of the instantiation and the launch-shape facts.
+// gemv_k256m_decide fills it in (host arithmetic only); launch_gemv_k256m launches exactly that - every launcher checks its own
+// template arguments against it - and vptq_quant_gemv*_instance prints it.
+struct K256MDecision {
+  bool ok;             // the kernel takes the launch at all
+  bool f16, fast, perm, selective;
+  bool sb;             // scale and bias staged in LDS (kSB in the kernel)
+  int tok;             // token slots of the instantiation: 1, 2 or 4
+  int ns, nst;         // sweeps of 2048 columns; staging phases (0: the unstaged wide form)
+  int max_cols;
+  int entry;           // 1: gemv_k256m_kernel_1 (preloaded arguments: one layer, one token), 0: the grouped entry
+  int slots;           // cross-wave partial-sum slots in LDS
+  int units;           // most row groups any workgroup walks
+  int gx;              // grid.x
+  int share[kMaxGroup];   // workgroups per layer
+};
+K256MDecision gemv_k256m_decide(const int* n_rows, int n, int tok, bool f16, bool fast, int max_cols, bool perm, bool selective);
+hipError_t launch_gemv_k256m(K256Params& P, const K256MDecision& D, hipStream_t st);
 bool gemv_k256m_selective_ok(const int* n_rows, int n, bool f16, int tok, int max_cols, bool perm);
 // most row groups any workgroup of one launch of these layers walks (the launch's duration in units of one row group)
 int gemv_k256m_launch_units(const int* n_rows, int n);

@@ -8,6 +8,19 @@
 
 namespace vptq {
 
+// CUs of the current device, looked up once per device; 256 (MI355X) where there is no device to ask - the host-only
+// queries (kernel names, chain plans, instances) then answer for that
+inline int device_cus() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  if (!cus[dev]) {
+    hipDeviceProp_t p;
+    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
+  }
+  return cus[dev];
+}
+
 // gemv_generic.hip — every configuration
 hipError_t launch_gemv_generic(const VptqLayerDesc& d, const void* x, void* y, int tokens,
                                bool out_f32, hipStream_t st);
@@ -17,6 +30,8 @@ hipError_t launch_gemv_generic(const VptqLayerDesc& d, const void* x, void* y, i
 bool gemv_k256_eligible(const VptqLayerDesc& d, int tokens);
 const char* gemv_k256_name(const VptqLayerDesc& d, int tokens, int flags);
 const char* gemv_k256_group_name(const VptqLayerDesc* descs, int n, int tokens, int flags);
+// the instantiation(s) launch_gemv_k256 would launch, as text (vptq_quant_gemv_grouped_instance); 0, -1: no kernel, -2: buffer too small
+int gemv_k256_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes);
 hipError_t launch_gemv_k256(const VptqLayerDesc* descs, int n, const void* const* x,
                             void* const* y, int tokens, int flags, hipStream_t st);
 
@@ -33,6 +48,10 @@ size_t gemv_k256c_perm_bytes(const VptqLayerDesc& d);
 hipError_t launch_permute_x(const VptqLayerDesc* descs, int n, const void* const* x, void* const* out, hipStream_t st);   // VPTQ_GEMV_EXACT inside the chain launch
 hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
                              int flags, bool dependent, uint32_t* sync, hipStream_t st);
+// what that launch is: MODE of gemv_k256c_kernel<DT, DEP, MODE> for these flags (0 folded, 1 reference roundings, 2 selective;
+// -1: no such launch) and a layer's sweeps of 2048 columns
+int gemv_k256c_mode(int flags, bool dependent);
+int gemv_k256c_sweeps(const VptqLayerDesc& d);
 // how that launch deals its row groups (vptq_quant_gemv_chain_plan); workgroups = 0: what a launch uses
 hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
                            int* first_wg, int* rows_per_wg);
@@ -100,10 +119,15 @@ hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* 
 // gather -> 16x16x32 MFMA with tokens as M; folded arithmetic; needs a workspace for the operand-ordered activations)
 bool gemm_k256t_eligible(const VptqLayerDesc& d, int tokens, int flags);
 size_t gemm_k256t_workspace_bytes(const VptqLayerDesc& d);
+struct GemmK256TDecision { bool f16, perm; int n_groups, n_sweeps, grid, groups_per_wg; };   // what launch_gemm_k256t launches
+GemmK256TDecision gemm_k256t_decide(const VptqLayerDesc& d);
 hipError_t launch_gemm_k256t(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, void* ws,
                              hipStream_t st);
 // gemm_k256.hip - canonical format, fp16, up to 16 tokens in one launch (tokens = MFMA M)
 bool gemm_k256_eligible(const VptqLayerDesc& d, int tokens, int flags);
+// what launch_gemm_k256 launches; passes: bit mask of the NRG = 4 / 2 / 1 passes the busiest workgroup runs
+struct GemmK256Decision { bool f16, perm; int n_groups, grid, passes; };
+GemmK256Decision gemm_k256_decide(const VptqLayerDesc& d);
 hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
                             hipStream_t st);
 
