@@ -322,7 +322,8 @@ VPTQ_API int vptq_quant_gemm(const VptqLayerDesc* desc, const void* x, void* y, 
  *            (prefix sum of `blocks` in (s, n) order)
  *   rows_per_wave : 1 .. 64 consecutive rows per wave (16 waves per workgroup); the layout does not
  *            depend on it
- * (vptq_amd/utils/sliced.py builds it with torch.)  It costs 2x (residual 256: 1.7x) the packed indices in device memory on
+ * (vptq_sliced_layout_plan / _fill below build it on the device; vptq_amd/utils/sliced.py:layout_from_indices is the torch model of
+ * that builder and serves CPU tensors.)  It costs 2x (residual 256: 1.7x) the packed indices in device memory on
  * top of them; the state-dict tensors are untouched.  A layer with 65536 RESIDUAL centroids is served table by table
  * - (c + r) s x = c s x + r s x: the residual table's (slice, row block) workgroups run beside the main table's in the same
  * launch - and `layout` then points to TWO consecutive structs with the same rows_per_wave: [0] built from the main
@@ -455,6 +456,51 @@ VPTQ_API int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const Vp
  * pointer not 16-byte aligned (VPTQ_E_ALIGN); nothing is launched then.  One workgroup per row, the row assembled in LDS. */
 VPTQ_API int vptq_sliced_layout_repack(const VptqLayerDesc* desc, const VptqSlicedLayout* layouts, int parts, void* indices_out,
                                        void* stream);
+
+/* Build a sliced layout from the packed indices ON THE DEVICE: the forward direction of vptq_sliced_layout_repack, and byte for
+ * byte what the torch recipe vptq_amd/utils/sliced.py:layout_from_indices builds (the recipe stays the model and serves CPU tensors).
+ * Added within ABI 11; present when the symbols are.
+ *
+ * `spec` names the layout wanted - every one vptq_amd/utils/sliced.py:SlicedGemv builds:
+ *   flags       0: a layout of the folded form; VPTQ_GEMV_EXACT: one of the reference's roundings
+ *   n_slices    what vptq_sliced_layout_supported_for(desc - or the column part of it -, flags) answers
+ *   table       0: bucketed by the main index; 1 (folded two-table formats, vptq_sliced_layout_tables() == 2): the residual
+ *               codebook as a second table, bucketed by the residual index
+ *   whole_table what vptq_sliced_layout_whole_table(desc, table) answers (folded; exact layouts: 0): slice = column * S / G, the
+ *               element word carries the whole index
+ *   side_bytes  the `res` side stream beside the element words: 0 none; 1 uint8 residual indices (v = 8 with 256 residual
+ *               centroids, table 0, one-table layouts); 2 uint16 (exact layouts of any other residual codebook)
+ *   parts, part 1, 0 - or (exact) the layer's 2 - 3 column parts and which of them: columns [part G / parts, (part + 1) G / parts),
+ *               counted from the part's first; two parts may share a 32-bit word of the packed row
+ * The layout's size depends on the data (lists are padded to blocks of 64 elements), so the build has two steps with one
+ * device -> host read between them:
+ *   plan : blocks int32 [S][N], first int32 [S][N], wstart int32 [S][N][VPTQ_SLICED_WINDOWS + 1] and *total_blocks (int64, device)
+ *   fill : elems uint32 x 64 x max(total, 1) and, with side_bytes, res (uint8 / uint16 per element) - `out` carries the five
+ *          pointers (n_slices as in spec; the other fields are not read), total_blocks is the number read back, past which nothing
+ *          is stored
+ * Order inside a list: rows of 16 different LDS bank classes (local & 15) first, the surplus spread evenly behind them by the
+ * recipe's float64 key, evaluated in the same order; equal keys (the recipe leaves their order open) by class, then column.
+ * Errors, before any launch: NULL pointers (VPTQ_E_NULL); n_slices / parts / part other than the layer's (VPTQ_E_SHAPE); formats
+ * without a layout, a table / whole_table / side_bytes the layer's layouts do not have (VPTQ_E_UNSUPPORTED); blocks / first /
+ * wstart / res not 4-byte, total_blocks not 8-byte, elems not 16-byte aligned (VPTQ_E_ALIGN).  No allocation, no synchronisation.
+ * flags | VPTQ_LAYOUT_ANY_SHAPE: the spec is taken as written - any slice count of 8 / 16 / 32, any 1 - 3 parts that divide the
+ * columns, any table, whole_table and side_bytes the index widths allow - for layouts no GEMV entry of this
+ * library takes (tests of the builder against its model, tools); everything that guards memory is still checked. */
+#define VPTQ_LAYOUT_ANY_SHAPE (1 << 16)
+typedef struct VptqSlicedLayoutSpec {
+  int32_t flags;
+  int32_t n_slices;
+  int32_t table;
+  int32_t whole_table;
+  int32_t side_bytes;
+  int32_t parts;
+  int32_t part;
+  int32_t reserved;   /* 0 */
+} VptqSlicedLayoutSpec;
+VPTQ_API int vptq_sliced_layout_plan(const VptqLayerDesc* desc, const VptqSlicedLayoutSpec* spec, void* blocks, void* first,
+                                     void* wstart, void* total_blocks, void* stream);
+VPTQ_API int vptq_sliced_layout_fill(const VptqLayerDesc* desc, const VptqSlicedLayoutSpec* spec, const VptqSlicedLayout* out,
+                                     int64_t total_blocks, void* stream);
 
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);

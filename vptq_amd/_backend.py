@@ -55,6 +55,14 @@ class SlicedLayout(C.Structure):
                 ("wstart", C.c_void_p)]
 
 
+class SlicedLayoutSpec(C.Structure):
+    """Mirror of `VptqSlicedLayoutSpec` (include/vptq_hip.h): which layout vptq_sliced_layout_plan / _fill build."""
+    _fields_ = [(n, C.c_int32) for n in ("flags", "n_slices", "table", "whole_table", "side_bytes", "parts", "part", "reserved")]
+
+
+LAYOUT_ANY_SHAPE = 1 << 16   # VptqSlicedLayoutSpec.flags: the spec as written, not checked against the layer's GEMV layouts
+
+
 class LayerDesc(C.Structure):
     """Mirror of `VptqLayerDesc` (include/vptq_hip.h)."""
     _fields_ = [(n, C.c_int32) for n in (
@@ -121,6 +129,9 @@ EXPORTS = {
     "vptq_quant_gemv_grouped_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
     # (added within ABI 11) the packed index stream rebuilt from a layer's exact sliced layout(s): compact mode
     "vptq_sliced_layout_repack": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, _vp, _vp]),
+    # (added within ABI 11) a sliced layout built from the packed indices on the device, in two steps (layout_build.hip)
+    "vptq_sliced_layout_plan": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayoutSpec), _vp, _vp, _vp, _vp, _vp]),
+    "vptq_sliced_layout_fill": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayoutSpec), C.POINTER(SlicedLayout), C.c_int64, _vp]),
     # (added within ABI 11) which instantiation a call would launch, as text: host logic, nothing is launched
     "vptq_quant_gemv_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "vptq_quant_gemv_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),

@@ -857,6 +857,109 @@ int vptq_sliced_layout_repack(const VptqLayerDesc* d, const VptqSlicedLayout* la
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "sliced_repack launch");
 }
 
+// what vptq_sliced_layout_plan / _fill build for (desc, spec): validation of the spec against the layouts the GEMV entries take for
+// the layer (VPTQ_LAYOUT_ANY_SHAPE: against the index widths alone), then the kernel's parameters
+static int layout_build_params(const VptqLayerDesc* d, const VptqSlicedLayoutSpec* spec, vptq::LayoutBuildParams* P) {
+  if (int rc = validate_layer(d)) return rc;
+  if (!spec) return fail(VPTQ_E_NULL, "spec is NULL");
+  const VptqSlicedLayoutSpec& s = *spec;
+  if (s.flags & ~(VPTQ_GEMV_EXACT | VPTQ_LAYOUT_ANY_SHAPE)) return fail(VPTQ_E_UNSUPPORTED, "spec flags 0x%x: VPTQ_GEMV_EXACT and VPTQ_LAYOUT_ANY_SHAPE only", s.flags);
+  const bool exact = (s.flags & VPTQ_GEMV_EXACT) != 0, any = (s.flags & VPTQ_LAYOUT_ANY_SHAPE) != 0;
+  if (d->num_codebooks != 1 || d->outlier_size != 0 || d->group_size != d->in_features || d->group_size > 32768)
+    return fail(VPTQ_E_UNSUPPORTED, "a sliced layout is built for layers of one codebook group without outlier columns, group_size <= 32768");
+  if (s.parts < 1 || s.parts > 3 || s.part < 0 || s.part >= s.parts || d->group_size % s.parts != 0)
+    return fail(VPTQ_E_SHAPE, "part %d of %d parts: 1 - 3 equal column parts of the layer's %d columns", s.part, s.parts, d->group_size);
+  if (s.n_slices != 8 && s.n_slices != 16 && s.n_slices != 32) return fail(VPTQ_E_SHAPE, "n_slices %d: 8, 16 or 32", s.n_slices);
+  if (s.table < 0 || s.table > 1 || (s.table == 1 && d->num_res_centroids == 0))
+    return fail(VPTQ_E_UNSUPPORTED, "table %d: 0, or 1 for a layer with a residual codebook", s.table);
+  if (s.side_bytes < 0 || s.side_bytes > 2 || (s.side_bytes && (d->num_res_centroids == 0 || s.table != 0)) || (s.side_bytes == 1 && d->res_bits > 8))
+    return fail(VPTQ_E_UNSUPPORTED, "side_bytes %d: 1 (up to 256 residual centroids) or 2 beside a table-0 layout of a layer with a residual codebook, else 0", s.side_bytes);
+  if (s.whole_table != 0 && s.whole_table != 1) return fail(VPTQ_E_UNSUPPORTED, "whole_table %d: 0 or 1", s.whole_table);
+  const int lg = s.n_slices == 8 ? 3 : (s.n_slices == 16 ? 4 : 5);
+  const int bits = s.table ? d->res_bits : d->index_bits;
+  if (!any) {
+    // the layouts vptq_amd/utils/sliced.py:SlicedGemv hands to the GEMV entries
+    int want_parts = 1, want_slices, want_whole = 0, want_side = 0, tables = 1;
+    if (exact) {
+      want_parts = repack_exact_parts(*d);
+      if (want_parts == 0)
+        return fail(VPTQ_E_UNSUPPORTED, "no exact sliced layout serves this layer (vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT), "
+                                        "or 2 / 3 column parts of it)");
+      if (s.parts != want_parts) return fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", s.parts, want_parts);
+      want_slices = vptq::gemv_sliced_slices(repack_part_desc(*d, want_parts, s.part), true);
+      want_side = d->num_res_centroids == 0 ? 0 : (d->vector_len == 8 && d->num_res_centroids == 256 ? 1 : 2);
+    } else {
+      if (!vptq::gemv_sliced_eligible(*d, false))
+        return fail(VPTQ_E_UNSUPPORTED, "the sliced layout serves v = 8 / 16 layers with 16384 ... 65536 main centroids, group_size <= 32768");
+      if (s.parts != 1) return fail(VPTQ_E_SHAPE, "parts %d: column parts are layouts of the reference's roundings (VPTQ_GEMV_EXACT)", s.parts);
+      want_slices = vptq::gemv_sliced_slices(*d, false);
+      tables = vptq::gemv_sliced_tables(*d);
+      want_whole = vptq::gemv_sliced_whole_table(*d, s.table);
+      want_side = tables == 1 && d->num_res_centroids > 0 ? 1 : 0;
+    }
+    if (s.n_slices != want_slices)
+      return fail(VPTQ_E_SHAPE, "n_slices %d: this layout of the layer has %d (vptq_sliced_layout_supported_for)", s.n_slices, want_slices);
+    if (s.table >= tables) return fail(VPTQ_E_UNSUPPORTED, "table %d: this arithmetic serves the layer from %d layout(s) per part (vptq_sliced_layout_tables)", s.table, tables);
+    if (s.whole_table != want_whole) return fail(VPTQ_E_UNSUPPORTED, "whole_table %d: must be %d (vptq_sliced_layout_whole_table)", s.whole_table, want_whole);
+    if (s.side_bytes != want_side) return fail(VPTQ_E_UNSUPPORTED, "side_bytes %d: this layout carries %d", s.side_bytes, want_side);
+  }
+  vptq::LayoutBuildParams a = {};
+  a.packed = (const uint32_t*)d->indices;
+  a.N = d->num_indices;
+  a.row_words = d->row_words;
+  a.T = d->index_bits + d->res_bits;
+  a.W = d->group_size / s.parts;
+  a.c0 = s.part * a.W;
+  a.wcols = (a.W + VPTQ_SLICED_WINDOWS * 8 - 1) / (VPTQ_SLICED_WINDOWS * 8) * 8;
+  const int last = a.W - (VPTQ_SLICED_WINDOWS - 1) * a.wcols;
+  a.cap = a.wcols < a.W ? a.wcols : a.W;
+  if (last > a.cap) a.cap = last;
+  a.S = s.n_slices;
+  a.slice_bits = s.whole_table || bits < lg ? 0 : bits - lg;   // (fewer entries than slices: slice = index, as the recipe has it)
+  a.bucket_shift = s.table ? d->index_bits : 0;
+  a.bucket_mask = (1u << bits) - 1u;
+  a.whole = s.whole_table;
+  a.side = s.side_bytes;
+  a.side_shift = d->index_bits;
+  *P = a;
+  return VPTQ_OK;
+}
+
+int vptq_sliced_layout_plan(const VptqLayerDesc* d, const VptqSlicedLayoutSpec* spec, void* blocks, void* first, void* wstart,
+                            void* total_blocks, void* stream) {
+  vptq::LayoutBuildParams a;
+  if (int rc = layout_build_params(d, spec, &a)) return rc;
+  if (!blocks || !first || !wstart || !total_blocks) return fail(VPTQ_E_NULL, "blocks / first / wstart / total_blocks is NULL");
+  if ((((uintptr_t)blocks | (uintptr_t)first | (uintptr_t)wstart) & 3) != 0 || (((uintptr_t)total_blocks) & 7) != 0)
+    return fail(VPTQ_E_ALIGN, "blocks / first / wstart 4-byte, total_blocks 8-byte aligned");
+  a.blocks = (int32_t*)blocks;
+  a.first = (int32_t*)first;
+  a.wstart = (int32_t*)wstart;
+  a.total = (long long*)total_blocks;
+  const hipError_t e = vptq::launch_layout_plan(a, (hipStream_t)stream);
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "sliced layout plan launch");
+}
+
+int vptq_sliced_layout_fill(const VptqLayerDesc* d, const VptqSlicedLayoutSpec* spec, const VptqSlicedLayout* out, int64_t total_blocks,
+                            void* stream) {
+  vptq::LayoutBuildParams a;
+  if (int rc = layout_build_params(d, spec, &a)) return rc;
+  if (!out || !out->elems || !out->blocks || !out->first || !out->wstart) return fail(VPTQ_E_NULL, "out / elems / blocks / first / wstart is NULL");
+  if ((a.side != 0) != (out->res != nullptr)) return fail(VPTQ_E_NULL, "the `res` side stream must be set iff the spec carries one");
+  if (out->n_slices != spec->n_slices) return fail(VPTQ_E_SHAPE, "out->n_slices %d, the spec has %d", out->n_slices, spec->n_slices);
+  if (total_blocks < 0 || total_blocks >= (1ll << 31)) return fail(VPTQ_E_SHAPE, "total_blocks %lld outside [0, 2^31)", (long long)total_blocks);
+  if ((((uintptr_t)out->elems) & 15) != 0 || (((uintptr_t)out->blocks | (uintptr_t)out->first | (uintptr_t)out->wstart | (uintptr_t)out->res) & 3) != 0)
+    return fail(VPTQ_E_ALIGN, "elems 16-byte, blocks / first / wstart / res 4-byte aligned");
+  a.blocks = (int32_t*)out->blocks;
+  a.first = (int32_t*)out->first;
+  a.wstart = (int32_t*)out->wstart;
+  a.elems = (uint32_t*)out->elems;
+  a.res = (void*)out->res;
+  a.total_blocks = total_blocks;
+  const hipError_t e = vptq::launch_layout_fill(a, (hipStream_t)stream);
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "sliced layout fill launch");
+}
+
 int vptq_quant_gemv_sliced_selective_supported(const VptqLayerDesc* d) {
   return validate_layer(d) == VPTQ_OK && vptq::gemv_hot_eligible(*d) ? 1 : 0;
 }

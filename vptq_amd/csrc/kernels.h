@@ -115,6 +115,28 @@ size_t gemv_sliced_exact_tokens_workspace_bytes(const VptqLayerDesc& d, int toke
 // repack.hip - the packed index stream of a layer rebuilt from its exact sliced layout(s) (vptq_sliced_layout_repack)
 size_t sliced_repack_lds_bytes(const VptqLayerDesc& d);
 hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, void* out, hipStream_t st);
+// layout_build.hip - a sliced layout built from the packed index stream (vptq_sliced_layout_plan / vptq_sliced_layout_fill)
+struct LayoutBuildParams {
+  const uint32_t* packed;   // [N][row_words]
+  int32_t* blocks;          // [S][N]
+  int32_t* first;           // [S][N]
+  int32_t* wstart;          // [S][N][VPTQ_SLICED_WINDOWS + 1]
+  long long* total;         // plan: the number of blocks (device)
+  uint32_t* elems;          // fill
+  void* res;                // fill: uint8 / uint16 side stream, or NULL
+  long long total_blocks;   // fill: blocks `elems` (and `res`) have room for - nothing is stored past them
+  int N, row_words, T;
+  int c0, W;                // the columns [c0, c0 + W) of the row this layout is for (a column part, or all of them)
+  int wcols, cap;           // window width; the widest window
+  int S, slice_bits;        // slices; bits of the index inside a slice
+  int bucket_shift;         // the bucket index = (field >> bucket_shift) & bucket_mask: the main index, or the residual one
+  uint32_t bucket_mask;
+  int whole;                // slices are equal column ranges, the word carries the whole bucket index
+  int side, side_shift;     // side stream: 0 none, 1 uint8, 2 uint16 = field >> side_shift
+};
+size_t layout_fill_lds_bytes(const LayoutBuildParams& a);
+hipError_t launch_layout_plan(const LayoutBuildParams& a, hipStream_t st);
+hipError_t launch_layout_fill(const LayoutBuildParams& a, hipStream_t st);
 // gemm_k256t.hip - canonical format, fp16 / bf16, up to 16 tokens in one pass over the indices (transposing
 // gather -> 16x16x32 MFMA with tokens as M; folded arithmetic; needs a workspace for the operand-ordered activations)
 bool gemm_k256t_eligible(const VptqLayerDesc& d, int tokens, int flags);

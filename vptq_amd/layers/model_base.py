@@ -19,7 +19,7 @@ from typing import Optional
 
 import torch
 
-from vptq_amd.layers.vqlinear import VQuantLinear, chain_prefetch, compact_model, link_siblings
+from vptq_amd.layers.vqlinear import VQuantLinear, chain_prefetch, compact_model, link_siblings, prepare_model
 
 
 def make_quant_linear(module: torch.nn.Module, config_for_layers: dict, shared_layer_config: dict,
@@ -96,7 +96,7 @@ class AutoModelForCausalLM:
     def from_pretrained(cls, pretrained_model_name_or_path: str, *model_args,
                         device: Optional[str] = None, dtype: Optional[torch.dtype] = None,
                         link_prefetch: bool = False, absorb_perm: bool = False,
-                        fuse_siblings: bool = False, compact_indices: bool = False, **kwargs):
+                        fuse_siblings: bool = False, compact_indices: bool = False, prepare: bool = False, **kwargs):
         import transformers
         from safetensors.torch import load_file
 
@@ -159,6 +159,10 @@ class AutoModelForCausalLM:
             link_siblings(model)
         if link_prefetch:
             chain_prefetch([m for m in model.modules() if isinstance(m, VQuantLinear)], circular=True)
+        if prepare and str(device).startswith("cuda"):
+            # the sliced layouts of the large-codebook formats and the one-token workspaces of the current stream now, not inside
+            # the first decode step (and not missed by a first step that is captured into a graph)
+            prepare_model(model)
         if compact_indices:
             # large-codebook layers served from their exact sliced layout keep it as the only copy of their indices
             compact_model(model)

@@ -116,6 +116,23 @@ def compact_model(model: nn.Module, force: bool = False) -> dict:
     return rep
 
 
+def prepare_model(model: nn.Module, stream=None) -> dict:
+    """`VQuantLinear.prepare(stream)` over every layer of `model`: the sliced layouts of the large-codebook formats are built now (by
+    the library's builder, layer by layer) instead of inside the first decode step, and every layer has its one-token workspace for
+    `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  Returns {"layers": {name: {"built", "bytes",
+    "seconds"}}, "built": layers with a layout, "bytes", "seconds"}."""
+    rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
+    for name, m in model.named_modules():
+        if not isinstance(m, VQuantLinear):
+            continue
+        r = m.prepare(stream)
+        rep["layers"][name] = r
+        rep["built"] += int(r["built"] in ("exact", "folded", "selective"))
+        rep["bytes"] += r["bytes"]
+        rep["seconds"] += r["seconds"]
+    return rep
+
+
 class SiblingGroup:
     """Layers that are applied to the SAME activation one after the other (q / k / v, gate / up).
     The first member called with a tensor launches all members in one grouped kernel
@@ -517,6 +534,54 @@ class VQuantLinear(nn.Module):
         self.__dict__["_sliced_on"] = bool(enable)
         self.__dict__.pop("_sliced", None)
 
+    def prepare(self, stream=None) -> dict:
+        """Make this layer ready NOW for one-token calls on `stream` (default: the current stream of the layer's device): the
+        descriptor's derived state, the sliced layout(s) `_sliced_gemv()` would otherwise build at the first one-token call in the
+        current arithmetic - same routing rule, same gate, cached under the same stamp - and the zeroed one-token workspace of
+        `stream` (workspaces are per stream and are not allocated during a capture: a caller who will capture on stream s passes
+        s).  Returns {"built": "exact" | "folded" | "selective" | the reason no layout was built, "bytes": device bytes of the
+        layout tensors, "seconds": wall time including the build's read-back}.  A first one-token call inside
+        `torch.cuda.graph(g, stream=s)` after `prepare(stream=s)` takes the sliced kernel."""
+        import time
+        t0 = time.perf_counter()
+        rep = {"built": None, "bytes": 0, "seconds": 0.0}
+        ind = self._parameters["indices"]
+        cp = self.__dict__.get("_compact")
+        why = None
+        if cp is None and not ind.is_cuda:
+            why = "indices are not on a ROCm device"
+        elif torch.cuda.is_current_stream_capturing():
+            why = "inside a stream capture"
+        elif not (self.num_centroids >= 16384 and self.vector_len in (8, 16) and self.num_codebooks == 1 and not self.enable_outlier and
+                  self.enable_norm):
+            self._descriptor()
+            why = "format has no sliced layout (v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no outliers, scale / bias)"
+        if why is None:
+            dev = self._descriptor()[3]
+            with torch.cuda.device(dev):
+                s = torch.cuda.current_stream(dev) if stream is None else stream
+                with torch.cuda.stream(s):
+                    sl = self._sliced_gemv()
+                    if sl is not None:
+                        sl._workspace(s.cuda_stream)
+                        s.synchronize()   # (the layout and the zeroed workspace are complete before any other stream uses them)
+            if sl is None:
+                on = self.__dict__.get("_sliced_on")
+                if not (_SLICED_LAYOUT_ENV if on is None else on):
+                    why = "sliced layouts are switched off (VPTQ_SLICED_LAYOUT=0 / enable_sliced_layout(False))"
+                elif "_sliced_oom" in self.__dict__:
+                    why = "out of device memory building the layout"
+                else:
+                    why = "one token takes the gather kernel for this layer (no sliced route for its size, width or arithmetic, or " \
+                          "too little free device memory for the layout)"
+            else:
+                rep["built"] = "exact" if sl.exact else ("selective" if sl.selective else "folded")
+                rep["bytes"] = sum(t.numel() * t.element_size() for tup in sl._tensors for t in tup if t is not None)
+        if why is not None:
+            rep["built"] = why
+        rep["seconds"] = time.perf_counter() - t0
+        return rep
+
     def _sliced_gemv(self):
         cp = self.__dict__.get("_compact")
         if cp is not None:
@@ -723,7 +788,10 @@ class VQuantLinear(nn.Module):
         free, total = torch.cuda.mem_get_info(cache[3])
         elems = self.indices.shape[1] * self.group_size
         two = B.lib().vptq_sliced_layout_tables(cache[1]) == 2   # (one layout per table)
-        need = elems * (8 if two else 5) + elems * 8 * 20   # layout + int64 / float64 temporaries of build_sliced_layout (window order: more of them)
+        from vptq_amd.utils.sliced import device_builder_enabled
+        need = elems * (8 if two else 5)   # the layout; the torch recipe: + its int64 / float64 temporaries (the HIP builder has none)
+        if not device_builder_enabled(self._parameters["indices"]):
+            need += elems * 8 * 20
         return free - need > _SLICED_MIN_FREE_FRACTION * total
 
     def _gemv_cached(self, x: torch.Tensor, tokens: int) -> torch.Tensor:

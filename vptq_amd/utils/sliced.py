@@ -9,7 +9,8 @@ lets a workgroup keep its 8192- (4096-) entry slice of the codebook in LDS.  The
 the contract, and the many-token / dequant paths keep using them); the derived tensors cost 2x (T = 16) / 1.7x
 (T = 24: 5 instead of 3 bytes per element) the packed indices in device memory on top.
 
-    sl = SlicedGemv(layer)          # builds the layout (torch, on the layer's device)
+    sl = SlicedGemv(layer)          # builds the layout (the library's builder for indices on a ROCm device: `layout_on_device`;
+                                    # the torch recipe `layout_from_indices`, its model, otherwise)
     y = sl(x)                       # one token; same result as layer(x) within the parity bar
 
 Round 5: `SlicedGemv(layer, exact=True)` - the reference's roundings per weight (the product default) over ONE layout bucketed by
@@ -139,6 +140,48 @@ def layout_from_indices(idx: torch.Tensor, slices: int = 8, ridx: torch.Tensor =
     return elems32, blocks_sn.to(torch.int32).contiguous(), first_sn.to(torch.int32).contiguous(), res, wstart
 
 
+def device_builder_enabled(indices: torch.Tensor) -> bool:
+    """is a layout of these packed indices built by the HIP kernel (`layout_on_device`)?  Indices on a ROCm device: yes; CPU
+    tensors take the torch recipe above, which is also the kernel's model.  (A/B: VPTQ_TUNING=1 VPTQ_LAYOUT_BUILDER=torch.)"""
+    return bool(indices.is_cuda) and (B.tune_env("VPTQ_LAYOUT_BUILDER", "hip") or "hip").strip().lower() != "torch"
+
+
+def layout_on_device(indices: torch.Tensor, desc, slices: int, exact: bool = False, table: int = 0, whole_table: bool = False,
+                     side_bytes: int = 0, parts: int = 1, part: int = 0, any_shape: bool = False):
+    """The same 5-tuple as `layout_from_indices`, byte for byte, built from the PACKED int32 `indices` [1, N, row_words] on their
+    ROCm device by the library (`vptq_sliced_layout_plan` / `_fill`, vptq_amd/csrc/layout_build.hip) on the current stream.  `desc`:
+    the layer's descriptor (shape of the stream and the format; its `indices` pointer is replaced by the tensor's).  table 0 / 1: bucketed
+    by the main / the residual index; side_bytes 0 / 1 / 2: no side stream / uint8 / uint16 (int16 bit patterns) residual indices;
+    part of parts: the columns [part G / parts, (part + 1) G / parts).  any_shape: the spec is not checked against the layouts the
+    GEMV entries take for the layer (tests, tools).  Device memory: the five tensors returned and one int64 - nothing else; one
+    device -> host read (the number of blocks) between the two steps."""
+    assert indices.dtype == torch.int32 and indices.dim() == 3 and indices.shape[0] == 1 and indices.is_cuda
+    if not indices.is_contiguous():
+        indices = indices.contiguous()
+    dev = indices.device
+    d = B.LayerDesc.from_buffer_copy(desc)
+    d.indices, d.prefetch, d.prefetch_bytes = indices.data_ptr(), None, 0
+    N = int(d.num_indices)
+    lib = B.lib()
+    spec = B.SlicedLayoutSpec((B.GEMV_EXACT if exact else 0) | (B.LAYOUT_ANY_SHAPE if any_shape else 0), int(slices), int(table),
+                              int(bool(whole_table)), int(side_bytes), int(parts), int(part), 0)
+    with torch.cuda.device(dev):
+        sp = B.current_stream_ptr(dev)
+        blocks = torch.empty(slices, N, dtype=torch.int32, device=dev)
+        first = torch.empty(slices, N, dtype=torch.int32, device=dev)
+        wstart = torch.empty(slices, N, WINDOWS + 1, dtype=torch.int32, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        B.check(lib.vptq_sliced_layout_plan(d, spec, blocks.data_ptr(), first.data_ptr(), wstart.data_ptr(), total.data_ptr(), sp),
+                "vptq_sliced_layout_plan")
+        n_blocks = int(total.item())
+        elems = torch.empty(max(n_blocks, 1) * 64, dtype=torch.int32, device=dev)
+        res = torch.empty(elems.numel(), dtype=torch.uint8 if side_bytes == 1 else torch.int16, device=dev) if side_bytes else None
+        out = B.SlicedLayout(elems.data_ptr(), blocks.data_ptr(), first.data_ptr(), res.data_ptr() if res is not None else None, 1, 1,
+                             int(slices), int(bool(whole_table)), wstart.data_ptr())
+        B.check(lib.vptq_sliced_layout_fill(d, spec, out, n_blocks, sp), "vptq_sliced_layout_fill")
+    return elems, blocks, first, res, wstart
+
+
 def repack_reference(layouts, group_size: int, index_bits: int, res_bits: int, row_words: int, slices: int) -> torch.Tensor:
     """Pure-torch model of `vptq_sliced_layout_repack` (tests and docs only): the packed int32 indices [1, N, row_words] rebuilt from
     the EXACT layout(s) `layout_from_indices` returned - one tuple (elems, blocks, first, res, wstart) per column part, part p
@@ -256,8 +299,30 @@ class SlicedGemv:
         # a second table whose slice would be under 16 KiB is held WHOLE by each of its workgroups while it fits (the
         # library decides: the kernel's LDS budget)
         whole = [False, n_tables == 2 and bool(B.lib().vptq_sliced_layout_whole_table(self.desc, 1))]
-        idx, ridx = split_index_streams(layer.indices.data, layer.group_size, rb, ib)
-        if self.parts > 1:
+        packed = layer.indices.data
+        if device_builder_enabled(packed):
+            # indices on a ROCm device: the library builds the same tensors, byte for byte, from the packed stream (layout_build.hip) -
+            # no index matrices, no sorts: the tensors themselves are the only memory the build takes
+            side = (2 if side16 else 1) if kr else 0
+
+            def build(table=0, whole_table=False, side_bytes=0, part=0):
+                return layout_on_device(packed, self.desc, self.slices, exact=self.exact, table=table, whole_table=whole_table,
+                                        side_bytes=side_bytes, parts=self.parts, part=part)
+            if self.parts > 1:
+                w = layer.group_size // self.parts
+                self._tensors = [build(side_bytes=side, part=p) for p in range(self.parts)]
+                self._part_descs = (B.LayerDesc * self.parts)(*[part_desc(self.desc, p * w, (p + 1) * w) for p in range(self.parts)])
+                whole = [False] * self.parts
+            elif n_tables == 2:
+                self._tensors = [build(), build(table=1, whole_table=whole[1])]
+            else:
+                self._tensors = [build(side_bytes=side)]
+            idx = ridx = None
+        else:
+            idx, ridx = split_index_streams(packed, layer.group_size, rb, ib)
+        if idx is None:
+            pass
+        elif self.parts > 1:
             w = layer.group_size // self.parts
             self._tensors = [layout_from_indices(idx[:, p * w:(p + 1) * w].contiguous(), self.slices,
                                                  ridx[:, p * w:(p + 1) * w].contiguous() if kr else None, ib,
