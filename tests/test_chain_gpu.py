@@ -361,7 +361,7 @@ def test_selective_chain_vs_oracle(dev, selective_arithmetic):
         ys = chain(xt, flags=CHAIN)
         torch.cuda.synchronize()
         for L, m, x, y in zip(Ls, ms, xv, ys):
-            flag = m._descriptor()[9]
+            flag = m._descriptor().arithmetic_flags
             assert flag in (B.GEMV_SELECTIVE, B.GEMV_EXACT)   # (EXACT: the load-time gate refused the layer)
             err = rel_err(tensor_to_bits(y), vo.forward(L, x), "f16")
             assert err <= 1e-3, f"{variant} {L.in_features}x{L.out_features}: {err:.3e}"
@@ -423,7 +423,7 @@ def test_selective_without_workspace_or_kernel_is_exact(dev, folded_arithmetic):
     Ls, ms, xs = _build(SHAPES[:3], "f16", dev)
     xt = [bits_to_tensor(x, "f16", dev).reshape(x.shape) for x in xs]
     n = len(ms)
-    descs = (B.LayerDesc * n)(*[m._descriptor()[1] for m in ms])
+    descs = (B.LayerDesc * n)(*[m._descriptor().desc for m in ms])
     xp, yp = (C.c_void_p * n)(), (C.c_void_p * n)()
 
     def run(flags, ws=None):

@@ -66,7 +66,7 @@ def test_compact_layer_bit_identical(I, O, v, k, kr, dt, dev):
     from vptq_amd.utils.sliced import SlicedGemv, exact_column_parts
     m = make_layer(I, O, v, k, kr, dt, seed=I + O + k + kr, dev=dev)
     ref = m.indices.detach().clone()
-    parts = exact_column_parts(m._descriptor()[1], I)[0]
+    parts = exact_column_parts(m._descriptor().desc, I)[0]
     if I in (24592, 28672):
         assert parts == 2
     # the kernel's repack of a fresh exact layout equals the packed indices

@@ -113,7 +113,7 @@ def test_sliced_layout_reference_roundings(I, O, kw, rpw, dt, v, kr, dev):
     L = vo.make_layer(I, O, dist=dist, seed=I + O + v, dtype=dt, vector_len=v, num_centroids=65536, num_res_centroids=kr, **kw)
     x = _x(I, dt, dist, I + 1)
     m = spec_to_module(L, dev)
-    desc = m._descriptor()[1]
+    desc = m._descriptor().desc
     want_slices = B.lib().vptq_sliced_layout_supported_for(desc, EXACT)
     small = 8 if v == 8 else 16
     lds = lambda nsl: (65536 // nsl) * v * 2 + (I + 64) * 6 + 64 + (4096 if kr == 256 else 0)   # noqa: E731
@@ -379,7 +379,7 @@ def test_sliced_layout_small_reference_golden_and_rejections(dev):
     from vptq_amd import _backend as B
     L, x, y, cfg, _ = load_golden("k65536_nores_nonorm")
     m = spec_to_module(L, dev)
-    if B.lib().vptq_sliced_layout_supported(m._descriptor()[1]):
+    if B.lib().vptq_sliced_layout_supported(m._descriptor().desc):
         xt = bits_to_tensor(x, cfg["dtype"], dev).reshape(x.shape)
         got = tensor_to_bits(SlicedGemv(m)(xt[:, :1].contiguous()))
         assert rel_err(got, y[:, :1], cfg["dtype"]) <= TOL[cfg["dtype"]]
@@ -398,7 +398,7 @@ def test_sliced_layout_small_reference_golden_and_rejections(dev):
     Lw = vo.make_layer(8192, 64, seed=3, num_centroids=65536, num_res_centroids=0)
     mw = spec_to_module(Lw, dev)
     slw = SlicedGemv(mw)
-    assert slw.slices == 8 and B.lib().vptq_sliced_layout_supported_for(mw._descriptor()[1], EXACT) == 16
+    assert slw.slices == 8 and B.lib().vptq_sliced_layout_supported_for(mw._descriptor().desc, EXACT) == 16
     assert slw(torch.zeros(1, 1, 8192, dtype=torch.float16, device=dev), flags=EXACT) is None
 
 

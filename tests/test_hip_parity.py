@@ -194,7 +194,7 @@ def test_default_and_exact_arithmetic(dev):
         # FAST_MATH (ABI 2's opt-in) = the default now; the module forward uses the default
         assert (tensor_to_bits(gemv_abi(m, xt, FAST)) == dflt).all()
         # (the reference test's distribution is above the load-time gate's bias line: the module serves it exact)
-        assert (tensor_to_bits(m(xt)) == (exact if (module_flags() | m._descriptor()[9]) & EXACT else dflt)).all()
+        assert (tensor_to_bits(m(xt)) == (exact if (module_flags() | m._descriptor().arithmetic_flags) & EXACT else dflt)).all()
 
 
 @pytest.mark.parametrize("name", [n for n in golden_names() if n.startswith("canon")])
@@ -856,7 +856,7 @@ def test_many_token_routes_vs_reference_goldens(name, dev):
     assert hashlib.sha256(tensor_to_bits(m.dequant()).tobytes()).hexdigest() == cfg["W_sha256"]
     xt = bits_to_tensor(x, dt, dev).reshape(x.shape)
     routes = {"module": lambda: m(xt), "dense_cached": lambda: m._dense_cached(xt),
-              "gemm_fused": lambda: ops.quant_gemm_fused(xt, m._descriptor()[1], L.out_features)}
+              "gemm_fused": lambda: ops.quant_gemm_fused(xt, m._descriptor().desc, L.out_features)}
     if T <= 64:
         # the batched-decode kernels (launches of 16 tokens): the one-pass kernel (default from 5 tokens, both dtypes) and
         # the kernel with the reference's roundings
@@ -1612,7 +1612,7 @@ def test_adversarial_families_reference_default(family, xkind, O, dev):
     want = vo.forward(L, x)
     m = spec_to_module(L, dev)
     xt = bits_to_tensor(x, "f16", dev).reshape(x.shape)
-    assert m._descriptor()[9] == EXACT
+    assert m._descriptor().arithmetic_flags == EXACT
     y = m(xt)
     assert torch.equal(y.view(torch.int16), gemv_abi(m, xt, EXACT).view(torch.int16))
     assert rel_err(tensor_to_bits(y), want, "f16") <= 1e-3      # (at most the flip of one last bit: 2^-10 of max|y|)
@@ -1632,7 +1632,7 @@ def test_adversarial_families_default_route(family, xkind, O, dev, folded_arithm
     want = vo.forward(L, x)
     m = spec_to_module(L, dev)
     xt = bits_to_tensor(x, "f16", dev).reshape(x.shape)
-    gated = m._descriptor()[9] != 0
+    gated = m._descriptor().arithmetic_flags != 0
     # (round 4: the cyclic pattern with in_features a multiple of k makes every index row the same - 8 distinct
     # outputs; layers with fewer than 32 distinct vector-rows are gated as well: tools/gpu_fuzz_count.py)
     # round 5: the gate MEASURES the folded form against the reference's roundings on probe activations (float32 outputs):
@@ -1659,9 +1659,9 @@ def test_adversarial_families_default_route(family, xkind, O, dev, folded_arithm
     import importlib
     qg = importlib.import_module("vptq_amd.ops.quant_gemm")   # (the package also exports a function of that name)
     assert (qg._safe_flags(m.indices, m.centroids.weight, m.res_centroids.weight, m.weight_scale, m.weight_bias,
-                           m._descriptor()[1], I, O) != 0) == gated
+                           m._descriptor().desc, I, O) != 0) == gated
     x6 = np.concatenate([x] * 6, axis=1)
     x6t = bits_to_tensor(x6, "f16", dev).reshape(x6.shape)
     y6 = m(x6t)
     assert rel_err(tensor_to_bits(y6)[:, 5:6], want, "f16") <= 1e-3, f"6 tokens, {family}/{xkind}"
-    assert kernel_name(m, 6, m._descriptor()[9]) == ("gemm_k256_kernel" if gated else "gemm_k256t_kernel")
+    assert kernel_name(m, 6, m._descriptor().arithmetic_flags) == ("gemm_k256_kernel" if gated else "gemm_k256t_kernel")

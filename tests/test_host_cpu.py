@@ -883,3 +883,102 @@ def test_one_launch_rule_for_two_to_four_tokens():
     for t in (2, 3):
         assert rule(14336, 4096, 8, 256, t, exact=True, slices=16, one_pass=2) and rule(4096, 14336, 8, 0, t, exact=True, slices=8, one_pass=2)
         assert not rule(4096, 4096, 8, 0, t, exact=True, slices=8, one_pass=2) and not rule(14336, 512, 8, 0, t, exact=True, slices=16, one_pass=2)
+
+
+def _rule_layer(I, O, v, kr, **more):
+    """stands in for a VQuantLinear in the sliced-route rules: what `_index_elements` / `_res_centroids` and the rules read"""
+    import types
+    return types.SimpleNamespace(indices=torch.empty(1, O // v, 1), group_size=I, vector_len=v, out_features=O,
+                                 num_res_centroids=kr, enable_residual=kr > 0, **more)
+
+
+def test_exact_route_size_rule_is_stated_once(monkeypatch):
+    """`_exact_route_is_large`, the one-token size rule of the reference arithmetic, at its boundaries (read from the constants), and
+    `_compact_refusal(force=False)` answering with that very function: compact mode keeps a layer's one-token speed BECAUSE it asks
+    the rule `_sliced_gemv` routes with - host logic, no GPU"""
+    import vptq_amd.layers.vqlinear as vq
+    import vptq_amd.utils.sliced as sliced
+    one, two = vq._SLICED_EXACT_MIN_ELEMENTS, vq._SLICED_EXACT_RG_MIN_ELEMENTS
+    assert (one, two) == (1 << 20, 2 << 20)
+    size_refusal = "one token takes the gather kernel for this layer (smaller than the exact sliced route's threshold; force=True compacts it)"
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    monkeypatch.setattr(sliced, "exact_column_parts", lambda desc, group_size: (1, 16))   # (the library serves every case: the size rule is asked)
+
+    class Indices:      # (packed indices "on a ROCm device", all zero: no bits past the end of a row)
+        is_cuda = True
+
+        def __init__(self, rows):
+            self.shape = (1, rows, 1)
+
+        def detach(self):
+            return torch.zeros(1, 1, 1, dtype=torch.int32)
+
+    def refusal(I, O, v, kr):
+        m = _rule_layer(I, O, v, kr, num_centroids=65536, num_codebooks=1, enable_outlier=False, enable_norm=True, total_index_bits=0)
+        m.indices = Indices(O // v)
+        m._parameters = {"indices": m.indices}
+        cache = vq.LayerCache("key", _family_desc(I, O, v, 65536, kr), [], torch.device("cpu"), None, 16, 1, torch.float16, 0, B.GEMV_EXACT, 0)
+        m._descriptor = lambda: cache
+        return vq.VQuantLinear._compact_refusal(m, False)
+
+    # (v, kr, I, O, the bound the case sits AT (want) or just below (not want) - None: no size is large enough -, want)
+    cases = ((8, 0, 4096, 2048, one, True), (8, 0, 4096, 2040, one, False), (8, 256, 4096, 2048, one, True), (8, 256, 4096, 2040, one, False),
+             (8, 4096, 8192, 2048, two, True), (8, 4096, 8192, 2040, two, False),
+             (8, 1024, 8192, 8192, None, False),     # a residual table under 4096 entries: the gather kernel holds it in LDS
+             (16, 256, 8192, 8192, None, False))     # v = 16 has no byte side stream: the "other residual" branch
+    for v, kr, I, O, bound, want in cases:
+        m = _rule_layer(I, O, v, kr)
+        if bound is not None:
+            assert vq._index_elements(m) == bound if want else bound - bound // 256 <= vq._index_elements(m) < bound
+        assert vq._res_centroids(m) == kr
+        assert vq._exact_route_is_large(m) is want, (v, kr, I, O)
+        assert refusal(I, O, v, kr) == (None if want else size_refusal), (v, kr, I, O)
+    # one rule, not two that agree today: the refusal follows whatever the function says
+    for v, kr, I, O, _, _ in cases:
+        monkeypatch.setattr(vq, "_exact_route_is_large", lambda layer: True)
+        assert refusal(I, O, v, kr) is None
+        monkeypatch.setattr(vq, "_exact_route_is_large", lambda layer: False)
+        assert refusal(I, O, v, kr) == size_refusal
+
+
+def test_sliced_token_limit_rule(monkeypatch):
+    """VQuantLinear._sliced_token_limit: most tokens served as one sliced launch per token (profiles/r04/sliced_tokens.txt, profiles/r05/
+    sliced_tokens_exact.txt as a rule) - host logic, no GPU"""
+    import types
+    import vptq_amd.layers.vqlinear as vq
+    monkeypatch.setattr(vq, "_SLICED_TOKENS_ENV", None)   # (the tuning override of the folded layouts' rule)
+
+    def limit(I, O, v, kr, exact, slices, tables=1):
+        sl = types.SimpleNamespace(exact=exact, slices=slices, layout=[None] * tables)
+        return vq.VQuantLinear._sliced_token_limit(_rule_layer(I, O, v, kr), sl)
+    assert limit(8192, 8192, 8, 256, True, 16) == 2
+    assert limit(8192, 8192, 8, 256, True, 8) == 1 and limit(4096, 4096, 8, 256, True, 16) == 1
+    assert limit(8192, 8192, 8, 65536, False, 16, 2) == 3
+    assert limit(8192, 8192, 16, 65536, False, 16, 2) == 2
+    assert limit(8192, 8192, 16, 1024, False, 16, 2) == 1
+    sl = types.SimpleNamespace(exact=True, slices=16, layout=[None])
+    assert vq.VQuantLinear._sliced_token_limit(_rule_layer(8192, 8192, 8, 256), sl) == 2 and sl._token_limit == 2   # (remembered on the layout)
+
+
+def test_layer_cache_record_keeps_its_positions(monkeypatch):
+    """`VQuantLinear._descriptor()` returns a `LayerCache`: eleven named fields in the order the positional readers depend on (the
+    benchmark reads `[1]`, `_gemv_cached` unpacks all eleven) - built on the CPU, the device-only steps stood in for"""
+    from vptq_amd.layers.vqlinear import LayerCache, VQuantLinear
+    assert LayerCache._fields == ("key", "desc", "keep", "device", "gemv", "max_tokens", "generation", "dtype", "device_index",
+                                  "arithmetic_flags", "workspace_bytes")
+    m = VQuantLinear(64, 32, vector_lens=[-1, 8], num_centroids=[-1, 256], num_res_centroids=[-1, 256], group_num=1,
+                     group_size=64, outlier_size=0, indices_as_float=False, enable_norm=True, enable_perm=False,
+                     is_indice_packed=True, bias=True, dtype=torch.float16, device="cpu", enable_proxy_error=False)
+    monkeypatch.setattr(B, "require_device", lambda *tensors: torch.device("cuda", 0))
+    monkeypatch.setattr(VQuantLinear, "_folded_form_is_safe", lambda self, tensors, desc=None: False)   # (the gate's probes run on a GPU)
+    cache = m._descriptor()
+    assert type(cache) is LayerCache and len(cache) == 11 and m._descriptor() is cache
+    assert cache[1] is cache.desc and isinstance(cache.desc, B.LayerDesc) and cache.desc.in_features == 64
+    assert cache[9] == cache.arithmetic_flags == B.GEMV_EXACT
+    assert cache[0] is cache.key and cache[2] is cache.keep and cache[3] is cache.device and cache[4] is cache.gemv
+    assert (cache[5], cache[6], cache[7], cache[8], cache[10]) == (cache.max_tokens, cache.generation, cache.dtype, cache.device_index,
+                                                                   cache.workspace_bytes)
+    assert cache.dtype == torch.float16 and cache.device_index == 0 and cache.generation == VQuantLinear._desc_generation
+    assert cache.max_tokens == B.lib().vptq_quant_gemv_max_tokens(cache.desc)
+    stand_in = LayerCache(*range(11))
+    assert stand_in[1] is stand_in.desc and stand_in[9] == stand_in.arithmetic_flags == 9

@@ -218,7 +218,7 @@ def test_tie_share():
 
 def test_two_builds_on_two_streams_are_identical(dev):
     m = make_layer(4096, 4096, 8, 65536, 256, torch.float16, seed=3, dev=dev)
-    d = m._descriptor()[1]
+    d = m._descriptor().desc
     n = B.lib().vptq_sliced_layout_supported_for(d, B.GEMV_EXACT)
     torch.cuda.synchronize()
     outs = []
@@ -248,7 +248,7 @@ def test_build_memory(dev):
     """a kernel build of an 8192^2 v8-k65536-256 layer takes the returned tensors and nothing else (+ 1 MiB: allocator rounding);
     the torch recipe's peak on the same indices is printed"""
     m = make_layer(8192, 8192, 8, 65536, 256, torch.float16, seed=9, dev=dev)
-    d = m._descriptor()[1]
+    d = m._descriptor().desc
     n = B.lib().vptq_sliced_layout_supported_for(d, B.GEMV_EXACT)
     peaks = {}
     for name in ("kernel", "torch"):

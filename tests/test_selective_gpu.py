@@ -115,7 +115,7 @@ def test_selective_grouped_siblings_and_the_fallbacks(dev):
     xb = vo.from_f32(xf, "f16")
     xt = bits_to_tensor(xb, "f16", dev).reshape(1, 1, I)
     n = len(ms)
-    descs = (B.LayerDesc * n)(*[m._descriptor()[1] for m in ms])
+    descs = (B.LayerDesc * n)(*[m._descriptor().desc for m in ms])
     assert B.lib().vptq_quant_gemv_grouped_kernel_name(descs, n, 1, B.GEMV_SELECTIVE).decode() == "gemv_k256m_kernel<selective>"
     ys = [torch.empty(1, 1, m.out_features, dtype=torch.float16, device=dev) for m in ms]
     xp = (C.c_void_p * n)(*[xt.data_ptr()] * n)
@@ -153,15 +153,15 @@ def test_module_forward_in_the_selective_arithmetic(dev, selective_arithmetic):
     assert vptq_amd.arithmetic() == "selective"
     L = vo.make_layer(8192, 8192, dist="llm", seed=11, dtype="f16")
     m = spec_to_module(L, dev)
-    assert m._descriptor()[9] in (B.GEMV_SELECTIVE, B.GEMV_EXACT)
+    assert m._descriptor().arithmetic_flags in (B.GEMV_SELECTIVE, B.GEMV_EXACT)
     xf = _x(8192, 12)
     xf[..., [100, 5000]] *= 50.0
     xb = vo.from_f32(xf, "f16")
     y = m(bits_to_tensor(xb, "f16", dev).reshape(1, 1, 8192))
     torch.cuda.synchronize()
     assert rel_err(tensor_to_bits(y), vo.forward(L, xb), "f16") <= 1e-3
-    if m._descriptor()[9] == B.GEMV_SELECTIVE:
-        assert kernel_name(m, 1, m._descriptor()[9]) == "gemv_k256m_kernel<selective>"
+    if m._descriptor().arithmetic_flags == B.GEMV_SELECTIVE:
+        assert kernel_name(m, 1, m._descriptor().arithmetic_flags) == "gemv_k256m_kernel<selective>"
     L2 = vo.make_layer(2048, 264, dist="llm", seed=13, dtype="f16", num_centroids=65536, num_res_centroids=256)
     m2 = spec_to_module(L2, dev)
     x2 = vo.from_f32(_x(2048, 14), "f16")
@@ -193,7 +193,7 @@ def test_selective_over_sliced_layouts(I, O, v, kr, kw, dev):
     dist = kw.pop("dist", "ref-test")
     L = vo.make_layer(I, O, dist=dist, seed=I + O + v + kr, dtype="f16", vector_len=v, num_centroids=65536, num_res_centroids=kr, **kw)
     m = spec_to_module(L, dev)
-    assert B.lib().vptq_quant_gemv_sliced_selective_supported(m._descriptor()[1]) == 1
+    assert B.lib().vptq_quant_gemv_sliced_selective_supported(m._descriptor().desc) == 1
     sl = SlicedGemv(m, selective=True)
     fo = SlicedGemv(m)
     assert sl.selective and not sl.exact and not sl.tokens_supported(2)
@@ -245,7 +245,7 @@ def test_module_takes_the_selective_sliced_route_for_two_table_formats(dev, sele
     assert rel_err(tensor_to_bits(y), vo.forward(L, xb), "f16") <= 1e-3
     sl = m.__dict__.get("_sliced")
     assert sl is not None and sl[1] is not None
-    if m._descriptor()[9] == B.GEMV_SELECTIVE:
+    if m._descriptor().arithmetic_flags == B.GEMV_SELECTIVE:
         assert sl[1].selective or sl[1].exact        # (exact: the load-time gate refused the selective form of this layer)
     L1 = vo.make_layer(4096, 2048, dist="llm", seed=23, dtype="f16", num_centroids=65536, num_res_centroids=256)
     m1 = spec_to_module(L1, dev)

@@ -53,7 +53,7 @@ def main():
     def run_single(fl=0):
         for m, y in zip(ring, ys):
             d = m._descriptor()
-            B.check(d[4](d[1], x.data_ptr(), y.data_ptr(), 1, fl, None, 0, B.current_stream_ptr(dev)), "gemv")
+            B.check(d.gemv(d.desc, x.data_ptr(), y.data_ptr(), 1, fl, None, 0, B.current_stream_ptr(dev)), "gemv")
 
     groups = {}
 
@@ -63,7 +63,7 @@ def main():
         if n not in groups:
             gl = []
             for i in range(0, R, n):
-                ds = [m._descriptor()[1] for m in ring[i:i + n]]
+                ds = [m._descriptor().desc for m in ring[i:i + n]]
                 k = len(ds)
                 gl.append((k, (B.LayerDesc * k)(*ds), (C.c_void_p * k)(*[x.data_ptr()] * k), (C.c_void_p * k)(*[y.data_ptr() for y in ys[i:i + k]])))
             groups[n] = gl

@@ -26,7 +26,7 @@ def main():
     ring = [bench.make_layer(I, O, dev, g) for _ in range(n)]
     x = torch.randn(1, 1, I, device=dev, generator=g).half()
     ys = [torch.empty(1, 1, O, dtype=torch.float16, device=dev) for _ in range(n)]
-    descs = (B.LayerDesc * n)(*[m._descriptor()[1] for m in ring])
+    descs = (B.LayerDesc * n)(*[m._descriptor().desc for m in ring])
     xp = (C.c_void_p * n)(*[x.data_ptr()] * n)
     yp = (C.c_void_p * n)(*[y.data_ptr() for y in ys])
     ws = torch.zeros(256 * 16 * 64, dtype=torch.int64, device=dev)

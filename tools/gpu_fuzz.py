@@ -122,7 +122,7 @@ def fuzz_adversarial(a, dev):
         want = vo.forward(L, x)
         m = spec_to_module(L, dev)
         xt = bits_to_tensor(x, "f16", dev).reshape(x.shape)
-        gated = m._descriptor()[9] != 0
+        gated = m._descriptor().arithmetic_flags != 0
         errs = {"default_route": rel_err(tensor_to_bits(m(xt)), want, "f16"),
                 "chain_route": rel_err(tensor_to_bits(GemvChain([m, m])([xt, xt], flags=None if gated else 8)[1]), want, "f16"),
                 "folded_form": rel_err(tensor_to_bits(gemv_abi(m, xt, 0)), want, "f16"),
@@ -286,7 +286,7 @@ def fuzz_sliced(a, dev):
         ex = -1.0
         sx = None
         from vptq_amd.utils.sliced import exact_column_parts
-        if exact_column_parts(m._descriptor()[1], I)[0]:    # (in one piece, or - layers wider than ~16300 columns - as 2 / 3 column parts)
+        if exact_column_parts(m._descriptor().desc, I)[0]:    # (in one piece, or - layers wider than ~16300 columns - as 2 / 3 column parts)
             sx = SlicedGemv(m, rows_per_wave=rpw, exact=True)
             print(f"  exact layout built (slices {sx.slices}, column parts {sx.parts})", flush=True)
             gx = sx(xt)

@@ -119,7 +119,7 @@ def main():
             ch = GemvChain(list(layers))
             outs = {}
             kn = ch.kernel_name(1, 0) or "?"
-            gated = any(m._descriptor()[9] for m in layers)
+            gated = any(m._descriptor().arithmetic_flags for m in layers)
             if gated:
                 kn += "+gate"
             outs["chain:" + kn] = (ch(list(xs), flags=0), ch(list(xs), flags=B.GEMV_OUT_F32))
@@ -127,17 +127,17 @@ def main():
                 kx = ch.kernel_name(1, B.GEMV_EXACT) or "?"
                 outs["chain-exact:" + kx] = (ch(list(xs), flags=B.GEMV_EXACT), ch(list(xs), flags=B.GEMV_EXACT | B.GEMV_OUT_F32))
             # single launches with the kernel pinned; like every product route they carry the layer's load-time gate
-            # (VQuantLinear._descriptor()[9]); "ungated" = the folded form whatever the gate says (reported, not counted)
+            # (VQuantLinear._descriptor().arithmetic_flags); "ungated" = the folded form whatever the gate says (reported, not counted)
             for tag, fl, gate in (("mfma", B.GEMV_FORCE_MFMA, True), ("valu", B.GEMV_FORCE_VALU, True), ("ungated-mfma", B.GEMV_FORCE_MFMA, False)):
                 y16, y32 = [], []
                 for m, x in zip(layers, xs):
                     d = m._descriptor()
-                    fg = fl | (d[9] if gate else 0)
-                    name = B.lib().vptq_quant_gemv_kernel_name(d[1], 1, fg)
+                    fg = fl | (d.arithmetic_flags if gate else 0)
+                    name = B.lib().vptq_quant_gemv_kernel_name(d.desc, 1, fg)
                     names[tag] = name.decode() if name else "?"
                     for out, f in ((y16, fg), (y32, fg | B.GEMV_OUT_F32)):
                         y = torch.empty(1, 1, O, dtype=torch.float32 if f & B.GEMV_OUT_F32 else dt, device=dev)
-                        B.check(B.lib().vptq_quant_gemv(d[1], x.data_ptr(), y.data_ptr(), 1, f, None, 0, B.current_stream_ptr(dev)), "gemv")
+                        B.check(B.lib().vptq_quant_gemv(d.desc, x.data_ptr(), y.data_ptr(), 1, f, None, 0, B.current_stream_ptr(dev)), "gemv")
                         out.append(y)
                 outs[tag + ":" + names[tag]] = (y16, y32)
             # 8 tokens through the one-pass batched-decode kernel (row 0 = the layer's x, the others scaled copies)
@@ -145,7 +145,7 @@ def main():
             for m, x in zip(layers, xs):
                 x8 = (x.reshape(1, -1).float() * torch.linspace(1.0, 0.3, 8, device=dev).view(8, 1)).to(dt).view(1, 8, I).contiguous()
                 d = m._descriptor()
-                name = B.lib().vptq_quant_gemv_kernel_name(d[1], 8, 0)
+                name = B.lib().vptq_quant_gemv_kernel_name(d.desc, 8, 0)
                 names["tok8"] = name.decode() if name else "?"
                 y16.append(m(x8)[:, :1, :])
             outs["tok8:" + names["tok8"]] = (y16, None)

@@ -138,9 +138,9 @@ def main_chain(a):
             # ("grouped": every layer of this list was turned to the reference's roundings by its load-time gate and the chain kernel has
             # no bf16 form of them - the list then goes out as grouped launches)
             assert name in ("gemv_k256c_kernel", "grouped"), name
-            gated += sum(int(bool(m._descriptor()[9] & B.GEMV_EXACT)) for m in ms)
+            gated += sum(int(bool(m._descriptor().arithmetic_flags & B.GEMV_EXACT)) for m in ms)
             if a.probe:
-                probes += [float(B.folded_probe_distance(m._descriptor()[1], m.in_features, m.out_features, m.weight_bias.data, dt, dev)) for m in ms]
+                probes += [float(B.folded_probe_distance(m._descriptor().desc, m.in_features, m.out_features, m.weight_bias.data, dt, dev)) for m in ms]
             ys = ch(xs, flags=fl)
             for m, x, y in zip(ms, xs, ys):
                 W = m.dequant()
@@ -200,7 +200,7 @@ def main():
             m = make(I, O, fam, dt, dev, g)
             x = make_x(m, XKINDS[(done + i) % len(XKINDS)], dt, dev, g)
             d = m._descriptor()
-            gated = bool(d[9] & B.GEMV_EXACT) if vptq_amd.arithmetic() != "reference" else False   # (sent to the reference roundings by the load-time gate)
+            gated = bool(d.arithmetic_flags & B.GEMV_EXACT) if vptq_amd.arithmetic() != "reference" else False   # (sent to the reference roundings by the load-time gate)
             st["gated"] += int(gated)
             W = m.dequant()
             s64 = W.double() @ x.reshape(-1).double()
@@ -209,9 +209,9 @@ def main():
             y = m(x)                                                  # the product route (with the gate)
             st["err"].append(float((y.reshape(-1).double() - r16.double()).abs().max() / den))
             yr = torch.empty(1, 1, O, dtype=dt, device=dev)          # the folded form whatever the gate says (information)
-            B.check(B.lib().vptq_quant_gemv(d[1], x.data_ptr(), yr.data_ptr(), 1, 0, None, 0, B.current_stream_ptr(dev)), "gemv")
+            B.check(B.lib().vptq_quant_gemv(d.desc, x.data_ptr(), yr.data_ptr(), 1, 0, None, 0, B.current_stream_ptr(dev)), "gemv")
             st["raw"].append(float((yr.reshape(-1).double() - r16.double()).abs().max() / den))
-            st["probe"].append(float(B.folded_probe_distance(d[1], I, O, m.weight_bias.data, dt, dev)))
+            st["probe"].append(float(B.folded_probe_distance(d.desc, I, O, m.weight_bias.data, dt, dev)))
             del m, W
         done += per
         print(f"# {fam}: {per} layers done after {time.time() - t0:.0f} s", flush=True)

@@ -96,7 +96,7 @@ def main():
     def run_single():
         for m, y in zip(ring, ys):
             d = m._descriptor()
-            B.check(d[4](d[1], x.data_ptr(), y.data_ptr(), 1, 0, None, 0, B.current_stream_ptr(dev)), "gemv")
+            B.check(d.gemv(d.desc, x.data_ptr(), y.data_ptr(), 1, 0, None, 0, B.current_stream_ptr(dev)), "gemv")
 
     chain = GemvChain(ring)
 

@@ -23,7 +23,7 @@ quantisation algorithm, which is not part of this hot path.
 from __future__ import annotations
 
 import math
-from typing import Sequence
+from typing import NamedTuple, Sequence
 
 import os
 import weakref
@@ -70,9 +70,58 @@ _SLICED_ONE_LAUNCH = B.tune_env("VPTQ_SLICED_ONE_LAUNCH", "auto").strip().lower(
 
 _SLICED_SELECTIVE_MIN_ELEMENTS = 6 << 20   # selective roundings over the folded sliced layouts (two-table formats): from 6 M index elements on
 _SLICED_OOM_RETRY_CALLS = 256   # calls of a layer before a sliced-layout build that ran out of memory is tried again
+_SLICED_FORMATS = "v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no outliers, scale / bias"   # `_has_sliced_format` in words
 
 
 _COMPACTED = weakref.WeakSet()   # compacted layers (their share of the compact-mode scratch)
+
+
+class LayerCache(NamedTuple):
+    """What `VQuantLinear._descriptor()` builds once per set of parameter storages.  The ORDER is part of the contract (`_gemv_cached`
+    unpacks it by position: one unpack is cheaper than eleven attribute reads per call; the benchmark reads `[1]`): new fields go last."""
+    key: tuple              # storage pointers, version counters, arithmetic generation: a different key rebuilds the whole record
+    desc: object            # the C-ABI LayerDesc: what every launch of this layer passes to the library
+    keep: list              # the tensors `desc` points at, derived ones included: alive as long as the record is
+    device: torch.device    # the parameters' device: activations are checked against it, launches run under it
+    gemv: object            # the library's vptq_quant_gemv entry: called by `_gemv_cached`
+    max_tokens: int         # most tokens the fused GEMV takes for this format: `forward` and the shards route on it
+    generation: int         # unique per record built: SiblingGroup, GemvChain, the sliced layout, the dense descriptor and compact mode key on it
+    dtype: torch.dtype      # the centroids' dtype: activations are checked against it, outputs are allocated in it
+    device_index: int       # `device` as an index: the raw-stream and workspace look-ups of every launch
+    arithmetic_flags: int   # load-time arithmetic gate (GEMV_EXACT / GEMV_SELECTIVE / 0), or-ed into every launch's flags; set_arithmetic renews it via `key`
+    workspace_bytes: int    # scratch bytes of the batched-decode kernel: `B.gemv_workspace` of 2+ token launches
+
+
+def _index_elements(layer) -> int:   # index elements per table: vector-rows x columns
+    return layer.indices.shape[1] * layer.group_size
+
+
+def _res_centroids(layer) -> int:   # entries of the residual codebook; 0 without one
+    return layer.num_res_centroids if layer.enable_residual else 0
+
+
+def _has_sliced_format(layer) -> bool:
+    """can a layer of this format have a sliced layout at all?  Static module configuration (a permutation may still be absorbed
+    later; the library decides: vptq_sliced_layout_supported)."""
+    return bool(layer.num_centroids >= 16384 and layer.vector_len in (8, 16) and layer.num_codebooks == 1 and
+                not layer.enable_outlier and layer.enable_norm)
+
+
+def _exact_route_is_large(layer) -> bool:
+    """The one-token size rule of the reference arithmetic: is the layer large enough for the exact sliced kernel to beat the
+    gather kernel?  (`enable_sliced_layout()` asks for the layout on any layer: `_sliced_gemv` adds that opt-in.)"""
+    n_el, kr = _index_elements(layer), _res_centroids(layer)
+    if kr > 0 and not (layer.vector_len == 8 and kr == 256):
+        # any other residual codebook: its entries are gathered from L2 behind the LDS-local main gathers (2 blocks per
+        # queue stage: the CU's L1 miss path is the limit) - us per layer, gather kernels -> sliced, profiles/r05/
+        # sliced_exact_two_table_queue_ab.txt: v8-k65536-65536 8192^2 78.0 -> 59.9, 14336 x 4096 68.5 -> 52.2, 4096^2 21.6 ->
+        # 21.2; v8-k65536-4096 69.9 -> 50.6 / 59.8 -> 44.3 / 20.5 -> 18.4; v16-k65536-65536 53.9 -> 46.7 / 52.3 -> 40.9 / 19.2 ->
+        # 18.3; small residual tables (v16-k65536-1024: the gather kernel holds them in LDS) stay there
+        return kr >= 4096 and n_el >= _SLICED_EXACT_RG_MIN_ELEMENTS
+    # (reference roundings, us per layer, gather -> exact sliced, profiles/r05/sliced_exact.txt: 8192^2 39.4 -> 17.2,
+    # 4096 x 14336 34.5 -> 17.0, 14336 x 4096 34.9 -> 14.7, 4096^2 12.6 -> 9.0, 4096 x 1024 7.8 -> 8.3: from 1 M index elements -
+    # 8 M weights - on)
+    return n_el >= _SLICED_EXACT_MIN_ELEMENTS
 
 
 def _compact_state_dict_hook(module, state_dict, prefix, local_metadata):
@@ -176,14 +225,15 @@ class SiblingGroup:
                 # a rebuilt layout or another arithmetic (set_arithmetic) makes new objects and the group is looked at again
                 sg = (key, None)
             self._sgroup = sg
-        if sg[1] is None:
+        group = sg[1]
+        if group is None:
             return None
         if tokens == 1:
-            ys = sg[1](x)
+            ys = group(x)
         else:   # (every member must be a layer this route was measured faster for: VQuantLinear._sliced_one_launch)
             if not all(m._sliced_one_launch(sl, tokens) for m, sl in zip(self.members, sls)):
                 return None
-            ys = sg[1].forward_tokens(x)
+            ys = group.forward_tokens(x)
         if ys is None:
             return None
         self._sx, self._sversion, self._keep_sx = x, ver, x
@@ -206,28 +256,29 @@ class SiblingGroup:
         self._out = {}     # a new leader call: whatever an earlier one left unconsumed is stale
         xc = layer._check_activation(x)
         caches = [m._descriptor() for m in self.members]
-        dev = caches[0][3]
-        if any(c[3] != dev for c in caches) or xc.device != dev or \
+        dev = caches[0].device
+        if any(c.device != dev for c in caches) or xc.device != dev or \
                 any(m.in_features != layer.in_features for m in self.members):
             raise RuntimeError("sibling layers must share the device and the input width")
-        key = tuple(c[6] for c in caches)  # descriptor generations: a rebuilt descriptor never matches
-        if (self._arrays is None or self._arrays[0] != key) and any("_compact" in m.__dict__ for m in self.members):
+        key = tuple(c.generation for c in caches)  # a rebuilt descriptor never matches
+        stale = self._arrays is None or self._arrays[0] != key
+        if stale and any("_compact" in m.__dict__ for m in self.members):
             # a compacted member has no packed indices for the grouped launch to read: every member launches for itself (compacting
             # or uncompacting a layer rebuilds its descriptor: a new key)
             self._arrays = (key, None, None)
-        if self._arrays is None or self._arrays[0] != key:
+        elif stale:
             import ctypes as C
             # one launch per ARITHMETIC: the members the load-time gate sends to the reference's roundings (VPTQ_GEMV_EXACT) go out as a
             # launch of their own, so that one such layer does not drag its siblings out of the selective / folded form (bf16 layers sit
             # close to the gate: with every group exact as soon as one member is, a decoder ran at the reference's speed)
             parts = []
             for want in (False, True):
-                idx = [i for i, c in enumerate(caches) if bool(c[9] & B.GEMV_EXACT) == want]
+                idx = [i for i, c in enumerate(caches) if bool(c.arithmetic_flags & B.GEMV_EXACT) == want]
                 if idx:
                     fl = 0
                     for i in idx:
-                        fl |= caches[i][9]
-                    parts.append((idx, (B.LayerDesc * len(idx))(*[caches[i][1] for i in idx]), (C.c_void_p * len(idx))(),
+                        fl |= caches[i].arithmetic_flags
+                    parts.append((idx, (B.LayerDesc * len(idx))(*[caches[i].desc for i in idx]), (C.c_void_p * len(idx))(),
                                   (C.c_void_p * len(idx))(), fl))
             self._arrays = (key, parts, B.lib().vptq_quant_gemv_grouped)
         _, parts, fn = self._arrays
@@ -235,7 +286,7 @@ class SiblingGroup:
             return None
         ys = [torch.empty(xc.shape[:-1] + (m.out_features,), dtype=xc.dtype, device=dev)
               for m in self.members]
-        dev_index = caches[0][8]
+        dev_index = caches[0].device_index
         base_flags = ops.quant_gemm_flags()
 
         def launch(sp):
@@ -398,7 +449,7 @@ class VQuantLinear(nn.Module):
                 "enable_proxy_error=False (HF does).")
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
-                (tokens <= B.GEMV_ANY_FORMAT_TOKENS or tokens <= self._descriptor()[5]):
+                (tokens <= B.GEMV_ANY_FORMAT_TOKENS or tokens <= self._descriptor().max_tokens):
             return self._gemv_cached(x, tokens)
         if tokens >= 1 and x.is_cuda and ops.fused_gemm_max_tokens() < tokens:
             return self._dense_cached(x)
@@ -432,9 +483,9 @@ class VQuantLinear(nn.Module):
         )
 
     def _descriptor(self):
-        """(desc, device, keep-alive): the C-ABI descriptor of this layer, built once and reused
-        while the parameter storages stay the same (building it costs ~25 us of Python per call,
-        several times the kernel itself)."""
+        """This layer's `LayerCache`: the C-ABI descriptor and what the launches need beside it, built once
+        and reused while the parameter storages stay the same (building it costs ~25 us of Python per
+        call, several times the kernel itself)."""
         # parameters straight out of the module's dicts: nn.Module.__getattr__ costs ~0.4 us per name,
         # ten names per call were a third of this function (tools/py_overhead.py)
         P, M = self._parameters, self._modules
@@ -454,35 +505,40 @@ class VQuantLinear(nn.Module):
         if perm is not None:
             key += (B.tensor_version(perm), B.tensor_version(tensors[6]), B.tensor_version(tensors[7]))
         cache = self.__dict__.get("_desc_cache")
-        if cache is None or cache[0] != key:
+        if cache is None or cache.key != key:
             # compact mode (the meta `indices` of a compacted layer are part of the key with pointer 0): the descriptor's `indices` is the
             # layout's stand-in, and there is no prefetch from or of a layer without packed indices
             cp = self.__dict__.get("_compact")
             if cp is not None or (nxt is not None and "_compact" in nxt.__dict__):
                 tensors = (tensors[0] if cp is None else cp["standin"],) + tensors[1:9] + (None,)
             dev = B.require_device(*[t for t in tensors if t is not None])
-            desc, keep = B.make_layer_desc(
-                indices=tensors[0], centroids=tensors[1], res_centroids=tensors[2],
-                outlier_indices=tensors[3], outlier_centroids=tensors[4], perm=tensors[5],
-                weight_scale=tensors[6], weight_bias=tensors[7], bias=tensors[8],
-                in_features=self.in_features, out_features=self.out_features,
-                vector_len=self.vector_len, num_codebooks=self.num_codebooks,
-                num_centroids=self.num_centroids,
-                num_res_centroids=self.num_res_centroids if self.enable_residual else 0,
-                group_size=self.group_size,
-                outlier_size=self.outlier_size if self.enable_outlier else 0,
-                outlier_vector_len=self.outlier_vector_len,
-                num_outlier_centroids=self.num_outlier_centroids, prefetch=tensors[9])
+            desc, keep = B.make_layer_desc(bias=tensors[8], prefetch=tensors[9], **self._layer_desc_keywords())
             VQuantLinear._desc_generation += 1
-            cache = (key, desc, keep, dev, B.lib().vptq_quant_gemv,
-                     B.lib().vptq_quant_gemv_max_tokens(desc), VQuantLinear._desc_generation,
-                     tensors[1].dtype, dev.index if dev.index is not None else torch.cuda.current_device(),
-                     # (compact mode: the gate is frozen at "refused" - it would read index data -, i.e. the reference's roundings in every
-                     # arithmetic, the documented fallback of every route without a selective form)
-                     B.GEMV_EXACT if cp is not None else B.layer_arithmetic_flags(self._folded_form_is_safe(tensors, desc)),
-                     B.lib().vptq_quant_gemv_workspace_bytes(desc, 16, 0))   # [10]: scratch bytes of the batched-decode kernel
+            cache = LayerCache(
+                key, desc, keep, dev, B.lib().vptq_quant_gemv, B.lib().vptq_quant_gemv_max_tokens(desc), VQuantLinear._desc_generation,
+                tensors[1].dtype, dev.index if dev.index is not None else torch.cuda.current_device(),
+                # (compact mode: the gate is frozen at "refused" - it would read index data -, i.e. the reference's roundings in every
+                # arithmetic, the documented fallback of every route without a selective form)
+                B.GEMV_EXACT if cp is not None else B.layer_arithmetic_flags(self._folded_form_is_safe(tensors, desc)),
+                B.lib().vptq_quant_gemv_workspace_bytes(desc, 16, 0))
             self.__dict__["_desc_cache"] = cache
         return cache
+
+    def _layer_desc_keywords(self) -> dict:
+        """the `B.make_layer_desc` keywords every descriptor of this layer shares (compact mode: `indices` is the layout's stand-in);
+        the caller adds `bias` and `prefetch` or `need_inv_perm`"""
+        P, M = self._parameters, self._modules
+        cp = self.__dict__.get("_compact")
+        return dict(
+            indices=P["indices"] if cp is None else cp["standin"], centroids=M["centroids"]._parameters["weight"],
+            res_centroids=M["res_centroids"]._parameters["weight"] if self.enable_residual else None,
+            outlier_indices=P.get("outlier_indices"),
+            outlier_centroids=M["outlier_centroids"]._parameters["weight"] if self.enable_outlier else None,
+            perm=P.get("perm") if self.enable_perm else None, weight_scale=P.get("weight_scale"), weight_bias=P.get("weight_bias"),
+            in_features=self.in_features, out_features=self.out_features, vector_len=self.vector_len,
+            num_codebooks=self.num_codebooks, num_centroids=self.num_centroids, num_res_centroids=_res_centroids(self),
+            group_size=self.group_size, outlier_size=self.outlier_size if self.enable_outlier else 0,
+            outlier_vector_len=self.outlier_vector_len, num_outlier_centroids=self.num_outlier_centroids)
 
     def _folded_form_is_safe(self, tensors, desc=None) -> bool:
         """Load-time gate of the library's default ("folded") decode arithmetic (`_backend.folded_form_is_safe`): the layer
@@ -552,12 +608,11 @@ class VQuantLinear(nn.Module):
             why = "indices are not on a ROCm device"
         elif torch.cuda.is_current_stream_capturing():
             why = "inside a stream capture"
-        elif not (self.num_centroids >= 16384 and self.vector_len in (8, 16) and self.num_codebooks == 1 and not self.enable_outlier and
-                  self.enable_norm):
+        elif not _has_sliced_format(self):
             self._descriptor()
-            why = "format has no sliced layout (v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no outliers, scale / bias)"
+            why = f"format has no sliced layout ({_SLICED_FORMATS})"
         if why is None:
-            dev = self._descriptor()[3]
+            dev = self._descriptor().device
             with torch.cuda.device(dev):
                 s = torch.cuda.current_stream(dev) if stream is None else stream
                 with torch.cuda.stream(s):
@@ -576,7 +631,7 @@ class VQuantLinear(nn.Module):
                           "too little free device memory for the layout)"
             else:
                 rep["built"] = "exact" if sl.exact else ("selective" if sl.selective else "folded")
-                rep["bytes"] = sum(t.numel() * t.element_size() for tup in sl._tensors for t in tup if t is not None)
+                rep["bytes"] = sl.layout_bytes()
         if why is not None:
             rep["built"] = why
         rep["seconds"] = time.perf_counter() - t0
@@ -588,8 +643,8 @@ class VQuantLinear(nn.Module):
             # compact mode: the exact layout is the only copy of the indices - served in every arithmetic, whatever
             # VPTQ_SLICED_LAYOUT says, never rebuilt (a rebuilt descriptor is only re-attached)
             cache = self._descriptor()
-            if cp["gen"] != cache[6]:
-                cp["sl"], cp["gen"] = cp["sl"].rebound(cache[1]), cache[6]
+            if cp["gen"] != cache.generation:
+                cp["sl"], cp["gen"] = cp["sl"].rebound(cache.desc), cache.generation
             return cp["sl"]
         on = self.__dict__.get("_sliced_on")
         if on is None:
@@ -599,52 +654,37 @@ class VQuantLinear(nn.Module):
         cache = self._descriptor()
         st = self.__dict__.get("_sliced")
         # (a rebuilt descriptor = other tensors; a bumped version counter = indices rewritten in place: rebuild)
-        stamp = (cache[6], B.tensor_version(self._parameters["indices"]))
+        stamp = (cache.generation, B.tensor_version(self._parameters["indices"]))
         if st is None or st[0] != stamp:
             if torch.cuda.is_current_stream_capturing():
                 return None   # (no layout is built inside a capture - and the "no" is not remembered: a later call builds it)
             obj = None
-            # the layer's arithmetic (cache[9]): the reference's roundings (the default) take the EXACT sliced kernel where it
-            # serves the layer - no residual codebook or the 256-entry one of v = 8, up to ~16000 columns; the others keep the
-            # gather kernel -, the opt-in folded form the folded one
-            exact = bool(cache[9] & (B.GEMV_EXACT | B.GEMV_SELECTIVE))   # (selective: the one-table formats take the reference's roundings)
-            # ... the two-table ones (v8-k65536-65536, v16-k65536-65536, ...: 59 / 46 us in the reference's roundings, the residual entry an
-            # L2 gather per element) the FOLDED layouts with VPTQ_GEMV_SELECTIVE - a pre-pass zeroes the blocks an activation dominates and
-            # hands their exact products to the folded launch (gemv_hot.hip): ~21 us
-            kr0 = self.num_res_centroids if self.enable_residual else 0
-            # (the pre-pass is a launch of its own, ~9 us at 8192^2: it pays on the large layers - from 6 M index elements on - where the
-            # reference's roundings cost 46 - 59 us; smaller two-table layers keep the exact layouts)
-            selective = bool(cache[9] & B.GEMV_SELECTIVE) and not (cache[9] & B.GEMV_EXACT) and kr0 >= 4096 and \
-                (self.indices.shape[1] * self.group_size >= _SLICED_SELECTIVE_MIN_ELEMENTS or "_sliced_on" in self.__dict__) and \
-                bool(B.lib().vptq_quant_gemv_sliced_selective_supported(cache[1])) and bool(B.lib().vptq_sliced_layout_supported_for(cache[1], 0))
-            if selective:
-                exact = False
-            # (reference roundings, us per layer, gather -> exact sliced, profiles/r05/sliced_exact.txt: 8192^2 39.4 -> 17.2,
-            # 4096 x 14336 34.5 -> 17.0, 14336 x 4096 34.9 -> 14.7, 4096^2 12.6 -> 9.0, 4096 x 1024 7.8 -> 8.3: from 1 M index elements -
-            # 8 M weights - on; enable_sliced_layout() asks for it on any layer)
-            n_el = self.indices.shape[1] * self.group_size
-            kr_ = self.num_res_centroids if self.enable_residual else 0
-            if exact and kr_ > 0 and not (self.vector_len == 8 and kr_ == 256):
-                # any other residual codebook: its entries are gathered from L2 behind the LDS-local main gathers (2 blocks per
-                # queue stage: the CU's L1 miss path is the limit) - us per layer, gather kernels -> sliced, profiles/r05/
-                # sliced_exact_two_table_queue_ab.txt: v8-k65536-65536 8192^2 78.0 -> 59.9, 14336 x 4096 68.5 -> 52.2, 4096^2 21.6 ->
-                # 21.2; v8-k65536-4096 69.9 -> 50.6 / 59.8 -> 44.3 / 20.5 -> 18.4; v16-k65536-65536 53.9 -> 46.7 / 52.3 -> 40.9 / 19.2 ->
-                # 18.3; small residual tables (v16-k65536-1024: the gather kernel holds them in LDS) stay there
-                big = (kr_ >= 4096 and n_el >= _SLICED_EXACT_RG_MIN_ELEMENTS) or "_sliced_on" in self.__dict__
-            else:
-                big = n_el >= _SLICED_EXACT_MIN_ELEMENTS or "_sliced_on" in self.__dict__
             from vptq_amd.utils.sliced import SlicedGemv, exact_column_parts
-            # (reference roundings: layers too wide for the LDS in one piece - 28672 columns - are served as equal column parts)
-            served = exact_column_parts(cache[1], self.group_size)[0] if exact else B.lib().vptq_sliced_layout_supported_for(cache[1], 0)
-            if selective:
-                big = True
-            if (big or not (exact or selective)) and served and self._sliced_fits(cache, on):
+            desc, flags, lib, n_el = cache.desc, cache.arithmetic_flags, B.lib(), _index_elements(self)
+            opted = "_sliced_on" in self.__dict__   # (enable_sliced_layout() asks for a layout on any layer)
+            # the layer's arithmetic (`arithmetic_flags`) decides the kind of layout, the kind's own rule whether one is wanted
+            if flags & B.GEMV_SELECTIVE and not flags & B.GEMV_EXACT and _res_centroids(self) >= 4096 and \
+                    (n_el >= _SLICED_SELECTIVE_MIN_ELEMENTS or opted) and \
+                    lib.vptq_quant_gemv_sliced_selective_supported(desc) and lib.vptq_sliced_layout_supported_for(desc, 0):
+                # selective roundings, two-table formats (v8-k65536-65536, v16-k65536-65536, ...: 59 / 46 us in the reference's roundings, the
+                # residual entry an L2 gather per element): the FOLDED layouts with VPTQ_GEMV_SELECTIVE - a pre-pass zeroes the blocks an activation
+                # dominates and hands their exact products to the folded launch (gemv_hot.hip): ~21 us (the pre-pass is a launch of its own, ~9 us
+                # at 8192^2: it pays on the large layers - from 6 M index elements on -; smaller two-table layers keep the exact layouts)
+                kind, wanted = "selective", True
+            elif flags & (B.GEMV_EXACT | B.GEMV_SELECTIVE):
+                # the reference's roundings (the default; selective: its one-table and smaller two-table layers) take the EXACT sliced kernel
+                # where the layer is large enough and served - too wide for the LDS in one piece, 28672 columns: as equal column parts
+                kind, wanted = "exact", (_exact_route_is_large(self) or opted) and bool(exact_column_parts(desc, self.group_size)[0])
+            else:   # the opt-in folded form: the folded layouts wherever the library has them
+                kind, wanted = "folded", bool(lib.vptq_sliced_layout_supported_for(desc, 0))
+            exact, selective = kind == "exact", kind == "selective"
+            if wanted and self._sliced_fits(cache, on):
                 # (a build that ran out of device memory is retried only after a back-off: every attempt costs int64 / float64
                 # temporaries of ~160 bytes per element, an empty_cache() and a warning - per decode call, while memory stays tight)
                 oom = self.__dict__.get("_sliced_oom")
                 if oom is not None:
                     oom[0] -= 1
-                    free = torch.cuda.mem_get_info(cache[3])[0] if oom[0] > 0 else 0
+                    free = torch.cuda.mem_get_info(cache.device)[0] if oom[0] > 0 else 0
                     if oom[0] > 0 and free < oom[1]:
                         return None
                 try:
@@ -658,25 +698,25 @@ class VQuantLinear(nn.Module):
                     if oom is None:   # (warn once per layer)
                         warnings.warn(f"sliced layout of a {self.in_features} x {self.out_features} layer not built "
                                       f"({str(e)[:120]}); the layer keeps the gather kernel for now", stacklevel=3)
-                    self.__dict__["_sliced_oom"] = [_SLICED_OOM_RETRY_CALLS, 2 * torch.cuda.mem_get_info(cache[3])[0] + (n_el * 160)]
+                    self.__dict__["_sliced_oom"] = [_SLICED_OOM_RETRY_CALLS, 2 * torch.cuda.mem_get_info(cache.device)[0] + (n_el * 160)]
                     return None
                 # the kernel over the layouts evaluates the folded form: the same measured gate as every folded route
                 # (_backend.folded_form_is_safe) - its float32 outputs against the gather kernel's (the reference's roundings)
                 # on the probe activations
-                lim = None if exact else (B.SELECTIVE_MAX_PROBE_DISTANCE if selective else B.FOLDED_MAX_PROBE_DISTANCE).get(cache[7])
+                lim = None if exact else (B.SELECTIVE_MAX_PROBE_DISTANCE if selective else B.FOLDED_MAX_PROBE_DISTANCE).get(cache.dtype)
                 if lim is not None and self._parameters.get("weight_bias") is not None:
                     run = obj
 
                     def folded(xr, yr):
                         return run(xr.view(1, 1, -1), yr.view(1, 1, -1), flags=B.GEMV_OUT_F32) is not None
-                    d = B.folded_probe_distance(cache[1], self.in_features, self.out_features, self._parameters["weight_bias"],
-                                                cache[7], cache[3], folded=folded)
+                    d = B.folded_probe_distance(desc, self.in_features, self.out_features, self._parameters["weight_bias"],
+                                                cache.dtype, cache.device, folded=folded)
                     if not bool((d <= lim).item()):
                         obj = None
                         if selective:
                             # the gate refused the selective form of this layer: the reference's roundings over an exact layout
                             # (main entry from LDS, residual entry from L2), where that route serves it
-                            if exact_column_parts(cache[1], self.group_size)[0] and self._sliced_fits(cache, on):
+                            if exact_column_parts(desc, self.group_size)[0] and self._sliced_fits(cache, on):
                                 try:
                                     obj = SlicedGemv(self, exact=True)
                                 except (torch.cuda.OutOfMemoryError, ValueError):
@@ -693,19 +733,16 @@ class VQuantLinear(nn.Module):
         against 40.2 / 44.0 / 24.1; small residual tables of v = 16: never)"""
         lim = sl.__dict__.get("_token_limit")
         if lim is None:
+            n_el, kr = _index_elements(self), _res_centroids(self)
             if sl.exact:
                 # the reference's roundings: the gather kernels take 2 - 8 tokens for the price of one; TWO exact sliced launches beat
                 # them on large v = 8 one-table layers only (profiles/r05/sliced_tokens_exact.txt, gather -> 2 launches, v8-k65536-256 /
                 # -0: 8192^2 41.8 -> 40.0 / 41.4 -> 32.9; 14336 x 4096 37.0 -> 32.6 / 37.1 -> 27.9; 8192 x 28672 148.7 -> 94.8 / 135.1 ->
                 # 80.9; but 4096 x 14336 36.7 -> 37.4, 4096^2 13.5 -> 19.5)
-                n_el = self.indices.shape[1] * self.group_size
-                kr = self.num_res_centroids if self.enable_residual else 0
                 lim = 2 if (self.vector_len == 8 and kr in (0, 256) and sl.slices >= 16 and n_el >= 6 << 20) else 1
             elif _SLICED_TOKENS_ENV is not None:
                 lim = _SLICED_TOKENS_ENV[1 if len(sl.layout) == 2 else 0]
             else:
-                n_el = self.indices.shape[1] * self.group_size      # elements per table
-                kr = self.num_res_centroids if self.enable_residual else 0
                 lim = 1
                 if self.vector_len == 8 and kr in (0, 256) and n_el >= 6 << 20:
                     lim = 2
@@ -727,6 +764,7 @@ class VQuantLinear(nn.Module):
         key = ("_one_launch", tokens)
         ok = sl.__dict__.get(key)
         if ok is None:
+            n_el, kr = _index_elements(self), _res_centroids(self)
             if _SLICED_ONE_LAUNCH in ("0", "off", "false", "no") or not sl.tokens_supported(tokens):
                 ok = False
             elif _SLICED_ONE_LAUNCH in ("1", "on", "true", "yes", "always"):
@@ -746,8 +784,6 @@ class VQuantLinear(nn.Module):
                 # two tables (v8-k65536-65536, -4096: the residual entries gathered from L2 ONCE for all tokens; profiles/r05/
                 # sliced_exact_tokens_one_pass.txt): 8192^2 77.8 -> 61.5 / 63.4, 8192 x 28672 255 -> 202 / 206, kr = 4096: 68 -> 53 / 54; small
                 # layers lose (8192 x 1024: 18.8 -> 21.1): the one-token rule's sizes
-                n_el = self.indices.shape[1] * self.group_size
-                kr = self.num_res_centroids if self.enable_residual else 0
                 # ... in WINDOW PARTS where only half of the columns' operands fit beside the slice (WPT; profiles/r05/
                 # sliced_exact_tokens_window_parts.txt, gather -> one pass, 2 / 3 tokens, k65536-256 / -0): 14336 x 4096 37.0 / 42.6 -> 24.9 / 28.4
                 # and 36.9 / 35.3 -> 21.7 / 26.2; 4096 x 14336 37.1 / 38.2 -> 31.5 / 37.1 and 36.2 / 35.0 -> 27.9 / 34.2; smaller layers lose
@@ -765,8 +801,6 @@ class VQuantLinear(nn.Module):
                     else:
                         ok = sl.slices >= 16 and 3 <= tokens <= 4 and n_el >= 6 << 20
             else:
-                n_el = self.indices.shape[1] * self.group_size      # index elements per table
-                kr = self.num_res_centroids if self.enable_residual else 0
                 if n_el < 1 << 19:       # (smaller layers are launch-bound on every route and were not measured)
                     ok = False
                 elif self.vector_len == 8 or kr == 0:
@@ -785,9 +819,9 @@ class VQuantLinear(nn.Module):
             return False
         if on is True and "_sliced_on" in self.__dict__ or _SLICED_LAYOUT_MODE in ("1", "on", "true", "yes", "always"):
             return True
-        free, total = torch.cuda.mem_get_info(cache[3])
-        elems = self.indices.shape[1] * self.group_size
-        two = B.lib().vptq_sliced_layout_tables(cache[1]) == 2   # (one layout per table)
+        free, total = torch.cuda.mem_get_info(cache.device)
+        elems = _index_elements(self)
+        two = B.lib().vptq_sliced_layout_tables(cache.desc) == 2   # (one layout per table)
         from vptq_amd.utils.sliced import device_builder_enabled
         need = elems * (8 if two else 5)   # the layout; the torch recipe: + its int64 / float64 temporaries (the HIP builder has none)
         if not device_builder_enabled(self._parameters["indices"]):
@@ -801,10 +835,7 @@ class VQuantLinear(nn.Module):
                                                                                          "_compact" in self.__dict__):
             if "_sliced_cand" not in self.__dict__:
                 # (static module configuration: decided once, so that every other layer pays one dict look-up per call)
-                self.__dict__["_sliced_cand"] = bool(
-                    self.num_centroids >= 16384 and self.vector_len in (8, 16) and self.num_codebooks == 1 and
-                    not self.enable_outlier and self.enable_norm)   # (a permutation may still be absorbed later; the library
-                    # decides: vptq_sliced_layout_supported)
+                self.__dict__["_sliced_cand"] = _has_sliced_format(self)
             sl = self._sliced_gemv() if self.__dict__["_sliced_cand"] else None
             gf = ops.quant_gemm_flags()
             if sl is not None and not (gf & B.GEMV_FORCE_GENERIC) and (sl.exact or not (gf & B.GEMV_EXACT)):
@@ -889,7 +920,7 @@ class VQuantLinear(nn.Module):
         argsort(perm)) cached: marshalling 28 keyword arguments and rebuilding the descriptor cost
         ~45 us of Python per layer, a third of the prompt pass of an 8B-shaped model at 128 tokens."""
         cache = self._descriptor()
-        dev, wdtype, dev_index = cache[3], cache[7], cache[8]
+        dev, wdtype, dev_index = cache.device, cache.dtype, cache.device_index
         if x.shape[-1] != self.in_features:
             raise RuntimeError(f"x has {x.shape[-1]} features, layer expects {self.in_features}")
         if x.dtype != wdtype:
@@ -897,35 +928,20 @@ class VQuantLinear(nn.Module):
         if x.device != dev:
             raise RuntimeError(f"tensors on different devices: {dev} vs {x.device}")
         dense = self.__dict__.get("_desc_dense")
-        if dense is None or dense[0] != cache[6]:
-            P, M = self._parameters, self._modules
-            cp = self.__dict__.get("_compact")
-            desc, keep = B.make_layer_desc(
-                indices=P["indices"] if cp is None else cp["standin"], centroids=M["centroids"]._parameters["weight"],
-                res_centroids=M["res_centroids"]._parameters["weight"] if self.enable_residual else None,
-                outlier_indices=P.get("outlier_indices"),
-                outlier_centroids=M["outlier_centroids"]._parameters["weight"] if self.enable_outlier else None,
-                perm=P.get("perm") if self.enable_perm else None,
-                weight_scale=P.get("weight_scale"), weight_bias=P.get("weight_bias"), bias=None,
-                in_features=self.in_features, out_features=self.out_features,
-                vector_len=self.vector_len, num_codebooks=self.num_codebooks,
-                num_centroids=self.num_centroids,
-                num_res_centroids=self.num_res_centroids if self.enable_residual else 0,
-                group_size=self.group_size,
-                outlier_size=self.outlier_size if self.enable_outlier else 0,
-                outlier_vector_len=self.outlier_vector_len,
-                num_outlier_centroids=self.num_outlier_centroids, need_inv_perm=True)
-            dense = (cache[6], desc, keep, B.lib().vptq_dequant)
+        if dense is None or dense[0] != cache.generation:
+            desc, keep = B.make_layer_desc(bias=None, need_inv_perm=True, **self._layer_desc_keywords())
+            dense = (cache.generation, desc, keep, B.lib().vptq_dequant)
             self.__dict__["_desc_dense"] = dense
+        _, desc, _, dequant = dense
         W = torch.empty((self.out_features, self.in_features), dtype=wdtype, device=dev)
         cp = self.__dict__.get("_compact")
         if torch.cuda.current_device() != dev_index:
             with torch.cuda.device(dev):
                 sp = B.current_stream_ptr(dev)
-                rc = dense[3](dense[1] if cp is None else self._repacked_desc(dense[1], dev_index, sp), W.data_ptr(), sp)
+                rc = dequant(desc if cp is None else self._repacked_desc(desc, dev_index, sp), W.data_ptr(), sp)
         else:
             sp = _raw_stream(dev_index)
-            rc = dense[3](dense[1] if cp is None else self._repacked_desc(dense[1], dev_index, sp), W.data_ptr(), sp)
+            rc = dequant(desc if cp is None else self._repacked_desc(desc, dev_index, sp), W.data_ptr(), sp)
         if rc:
             B.check(rc, "vptq_dequant")
         return torch.nn.functional.linear(x, W, self._parameters.get("bias"))
@@ -975,25 +991,18 @@ class VQuantLinear(nn.Module):
         """None, or why this layer cannot be compacted (nothing is changed here)"""
         from vptq_amd.utils.sliced import exact_column_parts, tail_bits_clear
         ind = self._parameters["indices"]
-        if not (self.num_centroids >= 16384 and self.vector_len in (8, 16) and self.num_codebooks == 1 and not self.enable_outlier and
-                self.enable_norm):
-            return "format has no exact sliced layout (v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no outliers, scale / bias)"
+        if not _has_sliced_format(self):
+            return f"format has no exact sliced layout ({_SLICED_FORMATS})"
         if not tail_bits_clear(ind.detach(), self.group_size, self.total_index_bits):
             return "non-zero bits past group_size x index bits in a row of the packed indices: a layout cannot hold them"
         if not ind.is_cuda:
             return "indices are not on a ROCm device"
         if torch.cuda.is_current_stream_capturing():
             return "inside a stream capture"
-        cache = self._descriptor()
-        if not exact_column_parts(cache[1], self.group_size)[0]:
+        if not exact_column_parts(self._descriptor().desc, self.group_size)[0]:
             return "no exact sliced layout serves this layer (too wide, or the format's LDS budget)"
-        if not force:
-            n_el = ind.shape[1] * self.group_size
-            kr = self.num_res_centroids if self.enable_residual else 0
-            big = (kr >= 4096 and n_el >= _SLICED_EXACT_RG_MIN_ELEMENTS) if (kr > 0 and not (self.vector_len == 8 and kr == 256)) \
-                else n_el >= _SLICED_EXACT_MIN_ELEMENTS
-            if not big:
-                return "one token takes the gather kernel for this layer (smaller than the exact sliced route's threshold; force=True compacts it)"
+        if not force and not _exact_route_is_large(self):
+            return "one token takes the gather kernel for this layer (smaller than the exact sliced route's threshold; force=True compacts it)"
         return None
 
     def _compact_install(self):
@@ -1001,14 +1010,14 @@ class VQuantLinear(nn.Module):
         ind = self._parameters["indices"]
         cache = self._descriptor()
         st = self.__dict__.get("_sliced")
-        sl = st[1] if st is not None and st[0] == (cache[6], B.tensor_version(ind)) else None
+        sl = st[1] if st is not None and st[0] == (cache.generation, B.tensor_version(ind)) else None
         if sl is None or not sl.exact:
             try:
                 sl = SlicedGemv(self, exact=True)
             except torch.cuda.OutOfMemoryError as e:
                 torch.cuda.empty_cache()
                 return f"out of device memory building the exact layout ({str(e)[:120]})"
-        with torch.cuda.device(cache[3]):
+        with torch.cuda.device(cache.device):
             same = torch.equal(sl.repack(), ind.detach())
         if not same:
             return "the repacked layout differs from the packed indices"
@@ -1074,7 +1083,7 @@ class VQuantLinear(nn.Module):
         sl = cp["sl"] if cp is not None else (st[1] if st is not None else None)
         layout = 0
         if sl is not None:
-            layout = sum(t.numel() * t.element_size() for tup in sl._tensors for t in tup if t is not None)
+            layout = sl.layout_bytes()
         scratch = 0
         if cp is not None:
             di = sl._dev_index

@@ -38,14 +38,14 @@ class GemvChain:
 
     def _prepare(self):
         caches = [m._descriptor() for m in self.layers]
-        key = tuple(c[6] for c in caches)
+        key = tuple(c.generation for c in caches)
         if self._state is None or self._state[0] != key:
             # (compacting or uncompacting a layer rebuilds its descriptor: a new key)
             if any("_compact" in m.__dict__ for m in self.layers):
                 raise ValueError("a chain reads every layer's packed indices: uncompact() compacted layers first")
             n = len(caches)
-            dev = caches[0][3]
-            if any(c[3] != dev for c in caches):
+            dev = caches[0].device
+            if any(c.device != dev for c in caches):
                 raise RuntimeError("the layers of a chain must share one device")
             flags = B.GEMV_CHAIN_DEPENDENT if self.dependent else 0
             # Layers the load-time gate serves with the reference's roundings (VQuantLinear._folded_form_is_safe:
@@ -53,24 +53,24 @@ class GemvChain:
             # independent layers are handed to the library as two lists - the gated ones with VPTQ_GEMV_EXACT - and one
             # odd layer does not slow the others down; a dependent chain stays one list (the order is the
             # dependency) and takes the reference's roundings as a whole.
-            gated = [i for i, c in enumerate(caches) if c[9] & B.GEMV_EXACT]
+            gated = [i for i, c in enumerate(caches) if c.arithmetic_flags & B.GEMV_EXACT]
             rest = 0
             for c in caches:
-                rest |= c[9] & B.GEMV_SELECTIVE      # (selective arithmetic: the un-gated layers' launch asks for it)
+                rest |= c.arithmetic_flags & B.GEMV_SELECTIVE      # (selective arithmetic: the un-gated layers' launch asks for it)
             if self.dependent or not gated or len(gated) == n:
                 parts = [(list(range(n)), B.GEMV_EXACT if gated else rest)]
             else:
-                parts = [([i for i in range(n) if not caches[i][9] & B.GEMV_EXACT], rest), (gated, B.GEMV_EXACT)]
+                parts = [([i for i in range(n) if not caches[i].arithmetic_flags & B.GEMV_EXACT], rest), (gated, B.GEMV_EXACT)]
             subs = []
             for idx, safe in parts:
                 m = len(idx)
-                descs = (B.LayerDesc * m)(*[caches[i][1] for i in idx])
+                descs = (B.LayerDesc * m)(*[caches[i].desc for i in idx])
                 # arrival flags of a dependent chain / x[perm] of independent layers that have an input permutation / the
                 # thresholds of a call with VPTQ_GEMV_SELECTIVE (one word per layer)
                 nbytes = B.lib().vptq_quant_gemv_chain_workspace_bytes_for(descs, m, flags | (0 if self.dependent else B.GEMV_SELECTIVE))
                 ws = torch.zeros(max(nbytes, 4) // 4, dtype=torch.int32, device=dev) if nbytes else None
                 subs.append((idx, descs, (C.c_void_p * m)(), (C.c_void_p * m)(), safe, ws, nbytes))
-            self._state = (key, subs, dev, caches[0][7], [c[2] for c in caches])
+            self._state = (key, subs, dev, caches[0].dtype, [c.keep for c in caches])
         return self._state
 
     def kernel_name(self, tokens: int = 1, flags: Optional[int] = None) -> Optional[str]:

@@ -116,11 +116,11 @@ def forward_partial_f32(layer: VQuantLinear, x: torch.Tensor) -> torch.Tensor:
     if tokens < 1:
         raise RuntimeError("forward_partial_f32 needs at least one token")
     cache = layer._descriptor()
-    _, desc, _, dev, fn = cache[:5]
+    desc, dev, fn = cache.desc, cache.device, cache.gemv
     # what vptq_quant_gemv takes for THIS layer: 64 tokens for fp16 layers of the canonical format
     # (vptq_quant_gemv_max_tokens answers 48 for them), 16 for every other layer; beyond that the partial
     # sum comes from the dense route: dequant + a matmul that accumulates and stays in fp32
-    limit = B.GEMV_MAX_TOKENS if cache[5] >= 48 else 16
+    limit = B.GEMV_MAX_TOKENS if cache.max_tokens >= 48 else 16
 
     def dense():
         W = layer.dequant().float()
@@ -134,9 +134,9 @@ def forward_partial_f32(layer: VQuantLinear, x: torch.Tensor) -> torch.Tensor:
     y = torch.empty(xc.shape[:-1] + (layer.out_features,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         sp = torch.cuda.current_stream(dev).cuda_stream
-        ws, wsb = B.gemv_workspace(cache[8], sp, cache[10]) if tokens > 1 else (None, 0)
+        ws, wsb = B.gemv_workspace(cache.device_index, sp, cache.workspace_bytes) if tokens > 1 else (None, 0)
         rc = fn(desc, xc.data_ptr(), y.data_ptr(), tokens,
-                ops.quant_gemm_flags() | B.GEMV_OUT_F32 | cache[9], ws, wsb, sp)
+                ops.quant_gemm_flags() | B.GEMV_OUT_F32 | cache.arithmetic_flags, ws, wsb, sp)
     if rc == B.E_TOKENS and tokens > B.GEMV_ANY_FORMAT_TOKENS:
         # the fused path takes 17+ tokens of this layer only under run-time conditions the descriptor cannot
         # promise (a workspace - none is handed out inside a stream capture before one exists -, no exact-arithmetic

@@ -263,6 +263,33 @@ def exact_column_parts(desc, group_size: int):
     return 0, 0
 
 
+def _layout_structs(tensors, whole, rpw: int, slices: int):
+    """the `B.SlicedLayout` array of these layout tuples (elems, blocks, first, res, wstart); whole[i]: table i is held whole by its workgroups"""
+    structs = [B.SlicedLayout(e.data_ptr(), b.data_ptr(), f.data_ptr(), r.data_ptr() if r is not None else None, rpw, 1, slices, int(w),
+                              ws.data_ptr()) for (e, b, f, r, ws), w in zip(tensors, whole)]
+    return (B.SlicedLayout * len(structs))(*structs)
+
+
+def _launch_activation(obj, lay, x: torch.Tensor, tokens=None, served: bool = True):
+    """The pre-checks of every entry point of `obj` (SlicedGemv / SlicedGroupGemv over layers like `lay`): x as the kernels take it, or None
+    where the call cannot take them (not `served`; x - several tokens: or its rows - not 16-byte aligned).  tokens None: the one-token entry."""
+    n = lay.in_features
+    if tokens is None:
+        if x.shape[-1] != n or x.numel() != n:
+            raise ValueError("the sliced path takes one token of in_features values")
+    elif x.shape[-1] != n or not 2 <= tokens <= 8:
+        raise ValueError("forward_tokens takes 2 - 8 tokens of in_features values")
+    elif not served:
+        return None
+    if x.dtype != obj._dtype or x.device != obj.dev:   # (the checks of VQuantLinear._check_activation: this is the per-token path)
+        x = lay._check_activation(x)
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if x.data_ptr() & 15 or (tokens is not None and (n * x.element_size()) & 15):
+        return None
+    return x
+
+
 class SlicedGemv:
     """One-token forward of a v8-k65536-0 `VQuantLinear` over its sliced layout."""
 
@@ -276,10 +303,10 @@ class SlicedGemv:
         self.exact = bool(exact)
         self.selective = bool(selective) and not self.exact
         self._flags = B.GEMV_EXACT if self.exact else (B.GEMV_SELECTIVE if self.selective else 0)
-        if self.selective and not B.lib().vptq_quant_gemv_sliced_selective_supported(layer._descriptor()[1]):
+        if self.selective and not B.lib().vptq_quant_gemv_sliced_selective_supported(layer._descriptor().desc):
             raise ValueError("selective roundings over the sliced layouts: fp16 layers with scale and bias")
         cache = layer._descriptor()
-        self.desc, self.dev = cache[1], cache[3]
+        self.desc, self.dev = cache.desc, cache.device
         self.parts = 1
         if self.exact:   # (a layer too wide for 6 bytes of LDS per column in one piece: equal column parts, one layout each)
             self.parts, self.slices = exact_column_parts(self.desc, layer.group_size)
@@ -300,50 +327,36 @@ class SlicedGemv:
         # library decides: the kernel's LDS budget)
         whole = [False, n_tables == 2 and bool(B.lib().vptq_sliced_layout_whole_table(self.desc, 1))]
         packed = layer.indices.data
+        side = (2 if side16 else 1) if kr else 0   # bytes per element of the residual side stream
         if device_builder_enabled(packed):
             # indices on a ROCm device: the library builds the same tensors, byte for byte, from the packed stream (layout_build.hip) -
             # no index matrices, no sorts: the tensors themselves are the only memory the build takes
-            side = (2 if side16 else 1) if kr else 0
-
-            def build(table=0, whole_table=False, side_bytes=0, part=0):
+            def build(table, whole_table, side, part):
                 return layout_on_device(packed, self.desc, self.slices, exact=self.exact, table=table, whole_table=whole_table,
-                                        side_bytes=side_bytes, parts=self.parts, part=part)
-            if self.parts > 1:
-                w = layer.group_size // self.parts
-                self._tensors = [build(side_bytes=side, part=p) for p in range(self.parts)]
-                self._part_descs = (B.LayerDesc * self.parts)(*[part_desc(self.desc, p * w, (p + 1) * w) for p in range(self.parts)])
-                whole = [False] * self.parts
-            elif n_tables == 2:
-                self._tensors = [build(), build(table=1, whole_table=whole[1])]
-            else:
-                self._tensors = [build(side_bytes=side)]
-            idx = ridx = None
+                                        side_bytes=side, parts=self.parts, part=part)
         else:
             idx, ridx = split_index_streams(packed, layer.group_size, rb, ib)
-        if idx is None:
-            pass
-        elif self.parts > 1:
             w = layer.group_size // self.parts
-            self._tensors = [layout_from_indices(idx[:, p * w:(p + 1) * w].contiguous(), self.slices,
-                                                 ridx[:, p * w:(p + 1) * w].contiguous() if kr else None, ib,
-                                                 side_dtype=torch.int16 if side16 else torch.uint8) for p in range(self.parts)]
-            self._part_descs = (B.LayerDesc * self.parts)(*[part_desc(self.desc, p * w, (p + 1) * w) for p in range(self.parts)])
+
+            def build(table, whole_table, side, part):
+                cols = slice(part * w, (part + 1) * w)
+                src, bits = (ridx, rb) if table else (idx, ib)
+                return layout_from_indices(src[:, cols].contiguous(), self.slices, ridx[:, cols].contiguous() if side else None, bits,
+                                           whole_table, side_dtype=torch.int16 if side == 2 else torch.uint8)
+        if self.parts > 1:
+            self._tensors = [build(0, False, side, p) for p in range(self.parts)]
+            self._part_descs = self._make_part_descs(self.desc)
             whole = [False] * self.parts
         elif n_tables == 2:
             # (c + r) s x = c s x + r s x: the residual codebook is a second table with a layout bucketed by ITS index
-            self._tensors = [layout_from_indices(idx, self.slices, None, ib), layout_from_indices(ridx, self.slices, None, rb, whole[1])]
+            self._tensors = [build(0, False, 0, 0), build(1, whole[1], 0, 0)]
         else:
-            self._tensors = [layout_from_indices(idx, self.slices, ridx if kr else None, ib,
-                                                 side_dtype=torch.int16 if side16 else torch.uint8)]
-        del idx, ridx
+            self._tensors = [build(0, False, side, 0)]
         self._whole = whole[:len(self._tensors)]
         self.elems, self.blocks, self.first, self.res, self.wstart = self._tensors[0]
         # (a two-table layer runs 2 x slices workgroups per row block in its one launch)
         rpw = rows_per_wave or rows_per_wave_for(self.blocks.shape[1], self.slices * len(self._tensors))
-        self.layout = (B.SlicedLayout * len(self._tensors))(*[
-            B.SlicedLayout(e.data_ptr(), b.data_ptr(), f.data_ptr(), r.data_ptr() if r is not None else None, rpw, 1, self.slices, int(w),
-                           ws.data_ptr())
-            for (e, b, f, r, ws), w in zip(self._tensors, self._whole)])
+        self.layout = _layout_structs(self._tensors, self._whole, rpw, self.slices)
         self._ws_bytes = B.lib().vptq_quant_gemv_sliced_workspace_bytes(self._part_descs[0] if self.parts > 1 else self.desc)
         if self.selective:   # (+ header, x with the hot blocks zeroed, the hot blocks' exact products)
             self._ws_bytes = B.lib().vptq_quant_gemv_sliced_workspace_bytes_for(self.desc, self._flags)
@@ -358,9 +371,18 @@ class SlicedGemv:
         self._fn = B.lib().vptq_quant_gemv_sliced
         self._fn_tok = B.lib().vptq_quant_gemv_sliced_tokens
         self._lay_ref = self.layout   # (an array of 1 or 2 structs: passed as a pointer to the first)
-        self._dtype = cache[7]
-        self._dev_index = cache[8]
+        self._dtype = cache.dtype
+        self._dev_index = cache.device_index
         self.extra_bytes = sum(e.numel() * (4 + (r.element_size() if r is not None else 0)) + b.numel() * 8 for e, b, f, r, _ in self._tensors)
+
+    def _make_part_descs(self, desc):
+        """one descriptor per column part of `desc` (`part_desc`), as the array the grouped entries take"""
+        w = self.layer.group_size // self.parts
+        return (B.LayerDesc * self.parts)(*[part_desc(desc, p * w, (p + 1) * w) for p in range(self.parts)])
+
+    def layout_bytes(self) -> int:
+        """device bytes of the layout tensors"""
+        return sum(t.numel() * t.element_size() for tup in self._tensors for t in tup if t is not None)
 
     def repack(self, out: torch.Tensor = None) -> torch.Tensor:
         """the layer's packed int32 indices rebuilt from this EXACT layout on the current stream (`vptq_sliced_layout_repack`): into
@@ -382,8 +404,7 @@ class SlicedGemv:
         new = copy.copy(self)
         new.desc = desc
         if self.parts > 1:
-            w = self.layer.group_size // self.parts
-            new._part_descs = (B.LayerDesc * self.parts)(*[part_desc(desc, p * w, (p + 1) * w) for p in range(self.parts)])
+            new._part_descs = self._make_part_descs(desc)
         return new
 
     def _workspace(self, stream_ptr: int):
@@ -398,15 +419,8 @@ class SlicedGemv:
     def __call__(self, x: torch.Tensor, out: torch.Tensor = None, flags: int = 0):
         """y, or None where this call cannot take the sliced kernel (activation not 16-byte aligned, no workspace for a
         capturing stream, the library says "unsupported"): the caller then takes the regular route."""
-        lay = self.layer
-        # (the checks of VQuantLinear._check_activation, against cached values: this is the per-token path)
-        if x.shape[-1] != lay.in_features or x.numel() != lay.in_features:
-            raise ValueError("the sliced path takes one token of in_features values")
-        if x.dtype != self._dtype or x.device != self.dev:
-            x = lay._check_activation(x)
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if x.data_ptr() & 15:
+        x = _launch_activation(self, self.layer, x)
+        if x is None:
             return None
         if torch.cuda.current_device() != self._dev_index:
             with torch.cuda.device(self.dev):
@@ -449,17 +463,10 @@ class SlicedGemv:
     def forward_tokens(self, x: torch.Tensor, out: torch.Tensor = None, flags: int = 0):
         """2 - 4 tokens in ONE launch (`vptq_quant_gemv_sliced_tokens`, gemv_sliced_tok.hip): x [..., in_features] with 2 - 4
         rows, contiguous.  Returns y, or None where the call cannot be served (the caller takes the regular route)."""
-        lay = self.layer
-        tokens = x.numel() // lay.in_features
-        if x.shape[-1] != lay.in_features or not 2 <= tokens <= 8:
-            raise ValueError("forward_tokens takes 2 - 8 tokens of in_features values")
-        if self.selective or (self.exact and (self.parts > 1 or self._side16) and not self.tokens_one_pass(tokens)):
-            return None
-        if x.dtype != self._dtype or x.device != self.dev:
-            x = lay._check_activation(x)
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if x.data_ptr() & 15 or (lay.in_features * x.element_size()) & 15:
+        tokens = x.numel() // self.layer.in_features
+        x = _launch_activation(self, self.layer, x, tokens, not (
+            self.selective or (self.exact and (self.parts > 1 or self._side16) and not self.tokens_one_pass(tokens))))
+        if x is None:
             return None
         if torch.cuda.current_device() != self._dev_index:
             with torch.cuda.device(self.dev):
@@ -559,10 +566,7 @@ class SlicedGroupGemv:
                                   m.layer.in_features != m0.layer.in_features or kind(m) != kind(m0) for m in self.members):
             raise ValueError("a sliced group takes 1..3 layers of one format (vector length, codebook sizes), dtype, device and input width")
         rpw = rows_per_wave_for(sum(m.blocks.shape[1] for m in self.members), m0.slices * tables)   # one round of workgroups over ALL layers
-        structs = [B.SlicedLayout(e.data_ptr(), b.data_ptr(), f.data_ptr(), r.data_ptr() if r is not None else None, rpw, 1, m.slices, int(w),
-                                  ws.data_ptr())
-                   for m in self.members for (e, b, f, r, ws), w in zip(m._tensors, m._whole)]
-        self.layouts = (B.SlicedLayout * len(structs))(*structs)
+        self.layouts = _layout_structs([t for m in self.members for t in m._tensors], [w for m in self.members for w in m._whole], rpw, m0.slices)
         self.descs = (B.LayerDesc * n)(*[m.desc for m in self.members])
         self._yp, self._wp = (C.c_void_p * n)(), (C.c_void_p * n)()
         self._wb = (C.c_size_t * n)(*[m._ws_bytes for m in self.members])
@@ -572,14 +576,8 @@ class SlicedGroupGemv:
 
     def __call__(self, x: torch.Tensor):
         """list of outputs (one per member), or None where the call cannot take the sliced kernel (as SlicedGemv.__call__)"""
-        lay = self.members[0].layer
-        if x.shape[-1] != lay.in_features or x.numel() != lay.in_features:
-            raise ValueError("the sliced path takes one token of in_features values")
-        if x.dtype != self._dtype or x.device != self.dev:
-            x = lay._check_activation(x)
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if x.data_ptr() & 15:
+        x = _launch_activation(self, self.members[0].layer, x)
+        if x is None:
             return None
         if torch.cuda.current_device() != self._dev_index:
             with torch.cuda.device(self.dev):
@@ -594,15 +592,8 @@ class SlicedGroupGemv:
         where the call cannot be served (as SlicedGemv.forward_tokens)"""
         lay = self.members[0].layer
         tokens = x.numel() // lay.in_features
-        if x.shape[-1] != lay.in_features or not 2 <= tokens <= 8:
-            raise ValueError("forward_tokens takes 2 - 8 tokens of in_features values")
-        if self.exact and self._side16 and not all(m.tokens_one_pass(tokens) for m in self.members):
-            return None
-        if x.dtype != self._dtype or x.device != self.dev:
-            x = lay._check_activation(x)
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if x.data_ptr() & 15 or (lay.in_features * x.element_size()) & 15:
+        x = _launch_activation(self, lay, x, tokens, not (self.exact and self._side16 and not all(m.tokens_one_pass(tokens) for m in self.members)))
+        if x is None:
             return None
         if torch.cuda.current_device() != self._dev_index:
             with torch.cuda.device(self.dev):
