@@ -374,6 +374,23 @@ VPTQ_API int vptq_sliced_layout_supported_for(const VptqLayerDesc* desc, int fla
 VPTQ_API int vptq_sliced_layout_tables(const VptqLayerDesc* desc);
 /* the `whole_table` value the layout of table 0 / 1 must be built with (1: a small residual table every workgroup holds whole) */
 VPTQ_API int vptq_sliced_layout_whole_table(const VptqLayerDesc* desc, int table);
+/* ALL of the above in one answer (added within ABI 11; present when the symbol is): the layouts a layer is served from in the
+ * arithmetic of `flags` (0: the folded form; VPTQ_GEMV_EXACT: the reference's roundings) - what every sliced entry, the builder and
+ * vptq_sliced_layout_repack hold the structs they are handed to.
+ *   parts          0: the layer is not served (every other field 0).  Folded: 1.  Exact: 1 where the layer fits in one piece, else 2 or 3
+ *                  equal COLUMN PARTS of a multiple of 8 columns (layers wider than ~16300 columns; VPTQ_GEMV_COLUMN_PARTS) whose
+ *                  parts x n_slices arrivals one accumulator word counts (<= 127).  The tuning knob VPTQ_SLICED_PARTS = 2 / 3 (read
+ *                  here and nowhere else): at least that many parts where the columns divide.
+ *   tables         consecutive structs per part: 1, or 2 (folded form, a residual codebook other than v = 8's 256-entry one)
+ *   n_slices       of every struct (a part's: what vptq_sliced_layout_supported_for answers for the part's descriptor)
+ *   whole_table[t] the value table t's struct carries
+ *   side_bytes     the `res` stream beside table 0's element words: 0 none; 1 uint8 (v = 8 with 256 residual centroids); 2 uint16
+ *                  (exact layouts of any other residual codebook); folded two-table layouts: 0
+ * Returns VPTQ_OK - also for a layer that is not served -, an error only for a bad descriptor or out = NULL. */
+typedef struct VptqSlicedLayoutSet {
+  int32_t parts, tables, n_slices, whole_table[2], side_bytes, reserved[2];
+} VptqSlicedLayoutSet;
+VPTQ_API int vptq_sliced_layout_set(const VptqLayerDesc* desc, int flags /* VPTQ_GEMV_EXACT or 0 */, VptqSlicedLayoutSet* out);
 VPTQ_API size_t vptq_quant_gemv_sliced_workspace_bytes(const VptqLayerDesc* desc);
 VPTQ_API int vptq_quant_gemv_sliced(const VptqLayerDesc* desc, const VptqSlicedLayout* layout, const void* x,
                            void* y, int flags, void* workspace, size_t workspace_bytes, void* stream);
@@ -441,7 +458,7 @@ VPTQ_API int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const Vp
                                    const size_t* workspace_bytes, void* stream);
 
 /* Rebuild a layer's packed int32 indices [1][N][row_words] from its EXACT sliced layout(s): `parts` consecutive structs,
- * part p covering columns [p G / parts, (p + 1) G / parts) (1 part, or the 2 - 3 column parts of exact_column_parts).
+ * part p covering columns [p G / parts, (p + 1) G / parts) (vptq_sliced_layout_set(desc, VPTQ_GEMV_EXACT).parts of them).
  * Output is bit-identical to the packed stream the layout was built from, with zero bits past G*T in each row's last word.
  * desc is validated like the sliced entries': its `indices` must be non-NULL but is not read.
  *

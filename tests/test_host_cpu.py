@@ -709,6 +709,244 @@ def test_exact_column_parts_without_gpu():
     assert p.indices == d.indices and p.bias == d.bias and not p.perm
 
 
+_SET_GRID = ([2048, 4096, 4704, 4712, 5376, 5384, 8192, 14080, 14336, 16288, 16296, 16304, 16312, 16320, 16392, 24576, 25704, 28672, 32768, 40000],
+             (8, 12, 16), (8192, 16384, 65536), (0, 4, 64, 256, 1024, 4096, 65536))
+
+
+def _layout_set_tuple(lib, d, flags):
+    out = B.SlicedLayoutSet()
+    assert lib.vptq_sliced_layout_set(d, flags, out) == 0
+    return (out.parts, out.tables, out.n_slices, out.whole_table[0], out.whole_table[1], out.side_bytes)
+
+
+def test_sliced_layout_set_without_gpu():
+    """vptq_sliced_layout_set: parts, tables, slices, whole tables and side stream in ONE answer - equal, over a grid of widths, vector
+    lengths and codebook sizes, to what the Python side used to put together from the primitive queries (the slice count of the layer
+    or of its `part_desc`, the table count, whole_table(., 1), and the side-stream rule restated here) - host logic"""
+    from vptq_amd.utils.sliced import part_desc
+    lib = B.lib()
+    EX = B.GEMV_EXACT
+    supf, tabs, whole = lib.vptq_sliced_layout_supported_for, lib.vptq_sliced_layout_tables, lib.vptq_sliced_layout_whole_table
+
+    def composed(d, I, v, kr, exact):
+        if not exact:
+            n = supf(d, 0)
+            if not n:
+                return (0,) * 6
+            t = tabs(d)
+            return (1, t, n, whole(d, 0), int(t == 2 and whole(d, 1)), 1 if (kr and t == 1) else 0)
+        parts, n = 1, supf(d, EX)
+        if not n:
+            for parts in (2, 3):
+                n = supf(part_desc(d, 0, I // parts), EX) if I % (8 * parts) == 0 else 0
+                if n and n * parts <= 127:
+                    break
+            else:
+                return (0,) * 6
+        side = 0 if not kr else (1 if (v == 8 and kr == 256) else 2)
+        return (parts, 1, n, 0, 0, side)
+    cells = 0
+    for I in _SET_GRID[0]:
+        for v in _SET_GRID[1]:
+            for k in _SET_GRID[2]:
+                for kr in _SET_GRID[3]:
+                    d = _family_desc(I, 4096, v, k, kr)
+                    for flags in (0, EX):
+                        assert _layout_set_tuple(lib, d, flags) == composed(d, I, v, kr, flags == EX), (I, v, k, kr, flags)
+                        cells += 1
+    assert cells == 20 * 3 * 3 * 7 * 2
+    # a bad descriptor or a NULL argument is the only error; the generic route has no layouts
+    out = B.SlicedLayoutSet()
+    d = _family_desc(8192, 4096, 8, 65536, 256)
+    assert lib.vptq_sliced_layout_set(d, 0, None) == B.E_NULL and lib.vptq_sliced_layout_set(None, 0, out) == B.E_NULL
+    assert _layout_set_tuple(lib, d, EX | B.GEMV_FORCE_GENERIC) == (0,) * 6
+    d.index_bits = 3
+    assert lib.vptq_sliced_layout_set(d, 0, out) == B.E_SHAPE
+
+
+def test_sliced_parts_knob_is_read_in_one_place():
+    """VPTQ_SLICED_PARTS=2 (a tuning knob, read per process: a subprocess): the query, `exact_column_parts` and
+    vptq_sliced_layout_repack agree on 2 column parts for an 8192-column layer that fits in one piece - the repack entry, handed
+    parts = 1, answers VPTQ_E_SHAPE; without the knob they agree on 1 (the same call is then turned down for its layout)"""
+    import os
+    import subprocess
+    import sys
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import ctypes as C\nfrom vptq_amd import _backend as B\nfrom vptq_amd.utils.sliced import exact_column_parts\n"
+            "from test_host_cpu import _family_desc\n"
+            "d = _family_desc(8192, 4096, 8, 65536, 256)\nout = B.SlicedLayoutSet()\n"
+            "assert B.lib().vptq_sliced_layout_set(d, B.GEMV_EXACT, out) == 0\n"
+            "lay = (B.SlicedLayout * 1)(B.SlicedLayout(None, None, None, None, 1, 1, 16, 0, None))\n"
+            "print(out.parts, exact_column_parts(d, 8192)[0], B.lib().vptq_sliced_layout_repack(d, lay, 1, 1 << 20, None))"
+            ) % (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden"))
+    env = dict(os.environ, VPTQ_SLICED_PARTS="2", VPTQ_TUNING="1")   # (tuning knobs are read only with VPTQ_TUNING=1)
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.strip().splitlines()[-1] == "2 2 %d" % B.E_SHAPE, out.stdout
+    env.pop("VPTQ_SLICED_PARTS")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().splitlines()[-1] == "1 1 %d" % B.E_NULL, out.stdout + out.stderr[-1000:]
+
+
+def _sliced_turn_down_cells(lib):
+    """(name, call) of every cell of `test_sliced_entries_turn_down_the_same_layouts`: per entry and layer a well-formed call with
+    exactly one thing broken.  Fake aligned pointers: every call is turned down before anything is launched or read."""
+    import ctypes as C
+    from vptq_amd.utils.sliced import part_desc
+    EX, PARTS = B.GEMV_EXACT, B.GEMV_COLUMN_PARTS
+    P, X, Y, WS, OUT = 16 << 20, 17 << 20, 18 << 20, 20 << 20, 40 << 20      # layout tensors, x, y, workspaces, repack output
+    def cells_of(cname, d, flags):
+        cells = []
+        s = B.SlicedLayoutSet()
+        assert lib.vptq_sliced_layout_set(d, flags, s) == 0 and s.parts == 1
+        tables, need = s.tables, lib.vptq_quant_gemv_sliced_workspace_bytes(d)
+
+        def structs(n_layers, change=None):
+            """the structs of n_layers members, `change(struct)` applied to the last one (a side stream rides beside table 0 of ONE table)"""
+            lay = [B.SlicedLayout(P, P, P, P if (s.side_bytes and t == 0) else None, 2, 1, s.n_slices, s.whole_table[t], P)
+                   for _ in range(n_layers) for t in range(tables)]
+            if change:
+                change(lay[-1])
+            return (B.SlicedLayout * len(lay))(*lay)
+
+        def one(change=None, x=X, ws=WS, ws_bytes=None):
+            return lambda: lib.vptq_quant_gemv_sliced(d, structs(1, change), x, Y, flags, ws, need if ws_bytes is None else ws_bytes, None)
+
+        def group(change=None, x=X, ws1=WS + (8 << 20), ws1_bytes=None, y1=Y + (1 << 20), descs=None, gflags=flags):
+            dd = (B.LayerDesc * 2)(*(descs or (d, d)))
+            yp, wp = (C.c_void_p * 2)(Y, y1), (C.c_void_p * 2)(WS, ws1)
+            wb = (C.c_size_t * 2)(need, need if ws1_bytes is None else ws1_bytes)
+            return lambda: lib.vptq_quant_gemv_sliced_grouped(dd, structs(2, change), 2, x, yp, gflags, wp, wb, None)
+
+        def setter(**kw):
+            def change(lay):
+                for k, val in kw.items():
+                    setattr(lay, k, val)
+            return change
+        broken = {"n_slices": lambda lay: setattr(lay, "n_slices", 2 * lay.n_slices), "whole_table": lambda lay: setattr(lay, "whole_table", 1 - lay.whole_table),
+                  "rows_per_wave_0": setter(rows_per_wave=0), "rows_per_wave_65": setter(rows_per_wave=65), "rows_per_wave_differs": setter(rows_per_wave=3),
+                  "elems_null": setter(elems=None), "elems_per_lane_2": setter(elems_per_lane=2), "elems_not_a_word": setter(elems=P + 2)}
+        if s.side_bytes:    # (the folded two-table layouts carry no side stream: their `res` is not read)
+            broken.update({"res_null": setter(res=None), "res_odd": setter(res=P + 1)})
+        for call, ename in ((one, "gemv_sliced"), (group, "gemv_sliced_grouped")):
+            for bname, change in broken.items():
+                if bname == "rows_per_wave_differs" and call is one and tables == 1:
+                    continue    # (one struct: nothing to differ from)
+                cells.append((f"{ename}:{cname}:{bname}", call(change)))
+            cells.append((f"{ename}:{cname}:x_misaligned", call(x=X + 8)))
+        cells += [(f"gemv_sliced:{cname}:workspace_short", one(ws_bytes=need - 1)), (f"gemv_sliced:{cname}:workspace_misaligned", one(ws=WS + 8)),
+                  (f"gemv_sliced_grouped:{cname}:workspace_short", group(ws1_bytes=need - 1)),
+                  (f"gemv_sliced_grouped:{cname}:workspace_misaligned", group(ws1=WS + (8 << 20) + 8))]
+        # column parts: the two descriptors stand for the halves of one layer - shared y and workspace, one width, VPTQ_GEMV_EXACT
+        narrow = part_desc(d, 0, 4096)
+        cells += [(f"gemv_sliced_grouped:{cname}:parts_y_differs", group(ws1=WS, gflags=EX | PARTS)),
+                  (f"gemv_sliced_grouped:{cname}:parts_workspace_differs", group(y1=Y, gflags=EX | PARTS)),
+                  (f"gemv_sliced_grouped:{cname}:parts_width_differs", group(y1=Y, ws1=WS, descs=(d, narrow), gflags=EX | PARTS)),
+                  (f"gemv_sliced_grouped:{cname}:parts_without_exact", group(y1=Y, ws1=WS, gflags=PARTS))]
+        # repack (always the EXACT layouts of the layer) and fill (one struct, held to its spec)
+        e = B.SlicedLayoutSet()
+        assert lib.vptq_sliced_layout_set(d, EX, e) == 0 and e.parts == 1
+
+        def exact_struct(change=None):
+            lay = B.SlicedLayout(P, P, P, P if e.side_bytes else None, 2, 1, e.n_slices, 0, P)
+            if change:
+                change(lay)
+            return (B.SlicedLayout * 1)(lay)
+
+        def repack(change):
+            return lambda: lib.vptq_sliced_layout_repack(d, exact_struct(change), 1, OUT, None)
+        table = tables - 1      # (the folded two-table layer: its second table's layout)
+        side = s.side_bytes if table == 0 else 0
+
+        def fill(change=None, whole=s.whole_table[table]):
+            spec = B.SlicedLayoutSpec(flags, s.n_slices, table, whole, side, 1, 0, 0)
+            lay = B.SlicedLayout(P, P, P, P if side else None, 2, 1, s.n_slices, s.whole_table[table], P)
+            if change:
+                change(lay)
+            return lambda: lib.vptq_sliced_layout_fill(d, spec, lay, 1, None)
+        for bname in ("n_slices", "whole_table", "elems_null", "elems_not_a_word"):
+            cells.append((f"sliced_layout_repack:{cname}:{bname}", repack(broken[bname])))
+            cells.append((f"sliced_layout_fill:{cname}:{bname}", fill(whole=1 - s.whole_table[table]) if bname == "whole_table" else fill(broken[bname])))
+        cells += [(f"sliced_layout_repack:{cname}:res_null", repack(setter(res=None))), (f"sliced_layout_repack:{cname}:res_odd", repack(setter(res=P + 1))),
+                  (f"sliced_layout_fill:{cname}:res_odd", fill(setter(res=P + 1)))]
+        if side:
+            cells.append((f"sliced_layout_fill:{cname}:res_null", fill(setter(res=None))))
+        return cells
+    return (cells_of("v8_kr256_exact", _family_desc(8192, 8192, 8, 65536, 256), EX) +
+            cells_of("v16_kr65536_folded", _family_desc(8192, 8192, 16, 65536, 65536), 0))
+
+
+# what the library BEFORE the entries shared one checker answered, cell by cell (recorded from a build of that commit): VPTQ_E_* of the
+# entry's own checks, or 1 = hipErrorInvalidValue from the parameter fill of the launch (before anything is launched)
+_TURN_DOWN_CODES = {name: code for code, names in (
+    (B.E_NULL, """
+        sliced_layout_fill:v16_kr65536_folded:elems_null sliced_layout_fill:v16_kr65536_folded:res_odd
+        sliced_layout_fill:v8_kr256_exact:elems_null sliced_layout_fill:v8_kr256_exact:res_null
+        sliced_layout_repack:v16_kr65536_folded:elems_null sliced_layout_repack:v16_kr65536_folded:res_null
+        sliced_layout_repack:v8_kr256_exact:elems_null sliced_layout_repack:v8_kr256_exact:res_null
+        """),
+    (B.E_SHAPE, """
+        sliced_layout_fill:v16_kr65536_folded:n_slices sliced_layout_fill:v8_kr256_exact:n_slices
+        sliced_layout_repack:v16_kr65536_folded:n_slices sliced_layout_repack:v8_kr256_exact:n_slices
+        """),
+    (B.E_UNSUPPORTED, """
+        gemv_sliced:v16_kr65536_folded:elems_null gemv_sliced:v16_kr65536_folded:n_slices gemv_sliced:v16_kr65536_folded:rows_per_wave_0
+        gemv_sliced:v16_kr65536_folded:rows_per_wave_65 gemv_sliced:v16_kr65536_folded:rows_per_wave_differs
+        gemv_sliced:v16_kr65536_folded:whole_table gemv_sliced:v16_kr65536_folded:x_misaligned gemv_sliced:v8_kr256_exact:elems_null
+        gemv_sliced:v8_kr256_exact:n_slices gemv_sliced:v8_kr256_exact:res_null gemv_sliced:v8_kr256_exact:res_odd
+        gemv_sliced:v8_kr256_exact:rows_per_wave_0 gemv_sliced:v8_kr256_exact:rows_per_wave_65 gemv_sliced:v8_kr256_exact:whole_table
+        gemv_sliced:v8_kr256_exact:x_misaligned gemv_sliced_grouped:v16_kr65536_folded:elems_null
+        gemv_sliced_grouped:v16_kr65536_folded:n_slices gemv_sliced_grouped:v16_kr65536_folded:parts_width_differs
+        gemv_sliced_grouped:v16_kr65536_folded:parts_without_exact gemv_sliced_grouped:v16_kr65536_folded:parts_workspace_differs
+        gemv_sliced_grouped:v16_kr65536_folded:parts_y_differs gemv_sliced_grouped:v16_kr65536_folded:rows_per_wave_0
+        gemv_sliced_grouped:v16_kr65536_folded:rows_per_wave_65 gemv_sliced_grouped:v16_kr65536_folded:rows_per_wave_differs
+        gemv_sliced_grouped:v16_kr65536_folded:whole_table gemv_sliced_grouped:v16_kr65536_folded:x_misaligned
+        gemv_sliced_grouped:v8_kr256_exact:elems_null gemv_sliced_grouped:v8_kr256_exact:n_slices
+        gemv_sliced_grouped:v8_kr256_exact:parts_width_differs gemv_sliced_grouped:v8_kr256_exact:parts_without_exact
+        gemv_sliced_grouped:v8_kr256_exact:parts_workspace_differs gemv_sliced_grouped:v8_kr256_exact:parts_y_differs
+        gemv_sliced_grouped:v8_kr256_exact:res_null gemv_sliced_grouped:v8_kr256_exact:res_odd
+        gemv_sliced_grouped:v8_kr256_exact:rows_per_wave_0 gemv_sliced_grouped:v8_kr256_exact:rows_per_wave_65
+        gemv_sliced_grouped:v8_kr256_exact:rows_per_wave_differs gemv_sliced_grouped:v8_kr256_exact:whole_table
+        gemv_sliced_grouped:v8_kr256_exact:x_misaligned sliced_layout_fill:v16_kr65536_folded:whole_table
+        sliced_layout_fill:v8_kr256_exact:whole_table sliced_layout_repack:v16_kr65536_folded:whole_table
+        sliced_layout_repack:v8_kr256_exact:whole_table
+        """),
+    (B.E_ALIGN, """
+        sliced_layout_fill:v16_kr65536_folded:elems_not_a_word sliced_layout_fill:v8_kr256_exact:elems_not_a_word
+        sliced_layout_fill:v8_kr256_exact:res_odd sliced_layout_repack:v16_kr65536_folded:elems_not_a_word
+        sliced_layout_repack:v16_kr65536_folded:res_odd sliced_layout_repack:v8_kr256_exact:elems_not_a_word
+        sliced_layout_repack:v8_kr256_exact:res_odd
+        """),
+    (B.E_WORKSPACE, """
+        gemv_sliced:v16_kr65536_folded:workspace_misaligned gemv_sliced:v16_kr65536_folded:workspace_short
+        gemv_sliced:v8_kr256_exact:workspace_misaligned gemv_sliced:v8_kr256_exact:workspace_short
+        gemv_sliced_grouped:v16_kr65536_folded:workspace_misaligned gemv_sliced_grouped:v16_kr65536_folded:workspace_short
+        gemv_sliced_grouped:v8_kr256_exact:workspace_misaligned gemv_sliced_grouped:v8_kr256_exact:workspace_short
+        """),
+    (1, """
+        gemv_sliced:v16_kr65536_folded:elems_not_a_word gemv_sliced:v16_kr65536_folded:elems_per_lane_2
+        gemv_sliced:v8_kr256_exact:elems_not_a_word gemv_sliced:v8_kr256_exact:elems_per_lane_2
+        gemv_sliced_grouped:v16_kr65536_folded:elems_not_a_word gemv_sliced_grouped:v16_kr65536_folded:elems_per_lane_2
+        gemv_sliced_grouped:v8_kr256_exact:elems_not_a_word gemv_sliced_grouped:v8_kr256_exact:elems_per_lane_2
+        """),
+) for name in names.split()}
+
+
+def test_sliced_entries_turn_down_the_same_layouts():
+    """vptq_quant_gemv_sliced, _sliced_grouped (2 layers), vptq_sliced_layout_repack and vptq_sliced_layout_fill hold the structs they
+    are handed to ONE checker: per entry, a well-formed call on an exact v8-k65536-256 layer and on a folded two-table v16-k65536-65536
+    layer with exactly one thing broken answers the literal code the entries answered while each carried its own copy of the checks"""
+    lib = B.lib()
+    cells = _sliced_turn_down_cells(lib)
+    assert sorted(n for n, _ in cells) == sorted(_TURN_DOWN_CODES)
+    got = {name: call() for name, call in cells}
+    assert got == _TURN_DOWN_CODES, {n: (got[n], _TURN_DOWN_CODES[n]) for n in got if got[n] != _TURN_DOWN_CODES[n]}
+    # (the "one format" rule of a group answers the same code: that the column-parts rule itself turned these down shows in the text)
+    for name, call in cells:
+        if ":parts_" in name:
+            assert call() == B.E_UNSUPPORTED and b"column parts" in lib.vptq_last_error(), (name, lib.vptq_last_error())
+
+
 def test_one_pass_plan_for_two_and_three_tokens_without_gpu():
     """vptq_quant_gemv_sliced_tokens_one_pass: in how many window parts 2 / 3 tokens take one pass of the one-token kernel in the reference's
     roundings - 1 where the slice leaves room for (2 tokens + 4) bytes of every column, 2 / 4 where for half / a quarter of them (v = 8, one

@@ -60,6 +60,12 @@ class SlicedLayoutSpec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("flags", "n_slices", "table", "whole_table", "side_bytes", "parts", "part", "reserved")]
 
 
+class SlicedLayoutSet(C.Structure):
+    """Mirror of `VptqSlicedLayoutSet` (include/vptq_hip.h): the layouts a layer is served from (`vptq_sliced_layout_set`)."""
+    _fields_ = [("parts", C.c_int32), ("tables", C.c_int32), ("n_slices", C.c_int32), ("whole_table", C.c_int32 * 2),
+                ("side_bytes", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 LAYOUT_ANY_SHAPE = 1 << 16   # VptqSlicedLayoutSpec.flags: the spec as written, not checked against the layer's GEMV layouts
 
 
@@ -127,6 +133,8 @@ EXPORTS = {
     "vptq_quant_gemv_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
     "vptq_sliced_layout_supported_for": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemv_grouped_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
+    # (added within ABI 11) parts, tables, slices, whole tables and side stream of a layer's sliced layouts in one answer
+    "vptq_sliced_layout_set": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.POINTER(SlicedLayoutSet)]),
     # (added within ABI 11) the packed index stream rebuilt from a layer's exact sliced layout(s): compact mode
     "vptq_sliced_layout_repack": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, _vp, _vp]),
     # (added within ABI 11) a sliced layout built from the packed indices on the device, in two steps (layout_build.hip)

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 
 #include "kernels.h"
+#include "sliced.h"
 
 namespace {
 
@@ -98,6 +99,27 @@ int selective_as_exact(int flags) {
 int drop_redundant_selective(int flags) {
   return (flags & VPTQ_GEMV_EXACT) ? (flags & ~VPTQ_GEMV_SELECTIVE) : flags;
 }
+
+// Why vptq::sl_check_layouts turned a struct down, as the entries report it: the first reason of `faults` in this order.  The GEMV
+// entries answer VPTQ_E_UNSUPPORTED for every one of them (the caller takes another route), repack / fill the code listed.
+const struct { unsigned fault; int code; const char* text; } kLayoutFaults[] = {
+  {vptq::kSLFaultTensors, VPTQ_E_NULL, "elems / blocks / first (building: wstart too) is NULL"},
+  {vptq::kSLFaultSlices, VPTQ_E_SHAPE, "n_slices is not this layer's"},
+  {vptq::kSLFaultWhole, VPTQ_E_UNSUPPORTED, "whole_table is not this table's"},
+  {vptq::kSLFaultRes, VPTQ_E_NULL, "the `res` side stream must be set where the layouts carry one (building / repacking: and only there), uint16 at an even address"},
+  {vptq::kSLFaultRows, VPTQ_E_UNSUPPORTED, "rows_per_wave in [1, 64], the same in every struct of the call"},
+  {vptq::kSLFaultAlign, VPTQ_E_ALIGN, "elems 16-byte, blocks / first / wstart / res 4-byte (repacking a uint16 res: 8-byte) aligned"},
+};
+int layout_fail(unsigned faults, bool gemv, const char* who, int layer, int which, const vptq::SlicedLayoutSet& S,
+                const char* whose = "vptq_sliced_layout_set") {
+  for (const auto& f : kLayoutFaults)
+    if (faults & f.fault)
+      return fail(gemv ? VPTQ_E_UNSUPPORTED : f.code, "%s: layer / part %d, layout %d: %s (%s: n_slices %d, whole_table %d / %d, "
+                  "side stream of %d byte(s))", who, layer, which, f.text, whose, S.slices, S.whole[0], S.whole[1], S.side_bytes);
+  return VPTQ_OK;
+}
+const char* const kNoExactLayout = "no exact sliced layout serves this layer (vptq_sliced_layout_set(desc, VPTQ_GEMV_EXACT): in one piece, or as 2 / 3 column parts)";
+const char* const kPartsShare = "column parts go with VPTQ_GEMV_EXACT, share y, the workspace, the output bias and have one width (tokens: and take them in one pass)";
 
 }  // namespace
 
@@ -747,6 +769,14 @@ int vptq_sliced_layout_whole_table(const VptqLayerDesc* d, int table) {
   return validate_layer(d) == VPTQ_OK && vptq::gemv_sliced_eligible(*d) ? vptq::gemv_sliced_whole_table(*d, table) : 0;
 }
 
+int vptq_sliced_layout_set(const VptqLayerDesc* d, int flags, VptqSlicedLayoutSet* out) {
+  if (int rc = validate_layer(d)) return rc;
+  if (!out) return fail(VPTQ_E_NULL, "out is NULL");
+  const vptq::SlicedLayoutSet S = (flags & VPTQ_GEMV_FORCE_GENERIC) ? vptq::SlicedLayoutSet{} : vptq::sl_layout_set(*d, (flags & VPTQ_GEMV_EXACT) != 0);
+  *out = VptqSlicedLayoutSet{S.parts, S.tables, S.slices, {S.whole[0], S.whole[1]}, S.side_bytes, {0, 0}};
+  return VPTQ_OK;
+}
+
 size_t vptq_quant_gemv_sliced_workspace_bytes(const VptqLayerDesc* d) {
   return validate_layer(d) == VPTQ_OK && vptq::gemv_sliced_eligible(*d) ? vptq::gemv_sliced_workspace_bytes(*d) : 0;
 }
@@ -773,19 +803,10 @@ int vptq_quant_gemv_sliced(const VptqLayerDesc* d, const VptqSlicedLayout* layou
   if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & (sel ? 255 : 15)) != 0)
     return fail(VPTQ_E_WORKSPACE, "workspace of %zu bytes (%d-byte aligned) needed", need, sel ? 256 : 16);
   // (folded, two tables: one layout per table, consecutive structs; the reference's roundings: always ONE layout)
-  const int n_layouts = exact ? 1 : vptq::gemv_sliced_tables(*d);
-  for (int i = 0; i < n_layouts; ++i) {
-    if (layout[i].rows_per_wave < 1 || layout[i].rows_per_wave > 64 || !layout[i].elems || !layout[i].blocks || !layout[i].first ||
-        (layout[i].n_slices != 0 ? layout[i].n_slices : 8) != vptq::gemv_sliced_slices(*d, exact))
-      return fail(VPTQ_E_UNSUPPORTED, "sliced layout %d: rows_per_wave in [1, 64], three tensors, n_slices = %d for this layer and arithmetic",
-                  i, vptq::gemv_sliced_slices(*d, exact));
-    if (exact && d->num_res_centroids > 0 && (!layout[i].res || (((uintptr_t)layout[i].res) & 1) != 0))
-      return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_EXACT over a sliced layout of a layer with a residual codebook needs the layout's `res` "
-                  "side stream (uint8 for v = 8 with 256 residual centroids, else uint16)");
-    if (layout[i].whole_table != (exact ? 0 : vptq::gemv_sliced_whole_table(*d, i)) || layout[i].rows_per_wave != layout[0].rows_per_wave)
-      return fail(VPTQ_E_UNSUPPORTED, "sliced layout %d: whole_table must be %d (vptq_sliced_layout_whole_table) and rows_per_wave the "
-                  "same for both tables", i, vptq::gemv_sliced_whole_table(*d, i));
-  }
+  const vptq::SlicedLayoutSet S = vptq::sl_piece_set(*d, exact);
+  int which = 0;
+  if (const unsigned faults = vptq::sl_check_layouts(*d, S, layout, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole, layout[0].rows_per_wave, &which))
+    return layout_fail(faults, true, "vptq_quant_gemv_sliced", 0, which, S);
   if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
   if (sel) {
     // the pre-pass (gemv_hot.hip): threshold, x with the hot blocks' features zeroed, the hot blocks' exact products - behind the
@@ -801,59 +822,18 @@ int vptq_quant_gemv_sliced(const VptqLayerDesc* d, const VptqSlicedLayout* layou
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced launch");
 }
 
-// the column parts vptq_amd/utils/sliced.py:exact_column_parts serves the reference's roundings with (its VPTQ_SLICED_PARTS A/B knob
-// included): 1 where the layer fits in one piece, else 2 or 3 equal parts of a multiple of 8 columns; 0 = none
-static VptqLayerDesc repack_part_desc(const VptqLayerDesc& d, int parts, int p) {
-  VptqLayerDesc q = d;
-  const int w = d.group_size / parts;
-  q.in_features = q.group_size = w;
-  const size_t off = (size_t)2 * p * w;   // (16-bit column-order tensors)
-  if (q.weight_scale) q.weight_scale = (const char*)q.weight_scale + off;
-  if (q.weight_bias) q.weight_bias = (const char*)q.weight_bias + off;
-  if (q.perm) q.perm = (const uint16_t*)((const char*)q.perm + off);
-  if (q.scale_permuted) q.scale_permuted = (const char*)q.scale_permuted + off;
-  if (q.bias_permuted) q.bias_permuted = (const char*)q.bias_permuted + off;
-  return q;
-}
-static int repack_exact_parts(const VptqLayerDesc& d) {
-  const char* e = vptq::tune_env("VPTQ_SLICED_PARTS");
-  const int least = e && atoi(e) > 1 ? atoi(e) : 1;
-  const bool whole = vptq::gemv_sliced_eligible(d, true);
-  if (whole && least <= 1) return 1;
-  for (int parts = 2; parts <= 3; ++parts) {
-    if (parts < least || d.group_size % (8 * parts) != 0) continue;
-    const VptqLayerDesc q = repack_part_desc(d, parts, 0);
-    if (vptq::gemv_sliced_eligible(q, true) && vptq::gemv_sliced_slices(q, true) * parts <= 127) return parts;
-  }
-  return least > 1 && whole ? 1 : 0;
-}
-
 int vptq_sliced_layout_repack(const VptqLayerDesc* d, const VptqSlicedLayout* layouts, int parts, void* indices_out, void* stream) {
   if (int rc = validate_layer(d)) return rc;
   if (!layouts || !indices_out) return fail(VPTQ_E_NULL, "layouts / indices_out is NULL");
-  const int want = repack_exact_parts(*d);
-  if (want == 0)
-    return fail(VPTQ_E_UNSUPPORTED, "no exact sliced layout serves this layer (vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT), "
-                                    "or 2 / 3 column parts of it)");
-  if (parts != want) return fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", parts, want);
+  const vptq::SlicedLayoutSet S = vptq::sl_layout_set(*d, true);
+  if (S.parts == 0) return fail(VPTQ_E_UNSUPPORTED, kNoExactLayout);
+  if (parts != S.parts) return fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", parts, S.parts);
   if ((((uintptr_t)indices_out) & 15) != 0) return fail(VPTQ_E_ALIGN, "indices_out must be 16-byte aligned");
   if (vptq::sliced_repack_lds_bytes(*d) > 163840) return fail(VPTQ_E_UNSUPPORTED, "row_words %d: a row's image exceeds the LDS", d->row_words);
-  const int side = d->num_res_centroids == 0 ? 0 : (d->vector_len == 8 && d->num_res_centroids == 256 ? 1 : 2);
-  for (int p = 0; p < parts; ++p) {
-    const VptqSlicedLayout& L = layouts[p];
-    const int nsl = vptq::gemv_sliced_slices(repack_part_desc(*d, parts, p), true);
-    if (!L.elems || !L.blocks || !L.first) return fail(VPTQ_E_NULL, "layout %d: elems / blocks / first is NULL", p);
-    if (L.n_slices != nsl)
-      return fail(VPTQ_E_SHAPE, "layout %d: n_slices %d, the exact layout of this part has %d (vptq_sliced_layout_supported_for)", p,
-                  L.n_slices, nsl);
-    if (L.whole_table) return fail(VPTQ_E_UNSUPPORTED, "layout %d: whole-table layouts are folded-form layouts, not exact ones", p);
-    if ((side != 0) != (L.res != nullptr))
-      return fail(VPTQ_E_NULL, "layout %d: the `res` side stream must be set iff the layer has a residual codebook", p);
-    if ((((uintptr_t)L.elems) & 15) != 0 || (((uintptr_t)L.blocks | (uintptr_t)L.first) & 3) != 0 ||
-        (side && (((uintptr_t)L.res) & (side == 1 ? 3 : 7)) != 0))
-      return fail(VPTQ_E_ALIGN, "layout %d: elems 16-byte, blocks / first 4-byte, res 4- (uint8) / 8-byte (uint16) aligned", p);
-  }
-  const hipError_t e = vptq::launch_sliced_repack(*d, layouts, parts, indices_out, (hipStream_t)stream);
+  int which = 0;   // (folded layouts - two tables, whole tables - do not hold the packed stream)
+  if (const unsigned faults = vptq::sl_check_layouts(*d, S, layouts, parts, vptq::kSLNeedBuilt | vptq::kSLNeedWhole | vptq::kSLNeedRes8, 0, &which))
+    return layout_fail(faults, false, "vptq_sliced_layout_repack", which, 0, S);
+  const hipError_t e = vptq::launch_sliced_repack(*d, layouts, parts, S.side_bytes, indices_out, (hipStream_t)stream);
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "sliced_repack launch");
 }
 
@@ -878,30 +858,17 @@ static int layout_build_params(const VptqLayerDesc* d, const VptqSlicedLayoutSpe
   const int lg = s.n_slices == 8 ? 3 : (s.n_slices == 16 ? 4 : 5);
   const int bits = s.table ? d->res_bits : d->index_bits;
   if (!any) {
-    // the layouts vptq_amd/utils/sliced.py:SlicedGemv hands to the GEMV entries
-    int want_parts = 1, want_slices, want_whole = 0, want_side = 0, tables = 1;
-    if (exact) {
-      want_parts = repack_exact_parts(*d);
-      if (want_parts == 0)
-        return fail(VPTQ_E_UNSUPPORTED, "no exact sliced layout serves this layer (vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT), "
-                                        "or 2 / 3 column parts of it)");
-      if (s.parts != want_parts) return fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", s.parts, want_parts);
-      want_slices = vptq::gemv_sliced_slices(repack_part_desc(*d, want_parts, s.part), true);
-      want_side = d->num_res_centroids == 0 ? 0 : (d->vector_len == 8 && d->num_res_centroids == 256 ? 1 : 2);
-    } else {
-      if (!vptq::gemv_sliced_eligible(*d, false))
-        return fail(VPTQ_E_UNSUPPORTED, "the sliced layout serves v = 8 / 16 layers with 16384 ... 65536 main centroids, group_size <= 32768");
-      if (s.parts != 1) return fail(VPTQ_E_SHAPE, "parts %d: column parts are layouts of the reference's roundings (VPTQ_GEMV_EXACT)", s.parts);
-      want_slices = vptq::gemv_sliced_slices(*d, false);
-      tables = vptq::gemv_sliced_tables(*d);
-      want_whole = vptq::gemv_sliced_whole_table(*d, s.table);
-      want_side = tables == 1 && d->num_res_centroids > 0 ? 1 : 0;
-    }
-    if (s.n_slices != want_slices)
-      return fail(VPTQ_E_SHAPE, "n_slices %d: this layout of the layer has %d (vptq_sliced_layout_supported_for)", s.n_slices, want_slices);
-    if (s.table >= tables) return fail(VPTQ_E_UNSUPPORTED, "table %d: this arithmetic serves the layer from %d layout(s) per part (vptq_sliced_layout_tables)", s.table, tables);
-    if (s.whole_table != want_whole) return fail(VPTQ_E_UNSUPPORTED, "whole_table %d: must be %d (vptq_sliced_layout_whole_table)", s.whole_table, want_whole);
-    if (s.side_bytes != want_side) return fail(VPTQ_E_UNSUPPORTED, "side_bytes %d: this layout carries %d", s.side_bytes, want_side);
+    // the layouts the GEMV entries take for the layer
+    const vptq::SlicedLayoutSet S = vptq::sl_layout_set(*d, exact);
+    if (S.parts == 0)
+      return fail(VPTQ_E_UNSUPPORTED, exact ? kNoExactLayout : "the sliced layout serves v = 8 / 16 layers with 16384 ... 65536 main centroids, group_size <= 32768");
+    if (s.parts != S.parts)
+      return exact ? fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", s.parts, S.parts)
+                   : fail(VPTQ_E_SHAPE, "parts %d: column parts are layouts of the reference's roundings (VPTQ_GEMV_EXACT)", s.parts);
+    if (s.n_slices != S.slices) return fail(VPTQ_E_SHAPE, "n_slices %d: this layout of the layer has %d (vptq_sliced_layout_set)", s.n_slices, S.slices);
+    if (s.table >= S.tables) return fail(VPTQ_E_UNSUPPORTED, "table %d: this arithmetic serves the layer from %d layout(s) per part (vptq_sliced_layout_set)", s.table, S.tables);
+    if (s.whole_table != S.whole[s.table]) return fail(VPTQ_E_UNSUPPORTED, "whole_table %d: must be %d (vptq_sliced_layout_set)", s.whole_table, S.whole[s.table]);
+    if (s.side_bytes != S.side_bytes) return fail(VPTQ_E_UNSUPPORTED, "side_bytes %d: this layout carries %d", s.side_bytes, S.side_bytes);
   }
   vptq::LayoutBuildParams a = {};
   a.packed = (const uint32_t*)d->indices;
@@ -944,12 +911,16 @@ int vptq_sliced_layout_fill(const VptqLayerDesc* d, const VptqSlicedLayoutSpec* 
                             void* stream) {
   vptq::LayoutBuildParams a;
   if (int rc = layout_build_params(d, spec, &a)) return rc;
-  if (!out || !out->elems || !out->blocks || !out->first || !out->wstart) return fail(VPTQ_E_NULL, "out / elems / blocks / first / wstart is NULL");
-  if ((a.side != 0) != (out->res != nullptr)) return fail(VPTQ_E_NULL, "the `res` side stream must be set iff the spec carries one");
-  if (out->n_slices != spec->n_slices) return fail(VPTQ_E_SHAPE, "out->n_slices %d, the spec has %d", out->n_slices, spec->n_slices);
+  if (!out) return fail(VPTQ_E_NULL, "out is NULL");
+  // (`out` is held to the SPEC - with VPTQ_LAYOUT_ANY_SHAPE that need not be a layout of the layer's set; whole_table is not read)
+  vptq::SlicedLayoutSet S = {};
+  S.parts = spec->parts, S.tables = 1, S.slices = spec->n_slices, S.whole[0] = spec->whole_table, S.side_bytes = a.side;
+  const unsigned faults = vptq::sl_check_layouts(*d, S, out, 1, vptq::kSLNeedBuilt | vptq::kSLNeedWstart);
+  // this entry's order of reasons: NULL tensors, `res`, n_slices, then total_blocks, then the alignments
+  for (const unsigned first : {vptq::kSLFaultTensors, vptq::kSLFaultRes, vptq::kSLFaultSlices})
+    if (faults & first) return layout_fail(first, false, "vptq_sliced_layout_fill", spec->part, 0, S, "the spec");
   if (total_blocks < 0 || total_blocks >= (1ll << 31)) return fail(VPTQ_E_SHAPE, "total_blocks %lld outside [0, 2^31)", (long long)total_blocks);
-  if ((((uintptr_t)out->elems) & 15) != 0 || (((uintptr_t)out->blocks | (uintptr_t)out->first | (uintptr_t)out->wstart | (uintptr_t)out->res) & 3) != 0)
-    return fail(VPTQ_E_ALIGN, "elems 16-byte, blocks / first / wstart / res 4-byte aligned");
+  if (faults) return layout_fail(faults, false, "vptq_sliced_layout_fill", spec->part, 0, S, "the spec");
   a.blocks = (int32_t*)out->blocks;
   a.first = (int32_t*)out->first;
   a.wstart = (int32_t*)out->wstart;
@@ -1020,33 +991,19 @@ int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const VptqSlicedL
   }
   const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
   if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_FORCE_GENERIC: use vptq_quant_gemv");
-  if (flags & VPTQ_GEMV_COLUMN_PARTS) {
-    if (!exact) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_COLUMN_PARTS goes with VPTQ_GEMV_EXACT (the folded form stages 32768 columns in one piece)");
-    for (int i = 1; i < n; ++i)
-      if (y[i] != y[0] || workspaces[i] != workspaces[0] || descs[i].out_features != descs[0].out_features ||
-          descs[i].num_indices != descs[0].num_indices || descs[i].bias != descs[0].bias || descs[i].in_features != descs[0].in_features)
-        return fail(VPTQ_E_UNSUPPORTED, "column parts share y, the workspace, the output bias and have one width");
-  }
+  if ((flags & VPTQ_GEMV_COLUMN_PARTS) && (!exact || !vptq::sl_parts_share(descs, y, workspaces, n))) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
   if (!vptq::gemv_sliced_groupable(descs, n, exact))
     return fail(VPTQ_E_UNSUPPORTED, "a sliced group takes layers of ONE format, dtype and input width that vptq_sliced_layout_supported_for() accepts");
   if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
-  const int tables = exact ? 1 : vptq::gemv_sliced_tables(descs[0]);
   for (int i = 0; i < n; ++i) {
     const size_t need = vptq::gemv_sliced_workspace_bytes(descs[i]);
     if (!workspaces[i] || workspace_bytes[i] < need || (((uintptr_t)workspaces[i]) & 15) != 0)
       return fail(VPTQ_E_WORKSPACE, "layer %d: workspace of %zu bytes (16-byte aligned) needed", i, need);
-    for (int t = 0; t < tables; ++t) {
-      const VptqSlicedLayout& L = layouts[(size_t)i * tables + t];
-      if (L.rows_per_wave < 1 || L.rows_per_wave > 64 || !L.elems || !L.blocks || !L.first ||
-          (L.n_slices != 0 ? L.n_slices : 8) != vptq::gemv_sliced_slices(descs[i], exact))
-        return fail(VPTQ_E_UNSUPPORTED, "layer %d, sliced layout %d: rows_per_wave in [1, 64], three tensors, n_slices = %d", i, t,
-                    vptq::gemv_sliced_slices(descs[i], exact));
-      if (exact && descs[i].num_res_centroids > 0 && (!L.res || (((uintptr_t)L.res) & 1) != 0))
-        return fail(VPTQ_E_UNSUPPORTED, "layer %d: VPTQ_GEMV_EXACT needs the layout's `res` side stream", i);
-      if (L.whole_table != (exact ? 0 : vptq::gemv_sliced_whole_table(descs[i], t)) || L.rows_per_wave != layouts[0].rows_per_wave)
-        return fail(VPTQ_E_UNSUPPORTED, "layer %d, sliced layout %d: whole_table must be %d and rows_per_wave the group's", i, t,
-                    vptq::gemv_sliced_whole_table(descs[i], t));
-    }
+    const vptq::SlicedLayoutSet S = vptq::sl_piece_set(descs[i], exact);   // (one format: the same table count for every member)
+    int which = 0;
+    if (const unsigned faults = vptq::sl_check_layouts(descs[i], S, layouts + (size_t)i * S.tables, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole,
+                                                       layouts[0].rows_per_wave, &which))
+      return layout_fail(faults, true, "vptq_quant_gemv_sliced_grouped", i, which, S);
   }
   const hipError_t e = vptq::launch_gemv_sliced_group(descs, layouts, n, x, y, flags, workspaces, (hipStream_t)stream);
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced grouped launch");
@@ -1064,11 +1021,9 @@ int vptq_quant_gemv_sliced_tokens_grouped(const VptqLayerDesc* descs, const Vptq
   }
   if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
   if (flags & VPTQ_GEMV_COLUMN_PARTS) {   // (as vptq_quant_gemv_sliced_grouped: parts of ONE layer; 2 / 3 tokens, where every part takes them in one pass)
-    if (!(flags & VPTQ_GEMV_EXACT)) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_COLUMN_PARTS goes with VPTQ_GEMV_EXACT");
+    if (!(flags & VPTQ_GEMV_EXACT) || !vptq::sl_parts_share(descs, y, workspaces, n)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
     for (int i = 0; i < n; ++i)
-      if (y[i] != y[0] || workspaces[i] != workspaces[0] || descs[i].out_features != descs[0].out_features || descs[i].num_indices != descs[0].num_indices ||
-          descs[i].bias != descs[0].bias || descs[i].in_features != descs[0].in_features || !vptq::gemv_sliced_tok_one_pass_parts(descs[i], tokens, true))
-        return fail(VPTQ_E_UNSUPPORTED, "column parts share y, the workspace, the output bias, have one width and take the tokens in one pass");
+      if (!vptq::gemv_sliced_tok_one_pass_parts(descs[i], tokens, true)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
   }
   if (!vptq::gemv_sliced_tok_groupable(descs, layouts, n, tokens, (flags & VPTQ_GEMV_EXACT) != 0))
     return fail(VPTQ_E_UNSUPPORTED, "a sliced group of 2 - 4 tokens takes layers of ONE format, dtype and input width whose layouts carry wstart");

@@ -978,11 +978,89 @@ static hipError_t launch_sl_dt(const SlicedGroupParams& P, int v, int nsl, bool 
   return res ? launch_sl<DT, 16, true, 8, false>(P, lds, st) : launch_sl<DT, 16, false, 8, false>(P, lds, st);
 }
 
-bool sl_layout_ok(const VptqLayerDesc& d, const VptqSlicedLayout& L, int nsl, bool res, int k) {
-  // (a sliced table needs at least one entry per slice; whole = every workgroup of the table holds all of it)
-  return (L.n_slices != 0 ? L.n_slices : 8) == nsl && (L.elems_per_lane == 0 || L.elems_per_lane == 1) && (!res || L.res) &&
-         L.rows_per_wave >= 1 && L.rows_per_wave <= kSLMaxRowsPerWave && L.elems && L.blocks && L.first &&
-         (((uintptr_t)L.elems) & 3) == 0 && (L.whole_table == 0 || L.whole_table == 1) && (L.whole_table || k >= nsl);
+SlicedLayoutSet sl_piece_set(const VptqLayerDesc& d, bool exact) {
+  // (the reference's roundings need c and r in one lane: always ONE layout, bucketed by the main index)
+  SlicedLayoutSet S = {};
+  S.parts = 1, S.tables = !exact && sl_two(d) ? 2 : 1, S.slices = gemv_sliced_slices(d, exact), S.exact = exact;
+  S.whole[1] = S.tables == 2 ? gemv_sliced_whole_table(d, 1) : 0;
+  S.side_bytes = d.num_res_centroids == 0 || S.tables == 2 ? 0 : (sl_res256(d) ? 1 : 2);
+  return S;
+}
+VptqLayerDesc sl_part_desc(const VptqLayerDesc& d, int parts, int p) {
+  VptqLayerDesc q = d;
+  const int w = d.group_size / parts;
+  q.in_features = q.group_size = w;
+  const size_t off = (size_t)2 * p * w;   // (16-bit column-order tensors)
+  if (q.weight_scale) q.weight_scale = (const char*)q.weight_scale + off;
+  if (q.weight_bias) q.weight_bias = (const char*)q.weight_bias + off;
+  if (q.perm) q.perm = (const uint16_t*)((const char*)q.perm + off);
+  if (q.scale_permuted) q.scale_permuted = (const char*)q.scale_permuted + off;
+  if (q.bias_permuted) q.bias_permuted = (const char*)q.bias_permuted + off;
+  return q;
+}
+// the column parts the reference's roundings are served with: 1 where the layer fits in one piece, else 2 or 3 equal parts of a
+// multiple of 8 columns whose slices' arrivals one accumulator word counts; 0 = none
+static int sl_exact_parts(const VptqLayerDesc& d) {
+  const char* e = vptq::tune_env("VPTQ_SLICED_PARTS");   // (A/B: at least this many parts where the columns divide)
+  const int least = e && atoi(e) > 1 ? atoi(e) : 1;
+  const bool whole = gemv_sliced_eligible(d, true);
+  if (whole && least <= 1) return 1;
+  for (int parts = 2; parts <= 3; ++parts) {
+    if (parts < least || d.group_size % (8 * parts) != 0) continue;
+    const VptqLayerDesc q = sl_part_desc(d, parts, 0);
+    if (gemv_sliced_eligible(q, true) && gemv_sliced_slices(q, true) * parts <= 127) return parts;
+  }
+  return least > 1 && whole ? 1 : 0;
+}
+SlicedLayoutSet sl_layout_set(const VptqLayerDesc& d, bool exact) {
+  const int parts = exact ? sl_exact_parts(d) : (gemv_sliced_eligible(d, false) ? 1 : 0);
+  if (parts == 0) return SlicedLayoutSet{};
+  SlicedLayoutSet S = sl_piece_set(parts > 1 ? sl_part_desc(d, parts, 0) : d, exact);   // (equal parts: one answer)
+  S.parts = parts;
+  return S;
+}
+
+unsigned sl_check_layouts(const VptqLayerDesc& d, const SlicedLayoutSet& S, const VptqSlicedLayout* L, int n, unsigned needs,
+                          int rows_per_wave, int* which) {
+  const bool launch = (needs & kSLNeedLaunch) != 0;
+  for (int i = 0; i < n; ++i) {
+    const VptqSlicedLayout& l = L[i];
+    const int t = S.tables == 2 ? i : 0;
+    const bool side = t == 0 && S.side_bytes != 0;
+    const uintptr_t e = (uintptr_t)l.elems, r = (uintptr_t)l.res;
+    unsigned f = 0;
+    if (!l.elems || !l.blocks || !l.first || ((needs & kSLNeedWstart) && !l.wstart)) f |= kSLFaultTensors;
+    if (((needs & kSLNeedRows) && l.n_slices == 0 ? 8 : l.n_slices) != S.slices) f |= kSLFaultSlices;
+    if ((needs & kSLNeedWhole) && l.whole_table != S.whole[t]) f |= kSLFaultWhole;
+    if (needs & kSLNeedBuilt) {
+      if (side != (l.res != nullptr)) f |= kSLFaultRes;
+      const uintptr_t words = (uintptr_t)l.blocks | (uintptr_t)l.first | r | ((needs & kSLNeedWstart) ? (uintptr_t)l.wstart : 0);
+      if ((e & 15) != 0 || (words & 3) != 0 || ((needs & kSLNeedRes8) && S.side_bytes == 2 && (r & 7) != 0)) f |= kSLFaultAlign;
+    } else if (side && (S.exact || launch)) {
+      // (WHO ASKS decides, as it did while each had its own copy: an entry holds the exact arithmetic's stream, uint8 or uint16, to "set,
+      // at an even address" and does not look at a folded one; the launch behind it needs every stream set and the uint16 one even)
+      if (!l.res || ((r & 1) != 0 && (!launch || S.side_bytes == 2))) f |= kSLFaultRes;
+    }
+    if ((needs & kSLNeedRows) && (l.rows_per_wave < 1 || l.rows_per_wave > kSLMaxRowsPerWave ||
+                                  (rows_per_wave != 0 && l.rows_per_wave != rows_per_wave)))
+      f |= kSLFaultRows;
+    if (launch) {
+      if (l.elems_per_lane != 0 && l.elems_per_lane != 1) f |= kSLFaultElemsPerLane;
+      if ((e & 3) != 0) f |= kSLFaultAlign;
+      // (a sliced table needs at least one entry per slice; whole = every workgroup of the table holds all of it)
+      if (!l.whole_table && (t ? d.num_res_centroids : d.num_centroids) < S.slices) f |= kSLFaultFewEntries;
+    }
+    if (f && which) *which = i;
+    if (f) return f;
+  }
+  return 0;
+}
+bool sl_parts_share(const VptqLayerDesc* d, void* const* y, void* const* ws, int n) {
+  for (int i = 1; i < n; ++i)
+    if (y[i] != y[0] || ws[i] != ws[0] || d[i].out_features != d[0].out_features || d[i].num_indices != d[0].num_indices ||
+        d[i].bias != d[0].bias || d[i].in_features != d[0].in_features)
+      return false;
+  return true;
 }
 
 // L: one layout (residual none / the 256-entry path of v = 8) or TWO consecutive ones (any other residual codebook: [0]
@@ -990,16 +1068,12 @@ bool sl_layout_ok(const VptqLayerDesc& d, const VptqSlicedLayout& L, int nsl, bo
 // (slice, row block) workgroups run beside the main table's in the SAME launch and meet them in the output's accumulator
 // word - two launches, one per table, cost a second boundary, a second epilogue and half the workgroups in flight (8192^2: 27.2 us
 // against 21.2; 4096^2: 17.8 against 12.0)
-static hipError_t sl_fill(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int flags, void* ws,
-                          SlicedParams& P, uint32_t& lds, int tokens = 1) {
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
+static hipError_t sl_fill(const VptqLayerDesc& d, const SlicedLayoutSet& S, const VptqSlicedLayout* L, const void* x, void* y, int flags,
+                          void* ws, SlicedParams& P, uint32_t& lds, int tokens = 1) {
+  const bool exact = S.exact;
   if (tokens != 1 && !gemv_sliced_exact_tokens_ok(d, tokens)) return hipErrorInvalidValue;
-  const bool res = sl_res256(d), rg = exact && sl_two(d), two = sl_two(d) && !exact;
-  const int nsl = gemv_sliced_slices(d, exact);
-  if (nsl == 0 || !sl_layout_ok(d, L[0], nsl, res || rg, d.num_centroids) || L[0].whole_table != 0 ||
-      (rg && (((uintptr_t)L[0].res) & 1) != 0) ||
-      (two && (!sl_layout_ok(d, L[1], nsl, false, d.num_res_centroids) || L[1].rows_per_wave != L[0].rows_per_wave ||
-               L[1].whole_table != gemv_sliced_whole_table(d, 1))) ||
+  const bool res = S.side_bytes == 1, rg = S.side_bytes == 2, two = S.tables == 2;
+  if (S.slices == 0 || sl_check_layouts(d, S, L, S.tables, kSLNeedRows | kSLNeedWhole | kSLNeedLaunch, L[0].rows_per_wave) != 0 ||
       !ws || (((uintptr_t)x) & 15) != 0)
     return hipErrorInvalidValue;
   P = SlicedParams{};
@@ -1100,23 +1174,18 @@ hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayo
   const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
   const bool parts = (flags & VPTQ_GEMV_COLUMN_PARTS) != 0;
   if (!gemv_sliced_groupable(d, n, exact) || (tokens != 1 && !exact)) return hipErrorInvalidValue;
-  if (parts) {
-    for (int i = 1; i < n; ++i)
-      if (y[i] != y[0] || ws[i] != ws[0] || d[i].out_features != d[0].out_features || d[i].num_indices != d[0].num_indices || d[i].bias != d[0].bias)
-        return hipErrorInvalidValue;
-    if (!exact) return hipErrorInvalidValue;   // (the folded form stages 32768 columns in one piece: no parts needed)
-  }
+  // (the folded form stages 32768 columns in one piece: no parts needed)
+  if (parts && (!exact || !sl_parts_share(d, y, ws, n))) return hipErrorInvalidValue;
   SlicedGroupParams GP = {};
   GP.n = n;
   uint32_t lds = 0;
-  const int tables = exact ? 1 : gemv_sliced_tables(d[0]);
-  const int nsl = gemv_sliced_slices(d[0], exact);
-  const int nslt = nsl * tables;
+  const SlicedLayoutSet S0 = sl_piece_set(d[0], exact);   // (one format: one table and slice count for every member)
+  const int tables = S0.tables, nsl = S0.slices, nslt = nsl * tables;
   for (int i = 0; i < n; ++i) {
     uint32_t l = 0;
     // (a part without a permutation reads its own columns of x; with one, its slice of `perm` indexes the whole activation)
     const void* const xi = (parts && d[i].perm == nullptr) ? (const void*)((const uint16_t*)x + (size_t)i * d[i].in_features) : x;
-    const hipError_t e = sl_fill(d[i], L + (size_t)i * tables, xi, y[i], flags, ws[i], GP.p[i], l, tokens);
+    const hipError_t e = sl_fill(d[i], i ? sl_piece_set(d[i], exact) : S0, L + (size_t)i * tables, xi, y[i], flags, ws[i], GP.p[i], l, tokens);
     if (e != hipSuccess) return e;
     if (parts) GP.p[i].x_stride = n * d[i].in_features;   // (tokens of the WHOLE activation: a part's columns lie one row of all parts apart)
     GP.p[i].corr = (n == 1 && tokens == 1 && !exact) ? corr : nullptr;   // (selective roundings: one layer, one token, folded form)

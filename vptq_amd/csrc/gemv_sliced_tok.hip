@@ -823,7 +823,8 @@ hipError_t launch_st_tok8(int dtype, const SlicedTokGroupParams& P, int grid, in
 // ---- host side -------------------------------------------------------------------
 static bool st_exact_ok(const VptqLayerDesc& d) { return !sl_two(d) && gemv_sliced_eligible(d, true); }
 static size_t st_partial_bytes(const VptqLayerDesc& d, int tokens, bool exact) {
-  const size_t parts = exact ? (size_t)gemv_sliced_slices(d, true) : (size_t)gemv_sliced_slices(d) * (sl_two(d) ? 2 : 1);
+  const SlicedLayoutSet S = sl_piece_set(d, exact);
+  const size_t parts = (size_t)S.slices * S.tables;
   return ((size_t)tokens * parts * d.num_indices * d.vector_len * sizeof(float) + 255) / 256 * 256;
 }
 static size_t st_counter_bytes(const VptqLayerDesc& d) {
@@ -853,7 +854,8 @@ static bool st_one_pass(const VptqLayerDesc& d, int tokens, bool exact) {
 
 // rows per wave: one round of workgroups (slices x tables x row blocks of 16 waves ~ the CUs)
 static int st_rows_per_wave(const VptqLayerDesc& d, bool exact) {
-  const long long nslt = exact ? (long long)gemv_sliced_slices(d, true) : (long long)gemv_sliced_slices(d) * (sl_two(d) ? 2 : 1);
+  const SlicedLayoutSet S = sl_piece_set(d, exact);
+  const long long nslt = (long long)S.slices * S.tables;
   long long r = ((long long)d.num_indices * nslt + kSLWaves * 256 - 1) / (kSLWaves * 256);
   return (int)(r < 1 ? 1 : r > kSLMaxRowsPerWave ? kSLMaxRowsPerWave : r);
 }
@@ -918,11 +920,10 @@ static hipError_t st_fill(const VptqLayerDesc& d, const VptqSlicedLayout* L, con
                           int rpw0, SlicedTokParams& TP, StPlan& pl, StPermJobs& jobs) {
   const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
   if (!gemv_sliced_tok_eligible(d, L, tokens, exact) || !st_plan(d, L, tokens, exact, pl, rpw0)) return hipErrorInvalidValue;
-  const bool res = sl_res256(d), two = sl_two(d);
-  const int nsl = gemv_sliced_slices(d, exact);
-  if (!sl_layout_ok(d, L[0], nsl, res, d.num_centroids) || L[0].whole_table != 0 ||
-      (two && (!sl_layout_ok(d, L[1], nsl, false, d.num_res_centroids) || L[1].whole_table != gemv_sliced_whole_table(d, 1))) ||
-      !ws || (((uintptr_t)x) & 15) != 0 || (d.in_features % 8) != 0)
+  const SlicedLayoutSet S = sl_piece_set(d, exact);
+  const bool res = S.side_bytes == 1, two = S.tables == 2;
+  // (the kernel takes its rows per wave from the plan: the structs' own need not agree)
+  if (sl_check_layouts(d, S, L, S.tables, kSLNeedRows | kSLNeedWhole | kSLNeedLaunch) != 0 || !ws || (((uintptr_t)x) & 15) != 0 || (d.in_features % 8) != 0)
     return hipErrorInvalidValue;
   TP = SlicedTokParams{};
   SlicedParams& P = TP.p;
@@ -1013,8 +1014,8 @@ hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSliced
   SlicedTokGroupParams GP = {};
   GP.n = n;
   StPermJobs jobs = {};
-  const int tables = exact ? 1 : gemv_sliced_tables(d[0]);
-  const int nslt = gemv_sliced_slices(d[0], exact) * tables;
+  const SlicedLayoutSet S0 = sl_piece_set(d[0], exact);
+  const int tables = S0.tables, nsl = S0.slices, nslt = nsl * tables;
   // rows per wave: one round of workgroups over ALL members
   long long rows = 0;
   for (int i = 0; i < n; ++i) rows += d[i].num_indices;
@@ -1040,8 +1041,7 @@ hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSliced
     if (e != hipSuccess) return e;
   }
   const int grid = GP.start[n];
-  const bool res = sl_res256(d[0]), two = sl_two(d[0]);
-  const int nsl = gemv_sliced_slices(d[0], exact);
+  const bool res = S0.side_bytes == 1, two = S0.tables == 2;
   if (exact)
     return tok == 8 ? launch_st_ex8(d[0].dtype, GP, grid, d[0].vector_len, nsl, res, lds, st)
                     : launch_st_ex4(d[0].dtype, GP, grid, d[0].vector_len, nsl, res, lds, st);

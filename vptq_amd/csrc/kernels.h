@@ -114,7 +114,7 @@ int gemv_sliced_exact_tokens_parts(const VptqLayerDesc& d, int tokens);   // 0: 
 size_t gemv_sliced_exact_tokens_workspace_bytes(const VptqLayerDesc& d, int tokens);
 // repack.hip - the packed index stream of a layer rebuilt from its exact sliced layout(s) (vptq_sliced_layout_repack)
 size_t sliced_repack_lds_bytes(const VptqLayerDesc& d);
-hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, void* out, hipStream_t st);
+hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, int side_bytes, void* out, hipStream_t st);   // side_bytes: SlicedLayoutSet's
 // layout_build.hip - a sliced layout built from the packed index stream (vptq_sliced_layout_plan / vptq_sliced_layout_fill)
 struct LayoutBuildParams {
   const uint32_t* packed;   // [N][row_words]

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kRPThreads) void sliced_repack_kernel(RepackArgs a)
 
 size_t sliced_repack_lds_bytes(const VptqLayerDesc& d) { return (size_t)((d.row_words + 3) / 4) * 16; }
 
-hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, void* out, hipStream_t st) {
+hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, int side_bytes, void* out, hipStream_t st) {
   static std::atomic<int> attr{0};
   if (!attr.load()) {
     const hipError_t e = hipFuncSetAttribute((const void*)sliced_repack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kRPMaxLds);
@@ -117,7 +117,7 @@ hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* 
   a.T = d.index_bits + d.res_bits;
   a.index_bits = d.index_bits;
   a.row_words = d.row_words;
-  a.side = d.num_res_centroids == 0 ? 0 : (d.vector_len == 8 && d.num_res_centroids == 256 ? 1 : 2);
+  a.side = side_bytes;
   hipLaunchKernelGGL(sliced_repack_kernel, dim3((unsigned)d.num_indices), dim3(kRPThreads), sliced_repack_lds_bytes(d), st, a);
   return hipGetLastError();
 }

@@ -70,6 +70,35 @@ static __device__ __forceinline__ void sl_for_slots(F&& f) { sl_for_range<0, Q>(
 bool sl_res256(const VptqLayerDesc& d);   // v = 8 with the 256-entry residual table: a byte per element beside the main layout
 bool sl_two(const VptqLayerDesc& d);      // any other residual table: a second table with a layout of its own
 uint32_t sl_tab_bytes(const VptqLayerDesc& d, int k, int whole, bool exact = false);   // bytes a workgroup of a k-entry table holds
-bool sl_layout_ok(const VptqLayerDesc& d, const VptqSlicedLayout& L, int nsl, bool res, int k);
+
+// WHICH LAYOUTS a layer is served from in one arithmetic (the one statement the entries, the builder and vptq_sliced_layout_set read):
+// parts: column parts with a layout each (0 = not served); per part `tables` consecutive structs of `slices` slices; whole[t]: every
+// workgroup of table t holds all of it; side_bytes: the `res` stream beside table 0's words - 0 none / 1 uint8 / 2 uint16
+// A set comes from sl_layout_set / sl_piece_set, never from a caller's own arithmetic (the one hand-built set is that of
+// vptq_sliced_layout_fill, which holds its struct to the caller's SPEC); name the members when building one: their order may change.
+struct SlicedLayoutSet { int parts, tables, slices, whole[2], side_bytes; bool exact; };
+SlicedLayoutSet sl_layout_set(const VptqLayerDesc& d, bool exact);
+// ... of a descriptor taken IN ONE PIECE (what a GEMV entry is handed: a layer, or one column part) that is gemv_sliced_eligible
+SlicedLayoutSet sl_piece_set(const VptqLayerDesc& d, bool exact);
+VptqLayerDesc sl_part_desc(const VptqLayerDesc& d, int parts, int p);   // column part p of `parts`: widths, column-order tensors advanced
+
+// IS THIS VptqSlicedLayout ARRAY VALID for (d, set)?  L: n consecutive structs of one piece (repack: the parts' structs).  Returns 0,
+// or the kSLFault* reasons the first bad struct (*which) is turned down for.  needs: what the caller requires of the structs -
+enum : unsigned {
+  kSLNeedRows = 1,      // GEMV entries: rows_per_wave in [1, 64] (and = rows_per_wave if != 0); n_slices 0 reads as 8; the `res` of an EXACT
+                        // set's side stream (uint8 or uint16) set, at an even address - a folded set's `res` is not looked at
+  kSLNeedLaunch = 2,    // + what only a launch's parameter fill asks: elems_per_lane 0 / 1, elems 4-byte aligned, an entry per slice; `res` set
+                        // for EVERY side stream (the folded uint8 one too), an even address only of the uint16 one (the uint8 one is read by bytes)
+  kSLNeedWhole = 4,     // whole_table as the set has it (the builder does not read it)
+  kSLNeedBuilt = 8,     // repack / fill: `res` set IFF the set has a side stream; elems 16-byte, blocks / first / res 4-byte aligned
+  kSLNeedWstart = 16,   // fill: wstart set and 4-byte aligned
+  kSLNeedRes8 = 32,     // repack: a uint16 side stream 8-byte aligned (read four at a time)
+};
+enum : unsigned { kSLFaultTensors = 1, kSLFaultSlices = 2, kSLFaultWhole = 4, kSLFaultRes = 8, kSLFaultRows = 16, kSLFaultAlign = 32,
+                  kSLFaultElemsPerLane = 64, kSLFaultFewEntries = 128 };
+unsigned sl_check_layouts(const VptqLayerDesc& d, const SlicedLayoutSet& set, const VptqSlicedLayout* L, int n, unsigned needs,
+                          int rows_per_wave = 0, int* which = nullptr);
+// VPTQ_GEMV_COLUMN_PARTS: the parts have one y, workspace, output bias and width
+bool sl_parts_share(const VptqLayerDesc* d, void* const* y, void* const* ws, int n);
 
 }  // namespace vptq

@@ -232,7 +232,8 @@ def rows_per_wave_for(n_rows: int, slices: int = 8, workgroups: int = 256) -> in
 
 def part_desc(desc, c0: int, c1: int):
     """copy of a layer's descriptor that stands for its columns [c0, c1) alone (`VPTQ_GEMV_COLUMN_PARTS`, include/vptq_hip.h): widths
-    and the column-order tensors advanced to c0 (16-bit elements).  The tensors stay owned by the layer's own descriptor."""
+    and the column-order tensors advanced to c0 (16-bit elements).  The tensors stay owned by the layer's own descriptor.  The twin of
+    the library's `sl_part_desc` (vptq_amd/csrc/gemv_sliced.hip), which the part rule of `vptq_sliced_layout_set` is stated with."""
     d = B.LayerDesc.from_buffer_copy(desc)
     d.in_features = d.group_size = c1 - c0
     for f in ("weight_scale", "weight_bias", "perm", "scale_permuted", "bias_permuted"):
@@ -242,25 +243,20 @@ def part_desc(desc, c0: int, c1: int):
     return d
 
 
+def layout_set(desc, exact: bool):
+    """the layouts the library serves this layer from in one arithmetic (`vptq_sliced_layout_set`, include/vptq_hip.h): column parts
+    (0: not served), tables per part, slices, which table is held whole, bytes per element of the residual side stream"""
+    out = B.SlicedLayoutSet()
+    B.check(B.lib().vptq_sliced_layout_set(desc, B.GEMV_EXACT if exact else 0, out), "vptq_sliced_layout_set")
+    return out
+
+
 def exact_column_parts(desc, group_size: int):
     """(parts, slices) with which the reference's roundings are served over sliced layouts: (1, n) where the layer fits in one
-    piece, (2 or 3, n) where equal column parts of a multiple of 8 columns do (28672-column layers: 2 x 14336), (0, 0) else"""
-    import os
-    least = int(B.tune_env("VPTQ_SLICED_PARTS", "1") or 1)     # (A/B: at least this many parts where the columns divide)
-    n = B.lib().vptq_sliced_layout_supported_for(desc, B.GEMV_EXACT)
-    if n and least <= 1:
-        return 1, n
-    for parts in (2, 3):
-        if parts < least:
-            continue
-        if group_size % (8 * parts) == 0:
-            n = B.lib().vptq_sliced_layout_supported_for(part_desc(desc, 0, group_size // parts), B.GEMV_EXACT)
-            if n and n * parts <= 127:
-                return parts, n
-    if least > 1:
-        n = B.lib().vptq_sliced_layout_supported_for(desc, B.GEMV_EXACT)
-        return (1, n) if n else (0, 0)
-    return 0, 0
+    piece, (2 or 3, n) where equal column parts of a multiple of 8 columns do (28672-column layers: 2 x 14336), (0, 0) else -
+    the library's answer (`layout_set`), which reads the descriptor's own group_size: the argument is kept for the signature only"""
+    s = layout_set(desc, True)
+    return int(s.parts), int(s.n_slices)
 
 
 def _layout_structs(tensors, whole, rpw: int, slices: int):
@@ -290,6 +286,22 @@ def _launch_activation(obj, lay, x: torch.Tensor, tokens=None, served: bool = Tr
     return x
 
 
+def _new_output(obj, x: torch.Tensor, out_features: int, flags: int = 0):
+    """the output tensor of a launch of `obj` over the activation x: its leading dimensions, float32 with `GEMV_OUT_F32`"""
+    return torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if (flags & B.GEMV_OUT_F32) else obj._dtype, device=obj.dev)
+
+
+def _launch_failed(rc: int, what: str, workspaces):
+    """the tail of every launch whose return code is not 0: None where the library says "unsupported" (the caller takes the regular
+    route); else the error, after zeroing the workspaces - a launch that did not happen or did not finish may have left accumulator
+    words or arrival counters behind; the buffers themselves stay: a captured graph may hold their addresses"""
+    if rc != B.E_UNSUPPORTED:
+        for ws in workspaces:
+            ws.zero_()
+        B.check(rc, what)
+    return None
+
+
 class SlicedGemv:
     """One-token forward of a v8-k65536-0 `VQuantLinear` over its sliced layout."""
 
@@ -307,27 +319,17 @@ class SlicedGemv:
             raise ValueError("selective roundings over the sliced layouts: fp16 layers with scale and bias")
         cache = layer._descriptor()
         self.desc, self.dev = cache.desc, cache.device
-        self.parts = 1
-        if self.exact:   # (a layer too wide for 6 bytes of LDS per column in one piece: equal column parts, one layout each)
-            self.parts, self.slices = exact_column_parts(self.desc, layer.group_size)
-        else:
-            self.slices = B.lib().vptq_sliced_layout_supported_for(self.desc, 0)
-        if not self.slices:
+        # (a layer too wide for the exact arithmetic's 6 bytes of LDS per column in one piece: equal column parts, one layout each; the
+        # reference's roundings need c and r in one lane: always ONE table, a residual codebook other than v8's 256-entry one rides
+        # along as a 16-bit side stream; folded: a second table whose slice would be under 16 KiB is held WHOLE by its workgroups)
+        lset = layout_set(self.desc, self.exact)
+        self.parts, self.slices, n_tables, side = int(lset.parts), int(lset.n_slices), int(lset.tables), int(lset.side_bytes)
+        if not self.parts:
             raise ValueError("the sliced layout serves v = 8 / 16 layers with 16384 ... 65536 main centroids, group_size <= 32768"
                              " (reference roundings: one table, up to ~16000 columns)")
-        kr = layer.num_res_centroids if layer.enable_residual else 0
-        ib = int(layer.num_centroids).bit_length() - 1
-        rb = int(kr).bit_length() - 1 if kr else 0
-        # (the reference's roundings need c and r in one lane: always ONE layout, bucketed by the main index; a residual codebook
-        # other than v8's 256-entry one rides along as a 16-bit side stream and its entries are gathered from device memory)
-        n_tables = 1 if self.exact else B.lib().vptq_sliced_layout_tables(self.desc)
-        side16 = self.exact and kr > 0 and not (layer.vector_len == 8 and kr == 256)
-        self._side16 = side16
-        # a second table whose slice would be under 16 KiB is held WHOLE by each of its workgroups while it fits (the
-        # library decides: the kernel's LDS budget)
-        whole = [False, n_tables == 2 and bool(B.lib().vptq_sliced_layout_whole_table(self.desc, 1))]
+        self._side16 = side == 2
+        ib, rb = int(self.desc.index_bits), int(self.desc.res_bits)
         packed = layer.indices.data
-        side = (2 if side16 else 1) if kr else 0   # bytes per element of the residual side stream
         if device_builder_enabled(packed):
             # indices on a ROCm device: the library builds the same tensors, byte for byte, from the packed stream (layout_build.hip) -
             # no index matrices, no sorts: the tensors themselves are the only memory the build takes
@@ -343,16 +345,11 @@ class SlicedGemv:
                 src, bits = (ridx, rb) if table else (idx, ib)
                 return layout_from_indices(src[:, cols].contiguous(), self.slices, ridx[:, cols].contiguous() if side else None, bits,
                                            whole_table, side_dtype=torch.int16 if side == 2 else torch.uint8)
+        # ((c + r) s x = c s x + r s x: a second table is a layout bucketed by ITS index; the side stream rides beside table 0)
+        self._whole = [bool(lset.whole_table[t]) for _ in range(self.parts) for t in range(n_tables)]
+        self._tensors = [build(t, bool(lset.whole_table[t]), 0 if t else side, p) for p in range(self.parts) for t in range(n_tables)]
         if self.parts > 1:
-            self._tensors = [build(0, False, side, p) for p in range(self.parts)]
             self._part_descs = self._make_part_descs(self.desc)
-            whole = [False] * self.parts
-        elif n_tables == 2:
-            # (c + r) s x = c s x + r s x: the residual codebook is a second table with a layout bucketed by ITS index
-            self._tensors = [build(0, False, 0, 0), build(1, whole[1], 0, 0)]
-        else:
-            self._tensors = [build(0, False, side, 0)]
-        self._whole = whole[:len(self._tensors)]
         self.elems, self.blocks, self.first, self.res, self.wstart = self._tensors[0]
         # (a two-table layer runs 2 x slices workgroups per row block in its one launch)
         rpw = rows_per_wave or rows_per_wave_for(self.blocks.shape[1], self.slices * len(self._tensors))
@@ -430,10 +427,8 @@ class SlicedGemv:
     def tokens_supported(self, tokens: int) -> bool:
         """does the library's kernel for 2 - 4 tokens over these layouts take this layer (its activations must fit the LDS
         beside the slice in at most 4 column phases)?"""
-        if self.exact and self.parts > 1:    # (column parts: 2 / 3 tokens where every part takes them in one pass, nothing else)
-            return self.tokens_one_pass(tokens)
-        if self.exact and self._side16:      # (the reference's roundings over two-table formats: 2 / 3 tokens in one pass, nothing else)
-            return self.tokens_one_pass(tokens)
+        if self.exact and (self.parts > 1 or self._side16):   # (column parts, and the reference's roundings over two-table formats:
+            return self.tokens_one_pass(tokens)               # 2 / 3 tokens where every part takes them in one pass, nothing else)
         if self.selective:                   # (one token: several tokens of such a layer take the module's regular route)
             return False
         return bool(B.lib().vptq_quant_gemv_sliced_tokens_supported_for(self.desc, self._lay_ref, int(tokens), self._flags))
@@ -497,14 +492,12 @@ class SlicedGemv:
         return ws[0]
 
     def _launch_tokens(self, x, out, flags, tokens):
-        lay = self.layer
         sp = B.current_stream_ptr(self.dev)
         ws = self._tokens_workspace(sp, tokens)
         if ws is None:
             return None
         if out is None:
-            out = torch.empty(x.shape[:-1] + (lay.out_features,),
-                              dtype=torch.float32 if (flags & B.GEMV_OUT_F32) else self._dtype, device=self.dev)
+            out = _new_output(self, x, self.layer.out_features, flags)
         if self.parts > 1:   # column parts of one layer: one grouped launch, shared output and workspace
             yp, wp, _ = self._pp
             for i in range(self.parts):
@@ -515,19 +508,14 @@ class SlicedGemv:
                                                                flags | self._flags | B.GEMV_COLUMN_PARTS, wp, wb, sp)
         else:
             rc = self._fn_tok(self.desc, self._lay_ref, x.data_ptr(), out.data_ptr(), tokens, flags | self._flags, ws.data_ptr(), ws.numel(), sp)
-        if rc == B.E_UNSUPPORTED:
-            return None
-        if rc:
-            ws.zero_()   # (a launch that did not happen or did not finish may have left arrival counters behind; the buffer
-            B.check(rc, "vptq_quant_gemv_sliced_tokens")   # itself stays: a captured graph may hold its address)
-        return out
+        return _launch_failed(rc, "vptq_quant_gemv_sliced_tokens", (ws,)) if rc else out
 
     def _launch(self, x, out, flags):
         sp = B.current_stream_ptr(self.dev)
         ws = self._workspace(sp)
         if ws is None:
             return None
-        if out is None:
+        if out is None:   # (written out, here and in SlicedGroupGemv._launch: the one-token path, a call per token and layer)
             out = torch.empty(x.shape[:-1] + (self.layer.out_features,),
                               dtype=torch.float32 if (flags & B.GEMV_OUT_F32) else self._dtype, device=self.dev)
         if self.parts > 1:   # column parts of one layer: one grouped launch, shared output and accumulator words
@@ -539,14 +527,7 @@ class SlicedGemv:
                                                         flags | self._flags | B.GEMV_COLUMN_PARTS, wp, wb, sp)
         else:
             rc = self._fn(self.desc, self._lay_ref, x.data_ptr(), out.data_ptr(), flags | self._flags, ws.data_ptr(), self._ws_bytes, sp)
-        if rc == B.E_UNSUPPORTED:
-            return None
-        if rc:
-            # (a launch that did not happen or did not finish may have left accumulator words behind; the buffer itself
-            # stays: a captured graph may hold its address)
-            ws.zero_()
-            B.check(rc, "vptq_quant_gemv_sliced")
-        return out
+        return _launch_failed(rc, "vptq_quant_gemv_sliced", (ws,)) if rc else out
 
 
 class SlicedGroupGemv:
@@ -602,26 +583,19 @@ class SlicedGroupGemv:
 
     def _launch_tokens(self, x, tokens):
         sp = B.current_stream_ptr(self.dev)
-        n = len(self.members)
         wss = []
         for m in self.members:
             ws = m._tokens_workspace(sp, tokens)
             if ws is None:
                 return None
             wss.append(ws)
-        ys = [torch.empty(x.shape[:-1] + (m.layer.out_features,), dtype=self._dtype, device=self.dev) for m in self.members]
-        wb = (C.c_size_t * n)(*[w.numel() for w in wss])
+        ys = [_new_output(self, x, m.layer.out_features) for m in self.members]
+        wb = (C.c_size_t * len(wss))(*[w.numel() for w in wss])
         for i, (y, w) in enumerate(zip(ys, wss)):
             self._yp[i] = y.data_ptr()
             self._wp[i] = w.data_ptr()
-        rc = B.lib().vptq_quant_gemv_sliced_tokens_grouped(self.descs, self.layouts, n, x.data_ptr(), self._yp, tokens, self._flags, self._wp, wb, sp)
-        if rc == B.E_UNSUPPORTED:
-            return None
-        if rc:
-            for w in wss:
-                w.zero_()
-            B.check(rc, "vptq_quant_gemv_sliced_tokens_grouped")
-        return ys
+        rc = B.lib().vptq_quant_gemv_sliced_tokens_grouped(self.descs, self.layouts, len(ys), x.data_ptr(), self._yp, tokens, self._flags, self._wp, wb, sp)
+        return _launch_failed(rc, "vptq_quant_gemv_sliced_tokens_grouped", wss) if rc else ys
 
     def _launch(self, x):
         sp = B.current_stream_ptr(self.dev)
@@ -633,10 +607,4 @@ class SlicedGroupGemv:
             self._yp[i] = y.data_ptr()
             self._wp[i] = w.data_ptr()
         rc = self._fn(self.descs, self.layouts, len(ys), x.data_ptr(), self._yp, self._flags, self._wp, self._wb, sp)
-        if rc == B.E_UNSUPPORTED:
-            return None
-        if rc:
-            for w in wss:
-                w.zero_()
-            B.check(rc, "vptq_quant_gemv_sliced_grouped")
-        return ys
+        return _launch_failed(rc, "vptq_quant_gemv_sliced_grouped", wss) if rc else ys
