@@ -554,6 +554,30 @@ VPTQ_API int vptq_quant_gemv_grouped_instance(const VptqLayerDesc* descs, int n,
                                               size_t bytes);
 VPTQ_API int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf,
                                             size_t bytes);
+/* The same for the SLICED entries (added within ABI 11; present when the symbols are): which instantiation of gemv_sliced_kernel /
+ * gemv_sliced_tok_kernel / gemv_hot_kernel a call over these layouts would launch.  descs, layouts, n, flags: as the call takes them
+ * (VPTQ_GEMV_COLUMN_PARTS included); of the VptqSlicedLayout structs only the scalar fields and the pointers' being set and their
+ * alignment are read - nothing is dereferenced, no device is needed.
+ *   vptq_quant_gemv_sliced_instance: n == 1 without VPTQ_GEMV_COLUMN_PARTS answers for vptq_quant_gemv_sliced (VPTQ_GEMV_SELECTIVE:
+ *       the pre-pass in front), else for vptq_quant_gemv_sliced_grouped - which launches the same for one layer, SELECTIVE read as
+ *       EXACT; tokens must be 1.
+ *   vptq_quant_gemv_sliced_tokens_instance: vptq_quant_gemv_sliced_tokens (n == 1 without column parts) / _tokens_grouped; 2 - 8
+ *       tokens; a call that takes the one pass of the one-token kernel answers with that kernel's line.
+ *   gemv_sliced dt=f16|bf16 nsl=8|16|32 res=0|1 v=8|16 two=0|1 ex=0|1 rg=0|1 tok=1|2|3 wpt=0|1 wparts=1|2|4 parts=1..3 n=1..3 rpw=N
+ *       arrivals=N whole1=0|1 side=0|1|2 perm=0|1 corr=0|1
+ *       the template arguments <DT, NSL, RES, V, TWO, EX, RG, TOK, WPT>, then the launch shape: window parts, column parts, group
+ *       members, rows per wave, arrivals per accumulator word (slices x tables x column parts x window parts), the second table held
+ *       whole, bytes per element of the residual side stream, any member with a permutation, the selective pre-pass's products added
+ *   gemv_sliced_tok dt= nsl= res= v= two= tok=2|4|8 ex= phases=1|2|4 rpw=N regsums=0|1 n=1..3 whole1= perm=
+ *       <DT, NSL, RES, V, TWO, TOK (token slots), EX>, column phases, rows per wave, the rows' sums in registers (else LDS), members,
+ *       perm: the permute_x pre-pass runs
+ *   gemv_hot dt= v=        the selective pre-pass, in front of the folded launch: "gemv_hot dt=f16 v=8 | gemv_sliced ... corr=1"
+ * Returns VPTQ_OK, the call's own validation error (VPTQ_E_NULL, VPTQ_E_SHAPE for n, VPTQ_E_TOKENS, VPTQ_E_UNSUPPORTED, the layout
+ * errors), or VPTQ_E_WORKSPACE when buf is too small. */
+VPTQ_API int vptq_quant_gemv_sliced_instance(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens, int flags,
+                                             char* buf, size_t bytes);
+VPTQ_API int vptq_quant_gemv_sliced_tokens_instance(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens,
+                                                    int flags, char* buf, size_t bytes);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,11 @@ appears in the enumeration and fails this test until someone adds its row.
 
 The launch-shape facts (units, slots, passes, rgs) depend on the CU count.  Without a device the library takes 256, the
 MI355X's; with a device it asks it.  The tables' instance strings, and so this census, are those of a 256-CU device: on another
-part test_table_instances_are_what_the_library_answers says so at its first row (its probe of the CU count)."""
+part test_table_instances_are_what_the_library_answers says so at its first row (its probe of the CU count).
+
+The second half does the same for the sliced family - gemv_sliced, gemv_sliced_tok, gemv_hot - through
+vptq_quant_gemv_sliced_instance / _tokens_instance and the rows of tests/test_route_models_sliced_gpu.py (their launch shapes do
+not depend on the CU count: the layouts' rows per wave come with the layout structs)."""
 import ctypes as C
 import os
 
@@ -20,6 +24,7 @@ import pytest
 from vptq_amd import _backend as B
 import test_route_models_gpu as rm
 import test_route_models_k256_gpu as k256
+import test_route_models_sliced_gpu as sliced
 from test_route_models_gpu import EXACT, MFMA, VALU, BATCHED, SEL
 
 
@@ -227,3 +232,212 @@ def test_instance_queries_validate_and_need_no_device():
     big_buf = C.create_string_buffer(4096)
     assert lib.vptq_quant_gemv_chain_instance(four, 4, 1, 0, big_buf, 4096) == 0 and big_buf.value.startswith(b"grouped: gemv_k256m ")
     assert lib.vptq_quant_gemv_chain_instance(four, 1, 1, 0, big_buf, 4096) == 0 and big_buf.value.startswith(b"per-layer: gemv_k256m ")
+
+
+# ---------------------------------------------------------------------------------------------- the sliced family
+# gemv_sliced_kernel, gemv_sliced_tok_kernel and gemv_hot_kernel: enumerated through vptq_quant_gemv_sliced_instance / _tokens_instance
+# over fake descriptors and fake layout structs filled from vptq_sliced_layout_set (scalar fields and aligned, never dereferenced
+# pointers), held to the rows of tests/test_route_models_sliced_gpu.py and the sliced tables of test_route_models_gpu.py.
+def fake_sliced_desc(I, O, dt="f16", v=8, k=65536, kr=0, perm=False):
+    d = B.LayerDesc()
+    ib, rb = k.bit_length() - 1, (kr.bit_length() - 1 if kr else 0)
+    d.in_features, d.out_features, d.vector_len, d.num_codebooks, d.group_size = I, O, v, 1, I
+    d.num_centroids, d.num_res_centroids, d.index_bits, d.res_bits = k, kr, ib, rb
+    d.row_words, d.num_indices, d.dtype = (I * (ib + rb) + 31) // 32, (O + v - 1) // v, DTYPES[dt]
+    d.indices, d.centroids, d.res_centroids = 1 << 20, 2 << 20, (3 << 20 if kr else None)
+    d.weight_scale, d.weight_bias = 4 << 20, 5 << 20
+    if perm:
+        d.perm, d.scale_permuted, d.bias_permuted = 6 << 20, 7 << 20, 8 << 20
+    return d
+
+
+def fake_call(I, Os, dt, v, k, kr, perm, mode, rpw=0):
+    """-> (descs, layouts, n, extra flags, entry kind) of the call a row (or a grid point) makes, as SlicedGemv / SlicedGroupGemv
+    would build it: the layout set, the column parts and the rows-per-wave rule of vptq_amd/utils/sliced.py; None: not served"""
+    from vptq_amd.utils.sliced import layout_set, part_desc, rows_per_wave_for
+    exact = mode == "exact"
+    descs = [fake_sliced_desc(I, O, dt, v, k, kr, perm) for O in Os]
+    if mode == "sel" and not B.lib().vptq_quant_gemv_sliced_selective_supported(descs[0]):
+        return None
+    ls = layout_set(descs[0], exact)
+    parts, tables = int(ls.parts), int(ls.tables)
+    if not parts or (parts > 1 and len(Os) > 1):
+        return None
+    if parts > 1:
+        w = I // parts
+        descs = [part_desc(descs[0], p * w, (p + 1) * w) for p in range(parts)]
+    # (SlicedGemv counts a layer's column parts as tables here; SlicedGroupGemv sums its members' rows)
+    rpw = rpw or rows_per_wave_for(sum(int(d.num_indices) for d in descs) if parts == 1 else int(descs[0].num_indices),
+                                   int(ls.n_slices) * tables * parts)
+    lay = [B.SlicedLayout(16 << 20, 17 << 20, 18 << 20, (19 << 20) if (t == 0 and ls.side_bytes) else None, rpw, 1, int(ls.n_slices),
+                          int(ls.whole_table[t]), 20 << 20) for _ in descs for t in range(tables)]
+    return (B.LayerDesc * len(descs))(*descs), (B.SlicedLayout * len(lay))(*lay), len(descs), (sliced.PARTS if parts > 1 else 0), parts
+
+
+def sliced_query(I, Os, dt, tokens, mode, v=8, k=65536, kr=0, perm=False, rpw=0):
+    """the instance string of that call, or None where the library turns it down (not served)"""
+    c = fake_call(I, Os, dt, v, k, kr, perm, mode, rpw)
+    if c is None:
+        return None
+    descs, lay, n, extra, parts = c
+    buf = C.create_string_buffer(1024)
+    fn = B.lib().vptq_quant_gemv_sliced_instance if tokens == 1 else B.lib().vptq_quant_gemv_sliced_tokens_instance
+    rc = fn(descs, lay, n, tokens, sliced.MODE_FLAGS[mode] | extra, buf, len(buf))
+    assert rc in (0, B.E_UNSUPPORTED) or (rc == B.E_TOKENS and tokens > 8), (rc, B.lib().vptq_last_error())
+    return buf.value.decode() if rc == 0 else None
+
+
+def entry_of(Os, entry, instance):
+    """the entry point as the census counts it"""
+    if " parts=2" in instance or " parts=3" in instance:
+        return "parts"
+    return "grouped" if len(Os) > 1 or entry == "grouped" else "single"
+
+
+def sliced_bucket(name, f, tokens, entry, k, kr):
+    """the axes as the census counts them: the tokens asked for, the entry point, the main table's size and the residual table's
+    (neither is in the instance string: the per-slice table bytes and the width of the residual index change with them), and the
+    one-token layouts' rows per wave as 1 / 2 - 16 / 17+"""
+    f = dict(f, tokens=str(tokens), entry=entry, k=str(k), kr=str(kr))
+    if name == "gemv_sliced":
+        r = int(f["rpw"])
+        f["rpw"] = "1" if r == 1 else "2-16" if r <= 16 else "17+"   # (past 16 the lanes holding the rows' words come round again)
+    return f
+
+
+VIEWS.update({
+    "gemv_sliced": [("dt", "nsl", "res", "v", "two", "ex", "rg", "tok", "wpt"),      # every instantiation
+                    ("wparts", "tok"), ("parts", "tok", "perm", "dt"), ("whole1", "two"), ("side", "nsl"), ("perm", "ex", "tok"),
+                    ("entry", "ex", "tok"), ("n", "ex", "dt"), ("rpw", "ex", "dt"), ("corr", "two", "dt", "v"),
+                    ("k", "ex", "dt"), ("kr", "ex", "dt", "v"), ("perm", "ex", "dt")],
+    "gemv_sliced_tok": [("dt", "nsl", "res", "v", "two", "tok", "ex"),              # every instantiation
+                        ("phases", "ex", "tok"), ("regsums", "tok", "dt"), ("whole1", "two"), ("perm", "ex", "dt"), ("n", "ex", "dt"),
+                        ("tok", "tokens"), ("entry", "ex", "tok"), ("k", "ex", "dt"), ("kr", "ex", "dt")],
+    "gemv_hot": [("dt", "v")],
+})
+SLICED_KERNELS = ("gemv_sliced", "gemv_sliced_tok", "gemv_hot")
+# full template tuples per dtype the enumeration must contain, as counted from the launchers
+SLICED_INSTANTIATIONS = {"gemv_sliced": 42, "gemv_sliced_tok": 42, "gemv_hot": 2}
+
+
+def sliced_cells_of(instance, tokens, entry, k=65536, kr=0):
+    out = set()
+    for one in instance.split(" | "):
+        name, f = parse(one)
+        f = sliced_bucket(name, f, tokens, entry, k, kr) if name != "gemv_hot" else f
+        for vi, view in enumerate(VIEWS[name]):
+            out.add((name, vi, tuple(f[k] for k in view)))
+    return out
+
+
+# widths on both sides of every edge: slice count of the exact layouts (5376 / 4704, 16288 / 15616), of the folded ones (14336 /
+# 14080), window parts (4096, 14336), column parts (16392 = 3 x 5464, 28672 = 2 x 14336), column phases
+SLICED_WIDTHS = [1000, 1024, 4096, 4104, 4704, 4712, 5376, 5384, 8192, 14080, 14088, 14336, 14344, 15616, 15624, 16288, 16296, 16392, 28672]
+SLICED_HEIGHTS = [72, 264, 8200]
+KR_CLASSES = [0, 256, 4, 1024, 4096, 65536]
+
+
+def enumerate_sliced_cells():
+    """every cell the sliced dispatch produces over the grid of requests (a form no public shape reaches is not listed)"""
+    cells = set()
+    for dt in DTYPES:
+        for v in (8, 16):
+            for k, krs in ((65536, KR_CLASSES), (32768, (0, 256)), (16384, (0, 256))):
+                for kr in krs:
+                    for I in SLICED_WIDTHS:
+                        for perm in (False, True):
+                            for mode in ("folded", "exact", "sel"):
+                                for Os in ([(O,) for O in SLICED_HEIGHTS] + [(264, 72), (264, 72, 8200)]):
+                                    if perm and (Os[0] == 8200 or len(Os) == 2):
+                                        continue
+                                    for tokens in range(1, 10):   # (9: the entries take 2 - 8, the query turns it down - nothing to list)
+                                        if tokens > 1 and mode == "sel":
+                                            continue
+                                        inst = sliced_query(I, Os, dt, tokens, mode, v, k, kr, perm)
+                                        if inst:
+                                            cells |= sliced_cells_of(inst, tokens, entry_of(Os, "single", inst), k, kr)
+                                            if len(Os) == 1 and mode != "sel" and entry_of(Os, "single", inst) == "single":
+                                                cells |= sliced_cells_of(inst, tokens, "grouped", k, kr)   # (a group of one launches the same)
+            # rows per wave of the one-token layouts beyond the objects' rule: 2 - 16 and past 16
+            for rpw in (2, 18):
+                for mode in ("folded", "exact"):
+                    inst = sliced_query(1024, (264,), dt, 1, mode, v, rpw=rpw)
+                    cells |= sliced_cells_of(inst, 1, "single")
+    return cells
+
+
+def sliced_table_cells():
+    cells = set()
+    for p in sliced.ROWS:
+        e = p.values[0]
+        ents = ("single", "grouped") if e["entry"] == "both" else (entry_of(e["Os"], e["entry"], e["instance"]),)
+        for ent in ents:
+            cells |= sliced_cells_of(e["instance"], e["tokens"], ent, e["k"], e["kr"])
+    for I, O, kw, dt, exact, slices, parts, inst in rm.SLICED:
+        cells |= sliced_cells_of(inst, 1, entry_of((O,), "single", inst), 65536, kw.get("num_res_centroids", 0))
+    for I, O, kw, dt, exact, tokens, one_pass, wparts, inst in rm.SLICED_TOKENS:
+        cells |= sliced_cells_of(inst, tokens, entry_of((O,), "single", inst))
+    return cells
+
+
+# (kernel, view, cell, reason): enumerated cells of the sliced family the tables leave out
+SLICED_NOT_COVERED = [
+]
+
+
+def test_sliced_tables_reach_every_instance_the_dispatch_produces(untuned):
+    want, have = enumerate_sliced_cells(), sliced_table_cells()
+    named = {(k, v, c) for k, v, c, _ in SLICED_NOT_COVERED}
+    assert all(reason for _, _, _, reason in SLICED_NOT_COVERED)
+    assert named <= want, f"SLICED_NOT_COVERED names cells the dispatch does not produce: {sorted(named - want)}"
+    assert not (named & have), f"SLICED_NOT_COVERED names covered cells: {sorted(named & have)}"
+    missing = want - have - named
+    assert not missing, f"{len(missing)} of {len(want)} instance cells without a row, e.g. {sorted(missing)[:12]}"
+    assert len(named) * 10 <= len(want), f"SLICED_NOT_COVERED holds {len(named)} of {len(want)} cells: more than 10 %"
+    for kernel in SLICED_KERNELS:   # no whole value of any axis is left out
+        for vi, view in enumerate(VIEWS[kernel]):
+            for pos, axis in enumerate(view):
+                w = {c[pos] for k, v, c in want if k == kernel and v == vi}
+                h = {c[pos] for k, v, c in have if k == kernel and v == vi}
+                assert w <= h, f"{kernel}: no row with {axis} in {sorted(w - h)}"
+    # the instantiations counted from the launchers are in the enumeration (a census that lost a kernel would pass vacuously)
+    for dt in DTYPES:
+        for kernel, count in SLICED_INSTANTIATIONS.items():
+            got = {c for k, v, c in want if k == kernel and v == 0 and c[0] == dt}
+            assert len(got) == count, f"{kernel} {dt}: {len(got)} instantiations enumerated, {count} expected: {sorted(got)}"
+
+
+def test_sliced_table_instances_are_what_the_library_answers(untuned):
+    """every sliced row's instance string is the library's answer for fake descriptors and layout structs of the row's shape"""
+    for p in sliced.ROWS:
+        e = p.values[0]
+        assert sliced_query(e["I"], e["Os"], e["dt"], e["tokens"], e["mode"], e["v"], e["k"], e["kr"], bool(e["perm"]), e["rpw"]) == e["instance"], p.id
+    for I, O, kw, dt, exact, slices, parts, inst in rm.SLICED:
+        assert sliced_query(I, (O,), dt, 1, "exact" if exact else "folded", kw.get("vector_len", 8), 65536, kw.get("num_res_centroids", 0),
+                            bool(kw.get("enable_perm"))) == inst, (I, O)
+    for I, O, kw, dt, exact, tokens, one_pass, wparts, inst in rm.SLICED_TOKENS:
+        assert sliced_query(I, (O,), dt, tokens, "exact" if exact else "folded") == inst, (I, O, tokens)
+
+
+def test_sliced_instance_queries_validate_and_need_no_device():
+    lib = B.lib()
+    descs, lay, n, _, _ = fake_call(4096, (264,), "f16", 8, 65536, 0, False, "exact")
+    buf = C.create_string_buffer(512)
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 1, EXACT, buf, 512) == 0 and buf.value.startswith(b"gemv_sliced dt=f16 nsl=8 ")
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 1, EXACT, buf, 8) == B.E_WORKSPACE
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 1, EXACT, None, 512) == B.E_NULL
+    assert lib.vptq_quant_gemv_sliced_instance(descs, None, 1, 1, EXACT, buf, 512) == B.E_NULL
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 2, EXACT, buf, 512) == B.E_TOKENS
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 0, 1, EXACT, buf, 512) == B.E_SHAPE
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 4, 1, EXACT, buf, 512) == B.E_SHAPE
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(descs, lay, 1, 1, EXACT, buf, 512) == B.E_TOKENS
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(descs, lay, 1, 9, EXACT, buf, 512) == B.E_TOKENS
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(descs, lay, 1, 5, EXACT, buf, 8) == B.E_WORKSPACE
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(descs, lay, 1, 5, EXACT, buf, 512) == 0 and buf.value.startswith(b"gemv_sliced_tok dt=f16 ")
+    # 2 tokens over 4096 columns: the one pass of the one-token kernel, in two window parts
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(descs, lay, 1, 2, EXACT, buf, 512) == 0 and b" tok=2 wpt=1 wparts=2 " in buf.value
+    # a folded layout is not an exact one (the slice counts differ at this width only beyond 5376 columns: the flags decide the kernel)
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 1, 0, buf, 512) == 0 and b" ex=0 " in buf.value
+    # the selective call: the pre-pass in front
+    assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 1, SEL, buf, 512) == 0
+    assert buf.value.startswith(b"gemv_hot dt=f16 v=8 | gemv_sliced ") and buf.value.endswith(b"corr=1")

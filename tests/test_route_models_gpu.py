@@ -376,26 +376,47 @@ def _arrivals(sl):
 
 
 SLICED = [
-    # (I, O, kw, dt, exact, slices, parts): folded one- and two-table; EX; EX + RG (16-bit residual side stream); column parts
-    (2048, 1032, dict(bias=True), "f16", False, 8, 1),
-    (4104, 264, dict(LLM, num_res_centroids=65536), "bf16", False, 8, 1),
-    (8192, 512, dict(LLM, bias=True), "f16", True, 16, 1),
-    (4712, 136, dict(LLM, num_res_centroids=256), "bf16", True, 16, 1),
-    (2048, 520, dict(LLM, vector_len=8, num_res_centroids=4096, enable_perm=True, bias=True), "f16", True, 8, 1),
-    (1024, 256, dict(LLM, vector_len=16, num_res_centroids=65536), "bf16", True, 16, 1),
-    (16392, 72, dict(LLM), "f16", True, 16, 3),
-    (28672, 136, dict(LLM, bias=True), "bf16", True, 16, 2),
+    # (I, O, kw, dt, exact, slices, parts, instance): folded one- and two-table; EX; EX + RG (16-bit residual side stream); column parts;
+    # the instance vptq_quant_gemv_sliced_instance must give (every instantiation has its row in tests/test_route_models_sliced_gpu.py)
+    (2048, 1032, dict(bias=True), "f16", False, 8, 1,
+     "gemv_sliced dt=f16 nsl=8 res=0 v=8 two=0 ex=0 rg=0 tok=1 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=8 whole1=0 side=0 perm=0 corr=0"),
+    (4104, 264, dict(LLM, num_res_centroids=65536), "bf16", False, 8, 1,
+     "gemv_sliced dt=bf16 nsl=8 res=0 v=8 two=1 ex=0 rg=0 tok=1 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=16 whole1=0 side=0 perm=0 corr=0"),
+    (8192, 512, dict(LLM, bias=True), "f16", True, 16, 1,
+     "gemv_sliced dt=f16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=1 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=16 whole1=0 side=0 perm=0 corr=0"),
+    (4712, 136, dict(LLM, num_res_centroids=256), "bf16", True, 16, 1,
+     "gemv_sliced dt=bf16 nsl=16 res=1 v=8 two=0 ex=1 rg=0 tok=1 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=16 whole1=0 side=1 perm=0 corr=0"),
+    (2048, 520, dict(LLM, vector_len=8, num_res_centroids=4096, enable_perm=True, bias=True), "f16", True, 8, 1,
+     "gemv_sliced dt=f16 nsl=8 res=0 v=8 two=0 ex=1 rg=1 tok=1 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=8 whole1=0 side=2 perm=1 corr=0"),
+    (1024, 256, dict(LLM, vector_len=16, num_res_centroids=65536), "bf16", True, 16, 1,
+     "gemv_sliced dt=bf16 nsl=16 res=0 v=16 two=0 ex=1 rg=1 tok=1 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=16 whole1=0 side=2 perm=0 corr=0"),
+    (16392, 72, dict(LLM), "f16", True, 16, 3,
+     "gemv_sliced dt=f16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=1 wpt=0 wparts=1 parts=3 n=1 rpw=1 arrivals=48 whole1=0 side=0 perm=0 corr=0"),
+    (28672, 136, dict(LLM, bias=True), "bf16", True, 16, 2,
+     "gemv_sliced dt=bf16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=1 wpt=0 wparts=1 parts=2 n=1 rpw=1 arrivals=32 whole1=0 side=0 perm=0 corr=0"),
 ]
 
 
-@pytest.mark.parametrize("I,O,kw,dt,exact,slices,parts", SLICED)
-def test_sliced_one_token_vs_its_model(I, O, kw, dt, exact, slices, parts, dev):
+def _sliced_instance(sl, tokens):
+    """the library's answer for this object's own descriptors and layout structs (a layer in column parts: the grouped entries)"""
+    from vptq_amd import _backend as B
+    from test_route_models_sliced_gpu import sliced_instance_of, PARTS
+    if sl.parts > 1:
+        return sliced_instance_of(sl._part_descs, sl._lay_ref, sl.parts, tokens, sl._flags | PARTS)
+    return sliced_instance_of((B.LayerDesc * 1)(sl.desc), sl._lay_ref, 1, tokens, sl._flags)
+
+
+# (ids: the ones these cases had before they carried their instance string)
+@pytest.mark.parametrize("I,O,kw,dt,exact,slices,parts,instance", SLICED,
+                         ids=[f"{r[0]}-{r[1]}-kw{i}-{r[3]}-{r[4]}-{r[5]}-{r[6]}" for i, r in enumerate(SLICED)])
+def test_sliced_one_token_vs_its_model(I, O, kw, dt, exact, slices, parts, instance, dev):
     kw = dict(kw)
     dist = kw.pop("dist", "ref-test")
     kw.setdefault("num_res_centroids", 0)
     L = vo.make_layer(I, O, dist=dist, seed=I + O + 1, dtype=dt, num_centroids=65536, **kw)
     m, sl = _sliced(L, dev, exact=exact)
     assert (sl.exact, sl.slices, sl.parts) == (exact, slices, parts)
+    assert _sliced_instance(sl, 1) == instance
     P = am.pieces(L)
     extra = am.sliced_extra_abs(dt, _arrivals(sl))
     for kind in (("dense",) if exact else ("planted",)):
@@ -408,21 +429,32 @@ def test_sliced_one_token_vs_its_model(I, O, kw, dt, exact, slices, parts, dev):
 SLICED_TOKENS = [
     # (I, O, kw, dt, exact, tokens, one pass, window parts): the column-phase kernel (folded / EX, 2 - 8 tokens); one pass of the
     # one-token kernel for 2 / 3 tokens (whole columns; window parts); column parts in one pass
-    (2048, 1032, dict(bias=True), "f16", False, 2, False, 0),
-    (4104, 264, dict(LLM), "bf16", False, 4, False, 0),
-    (2048, 520, dict(LLM, bias=True), "f16", False, 8, False, 0),
-    (4104, 264, dict(LLM, bias=True), "f16", True, 5, False, 0),
-    (2048, 1032, dict(LLM), "bf16", True, 8, False, 0),
-    (8192, 512, dict(LLM, bias=True), "f16", True, 2, True, 1),
-    (8192, 264, dict(LLM), "bf16", True, 3, True, 1),
-    (4096, 256, dict(LLM), "f16", True, 2, True, 2),
-    (14336, 72, dict(LLM), "bf16", True, 3, True, 2),
-    (28672, 136, dict(LLM, bias=True), "f16", True, 2, True, 2),
+    (2048, 1032, dict(bias=True), "f16", False, 2, False, 0,
+     "gemv_sliced_tok dt=f16 nsl=8 res=0 v=8 two=0 tok=2 ex=0 phases=1 rpw=1 regsums=0 n=1 whole1=0 perm=0"),
+    (4104, 264, dict(LLM), "bf16", False, 4, False, 0,
+     "gemv_sliced_tok dt=bf16 nsl=8 res=0 v=8 two=0 tok=4 ex=0 phases=2 rpw=1 regsums=1 n=1 whole1=0 perm=0"),
+    (2048, 520, dict(LLM, bias=True), "f16", False, 8, False, 0,
+     "gemv_sliced_tok dt=f16 nsl=8 res=0 v=8 two=0 tok=8 ex=0 phases=2 rpw=1 regsums=1 n=1 whole1=0 perm=0"),
+    (4104, 264, dict(LLM, bias=True), "f16", True, 5, False, 0,
+     "gemv_sliced_tok dt=f16 nsl=8 res=0 v=8 two=0 tok=8 ex=1 phases=4 rpw=1 regsums=1 n=1 whole1=0 perm=0"),
+    (2048, 1032, dict(LLM), "bf16", True, 8, False, 0,
+     "gemv_sliced_tok dt=bf16 nsl=8 res=0 v=8 two=0 tok=8 ex=1 phases=2 rpw=1 regsums=1 n=1 whole1=0 perm=0"),
+    (8192, 512, dict(LLM, bias=True), "f16", True, 2, True, 1,
+     "gemv_sliced dt=f16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=2 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=16 whole1=0 side=0 perm=0 corr=0"),
+    (8192, 264, dict(LLM), "bf16", True, 3, True, 1,
+     "gemv_sliced dt=bf16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=3 wpt=0 wparts=1 parts=1 n=1 rpw=1 arrivals=16 whole1=0 side=0 perm=0 corr=0"),
+    (4096, 256, dict(LLM), "f16", True, 2, True, 2,
+     "gemv_sliced dt=f16 nsl=8 res=0 v=8 two=0 ex=1 rg=0 tok=2 wpt=1 wparts=2 parts=1 n=1 rpw=2 arrivals=16 whole1=0 side=0 perm=0 corr=0"),
+    (14336, 72, dict(LLM), "bf16", True, 3, True, 2,
+     "gemv_sliced dt=bf16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=3 wpt=1 wparts=2 parts=1 n=1 rpw=2 arrivals=32 whole1=0 side=0 perm=0 corr=0"),
+    (28672, 136, dict(LLM, bias=True), "f16", True, 2, True, 2,
+     "gemv_sliced dt=f16 nsl=16 res=0 v=8 two=0 ex=1 rg=0 tok=2 wpt=1 wparts=2 parts=2 n=1 rpw=2 arrivals=64 whole1=0 side=0 perm=0 corr=0"),
 ]
 
 
-@pytest.mark.parametrize("I,O,kw,dt,exact,tokens,one_pass,wparts", SLICED_TOKENS)
-def test_sliced_tokens_vs_its_model(I, O, kw, dt, exact, tokens, one_pass, wparts, dev):
+@pytest.mark.parametrize("I,O,kw,dt,exact,tokens,one_pass,wparts,instance", SLICED_TOKENS,
+                         ids=[f"{r[0]}-{r[1]}-kw{i}-{r[3]}-{r[4]}-{r[5]}-{r[6]}-{r[7]}" for i, r in enumerate(SLICED_TOKENS)])
+def test_sliced_tokens_vs_its_model(I, O, kw, dt, exact, tokens, one_pass, wparts, instance, dev):
     kw = dict(kw)
     dist = kw.pop("dist", "ref-test")
     L = vo.make_layer(I, O, dist=dist, seed=I + O + tokens, dtype=dt, num_centroids=65536, num_res_centroids=0, **kw)
@@ -431,6 +463,7 @@ def test_sliced_tokens_vs_its_model(I, O, kw, dt, exact, tokens, one_pass, wpart
     assert sl.tokens_one_pass(tokens) == one_pass
     if one_pass:
         assert sl.tokens_window_parts(tokens) == wparts
+    assert _sliced_instance(sl, tokens) == instance
     x, hot = (_dense if exact else _planted)(I, tokens, dt, I + tokens)
     xt = bits_to_tensor(x, dt, dev).reshape(1, tokens, I)
     y16, y32 = sl.forward_tokens(xt), sl.forward_tokens(xt, flags=F32)
@@ -524,11 +557,11 @@ def _reached():
             add("gemv_k256c_kernel", "dependent", arith, dt)
     for I, O, dt, tokens, arith, kw in FUSED:
         add("vptq_quant_gemm", arith, dt)
-    for I, O, kw, dt, exact, slices, parts in SLICED:
+    for I, O, kw, dt, exact, slices, parts, _ in SLICED:
         kr = kw.get("num_res_centroids", 0)
         add("gemv_sliced_kernel", "folded" if not exact else "EX+RG" if kr and not (kw.get("vector_len", 8) == 8 and kr == 256) else "EX",
             dt, 1, "column parts" if parts > 1 else "whole")
-    for I, O, kw, dt, exact, tokens, one_pass, wparts in SLICED_TOKENS:
+    for I, O, kw, dt, exact, tokens, one_pass, wparts, _ in SLICED_TOKENS:
         if one_pass:
             add("gemv_sliced_kernel", "EX", dt, tokens, f"one pass, {wparts} window part(s)")
         else:

@@ -1037,6 +1037,74 @@ int vptq_quant_gemv_sliced_tokens_grouped(const VptqLayerDesc* descs, const Vptq
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced_tok grouped launch");
 }
 
+// ---- which instantiation a sliced call would launch (vptq_quant_gemv_sliced_instance / _tokens_instance): the entries' own checks of
+// the descriptors, layouts and flags in their order (x, y and the workspaces are not there to check), then the text of the very
+// decide functions the launches run (gemv_sliced.hip:sl_decide, gemv_sliced_tok.hip:st_decide, gemv_hot_decide)
+static int sliced_instance_rc(int rc, size_t bytes) {
+  if (rc == -2) return fail(VPTQ_E_WORKSPACE, "instance: buffer of %zu bytes too small", bytes);
+  return rc ? fail(VPTQ_E_UNSUPPORTED, "instance: no sliced launch serves this call") : VPTQ_OK;
+}
+int vptq_quant_gemv_sliced_instance(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens, int flags, char* buf,
+                                    size_t bytes) {
+  if (!descs || !layouts || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / layouts / buf is NULL");
+  buf[0] = 0;
+  if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
+  if (tokens != 1) return fail(VPTQ_E_TOKENS, "tokens %d: the one-token entries (several tokens: vptq_quant_gemv_sliced_tokens_instance)", tokens);
+  for (int i = 0; i < n; ++i)
+    if (int rc = validate_layer(&descs[i])) return rc;
+  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_FORCE_GENERIC: use vptq_quant_gemv");
+  const bool single = n == 1 && !(flags & VPTQ_GEMV_COLUMN_PARTS);   // vptq_quant_gemv_sliced
+  flags = single ? drop_redundant_selective(flags) : selective_as_exact(flags);
+  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0, sel = (flags & VPTQ_GEMV_SELECTIVE) != 0;
+  if (sel && !vptq::gemv_hot_eligible(descs[0])) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_SELECTIVE over a sliced layout: not served for this layer");
+  if ((flags & VPTQ_GEMV_COLUMN_PARTS) && !exact) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
+  if (!vptq::gemv_sliced_groupable(descs, n, exact))
+    return fail(VPTQ_E_UNSUPPORTED, "a sliced launch takes layers of ONE format, dtype and input width that vptq_sliced_layout_supported_for() accepts");
+  for (int i = 0; i < n; ++i) {
+    const vptq::SlicedLayoutSet S = vptq::sl_piece_set(descs[i], exact);
+    int which = 0;
+    if (const unsigned faults = vptq::sl_check_layouts(descs[i], S, layouts + (size_t)i * S.tables, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole,
+                                                       layouts[0].rows_per_wave, &which))
+      return layout_fail(faults, true, "vptq_quant_gemv_sliced_instance", i, which, S);
+  }
+  Text t = {buf, bytes, 0, true};
+  char one[384];
+  if (sel) {
+    if (const int rc = vptq::gemv_hot_instance(descs[0], one, sizeof(one))) return sliced_instance_rc(rc, bytes);
+    t.add("%s | ", one);
+  }
+  if (const int rc = vptq::gemv_sliced_instance(descs, layouts, n, 1, flags & ~VPTQ_GEMV_SELECTIVE, sel, one, sizeof(one)))
+    return sliced_instance_rc(rc, bytes);
+  t.add("%s", one);
+  return text_done(t);
+}
+
+int vptq_quant_gemv_sliced_tokens_instance(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens, int flags,
+                                           char* buf, size_t bytes) {
+  if (!descs || !layouts || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / layouts / buf is NULL");
+  buf[0] = 0;
+  if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
+  if (tokens < 2 || tokens > 8) return fail(VPTQ_E_TOKENS, "tokens %d outside [2, 8]", tokens);
+  flags = selective_as_exact(flags);
+  for (int i = 0; i < n; ++i)
+    if (int rc = validate_layer(&descs[i])) return rc;
+  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
+  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
+  if (flags & VPTQ_GEMV_COLUMN_PARTS) {
+    if (!exact) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
+    for (int i = 0; i < n; ++i)
+      if (!vptq::gemv_sliced_tok_one_pass_parts(descs[i], tokens, true)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
+  }
+  if (!vptq::gemv_sliced_groupable(descs, n, exact) || !vptq::gemv_sliced_tok_groupable(descs, layouts, n, tokens, exact))
+    return fail(VPTQ_E_UNSUPPORTED, "sliced layouts with column windows (wstart), 2 - 8 tokens, layers of ONE format, dtype and input width whose "
+                                    "activations fit the LDS beside the slice");
+  char one[384];
+  if (const int rc = vptq::gemv_sliced_tok_instance(descs, layouts, n, tokens, flags, one, sizeof(one))) return sliced_instance_rc(rc, bytes);
+  Text t = {buf, bytes, 0, true};
+  t.add("%s", one);
+  return text_done(t);
+}
+
 size_t vptq_quant_gemm_workspace_bytes(const VptqLayerDesc* d, int tokens) {
   if (validate_layer(d) != VPTQ_OK || tokens < 1) return 0;
   return vptq::gemm_fused_workspace_bytes(*d, tokens);

@@ -12,6 +12,7 @@
 //     hold what they touch - and stores sum w x per output (float32, zeros without a hot block) as `corr`, which the folded launch
 //     adds before its one rounding (SlicedParams::corr).
 // Replaces, for those columns, the reference's global gathers of both entries (csrc/kernels/quant_gemv.cuh:114-125).
+#include <cstdio>
 #include <type_traits>
 
 #include "common.h"
@@ -241,9 +242,26 @@ static float gh_kappa() {
   if (milli < 0) { const char* e = tune_env("VPTQ_SELECTIVE_KAPPA"); const double v = e ? atof(e) : 0.0; milli = v > 0.0 ? (int)(v * 1000.0) : 6000; }
   return (float)milli.load() * 1e-3f;
 }
+// decide, then launch: which instantiation serves the layer (gemv_hot_instance prints it)
+HotDecision gemv_hot_decide(const VptqLayerDesc& d) {
+  return HotDecision{gemv_hot_eligible(d), d.dtype == VPTQ_DTYPE_F16, d.vector_len};
+}
+int gemv_hot_instance(const VptqLayerDesc& d, char* buf, size_t bytes) {
+  const HotDecision D = gemv_hot_decide(d);
+  if (!D.ok) return -1;
+  const int w = snprintf(buf, bytes, "gemv_hot dt=%s v=%d", D.f16 ? "f16" : "bf16", D.v);
+  return w < 0 || (size_t)w >= bytes ? -2 : 0;
+}
+template <typename DT, int V>
+static hipError_t launch_hot(const HotDecision& D, const HotParams& P, int grid, hipStream_t st) {
+  if (!D.ok || D.f16 != std::is_same<DT, F16>::value || D.v != V) return hipErrorInvalidValue;   // the instantiation the decision names
+  hipLaunchKernelGGL((gemv_hot_kernel<DT, V>), dim3(grid), dim3(256), 0, st, P);
+  return hipGetLastError();
+}
 // extra = gemv_hot_bytes(d) bytes, 256-byte aligned; returns where x_masked and corr are
 hipError_t launch_gemv_hot(const VptqLayerDesc& d, const void* x, void* extra, const void** x_masked, const float** corr, hipStream_t st) {
-  if (!gemv_hot_eligible(d) || !extra || (((uintptr_t)extra) & 255) != 0 || (((uintptr_t)x) & 15) != 0) return hipErrorInvalidValue;
+  const HotDecision D = gemv_hot_decide(d);
+  if (!D.ok || !extra || (((uintptr_t)extra) & 255) != 0 || (((uintptr_t)x) & 15) != 0) return hipErrorInvalidValue;
   HotParams P;
   P.idx = (const uint32_t*)d.indices;
   P.cent = (const uint32_t*)d.centroids;
@@ -260,17 +278,10 @@ hipError_t launch_gemv_hot(const VptqLayerDesc& d, const void* x, void* extra, c
   P.kappa = gh_kappa();
   if ((((uintptr_t)P.cent | (uintptr_t)P.rcent) & 15) != 0) return hipErrorInvalidValue;
   const int grid = (d.num_indices + kGHRows - 1) / kGHRows;
-  const bool f16 = d.dtype == VPTQ_DTYPE_F16;
-  if (d.vector_len == 8) {
-    if (f16) hipLaunchKernelGGL((gemv_hot_kernel<F16, 8>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((gemv_hot_kernel<BF16, 8>), dim3(grid), dim3(256), 0, st, P);
-  } else {
-    if (f16) hipLaunchKernelGGL((gemv_hot_kernel<F16, 16>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((gemv_hot_kernel<BF16, 16>), dim3(grid), dim3(256), 0, st, P);
-  }
   *x_masked = P.xm;
   *corr = P.corr;
-  return hipGetLastError();
+  if (D.v == 8) return D.f16 ? launch_hot<F16, 8>(D, P, grid, st) : launch_hot<BF16, 8>(D, P, grid, st);
+  return D.f16 ? launch_hot<F16, 16>(D, P, grid, st) : launch_hot<BF16, 16>(D, P, grid, st);
 }
 
 }  // namespace vptq

@@ -31,6 +31,7 @@
 //                         c f16(s x) and r f16(s x) from different workgroups)
 //   reference roundings (VPTQ_GEMV_EXACT, template EX): w = f16(f16(f16(c + r) * s) + b) per weight, y = sum w x + bias -
 //                         the product default since round 5; one table only (none or the 256-entry residual codebook)
+#include <cstdio>
 #include <cstring>
 
 #include "sliced.h"
@@ -811,7 +812,11 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
 // ---- launchers (both parts of the build: the file is compiled twice, VPTQ_SL_PART = 1: the one-token instantiations + the host
 // side, 2: the 2 / 3-token instantiations of the reference's roundings)
 template <typename DT, int NSL, bool RES, int V, bool TWO, bool EX = false, bool RG = false, int TOK = 1, bool WPT = false>
-static hipError_t launch_sl(const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+static hipError_t launch_sl(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  // this instantiation is the one the decision names (sl_decide)
+  if (D.f16 != std::is_same<DT, F16>::value || D.nsl != NSL || D.res != RES || D.v != V || D.two != TWO || D.ex != EX || D.rg != RG ||
+      D.tok != TOK || D.wpt != WPT)
+    return hipErrorInvalidValue;
   auto kern = gemv_sliced_kernel<DT, NSL, RES, V, TWO, EX, RG, TOK, WPT>;
   static std::atomic<bool> attr_set[64];
   int dev = 0;
@@ -824,38 +829,42 @@ static hipError_t launch_sl(const SlicedGroupParams& P, uint32_t lds, hipStream_
   hipLaunchKernelGGL(kern, dim3(P.start[P.n]), dim3(kSLThreads), lds, st, P);
   return hipGetLastError();
 }
-hipError_t launch_sl_tokens(int dtype, const SlicedGroupParams& P, int v, int nsl, bool res, bool rg, int tokens, uint32_t lds, hipStream_t st);
-hipError_t launch_sl_tokens_wpt(int dtype, const SlicedGroupParams& P, int nsl, bool res, int tokens, uint32_t lds, hipStream_t st);
+hipError_t launch_sl_tokens(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);
+hipError_t launch_sl_tokens_wpt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);
 #if !defined(VPTQ_SL_PART) || VPTQ_SL_PART == 3
 // (window parts: v = 8, one table)
 template <typename DT, int TOK>
-static hipError_t launch_sl_tok_wpt(const SlicedGroupParams& P, int nsl, bool res, uint32_t lds, hipStream_t st) {
-  if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false, true, false, TOK, true>(P, lds, st) : launch_sl<DT, 8, false, 8, false, true, false, TOK, true>(P, lds, st);
-  return res ? launch_sl<DT, 16, true, 8, false, true, false, TOK, true>(P, lds, st) : launch_sl<DT, 16, false, 8, false, true, false, TOK, true>(P, lds, st);
+static hipError_t launch_sl_tok_wpt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  const int nsl = D.nsl;
+  const bool res = D.res;
+  if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false, true, false, TOK, true>(D, P, lds, st) : launch_sl<DT, 8, false, 8, false, true, false, TOK, true>(D, P, lds, st);
+  return res ? launch_sl<DT, 16, true, 8, false, true, false, TOK, true>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false, true, false, TOK, true>(D, P, lds, st);
 }
-hipError_t launch_sl_tokens_wpt(int dtype, const SlicedGroupParams& P, int nsl, bool res, int tokens, uint32_t lds, hipStream_t st) {
-  if (tokens == 2) return dtype == VPTQ_DTYPE_F16 ? launch_sl_tok_wpt<F16, 2>(P, nsl, res, lds, st) : launch_sl_tok_wpt<BF16, 2>(P, nsl, res, lds, st);
-  if (tokens == 3) return dtype == VPTQ_DTYPE_F16 ? launch_sl_tok_wpt<F16, 3>(P, nsl, res, lds, st) : launch_sl_tok_wpt<BF16, 3>(P, nsl, res, lds, st);
+hipError_t launch_sl_tokens_wpt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  if (D.tok == 2) return D.f16 ? launch_sl_tok_wpt<F16, 2>(D, P, lds, st) : launch_sl_tok_wpt<BF16, 2>(D, P, lds, st);
+  if (D.tok == 3) return D.f16 ? launch_sl_tok_wpt<F16, 3>(D, P, lds, st) : launch_sl_tok_wpt<BF16, 3>(D, P, lds, st);
   return hipErrorInvalidValue;
 }
 #endif
 #if !defined(VPTQ_SL_PART) || VPTQ_SL_PART == 2
 template <typename DT, int TOK>
-static hipError_t launch_sl_tok(const SlicedGroupParams& P, int v, int nsl, bool res, bool rg, uint32_t lds, hipStream_t st) {
+static hipError_t launch_sl_tok(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  const int v = D.v, nsl = D.nsl;
+  const bool res = D.res, rg = D.rg;
   if (rg) {   // (v = 8 only: the gathered residual entries of v = 16 on top of two tokens' sums spill)
     if (v != 8) return hipErrorInvalidValue;
-    return nsl == 8 ? launch_sl<DT, 8, false, 8, false, true, true, TOK>(P, lds, st) : launch_sl<DT, 16, false, 8, false, true, true, TOK>(P, lds, st);
+    return nsl == 8 ? launch_sl<DT, 8, false, 8, false, true, true, TOK>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false, true, true, TOK>(D, P, lds, st);
   }
   if (v == 16) {   // (3 tokens of 16 outputs: 48 sums + 12 returned words per lane spill - 2 tokens only)
-    if constexpr (TOK == 2) return nsl == 16 ? launch_sl<DT, 16, false, 16, false, true, false, TOK>(P, lds, st) : launch_sl<DT, 32, false, 16, false, true, false, TOK>(P, lds, st);
+    if constexpr (TOK == 2) return nsl == 16 ? launch_sl<DT, 16, false, 16, false, true, false, TOK>(D, P, lds, st) : launch_sl<DT, 32, false, 16, false, true, false, TOK>(D, P, lds, st);
     else return hipErrorInvalidValue;
   }
-  if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false, true, false, TOK>(P, lds, st) : launch_sl<DT, 8, false, 8, false, true, false, TOK>(P, lds, st);
-  return res ? launch_sl<DT, 16, true, 8, false, true, false, TOK>(P, lds, st) : launch_sl<DT, 16, false, 8, false, true, false, TOK>(P, lds, st);
+  if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false, true, false, TOK>(D, P, lds, st) : launch_sl<DT, 8, false, 8, false, true, false, TOK>(D, P, lds, st);
+  return res ? launch_sl<DT, 16, true, 8, false, true, false, TOK>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false, true, false, TOK>(D, P, lds, st);
 }
-hipError_t launch_sl_tokens(int dtype, const SlicedGroupParams& P, int v, int nsl, bool res, bool rg, int tokens, uint32_t lds, hipStream_t st) {
-  if (tokens == 2) return dtype == VPTQ_DTYPE_F16 ? launch_sl_tok<F16, 2>(P, v, nsl, res, rg, lds, st) : launch_sl_tok<BF16, 2>(P, v, nsl, res, rg, lds, st);
-  if (tokens == 3) return dtype == VPTQ_DTYPE_F16 ? launch_sl_tok<F16, 3>(P, v, nsl, res, rg, lds, st) : launch_sl_tok<BF16, 3>(P, v, nsl, res, rg, lds, st);
+hipError_t launch_sl_tokens(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  if (D.tok == 2) return D.f16 ? launch_sl_tok<F16, 2>(D, P, lds, st) : launch_sl_tok<BF16, 2>(D, P, lds, st);
+  if (D.tok == 3) return D.f16 ? launch_sl_tok<F16, 3>(D, P, lds, st) : launch_sl_tok<BF16, 3>(D, P, lds, st);
   return hipErrorInvalidValue;
 }
 #endif
@@ -959,23 +968,25 @@ size_t gemv_sliced_workspace_bytes(const VptqLayerDesc& d) {
 }
 
 template <typename DT>
-static hipError_t launch_sl_dt(const SlicedGroupParams& P, int v, int nsl, bool res, bool two, bool exact, uint32_t lds, hipStream_t st) {
+static hipError_t launch_sl_dt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  const int v = D.v, nsl = D.nsl;
+  const bool res = D.res, two = D.two || D.rg, exact = D.ex;   // (exact && two = RG)
   if (exact) {   // the reference's roundings: one layout; another residual codebook than the 256-entry one comes from L2 (RG)
     if (two) {
-      if (v == 16) return nsl == 16 ? launch_sl<DT, 16, false, 16, false, true, true>(P, lds, st) : launch_sl<DT, 32, false, 16, false, true, true>(P, lds, st);
-      return nsl == 8 ? launch_sl<DT, 8, false, 8, false, true, true>(P, lds, st) : launch_sl<DT, 16, false, 8, false, true, true>(P, lds, st);
+      if (v == 16) return nsl == 16 ? launch_sl<DT, 16, false, 16, false, true, true>(D, P, lds, st) : launch_sl<DT, 32, false, 16, false, true, true>(D, P, lds, st);
+      return nsl == 8 ? launch_sl<DT, 8, false, 8, false, true, true>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false, true, true>(D, P, lds, st);
     }
-    if (v == 16) return nsl == 16 ? launch_sl<DT, 16, false, 16, false, true>(P, lds, st) : launch_sl<DT, 32, false, 16, false, true>(P, lds, st);
-    if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false, true>(P, lds, st) : launch_sl<DT, 8, false, 8, false, true>(P, lds, st);
-    return res ? launch_sl<DT, 16, true, 8, false, true>(P, lds, st) : launch_sl<DT, 16, false, 8, false, true>(P, lds, st);
+    if (v == 16) return nsl == 16 ? launch_sl<DT, 16, false, 16, false, true>(D, P, lds, st) : launch_sl<DT, 32, false, 16, false, true>(D, P, lds, st);
+    if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false, true>(D, P, lds, st) : launch_sl<DT, 8, false, 8, false, true>(D, P, lds, st);
+    return res ? launch_sl<DT, 16, true, 8, false, true>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false, true>(D, P, lds, st);
   }
   if (v == 16) {
-    if (two) return nsl == 16 ? launch_sl<DT, 16, false, 16, true>(P, lds, st) : launch_sl<DT, 32, false, 16, true>(P, lds, st);
-    return nsl == 16 ? launch_sl<DT, 16, false, 16, false>(P, lds, st) : launch_sl<DT, 32, false, 16, false>(P, lds, st);
+    if (two) return nsl == 16 ? launch_sl<DT, 16, false, 16, true>(D, P, lds, st) : launch_sl<DT, 32, false, 16, true>(D, P, lds, st);
+    return nsl == 16 ? launch_sl<DT, 16, false, 16, false>(D, P, lds, st) : launch_sl<DT, 32, false, 16, false>(D, P, lds, st);
   }
-  if (two) return nsl == 8 ? launch_sl<DT, 8, false, 8, true>(P, lds, st) : launch_sl<DT, 16, false, 8, true>(P, lds, st);
-  if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false>(P, lds, st) : launch_sl<DT, 8, false, 8, false>(P, lds, st);
-  return res ? launch_sl<DT, 16, true, 8, false>(P, lds, st) : launch_sl<DT, 16, false, 8, false>(P, lds, st);
+  if (two) return nsl == 8 ? launch_sl<DT, 8, false, 8, true>(D, P, lds, st) : launch_sl<DT, 16, false, 8, true>(D, P, lds, st);
+  if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false>(D, P, lds, st) : launch_sl<DT, 8, false, 8, false>(D, P, lds, st);
+  return res ? launch_sl<DT, 16, true, 8, false>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false>(D, P, lds, st);
 }
 
 SlicedLayoutSet sl_piece_set(const VptqLayerDesc& d, bool exact) {
@@ -1169,18 +1180,22 @@ size_t gemv_sliced_exact_tokens_workspace_bytes(const VptqLayerDesc& d, int toke
 // order tensors (scale, bias, permutation) advanced to the part's first column, a layout per part built from those columns of
 // the index matrix; x is the WHOLE activation (part i reads it from column i G / n on, or through its slice of the permutation),
 // y and the accumulator words are shared: an output is complete after n x slices arrivals.
-hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
-                                    int flags, void* const* ws, hipStream_t st, int tokens, const float* corr) {
+// ---- decide, then launch (as gemv_k256.hip): sl_decide says what one call is - the parameter blocks, the LDS, the instantiation's
+// template arguments and the launch shape; launch_gemv_sliced_group launches exactly that and gemv_sliced_instance prints it, so the
+// two cannot disagree.  Nothing is dereferenced: the query passes placeholder x / y / workspace pointers.
+static hipError_t sl_decide(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y, int flags,
+                            void* const* ws, int tokens, const float* corr, SlicedGroupParams& GP, uint32_t& lds, SlicedDecision& D) {
   const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
   const bool parts = (flags & VPTQ_GEMV_COLUMN_PARTS) != 0;
   if (!gemv_sliced_groupable(d, n, exact) || (tokens != 1 && !exact)) return hipErrorInvalidValue;
   // (the folded form stages 32768 columns in one piece: no parts needed)
   if (parts && (!exact || !sl_parts_share(d, y, ws, n))) return hipErrorInvalidValue;
-  SlicedGroupParams GP = {};
+  GP = SlicedGroupParams{};
   GP.n = n;
-  uint32_t lds = 0;
+  lds = 0;
   const SlicedLayoutSet S0 = sl_piece_set(d[0], exact);   // (one format: one table and slice count for every member)
   const int tables = S0.tables, nsl = S0.slices, nslt = nsl * tables;
+  bool perm = false;
   for (int i = 0; i < n; ++i) {
     uint32_t l = 0;
     // (a part without a permutation reads its own columns of x; with one, its slice of `perm` indexes the whole activation)
@@ -1192,15 +1207,48 @@ hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayo
     lds = l > lds ? l : lds;
     GP.start[i + 1] = GP.start[i] + nslt * GP.p[i].wparts * GP.p[i].n_rowblocks;
     if (GP.p[i].wparts != GP.p[0].wparts) return hipErrorInvalidValue;   // (one input width: one answer)
+    perm = perm || d[i].perm != nullptr;
   }
   for (int i = n; i < kSLMaxGroup; ++i) GP.start[i + 1] = GP.start[n];
   GP.arrivals = nslt * (parts ? n : 1) * GP.p[0].wparts;
   if (GP.arrivals > 127) return hipErrorInvalidValue;   // (7 bits of the accumulator word count them)
-  if (tokens != 1 && GP.p[0].wparts > 1) return launch_sl_tokens_wpt(d[0].dtype, GP, nsl, sl_res256(d[0]), tokens, lds, st);
-  if (tokens != 1) return launch_sl_tokens(d[0].dtype, GP, d[0].vector_len, nsl, sl_res256(d[0]), sl_two(d[0]), tokens, lds, st);
-  return d[0].dtype == VPTQ_DTYPE_F16
-             ? launch_sl_dt<F16>(GP, d[0].vector_len, nsl, sl_res256(d[0]), sl_two(d[0]), exact, lds, st)
-             : launch_sl_dt<BF16>(GP, d[0].vector_len, nsl, sl_res256(d[0]), sl_two(d[0]), exact, lds, st);   // (exact && two = RG)
+  D = SlicedDecision{};
+  D.f16 = d[0].dtype == VPTQ_DTYPE_F16;
+  D.nsl = nsl; D.v = d[0].vector_len; D.tok = tokens;
+  D.res = sl_res256(d[0]); D.two = !exact && sl_two(d[0]); D.ex = exact; D.rg = exact && sl_two(d[0]);
+  D.wpt = tokens != 1 && GP.p[0].wparts > 1;
+  D.wparts = GP.p[0].wparts; D.parts = parts ? n : 1; D.n = parts ? 1 : n;
+  D.rpw = GP.p[0].rows_per_wave; D.arrivals = GP.arrivals;
+  D.whole1 = tables == 2 ? L[1].whole_table : 0; D.side = S0.side_bytes;
+  D.perm = perm; D.corr = GP.p[0].corr != nullptr;
+  return hipSuccess;
+}
+hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
+                                    int flags, void* const* ws, hipStream_t st, int tokens, const float* corr) {
+  SlicedGroupParams GP;
+  SlicedDecision D;
+  uint32_t lds = 0;
+  if (const hipError_t e = sl_decide(d, L, n, x, y, flags, ws, tokens, corr, GP, lds, D); e != hipSuccess) return e;
+  if (D.wpt) return launch_sl_tokens_wpt(D, GP, lds, st);
+  if (D.tok != 1) return launch_sl_tokens(D, GP, lds, st);
+  return D.f16 ? launch_sl_dt<F16>(D, GP, lds, st) : launch_sl_dt<BF16>(D, GP, lds, st);
+}
+// the instantiation launch_gemv_sliced_group would launch for (d, L, n, tokens, flags), as text; corr: with the hot blocks' products of
+// the selective pre-pass.  0, -1: no launch, -2: buffer too small
+int gemv_sliced_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, int flags, bool corr, char* buf, size_t bytes) {
+  if (n < 1 || n > kSLMaxGroup) return -1;
+  // placeholders: aligned, never dereferenced (column parts share one y and one workspace, as the call requires)
+  void* const some = (void*)(uintptr_t)4096;
+  void* ys[kSLMaxGroup] = {some, some, some};
+  void* wss[kSLMaxGroup] = {some, some, some};
+  SlicedGroupParams GP;
+  SlicedDecision D;
+  uint32_t lds = 0;
+  if (sl_decide(d, L, n, some, ys, flags, wss, tokens, corr ? (const float*)some : nullptr, GP, lds, D) != hipSuccess) return -1;
+  const int w = snprintf(buf, bytes, "gemv_sliced dt=%s nsl=%d res=%d v=%d two=%d ex=%d rg=%d tok=%d wpt=%d wparts=%d parts=%d n=%d rpw=%d "
+                         "arrivals=%d whole1=%d side=%d perm=%d corr=%d", D.f16 ? "f16" : "bf16", D.nsl, (int)D.res, D.v, (int)D.two, (int)D.ex,
+                         (int)D.rg, D.tok, (int)D.wpt, D.wparts, D.parts, D.n, D.rpw, D.arrivals, D.whole1, D.side, (int)D.perm, (int)D.corr);
+  return w < 0 || (size_t)w >= bytes ? -2 : 0;
 }
 hipError_t launch_gemv_sliced(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int flags,
                               void* ws, hipStream_t st, const float* corr) {

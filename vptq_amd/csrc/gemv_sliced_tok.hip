@@ -24,6 +24,8 @@
 // (it then waits for vmcnt(0) in every step - the activations of a phase are loaded by ONE asm statement with its own wait,
 // a layer's permutation is applied by a pre-pass), a load that is issued on some paths only (the waits then shrink down the
 // unrolled round), 64-bit booleans and index -> address arithmetic in the scalar bookkeeping.
+#include <cstdio>
+
 #include "sliced.h"
 
 namespace vptq {
@@ -769,7 +771,10 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
 // side, 2: the 8-slot instantiations, 3 / 4: 4 / 8 slots with the reference's roundings - minutes of compile time as one
 // translation unit)
 template <typename DT, int NSL, bool RES, int V, bool TWO, int TOK, bool EX = false>
-static hipError_t launch_st(const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+static hipError_t launch_st(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  // this instantiation is the one the decision names (st_decide)
+  if (D.f16 != std::is_same<DT, F16>::value || D.nsl != NSL || D.res != RES || D.v != V || D.two != TWO || D.tok != TOK || D.ex != EX)
+    return hipErrorInvalidValue;
   auto kern = gemv_sliced_tok_kernel<DT, NSL, RES, V, TWO, TOK, EX>;
   static std::atomic<bool> attr_set[64];
   int dev = 0;
@@ -783,39 +788,43 @@ static hipError_t launch_st(const SlicedTokGroupParams& P, int grid, uint32_t ld
   return hipGetLastError();
 }
 template <typename DT, int TOK>
-static hipError_t launch_st_dt(const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, bool two, uint32_t lds, hipStream_t st) {
+static hipError_t launch_st_dt(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  const int v = D.v, nsl = D.nsl;
+  const bool res = D.res, two = D.two;
   if (v == 16) {
-    if (two) return nsl == 16 ? launch_st<DT, 16, false, 16, true, TOK>(P, grid, lds, st) : launch_st<DT, 32, false, 16, true, TOK>(P, grid, lds, st);
-    return nsl == 16 ? launch_st<DT, 16, false, 16, false, TOK>(P, grid, lds, st) : launch_st<DT, 32, false, 16, false, TOK>(P, grid, lds, st);
+    if (two) return nsl == 16 ? launch_st<DT, 16, false, 16, true, TOK>(D, P, grid, lds, st) : launch_st<DT, 32, false, 16, true, TOK>(D, P, grid, lds, st);
+    return nsl == 16 ? launch_st<DT, 16, false, 16, false, TOK>(D, P, grid, lds, st) : launch_st<DT, 32, false, 16, false, TOK>(D, P, grid, lds, st);
   }
-  if (two) return nsl == 8 ? launch_st<DT, 8, false, 8, true, TOK>(P, grid, lds, st) : launch_st<DT, 16, false, 8, true, TOK>(P, grid, lds, st);
-  if (nsl == 8) return res ? launch_st<DT, 8, true, 8, false, TOK>(P, grid, lds, st) : launch_st<DT, 8, false, 8, false, TOK>(P, grid, lds, st);
-  return res ? launch_st<DT, 16, true, 8, false, TOK>(P, grid, lds, st) : launch_st<DT, 16, false, 8, false, TOK>(P, grid, lds, st);
+  if (two) return nsl == 8 ? launch_st<DT, 8, false, 8, true, TOK>(D, P, grid, lds, st) : launch_st<DT, 16, false, 8, true, TOK>(D, P, grid, lds, st);
+  if (nsl == 8) return res ? launch_st<DT, 8, true, 8, false, TOK>(D, P, grid, lds, st) : launch_st<DT, 8, false, 8, false, TOK>(D, P, grid, lds, st);
+  return res ? launch_st<DT, 16, true, 8, false, TOK>(D, P, grid, lds, st) : launch_st<DT, 16, false, 8, false, TOK>(D, P, grid, lds, st);
 }
 
 template <typename DT, int TOK>
-static hipError_t launch_st_ex(const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, uint32_t lds, hipStream_t st) {
-  if (v == 16) return nsl == 16 ? launch_st<DT, 16, false, 16, false, TOK, true>(P, grid, lds, st) : launch_st<DT, 32, false, 16, false, TOK, true>(P, grid, lds, st);
-  if (nsl == 8) return res ? launch_st<DT, 8, true, 8, false, TOK, true>(P, grid, lds, st) : launch_st<DT, 8, false, 8, false, TOK, true>(P, grid, lds, st);
-  return res ? launch_st<DT, 16, true, 8, false, TOK, true>(P, grid, lds, st) : launch_st<DT, 16, false, 8, false, TOK, true>(P, grid, lds, st);
+static hipError_t launch_st_ex(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  const int v = D.v, nsl = D.nsl;
+  const bool res = D.res;
+  if (v == 16) return nsl == 16 ? launch_st<DT, 16, false, 16, false, TOK, true>(D, P, grid, lds, st) : launch_st<DT, 32, false, 16, false, TOK, true>(D, P, grid, lds, st);
+  if (nsl == 8) return res ? launch_st<DT, 8, true, 8, false, TOK, true>(D, P, grid, lds, st) : launch_st<DT, 8, false, 8, false, TOK, true>(D, P, grid, lds, st);
+  return res ? launch_st<DT, 16, true, 8, false, TOK, true>(D, P, grid, lds, st) : launch_st<DT, 16, false, 8, false, TOK, true>(D, P, grid, lds, st);
 }
-hipError_t launch_st_ex4(int dtype, const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, uint32_t lds, hipStream_t st);
-hipError_t launch_st_ex8(int dtype, const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, uint32_t lds, hipStream_t st);
+hipError_t launch_st_ex4(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
+hipError_t launch_st_ex8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
 #if !defined(VPTQ_ST_PART) || VPTQ_ST_PART == 3
-hipError_t launch_st_ex4(int dtype, const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, uint32_t lds, hipStream_t st) {
-  return dtype == VPTQ_DTYPE_F16 ? launch_st_ex<F16, 4>(P, grid, v, nsl, res, lds, st) : launch_st_ex<BF16, 4>(P, grid, v, nsl, res, lds, st);
+hipError_t launch_st_ex4(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  return D.f16 ? launch_st_ex<F16, 4>(D, P, grid, lds, st) : launch_st_ex<BF16, 4>(D, P, grid, lds, st);
 }
 #endif
 #if !defined(VPTQ_ST_PART) || VPTQ_ST_PART == 4
-hipError_t launch_st_ex8(int dtype, const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, uint32_t lds, hipStream_t st) {
-  return dtype == VPTQ_DTYPE_F16 ? launch_st_ex<F16, 8>(P, grid, v, nsl, res, lds, st) : launch_st_ex<BF16, 8>(P, grid, v, nsl, res, lds, st);
+hipError_t launch_st_ex8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  return D.f16 ? launch_st_ex<F16, 8>(D, P, grid, lds, st) : launch_st_ex<BF16, 8>(D, P, grid, lds, st);
 }
 #endif
 
-hipError_t launch_st_tok8(int dtype, const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, bool two, uint32_t lds, hipStream_t st);
+hipError_t launch_st_tok8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
 #if !defined(VPTQ_ST_PART) || VPTQ_ST_PART == 2
-hipError_t launch_st_tok8(int dtype, const SlicedTokGroupParams& P, int grid, int v, int nsl, bool res, bool two, uint32_t lds, hipStream_t st) {
-  return dtype == VPTQ_DTYPE_F16 ? launch_st_dt<F16, 8>(P, grid, v, nsl, res, two, lds, st) : launch_st_dt<BF16, 8>(P, grid, v, nsl, res, two, lds, st);
+hipError_t launch_st_tok8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  return D.f16 ? launch_st_dt<F16, 8>(D, P, grid, lds, st) : launch_st_dt<BF16, 8>(D, P, grid, lds, st);
 }
 #endif
 
@@ -993,27 +1002,28 @@ bool gemv_sliced_tok_groupable(const VptqLayerDesc* d, const VptqSlicedLayout* L
   return true;
 }
 
-// x: [tokens][in_features], y[i]: [tokens][out_features of layer i] (fp32 with VPTQ_GEMV_OUT_F32); ws[i]:
-// gemv_sliced_tok_workspace_bytes of layer i, zero before its first use (every launch leaves the counters zero)
-hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
-                                        int tokens, int flags, void* const* ws, hipStream_t st) {
+// ---- decide, then launch (as gemv_sliced.hip:sl_decide): what one call is.  one_pass: the call is a launch of the one-token kernel over
+// the accumulator words acc[] (2 / 3 tokens in the reference's roundings) - nothing else is filled; else the column-phase kernel's
+// parameter blocks, the permutation pre-pass's jobs, grid, LDS and the instantiation.  Nothing is dereferenced.
+static hipError_t st_decide(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y, int tokens, int flags,
+                            void* const* ws, bool& one_pass, void** acc, SlicedTokGroupParams& GP, StPermJobs& jobs, uint32_t& lds,
+                            SlicedTokDecision& D) {
   const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
   if (!gemv_sliced_tok_groupable(d, L, n, tokens, exact)) return hipErrorInvalidValue;
   {   // 2 / 3 tokens in the reference's roundings: ONE pass of the one-token kernel where every member's operands fit its LDS
-    bool one_pass = true;
+    one_pass = true;
     for (int i = 0; i < n; ++i) one_pass = one_pass && st_one_pass(d[i], tokens, exact);
     if (one_pass) {
-      void* acc[kSTMaxGroup];
       for (int i = 0; i < n; ++i) acc[i] = (char*)ws[i] + st_counter_bytes(d[i]);
-      return launch_gemv_sliced_group(d, L, n, x, y, flags, acc, st, tokens);
+      return hipSuccess;
     }
     // (column parts of one layer share their output and accumulator words: the one pass only - the column-phase kernel below keeps
     // partial sums and counters per layer)
     if (flags & VPTQ_GEMV_COLUMN_PARTS) return hipErrorInvalidValue;
   }
-  SlicedTokGroupParams GP = {};
+  GP = SlicedTokGroupParams{};
   GP.n = n;
-  StPermJobs jobs = {};
+  jobs.n = 0;
   const SlicedLayoutSet S0 = sl_piece_set(d[0], exact);
   const int tables = S0.tables, nsl = S0.slices, nslt = nsl * tables;
   // rows per wave: one round of workgroups over ALL members
@@ -1025,32 +1035,66 @@ hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSliced
   // 2 x 14336 outputs, v8-k65536-256: 7 rows per wave 55.5 us, 4 rows per wave 52.3 - but not a third and fourth round: the
   // two-table format of the same layers, 14 rows per wave 72.9 us, 4 rows per wave 90.9)
   if (tokens > 2 && rpw0 > kSTRegRows && rpw0 <= 2 * kSTRegRows) rpw0 = kSTRegRows;
-  uint32_t lds = 0;
-  int tok = 0;
+  lds = 0;
+  D = SlicedTokDecision{};
   for (int i = 0; i < n; ++i) {
     StPlan pl;
     const hipError_t e = st_fill(d[i], L + (size_t)i * tables, x, y[i], tokens, flags, ws[i], rpw0, GP.p[i], pl, jobs);
     if (e != hipSuccess) return e;
     lds = pl.lds > lds ? pl.lds : lds;
-    tok = pl.tok;
+    D.tok = pl.tok;
+    if (i == 0) { D.phases = pl.phases; D.rpw = pl.rpw; D.reg_sums = pl.reg_sums; }
     GP.start[i + 1] = GP.start[i] + nslt * GP.p[i].p.n_rowblocks;
   }
   for (int i = n; i < kSTMaxGroup; ++i) GP.start[i + 1] = GP.start[n];
+  D.f16 = d[0].dtype == VPTQ_DTYPE_F16;
+  D.nsl = nsl; D.v = d[0].vector_len;
+  D.res = S0.side_bytes == 1; D.two = S0.tables == 2; D.ex = exact;
+  D.n = n; D.whole1 = tables == 2 ? L[1].whole_table : 0;
+  D.perm = jobs.n > 0;
+  return hipSuccess;
+}
+
+// x: [tokens][in_features], y[i]: [tokens][out_features of layer i] (fp32 with VPTQ_GEMV_OUT_F32); ws[i]:
+// gemv_sliced_tok_workspace_bytes of layer i, zero before its first use (every launch leaves the counters zero)
+hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
+                                        int tokens, int flags, void* const* ws, hipStream_t st) {
+  SlicedTokGroupParams GP;
+  StPermJobs jobs = {};
+  SlicedTokDecision D;
+  uint32_t lds = 0;
+  bool one_pass = false;
+  void* acc[kSTMaxGroup];
+  if (const hipError_t e = st_decide(d, L, n, x, y, tokens, flags, ws, one_pass, acc, GP, jobs, lds, D); e != hipSuccess) return e;
+  if (one_pass) return launch_gemv_sliced_group(d, L, n, x, y, flags, acc, st, tokens);
   if (jobs.n > 0) {
     const hipError_t e = launch_permute_x(jobs.d, jobs.n, jobs.xin, jobs.xout, st);
     if (e != hipSuccess) return e;
   }
   const int grid = GP.start[n];
-  const bool res = S0.side_bytes == 1, two = S0.tables == 2;
-  if (exact)
-    return tok == 8 ? launch_st_ex8(d[0].dtype, GP, grid, d[0].vector_len, nsl, res, lds, st)
-                    : launch_st_ex4(d[0].dtype, GP, grid, d[0].vector_len, nsl, res, lds, st);
-  if (tok == 8) return launch_st_tok8(d[0].dtype, GP, grid, d[0].vector_len, nsl, res, two, lds, st);
-  if (d[0].dtype == VPTQ_DTYPE_F16)
-    return tok == 2 ? launch_st_dt<F16, 2>(GP, grid, d[0].vector_len, nsl, res, two, lds, st)
-                    : launch_st_dt<F16, 4>(GP, grid, d[0].vector_len, nsl, res, two, lds, st);
-  return tok == 2 ? launch_st_dt<BF16, 2>(GP, grid, d[0].vector_len, nsl, res, two, lds, st)
-                  : launch_st_dt<BF16, 4>(GP, grid, d[0].vector_len, nsl, res, two, lds, st);
+  if (D.ex) return D.tok == 8 ? launch_st_ex8(D, GP, grid, lds, st) : launch_st_ex4(D, GP, grid, lds, st);
+  if (D.tok == 8) return launch_st_tok8(D, GP, grid, lds, st);
+  if (D.f16) return D.tok == 2 ? launch_st_dt<F16, 2>(D, GP, grid, lds, st) : launch_st_dt<F16, 4>(D, GP, grid, lds, st);
+  return D.tok == 2 ? launch_st_dt<BF16, 2>(D, GP, grid, lds, st) : launch_st_dt<BF16, 4>(D, GP, grid, lds, st);
+}
+// what launch_gemv_sliced_tok_group would launch, as text: the column-phase kernel's instance, or (one pass) gemv_sliced's
+int gemv_sliced_tok_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, int flags, char* buf, size_t bytes) {
+  if (n < 1 || n > kSTMaxGroup) return -1;
+  void* const some = (void*)(uintptr_t)4096;   // placeholders: aligned, never dereferenced
+  void* ys[kSTMaxGroup] = {some, some, some};
+  void* wss[kSTMaxGroup] = {some, some, some};
+  SlicedTokGroupParams GP;
+  StPermJobs jobs = {};
+  SlicedTokDecision D;
+  uint32_t lds = 0;
+  bool one_pass = false;
+  void* acc[kSTMaxGroup];
+  if (st_decide(d, L, n, some, ys, tokens, flags, wss, one_pass, acc, GP, jobs, lds, D) != hipSuccess) return -1;
+  if (one_pass) return gemv_sliced_instance(d, L, n, tokens, flags, false, buf, bytes);
+  const int w = snprintf(buf, bytes, "gemv_sliced_tok dt=%s nsl=%d res=%d v=%d two=%d tok=%d ex=%d phases=%d rpw=%d regsums=%d n=%d whole1=%d perm=%d",
+                         D.f16 ? "f16" : "bf16", D.nsl, (int)D.res, D.v, (int)D.two, D.tok, (int)D.ex, D.phases, D.rpw, D.reg_sums, D.n, D.whole1,
+                         (int)D.perm);
+  return w < 0 || (size_t)w >= bytes ? -2 : 0;
 }
 hipError_t launch_gemv_sliced_tok(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int tokens, int flags,
                                   void* ws, hipStream_t st) {

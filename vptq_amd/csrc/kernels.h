@@ -108,6 +108,26 @@ hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSliced
 bool gemv_sliced_groupable(const VptqLayerDesc* d, int n, bool exact = false);
 hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
                                     int flags, void* const* ws, hipStream_t st, int tokens = 1, const float* corr = nullptr);
+// what one launch of the sliced family IS - the instantiation's template arguments and the launch shape: decided once per call
+// (gemv_sliced.hip:sl_decide, gemv_sliced_tok.hip:st_decide, gemv_hot_decide), checked by the launchers against their template arguments
+// and printed by the *_instance functions (vptq_quant_gemv_sliced_instance / _tokens_instance): 0, -1: no launch, -2: buffer too small
+struct SlicedDecision {
+  bool f16, res, two, ex, rg, wpt;   // gemv_sliced_kernel<DT, NSL, RES, V, TWO, EX, RG, TOK, WPT>
+  int nsl, v, tok;
+  int wparts, parts, n, rpw, arrivals, whole1, side;   // window parts, column parts, members, rows per wave, arrivals per accumulator
+  bool perm, corr;                                     // word, the second table held whole, bytes of the side stream; a permutation; SELECTIVE's products
+};
+struct SlicedTokDecision {
+  bool f16, res, two, ex;            // gemv_sliced_tok_kernel<DT, NSL, RES, V, TWO, TOK, EX>
+  int nsl, v, tok;
+  int phases, rpw, reg_sums, n, whole1;
+  bool perm;                         // the permute_x pre-pass runs
+};
+struct HotDecision { bool ok, f16; int v; };   // gemv_hot_kernel<DT, V>
+HotDecision gemv_hot_decide(const VptqLayerDesc& d);
+int gemv_hot_instance(const VptqLayerDesc& d, char* buf, size_t bytes);
+int gemv_sliced_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, int flags, bool corr, char* buf, size_t bytes);
+int gemv_sliced_tok_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, int flags, char* buf, size_t bytes);
 // (VPTQ_GEMV_EXACT) 2 / 3 tokens in ONE pass of the one-token kernel: x [tokens][in], y[i] [tokens][out], ws[i]: accumulator words
 bool gemv_sliced_exact_tokens_ok(const VptqLayerDesc& d, int tokens);
 int gemv_sliced_exact_tokens_parts(const VptqLayerDesc& d, int tokens);   // 0: not served; 1: all columns staged; 2 / 4: window parts (needs wstart)
