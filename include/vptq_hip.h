@@ -467,12 +467,26 @@ VPTQ_API int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const Vp
  * and the index inside the slice, the (slice, row) list it sits in the slice and the row - index = slice << (index_bits -
  * log2(slices)) | local -, and `res` the residual index (uint8: v = 8 with 256 residual centroids; uint16: any other residual
  * codebook).  Padding words (column = part width) are skipped.  So a layer served from such a layout needs no packed copy: the
- * paths that read the stream (gather kernels, vptq_dequant) get it from here, into a scratch buffer.  Folded layouts (two
+ * paths that read the stream (the gather kernels; vptq_dequant where vptq_dequant_sliced below is not taken) get it from here, into
+ * a scratch buffer.  Folded layouts (two
  * tables, whole tables) are not taken.  Errors: NULL layouts / out (VPTQ_E_NULL), `parts` other than the layer's
  * (VPTQ_E_SHAPE), a part's n_slices other than vptq_sliced_layout_supported_for(part, VPTQ_GEMV_EXACT) (VPTQ_E_SHAPE), an out
  * pointer not 16-byte aligned (VPTQ_E_ALIGN); nothing is launched then.  One workgroup per row, the row assembled in LDS. */
 VPTQ_API int vptq_sliced_layout_repack(const VptqLayerDesc* desc, const VptqSlicedLayout* layouts, int parts, void* indices_out,
                                        void* stream);
+
+/* W[O, I] dense, row-major, desc->dtype, STRAIGHT FROM the layer's EXACT sliced layout(s): bit for bit what vptq_dequant writes for
+ * the packed indices the layouts were built from (= vptq_sliced_layout_repack + vptq_dequant, without the packed stream, its scratch
+ * buffer and one launch) - the many-token route and dequant() of a layer that holds its indices in the layout only.
+ * Added within ABI 11; present when the symbol is.  `layouts`, `parts`: as vptq_sliced_layout_repack takes them, and validated the
+ * same way - NULL layouts / W (VPTQ_E_NULL), `parts` other than the layer's (VPTQ_E_SHAPE), a part's n_slices other than the exact
+ * answer (VPTQ_E_SHAPE), folded or whole-table layouts and layers without an exact layout (VPTQ_E_UNSUPPORTED), W - or a pointer of the
+ * layout - not aligned as repack asks (W: 16 bytes; VPTQ_E_ALIGN); nothing is launched then.  desc->indices must be non-NULL and is
+ * not read.  The kernel reads desc->perm (column g of the quantised matrix is column perm[g] of W), never desc->inv_perm: any
+ * descriptor of the layer that its exact layouts are valid for serves, the one of the sliced entries and the dense one alike.  A
+ * layout's `wstart`, where set (4-byte aligned), bounds the walk of a column tile; NULL is accepted.  One workgroup per vector-row
+ * and column tile, the tile assembled in LDS and stored in 16-byte pieces; no workspace, no allocation: graph-capturable. */
+VPTQ_API int vptq_dequant_sliced(const VptqLayerDesc* desc, const VptqSlicedLayout* layouts, int parts, void* W, void* stream);
 
 /* Build a sliced layout from the packed indices ON THE DEVICE: the forward direction of vptq_sliced_layout_repack, and byte for
  * byte what the torch recipe vptq_amd/utils/sliced.py:layout_from_indices builds (the recipe stays the model and serves CPU tensors).

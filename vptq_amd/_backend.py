@@ -137,6 +137,8 @@ EXPORTS = {
     "vptq_sliced_layout_set": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.POINTER(SlicedLayoutSet)]),
     # (added within ABI 11) the packed index stream rebuilt from a layer's exact sliced layout(s): compact mode
     "vptq_sliced_layout_repack": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, _vp, _vp]),
+    # (added within ABI 11) the dense W straight from a layer's exact sliced layout(s): compact mode's many-token route
+    "vptq_dequant_sliced": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, _vp, _vp]),
     # (added within ABI 11) a sliced layout built from the packed indices on the device, in two steps (layout_build.hip)
     "vptq_sliced_layout_plan": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayoutSpec), _vp, _vp, _vp, _vp, _vp]),
     "vptq_sliced_layout_fill": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayoutSpec), C.POINTER(SlicedLayout), C.c_int64, _vp]),

@@ -837,6 +837,23 @@ int vptq_sliced_layout_repack(const VptqLayerDesc* d, const VptqSlicedLayout* la
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "sliced_repack launch");
 }
 
+int vptq_dequant_sliced(const VptqLayerDesc* d, const VptqSlicedLayout* layouts, int parts, void* W, void* stream) {
+  if (int rc = validate_layer(d)) return rc;
+  if (!layouts || !W) return fail(VPTQ_E_NULL, "layouts / W is NULL");
+  const vptq::SlicedLayoutSet S = vptq::sl_layout_set(*d, true);
+  if (S.parts == 0) return fail(VPTQ_E_UNSUPPORTED, kNoExactLayout);
+  if (parts != S.parts) return fail(VPTQ_E_SHAPE, "parts %d: the exact layouts of this layer come in %d column part(s)", parts, S.parts);
+  if ((((uintptr_t)W) & 15) != 0) return fail(VPTQ_E_ALIGN, "W must be 16-byte aligned");
+  if (!vptq::dequant_sliced_eligible(*d)) return fail(VPTQ_E_UNSUPPORTED, "vptq_dequant_sliced: v = 8 / 16 layers of one codebook group with scale and bias, a multiple of 8 columns");
+  int which = 0;   // (the checks of vptq_sliced_layout_repack: folded layouts - two tables, whole tables - do not hold the packed stream)
+  if (const unsigned faults = vptq::sl_check_layouts(*d, S, layouts, parts, vptq::kSLNeedBuilt | vptq::kSLNeedWhole | vptq::kSLNeedRes8, 0, &which))
+    return layout_fail(faults, false, "vptq_dequant_sliced", which, 0, S);
+  for (int p = 0; p < parts; ++p)   // (optional here, read where set: the lists' window order bounds a tile's walk)
+    if ((((uintptr_t)layouts[p].wstart) & 3) != 0) return fail(VPTQ_E_ALIGN, "vptq_dequant_sliced: part %d: wstart must be 4-byte aligned", p);
+  const hipError_t e = vptq::launch_dequant_sliced(*d, layouts, parts, S.side_bytes, W, (hipStream_t)stream);
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "dequant_sliced launch");
+}
+
 // what vptq_sliced_layout_plan / _fill build for (desc, spec): validation of the spec against the layouts the GEMV entries take for
 // the layer (VPTQ_LAYOUT_ANY_SHAPE: against the index widths alone), then the kernel's parameters
 static int layout_build_params(const VptqLayerDesc* d, const VptqSlicedLayoutSpec* spec, vptq::LayoutBuildParams* P) {

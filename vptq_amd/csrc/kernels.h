@@ -135,6 +135,9 @@ size_t gemv_sliced_exact_tokens_workspace_bytes(const VptqLayerDesc& d, int toke
 // repack.hip - the packed index stream of a layer rebuilt from its exact sliced layout(s) (vptq_sliced_layout_repack)
 size_t sliced_repack_lds_bytes(const VptqLayerDesc& d);
 hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, int side_bytes, void* out, hipStream_t st);   // side_bytes: SlicedLayoutSet's
+// dequant_sliced.hip - the dense W straight from a layer's exact sliced layout(s) (vptq_dequant_sliced); reads d.perm, not d.inv_perm
+bool dequant_sliced_eligible(const VptqLayerDesc& d);
+hipError_t launch_dequant_sliced(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, int side_bytes, void* W, hipStream_t st);   // side_bytes: SlicedLayoutSet's
 // layout_build.hip - a sliced layout built from the packed index stream (vptq_sliced_layout_plan / vptq_sliced_layout_fill)
 struct LayoutBuildParams {
   const uint32_t* packed;   // [N][row_words]

@@ -76,6 +76,33 @@ _SLICED_FORMATS = "v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no 
 _COMPACTED = weakref.WeakSet()   # compacted layers (their share of the compact-mode scratch)
 
 
+# WHICH compacted layers build their dense W straight from the layout (`vptq_dequant_sliced`) instead of repack + `vptq_dequant`: the one
+# rule, read by `_dense_cached` and `dequant()`.  Measured on one MI355X, graph replays over a ring of 4 layers, the two routes in turns,
+# median us per layer, new / repack route (tools/dequant_sliced_bench.py, profiles/r12; spread of the repack route 0.2 - 1.3 us):
+#   rows x columns    v8-k65536-256     v8-k65536-0       v8-k65536-65536   v16-k65536-65536      (fp16 | bf16)
+#   4096 x 4096       0.70 | 0.83       0.74 | 0.85       0.72 | 0.84       0.84 | 0.87
+#   14336 x 4096      0.89 | 0.98       0.98 | 1.07       0.85 | 0.97       1.12 | 1.12
+#   4096 x 14336      1.01 | 1.04       1.09 | 1.13       0.98 | 1.01       1.02 | 1.06
+#   8192 x 8192       1.01 | 1.05       1.09 | 1.12       1.00 | 1.03       1.02 | 1.03
+#   4096 x 28672      0.99 | 1.03       1.21 | 1.27       0.96 | 1.01       1.16 | 1.22
+# The new kernel wins in every format and dtype only on layers of up to 4096 x 4096 (one round of workgroups: its gather and store
+# phases do not overlap inside a workgroup); larger layers keep the repack route.  VPTQ_DEQUANT_SLICED=1 / 0 (with VPTQ_TUNING=1):
+# every compacted layer / none (A/B, and a model that must not hold the repack scratch).
+_DEQUANT_SLICED_MAX_ROWS = 4096
+_DEQUANT_SLICED_MAX_COLS = 4096
+_DEQUANT_SLICED_MODE = (B.tune_env("VPTQ_DEQUANT_SLICED", "auto") or "auto").strip().lower()
+
+
+def _dense_from_layout(layer) -> bool:
+    """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (a library without the entry, added within ABI 11:
+    never - the repack route stays)"""
+    if getattr(B.lib(), "vptq_dequant_sliced", None) is None or _DEQUANT_SLICED_MODE in ("0", "off"):
+        return False
+    if _DEQUANT_SLICED_MODE in ("1", "on"):
+        return True
+    return layer.out_features <= _DEQUANT_SLICED_MAX_ROWS and layer.in_features <= _DEQUANT_SLICED_MAX_COLS
+
+
 class LayerCache(NamedTuple):
     """What `VQuantLinear._descriptor()` builds once per set of parameter storages.  The ORDER is part of the contract (`_gemv_cached`
     unpacks it by position: one unpack is cheaper than eleven attribute reads per call; the benchmark reads `[1]`): new fields go last."""
@@ -935,13 +962,23 @@ class VQuantLinear(nn.Module):
         _, desc, _, dequant = dense
         W = torch.empty((self.out_features, self.in_features), dtype=wdtype, device=dev)
         cp = self.__dict__.get("_compact")
+        # (compact mode: W straight from the layout where that is the faster route - no repack, no scratch; `_dense_from_layout`)
+        sl = self._sliced_gemv() if cp is not None and _dense_from_layout(self) else None
         if torch.cuda.current_device() != dev_index:
             with torch.cuda.device(dev):
                 sp = B.current_stream_ptr(dev)
-                rc = dequant(desc if cp is None else self._repacked_desc(desc, dev_index, sp), W.data_ptr(), sp)
+                if sl is not None:
+                    sl.dequant(W, sp)
+                    rc = 0
+                else:
+                    rc = dequant(desc if cp is None else self._repacked_desc(desc, dev_index, sp), W.data_ptr(), sp)
         else:
             sp = _raw_stream(dev_index)
-            rc = dequant(desc if cp is None else self._repacked_desc(desc, dev_index, sp), W.data_ptr(), sp)
+            if sl is not None:
+                sl.dequant(W, sp)
+                rc = 0
+            else:
+                rc = dequant(desc if cp is None else self._repacked_desc(desc, dev_index, sp), W.data_ptr(), sp)
         if rc:
             B.check(rc, "vptq_dequant")
         return torch.nn.functional.linear(x, W, self._parameters.get("bias"))
@@ -949,6 +986,8 @@ class VQuantLinear(nn.Module):
     def dequant(self) -> torch.Tensor:
         """Dense W[out_features, in_features] (what the reference calls
         `ops.dequant(...)` with this layer's fields)."""
+        if "_compact" in self.__dict__ and _dense_from_layout(self):
+            return self._sliced_gemv().dequant()   # (compact mode: straight from the layout, the same bits)
         return ops.dequant(
             indices=self.packed_indices(), centroids=self.centroids.weight,
             outlier_indices=self.outlier_indices,
@@ -968,9 +1007,11 @@ class VQuantLinear(nn.Module):
     # ---- compact mode: the exact sliced layout as the ONLY copy of the indices ----------------------------------------------------
     # The exact layout (vptq_amd/utils/sliced.py, SlicedGemv(exact=True)) holds every bit of the packed stream (include/vptq_hip.h,
     # vptq_sliced_layout_repack), so a layer served from it at one token can drop its packed `indices`: about a third of the resident
-    # weights of the large-codebook formats.  1 - 4 tokens take the sliced kernels as before; every path that reads the packed stream
-    # (gather kernels, vptq_dequant, dequant(), state_dict(), shards, copies) gets it rebuilt by the repack kernel - into a per-stream
-    # scratch buffer for launches, into a fresh tensor otherwise.  `indices` is a meta-device parameter of the same shape meanwhile.
+    # weights of the large-codebook formats.  1 - 4 tokens take the sliced kernels as before; the dense route (many tokens) and
+    # dequant() of layers up to 4096 x 4096 build W straight from the layout (vptq_dequant_sliced: the bits of vptq_dequant, no packed
+    # stream in between; `_dense_from_layout` above has the rule and its numbers); every path that still reads the packed stream (the
+    # gather kernels of 5 - 8 tokens, the dense route of larger layers, state_dict(), shards, copies) gets it rebuilt by the repack kernel - into a per-stream scratch buffer for launches,
+    # into a fresh tensor otherwise.  `indices` is a meta-device parameter of the same shape meanwhile.
 
     def compact(self, force: bool = False) -> int:
         """Hold this layer's indices in its exact sliced layout only; returns the bytes freed (0: not compacted - the reason is

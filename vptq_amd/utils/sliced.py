@@ -394,6 +394,20 @@ class SlicedGemv:
                                                       B.current_stream_ptr(self.dev)), "vptq_sliced_layout_repack")
         return out
 
+    def dequant(self, out: torch.Tensor = None, stream: int = None) -> torch.Tensor:
+        """the layer's dense W [out_features, in_features] straight from this EXACT layout (`vptq_dequant_sliced`): bit for bit what
+        `vptq_dequant` writes for the packed indices the layout was built from, without rebuilding them.  Into `out` (the layer's
+        dtype, contiguous, 16-byte aligned) or a fresh tensor; on `stream` (a raw handle of the layer's device) or the current one."""
+        if not self.exact:
+            raise ValueError("only an exact layout holds the packed stream")
+        if out is None:
+            out = torch.empty((int(self.desc.out_features), int(self.desc.in_features)), dtype=self._dtype, device=self.dev)
+        if stream is None:
+            with torch.cuda.device(self.dev):
+                stream = B.current_stream_ptr(self.dev)
+        B.check(B.lib().vptq_dequant_sliced(self.desc, self._lay_ref, self.parts, out.data_ptr(), stream), "vptq_dequant_sliced")
+        return out
+
     def rebound(self, desc) -> "SlicedGemv":
         """a copy of this object over the same layout tensors and workspaces for another descriptor of the same layer (a compacted
         layer's descriptor is rebuilt after set_arithmetic or a parameter change; its layout never is)"""
