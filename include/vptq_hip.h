@@ -560,14 +560,27 @@ VPTQ_API const char* vptq_quant_gemv_grouped_kernel_name(const VptqLayerDesc* de
  *   gemm_k256 dt= perm= tok=N passes=4+2+1      (the passes of 4 / 2 / 1 row groups the busiest workgroup runs)
  *   gemm_k256t dt= perm= tok=N sweeps=N rgs=N    (rgs: the most row groups one workgroup walks)
  *   gemv_k256c dt= dep=0|1 mode=folded|exact|selective layers=N sweeps=a,b,... perm=a,b,...   (per layer, in list order)
- * vptq_quant_gemv_chain_instance puts "grouped: " / "per-layer: " in front where the chain call hands the list to those.  The
- * other kernel families answer with their kernel name alone.  tokens beyond one launch's: the first launch.  Returns VPTQ_OK,
- * the validation error of the call itself, or VPTQ_E_WORKSPACE when buf (bytes long, NUL included) is too small. */
+ *   gemv_gather dt= t=16|24|32 rows=1|2 tok=1|2|4|8 perm= wide=0|1
+ *       <DT, T, ROWS, TOK, PERM, WIDE>: t the index width, rows vector-rows per workgroup, wide 8 elements per lane and piece
+ *   gemv_gatherx dt= v=2|4|6|8|10|12|16 tok=1|2|4|8 perm= reslds=0|1 outl=0|same|4 groups=N
+ *       <DT, V, TOK, PERM>, then the forks inside the kernel: the residual table gathered from LDS (<= 32 KiB) or from L2, outlier
+ *       columns (none, a codebook of the layer's vector length, of length 4), codebook groups
+ *   gemv_generic dt= v= tok=1|2|4|8
+ *   gemv_lds dt= fmt=12|13|20|21|22|v2|v2u8|v2u16 tok=1|2|4 rw=1|2|4|8|16 dma=0|1 perm=
+ *       <DT, FMT, TOK>: fmt the packed stream's index width or the v2 wire format (no / uint8 / uint16 residual ids); rw vector-rows
+ *       per row group (by the CU count), dma the main table copied by LDS-DMA (k a multiple of 64) or through registers
+ *   gemv_lds_mfma dt= fmt= rw=4|8|16 stages=1..4 dma= perm=      (stages: staging passes of 8192 columns)
+ *   gemv_v2 dt= v=4|8|16 tok=1|2|4|8                             (vptq_quant_gemv_v2_instance only)
+ * vptq_quant_gemv_chain_instance puts "grouped: " / "per-layer: " in front where the chain call hands the list to those.
+ * tok: the token slots of the FIRST launch where a call is served in several.  vptq_quant_gemv_v2_instance answers for
+ * vptq_quant_gemv_v2: a gemv_lds / gemv_lds_mfma line (fmt=v2*) or a gemv_v2 line.  Returns VPTQ_OK, the validation error of the call
+ * itself, or VPTQ_E_WORKSPACE when buf (bytes long, NUL included) is too small. */
 VPTQ_API int vptq_quant_gemv_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 VPTQ_API int vptq_quant_gemv_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf,
                                               size_t bytes);
 VPTQ_API int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf,
                                             size_t bytes);
+VPTQ_API int vptq_quant_gemv_v2_instance(const VptqV2Desc* desc, int tokens, int flags, char* buf, size_t bytes);
 /* The same for the SLICED entries (added within ABI 11; present when the symbols are): which instantiation of gemv_sliced_kernel /
  * gemv_sliced_tok_kernel / gemv_hot_kernel a call over these layouts would launch.  descs, layouts, n, flags: as the call takes them
  * (VPTQ_GEMV_COLUMN_PARTS included); of the VptqSlicedLayout structs only the scalar fields and the pointers' being set and their

@@ -85,6 +85,65 @@ def pieces(L):
     return dict(c=c, r=r, s=s, b=b, bias=bias, W=W, dtype=dt, norm=L.weight_scale is not None)
 
 
+def pieces_v2(dtype, I, O, v, indices, centroids, res_indices=None, res_centroids=None, scale=None, sbias=None, bias=None):
+    """the same dict as pieces(L) from the tensors of the v2 wire format (ids [N * I], one codebook, uint16 bit patterns; there is
+    no permutation): W by vo.dequant_v2, so model() / check_outputs() take the v2 rows unchanged"""
+    N = O // v
+    ids = np.asarray(indices).reshape(N, I).astype(np.int64)
+    cent = vo.to_f32(np.asarray(centroids), dtype).reshape(-1, v).astype(np.float64)
+    c = cent[ids].transpose(0, 2, 1).reshape(N * v, I)
+    if res_indices is not None:
+        rc = vo.to_f32(np.asarray(res_centroids), dtype).reshape(-1, v).astype(np.float64)
+        r = rc[np.asarray(res_indices).reshape(N, I).astype(np.int64)].transpose(0, 2, 1).reshape(N * v, I)
+    else:
+        r = np.zeros_like(c)
+    s = vo.to_f32(np.asarray(scale), dtype).reshape(I).astype(np.float64) if scale is not None else np.ones(I)
+    b = vo.to_f32(np.asarray(sbias), dtype).reshape(I).astype(np.float64) if sbias is not None else np.zeros(I)
+    bb = vo.to_f32(np.asarray(bias), dtype).reshape(O).astype(np.float64) if bias is not None else np.zeros(O)
+    W = vo.dequant_v2(indices, centroids, res_indices, res_centroids, scale, sbias, I, O, v, dtype).astype(np.float64).T
+    return dict(c=c, r=r, s=s, b=b, bias=bb, W=np.ascontiguousarray(W), dtype=dtype, norm=scale is not None)
+
+
+MAX_WEIGHTS = 16 << 20   # float64 weights one step of a blocked model holds (the size limit of the route tables' cases)
+
+
+def row_blocks(L, max_weights=MAX_WEIGHTS):
+    """-> [(n0, n1)]: ranges of vector-rows of at most max_weights weights each (at least one vector-row)"""
+    rows = max(1, max_weights // (L.vector_len * L.in_features))
+    return [(n0, min(n0 + rows, L.num_indices)) for n0 in range(0, L.num_indices, rows)]
+
+
+def slice_rows(L, n0, n1):
+    """the layer of the vector-rows [n0, n1) of L: the index rows, the outlier index rows and the output bias sliced; codebooks,
+    scale, bias and permutation shared"""
+    import dataclasses
+    v, O = L.vector_len, L.out_features
+    o0, o1 = n0 * v, min(n1 * v, O)
+    S = dataclasses.replace(L, out_features=o1 - o0, indices=np.ascontiguousarray(np.asarray(L.indices)[:, n0:n1]))
+    if L.enable_outlier:
+        ov = L.outlier_vector_len
+        assert o0 % ov == 0, "a row block must start on an outlier vector"
+        oi = np.ascontiguousarray(L.outlier_indices).view(np.uint16).reshape(1, -1, L.outlier_size)
+        S.outlier_indices = np.ascontiguousarray(oi[:, o0 // ov:(o1 + ov - 1) // ov])
+    if L.bias is not None:
+        S.bias = np.ascontiguousarray(np.asarray(L.bias).reshape(-1)[o0:o1])
+    return S
+
+
+def pieces_blocks(L, max_weights=MAX_WEIGHTS):
+    """the row-block form of pieces(L): yields ((n0, n1) vector-rows, (o0, o1) outputs, pieces of that slice of the layer), so that
+    no step holds more than max_weights float64 weights per array"""
+    for n0, n1 in row_blocks(L, max_weights):
+        yield (n0, n1), (n0 * L.vector_len, min(n1 * L.vector_len, L.out_features)), pieces(slice_rows(L, n0, n1))
+
+
+def model_blocks(L, x_bits, arith="exact", max_weights=MAX_WEIGHTS, **kw):
+    """model() block by block: yields ((o0, o1), m, a) with m, a [tokens, o1 - o0]"""
+    for _, orange, P in pieces_blocks(L, max_weights):
+        m, a = model(P, x_bits, arith, **kw)
+        yield orange, m, a
+
+
 def _x64(x_bits, dtype, I):
     return vo.to_f32(np.asarray(x_bits), dtype).astype(np.float64).reshape(-1, I)
 

@@ -95,6 +95,49 @@ def gemv_abi(m, x, flags=0, workspace=True, out_f32=False):
     return y
 
 
+def gemv_abi_nan(m, x, flags=0, out_f32=False):
+    """gemv_abi with y filled with NaN before the call: an output the launch does not write stays NaN (and _arith_model.check_outputs
+    rejects it)"""
+    from vptq_amd import _backend as B
+    desc, keep = module_desc(m)
+    tokens = x.numel() // x.shape[-1]
+    y = torch.full(x.shape[:-1] + (m.out_features,), float("nan"), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    nb = B.lib().vptq_quant_gemv_workspace_bytes(desc, tokens, flags)
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb else None
+    B.check(B.lib().vptq_quant_gemv(desc, x.data_ptr(), y.data_ptr(), tokens, flags | (B.GEMV_OUT_F32 if out_f32 else 0),
+                                    None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(),
+                                    B.current_stream_ptr(x.device)), "vptq_quant_gemv")
+    torch.cuda.current_stream(x.device).synchronize()
+    return y
+
+
+def v2_desc(t, dtype):
+    """C-ABI VptqV2Desc of a dict of v2 tensors (keys: I, O, v, k, kr, ids, cent, rids, rcent, scale, sbias, bias; absent = None);
+    -> (desc, the tensors kept alive)"""
+    from vptq_amd import _backend as B
+    d = B.V2Desc()
+    d.in_features, d.out_features, d.vector_len, d.num_centroids = t["I"], t["O"], t["v"], t["k"]
+    has_res = t.get("rids") is not None
+    d.num_res_centroids = t["kr"] if has_res else 0
+    d.res_index_bytes = t["rids"].element_size() if has_res else 0
+    d.dtype = {"f16": 0, "bf16": 1}[dtype]
+    ptr = lambda key: None if t.get(key) is None else t[key].data_ptr()   # noqa: E731
+    d.indices, d.centroids, d.res_indices, d.res_centroids = ptr("ids"), ptr("cent"), ptr("rids"), ptr("rcent")
+    d.scale_weights, d.scale_bias, d.bias = ptr("scale"), ptr("sbias"), ptr("bias")
+    return d, t
+
+
+def gemv_v2_abi_nan(desc, x, O, flags=0, out_f32=False):
+    """vptq_quant_gemv_v2 through the C ABI with explicit flags, y filled with NaN before the call"""
+    from vptq_amd import _backend as B
+    tokens = x.numel() // x.shape[-1]
+    y = torch.full(x.shape[:-1] + (O,), float("nan"), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    B.check(B.lib().vptq_quant_gemv_v2(desc, x.data_ptr(), y.data_ptr(), tokens, flags | (B.GEMV_OUT_F32 if out_f32 else 0),
+                                       B.current_stream_ptr(x.device)), "vptq_quant_gemv_v2")
+    torch.cuda.current_stream(x.device).synchronize()
+    return y
+
+
 def kernel_name(m, tokens=1, flags=0):
     from vptq_amd import _backend as B
     desc, keep = module_desc(m)

@@ -228,3 +228,81 @@ def test_overflow_and_nan_rules():
         with pytest.raises(AssertionError):
             am.check_outputs(np.array(bad), m, a, "f16", False)
     am.check_outputs(np.array([[np.inf, -np.inf, np.nan, 65024.0]]), m, a, "f16", False, allow_nan=True)
+
+
+# ---------------------------------------------------------------------------------------------- the row-block form, the v2 pieces
+BLOCK_LAYERS = [
+    dict(I=520, O=100, kw=dict(num_centroids=4096, num_res_centroids=256, bias=True, enable_perm=True)),
+    dict(I=4 * 260 + 8, O=98, kw=dict(vector_len=8, num_centroids=4096, num_res_centroids=16, num_codebooks=4, outlier_size=8,
+                                      outlier_vector_len=4, num_outlier_centroids=256, bias=True)),
+    dict(I=264, O=85, kw=dict(vector_len=12, num_centroids=256, num_res_centroids=0, outlier_size=4, outlier_vector_len=12,
+                              num_outlier_centroids=256, enable_norm=False)),
+]
+
+
+@pytest.mark.parametrize("spec", BLOCK_LAYERS, ids=[f"{s['I']}x{s['O']}" for s in BLOCK_LAYERS])
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+def test_blocked_model_equals_the_whole_model_bit_for_bit(spec, dt):
+    """pieces_blocks / model_blocks (row blocks of a few vector-rows: index rows, outlier index rows and output bias sliced,
+    the rest shared) give the values of pieces + model, bit for bit, for every arithmetic - a large row checked block by block is
+    checked against the same numbers"""
+    L = vo.make_layer(spec["I"], spec["O"], dist="llm", seed=3, dtype=dt, **spec["kw"])
+    P = am.pieces(L)
+    x = _x(spec["I"], 3, dt, "massive", 5)
+    limit = 3 * L.vector_len * L.in_features          # three vector-rows per block: several blocks, a short last one
+    blocks = list(am.pieces_blocks(L, limit))
+    assert len(blocks) > 2 and blocks[0][0] == (0, 3) and blocks[-1][1][1] == spec["O"]
+    for (n0, n1), (o0, o1), Pb in blocks:
+        for key in ("c", "r", "W"):
+            assert np.array_equal(Pb[key], P[key][o0:o1]), key
+        assert np.array_equal(Pb["bias"], P["bias"][o0:o1]) and np.array_equal(Pb["s"], P["s"]) and np.array_equal(Pb["b"], P["b"])
+    for arith, kw in (("exact", {}), ("folded", {}), ("folded", dict(rounded=True)), ("folded", dict(round_sx=False))):
+        m, a = am.model(P, x, arith, **kw)
+        got = list(am.model_blocks(L, x, arith, limit, **kw))
+        assert [r for r, _, _ in got] == [b[1] for b in blocks]
+        assert np.array_equal(np.concatenate([mb for _, mb, _ in got], axis=1), m), arith
+        assert np.array_equal(np.concatenate([ab for _, _, ab in got], axis=1), a), arith
+
+
+@pytest.mark.parametrize("dt,kr,rb", [("f16", 256, np.uint8), ("bf16", 512, np.uint16), ("f16", 0, None)])
+def test_v2_pieces_are_the_packed_layers_pieces(dt, kr, rb):
+    """pieces_v2 of a packed layer's own ids and tables (one codebook, no permutation: the same weights in the v2 wire format)
+    equals pieces(L) - c, r, s, b, bias and the exact W - so model() and check_outputs() take the v2 rows unchanged"""
+    I, O, v = 264, 72, 8
+    L = vo.make_layer(I, O, dist="ref-test", seed=9, dtype=dt, num_centroids=1024, num_res_centroids=kr, bias=True)
+    idx, ridx = vo.unpack_indices(L.indices, L.index_bits, I, L.res_bits, False)
+    P2 = am.pieces_v2(dt, I, O, v, idx[0].reshape(-1).astype(np.uint16), L.centroids, None if not kr else ridx[0].reshape(-1).astype(rb),
+                      L.res_centroids if kr else None, L.weight_scale.reshape(I, 1), L.weight_bias.reshape(I, 1), L.bias.reshape(1, O))
+    P = am.pieces(L)
+    for key in ("c", "r", "s", "b", "bias", "W"):
+        assert np.array_equal(P2[key], P[key]), key
+    x = _x(I, 2, dt, "dense", 1)
+    for arith in ("exact", "folded"):
+        assert all(np.array_equal(u, w) for u, w in zip(am.model(P2, x, arith), am.model(P, x, arith)))
+
+
+# ---------------------------------------------------------------------------------------------- bf16 gemv_lds: which arithmetic ran
+def _bf16_lds_rows():
+    import test_route_models_other_gpu as other
+    return [p for p in other.ALL_ROWS if p.values[0]["instance"].startswith("gemv_lds ") and p.values[0]["dt"] == "bf16"
+            and not p.values[0].get("big")]
+
+
+@pytest.mark.parametrize("e", _bf16_lds_rows())
+def test_bf16_lds_rows_tell_the_two_arithmetics_apart(e):
+    """gemv_lds computes bf16 in the folded form with s x unrounded and c + r kept in fp32; every bf16 row of it (packed and v2) must
+    be able to tell that from the reference's roundings: on the row's own planted input the exact model's values violate the
+    folded-unrounded bounds at some output, and the folded-unrounded model's values violate the exact bounds at some output (the
+    fp32 output's bounds: the row checks that output too)"""
+    import test_route_models_other_gpu as other
+    assert e["arith"] == "folded" and e["rounded"] is False and e["round_sx"] is False and e["x"] == "planted"
+    if e["entry"] == "v2":
+        P, perm = other.v2_pieces(e, other.v2_tensors(e)), None
+    else:
+        L = other.layer_of(e)
+        P, perm = am.pieces(L), L.perm
+    x, _ = other.x_of(e, perm)
+    mf, af = am.model(P, x, "folded", **other.FOLDED_UNROUNDED)
+    me, ae = am.model(P, x, "exact")
+    assert am.violations(me, mf, af, "bf16", True)[0].any(), "the exact values pass as folded-unrounded ones"
+    assert am.violations(mf, me, ae, "bf16", True)[0].any(), "the folded-unrounded values pass as exact ones"

@@ -38,7 +38,8 @@ def test_library_exports_every_declared_symbol_at_abi_11():
     assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "11"
     assert "vptq_quant_gemv_chain_plan" in syms
     # (added within ABI 11) which instantiation a call would launch
-    assert {"vptq_quant_gemv_instance", "vptq_quant_gemv_grouped_instance", "vptq_quant_gemv_chain_instance"} <= set(syms)
+    assert {"vptq_quant_gemv_instance", "vptq_quant_gemv_grouped_instance", "vptq_quant_gemv_chain_instance",
+            "vptq_quant_gemv_v2_instance"} <= set(syms)
 
 
 def test_ctypes_struct_layout_matches_header():

@@ -15,7 +15,11 @@ part test_table_instances_are_what_the_library_answers says so at its first row 
 
 The second half does the same for the sliced family - gemv_sliced, gemv_sliced_tok, gemv_hot - through
 vptq_quant_gemv_sliced_instance / _tokens_instance and the rows of tests/test_route_models_sliced_gpu.py (their launch shapes do
-not depend on the CU count: the layouts' rows per wave come with the layout structs)."""
+not depend on the CU count: the layouts' rows per wave come with the layout structs).
+
+The third part does it for the remaining families - gemv_gather, gemv_gatherx, gemv_generic, gemv_lds, gemv_lds_mfma and the v2
+entry's gemv_v2 - through vptq_quant_gemv_instance / vptq_quant_gemv_v2_instance and the rows of
+tests/test_route_models_other_gpu.py (gemv_lds' rows per row group depend on the CU count: 256 here)."""
 import ctypes as C
 import os
 
@@ -441,3 +445,229 @@ def test_sliced_instance_queries_validate_and_need_no_device():
     # the selective call: the pre-pass in front
     assert lib.vptq_quant_gemv_sliced_instance(descs, lay, 1, 1, SEL, buf, 512) == 0
     assert buf.value.startswith(b"gemv_hot dt=f16 v=8 | gemv_sliced ") and buf.value.endswith(b"corr=1")
+
+
+# ---------------------------------------------------------------------------------------------- the remaining families
+# gemv_gather, gemv_gatherx, gemv_generic, gemv_lds / gemv_lds_mfma (packed layers, vptq_quant_gemv_instance) and the v2 entry
+# (gemv_lds* with fmt=v2*, gemv_v2: vptq_quant_gemv_v2_instance), over fake descriptors built from a row's own fields - the grid
+# points are rows without an instance string - and held to the rows of tests/test_route_models_other_gpu.py.
+import test_route_models_other_gpu as other  # noqa: E402
+from test_route_models_gpu import GENERIC  # noqa: E402
+
+
+def _bits(n):
+    return (n - 1).bit_length() if n > 0 else 0
+
+
+def fake_other_desc(e):
+    """the descriptor spec_to_module + module_desc give for the layer of a packed row, with fake (aligned, never dereferenced)
+    pointers"""
+    d = B.LayerDesc()
+    I, O, v, C_, S = e["I"], e["O"], e["v"], e["C"], e["S"]
+    G = (I - S) // C_
+    ib, rb = _bits(e["k"]), _bits(e["kr"])
+    d.in_features, d.out_features, d.vector_len, d.num_codebooks, d.group_size = I, O, v, C_, G
+    d.num_centroids, d.num_res_centroids, d.index_bits, d.res_bits = e["k"], e["kr"], ib, rb
+    d.row_words, d.num_indices, d.dtype = (G * (ib + rb) + 31) // 32, (O + v - 1) // v, DTYPES[e["dt"]]
+    d.indices, d.centroids, d.res_centroids = 1 << 20, 2 << 20, (3 << 20 if e["kr"] else None)
+    if S:
+        d.outlier_size, d.outlier_vector_len, d.num_outlier_centroids = S, e["ov"], 256
+        d.num_outlier_indices = (O + e["ov"] - 1) // e["ov"]
+        d.outlier_indices, d.outlier_centroids = 9 << 20, 10 << 20
+    if e["norm"]:
+        d.weight_scale, d.weight_bias = 4 << 20, 5 << 20
+    if e["perm"]:
+        d.perm = 6 << 20
+        if e["norm"]:
+            d.scale_permuted, d.bias_permuted = 7 << 20, 8 << 20
+    if e["bias"]:
+        d.bias = 11 << 20
+    return d
+
+
+def fake_v2_desc(e):
+    d = B.V2Desc()
+    d.in_features, d.out_features, d.vector_len, d.num_centroids = e["I"], e["O"], e["v"], e["k"]
+    d.num_res_centroids, d.res_index_bytes, d.dtype = e["kr"], e["rb"], DTYPES[e["dt"]]
+    d.indices, d.centroids = 1 << 20, 2 << 20
+    if e["kr"]:
+        d.res_indices, d.res_centroids = 3 << 20, 4 << 20
+    if e["norm"]:
+        d.scale_weights, d.scale_bias = 5 << 20, 6 << 20
+    if e["bias"]:
+        d.bias = 7 << 20
+    return d
+
+
+def other_query(e):
+    """the instance string of the call a row (or a grid point) makes, or None where the library turns it down"""
+    buf = C.create_string_buffer(512)
+    if e["entry"] == "v2":
+        rc = B.lib().vptq_quant_gemv_v2_instance(fake_v2_desc(e), e["tokens"], e["flags"], buf, len(buf))
+    else:
+        rc = B.lib().vptq_quant_gemv_instance(fake_other_desc(e), e["tokens"], e["flags"], buf, len(buf))
+    return buf.value.decode() if rc == 0 else None
+
+
+OTHER_VIEWS = {
+    "gemv_gather": [("dt", "t", "rows", "tok", "perm", "wide"), ("tok", "tokens")],                 # every instantiation
+    "gemv_gatherx": [("dt", "v", "tok", "perm"), ("reslds", "v"), ("outl", "v"), ("groups",), ("tok", "tokens")],
+    "gemv_generic": [("dt", "v", "tok"), ("tok", "tokens")],
+    "gemv_lds": [("dt", "fmt", "tok"), ("rw", "tok"), ("dma", "fmt"), ("perm", "dt"), ("tok", "tokens")],
+    "gemv_lds_mfma": [("dt", "fmt"), ("rw",), ("dma", "fmt"), ("stages", "dt"), ("perm", "dt")],
+    "gemv_v2": [("dt", "v", "tok"), ("tok", "tokens")],
+}
+VIEWS.update(OTHER_VIEWS)
+# full template tuples (view 0) the enumeration must contain, as counted from the launch code
+OTHER_INSTANTIATIONS = {"gemv_gather": 68, "gemv_gatherx": 100, "gemv_generic": 56, "gemv_lds": 40, "gemv_lds_mfma": 16, "gemv_v2": 24}
+
+
+def other_cells_of(instance, tokens):
+    name, f = parse(instance)
+    if name not in OTHER_VIEWS:
+        return set()
+    f = dict(f, tokens=str(tokens) if tokens < 10 else "10+")   # (tokens past every family's slots twice over: one class)
+    return {(name, vi, tuple(f[k] for k in view)) for vi, view in enumerate(OTHER_VIEWS[name])}
+
+
+def _P(I, O, dt, tokens, **kw):
+    return other.R(I, O, dt, tokens, "?", **kw).values[0]
+
+
+def _Q(I, O, dt, tokens, **kw):
+    return other.V(I, O, dt, tokens, "?", **kw).values[0]
+
+
+# residual tables on both sides of the 32 KiB an LDS copy takes, per vector length (2 kr v bytes; not a multiple of 16: L2 as well)
+X_FORMATS = [(256, 0), (256, 16), (32768, 0), (65536, 2), (4096, 256), (32768, 256), (65536, 1024), (512, 2048), (32768, 4096),
+             (32768, 65536), (65536, 65536), (256, 16384), (1024, 2)]
+LDS_FORMATS = [(4096, 0), (1024, 4), (8192, 0), (4096, 256), (2048, 512), (4096, 512), (8192, 256), (8192, 512)]
+LDS_SHAPES = [(264, 60), (520, 60), (1032, 136), (264, 4804), (264, 8806), (264, 16804), (264, 32804)]
+
+
+def other_grid():
+    """the requests the census makes: row specs without an instance string (dtype x format x tokens 1 - 16 x perm x widths x
+    heights; the shapes that cannot be small only where they decide an axis)"""
+    for dt in DTYPES:
+        for tokens in range(1, 17):
+            for perm in (0, 1):
+                # k = 65536, v = 8: cache gathers; 2049 vector-rows (ROWS = 2) and 6152 columns (WIDE) at one token
+                for kr in (0, 256, 65536):
+                    for I, O in ((264, 72), (520, 100), (6136, 72), (6152, 72)) + (((264, 16392), (6152, 16392)) if tokens == 1 else ()):
+                        if I * O < (1 << 24) or kr == 256:
+                            yield _P(I, O, dt, tokens, k=65536, kr=kr, perm=perm, big=int(I * O > (1 << 24)))
+                # LDS-resident tables: every row-group height on 256 CUs
+                for k, kr in LDS_FORMATS:
+                    for I, O in LDS_SHAPES:
+                        for flags in (0, EXACT):
+                            yield _P(I, O, dt, tokens, k=k, kr=kr, perm=perm, flags=flags)
+                # L2 gathers of every other format; the generic kernel by flag
+                for v in (2, 4, 6, 8, 10, 12, 16):
+                    for k, kr in X_FORMATS:
+                        for I, O in ((260, 72), (520, 100), (1028, 72)):
+                            yield _P(I, O, dt, tokens, v=v, k=k, kr=kr, perm=perm)
+                    for C_ in (2, 4):
+                        yield _P(260 * C_, 100, dt, tokens, v=v, k=4096, kr=16, C=C_, perm=perm)
+                    for ov in ((v, 4) if v in (8, 12, 16) else (v,)):
+                        yield _P(520 + 8, 100 - 2, dt, tokens, v=v, k=32768, kr=16, S=8, ov=ov, perm=perm)
+                    for k, kr in ((256, 256), (4096, 4096)):
+                        yield _P(264, 100, dt, tokens, v=v, k=k, kr=kr, perm=perm, flags=GENERIC)
+            # the staging passes of the MFMA variant: 1024 vector-rows of more than 8192 / 24576 columns
+            if tokens == 1:
+                for I in (8200, 24584):
+                    yield _P(I, 8192, dt, 1, k=4096, kr=0, big=1)
+            # the v2 entry: LDS-resident up to k = 8192 at v = 8 (k not a multiple of 64: the main table through registers), else gemv_v2
+            if tokens < 16:
+                for v in (4, 8, 16):
+                    for k in (8192, 5000, 16384):
+                        for kr, rb in ((0, 0), (256, 1), (256, 2), (512, 2)):
+                            for I, O in ((264, 64), (520, 4800), (264, 8816)):
+                                for flags in (0, GENERIC):
+                                    if O > 64 and (v != 8 or flags or k > 8192):
+                                        continue   # (the heights matter to the LDS kernels' row groups only)
+                                    yield _Q(I, O, dt, tokens, v=v, k=k, kr=kr, rb=rb, flags=flags)
+
+
+def enumerate_other_cells():
+    cells = set()
+    for e in other_grid():
+        inst = other_query(e)
+        if inst:
+            cells |= other_cells_of(inst, e["tokens"])
+    return cells
+
+
+def other_table_cells():
+    cells = set()
+    for p in other.ALL_ROWS:
+        e = p.values[0]
+        cells |= other_cells_of(e["instance"], e["tokens"])
+    return cells
+
+
+# (kernel, view, cell, reason): enumerated cells of these families the tables leave out
+OTHER_NOT_COVERED = [
+]
+
+
+def test_other_tables_reach_every_instance_the_dispatch_produces(untuned):
+    want, have = enumerate_other_cells(), other_table_cells()
+    named = {(k, v, c) for k, v, c, _ in OTHER_NOT_COVERED}
+    assert all(reason for _, _, _, reason in OTHER_NOT_COVERED)
+    assert named <= want, f"OTHER_NOT_COVERED names cells the dispatch does not produce: {sorted(named - want)}"
+    assert not (named & have), f"OTHER_NOT_COVERED names covered cells: {sorted(named & have)}"
+    missing = want - have - named
+    assert not missing, f"{len(missing)} of {len(want)} instance cells without a row, e.g. {sorted(missing)[:12]}"
+    assert len(named) * 10 <= len(want), f"OTHER_NOT_COVERED holds {len(named)} of {len(want)} cells: more than 10 %"
+    for kernel, views in OTHER_VIEWS.items():   # no whole value of any axis is left out
+        for vi, view in enumerate(views):
+            for pos, axis in enumerate(view):
+                w = {c[pos] for k, v, c in want if k == kernel and v == vi}
+                h = {c[pos] for k, v, c in have if k == kernel and v == vi}
+                assert w <= h, f"{kernel}: no row with {axis} in {sorted(w - h)}"
+    # the instantiations counted from the launch code are in the enumeration (a census that lost a kernel would pass vacuously)
+    for kernel, count in OTHER_INSTANTIATIONS.items():
+        got = {c for k, v, c in want if k == kernel and v == 0}
+        assert len(got) == count, f"{kernel}: {len(got)} instantiations enumerated, {count} expected: {sorted(got)}"
+    assert {c[0] for k, v, c in want if k == "gemv_lds" and v == 1} == {"1", "2", "4", "8", "16"}
+    assert {c[0] for k, v, c in want if k == "gemv_lds_mfma" and v == 1} == {"4", "8", "16"}
+    assert {c[0] for k, v, c in want if k == "gemv_lds_mfma" and v == 3} == {"1", "2", "4"}
+    assert {c[0] for k, v, c in want if k == "gemv_lds" and v == 2} == {"0", "1"}
+    assert {c[0] for k, v, c in want if k == "gemv_gatherx" and v == 2} == {"0", "same", "4"}
+    assert {c[0] for k, v, c in want if k == "gemv_gatherx" and v == 3} == {"1", "2", "4"}
+
+
+def test_other_table_instances_are_what_the_library_answers(untuned):
+    """every row's instance string is the library's answer for a fake descriptor of the row's shape (the GPU test asserts the same
+    on the real layer), and the kernel-name query agrees on the kernel"""
+    # 1101 vector-rows: row groups of 4 on 256 CUs (276 groups), of 2 or 8 on parts with more or fewer
+    probe = parse(other_query(_P(264, 8806, "f16", 2, k=4096)))[1]
+    assert probe["rw"] == "4", "the tables are written for a 256-CU device (MI355X); this one has another CU count"
+    for p in other.ALL_ROWS:
+        e = p.values[0]
+        assert other_query(e) == e["instance"], p.id
+        if e["entry"] == "packed":
+            name = B.lib().vptq_quant_gemv_kernel_name(fake_other_desc(e), e["tokens"], e["flags"]).decode()
+            assert name == e["instance"].split()[0] + "_kernel", p.id
+
+
+def test_other_instance_queries_validate_and_need_no_device():
+    lib = B.lib()
+    buf = C.create_string_buffer(256)
+    d = fake_v2_desc(_Q(264, 64, "f16", 1, k=8192, kr=256))
+    assert lib.vptq_quant_gemv_v2_instance(d, 1, 0, buf, 256) == 0 and buf.value.startswith(b"gemv_lds dt=f16 fmt=v2u8 tok=1 rw=1 ")
+    assert lib.vptq_quant_gemv_v2_instance(d, 1, GENERIC, buf, 256) == 0 and buf.value == b"gemv_v2 dt=f16 v=8 tok=1"
+    assert lib.vptq_quant_gemv_v2_instance(d, 1, 0, buf, 8) == B.E_WORKSPACE
+    assert lib.vptq_quant_gemv_v2_instance(d, 1, 0, None, 256) == B.E_NULL
+    assert lib.vptq_quant_gemv_v2_instance(None, 1, 0, buf, 256) == B.E_NULL
+    assert lib.vptq_quant_gemv_v2_instance(d, 0, 0, buf, 256) == B.E_TOKENS
+    assert lib.vptq_quant_gemv_v2_instance(d, 16, 0, buf, 256) == B.E_TOKENS
+    d.vector_len = 6
+    assert lib.vptq_quant_gemv_v2_instance(d, 1, 0, buf, 256) == B.E_UNSUPPORTED
+    # every family's line starts with its kernel's name
+    for e in (_P(264, 72, "f16", 3, k=65536, kr=256), _P(264, 72, "bf16", 2, k=4096, kr=256), _P(260, 72, "f16", 1, v=6, k=4096),
+              _P(264, 72, "f16", 9, k=256, kr=256, flags=GENERIC), _P(264, 8806, "f16", 1, k=4096)):
+        fd = fake_other_desc(e)
+        name = lib.vptq_quant_gemv_kernel_name(fd, e["tokens"], e["flags"]).decode()
+        assert lib.vptq_quant_gemv_instance(fd, e["tokens"], e["flags"], buf, 256) == 0
+        assert name.split("_kernel")[0] == buf.value.decode().split()[0], (name, buf.value)

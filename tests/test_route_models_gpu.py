@@ -536,7 +536,8 @@ def test_row_parallel_partials_vs_column_range_model(world, dt, dev):
 REQUIRED = {"gemv_k256_kernel", "gemv_k256_kernel<fast>", "gemv_k256m_kernel", "gemv_k256m_kernel<fast>", "gemv_k256m_kernel<selective>",
             "gemv_k256c_kernel", "vptq_quant_gemv_grouped", "gemm_k256t_kernel", "gemm_k256_kernel", "vptq_quant_gemm",
             "gemv_lds_kernel", "gemv_lds_mfma_kernel", "gemv_gather_kernel", "gemv_gatherx_kernel", "gemv_generic_kernel",
-            "gemv_sliced_kernel", "gemv_sliced_tok_kernel", "gemv_hot_kernel", "row-parallel shards"}
+            "gemv_sliced_kernel", "gemv_sliced_tok_kernel", "gemv_hot_kernel", "row-parallel shards",
+            "gemv_v2_kernel", "vptq_quant_gemv_v2"}
 
 
 def _reached():
@@ -548,6 +549,13 @@ def _reached():
     for p in ONE_LAYER:
         e = p.values[0]
         add(e["route"], e["arith"], e["dt"], e["tokens"])
+    # (every instantiation of the remaining families and the v2 entry: tests/test_route_models_other_gpu.py)
+    import test_route_models_other_gpu as other
+    for p in other.ALL_ROWS:
+        e = p.values[0]
+        add(e["instance"].split()[0] + "_kernel", e["arith"], e["dt"], e["tokens"])
+        if e["entry"] == "v2":
+            add("vptq_quant_gemv_v2", e["instance"].split()[0], e["dt"], e["tokens"])
     for shapes, dt, tokens, flags, route, arith in GROUPS:
         add("vptq_quant_gemv_grouped", route, arith, dt, len(shapes), len({repr(sh) for sh in shapes}) == 1)
     for dt in ("f16", "bf16"):
@@ -598,6 +606,8 @@ def test_route_table_reaches_every_kernel():
     tok = r["gemv_sliced_tok_kernel"]
     assert {c[0] for c in tok} == {"folded", "EX"} and min(c[2] for c in tok) == 2 and max(c[2] for c in tok) == 8
     assert {c[0] for c in r["row-parallel shards"]} >= {2, 4}
+    assert {c[0] for c in r["vptq_quant_gemv_v2"]} == {"gemv_lds", "gemv_lds_mfma", "gemv_v2"}
+    assert {c[1] for c in r["gemv_v2_kernel"]} == {"f16", "bf16"} and {c[2] for c in r["gemv_v2_kernel"]} >= {1, 2, 3, 4, 7, 9}
 
 
 # ---------------------------------------------------------------------------------------------- the sliced entry points' flags

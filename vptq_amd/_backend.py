@@ -146,6 +146,7 @@ EXPORTS = {
     "vptq_quant_gemv_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "vptq_quant_gemv_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "vptq_quant_gemv_chain_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "vptq_quant_gemv_v2_instance": (C.c_int, [C.POINTER(V2Desc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     # ... and of the sliced entries (one token, single / grouped / column parts; 2 - 8 tokens): descs, layouts, n, tokens, flags
     "vptq_quant_gemv_sliced_instance": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, C.c_int, C.c_int, C.c_char_p,
                                                   C.c_size_t]),

@@ -164,6 +164,9 @@ static int batch_t_min_tokens(int dtype) {
   return v;
 }
 
+// gemv_lds.hip: every token of one call in the same arithmetic - the one-token MFMA form only for one-token calls
+static int lds_launch_flags(int tokens, int flags) { return tokens > 1 ? (flags | VPTQ_GEMV_EXACT) : flags; }
+
 // have_ws: the caller's workspace holds vptq_quant_gemv_workspace_bytes (kernel-name queries: assumed)
 static Route route_gemv(const VptqLayerDesc& d, int tokens, int flags, const void* x, bool have_ws) {
   const uintptr_t xa = (uintptr_t)x;   // 0 when unknown
@@ -268,8 +271,7 @@ int vptq_quant_gemv(const VptqLayerDesc* d, const void* x, void* y, int tokens, 
       return chunks(8, "gemv_gather launch", [&](const void* xc, void* yc, int m) {
         return vptq::launch_gemv_gather(*d, xc, yc, m, out_f32, st); });
     case kRouteLds: {
-      // every token of one call in the same arithmetic: the one-token MFMA form only for one-token calls
-      const int lflags = tokens > 1 ? (flags | VPTQ_GEMV_EXACT) : flags;
+      const int lflags = lds_launch_flags(tokens, flags);
       return chunks(vptq::gemv_lds_max_chunk(d->dtype), "gemv_lds launch", [&](const void* xc, void* yc, int m) {
         return vptq::launch_gemv_lds(*d, xc, yc, m, out_f32, lflags, st); });
     }
@@ -370,6 +372,17 @@ int add_k256(Text& t, const VptqLayerDesc* descs, int n, int tokens, int flags) 
   return VPTQ_OK;
 }
 
+// a launch of gemv_lds.hip (packed or v2 layers)
+void add_lds(Text& t, const vptq::LdsDecision& D) {
+  if (!D.ok) { t.add("none"); return; }
+  if (D.mfma)
+    t.add("gemv_lds_mfma dt=%s fmt=%s rw=%d stages=%d dma=%d perm=%d", D.f16 ? "f16" : "bf16", vptq::gemv_lds_fmt_text(D.fmt), D.rw, D.stages,
+          (int)D.dma, (int)D.perm);
+  else
+    t.add("gemv_lds dt=%s fmt=%s tok=%d rw=%d dma=%d perm=%d", D.f16 ? "f16" : "bf16", vptq::gemv_lds_fmt_text(D.fmt), D.tok, D.rw, (int)D.dma,
+          (int)D.perm);
+}
+
 // what vptq_quant_gemv(d, tokens, flags) launches (the first launch of a call that is served in several)
 int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
   const int kflags = drop_redundant_selective(flags);
@@ -396,12 +409,34 @@ int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
     }
     case kRouteNone:
       return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d] for this layer", tokens, VPTQ_GEMV_MAX_TOKENS_ANY);
-    default: {   // the other families: their kernel's name (their instantiations are not reported yet)
-      const char* name = vptq_quant_gemv_kernel_name(&d, tokens, kflags);
-      t.add("%s", name ? name : "none");
+    // the other families: the first launch of the call, as vptq_quant_gemv's own switch chunks it
+    case kRouteGather: {
+      const vptq::GatherDecision D = vptq::gemv_gather_decide(d, tokens > 8 ? 8 : tokens);
+      t.add("gemv_gather dt=%s t=%d rows=%d tok=%d perm=%d wide=%d", dt_text(d.dtype), D.T, D.rows, D.tok, (int)D.perm, (int)D.wide);
+      return VPTQ_OK;
+    }
+    case kRouteLds: {
+      const int step = vptq::gemv_lds_max_chunk(d.dtype);
+      add_lds(t, vptq::gemv_lds_decide(d, tokens > step ? step : tokens, lds_launch_flags(tokens, flags)));
+      return VPTQ_OK;
+    }
+    case kRouteGatherX: {
+      const int step = vptq::gemv_gatherx_max_chunk(d);
+      const vptq::GatherXDecision D = vptq::gemv_gatherx_decide(d, tokens > step ? step : tokens);
+      t.add("gemv_gatherx dt=%s v=%d tok=%d perm=%d reslds=%d outl=", dt_text(d.dtype), D.v, D.tok, (int)D.perm, (int)D.res_lds);
+      if (D.ov == 0) t.add("0");
+      else if (D.ov == D.v) t.add("same");
+      else t.add("%d", D.ov);
+      t.add(" groups=%d", D.groups);
+      return VPTQ_OK;
+    }
+    case kRouteGeneric: {
+      const vptq::GenericDecision D = vptq::gemv_generic_decide(d, tokens > 8 ? 8 : tokens);
+      t.add("gemv_generic dt=%s v=%d tok=%d", dt_text(d.dtype), D.v, D.tok);
       return VPTQ_OK;
     }
   }
+  return fail(VPTQ_E_UNSUPPORTED, "instance: no route");
 }
 }  // namespace
 
@@ -1156,12 +1191,10 @@ int vptq_dequant(const VptqLayerDesc* d, void* W, void* stream) {
   return VPTQ_OK;
 }
 
-int vptq_quant_gemv_v2(const VptqV2Desc* d, const void* x, void* y, int tokens, int flags,
-                       void* stream) {
-  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+// the checks of vptq_quant_gemv_v2 and vptq_quant_gemv_v2_instance on the descriptor and the token count
+static int validate_v2(const VptqV2Desc* d, int tokens) {
   if (!d) return fail(VPTQ_E_NULL, "desc is NULL");
-  if (!d->indices || !d->centroids || !x || !y)
-    return fail(VPTQ_E_NULL, "indices / centroids / x / y is NULL");
+  if (!d->indices || !d->centroids) return fail(VPTQ_E_NULL, "indices / centroids is NULL");
   if (d->dtype != VPTQ_DTYPE_F16 && d->dtype != VPTQ_DTYPE_BF16)
     return fail(VPTQ_E_UNSUPPORTED, "dtype %d", d->dtype);
   // the reference instantiates v in {4, 8, 16} (csrc/dispatch_macros.h:12-89)
@@ -1182,13 +1215,27 @@ int vptq_quant_gemv_v2(const VptqV2Desc* d, const void* x, void* y, int tokens, 
   // reference: "tokens < 16" (vptq/ops/quant_gemm.py:338, csrc/quant_gemv_v2.cu:58)
   if (tokens < 1 || tokens >= 16)
     return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 15]", tokens);
+  return VPTQ_OK;
+}
+
+// ONE decision for vptq_quant_gemv_v2 and vptq_quant_gemv_v2_instance: codebooks LDS-resident (what the reference's kernel does,
+// quant_gemv_v2.cuh:85-94), else gathered through L1 / L2 (x = NULL: assumed aligned)
+static bool v2_takes_lds(const VptqV2Desc& d, const void* x, int tokens, int flags) {
+  return !(flags & VPTQ_GEMV_FORCE_GENERIC) && vptq::gemv_lds_v2_eligible(d, tokens > 4 ? 4 : tokens) && (((uintptr_t)x) & 15) == 0;
+}
+
+int vptq_quant_gemv_v2(const VptqV2Desc* d, const void* x, void* y, int tokens, int flags,
+                       void* stream) {
+  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+  if (!d) return fail(VPTQ_E_NULL, "desc is NULL");
+  if (!d->indices || !d->centroids || !x || !y)
+    return fail(VPTQ_E_NULL, "indices / centroids / x / y is NULL");
+  if (const int rc = validate_v2(d, tokens)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t es = 2;
-  if (!(flags & VPTQ_GEMV_FORCE_GENERIC) && vptq::gemv_lds_v2_eligible(*d, tokens > 4 ? 4 : tokens) &&
-      (((uintptr_t)x) & 15) == 0) {
-    // codebooks LDS-resident (what the reference's kernel does, quant_gemv_v2.cuh:85-94)
+  if (v2_takes_lds(*d, x, tokens, flags)) {
     const int step = vptq::gemv_lds_max_chunk(d->dtype);
-    const int lflags = tokens > 1 ? (flags | VPTQ_GEMV_EXACT) : flags;
+    const int lflags = lds_launch_flags(tokens, flags);
     for (int t0 = 0; t0 < tokens; t0 += step) {
       const int m = tokens - t0 < step ? tokens - t0 : step;
       hipError_t e = vptq::launch_gemv_lds_v2(*d, (const char*)x + (size_t)t0 * d->in_features * es,
@@ -1206,6 +1253,21 @@ int vptq_quant_gemv_v2(const VptqV2Desc* d, const void* x, void* y, int tokens, 
     if (e != hipSuccess) return hip_fail(e, "gemv_v2 launch");
   }
   return VPTQ_OK;
+}
+
+int vptq_quant_gemv_v2_instance(const VptqV2Desc* d, int tokens, int flags, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_v2(d, tokens)) return rc;
+  Text t = {buf, bytes, 0, true};
+  if (v2_takes_lds(*d, nullptr, tokens, flags)) {
+    const int step = vptq::gemv_lds_max_chunk(d->dtype);
+    add_lds(t, vptq::gemv_lds_v2_decide(*d, tokens > step ? step : tokens, lds_launch_flags(tokens, flags)));
+  } else {
+    const vptq::V2Decision D = vptq::gemv_v2_decide(*d, tokens > 8 ? 8 : tokens);
+    t.add("gemv_v2 dt=%s v=%d tok=%d", D.f16 ? "f16" : "bf16", D.v, D.tok);
+  }
+  return text_done(t);
 }
 
 }  // extern "C"

@@ -216,51 +216,55 @@ bool gemv_gather_eligible(const VptqLayerDesc& d, int tokens) {
            (uintptr_t)d.bias_permuted | (uintptr_t)d.perm) & 3) == 0;
 }
 
-template <typename DT, int T, int ROWS, int TOK>
+// what one launch IS: the template arguments of gemv_gather_kernel<DT, T, ROWS, TOK, PERM, WIDE>, decided once for the launch and
+// for vptq_quant_gemv_instance (tokens: those of this launch, 1 ... 8)
+GatherDecision gemv_gather_decide(const VptqLayerDesc& d, int tokens) {
+  GatherDecision D = {};
+  D.f16 = d.dtype == VPTQ_DTYPE_F16;
+  D.perm = d.perm != nullptr;
+  D.T = gather_T(d);
+  // token slots per launch: 1, 2, 4 or 8 (5-8 tokens in ONE pass over the indices and gathers - the
+  // gathers, not the FMAs, bound these kernels: two launches of <= 4 tokens cost twice)
+  D.tok = tokens > 4 ? 8 : tokens > 2 ? 4 : tokens;
+  // ROWS = 2 amortises the per-column scale / bias / x loads when there are enough rows
+  D.rows = D.tok == 1 && d.num_indices >= 2048 ? 2 : 1;
+  // T = 24, one token: 8 elements per lane and piece: 8192^2 45.3 -> 42.3 us; loses on short rows (4096: two pieces)
+  D.wide = D.T == 24 && D.tok == 1 && d.group_size >= 6144;
+  return D;
+}
+
+template <typename DT, int T, int ROWS, int TOK, bool WIDE = false>
 static hipError_t launch_rt(const GatherParams& P, bool perm, hipStream_t st) {
   const dim3 grid((P.N + ROWS - 1) / ROWS), block(kGThreads);
   if (perm)
-    hipLaunchKernelGGL((gemv_gather_kernel<DT, T, ROWS, TOK, true>), grid, block, 0, st, P);
+    hipLaunchKernelGGL((gemv_gather_kernel<DT, T, ROWS, TOK, true, WIDE>), grid, block, 0, st, P);
   else
-    hipLaunchKernelGGL((gemv_gather_kernel<DT, T, ROWS, TOK, false>), grid, block, 0, st, P);
+    hipLaunchKernelGGL((gemv_gather_kernel<DT, T, ROWS, TOK, false, WIDE>), grid, block, 0, st, P);
   return hipGetLastError();
 }
 
 template <typename DT, int T>
-static hipError_t launch_t(const GatherParams& P, bool perm, hipStream_t st) {
-  // token slots per launch: 1, 2, 4 or 8 (5-8 tokens in ONE pass over the indices and gathers - the
-  // gathers, not the FMAs, bound these kernels: two launches of <= 4 tokens cost twice)
-  const int tok = P.tokens > 4 ? 8 : P.tokens > 2 ? 4 : P.tokens;
-  // ROWS = 2 amortises the per-column scale / bias / x loads when there are enough rows
-  if (tok == 1) {
+static hipError_t launch_t(const GatherParams& P, const GatherDecision& D, hipStream_t st) {
+  if (D.tok == 1) {
     if constexpr (T == 24) {
-      // 8 elements per lane and piece: 8192^2 45.3 -> 42.3 us; loses on short rows (4096: two pieces)
-      if (P.G >= 6144) {
-        const dim3 grid((P.N + (P.N >= 2048 ? 2 : 1) - 1) / (P.N >= 2048 ? 2 : 1)), block(kGThreads);
-        if (P.N >= 2048) {
-          if (perm) hipLaunchKernelGGL((gemv_gather_kernel<DT, 24, 2, 1, true, true>), grid, block, 0, st, P);
-          else hipLaunchKernelGGL((gemv_gather_kernel<DT, 24, 2, 1, false, true>), grid, block, 0, st, P);
-        } else {
-          if (perm) hipLaunchKernelGGL((gemv_gather_kernel<DT, 24, 1, 1, true, true>), grid, block, 0, st, P);
-          else hipLaunchKernelGGL((gemv_gather_kernel<DT, 24, 1, 1, false, true>), grid, block, 0, st, P);
-        }
-        return hipGetLastError();
-      }
+      if (D.wide) return D.rows == 2 ? launch_rt<DT, 24, 2, 1, true>(P, D.perm, st) : launch_rt<DT, 24, 1, 1, true>(P, D.perm, st);
     }
-    if (P.N >= 2048) return launch_rt<DT, T, 2, 1>(P, perm, st);
-    return launch_rt<DT, T, 1, 1>(P, perm, st);
+    if (D.wide) return hipErrorInvalidValue;
+    return D.rows == 2 ? launch_rt<DT, T, 2, 1>(P, D.perm, st) : launch_rt<DT, T, 1, 1>(P, D.perm, st);
   }
-  if (tok == 2) return launch_rt<DT, T, 1, 2>(P, perm, st);
-  if (tok == 4) return launch_rt<DT, T, 1, 4>(P, perm, st);
-  return launch_rt<DT, T, 1, 8>(P, perm, st);
+  if (D.rows != 1 || D.wide) return hipErrorInvalidValue;
+  if (D.tok == 2) return launch_rt<DT, T, 1, 2>(P, D.perm, st);
+  if (D.tok == 4) return launch_rt<DT, T, 1, 4>(P, D.perm, st);
+  if (D.tok == 8) return launch_rt<DT, T, 1, 8>(P, D.perm, st);
+  return hipErrorInvalidValue;
 }
 
 template <typename DT>
-static hipError_t launch_dt(const GatherParams& P, int T, bool perm, hipStream_t st) {
-  switch (T) {
-    case 16: return launch_t<DT, 16>(P, perm, st);
-    case 24: return launch_t<DT, 24>(P, perm, st);
-    case 32: return launch_t<DT, 32>(P, perm, st);
+static hipError_t launch_dt(const GatherParams& P, const GatherDecision& D, hipStream_t st) {
+  switch (D.T) {
+    case 16: return launch_t<DT, 16>(P, D, st);
+    case 24: return launch_t<DT, 24>(P, D, st);
+    case 32: return launch_t<DT, 32>(P, D, st);
     default: return hipErrorInvalidValue;
   }
 }
@@ -283,9 +287,8 @@ hipError_t launch_gemv_gather(const VptqLayerDesc& d, const void* x, void* y, in
   P.row_words = d.row_words;
   P.tokens = tokens;
   P.out_f32 = out_f32 ? 1 : 0;
-  const int T = gather_T(d);
-  return d.dtype == VPTQ_DTYPE_F16 ? launch_dt<F16>(P, T, d.perm != nullptr, st)
-                                   : launch_dt<BF16>(P, T, d.perm != nullptr, st);
+  const GatherDecision D = gemv_gather_decide(d, tokens);
+  return D.f16 ? launch_dt<F16>(P, D, st) : launch_dt<BF16>(P, D, st);
 }
 
 }  // namespace vptq

@@ -333,6 +333,22 @@ bool gemv_gatherx_eligible(const VptqLayerDesc& d, int tokens) {
            (uintptr_t)d.scale_permuted | (uintptr_t)d.bias_permuted | (uintptr_t)d.perm) & 3) == 0;
 }
 
+// what one launch IS: the template arguments of gemv_gatherx_kernel<DT, V, TOK, PERM> and the runtime forks inside it, decided once
+// for the launch and for vptq_quant_gemv_instance (tokens: those of this launch, 1 ... gemv_gatherx_max_chunk)
+GatherXDecision gemv_gatherx_decide(const VptqLayerDesc& d, int tokens) {
+  GatherXDecision D = {};
+  D.f16 = d.dtype == VPTQ_DTYPE_F16;
+  D.perm = d.perm != nullptr;
+  D.v = d.vector_len;
+  D.tok = tokens > 4 ? 8 : tokens > 2 ? 4 : tokens;
+  // (12-half entries are read with 16 + 8 bytes from LDS as well: the table must hold whole 16-byte units)
+  const int res_bytes = d.num_res_centroids * d.vector_len * 2;
+  D.res_lds = res_bytes > 0 && res_bytes <= kXResLdsMax && (res_bytes % 16) == 0;
+  D.ov = d.outlier_size > 0 ? d.outlier_vector_len : 0;
+  D.groups = d.num_codebooks;
+  return D;
+}
+
 template <typename DT, int V, int TOK>
 static hipError_t launch_x(const GatherXParams& P, bool perm, hipStream_t st) {
   const dim3 grid(P.N), block(kXThreads);
@@ -343,25 +359,26 @@ static hipError_t launch_x(const GatherXParams& P, bool perm, hipStream_t st) {
 }
 
 template <typename DT, int V>
-static hipError_t launch_xv(const GatherXParams& P, bool perm, hipStream_t st) {
-  const int tok = P.tokens > 4 ? 8 : P.tokens > 2 ? 4 : P.tokens;
-  if (tok == 1) return launch_x<DT, V, 1>(P, perm, st);
-  if (tok == 2) return launch_x<DT, V, 2>(P, perm, st);
-  if (tok == 4) return launch_x<DT, V, 4>(P, perm, st);
-  if constexpr (V <= 8) return launch_x<DT, V, 8>(P, perm, st);
+static hipError_t launch_xv(const GatherXParams& P, const GatherXDecision& D, hipStream_t st) {
+  if (D.tok == 1) return launch_x<DT, V, 1>(P, D.perm, st);
+  if (D.tok == 2) return launch_x<DT, V, 2>(P, D.perm, st);
+  if (D.tok == 4) return launch_x<DT, V, 4>(P, D.perm, st);
+  if constexpr (V <= 8) {
+    if (D.tok == 8) return launch_x<DT, V, 8>(P, D.perm, st);
+  }
   return hipErrorInvalidValue;
 }
 
 template <typename DT>
-static hipError_t launch_xdt(const GatherXParams& P, int v, bool perm, hipStream_t st) {
-  switch (v) {
-    case 2: return launch_xv<DT, 2>(P, perm, st);
-    case 4: return launch_xv<DT, 4>(P, perm, st);
-    case 6: return launch_xv<DT, 6>(P, perm, st);
-    case 8: return launch_xv<DT, 8>(P, perm, st);
-    case 10: return launch_xv<DT, 10>(P, perm, st);
-    case 12: return launch_xv<DT, 12>(P, perm, st);
-    case 16: return launch_xv<DT, 16>(P, perm, st);
+static hipError_t launch_xdt(const GatherXParams& P, const GatherXDecision& D, hipStream_t st) {
+  switch (D.v) {
+    case 2: return launch_xv<DT, 2>(P, D, st);
+    case 4: return launch_xv<DT, 4>(P, D, st);
+    case 6: return launch_xv<DT, 6>(P, D, st);
+    case 8: return launch_xv<DT, 8>(P, D, st);
+    case 10: return launch_xv<DT, 10>(P, D, st);
+    case 12: return launch_xv<DT, 12>(P, D, st);
+    case 16: return launch_xv<DT, 16>(P, D, st);
     default: return hipErrorInvalidValue;
   }
 }
@@ -382,19 +399,16 @@ hipError_t launch_gemv_gatherx(const VptqLayerDesc& d, const void* x, void* y, i
   P.oidx = d.outlier_size > 0 ? (const uint16_t*)d.outlier_indices : nullptr;
   P.ocent = d.outlier_size > 0 ? (const char*)d.outlier_centroids : nullptr;
   P.S = d.outlier_size;
-  P.ov = d.outlier_size > 0 ? d.outlier_vector_len : 0;
+  P.ov = d.outlier_size > 0 ? d.outlier_vector_len : 0;   // (= gemv_gatherx_decide's ov)
   P.M = d.outlier_size > 0 ? d.num_outlier_indices : 0;
   P.N = d.num_indices; P.G = d.group_size; P.C = d.num_codebooks; P.I = d.in_features; P.O = d.out_features;
   P.row_words = d.row_words;
   P.k = d.num_centroids; P.kr = d.num_res_centroids; P.ib = d.index_bits; P.rb = d.res_bits;
   P.tokens = tokens;
   P.out_f32 = out_f32 ? 1 : 0;
-  // (12-half entries are read with 16 + 8 bytes from LDS as well: the table must hold whole 16-byte units)
-  const int res_bytes = d.num_res_centroids * d.vector_len * 2;
-  P.res_lds = (res_bytes > 0 && res_bytes <= kXResLdsMax && (res_bytes % 16) == 0) ? 1 : 0;
-  const bool perm = d.perm != nullptr;
-  const int v = d.vector_len;
-  return d.dtype == VPTQ_DTYPE_F16 ? launch_xdt<F16>(P, v, perm, st) : launch_xdt<BF16>(P, v, perm, st);
+  const GatherXDecision D = gemv_gatherx_decide(d, tokens);
+  P.res_lds = D.res_lds ? 1 : 0;
+  return D.f16 ? launch_xdt<F16>(P, D, st) : launch_xdt<BF16>(P, D, st);
 }
 
 }  // namespace vptq

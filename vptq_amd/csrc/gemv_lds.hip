@@ -774,22 +774,40 @@ static bool lds_use_mfma(const LdsParams& P, int RW, bool exact) {
          lds_mfma_bytes(P.k, P.kr, P.G) <= kLMaxLds && (((uintptr_t)P.x | (uintptr_t)P.scale | (uintptr_t)P.wbias_plain | (uintptr_t)P.perm) & 15) == 0;
 }
 
-// common tail: row-group geometry + launch (tokens <= 4 per launch)
-static hipError_t launch_lds(LdsParams& P, int fmt, bool f16, bool exact, hipStream_t st) {
-  if (!f16 && P.tokens > 2) return hipErrorInvalidValue;  // (bf16: 2 token slots, see gemv_lds_max_chunk)
-  const int tok = P.tokens > 2 ? 4 : P.tokens;
-  const int lds = lds_bytes(P.k, P.kr, tok);
-  if (lds > kLMaxLds || !lds_fmt_ok(fmt)) return hipErrorInvalidValue;
+// what one launch IS (tokens <= 4 per launch): which of the two kernels, its template arguments <DT, FMT, TOK> / <DT, FMT>, the
+// row-group geometry and the runtime forks inside the kernels - decided once for the launch, for gemv_lds_name and for
+// vptq_quant_gemv_instance / vptq_quant_gemv_v2_instance (P.x = NULL there: the activations are assumed aligned)
+static LdsDecision lds_decide(const LdsParams& P, int fmt, bool f16, bool exact) {
+  LdsDecision D = {};
+  D.f16 = f16;
+  D.fmt = fmt;
+  D.perm = P.perm != nullptr;
+  if (P.tokens < 1 || P.tokens > (f16 ? 4 : 2)) return D;  // (bf16: 2 token slots, see gemv_lds_max_chunk)
+  D.tok = P.tokens > 2 ? 4 : P.tokens;
+  D.lds = lds_bytes(P.k, P.kr, D.tok);
+  if (D.lds > kLMaxLds || !lds_fmt_ok(fmt)) return D;
   const int cus = lds_cus();
-  const int RW = lds_rows_per_group(P.N);
-  P.RW = RW;
-  P.n_groups = (P.N + RW - 1) / RW;
-  const int grid = P.n_groups < cus ? P.n_groups : cus;
-  if (lds_use_mfma(P, RW, exact)) {
-    const int ldsm = lds_mfma_bytes(P.k, P.kr, P.G);
-    return f16 ? launch_lds_mfma_dt<F16>(P, fmt, grid, ldsm, st) : launch_lds_mfma_dt<BF16>(P, fmt, grid, ldsm, st);
+  D.rw = lds_rows_per_group(P.N);
+  D.n_groups = (P.N + D.rw - 1) / D.rw;
+  D.grid = D.n_groups < cus ? D.n_groups : cus;
+  D.dma = VPTQ_LDS_DMA && (P.k & 63) == 0;   // the kernels' own test: the main table by LDS-DMA, else through registers
+  D.mfma = lds_use_mfma(P, D.rw, exact);
+  if (D.mfma) {
+    D.lds = lds_mfma_bytes(P.k, P.kr, P.G);
+    D.stages = (P.G + kLThreads * 8 - 1) / (kLThreads * 8);   // staging passes of 8192 columns that hold columns
   }
-  return f16 ? launch_lds_dt<F16>(P, fmt, tok, grid, lds, st) : launch_lds_dt<BF16>(P, fmt, tok, grid, lds, st);
+  D.ok = true;
+  return D;
+}
+
+// common tail: row-group geometry + launch
+static hipError_t launch_lds(LdsParams& P, const LdsDecision& D, hipStream_t st) {
+  if (!D.ok) return hipErrorInvalidValue;
+  P.RW = D.rw;
+  P.n_groups = D.n_groups;
+  if (D.mfma)
+    return D.f16 ? launch_lds_mfma_dt<F16>(P, D.fmt, D.grid, D.lds, st) : launch_lds_mfma_dt<BF16>(P, D.fmt, D.grid, D.lds, st);
+  return D.f16 ? launch_lds_dt<F16>(P, D.fmt, D.tok, D.grid, D.lds, st) : launch_lds_dt<BF16>(P, D.fmt, D.tok, D.grid, D.lds, st);
 }
 
 // tokens one launch takes: 4 (fp16) / 2 (bf16)
@@ -810,16 +828,8 @@ bool gemv_lds_eligible(const VptqLayerDesc& d, int tokens, int flags) {
   return tokens >= 1 && tokens <= 4;
 }
 
-// which of the two kernels a one-call launch of `tokens` tokens takes (host logic, no launch)
-const char* gemv_lds_name(const VptqLayerDesc& d, int tokens, int flags) {
-  LdsParams P = {};
-  P.k = d.num_centroids; P.kr = d.num_res_centroids; P.G = d.group_size; P.tokens = tokens;
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0 || tokens > 1;
-  return lds_use_mfma(P, lds_rows_per_group(d.num_indices), exact) ? "gemv_lds_mfma_kernel" : "gemv_lds_kernel";
-}
-
-hipError_t launch_gemv_lds(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
-                           int flags, hipStream_t st) {
+// the kernels' parameters for one launch over a packed layer / a v2 layer (x, y: NULL for the host-only queries)
+static LdsParams lds_params(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32) {
   LdsParams P = {};
   P.idx = (const uint32_t*)d.indices;
   P.ridx = nullptr;
@@ -836,20 +846,10 @@ hipError_t launch_gemv_lds(const VptqLayerDesc& d, const void* x, void* y, int t
   P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
   P.k = d.num_centroids; P.kr = d.num_res_centroids; P.ib = d.index_bits; P.rb = d.res_bits;
   P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
-  return launch_lds(P, d.index_bits + d.res_bits, d.dtype == VPTQ_DTYPE_F16, (flags & VPTQ_GEMV_EXACT) != 0, st);
+  return P;
 }
 
-bool gemv_lds_v2_eligible(const VptqV2Desc& d, int tokens) {
-  if (d.vector_len != 8 || d.num_centroids < 1 || d.num_centroids > 8192 || d.num_res_centroids > 512)
-    return false;
-  if ((d.in_features & 7) || lds_bytes(d.num_centroids, d.num_res_centroids, 4) > kLMaxLds) return false;
-  if ((((uintptr_t)d.centroids | (uintptr_t)d.res_centroids | (uintptr_t)d.indices) & 15) != 0) return false;
-  if (d.num_res_centroids > 0 && (((uintptr_t)d.res_indices) & 7) != 0) return false;
-  return tokens >= 1 && tokens <= 4;
-}
-
-hipError_t launch_gemv_lds_v2(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32,
-                              int flags, hipStream_t st) {
+static LdsParams lds_params_v2(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32) {
   LdsParams P = {};
   P.idx = (const uint32_t*)d.indices;
   P.ridx = d.num_res_centroids > 0 ? d.res_indices : nullptr;
@@ -866,8 +866,64 @@ hipError_t launch_gemv_lds_v2(const VptqV2Desc& d, const void* x, void* y, int t
   P.k = d.num_centroids; P.kr = d.num_res_centroids > 0 ? d.num_res_centroids : 0;
   P.ib = 16; P.rb = 0;
   P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
-  const int fmt = d.num_res_centroids <= 0 ? kFmtV2None : d.res_index_bytes == 1 ? kFmtV2U8 : kFmtV2U16;
-  return launch_lds(P, fmt, d.dtype == VPTQ_DTYPE_F16, (flags & VPTQ_GEMV_EXACT) != 0, st);
+  return P;
+}
+
+static int lds_v2_fmt(const VptqV2Desc& d) {
+  return d.num_res_centroids <= 0 ? kFmtV2None : d.res_index_bytes == 1 ? kFmtV2U8 : kFmtV2U16;
+}
+
+// tokens, flags: those of ONE launch (the entries hand 2 - 4 tokens over with VPTQ_GEMV_EXACT set); x: NULL = assumed aligned
+LdsDecision gemv_lds_decide(const VptqLayerDesc& d, int tokens, int flags, const void* x) {
+  const LdsParams P = lds_params(d, x, nullptr, tokens, false);
+  return lds_decide(P, d.index_bits + d.res_bits, d.dtype == VPTQ_DTYPE_F16, (flags & VPTQ_GEMV_EXACT) != 0);
+}
+
+LdsDecision gemv_lds_v2_decide(const VptqV2Desc& d, int tokens, int flags, const void* x) {
+  const LdsParams P = lds_params_v2(d, x, nullptr, tokens, false);
+  return lds_decide(P, lds_v2_fmt(d), d.dtype == VPTQ_DTYPE_F16, (flags & VPTQ_GEMV_EXACT) != 0);
+}
+
+// FMT as the instance strings name it: the packed stream's T, or v2 / v2u8 / v2u16
+const char* gemv_lds_fmt_text(int fmt) {
+  switch (fmt) {
+    case 12: return "12";
+    case 13: return "13";
+    case 20: return "20";
+    case 21: return "21";
+    case 22: return "22";
+    case kFmtV2None: return "v2";
+    case kFmtV2U8: return "v2u8";
+    case kFmtV2U16: return "v2u16";
+    default: return "?";
+  }
+}
+
+// which of the two kernels a one-call launch of `tokens` tokens takes (host logic, no launch)
+const char* gemv_lds_name(const VptqLayerDesc& d, int tokens, int flags) {
+  const int m = tokens > gemv_lds_max_chunk(d.dtype) ? gemv_lds_max_chunk(d.dtype) : tokens;
+  return gemv_lds_decide(d, m, tokens > 1 ? (flags | VPTQ_GEMV_EXACT) : flags, nullptr).mfma ? "gemv_lds_mfma_kernel" : "gemv_lds_kernel";
+}
+
+hipError_t launch_gemv_lds(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
+                           int flags, hipStream_t st) {
+  LdsParams P = lds_params(d, x, y, tokens, out_f32);
+  return launch_lds(P, lds_decide(P, d.index_bits + d.res_bits, d.dtype == VPTQ_DTYPE_F16, (flags & VPTQ_GEMV_EXACT) != 0), st);
+}
+
+bool gemv_lds_v2_eligible(const VptqV2Desc& d, int tokens) {
+  if (d.vector_len != 8 || d.num_centroids < 1 || d.num_centroids > 8192 || d.num_res_centroids > 512)
+    return false;
+  if ((d.in_features & 7) || lds_bytes(d.num_centroids, d.num_res_centroids, 4) > kLMaxLds) return false;
+  if ((((uintptr_t)d.centroids | (uintptr_t)d.res_centroids | (uintptr_t)d.indices) & 15) != 0) return false;
+  if (d.num_res_centroids > 0 && (((uintptr_t)d.res_indices) & 7) != 0) return false;
+  return tokens >= 1 && tokens <= 4;
+}
+
+hipError_t launch_gemv_lds_v2(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32,
+                              int flags, hipStream_t st) {
+  LdsParams P = lds_params_v2(d, x, y, tokens, out_f32);
+  return launch_lds(P, lds_decide(P, lds_v2_fmt(d), d.dtype == VPTQ_DTYPE_F16, (flags & VPTQ_GEMV_EXACT) != 0), st);
 }
 
 }  // namespace vptq

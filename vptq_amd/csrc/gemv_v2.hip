@@ -90,38 +90,48 @@ __global__ __launch_bounds__(256) void gemv_v2_kernel(const VptqV2Desc d,
   }
 }
 
+// what one launch IS: the template arguments of gemv_v2_kernel<DT, V, TOK>, decided once for the launch and for
+// vptq_quant_gemv_v2_instance (tokens: those of this launch, 1 ... 8)
+V2Decision gemv_v2_decide(const VptqV2Desc& d, int tokens) {
+  V2Decision D = {};
+  D.f16 = d.dtype == VPTQ_DTYPE_F16;
+  D.v = d.vector_len;
+  D.tok = tokens > 4 ? 8 : tokens > 2 ? 4 : tokens;
+  return D;
+}
+
 template <typename DT, int V>
-static hipError_t launch_v(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32,
+static hipError_t launch_v(const VptqV2Desc& d, const V2Decision& D, const void* x, void* y, int tokens, bool out_f32,
                            hipStream_t st) {
   dim3 grid((d.out_features + V - 1) / V), block(256);
   const uint16_t* xp = (const uint16_t*)x;
   uint16_t* yp = (uint16_t*)y;
-  if (tokens == 1)
-    hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 1>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32);
-  else if (tokens == 2)
-    hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 2>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32);
-  else if (tokens <= 4)
-    hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 4>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32);
-  else
-    hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 8>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32);
+  switch (D.tok) {
+    case 1: hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 1>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32); break;
+    case 2: hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 2>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32); break;
+    case 4: hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 4>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32); break;
+    case 8: hipLaunchKernelGGL((gemv_v2_kernel<DT, V, 8>), grid, block, 0, st, d, xp, yp, tokens, (int)out_f32); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
 template <typename DT>
-static hipError_t launch_dt(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32,
+static hipError_t launch_dt(const VptqV2Desc& d, const V2Decision& D, const void* x, void* y, int tokens, bool out_f32,
                             hipStream_t st) {
-  switch (d.vector_len) {
-    case 4: return launch_v<DT, 4>(d, x, y, tokens, out_f32, st);
-    case 8: return launch_v<DT, 8>(d, x, y, tokens, out_f32, st);
-    case 16: return launch_v<DT, 16>(d, x, y, tokens, out_f32, st);
+  switch (D.v) {
+    case 4: return launch_v<DT, 4>(d, D, x, y, tokens, out_f32, st);
+    case 8: return launch_v<DT, 8>(d, D, x, y, tokens, out_f32, st);
+    case 16: return launch_v<DT, 16>(d, D, x, y, tokens, out_f32, st);
     default: return hipErrorInvalidValue;
   }
 }
 
 hipError_t launch_gemv_v2(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32,
                           hipStream_t st) {
-  return d.dtype == VPTQ_DTYPE_F16 ? launch_dt<F16>(d, x, y, tokens, out_f32, st)
-                                   : launch_dt<BF16>(d, x, y, tokens, out_f32, st);
+  if (tokens < 1 || tokens > 8) return hipErrorInvalidValue;
+  const V2Decision D = gemv_v2_decide(d, tokens);
+  return D.f16 ? launch_dt<F16>(d, D, x, y, tokens, out_f32, st) : launch_dt<BF16>(d, D, x, y, tokens, out_f32, st);
 }
 
 }  // namespace vptq

@@ -21,6 +21,28 @@ inline int device_cus() {
   return cus[dev];
 }
 
+// What one launch of the remaining GEMV families IS - the instantiation's template arguments and the launch-shape facts: each
+// family's *_decide is read by its launcher AND printed by vptq_quant_gemv_instance / vptq_quant_gemv_v2_instance (abi.hip), so the
+// text is the launch's own decision.  tokens (and flags): those of ONE launch, as the entries hand them over.
+struct GenericDecision { bool f16; int v, tok; };                         // gemv_generic_kernel<DT, V, TOK>
+struct V2Decision { bool f16; int v, tok; };                              // gemv_v2_kernel<DT, V, TOK>
+struct GatherDecision { bool f16, perm, wide; int T, rows, tok; };        // gemv_gather_kernel<DT, T, ROWS, TOK, PERM, WIDE>
+struct GatherXDecision {                                                  // gemv_gatherx_kernel<DT, V, TOK, PERM>
+  bool f16, perm, res_lds;   // res_lds: the residual table (<= 32 KiB) gathered from LDS, else from L2
+  int v, tok, ov, groups;    // ov: the outlier codebook's vector length (0: no outlier columns); codebook groups
+};
+struct LdsDecision {         // gemv_lds_kernel<DT, FMT, TOK> / gemv_lds_mfma_kernel<DT, FMT>
+  bool ok, mfma, f16, dma, perm;   // ok: a launch exists; dma: the main table copied by LDS-DMA (k a multiple of 64), else through registers
+  int fmt, tok, rw, n_groups, grid, lds, stages;   // rw vector-rows per row group; stages: staging passes of 8192 columns (MFMA kernel)
+};
+GenericDecision gemv_generic_decide(const VptqLayerDesc& d, int tokens);
+V2Decision gemv_v2_decide(const VptqV2Desc& d, int tokens);
+GatherDecision gemv_gather_decide(const VptqLayerDesc& d, int tokens);
+GatherXDecision gemv_gatherx_decide(const VptqLayerDesc& d, int tokens);
+LdsDecision gemv_lds_decide(const VptqLayerDesc& d, int tokens, int flags, const void* x = nullptr);   // x = NULL: assumed aligned
+LdsDecision gemv_lds_v2_decide(const VptqV2Desc& d, int tokens, int flags, const void* x = nullptr);
+const char* gemv_lds_fmt_text(int fmt);   // "12" ... "22", "v2", "v2u8", "v2u16"
+
 // gemv_generic.hip — every configuration
 hipError_t launch_gemv_generic(const VptqLayerDesc& d, const void* x, void* y, int tokens,
                                bool out_f32, hipStream_t st);
