@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VPTQ_ABI_VERSION 11
+#define VPTQ_ABI_VERSION 12
 
 #if defined(__GNUC__)
 #define VPTQ_API __attribute__((visibility("default")))
@@ -535,6 +535,19 @@ VPTQ_API int vptq_sliced_layout_fill(const VptqLayerDesc* desc, const VptqSliced
 
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
+/* Diagnostic (ABI 12): WHICH INSTANTIATION of dequant_kernel<DT, V, TAB> vptq_dequant(desc, W) would launch and which paths its
+ * threads take, as one line of `dequant key=value ...` - the launcher's own decision and the kernel's own predicates, evaluated on
+ * the host for the chunks of 8 columns of one vector-row.  Host logic: nothing is launched or dereferenced, no device is needed; W
+ * is read for its alignment only.
+ *   dequant dt=f16|bf16 v=2|4|6|8|10|12|16 tab=0|1|2 lds=N colblocks=N t=1..32 norm=vec|scalar|none store=vec|scalar
+ *       idx=vec:N,win:N,win5:N,elem:N perm=0|1 outl=0|N groups=N ragged=0|1
+ *       tab: both codebooks in LDS (1), the residual one only (2), neither (0); lds: bytes of LDS; colblocks: workgroups of 2048
+ *       columns per vector-row; t: bits per index element; norm: scale / bias as 16-byte loads, element loads, or absent; store: 16-byte
+ *       or element stores; idx: the chunks that read their 8 index elements as one 16-byte piece (vec), as two windows of 4 (win), the
+ *       same with a fifth word (win5), element by element (elem) - classes with no chunk are left out; outl: the outlier codebook's
+ *       vector length (0: no outlier columns); groups: codebook groups; ragged: in_features is no multiple of 8.
+ * Returns VPTQ_OK, vptq_dequant's own validation error, or VPTQ_E_WORKSPACE when buf (bytes long, NUL included) is too small. */
+VPTQ_API int vptq_dequant_instance(const VptqLayerDesc* desc, const void* W, char* buf, size_t bytes);
 
 VPTQ_API int vptq_quant_gemv_v2(const VptqV2Desc* desc, const void* x, void* y, int tokens,
                        int flags, void* stream);

@@ -30,10 +30,10 @@ def _family_desc(I, O, v, k, kr):
 def test_repack_symbol_is_exported_at_abi_11():
     hdr = open(os.path.join(ROOT, "include", "vptq_hip.h")).read()
     assert re.search(r"VPTQ_API int vptq_sliced_layout_repack\(", hdr)
-    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "11"
+    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "12"
     assert "vptq_sliced_layout_repack" in B.EXPORTS
     lib = B.lib()
-    assert lib.vptq_abi_version() == B.ABI_VERSION == 11
+    assert lib.vptq_abi_version() == B.ABI_VERSION == 12
     assert lib.vptq_sliced_layout_repack.argtypes == B.EXPORTS["vptq_sliced_layout_repack"][1]
 
 

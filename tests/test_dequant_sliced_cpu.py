@@ -31,10 +31,10 @@ def test_symbol_is_declared_exported_and_bound_at_abi_11():
     hdr = open(os.path.join(ROOT, "include", "vptq_hip.h")).read()
     assert re.search(r"VPTQ_API int vptq_dequant_sliced\(const VptqLayerDesc\* desc, const VptqSlicedLayout\* layouts, int parts, "
                      r"void\* W, void\* stream\);", hdr)
-    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "11"
+    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "12"
     assert "vptq_dequant_sliced" in B.EXPORTS
     lib = B.lib()
-    assert lib.vptq_abi_version() == B.ABI_VERSION == 11
+    assert lib.vptq_abi_version() == B.ABI_VERSION == 12
     assert lib.vptq_dequant_sliced.argtypes == B.EXPORTS["vptq_dequant_sliced"][1]
     assert lib.vptq_dequant_sliced.argtypes == B.EXPORTS["vptq_sliced_layout_repack"][1]   # (what repack takes, W for the indices)
 

@@ -86,6 +86,24 @@ def test_rows_past_out_features_are_not_stored(dt, dev):
     assert bool((_bits(buf[O:]) == 0x5a5a).all())
 
 
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("v,k,kr", [(8, 65536, 0), (8, 65536, 256), (16, 65536, 65536)], ids=lambda p: str(p))
+def test_special_values_against_the_oracle(v, k, kr, dt, dev):
+    """the kernel has its own arithmetic (and otherwise inherits its reference from vptq_dequant): the hand-written tables of
+    tests/_dequant_specials.py - signed zeros, subnormals, infinities, NaN, ties, overflow, underflow - against the oracle itself,
+    which tests/test_dequant_specials_cpu.py pins to torch's CPU arithmetic.  NaN by position, everything else by bits."""
+    import numpy as np
+    from oracle import vptq_oracle as vo
+    from _gpu_util import spec_to_module, tensor_to_bits
+    import _dequant_specials as sp
+    L = sp.special_layer(dt, v, k, kr)
+    with np.errstate(all="ignore"):
+        want = vo.dequant(L, ref_residual_mask_quirk=False)
+    got = SlicedGemv(spec_to_module(L, dev), exact=True).dequant()
+    torch.cuda.synchronize()
+    sp.same_bits(tensor_to_bits(got), want, dt, f"vptq_dequant_sliced v{v}-k{k}-{kr} {dt}")
+
+
 @pytest.mark.parametrize("I,O", [(1024, 264), (5384, 64)])
 def test_with_a_permutation(I, O, dev):
     m = _perm_layer(I, O, 8, 65536, 256, F16, seed=I + O, dev=dev)

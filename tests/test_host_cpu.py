@@ -23,8 +23,8 @@ def _declared_symbols():
 
 
 def test_library_exports_every_declared_symbol_at_abi_11():
-    """every symbol the header declares is exported and bound; ABI 11 (vptq_quant_gemv_chain_plan) in the header, the
-    library and the binding"""
+    """every symbol the header declares is exported and bound; the ABI version - 12 since vptq_dequant_instance (the test keeps the
+    name it had at 11) - is the same in the header, the library and the binding"""
     syms = _declared_symbols()
     assert len(syms) >= 8, syms
     assert os.path.exists(B.LIB_PATH), "build libvptq_hip.so first (__graft_entry__.build())"
@@ -33,13 +33,14 @@ def test_library_exports_every_declared_symbol_at_abi_11():
         assert hasattr(lib, s), f"{s} declared in include/vptq_hip.h but not exported"
     assert sorted(B.EXPORTS) == syms, "python binding table out of sync with the header"
     lib.vptq_abi_version.restype = ctypes.c_int
-    assert lib.vptq_abi_version() == B.ABI_VERSION == 11
+    assert lib.vptq_abi_version() == B.ABI_VERSION == 12
     hdr = open(os.path.join(ROOT, "include", "vptq_hip.h")).read()
-    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "11"
+    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "12"
     assert "vptq_quant_gemv_chain_plan" in syms
     # (added within ABI 11) which instantiation a call would launch
     assert {"vptq_quant_gemv_instance", "vptq_quant_gemv_grouped_instance", "vptq_quant_gemv_chain_instance",
             "vptq_quant_gemv_v2_instance"} <= set(syms)
+    assert "vptq_dequant_instance" in syms   # (ABI 12)
 
 
 def test_ctypes_struct_layout_matches_header():

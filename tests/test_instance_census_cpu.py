@@ -19,7 +19,10 @@ not depend on the CU count: the layouts' rows per wave come with the layout stru
 
 The third part does it for the remaining families - gemv_gather, gemv_gatherx, gemv_generic, gemv_lds, gemv_lds_mfma and the v2
 entry's gemv_v2 - through vptq_quant_gemv_instance / vptq_quant_gemv_v2_instance and the rows of
-tests/test_route_models_other_gpu.py (gemv_lds' rows per row group depend on the CU count: 256 here)."""
+tests/test_route_models_other_gpu.py (gemv_lds' rows per row group depend on the CU count: 256 here).
+
+The fourth part does it for vptq_dequant - dequant_kernel<DT, V, TAB> and the paths its threads take to their index elements - through
+vptq_dequant_instance and the rows of tests/test_dequant_models_gpu.py (nothing there depends on the CU count)."""
 import ctypes as C
 import os
 
@@ -671,3 +674,194 @@ def test_other_instance_queries_validate_and_need_no_device():
         name = lib.vptq_quant_gemv_kernel_name(fd, e["tokens"], e["flags"]).decode()
         assert lib.vptq_quant_gemv_instance(fd, e["tokens"], e["flags"], buf, 256) == 0
         assert name.split("_kernel")[0] == buf.value.decode().split()[0], (name, buf.value)
+
+
+# ---------------------------------------------------------------------------------------------- vptq_dequant
+# dequant_kernel<DT, V, TAB>: enumerated through vptq_dequant_instance over fake descriptors built from a row's own fields - the grid
+# points are rows without an instance string - and held to the rows of tests/test_dequant_models_gpu.py.  The line carries the launch
+# decision and, per path to a thread's 8 index elements, the chunks of one vector-row that take it (dequant_paths.h: the kernel's
+# own predicates).
+import test_dequant_models_gpu as dq  # noqa: E402
+
+DQ_LDS_MAX = 16384   # dequant_paths.h:kDqLdsMax - only to name the side of the limit a request's tables lie on
+
+
+def fake_dequant_desc(e):
+    """-> (descriptor, W): what module_desc gives for the layer of a dequant row, with fake (never dereferenced) pointers at the
+    row's alignments"""
+    d = B.LayerDesc()
+    I, O, v, C_, S = e["I"], e["O"], e["v"], e["C"], e["S"]
+    G = (I - S) // C_
+    ib, rb = _bits(e["k"]), _bits(e["kr"])
+    d.in_features, d.out_features, d.vector_len, d.num_codebooks, d.group_size = I, O, v, C_, G
+    d.num_centroids, d.num_res_centroids, d.index_bits, d.res_bits = e["k"], e["kr"], ib, rb
+    d.row_words, d.num_indices, d.dtype = (G * (ib + rb) + 31) // 32, (O + v - 1) // v, DTYPES[e["dt"]]
+    d.indices, d.centroids, d.res_centroids = (1 << 20) + e["idx_off"], 2 << 20, (3 << 20 if e["kr"] else None)
+    if S:
+        d.outlier_size, d.outlier_vector_len, d.num_outlier_centroids = S, e["ov"], 256
+        d.num_outlier_indices = (O + e["ov"] - 1) // e["ov"]
+        d.outlier_indices, d.outlier_centroids = 9 << 20, 10 << 20
+    if e["norm"]:
+        d.weight_scale, d.weight_bias = (4 << 20) + e["norm_off"], (5 << 20) + e["norm_off"]
+    if e["perm"]:
+        d.perm, d.inv_perm = 6 << 20, 7 << 20
+    return d, (16 << 20) + e["w_off"]
+
+
+def dequant_query(e):
+    d, W = fake_dequant_desc(e)
+    buf = C.create_string_buffer(512)
+    rc = B.lib().vptq_dequant_instance(d, W, buf, len(buf))
+    assert rc == 0, (rc, B.lib().vptq_last_error(), e)
+    return buf.value.decode()
+
+
+DEQUANT_VIEWS = [("dt", "v", "tab"),               # every instantiation
+                 ("t", "idxclasses"),              # the set of paths with a chunk, per index width
+                 ("norm", "store", "dt"), ("colblocks",), ("ragged", "dt"), ("perm", "outl", "groups"), ("lds_edge",)]
+DEQUANT_INSTANTIATIONS = 42   # 2 dtypes x 7 vector lengths x TAB 0 / 1 / 2 (dequant.hip: launch_dt, launch_v)
+
+
+def _side(nbytes):
+    return "none" if nbytes == 0 else "below" if nbytes < DQ_LDS_MAX else "at" if nbytes == DQ_LDS_MAX else "above"
+
+
+def dequant_cells_of(instance, e):
+    name, f = parse(instance)
+    assert name == "dequant"
+    f["idxclasses"] = "+".join(c.split(":")[0] for c in f["idx"].split(","))
+    f["colblocks"] = "1" if f["colblocks"] == "1" else "2+"
+    # which side of the LDS limit both tables together, and the residual table alone, lie on (of the REQUEST: the line says what came of it)
+    f["lds_edge"] = f"tab={f['tab']} both={_side((e['k'] + e['kr']) * e['v'] * 2)} res={_side(e['kr'] * e['v'] * 2)} groups={'1' if e['C'] == 1 else 'n'}"
+    return {("dequant", vi, tuple(f[k] for k in view)) for vi, view in enumerate(DEQUANT_VIEWS)}
+
+
+def _DQ(I, O, dt, **kw):
+    return dq.D(I, O, dt, "?", **kw).values[0]
+
+
+DQ_VECTOR_LENS = (2, 4, 6, 8, 10, 12, 16)
+# (k, kr): TAB 1 / 2 / 0 of every vector length, then both sides of the limit - 16384 bytes are (k + kr) v 2 = 512 entries at v = 16
+# and 1024 at v = 8
+DQ_FORMATS = [(256, 256), (65536, 256), (65536, 0), (512, 256), (65536, 512), (65536, 1024), (256, 0)]
+DQ_WIDTHS = [264, 8, 2040, 2048, 2056, 1001, 7]
+# (perm, S, ov, C, I): a permutation, outlier columns of length 4 and of the layer's, 2 / 4 groups of 136 (whole chunks) and of 132
+# columns, all of them together
+DQ_ELEMENT_CAUSES = [(1, 0, 0, 1, 264), (0, 12, 4, 1, 280), (0, 8, 8, 1, 272), (0, 0, 0, 2, 272), (0, 0, 0, 4, 544), (0, 0, 0, 2, 264),
+                     (0, 0, 0, 4, 528), (1, 8, 4, 2, 272)]
+DQ_ALIGNMENTS = [dict(), dict(w_off=2), dict(norm_off=2), dict(idx_off=4), dict(norm=0)]
+
+
+def split_bits(T):
+    """(k, kr) of an index width: the main table up to 16 bits, the residual one making up the rest"""
+    return 1 << min(T, 16), (1 << (T - 16)) if T > 16 else 0
+
+
+def dequant_grid():
+    """the requests the census makes: dtype x vector length x format, every index width 1 ... 32 x width, the causes of the
+    element path and the alignment variants at 16 and 24 bits"""
+    for dt in DTYPES:
+        for v in DQ_VECTOR_LENS:
+            for k, kr in DQ_FORMATS:
+                yield _DQ(264, 5 * v - 3, dt, v=v, k=k, kr=kr)
+            yield _DQ(272, 5 * v - 3, dt, v=v, k=256, kr=256, C=2)   # two groups whose tables would fit
+        for T in range(1, 33):
+            k, kr = split_bits(T)
+            for I in DQ_WIDTHS:
+                if dt == "f16" or I in (264, 2056, 1001):
+                    yield _DQ(I, 37, dt, k=k, kr=kr)
+            yield _DQ(264, 77, dt, v=16, k=k, kr=kr)
+        for k, kr in ((256, 16384), (512, 2048)):   # res_bits > index_bits
+            yield _DQ(264, 37, dt, k=k, kr=kr)
+        for kr in (0, 256):
+            for perm, S, ov, C_, I in DQ_ELEMENT_CAUSES:
+                yield _DQ(I, 37, dt, k=65536, kr=kr, perm=perm, S=S, ov=ov, C=C_)
+            for kw in DQ_ALIGNMENTS:
+                yield _DQ(264, 37, dt, k=65536, kr=kr, **kw)
+
+
+def enumerate_dequant_cells():
+    cells = set()
+    for e in dequant_grid():
+        cells |= dequant_cells_of(dequant_query(e), e)
+    return cells
+
+
+def dequant_table_cells():
+    cells = set()
+    for p in dq.ROWS:
+        e = p.values[0]
+        cells |= dequant_cells_of(e["instance"], e)
+    return cells
+
+
+# (kernel, view, cell, reason): enumerated cells of vptq_dequant the table leaves out
+DEQUANT_NOT_COVERED = [
+]
+
+
+def test_dequant_table_reaches_every_instance_the_launcher_produces():
+    want, have = enumerate_dequant_cells(), dequant_table_cells()
+    named = {(k, v, c) for k, v, c, _ in DEQUANT_NOT_COVERED}
+    assert all(reason for _, _, _, reason in DEQUANT_NOT_COVERED)
+    assert named <= want, f"DEQUANT_NOT_COVERED names cells the launcher does not produce: {sorted(named - want)}"
+    assert not (named & have), f"DEQUANT_NOT_COVERED names covered cells: {sorted(named & have)}"
+    missing = want - have - named
+    assert not missing, f"{len(missing)} of {len(want)} instance cells without a row, e.g. {sorted(missing)[:12]}"
+    assert len(named) * 10 <= len(want), f"DEQUANT_NOT_COVERED holds {len(named)} of {len(want)} cells: more than 10 %"
+    for vi, view in enumerate(DEQUANT_VIEWS):   # no whole value of any axis is left out
+        for pos, axis in enumerate(view):
+            w = {c[pos] for k, v, c in want if v == vi}
+            h = {c[pos] for k, v, c in have if v == vi}
+            assert w <= h, f"dequant: no row with {axis} in {sorted(w - h)}"
+    # the instantiations counted from the launcher are in the enumeration (a census that lost one would pass vacuously)
+    got = {c for k, v, c in want if v == 0}
+    assert len(got) == DEQUANT_INSTANTIATIONS and got == {(dt, str(v), str(tab)) for dt in DTYPES for v in DQ_VECTOR_LENS for tab in (0, 1, 2)}
+    # every index width occurs; the fifth-word windows at exactly four of them, the 16-byte piece at exactly one
+    paths = {}
+    for k, v, c in want:
+        if v == 1:
+            paths.setdefault(int(c[0]), set()).update(c[1].split("+"))
+    assert sorted(paths) == list(range(1, 33))
+    assert {t for t, p in paths.items() if "win5" in p} == {27, 29, 30, 31}
+    assert {t for t, p in paths.items() if "vec" in p} == {16}
+    assert {t for t, p in paths.items() if "win" in p} == set(range(1, 33)) - {16, 27, 29, 30, 31}
+    assert all("elem" in p for p in paths.values())
+    assert {c[0] for k, v, c in want if v == 3} == {"1", "2+"}
+    assert {c[:2] for k, v, c in want if v == 2} == {("vec", "vec"), ("vec", "scalar"), ("scalar", "vec"), ("scalar", "scalar"), ("none", "vec")}
+    edges = {c[0] for k, v, c in want if v == 6}
+    assert {"tab=1 both=at res=below groups=1", "tab=2 both=above res=at groups=1", "tab=0 both=above res=above groups=1",
+            "tab=0 both=below res=below groups=n", "tab=1 both=below res=none groups=1", "tab=0 both=above res=none groups=1"} <= edges
+
+
+def test_dequant_table_instances_are_what_the_library_answers():
+    """every row's instance string is the library's answer for a fake descriptor of the row's shape and alignments (the GPU test
+    asserts the same on the real layer): a change of the launcher or of a path predicate shows here first, without a GPU"""
+    assert len(dq.ROWS) >= DEQUANT_INSTANTIATIONS
+    for p in dq.ROWS:
+        e = p.values[0]
+        assert dequant_query(e) == e["instance"], p.id
+
+
+def test_dequant_instance_query_validates_and_needs_no_device():
+    lib = B.lib()
+    buf = C.create_string_buffer(256)
+    d, W = fake_dequant_desc(_DQ(4104, 37, "f16", k=65536, kr=256))
+    assert lib.vptq_dequant_instance(d, W, buf, 256) == 0
+    assert buf.value == (b"dequant dt=f16 v=8 tab=2 lds=4096 colblocks=3 t=24 norm=vec store=vec idx=win:512,elem:1 perm=0 outl=0 groups=1 "
+                         b"ragged=0")
+    assert lib.vptq_dequant_instance(d, W, buf, 8) == B.E_WORKSPACE and buf.value == b""
+    assert lib.vptq_dequant_instance(d, W, None, 256) == B.E_NULL
+    assert lib.vptq_dequant_instance(None, W, buf, 256) == B.E_NULL
+    # vptq_dequant's own validation in front: W, the inverse permutation, the layer
+    assert lib.vptq_dequant_instance(d, None, buf, 256) == B.E_NULL
+    d.perm = 6 << 20
+    assert lib.vptq_dequant_instance(d, W, buf, 256) == B.E_NULL and b"inv_perm" in lib.vptq_last_error()
+    d.inv_perm = 7 << 20
+    assert lib.vptq_dequant_instance(d, W, buf, 256) == 0 and b" idx=elem:513 perm=1 " in buf.value
+    d.vector_len = 5
+    assert lib.vptq_dequant_instance(d, W, buf, 256) == B.E_UNSUPPORTED
+    d.vector_len, d.row_words = 8, 10
+    assert lib.vptq_dequant_instance(d, W, buf, 256) == B.E_SHAPE
+    d.row_words, d.indices = 4104 * 24 // 32, (1 << 20) + 2
+    assert lib.vptq_dequant_instance(d, W, buf, 256) == B.E_ALIGN

@@ -31,9 +31,9 @@ def _spec(flags, slices, table=0, whole=0, side=0, parts=1, part=0):
 
 def test_builder_symbols_are_exported_at_abi_11():
     hdr = open(os.path.join(ROOT, "include", "vptq_hip.h")).read()
-    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "11"
+    assert re.search(r"#define VPTQ_ABI_VERSION (\d+)", hdr).group(1) == "12"
     lib = B.lib()
-    assert lib.vptq_abi_version() == B.ABI_VERSION == 11
+    assert lib.vptq_abi_version() == B.ABI_VERSION == 12
     for name in ("vptq_sliced_layout_plan", "vptq_sliced_layout_fill"):
         assert re.search(r"VPTQ_API int %s\(" % name, hdr), name
         assert name in B.EXPORTS

@@ -26,7 +26,7 @@ def tune_env(name: str, default=None):
     VPTQ_FUSED_GEMM_MAX_TOKENS, VPTQ_HIP_LIB (another build of the library)."""
     return os.environ.get(name, default) if os.environ.get("VPTQ_TUNING") == "1" else default
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 DTYPE_F16, DTYPE_BF16 = 0, 1
 GEMV_FAST_MATH = 1 << 0
 GEMV_FORCE_GENERIC = 1 << 1
@@ -108,6 +108,8 @@ EXPORTS = {
     "vptq_quant_gemv_chain_plan": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "vptq_dequant": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp]),
+    # (ABI 12) which instantiation of dequant_kernel vptq_dequant would launch and the paths its threads take, as text
+    "vptq_dequant_instance": (C.c_int, [C.POINTER(LayerDesc), _vp, C.c_char_p, C.c_size_t]),
     "vptq_sliced_layout_supported": (C.c_int, [C.POINTER(LayerDesc)]),
     "vptq_sliced_layout_tables": (C.c_int, [C.POINTER(LayerDesc)]),
     "vptq_sliced_layout_whole_table": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),

@@ -1180,14 +1180,31 @@ int vptq_quant_gemm(const VptqLayerDesc* d, const void* x, void* y, int tokens, 
   return VPTQ_OK;
 }
 
-int vptq_dequant(const VptqLayerDesc* d, void* W, void* stream) {
+// the checks of vptq_dequant and vptq_dequant_instance
+static int validate_dequant(const VptqLayerDesc* d, const void* W) {
   int rc = validate_layer(d);
   if (rc) return rc;
   if (!W) return fail(VPTQ_E_NULL, "W is NULL");
   if (d->perm && !d->inv_perm)
     return fail(VPTQ_E_NULL, "dequant needs inv_perm = argsort(perm) when perm is set");
+  return VPTQ_OK;
+}
+
+int vptq_dequant(const VptqLayerDesc* d, void* W, void* stream) {
+  if (const int rc = validate_dequant(d, W)) return rc;
   hipError_t e = vptq::launch_dequant(*d, W, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, "dequant launch");
+  return VPTQ_OK;
+}
+
+int vptq_dequant_instance(const VptqLayerDesc* d, const void* W, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_dequant(d, W)) return rc;
+  if (vptq::dequant_instance(*d, W, buf, bytes)) {
+    buf[0] = 0;
+    return fail(VPTQ_E_WORKSPACE, "instance: buffer of %zu bytes too small", bytes);
+  }
   return VPTQ_OK;
 }
 

@@ -6,6 +6,7 @@
 // permutation the READ side is the gather (inv_perm[j] -> index element), the write side
 // stays coalesced.
 #include "common.h"
+#include "dequant_paths.h"
 #include "kernels.h"
 
 namespace vptq {
@@ -28,7 +29,8 @@ namespace vptq {
 // gemv_gatherx.hip) - instead of two dword loads per element: for "v8-k65536-256" the kernel issued 42
 // lane addresses per 8 elements (16 of them index words, 8 residual gathers) and ran at exactly that pace,
 // 84 us per 8192^2 layer.
-constexpr int kDqLdsMax = 16384;
+// The launch decision (TAB, grid) and the path predicates (full, vec_norm, vec_idx, win_idx, need5): dequant_paths.h, shared with
+// dequant_instance below.
 
 typedef uint32_t dq_u32_a4 __attribute__((aligned(4)));
 typedef uint32_t dq_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
@@ -58,12 +60,11 @@ __global__ __launch_bounds__(256) void dequant_kernel(const VptqLayerDesc d,
   }
   if (j0 >= I) return;
   const int T = d.index_bits + d.res_bits;
-  const bool full = j0 + 8 <= I && (I & 7) == 0;  // 16-byte aligned, whole chunk inside the row
+  const bool full = dq_full(j0, I);  // 16-byte aligned, whole chunk inside the row
   // scale / bias of the 8 output columns: contiguous whatever the permutation - two 16-byte loads
   // instead of sixteen 2-byte ones (the kernel is paced by lane addresses, not bytes)
   u32x4 sv8 = {0, 0, 0, 0}, bv8 = {0, 0, 0, 0};
-  const bool vec_norm = full && d.weight_scale != nullptr &&
-                        ((((uintptr_t)d.weight_scale | (uintptr_t)d.weight_bias) & 15) == 0);
+  const bool vec_norm = dq_vec_norm(d, full);
   if (vec_norm) {
     sv8 = *(const u32x4*)((const uint16_t*)d.weight_scale + j0);
     bv8 = *(const u32x4*)((const uint16_t*)d.weight_bias + j0);
@@ -71,24 +72,21 @@ __global__ __launch_bounds__(256) void dequant_kernel(const VptqLayerDesc d,
   // 16-bit elements, no permutation, no outlier columns: the thread's 8 index elements are one
   // aligned 16-byte piece of the row
   u32x4 iw8 = {0, 0, 0, 0};
-  const bool vec_idx = full && T == 16 && !d.inv_perm && S == 0 && (G & 7) == 0 &&
-                       ((((uintptr_t)d.indices) & 15) == 0) && ((d.row_words & 3) == 0);
+  const bool vec_idx = dq_vec_idx(d, full, T);
   if (vec_idx) {
     const int cb = j0 / G, g = j0 - cb * G;
     iw8 = *(const u32x4*)((const uint32_t*)d.indices + ((size_t)cb * d.num_indices + n) * d.row_words + (g >> 1));
   }
   // any other width, same conditions: two windows of 4 elements (nwin[k][0..3] = element 4k at bit 0)
   uint32_t nwin[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-  bool win_idx = full && T != 16 && !d.inv_perm && S == 0 && (G & 7) == 0;
+  bool win_idx = dq_win_form(d, full, T);
   if (win_idx) {
     const int cb = j0 / G, g = j0 - cb * G;
     const uint32_t* row = (const uint32_t*)d.indices + ((size_t)cb * d.num_indices + n) * d.row_words;
     // a window that would run past the row end (the last chunk of a row): element by element instead
-    const uint32_t bit1 = (uint32_t)(g + 4) * (uint32_t)T;
-    win_idx = (int)(bit1 >> 5) + 5 <= d.row_words;
+    win_idx = dq_win_in_row(g, T, d.row_words);
     if (win_idx) {
-      const int g32 = (4 * T) & -(4 * T) & 31 ? ((4 * T) & -(4 * T)) : 32;
-      const bool need5 = 4 * T > 96 + g32;   // some lane's window reaches a fifth word: a property of T
+      const bool need5 = dq_need5(T);   // some lane's window reaches a fifth word: a property of T
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const uint32_t bit = (uint32_t)(g + 4 * k) * (uint32_t)T;
@@ -190,7 +188,7 @@ __global__ __launch_bounds__(256) void dequant_kernel(const VptqLayerDesc d,
       for (int k = 0; k < 4; ++k)
         r[k] = __builtin_amdgcn_perm(w2[2 * k + 1][p], w2[2 * k][p], h ? 0x07060302u : 0x05040100u);
       uint16_t* const dst = W + (size_t)o * I + j0;
-      if (full && (((uintptr_t)W) & 15) == 0) {   // (rows are 2 I bytes, I % 8 == 0: W's alignment is every row's)
+      if (dq_vec_store(W, full)) {   // (rows are 2 I bytes, I % 8 == 0: W's alignment is every row's)
         *(u32x4*)dst = r;
       } else {
 #pragma unroll
@@ -202,40 +200,69 @@ __global__ __launch_bounds__(256) void dequant_kernel(const VptqLayerDesc d,
 }
 
 template <typename DT, int V>
-static hipError_t launch_v(const VptqLayerDesc& d, void* W, hipStream_t st) {
-  const int col_blocks = (d.in_features + 2047) / 2048;
-  const long long blocks = (long long)col_blocks * d.num_indices;
-  if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
-  const int tab_bytes = (d.num_centroids + d.num_res_centroids) * V * 2;
-  const int res_bytes = d.num_res_centroids * V * 2;
-  if (d.num_codebooks == 1 && tab_bytes <= kDqLdsMax)
-    hipLaunchKernelGGL((dequant_kernel<DT, V, 1>), dim3((unsigned)blocks), dim3(256), tab_bytes, st, d,
-                       (uint16_t*)W, col_blocks);
-  else if (d.num_codebooks == 1 && res_bytes > 0 && res_bytes <= kDqLdsMax)
-    hipLaunchKernelGGL((dequant_kernel<DT, V, 2>), dim3((unsigned)blocks), dim3(256), res_bytes, st, d,
-                       (uint16_t*)W, col_blocks);
+static hipError_t launch_v(const VptqLayerDesc& d, const DequantDecision& D, void* W, hipStream_t st) {
+  if (D.v != V || D.f16 != (DT::kDtype == VPTQ_DTYPE_F16)) return hipErrorInvalidValue;   // the instantiation the decision names
+  if (D.blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)D.blocks), block(256);
+  if (D.tab == 1)
+    hipLaunchKernelGGL((dequant_kernel<DT, V, 1>), grid, block, D.lds, st, d, (uint16_t*)W, D.col_blocks);
+  else if (D.tab == 2)
+    hipLaunchKernelGGL((dequant_kernel<DT, V, 2>), grid, block, D.lds, st, d, (uint16_t*)W, D.col_blocks);
   else
-    hipLaunchKernelGGL((dequant_kernel<DT, V, 0>), dim3((unsigned)blocks), dim3(256), 0, st, d, (uint16_t*)W,
-                       col_blocks);
+    hipLaunchKernelGGL((dequant_kernel<DT, V, 0>), grid, block, 0, st, d, (uint16_t*)W, D.col_blocks);
   return hipGetLastError();
 }
 
 template <typename DT>
-static hipError_t launch_dt(const VptqLayerDesc& d, void* W, hipStream_t st) {
-  switch (d.vector_len) {
-    case 2: return launch_v<DT, 2>(d, W, st);
-    case 4: return launch_v<DT, 4>(d, W, st);
-    case 6: return launch_v<DT, 6>(d, W, st);
-    case 8: return launch_v<DT, 8>(d, W, st);
-    case 10: return launch_v<DT, 10>(d, W, st);
-    case 12: return launch_v<DT, 12>(d, W, st);
-    case 16: return launch_v<DT, 16>(d, W, st);
+static hipError_t launch_dt(const VptqLayerDesc& d, const DequantDecision& D, void* W, hipStream_t st) {
+  switch (D.v) {
+    case 2: return launch_v<DT, 2>(d, D, W, st);
+    case 4: return launch_v<DT, 4>(d, D, W, st);
+    case 6: return launch_v<DT, 6>(d, D, W, st);
+    case 8: return launch_v<DT, 8>(d, D, W, st);
+    case 10: return launch_v<DT, 10>(d, D, W, st);
+    case 12: return launch_v<DT, 12>(d, D, W, st);
+    case 16: return launch_v<DT, 16>(d, D, W, st);
     default: return hipErrorInvalidValue;
   }
 }
 
 hipError_t launch_dequant(const VptqLayerDesc& d, void* W, hipStream_t st) {
-  return d.dtype == VPTQ_DTYPE_F16 ? launch_dt<F16>(d, W, st) : launch_dt<BF16>(d, W, st);
+  const DequantDecision D = dequant_decide(d);
+  return D.f16 ? launch_dt<F16>(d, D, W, st) : launch_dt<BF16>(d, D, W, st);
+}
+
+// vptq_dequant_instance: the decision above and, for ONE vector-row, how many of its chunks of 8 columns take each path - the
+// kernel's own predicates (dequant_paths.h) evaluated chunk by chunk as a thread would (nothing is dereferenced).
+//   idx: vec (one 16-byte load), win (two windows), win5 (... with a fifth word), elem (element by element - also every chunk
+//   with a permutation, outlier columns or a ragged width)
+int dequant_instance(const VptqLayerDesc& d, const void* W, char* buf, size_t bytes) {
+  const DequantDecision D = dequant_decide(d);
+  const int I = d.in_features, G = d.group_size, T = d.index_bits + d.res_bits;
+  long long chunks = 0, n_idx[4] = {0, 0, 0, 0}, n_norm = 0, n_store = 0;
+  for (int j0 = 0; j0 < I; j0 += 8, ++chunks) {
+    const bool full = dq_full(j0, I);
+    n_norm += dq_vec_norm(d, full);
+    n_store += dq_vec_store(W, full);
+    int cls = 3;
+    if (dq_vec_idx(d, full, T)) cls = 0;
+    else if (dq_win_form(d, full, T)) {
+      const int cb = j0 / G, g = j0 - cb * G;
+      if (dq_win_in_row(g, T, d.row_words)) cls = dq_need5(T) ? 2 : 1;
+    }
+    ++n_idx[cls];
+  }
+  static const char* const kIdx[4] = {"vec", "win", "win5", "elem"};
+  char idx[96];
+  size_t used = 0;
+  for (int c = 0; c < 4; ++c)
+    if (n_idx[c]) used += (size_t)snprintf(idx + used, sizeof(idx) - used, "%s%s:%lld", used ? "," : "", kIdx[c], n_idx[c]);
+  const char* norm = !d.weight_scale ? "none" : n_norm == chunks ? "vec" : n_norm == 0 ? "scalar" : "mixed";
+  const char* store = n_store == chunks ? "vec" : n_store == 0 ? "scalar" : "mixed";
+  const int w = snprintf(buf, bytes, "dequant dt=%s v=%d tab=%d lds=%d colblocks=%d t=%d norm=%s store=%s idx=%s perm=%d outl=%d groups=%d ragged=%d",
+                         D.f16 ? "f16" : "bf16", D.v, D.tab, D.lds, D.col_blocks, T, norm, store, idx, (int)(d.inv_perm != nullptr),
+                         d.outlier_size > 0 ? d.outlier_vector_len : 0, d.num_codebooks, (int)((I & 7) != 0));
+  return w < 0 || (size_t)w >= bytes ? -2 : 0;
 }
 
 }  // namespace vptq

@@ -204,8 +204,10 @@ size_t gemm_fused_workspace_bytes(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_fused(const VptqLayerDesc& d, const void* x, void* y, int tokens, void* workspace,
                              size_t workspace_bytes, hipStream_t st);
 
-// dequant.hip
+// dequant.hip; dequant_instance: the instantiation and the per-chunk paths launch_dequant(d, W) takes, as text (vptq_dequant_instance;
+// 0, -2: buffer too small) - the launch decision and the kernel's own predicates (dequant_paths.h)
 hipError_t launch_dequant(const VptqLayerDesc& d, void* W, hipStream_t st);
+int dequant_instance(const VptqLayerDesc& d, const void* W, char* buf, size_t bytes);
 
 // gemv_v2.hip
 hipError_t launch_gemv_v2(const VptqV2Desc& d, const void* x, void* y, int tokens,
