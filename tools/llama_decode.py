@@ -31,7 +31,7 @@ SIZES = {"8b": dict(hidden_size=4096, intermediate_size=14336, num_attention_hea
          "70b": dict(hidden_size=8192, intermediate_size=28672, num_attention_heads=64, layers=80)}
 
 
-def build_model(layers, dev, k=256, kr=256, perm=False, size="8b", dt=torch.float16):
+def build_model(layers, dev, k=256, kr=256, v=8, perm=False, size="8b", dt=torch.float16):
     from transformers import LlamaConfig, LlamaForCausalLM
     from transformers.integrations.vptq import replace_with_vptq_linear
     from transformers.models.llama.modeling_llama import LlamaRotaryEmbedding
@@ -51,7 +51,7 @@ def build_model(layers, dev, k=256, kr=256, perm=False, size="8b", dt=torch.floa
     per_layer = {}
     for name, mod in model.named_modules():
         if isinstance(mod, torch.nn.Linear) and name != "lm_head":
-            per_layer[name] = dict(vector_lens=[-1, 8], num_centroids=[-1, k],
+            per_layer[name] = dict(vector_lens=[-1, v], num_centroids=[-1, k],
                                    num_res_centroids=[-1, kr if kr > 0 else -1], group_num=1,
                                    group_size=mod.in_features, outlier_size=0,
                                    indices_as_float=False, enable_norm=True, enable_perm=perm,
@@ -110,7 +110,7 @@ def run(args):
     def stage(msg):
         print(f"[stage] {msg}", file=sys.stderr, flush=True)
     stage("build")
-    model, cfg, qlayers = build_model(args.layers, dev, k=args.k, kr=args.kr, perm=args.perm, size=args.model, dt=torch.bfloat16 if args.dtype == "bf16" else torch.float16)
+    model, cfg, qlayers = build_model(args.layers, dev, k=args.k, kr=args.kr, v=args.v, perm=args.perm, size=args.model, dt=torch.bfloat16 if args.dtype == "bf16" else torch.float16)
     fused = 0
     if args.fuse:
         import vptq
@@ -222,7 +222,7 @@ def run(args):
         vq_us = f"failed: {type(e).__name__}: {e}"
 
     lm_head_bytes = cfg.vocab_size * cfg.hidden_size * 2
-    res = dict(model=f"Llama-3-{args.model.upper()} shapes, {cfg.num_hidden_layers} layers, VQuantLinear v8-k{args.k}-{args.kr}" + (" (2-bit)" if (args.k, args.kr) == (256, 256) else "")
+    res = dict(model=f"Llama-3-{args.model.upper()} shapes, {cfg.num_hidden_layers} layers, VQuantLinear v{args.v}-k{args.k}-{args.kr}" + (" (2-bit)" if (args.k, args.kr) == (256, 256) else "")
                      + (" +perm" if args.perm else ""),
                quantized_linears=len(qlayers), packed_index_GB=qbytes / 1e9,
                lm_head_GB=lm_head_bytes / 1e9, prompt=args.prompt, new_tokens=args.new,
@@ -259,6 +259,7 @@ if __name__ == "__main__":
     ap.add_argument("--perm", action="store_true")
     ap.add_argument("--k", type=int, default=256, help="main codebook entries (v = 8): 256 = the 2-bit format, 65536 = the published 3-bit ones")
     ap.add_argument("--kr", type=int, default=256, help="residual codebook entries")
+    ap.add_argument("--v", type=int, default=8, choices=[8, 16], help="vector length (16: the 1.4 - 1.6 bit formats, --k 65536 --kr 1024 / 256 / 64)")
     ap.add_argument("--fuse", action="store_true", help="link_siblings: q/k/v and gate/up share one grouped launch")
     ap.add_argument("--batch", type=int, default=1, help="sequences decoded together: every VQuantLinear call of a step sees that many tokens")
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"], help="dtype of the model and its VQuantLinear tensors")
