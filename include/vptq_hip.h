@@ -533,6 +533,28 @@ VPTQ_API int vptq_sliced_layout_plan(const VptqLayerDesc* desc, const VptqSliced
 VPTQ_API int vptq_sliced_layout_fill(const VptqLayerDesc* desc, const VptqSlicedLayoutSpec* spec, const VptqSlicedLayout* out,
                                      int64_t total_blocks, void* stream);
 
+/* Batched decode of the large-codebook formats: 1 - 16 tokens in ONE launch (gemm_gather.hip; added within ABI 12; present when the
+ * symbols are).  The layers vptq_quant_gemv serves with gemv_gather_kernel - v = 8, 65536 main centroids, 0 / 256 / 65536 residual
+ * centroids ("v8-k65536-0", "-256", "-65536"), one codebook group, no outlier columns, weight_scale and weight_bias set, group_size ==
+ * in_features (a multiple of 8), indices and codebooks 16-byte aligned - with the tokens as the M dimension of a 16x16x32 MFMA: one
+ * pass over the packed indices and one gather per index for any token count, where vptq_quant_gemv takes 8 tokens per pass.  The
+ * reference's roundings per weight (bit-identical to vptq_dequant's W), fp32 sums added in a fixed order (two calls give the same
+ * bits), one rounding of the output, the output bias added in fp32.  No workspace, no atomics; graph-capturable.
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags: VPTQ_GEMV_OUT_F32 stores the fp32 sums (y is float32);
+ *   VPTQ_GEMV_FAST_MATH / _EXACT / _SELECTIVE are accepted and change nothing.
+ * vptq_quant_gemm_gather_supported: 1 where the call serves (desc, tokens), else 0; host logic.
+ * vptq_quant_gemm_gather: NULL desc / x / y VPTQ_E_NULL; tokens outside [1, 16] VPTQ_E_TOKENS; a layer it does not serve, or an x that
+ *   is not 16-byte aligned, VPTQ_E_UNSUPPORTED; nothing is launched then.
+ * vptq_quant_gemm_gather_instance: the instantiation of gemm_gather_kernel<DT, T, PERM> and the launch shape, as one line (the
+ *   launcher's own decision; host logic, without a device the CU count is taken as 256):
+ *   gemm_gather dt=f16|bf16 t=16|24|32 perm=0|1 tok=N tiles=N rgs=N
+ *       t the index width, tok the tokens of the launch, tiles the column tiles (1024 columns) per row group (2 vector-rows), rgs the
+ *       most row groups one workgroup walks.  Returns VPTQ_OK, the call's own validation error, or VPTQ_E_WORKSPACE (buf too small).
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens and vptq_quant_gemv_kernel_name do not route here: callers choose this entry. */
+VPTQ_API int vptq_quant_gemm_gather_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gather(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
+VPTQ_API int vptq_quant_gemm_gather_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
 /* Diagnostic (ABI 12): WHICH INSTANTIATION of dequant_kernel<DT, V, TAB> vptq_dequant(desc, W) would launch and which paths its

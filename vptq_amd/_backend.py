@@ -154,6 +154,10 @@ EXPORTS = {
                                                   C.c_size_t]),
     "vptq_quant_gemv_sliced_tokens_instance": (C.c_int, [C.POINTER(LayerDesc), C.POINTER(SlicedLayout), C.c_int, C.c_int, C.c_int,
                                                          C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 16 tokens of the large-codebook formats in one launch (gemm_gather.hip): query, call, instance text
+    "vptq_quant_gemm_gather_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gather": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
+    "vptq_quant_gemm_gather_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

@@ -204,12 +204,12 @@ static int gather_T(const VptqLayerDesc& d) {
   return 0;
 }
 
-bool gemv_gather_eligible(const VptqLayerDesc& d, int tokens) {
+bool gemv_gather_eligible(const VptqLayerDesc& d, int tokens, int max_tokens) {
   const int T = gather_T(d);
   return T != 0 && d.vector_len == 8 && d.num_codebooks == 1 && d.outlier_size == 0 &&
          d.weight_scale != nullptr && d.weight_bias != nullptr && (d.group_size % 8) == 0 &&
          d.group_size == d.in_features && (long long)d.row_words * 32 == (long long)d.group_size * T &&
-         tokens >= 1 && tokens <= 8 &&
+         tokens >= 1 && tokens <= max_tokens &&
          (d.perm == nullptr || (d.scale_permuted != nullptr && d.bias_permuted != nullptr)) &&
          (((uintptr_t)d.indices | (uintptr_t)d.centroids | (uintptr_t)d.res_centroids) & 15) == 0 &&
          (((uintptr_t)d.weight_scale | (uintptr_t)d.weight_bias | (uintptr_t)d.scale_permuted |

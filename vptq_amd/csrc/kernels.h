@@ -80,7 +80,8 @@ hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, in
 
 // gemv_gather.hip — v=8, k=65536 (+ residual 0 / 256 / 65536), C=1, no outliers:
 // centroid rows gathered from L2.
-bool gemv_gather_eligible(const VptqLayerDesc& d, int tokens);
+// max_tokens: the most tokens one launch takes - 8 here, 16 for gemm_gather.hip over the same layers
+bool gemv_gather_eligible(const VptqLayerDesc& d, int tokens, int max_tokens = 8);
 hipError_t launch_gemv_gather(const VptqLayerDesc& d, const void* x, void* y, int tokens,
                               bool out_f32, hipStream_t st);
 
@@ -197,6 +198,15 @@ struct GemmK256Decision { bool f16, perm; int n_groups, grid, passes; };
 GemmK256Decision gemm_k256_decide(const VptqLayerDesc& d);
 hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
                             hipStream_t st);
+
+// gemm_gather.hip - gemv_gather's layers (v = 8, k = 65536, residual 0 / 256 / 65536), up to 16 tokens in one launch (tokens = MFMA M;
+// centroid rows gathered from L2, the rebuilt tile in LDS in operand order; reference roundings; no workspace)
+bool gemm_gather_eligible(const VptqLayerDesc& d, int tokens);
+// what launch_gemm_gather launches: gemm_gather_kernel<DT, T, PERM>; tiles: column tiles per row group; rgs: the most row groups
+// one workgroup walks
+struct GemmGatherDecision { bool f16, perm; int T, tok, tiles, n_groups, grid, rgs; };
+GemmGatherDecision gemm_gather_decide(const VptqLayerDesc& d, int tokens);
+hipError_t launch_gemm_gather(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
 
 // gemm_fused.hip - canonical format, many tokens: dequantised tile -> LDS -> 32x32x16 MFMA
 bool gemm_fused_eligible(const VptqLayerDesc& d);

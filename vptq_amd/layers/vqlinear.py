@@ -93,6 +93,34 @@ _DEQUANT_SLICED_MAX_COLS = 4096
 _DEQUANT_SLICED_MODE = (B.tune_env("VPTQ_DEQUANT_SLICED", "auto") or "auto").strip().lower()
 
 
+# WHICH (format, shape, token count) take the large-codebook formats' batched-decode kernel (`vptq_quant_gemm_gather`, gemm_gather.hip:
+# 1 - 16 tokens in one launch) in place of the route they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.
+# A cell is routed only where the new kernel was MEASURED to beat the route it replaces by more than the larger of 5 % and three times
+# the run-to-run spread, both in one process on one box (tools/gemm_gather_bench.py writes that table; profiles/r15/README.md).  No
+# such table exists yet, so no cell is routed: `_GEMM_GATHER_CELLS` is empty and the module's default is what it was.  A cell is
+# (residual centroids, least index elements = vector-rows x columns, least tokens).  VPTQ_GEMM_GATHER=1 / 0 (with VPTQ_TUNING=1):
+# every supported layer from 5 tokens / none - what the bench tool, the tests and a user who has measured their own shapes use.
+GEMM_GATHER_MAX_TOKENS = 16
+_GEMM_GATHER_MODE = (B.tune_env("VPTQ_GEMM_GATHER", "auto") or "auto").strip().lower()
+_GEMM_GATHER_CELLS = ()   # ((num_res_centroids, min_index_elements, min_tokens), ...)
+
+
+def gemm_gather_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
+    """does a layer of this format (vector length, main / residual codebook entries) and shape take `vptq_quant_gemm_gather` for
+    `tokens` tokens?  Pure: no device, no library (whether the library serves the layer - one codebook group, no outliers, scale and
+    bias, alignment - is `vptq_quant_gemm_gather_supported`'s answer)."""
+    if vector_len != 8 or num_centroids != 65536 or num_res_centroids not in (0, 256, 65536):
+        return False
+    if _GEMM_GATHER_MODE in ("0", "off"):
+        return False
+    if _GEMM_GATHER_MODE in ("1", "on"):
+        return 5 <= tokens <= GEMM_GATHER_MAX_TOKENS
+    if not 5 <= tokens <= GEMM_GATHER_MAX_TOKENS:
+        return False
+    n_el = ((out_features + 7) // 8) * in_features
+    return any(kr == num_res_centroids and n_el >= min_el and tokens >= min_tok for kr, min_el, min_tok in _GEMM_GATHER_CELLS)
+
+
 def _dense_from_layout(layer) -> bool:
     """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (a library without the entry, added within ABI 11:
     never - the repack route stays)"""
@@ -475,6 +503,10 @@ class VQuantLinear(nn.Module):
                 "path, which is outside this inference package; construct the layer with "
                 "enable_proxy_error=False (HF does).")
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_gg_cand", True):
+            y = self._gemm_gather_cached(x, tokens)   # (the large-codebook formats' batched decode, where `gemm_gather_route` says so)
+            if y is not None:
+                return y
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
                 (tokens <= B.GEMV_ANY_FORMAT_TOKENS or tokens <= self._descriptor().max_tokens):
             return self._gemv_cached(x, tokens)
@@ -588,7 +620,7 @@ class VQuantLinear(nn.Module):
 
     # derived, device-bound state (ctypes descriptors, the sliced layout, sibling links) is rebuilt on demand: it is
     # neither pickled nor deep-copied with the module (torch.save(model), copy.deepcopy(model))
-    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings")
+    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_gg_ok")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -939,6 +971,43 @@ class VQuantLinear(nn.Module):
             return self._dense_cached(x)
         if rc:
             B.check(rc, "vptq_quant_gemv")
+        return y
+
+    def _gemm_gather_cached(self, x: torch.Tensor, tokens: int):
+        """5 - 16 tokens of a large-codebook layer in ONE launch of `vptq_quant_gemm_gather` where `gemm_gather_route` gives the
+        layer's (format, shape, tokens) to it and the library serves the layer; None: the caller's other routes.  Compact layers
+        hand it the repacked stream, as the gather route does."""
+        if "_gg_cand" not in self.__dict__:
+            # (static module configuration: decided once, every other layer pays one dict look-up per call)
+            self.__dict__["_gg_cand"] = bool(self.vector_len == 8 and self.num_centroids == 65536 and self.num_codebooks == 1 and
+                                             not self.enable_outlier and self.enable_norm and
+                                             getattr(B.lib(), "vptq_quant_gemm_gather", None) is not None)
+            if not self.__dict__["_gg_cand"]:
+                return None
+        if not gemm_gather_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
+                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
+            return None
+        cache = self._descriptor()
+        desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
+        ok = self.__dict__.get("_gg_ok")
+        if ok is None or ok[0] != cache.generation:
+            ok = (cache.generation, bool(B.lib().vptq_quant_gemm_gather_supported(desc, GEMM_GATHER_MAX_TOKENS)))
+            self.__dict__["_gg_ok"] = ok
+        if not ok[1] or x.shape[-1] != self.in_features or x.dtype != wdtype or x.device != dev:
+            return None   # (the other routes raise the shape / dtype / device errors)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if x.data_ptr() % 16:
+            return None
+        y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
+        cp = self.__dict__.get("_compact")
+        with torch.cuda.device(dev):
+            sp = B.current_stream_ptr(dev)
+            if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
+                desc = self._repacked_desc(desc, dev_index, sp)
+            rc = B.lib().vptq_quant_gemm_gather(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
+        if rc:
+            B.check(rc, "vptq_quant_gemm_gather")
         return y
 
     def _dense_cached(self, x: torch.Tensor) -> torch.Tensor:

@@ -20,7 +20,7 @@ from torch.nn import functional as F
 
 from vptq_amd import _backend as B
 
-__all__ = ["dequant", "quant_gemm", "quant_gemv_v2"]
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
 # says (`_backend.set_arithmetic`: "reference" is the default since round 5, "folded" the opt-in fast form)
@@ -198,8 +198,16 @@ def quant_gemm(
             group_size=group_size, outlier_size=outlier_size if enable_outlier else 0,
             outlier_vector_len=outlier_vector_len,
             num_outlier_centroids=num_outlier_centroids, prefetch=prefetch)
+        gdesc = desc
         if tokens > B.GEMV_ANY_FORMAT_TOKENS and tokens > B.lib().vptq_quant_gemv_max_tokens(desc):
             desc = None  # 9-16 tokens: only the canonical format's GEMV still beats dequant + GEMM
+        # the large-codebook formats' batched decode (gemm_gather.hip): the token counts `gemm_gather_route` gives it, as
+        # `VQuantLinear.forward` routes them
+        from vptq_amd.layers.vqlinear import gemm_gather_route
+        if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
+                gemm_gather_route(vector_len, num_centroids, num_res_centroids if enable_residual else 0, out_features, in_features, tokens) and \
+                B.lib().vptq_quant_gemm_gather_supported(gdesc, tokens):
+            return quant_gemm_gather(x, gdesc, out_features)
     if desc is not None:
         y = torch.empty(x.shape[:-1] + (out_features,), dtype=x.dtype, device=dev)
         flags = _FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
@@ -258,6 +266,22 @@ def quant_gemm_fused(x: torch.Tensor, desc, out_features: int) -> torch.Tensor:
         B.check(B.lib().vptq_quant_gemm(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS,
                                         None if ws is None else ws.data_ptr(), ws_bytes,
                                         B.current_stream_ptr(dev)), "vptq_quant_gemm")
+    return y
+
+
+def quant_gemm_gather(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 1 - 16 tokens of a large-codebook layer (v = 8, 65536 main centroids, 0 / 256 / 65536 residual
+    centroids) in ONE launch (`vptq_quant_gemm_gather`, gemm_gather.hip: centroid rows gathered from L2, the contraction on the
+    matrix pipe, the reference's roundings; replaces dequant + F.linear for 9 - 16 tokens).  `desc` = a LayerDesc of a layer
+    `vptq_quant_gemm_gather_supported` accepts; out_f32: the un-rounded fp32 sums."""
+    tokens = x.numel() // x.shape[-1]
+    dev = x.device
+    if not x.is_contiguous():
+        x = x.contiguous()
+    y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
+    with torch.cuda.device(dev):
+        B.check(B.lib().vptq_quant_gemm_gather(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
+                                               B.current_stream_ptr(dev)), "vptq_quant_gemm_gather")
     return y
 
 
