@@ -555,6 +555,31 @@ VPTQ_API int vptq_quant_gemm_gather_supported(const VptqLayerDesc* desc, int tok
 VPTQ_API int vptq_quant_gemm_gather(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_gather_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of the large-codebook formats vptq_quant_gemm_gather does not serve: 1 - 16 tokens in ONE launch (gemm_gatherx.hip;
+ * added within ABI 12; present when the symbols are).  Vector length 8 or 16, 16384 ... 65536 main centroids, any residual codebook or
+ * none (index_bits + res_bits <= 32: "v16-k65536-65536", "-32768", "-1024", "-256", "-64", "-0", "v8-k65536-4096", "-4", "v8-k32768-0",
+ * "v8-k16384-0"), one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and
+ * bias_permuted), group_size == in_features (a multiple of 8), row_words * 32 >= group_size * (index_bits + res_bits), indices and
+ * codebooks 16-byte aligned - and NOT a layer vptq_quant_gemm_gather_supported accepts: a layer has one batched-decode kernel.  The same
+ * arithmetic and guarantees as vptq_quant_gemm_gather: the reference's roundings per weight (bit-identical to vptq_dequant's W), fp32
+ * sums added in a fixed order, one rounding of the output, the output bias added in fp32; no workspace, no atomics; graph-capturable.
+ * A residual table of at most 32 KiB is held in LDS, a larger one is gathered from L2.
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags: VPTQ_GEMV_OUT_F32 stores the fp32 sums (y is float32);
+ *   VPTQ_GEMV_FAST_MATH / _EXACT / _SELECTIVE are accepted and change nothing.
+ * vptq_quant_gemm_gatherx_supported: 1 where the call serves (desc, tokens), else 0; host logic.
+ * vptq_quant_gemm_gatherx: NULL desc / x / y VPTQ_E_NULL; tokens outside [1, 16] VPTQ_E_TOKENS; a layer it does not serve, or an x that
+ *   is not 16-byte aligned, VPTQ_E_UNSUPPORTED; nothing is launched then.
+ * vptq_quant_gemm_gatherx_instance: the instantiation of gemm_gatherx_kernel<DT, V, RES, PERM>, the run-time index widths and the
+ *   launch shape, as one line (the launcher's own decision; host logic, without a device the CU count is taken as 256):
+ *   gemm_gatherx dt=f16|bf16 v=8|16 ib=N rb=N res=none|lds|l2 perm=0|1 tok=N tiles=N wgcu=N rgs=N
+ *       ib / rb the main / residual index widths, res where the residual entries come from, tok the tokens of the launch, tiles the
+ *       column tiles (1024 columns) per row group (16 outputs), wgcu the workgroups per CU the LDS in use (32 KiB + an LDS-held
+ *       table) leaves, rgs the most row groups one workgroup walks.  Returns as vptq_quant_gemm_gather_instance does.
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens, vptq_quant_gemv_kernel_name and vptq_quant_gemm_gather* are what they were. */
+VPTQ_API int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gatherx(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
+VPTQ_API int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
 /* Diagnostic (ABI 12): WHICH INSTANTIATION of dequant_kernel<DT, V, TAB> vptq_dequant(desc, W) would launch and which paths its

@@ -158,6 +158,10 @@ EXPORTS = {
     "vptq_quant_gemm_gather_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gather": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
     "vptq_quant_gemm_gather_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) ... and of the large-codebook formats that entry does not serve: v = 16, any index width (gemm_gatherx.hip)
+    "vptq_quant_gemm_gatherx_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gatherx": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
+    "vptq_quant_gemm_gatherx_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

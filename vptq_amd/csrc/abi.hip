@@ -1218,6 +1218,46 @@ int vptq_quant_gemm_gather_instance(const VptqLayerDesc* d, int tokens, int flag
   return text_done(t);
 }
 
+// ---- gemm_gatherx.hip: 1 - 16 tokens of the large-codebook formats gemm_gather does not take (added within ABI 12)
+int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* d, int tokens) {
+  return validate_layer(d) == VPTQ_OK && vptq::gemm_gatherx_eligible(*d, tokens) ? 1 : 0;
+}
+
+// the checks of vptq_quant_gemm_gatherx and vptq_quant_gemm_gatherx_instance on the descriptor and the token count
+static int validate_gemm_gatherx(const VptqLayerDesc* d, int tokens) {
+  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
+  if (!vptq::gemm_gatherx_eligible(*d, tokens))
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherx serves v = 8 / 16, 16384 ... 65536 main centroids, any residual codebook (index_bits + "
+                                    "res_bits <= 32), one codebook, no outlier columns, scale and bias, group_size == in_features (a "
+                                    "multiple of 8), 16-byte aligned tables - and not the layers gemm_gather serves");
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gatherx(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  if (const int rc = validate_gemm_gatherx(d, tokens)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherx: x must be 16-byte aligned");
+  hipError_t e = vptq::launch_gemm_gatherx(*d, x, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, "gemm_gatherx launch");
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* d, int tokens, int flags, char* buf, size_t bytes) {
+  (void)flags;
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  if (const int rc = validate_gemm_gatherx(d, tokens)) return rc;
+  const vptq::GemmGatherXDecision D = vptq::gemm_gatherx_decide(*d, tokens);
+  Text t = {buf, bytes, 0, true};
+  t.add("gemm_gatherx dt=%s v=%d ib=%d rb=%d res=%s perm=%d tok=%d tiles=%d wgcu=%d rgs=%d", D.f16 ? "f16" : "bf16", D.v, D.ib, D.rb,
+        D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", (int)D.perm, D.tok, D.tiles, D.wgcu, D.rgs);
+  if (!t.fits) buf[0] = 0;
+  return text_done(t);
+}
+
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {
   int rc = validate_layer(d);

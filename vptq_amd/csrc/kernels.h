@@ -208,6 +208,15 @@ struct GemmGatherDecision { bool f16, perm; int T, tok, tiles, n_groups, grid, r
 GemmGatherDecision gemm_gather_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gather(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
 
+// gemm_gatherx.hip - the large-codebook layers gemm_gather does not take (v = 8 / 16, 16384 ... 65536 main centroids, any residual
+// codebook, any total index width), up to 16 tokens in one launch: gemm_gather's structure with gemv_gatherx's index path
+bool gemm_gatherx_eligible(const VptqLayerDesc& d, int tokens);
+// what launch_gemm_gatherx launches: gemm_gatherx_kernel<DT, V, RES, PERM> (res: 0 none, 1 table in LDS, 2 gathered from L2) with the
+// run-time index widths ib / rb; lds: dynamic LDS bytes (tile + table), wgcu: the workgroups per CU that LDS leaves; rgs as above
+struct GemmGatherXDecision { bool f16, perm; int v, ib, rb, res, res_bytes, tok, tiles, lds, wgcu, n_groups, grid, rgs; };
+GemmGatherXDecision gemm_gatherx_decide(const VptqLayerDesc& d, int tokens);
+hipError_t launch_gemm_gatherx(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+
 // gemm_fused.hip - canonical format, many tokens: dequantised tile -> LDS -> 32x32x16 MFMA
 bool gemm_fused_eligible(const VptqLayerDesc& d);
 size_t gemm_fused_workspace_bytes(const VptqLayerDesc& d, int tokens);

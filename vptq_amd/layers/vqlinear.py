@@ -96,13 +96,16 @@ _DEQUANT_SLICED_MODE = (B.tune_env("VPTQ_DEQUANT_SLICED", "auto") or "auto").str
 # WHICH (format, shape, token count) take the large-codebook formats' batched-decode kernel (`vptq_quant_gemm_gather`, gemm_gather.hip:
 # 1 - 16 tokens in one launch) in place of the route they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.
 # A cell is routed only where the new kernel was MEASURED to beat the route it replaces by more than the larger of 5 % and three times
-# the run-to-run spread, both in one process on one box (tools/gemm_gather_bench.py writes that table; profiles/r15/README.md).  No
-# such table exists yet, so no cell is routed: `_GEMM_GATHER_CELLS` is empty and the module's default is what it was.  A cell is
-# (residual centroids, least index elements = vector-rows x columns, least tokens).  VPTQ_GEMM_GATHER=1 / 0 (with VPTQ_TUNING=1):
-# every supported layer from 5 tokens / none - what the bench tool, the tests and a user who has measured their own shapes use.
+# the run-to-run spread, both in one process on one box (tools/gemm_gather_bench.py writes that table; profiles/r15/README.md).  A
+# cell is (residual centroids, least index elements = vector-rows x columns, least tokens).  The table (profiles/r15/table.md: one
+# MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16): from 9 tokens the kernel beats the dense route in
+# every measured cell of the three formats (0.51 - 0.86 of its time), so 9 - 16 tokens are routed from the smallest measured layer
+# (4096 x 4096 = 2 M index elements) up; at 5 - 8 tokens it is level with gemv_gather in most cells (0.84 - 1.12), which stays.
+# VPTQ_GEMM_GATHER=1 / 0 (with VPTQ_TUNING=1): every supported layer from 5 tokens / none - what the bench tool, the tests and a user
+# who has measured their own shapes use.
 GEMM_GATHER_MAX_TOKENS = 16
 _GEMM_GATHER_MODE = (B.tune_env("VPTQ_GEMM_GATHER", "auto") or "auto").strip().lower()
-_GEMM_GATHER_CELLS = ()   # ((num_res_centroids, min_index_elements, min_tokens), ...)
+_GEMM_GATHER_CELLS = ((0, 2 << 20, 9), (256, 2 << 20, 9), (65536, 2 << 20, 9))   # ((num_res_centroids, min_index_elements, min_tokens), ...)
 
 
 def gemm_gather_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
@@ -119,6 +122,51 @@ def gemm_gather_route(vector_len: int, num_centroids: int, num_res_centroids: in
         return False
     n_el = ((out_features + 7) // 8) * in_features
     return any(kr == num_res_centroids and n_el >= min_el and tokens >= min_tok for kr, min_el, min_tok in _GEMM_GATHER_CELLS)
+
+
+# WHICH (format, shape, token count) take the generic batched-decode kernel (`vptq_quant_gemm_gatherx`, gemm_gatherx.hip: vector length
+# 8 / 16, 16384 ... 65536 main centroids, any residual codebook - every large-codebook format `gemm_gather_route` does not own) in place
+# of the route they had (5 - 8 tokens: the gemv_gatherx launches; 9 - 16: the dense route): the same rule as above, the same tool
+# (tools/gemm_gather_bench.py --formats ... writes profiles/r16/table.md).  A cell is (vector length, main centroids, residual
+# centroids, least index elements = vector-rows x columns, least tokens); a region is routed only where EVERY measured cell in it wins
+# in both dtypes.  The table (one MI355X, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16):
+#   v16-k65536-0, v16-k65536-1024     every cell wins (0.48 - 0.93 of the parent's time): 5 - 16 tokens from 4096 x 4096 (1 M elements) up
+#   v8-k32768-0, v8-k65536-4096       9 - 16 tokens: every cell (0.53 - 0.91); 5 - 8 tokens: only from 8192 x 8192 (8 M elements) up (0.73 - 0.94)
+#   v16-k65536-65536                  wins at 5 - 8 tokens (0.66 - 0.88) but is level with the dense route at 9 - 16 on the larger
+#                                     layers (0.94 - 1.05 at 8192 x 8192): a route has to be monotone in tokens, so nothing is routed
+# Formats that were not measured (v16-k65536-32768 / -256 / -64, v8-k65536-4, v8-k16384-0) and smaller layers are not routed.
+# VPTQ_GEMM_GATHERX=1 / 0 (with VPTQ_TUNING=1): every supported layer from 5 tokens / none.
+_GEMM_GATHERX_MODE = (B.tune_env("VPTQ_GEMM_GATHERX", "auto") or "auto").strip().lower()
+_GEMM_GATHERX_CELLS = (   # ((vector_len, num_centroids, num_res_centroids, min_index_elements, min_tokens), ...)
+    (16, 65536, 0, 1 << 20, 5), (16, 65536, 1024, 1 << 20, 5),
+    (8, 32768, 0, 2 << 20, 9), (8, 32768, 0, 8 << 20, 5),
+    (8, 65536, 4096, 2 << 20, 9), (8, 65536, 4096, 8 << 20, 5),
+)
+
+
+def _pow2(n: int) -> bool:
+    return n > 0 and (n & (n - 1)) == 0
+
+
+def gemm_gatherx_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
+    """does a layer of this format and shape take `vptq_quant_gemm_gatherx` for `tokens` tokens?  Pure: no device, no library (one
+    codebook group, no outliers, scale and bias, alignment: `vptq_quant_gemm_gatherx_supported`'s answer).  Never for the formats
+    `gemm_gather_route` owns (v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids): a layer has one batched-decode kernel."""
+    if vector_len not in (8, 16) or not _pow2(num_centroids) or not 16384 <= num_centroids <= 65536 or in_features % 8:
+        return False
+    if num_res_centroids and (not _pow2(num_res_centroids) or num_res_centroids > 65536):
+        return False
+    if vector_len == 8 and num_centroids == 65536 and num_res_centroids in (0, 256, 65536):
+        return False
+    if _GEMM_GATHERX_MODE in ("0", "off"):
+        return False
+    if not 5 <= tokens <= GEMM_GATHER_MAX_TOKENS:
+        return False
+    if _GEMM_GATHERX_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any(v == vector_len and k == num_centroids and kr == num_res_centroids and n_el >= min_el and tokens >= min_tok
+               for v, k, kr, min_el, min_tok in _GEMM_GATHERX_CELLS)
 
 
 def _dense_from_layout(layer) -> bool:
@@ -505,6 +553,10 @@ class VQuantLinear(nn.Module):
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
         if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_gg_cand", True):
             y = self._gemm_gather_cached(x, tokens)   # (the large-codebook formats' batched decode, where `gemm_gather_route` says so)
+            if y is not None:
+                return y
+        if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_ggx_cand", True):
+            y = self._gemm_gatherx_cached(x, tokens)   # (... and its generic sibling, where `gemm_gatherx_route` says so)
             if y is not None:
                 return y
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
@@ -1008,6 +1060,43 @@ class VQuantLinear(nn.Module):
             rc = B.lib().vptq_quant_gemm_gather(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
         if rc:
             B.check(rc, "vptq_quant_gemm_gather")
+        return y
+
+    def _gemm_gatherx_cached(self, x: torch.Tensor, tokens: int):
+        """5 - 16 tokens of a large-codebook layer `gemm_gather_route` does not own in ONE launch of `vptq_quant_gemm_gatherx`, where
+        `gemm_gatherx_route` gives the layer's (format, shape, tokens) to it and the library serves the layer; None: the caller's other
+        routes.  Compact layers hand it the repacked stream, exactly as `_gemm_gather_cached` does."""
+        if "_ggx_cand" not in self.__dict__:
+            # (static module configuration: decided once, every other layer pays one dict look-up per call)
+            self.__dict__["_ggx_cand"] = bool(self.vector_len in (8, 16) and 16384 <= self.num_centroids <= 65536 and
+                                              self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm and
+                                              getattr(B.lib(), "vptq_quant_gemm_gatherx", None) is not None)
+            if not self.__dict__["_ggx_cand"]:
+                return None
+        if not gemm_gatherx_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
+                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
+            return None
+        cache = self._descriptor()
+        desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
+        ok = self.__dict__.get("_ggx_ok")
+        if ok is None or ok[0] != cache.generation:
+            ok = (cache.generation, bool(B.lib().vptq_quant_gemm_gatherx_supported(desc, GEMM_GATHER_MAX_TOKENS)))
+            self.__dict__["_ggx_ok"] = ok
+        if not ok[1] or x.shape[-1] != self.in_features or x.dtype != wdtype or x.device != dev:
+            return None   # (the other routes raise the shape / dtype / device errors)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        if x.data_ptr() % 16:
+            return None
+        y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
+        cp = self.__dict__.get("_compact")
+        with torch.cuda.device(dev):
+            sp = B.current_stream_ptr(dev)
+            if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
+                desc = self._repacked_desc(desc, dev_index, sp)
+            rc = B.lib().vptq_quant_gemm_gatherx(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
+        if rc:
+            B.check(rc, "vptq_quant_gemm_gatherx")
         return y
 
     def _dense_cached(self, x: torch.Tensor) -> torch.Tensor:

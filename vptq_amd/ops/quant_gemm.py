@@ -20,7 +20,7 @@ from torch.nn import functional as F
 
 from vptq_amd import _backend as B
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemv_v2"]
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gatherx", "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
 # says (`_backend.set_arithmetic`: "reference" is the default since round 5, "folded" the opt-in fast form)
@@ -208,6 +208,12 @@ def quant_gemm(
                 gemm_gather_route(vector_len, num_centroids, num_res_centroids if enable_residual else 0, out_features, in_features, tokens) and \
                 B.lib().vptq_quant_gemm_gather_supported(gdesc, tokens):
             return quant_gemm_gather(x, gdesc, out_features)
+        # ... and its generic sibling (gemm_gatherx.hip) for the large-codebook formats that one does not own
+        from vptq_amd.layers.vqlinear import gemm_gatherx_route
+        if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
+                gemm_gatherx_route(vector_len, num_centroids, num_res_centroids if enable_residual else 0, out_features, in_features, tokens) and \
+                B.lib().vptq_quant_gemm_gatherx_supported(gdesc, tokens):
+            return quant_gemm_gatherx(x, gdesc, out_features)
     if desc is not None:
         y = torch.empty(x.shape[:-1] + (out_features,), dtype=x.dtype, device=dev)
         flags = _FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
@@ -282,6 +288,22 @@ def quant_gemm_gather(x: torch.Tensor, desc, out_features: int, out_f32: bool = 
     with torch.cuda.device(dev):
         B.check(B.lib().vptq_quant_gemm_gather(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
                                                B.current_stream_ptr(dev)), "vptq_quant_gemm_gather")
+    return y
+
+
+def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 1 - 16 tokens of a large-codebook layer `quant_gemm_gather` does not serve (vector length 8 / 16, 16384 ...
+    65536 main centroids, any residual codebook) in ONE launch (`vptq_quant_gemm_gatherx`, gemm_gatherx.hip: the same structure with an
+    index path for any total width and 32-byte entries; the reference's roundings).  `desc` = a LayerDesc of a layer
+    `vptq_quant_gemm_gatherx_supported` accepts; out_f32: the un-rounded fp32 sums."""
+    tokens = x.numel() // x.shape[-1]
+    dev = x.device
+    if not x.is_contiguous():
+        x = x.contiguous()
+    y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
+    with torch.cuda.device(dev):
+        B.check(B.lib().vptq_quant_gemm_gatherx(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
+                                                B.current_stream_ptr(dev)), "vptq_quant_gemm_gatherx")
     return y
 
 
