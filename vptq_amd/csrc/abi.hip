@@ -1180,83 +1180,74 @@ int vptq_quant_gemm(const VptqLayerDesc* d, const void* x, void* y, int tokens, 
   return VPTQ_OK;
 }
 
-// ---- gemm_gather.hip: 1 - 16 tokens of the large-codebook formats in one launch (added within ABI 12)
-int vptq_quant_gemm_gather_supported(const VptqLayerDesc* d, int tokens) {
-  return validate_layer(d) == VPTQ_OK && vptq::gemm_gather_eligible(*d, tokens) ? 1 : 0;
-}
-
-// the checks of vptq_quant_gemm_gather and vptq_quant_gemm_gather_instance on the descriptor and the token count
-static int validate_gemm_gather(const VptqLayerDesc* d, int tokens) {
-  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
-  if (!vptq::gemm_gather_eligible(*d, tokens))
-    return fail(VPTQ_E_UNSUPPORTED, "gemm_gather serves v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids, one codebook, no "
-                                    "outlier columns, scale and bias, group_size == in_features (a multiple of 8), 16-byte aligned tables");
-  return VPTQ_OK;
-}
-
-int vptq_quant_gemm_gather(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) {
-  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
-  if (const int rc = validate_layer(d)) return rc;
-  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
-  if (const int rc = validate_gemm_gather(d, tokens)) return rc;
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "gemm_gather: x must be 16-byte aligned");
-  hipError_t e = vptq::launch_gemm_gather(*d, x, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "gemm_gather launch");
-  return VPTQ_OK;
-}
-
-int vptq_quant_gemm_gather_instance(const VptqLayerDesc* d, int tokens, int flags, char* buf, size_t bytes) {
-  (void)flags;
-  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
-  buf[0] = 0;
-  if (const int rc = validate_layer(d)) return rc;
-  if (const int rc = validate_gemm_gather(d, tokens)) return rc;
-  const vptq::GemmGatherDecision D = vptq::gemm_gather_decide(*d, tokens);
-  Text t = {buf, bytes, 0, true};
+// ---- gemm_gather.hip / gemm_gatherx.hip: 1 - 16 tokens of the large-codebook formats in one launch (added within ABI 12).  A layer
+// has one of the two kernels; the entries of both are the three shapes below, given the kernel's name, what it serves, its
+// eligibility function and its launcher
+struct BatchedDecode {
+  const char* name;
+  const char* launch_what;   // hip_fail's "what" of a failed launch
+  const char* serves;
+  bool (*eligible)(const VptqLayerDesc&, int);
+  hipError_t (*launch)(const VptqLayerDesc&, const void*, void*, int, bool, hipStream_t);
+  void (*print)(Text&, const VptqLayerDesc&, int);   // the kernel's own decision as its instance line
+};
+static void print_gemm_gather(Text& t, const VptqLayerDesc& d, int tokens) {
+  const vptq::GemmGatherDecision D = vptq::gemm_gather_decide(d, tokens);
   t.add("gemm_gather dt=%s t=%d perm=%d tok=%d tiles=%d rgs=%d", D.f16 ? "f16" : "bf16", D.T, (int)D.perm, D.tok, D.tiles, D.rgs);
-  if (!t.fits) buf[0] = 0;
-  return text_done(t);
 }
-
-// ---- gemm_gatherx.hip: 1 - 16 tokens of the large-codebook formats gemm_gather does not take (added within ABI 12)
-int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* d, int tokens) {
-  return validate_layer(d) == VPTQ_OK && vptq::gemm_gatherx_eligible(*d, tokens) ? 1 : 0;
-}
-
-// the checks of vptq_quant_gemm_gatherx and vptq_quant_gemm_gatherx_instance on the descriptor and the token count
-static int validate_gemm_gatherx(const VptqLayerDesc* d, int tokens) {
-  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
-  if (!vptq::gemm_gatherx_eligible(*d, tokens))
-    return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherx serves v = 8 / 16, 16384 ... 65536 main centroids, any residual codebook (index_bits + "
-                                    "res_bits <= 32), one codebook, no outlier columns, scale and bias, group_size == in_features (a "
-                                    "multiple of 8), 16-byte aligned tables - and not the layers gemm_gather serves");
-  return VPTQ_OK;
-}
-
-int vptq_quant_gemm_gatherx(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) {
-  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
-  if (const int rc = validate_layer(d)) return rc;
-  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
-  if (const int rc = validate_gemm_gatherx(d, tokens)) return rc;
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherx: x must be 16-byte aligned");
-  hipError_t e = vptq::launch_gemm_gatherx(*d, x, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, (hipStream_t)stream);
-  if (e != hipSuccess) return hip_fail(e, "gemm_gatherx launch");
-  return VPTQ_OK;
-}
-
-int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* d, int tokens, int flags, char* buf, size_t bytes) {
-  (void)flags;
-  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
-  buf[0] = 0;
-  if (const int rc = validate_layer(d)) return rc;
-  if (const int rc = validate_gemm_gatherx(d, tokens)) return rc;
-  const vptq::GemmGatherXDecision D = vptq::gemm_gatherx_decide(*d, tokens);
-  Text t = {buf, bytes, 0, true};
+static void print_gemm_gatherx(Text& t, const VptqLayerDesc& d, int tokens) {
+  const vptq::GemmGatherXDecision D = vptq::gemm_gatherx_decide(d, tokens);
   t.add("gemm_gatherx dt=%s v=%d ib=%d rb=%d res=%s perm=%d tok=%d tiles=%d wgcu=%d rgs=%d", D.f16 ? "f16" : "bf16", D.v, D.ib, D.rb,
         D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", (int)D.perm, D.tok, D.tiles, D.wgcu, D.rgs);
+}
+static const BatchedDecode kGemmGather = {
+  "gemm_gather", "gemm_gather launch", "v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids, one codebook, no outlier columns, scale and bias, "
+  "group_size == in_features (a multiple of 8), 16-byte aligned tables", vptq::gemm_gather_eligible, vptq::launch_gemm_gather,
+  print_gemm_gather};
+static const BatchedDecode kGemmGatherX = {
+  "gemm_gatherx", "gemm_gatherx launch", "v = 8 / 16, 16384 ... 65536 main centroids, any residual codebook (index_bits + res_bits <= 32), one codebook, no "
+  "outlier columns, scale and bias, group_size == in_features (a multiple of 8), 16-byte aligned tables - and not the layers gemm_gather "
+  "serves", vptq::gemm_gatherx_eligible, vptq::launch_gemm_gatherx, print_gemm_gatherx};
+
+static int batched_supported(const BatchedDecode& k, const VptqLayerDesc* d, int tokens) {
+  return validate_layer(d) == VPTQ_OK && k.eligible(*d, tokens) ? 1 : 0;
+}
+
+// the checks of an entry and its `_instance` on the token count and the layer
+static int batched_validate(const BatchedDecode& k, const VptqLayerDesc* d, int tokens) {
+  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
+  if (!k.eligible(*d, tokens)) return fail(VPTQ_E_UNSUPPORTED, "%s serves %s", k.name, k.serves);
+  return VPTQ_OK;
+}
+
+static int batched_launch(const BatchedDecode& k, const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernels have the reference's roundings only)
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  if (const int rc = batched_validate(k, d, tokens)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "%s: x must be 16-byte aligned", k.name);
+  const hipError_t e = k.launch(*d, x, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return hip_fail(e, k.launch_what);
+  return VPTQ_OK;
+}
+
+static int batched_instance(const BatchedDecode& k, const VptqLayerDesc* d, int tokens, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  if (const int rc = batched_validate(k, d, tokens)) return rc;
+  Text t = {buf, bytes, 0, true};
+  k.print(t, *d, tokens);
   if (!t.fits) buf[0] = 0;
   return text_done(t);
 }
+
+int vptq_quant_gemm_gather_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmGather, d, tokens); }
+int vptq_quant_gemm_gather(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmGather, d, x, y, tokens, flags, stream); }
+int vptq_quant_gemm_gather_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmGather, d, tokens, buf, bytes); }
+int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmGatherX, d, tokens); }
+int vptq_quant_gemm_gatherx(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmGatherX, d, x, y, tokens, flags, stream); }
+int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmGatherX, d, tokens, buf, bytes); }
 
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {

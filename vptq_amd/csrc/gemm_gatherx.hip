@@ -6,11 +6,8 @@
 // gemv_gatherx keeps TOK x V fp32 sums per lane and stops at 4 tokens for v = 16 (8 for v = 8): 5 - 8 tokens of a v = 16 layer were two
 // launches, each a full pass over the indices and the gathers, and 9 - 16 tokens went through vptq_dequant + a dense GEMM.
 //
-// Structure: gemm_gather.hip's (see its head comment) - 256 threads; a row group = 16 outputs (one MFMA N block) over ALL columns;
-// column tiles of 1024; a thread rebuilds 8 consecutive columns of 8 outputs with the reference's roundings (DT::add4 /
-// DT::scale_bias4: bit-identical to vptq_dequant), transposes 8 x 8 in registers and writes swizzled ds_write_b128 in B-operand
-// order; the tile's 32 K-steps are dealt to the 4 waves; the next tile's gathers are issued before this tile's MFMA phase; the 4
-// waves' partial sums meet in LDS and are added in wave order.  No atomics, no workspace, no scratch.  What differs:
+// Structure: the tile pipeline described in gemm_gather_tile.h, whose phases are that header's functions, inside gemm_gather.hip's loop
+// skeleton.  No atomics, no workspace, no scratch.  What differs from gemm_gather.hip:
 //  * V = 16: a row group is ONE vector-row; the two thread halves (tid >> 7) take the two 16-byte halves of the same 32-byte entry
 //    (cent + idx * 32 + 16 * half) and read the same index window.  V = 8: two vector-rows per group, as in gemm_gather.
 //  * index path for any T (run-time, wave-uniform): a thread's 8 elements are 8 T bits that start at byte T * chunk of the packed
@@ -21,46 +18,16 @@
 //  * residual table: RES = 1: a table of at most kXResLdsMax = 32 KiB is copied into the dynamic LDS behind the tile once per
 //    workgroup (as gemv_gatherx does); RES = 2: gathered from L2; RES = 0: none.
 // LDS: 32 KiB tile + the table: 4 workgroups per CU up to 40 KiB, 3 up to 48 KiB, 2 at 64 KiB (gemm_gatherx_decide: wgcu).
-#include <type_traits>
-
-#include "common.h"
-#include "kernels.h"
+#include "gemm_gather_tile.h"
 
 namespace vptq {
 
-constexpr int kGXThreads = 256;
-constexpr int kGXTile = 1024;                      // columns per tile: 128 chunks of 8
-constexpr int kGXChunks = kGXTile / 8;
-constexpr int kGXTileBytes = kGXChunks * 16 * 16;  // [chunk][16 outputs][16 bytes]: 32 KiB
 constexpr int kGXResLdsMax = 32768;                // (gemv_gatherx.hip: kXResLdsMax)
 constexpr int kGXLdsPerCu = 160 * 1024;
 constexpr int kGXMaxWgPerCu = 4;                   // 16 waves per CU: 128 VGPRs per lane
 
-struct GemmGatherXParams {
-  const uint32_t* idx;    // [N][row_words]
-  const char* cent;       // [k][V] 2 V bytes per entry
-  const char* rcent;      // [kr][V] or NULL
-  const uint16_t* x;      // [tokens][G]
-  void* y;                // [tokens][O]
-  const uint16_t* scale;  // [G] column order
-  const uint16_t* wbias;  // [G] column order
-  const uint16_t* bias;   // [O] or NULL
-  const uint16_t* perm;   // [G] or NULL
-  int N, G, O, row_words, tokens, out_f32, n_groups;
-  int ib, rb, res_bytes;  // index widths; bytes of the residual table (RES = 1: copied into LDS)
-};
-
-typedef _Float16 gx_h8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 gx_b8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t gx_u32_a4 __attribute__((aligned(4)));
 typedef uint32_t gx_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-template <typename DT>
-static __device__ __forceinline__ f32x4 gx_mfma(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<DT, F16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gx_h8_t, a), __builtin_bit_cast(gx_h8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gx_b8_t, a), __builtin_bit_cast(gx_b8_t, b), c, 0, 0, 0);
-}
 
 // element E (compile time) of T bits (wave uniform) out of the normalised window n[0..7]: it sits at bit E * T, word (E * T) >> 5 <= E
 template <int E>
@@ -78,14 +45,14 @@ static __device__ __forceinline__ uint32_t gx_elem(const uint32_t (&n)[8], int T
 }
 
 template <typename DT, int V, int RES, bool PERM>
-__global__ __launch_bounds__(kGXThreads) void gemm_gatherx_kernel(const GemmGatherXParams P) {
+__global__ __launch_bounds__(kGTThreads) void gemm_gatherx_kernel(const GemmGatherParams P) {
   static_assert(V == 8 || V == 16, "vector length");
   static_assert(RES >= 0 && RES <= 2, "residual: none, LDS, L2");
   constexpr int kRows = 16 / V;   // vector-rows per row group (16 outputs)
   constexpr int EB = V * 2;       // bytes per codebook entry
   extern __shared__ __attribute__((aligned(16))) unsigned char gx_smem[];
   u32x4* const tile = (u32x4*)gx_smem;                              // [chunk][16 outputs]: 32 KiB
-  const unsigned char* const rtab = gx_smem + kGXTileBytes;         // RES = 1: the residual table
+  const unsigned char* const rtab = gx_smem + kGTTileBytes;         // RES = 1: the residual table
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int G = P.G, N = P.N, O = P.O, tokens = P.tokens;
   const int T = P.ib + P.rb, ib = P.ib;
@@ -93,15 +60,15 @@ __global__ __launch_bounds__(kGXThreads) void gemm_gatherx_kernel(const GemmGath
   // the 9th window word: 8 T bits + the largest offset (24, 16 or 0 bits: T odd, T % 4 == 2, T % 4 == 0) beyond 8 words (T = 31)
   const bool need9 = 8 * T + ((T & 1) ? 24 : (T & 2) ? 16 : 0) > 256;
   const int last = P.row_words - 1;
-  const int n_tiles = (G + kGXTile - 1) / kGXTile;
+  const int n_tiles = (G + kGTTile - 1) / kGTTile;
   if constexpr (RES == 1) {
     const int n16 = P.res_bytes >> 4;
-    for (int i = tid; i < n16; i += kGXThreads)
-      *(u32x4*)(gx_smem + kGXTileBytes + (size_t)i * 16) = *(const u32x4*)(P.rcent + (size_t)i * 16);
+    for (int i = tid; i < n16; i += kGTThreads)
+      *(u32x4*)(gx_smem + kGTTileBytes + (size_t)i * 16) = *(const u32x4*)(P.rcent + (size_t)i * 16);
     __syncthreads();
   }
   // dequant role: 8 consecutive columns (chunk dch) of 8 outputs: V = 8 vector-row dr of the group, V = 16 half dr of its one entry
-  const int dr = tid >> 7, dch = tid & (kGXChunks - 1);
+  const int dr = tid >> 7, dch = tid & (kGTChunks - 1);
   const uint32_t hoff = V == 16 ? (uint32_t)dr * 16u : 0u;
   const uint32_t wslot = (uint32_t)(dch * 16 + dr * 8), wx = (uint32_t)(dch & 7);
   // MFMA role: lane (token / output mj, k group mkg); step i reads chunk 32 wave + 8 mkg + i
@@ -112,8 +79,7 @@ __global__ __launch_bounds__(kGXThreads) void gemm_gatherx_kernel(const GemmGath
   for (int rg = blockIdx.x; rg < P.n_groups; rg += gridDim.x) {
     const int row = V == 16 ? rg : rg * kRows + dr;
     const uint32_t* const irow = P.idx + (size_t)(row < N ? row : N - 1) * P.row_words;
-    // (tiles past the end clamp to the last chunk of the row: every address stays inside the layer)
-    auto dcol = [&](int t) { const int c = t * kGXTile + dch * 8; return c < G ? c : G - 8; };
+    auto dcol = [&](int t) { return gt_dcol(t, dch, G); };
     auto load_idx = [&](int t, uint32_t (&n)[8]) {
       const uint32_t cb = (uint32_t)(dcol(t) >> 3) * (uint32_t)T;   // the chunk's first byte in the row
       const int w0 = (int)(cb >> 2);
@@ -132,12 +98,6 @@ __global__ __launch_bounds__(kGXThreads) void gemm_gatherx_kernel(const GemmGath
 #pragma unroll
       for (int j = 0; j < 8; ++j) n[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], off);
     };
-    auto load_sb = [&](int t, uint32_t (&s)[4], uint32_t (&b)[4]) {
-      const uint32_t* s32 = (const uint32_t*)(P.scale + dcol(t));
-      const uint32_t* b32 = (const uint32_t*)(P.wbias + dcol(t));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { s[q] = s32[q]; b[q] = b32[q]; }
-    };
     u32x4 cv[8], rv[RES ? 8 : 1];
     auto gather1 = [&](int e, uint32_t v) {
       cv[e] = *(const u32x4*)(P.cent + (size_t)(v & mmask) * EB + hoff);
@@ -152,90 +112,37 @@ __global__ __launch_bounds__(kGXThreads) void gemm_gatherx_kernel(const GemmGath
     };
     uint32_t wq[8], sp[4], bp[4], sp_next[4], bp_next[4];
     load_idx(0, wq);
-    load_sb(0, sp, bp);
+    gt_load_sb(P, dcol(0), sp, bp);
     gather(wq);
     load_idx(1, wq);
-    load_sb(1, sp_next, bp_next);
+    gt_load_sb(P, dcol(1), sp_next, bp_next);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 
     for (int t = 0; t < n_tiles; ++t) {
-      // ---- this tile's A operands: 8 x 16 bytes of x, 64 consecutive columns of one token
       u32x4 xa[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int col = t * kGXTile + (mch0 + i) * 8;
-        const int cc = col < G ? col : G - 8;
-        if constexpr (PERM) {
-          const uint32_t* p32 = (const uint32_t*)(P.perm + cc);
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const uint32_t pv = p32[q];
-            xa[i][q] = (uint32_t)xrow[pv & 0xffffu] | ((uint32_t)xrow[pv >> 16] << 16);
-          }
-        } else {
-          xa[i] = *(const u32x4*)(xrow + cc);
-        }
-      }
-      // ---- rebuild 8 columns x 8 outputs: c + r, * s, + b, each rounded to 16 bits
-      const bool dvalid = t * kGXTile + dch * 8 < G;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        uint32_t v[4] = {cv[e][0], cv[e][1], cv[e][2], cv[e][3]};
-        if constexpr (RES != 0) {
-          const uint32_t r[4] = {rv[e][0], rv[e][1], rv[e][2], rv[e][3]};
-          DT::add4(v, r);
-        }
-        DT::scale_bias4(v, sp[e >> 1], e & 1, bp[e >> 1], e & 1);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) cv[e][p] = dvalid ? v[p] : 0u;
-      }
+      gt_load_a<PERM>(P.perm, xrow, G, mch0, t, xa);
+      gt_rebuild<DT, RES != 0>(cv, rv, sp, bp, t * kGTTile + dch * 8 < G);
       __syncthreads();   // the previous tile's MFMA reads (and the previous row group's sums) are done
-      // ---- transpose to 8 outputs x 8 k values and write them in B-operand order
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const u32x4 lo = {__builtin_amdgcn_perm(cv[1][p], cv[0][p], 0x05040100u), __builtin_amdgcn_perm(cv[3][p], cv[2][p], 0x05040100u),
-                          __builtin_amdgcn_perm(cv[5][p], cv[4][p], 0x05040100u), __builtin_amdgcn_perm(cv[7][p], cv[6][p], 0x05040100u)};
-        const u32x4 hi = {__builtin_amdgcn_perm(cv[1][p], cv[0][p], 0x07060302u), __builtin_amdgcn_perm(cv[3][p], cv[2][p], 0x07060302u),
-                          __builtin_amdgcn_perm(cv[5][p], cv[4][p], 0x07060302u), __builtin_amdgcn_perm(cv[7][p], cv[6][p], 0x07060302u)};
-        tile[wslot + ((uint32_t)(2 * p) ^ wx)] = lo;
-        tile[wslot + ((uint32_t)(2 * p + 1) ^ wx)] = hi;
-      }
+      gt_write_tile(tile, wslot, wx, cv);
       // ---- the next tile's gathers fly during the MFMA phase; the index window and scale / bias of the one after follow
       if (t + 1 < n_tiles) {
         gather(wq);
 #pragma unroll
         for (int q = 0; q < 4; ++q) { sp[q] = sp_next[q]; bp[q] = bp_next[q]; }
         load_idx(t + 2, wq);
-        load_sb(t + 2, sp_next, bp_next);
+        gt_load_sb(P, dcol(t + 2), sp_next, bp_next);
       }
       __syncthreads();   // tile complete
+      // ---- this wave's 8 K-steps (kept in this file: as a shared function it cost 3 - 8 % at 16 tokens, profiles/r17)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const bool live = mj < tokens && t * kGXTile + (mch0 + i) * 8 < G;
+        const bool live = mj < tokens && t * kGTTile + (mch0 + i) * 8 < G;
         const u32x4 a = {live ? xa[i][0] : 0u, live ? xa[i][1] : 0u, live ? xa[i][2] : 0u, live ? xa[i][3] : 0u};
         const u32x4 b = tile[(mch0 + i) * 16 + (mj ^ i)];   // ((mch0 + i) & 7 == i)
-        acc = gx_mfma<DT>(a, b, acc);
+        acc = gt_mfma<DT>(a, b, acc);
       }
     }
-    // ---- the 4 waves' partial D, added in wave order; D element (token = (l >> 4) * 4 + reg, output = l & 15)
-    __syncthreads();
-    float* const scr = (float*)gx_smem;   // [wave][reg][lane]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) scr[(wave * 4 + r) * 64 + lane] = acc[r];
-    __syncthreads();
-    {
-      const int r = tid >> 6, l = tid & 63;
-      float sum = scr[r * 64 + l];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) sum += scr[(w * 4 + r) * 64 + l];
-      const int token = (l >> 4) * 4 + r;
-      const int o = rg * 16 + (l & 15);
-      if (token < tokens && o < O) {
-        if (P.bias) sum += DT::to_float(P.bias[o]);
-        if (P.out_f32) ((float*)P.y)[(size_t)token * O + o] = sum;
-        else ((uint16_t*)P.y)[(size_t)token * O + o] = DT::from_float(sum);
-      }
-    }
+    gt_epilogue<DT>(P, tid, lane, wave, (float*)gx_smem, rg, acc);
   }
 }
 
@@ -267,27 +174,24 @@ GemmGatherXDecision gemm_gatherx_decide(const VptqLayerDesc& d, int tokens) {
   D.res_bytes = d.num_res_centroids * d.vector_len * 2;
   D.res = D.res_bytes == 0 ? 0 : D.res_bytes <= kGXResLdsMax ? 1 : 2;
   D.tok = tokens;
-  D.tiles = (d.group_size + kGXTile - 1) / kGXTile;
-  D.lds = kGXTileBytes + (D.res == 1 ? D.res_bytes : 0);
+  D.tiles = (d.group_size + kGTTile - 1) / kGTTile;
+  D.lds = kGTTileBytes + (D.res == 1 ? D.res_bytes : 0);
   D.wgcu = kGXLdsPerCu / D.lds < kGXMaxWgPerCu ? kGXLdsPerCu / D.lds : kGXMaxWgPerCu;
-  const int rows = 16 / (D.v == 16 ? 16 : 8);
-  D.n_groups = (d.num_indices + rows - 1) / rows;
-  const int slots = device_cus() * D.wgcu;
-  D.grid = D.n_groups < slots ? D.n_groups : slots;
-  D.rgs = D.grid > 0 ? (D.n_groups + D.grid - 1) / D.grid : 0;
+  const GemmGatherGrid g = gemm_gather_grid(d.num_indices, 16 / (D.v == 16 ? 16 : 8), D.wgcu);
+  D.n_groups = g.n_groups; D.grid = g.grid; D.rgs = g.rgs;
   return D;
 }
 
 template <typename DT, int V, int RES>
-static hipError_t launch_gx(const GemmGatherXParams& P, const GemmGatherXDecision& D, hipStream_t st) {
-  const dim3 grid(D.grid), block(kGXThreads);
+static hipError_t launch_gx(const GemmGatherParams& P, const GemmGatherXDecision& D, hipStream_t st) {
+  const dim3 grid(D.grid), block(kGTThreads);
   if (D.perm) hipLaunchKernelGGL((gemm_gatherx_kernel<DT, V, RES, true>), grid, block, D.lds, st, P);
   else hipLaunchKernelGGL((gemm_gatherx_kernel<DT, V, RES, false>), grid, block, D.lds, st, P);
   return hipGetLastError();
 }
 
 template <typename DT, int V>
-static hipError_t launch_gx_v(const GemmGatherXParams& P, const GemmGatherXDecision& D, hipStream_t st) {
+static hipError_t launch_gx_v(const GemmGatherParams& P, const GemmGatherXDecision& D, hipStream_t st) {
   switch (D.res) {
     case 0: return launch_gx<DT, V, 0>(P, D, st);
     case 1: return launch_gx<DT, V, 1>(P, D, st);
@@ -297,7 +201,7 @@ static hipError_t launch_gx_v(const GemmGatherXParams& P, const GemmGatherXDecis
 }
 
 template <typename DT>
-static hipError_t launch_gx_dt(const GemmGatherXParams& P, const GemmGatherXDecision& D, hipStream_t st) {
+static hipError_t launch_gx_dt(const GemmGatherParams& P, const GemmGatherXDecision& D, hipStream_t st) {
   switch (D.v) {
     case 8: return launch_gx_v<DT, 8>(P, D, st);
     case 16: return launch_gx_v<DT, 16>(P, D, st);
@@ -308,20 +212,8 @@ static hipError_t launch_gx_dt(const GemmGatherXParams& P, const GemmGatherXDeci
 hipError_t launch_gemm_gatherx(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st) {
   const GemmGatherXDecision D = gemm_gatherx_decide(d, tokens);
   if (D.grid < 1 || tokens < 1 || tokens > 16 || D.lds > 65536) return hipErrorInvalidValue;
-  GemmGatherXParams P = {};
-  P.idx = (const uint32_t*)d.indices;
-  P.cent = (const char*)d.centroids;
-  P.rcent = d.num_res_centroids > 0 ? (const char*)d.res_centroids : nullptr;
-  P.x = (const uint16_t*)x;
-  P.y = y;
-  P.scale = (const uint16_t*)(d.perm ? d.scale_permuted : d.weight_scale);
-  P.wbias = (const uint16_t*)(d.perm ? d.bias_permuted : d.weight_bias);
-  P.bias = (const uint16_t*)d.bias;
-  P.perm = d.perm;
-  P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
-  P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
-  P.n_groups = D.n_groups;
-  P.ib = D.ib; P.rb = D.rb; P.res_bytes = D.res_bytes;
+  GemmGatherParams P = gemm_gather_params(d, x, y, tokens, out_f32, D.n_groups);
+  P.ib = D.ib; P.rb = D.rb; P.res_bytes = D.res_bytes;   // (the table copied into LDS is the one D.lds has room for)
   return D.f16 ? launch_gx_dt<F16>(P, D, st) : launch_gx_dt<BF16>(P, D, st);
 }
 

@@ -200,7 +200,8 @@ hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int 
                             hipStream_t st);
 
 // gemm_gather.hip - gemv_gather's layers (v = 8, k = 65536, residual 0 / 256 / 65536), up to 16 tokens in one launch (tokens = MFMA M;
-// centroid rows gathered from L2, the rebuilt tile in LDS in operand order; reference roundings; no workspace)
+// centroid rows gathered from L2, the rebuilt tile in LDS in operand order; reference roundings; no workspace).  The kernels'
+// argument block, its fill and the launch-shape arithmetic are gemm_gather_host.h's, the device phases gemm_gather_tile.h's: shared with gemm_gatherx.hip
 bool gemm_gather_eligible(const VptqLayerDesc& d, int tokens);
 // what launch_gemm_gather launches: gemm_gather_kernel<DT, T, PERM>; tiles: column tiles per row group; rgs: the most row groups
 // one workgroup walks

@@ -93,51 +93,34 @@ _DEQUANT_SLICED_MAX_COLS = 4096
 _DEQUANT_SLICED_MODE = (B.tune_env("VPTQ_DEQUANT_SLICED", "auto") or "auto").strip().lower()
 
 
-# WHICH (format, shape, token count) take the large-codebook formats' batched-decode kernel (`vptq_quant_gemm_gather`, gemm_gather.hip:
-# 1 - 16 tokens in one launch) in place of the route they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.
-# A cell is routed only where the new kernel was MEASURED to beat the route it replaces by more than the larger of 5 % and three times
-# the run-to-run spread, both in one process on one box (tools/gemm_gather_bench.py writes that table; profiles/r15/README.md).  A
-# cell is (residual centroids, least index elements = vector-rows x columns, least tokens).  The table (profiles/r15/table.md: one
-# MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16): from 9 tokens the kernel beats the dense route in
-# every measured cell of the three formats (0.51 - 0.86 of its time), so 9 - 16 tokens are routed from the smallest measured layer
-# (4096 x 4096 = 2 M index elements) up; at 5 - 8 tokens it is level with gemv_gather in most cells (0.84 - 1.12), which stays.
-# VPTQ_GEMM_GATHER=1 / 0 (with VPTQ_TUNING=1): every supported layer from 5 tokens / none - what the bench tool, the tests and a user
-# who has measured their own shapes use.
-GEMM_GATHER_MAX_TOKENS = 16
-_GEMM_GATHER_MODE = (B.tune_env("VPTQ_GEMM_GATHER", "auto") or "auto").strip().lower()
-_GEMM_GATHER_CELLS = ((0, 2 << 20, 9), (256, 2 << 20, 9), (65536, 2 << 20, 9))   # ((num_res_centroids, min_index_elements, min_tokens), ...)
-
-
-def gemm_gather_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
-    """does a layer of this format (vector length, main / residual codebook entries) and shape take `vptq_quant_gemm_gather` for
-    `tokens` tokens?  Pure: no device, no library (whether the library serves the layer - one codebook group, no outliers, scale and
-    bias, alignment - is `vptq_quant_gemm_gather_supported`'s answer)."""
-    if vector_len != 8 or num_centroids != 65536 or num_res_centroids not in (0, 256, 65536):
-        return False
-    if _GEMM_GATHER_MODE in ("0", "off"):
-        return False
-    if _GEMM_GATHER_MODE in ("1", "on"):
-        return 5 <= tokens <= GEMM_GATHER_MAX_TOKENS
-    if not 5 <= tokens <= GEMM_GATHER_MAX_TOKENS:
-        return False
-    n_el = ((out_features + 7) // 8) * in_features
-    return any(kr == num_res_centroids and n_el >= min_el and tokens >= min_tok for kr, min_el, min_tok in _GEMM_GATHER_CELLS)
-
-
-# WHICH (format, shape, token count) take the generic batched-decode kernel (`vptq_quant_gemm_gatherx`, gemm_gatherx.hip: vector length
-# 8 / 16, 16384 ... 65536 main centroids, any residual codebook - every large-codebook format `gemm_gather_route` does not own) in place
-# of the route they had (5 - 8 tokens: the gemv_gatherx launches; 9 - 16: the dense route): the same rule as above, the same tool
-# (tools/gemm_gather_bench.py --formats ... writes profiles/r16/table.md).  A cell is (vector length, main centroids, residual
-# centroids, least index elements = vector-rows x columns, least tokens); a region is routed only where EVERY measured cell in it wins
-# in both dtypes.  The table (one MI355X, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16):
+# WHICH (format, shape, token count) take a batched-decode kernel of the large-codebook formats (1 - 16 tokens in one launch) in place
+# of the route they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.
+# A layer has ONE such kernel: v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids belong to `vptq_quant_gemm_gather`
+# (gemm_gather.hip), every other vector length 8 / 16, 16384 ... 65536 main centroids, any residual codebook to
+# `vptq_quant_gemm_gatherx` (gemm_gatherx.hip); `_batched_decode_entry` says which.  Each has a knob and a table of cells; a cell is
+# (vector length, main centroids, residual centroids, least index elements = vector-rows x columns, least tokens).  A cell is routed
+# only where the kernel was MEASURED to beat the route it replaces (5 - 8 tokens: the gemv_gather / gemv_gatherx launches; 9 - 16:
+# the dense route) by more than the larger of 5 % and three times the run-to-run spread, both in one process on one box
+# (tools/gemm_gather_bench.py writes the tables); a region is routed only where EVERY measured cell in it wins in both dtypes.
+# VPTQ_GEMM_GATHER=1 / 0, VPTQ_GEMM_GATHERX=1 / 0 (with VPTQ_TUNING=1): every supported layer of that kernel from 5 tokens / none -
+# what the bench tool, the tests and a user who has measured their own shapes use.
+#
+# gemm_gather (profiles/r15/table.md, profiles/r15/README.md: one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 /
+# 9 / 12 / 16): from 9 tokens the kernel beats the dense route in every measured cell of the three formats (0.51 - 0.86 of its time),
+# so 9 - 16 tokens are routed from the smallest measured layer (4096 x 4096 = 2 M index elements) up; at 5 - 8 tokens it is level
+# with gemv_gather in most cells (0.84 - 1.12), which stays.
+#
+# gemm_gatherx (profiles/r16/table.md: one MI355X, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16):
 #   v16-k65536-0, v16-k65536-1024     every cell wins (0.48 - 0.93 of the parent's time): 5 - 16 tokens from 4096 x 4096 (1 M elements) up
 #   v8-k32768-0, v8-k65536-4096       9 - 16 tokens: every cell (0.53 - 0.91); 5 - 8 tokens: only from 8192 x 8192 (8 M elements) up (0.73 - 0.94)
 #   v16-k65536-65536                  wins at 5 - 8 tokens (0.66 - 0.88) but is level with the dense route at 9 - 16 on the larger
 #                                     layers (0.94 - 1.05 at 8192 x 8192): a route has to be monotone in tokens, so nothing is routed
 # Formats that were not measured (v16-k65536-32768 / -256 / -64, v8-k65536-4, v8-k16384-0) and smaller layers are not routed.
-# VPTQ_GEMM_GATHERX=1 / 0 (with VPTQ_TUNING=1): every supported layer from 5 tokens / none.
+GEMM_GATHER_MAX_TOKENS = 16
+_GEMM_GATHER_MODE = (B.tune_env("VPTQ_GEMM_GATHER", "auto") or "auto").strip().lower()
+_GEMM_GATHER_CELLS = ((8, 65536, 0, 2 << 20, 9), (8, 65536, 256, 2 << 20, 9), (8, 65536, 65536, 2 << 20, 9))
 _GEMM_GATHERX_MODE = (B.tune_env("VPTQ_GEMM_GATHERX", "auto") or "auto").strip().lower()
-_GEMM_GATHERX_CELLS = (   # ((vector_len, num_centroids, num_res_centroids, min_index_elements, min_tokens), ...)
+_GEMM_GATHERX_CELLS = (
     (16, 65536, 0, 1 << 20, 5), (16, 65536, 1024, 1 << 20, 5),
     (8, 32768, 0, 2 << 20, 9), (8, 32768, 0, 8 << 20, 5),
     (8, 65536, 4096, 2 << 20, 9), (8, 65536, 4096, 8 << 20, 5),
@@ -148,25 +131,41 @@ def _pow2(n: int) -> bool:
     return n > 0 and (n & (n - 1)) == 0
 
 
+def _batched_decode_entry(vector_len: int, num_centroids: int, num_res_centroids: int):
+    """the library entry whose kernel has this format ("vptq_quant_gemm_gather" / "vptq_quant_gemm_gatherx"), or None"""
+    if vector_len == 8 and num_centroids == 65536 and num_res_centroids in (0, 256, 65536):
+        return "vptq_quant_gemm_gather"
+    if vector_len in (8, 16) and _pow2(num_centroids) and 16384 <= num_centroids <= 65536 and \
+            (not num_res_centroids or (_pow2(num_res_centroids) and num_res_centroids <= 65536)):
+        return "vptq_quant_gemm_gatherx"
+    return None
+
+
+def _batched_decode_route(mode, cells, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens) -> bool:
+    """the tail both route functions share: the knob, the token window, the measured cells"""
+    if mode in ("0", "off") or not 5 <= tokens <= GEMM_GATHER_MAX_TOKENS:
+        return False
+    if mode in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and n_el >= min_el and tokens >= min_tok
+               for v, k, kr, min_el, min_tok in cells)
+
+
+def gemm_gather_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
+    """does a layer of this format (vector length, main / residual codebook entries) and shape take `vptq_quant_gemm_gather` for
+    `tokens` tokens?  Pure: no device, no library (whether the library serves the layer - one codebook group, no outliers, scale and
+    bias, alignment - is `vptq_quant_gemm_gather_supported`'s answer)."""
+    return _batched_decode_entry(vector_len, num_centroids, num_res_centroids) == "vptq_quant_gemm_gather" and \
+        _batched_decode_route(_GEMM_GATHER_MODE, _GEMM_GATHER_CELLS, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
+
+
 def gemm_gatherx_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
     """does a layer of this format and shape take `vptq_quant_gemm_gatherx` for `tokens` tokens?  Pure: no device, no library (one
     codebook group, no outliers, scale and bias, alignment: `vptq_quant_gemm_gatherx_supported`'s answer).  Never for the formats
     `gemm_gather_route` owns (v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids): a layer has one batched-decode kernel."""
-    if vector_len not in (8, 16) or not _pow2(num_centroids) or not 16384 <= num_centroids <= 65536 or in_features % 8:
-        return False
-    if num_res_centroids and (not _pow2(num_res_centroids) or num_res_centroids > 65536):
-        return False
-    if vector_len == 8 and num_centroids == 65536 and num_res_centroids in (0, 256, 65536):
-        return False
-    if _GEMM_GATHERX_MODE in ("0", "off"):
-        return False
-    if not 5 <= tokens <= GEMM_GATHER_MAX_TOKENS:
-        return False
-    if _GEMM_GATHERX_MODE in ("1", "on"):
-        return True
-    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
-    return any(v == vector_len and k == num_centroids and kr == num_res_centroids and n_el >= min_el and tokens >= min_tok
-               for v, k, kr, min_el, min_tok in _GEMM_GATHERX_CELLS)
+    return _batched_decode_entry(vector_len, num_centroids, num_res_centroids) == "vptq_quant_gemm_gatherx" and in_features % 8 == 0 and \
+        _batched_decode_route(_GEMM_GATHERX_MODE, _GEMM_GATHERX_CELLS, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
 
 
 def _dense_from_layout(layer) -> bool:
@@ -551,12 +550,8 @@ class VQuantLinear(nn.Module):
                 "path, which is outside this inference package; construct the layer with "
                 "enable_proxy_error=False (HF does).")
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_gg_cand", True):
-            y = self._gemm_gather_cached(x, tokens)   # (the large-codebook formats' batched decode, where `gemm_gather_route` says so)
-            if y is not None:
-                return y
-        if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_ggx_cand", True):
-            y = self._gemm_gatherx_cached(x, tokens)   # (... and its generic sibling, where `gemm_gatherx_route` says so)
+        if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_bd_entry", True):
+            y = self._batched_decode_cached(x, tokens)   # (the large-codebook formats' batched decode, where the layer's route function says so)
             if y is not None:
                 return y
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
@@ -672,7 +667,7 @@ class VQuantLinear(nn.Module):
 
     # derived, device-bound state (ctypes descriptors, the sliced layout, sibling links) is rebuilt on demand: it is
     # neither pickled nor deep-copied with the module (torch.save(model), copy.deepcopy(model))
-    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_gg_ok")
+    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_ok")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -1025,26 +1020,30 @@ class VQuantLinear(nn.Module):
             B.check(rc, "vptq_quant_gemv")
         return y
 
-    def _gemm_gather_cached(self, x: torch.Tensor, tokens: int):
-        """5 - 16 tokens of a large-codebook layer in ONE launch of `vptq_quant_gemm_gather` where `gemm_gather_route` gives the
-        layer's (format, shape, tokens) to it and the library serves the layer; None: the caller's other routes.  Compact layers
-        hand it the repacked stream, as the gather route does."""
-        if "_gg_cand" not in self.__dict__:
-            # (static module configuration: decided once, every other layer pays one dict look-up per call)
-            self.__dict__["_gg_cand"] = bool(self.vector_len == 8 and self.num_centroids == 65536 and self.num_codebooks == 1 and
-                                             not self.enable_outlier and self.enable_norm and
-                                             getattr(B.lib(), "vptq_quant_gemm_gather", None) is not None)
-            if not self.__dict__["_gg_cand"]:
-                return None
-        if not gemm_gather_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
+    def _batched_decode_cached(self, x: torch.Tensor, tokens: int):
+        """5 - 16 tokens of a large-codebook layer in ONE launch of the layer's batched-decode entry (`vptq_quant_gemm_gather` or
+        `vptq_quant_gemm_gatherx`: `_batched_decode_entry`) where that entry's route function gives the layer's (format, shape,
+        tokens) to it and the library serves the layer; None: the caller's other routes.  Compact layers hand it the repacked
+        stream, as the gather route does."""
+        entry = self.__dict__.get("_bd_entry")
+        if entry is None:
+            # (static module configuration: decided once, every other layer pays one dict look-up per call; False: no entry)
+            entry = _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self))
+            if entry is None or self.num_codebooks != 1 or self.enable_outlier or not self.enable_norm or getattr(B.lib(), entry, None) is None:
+                entry = False
+            self.__dict__["_bd_entry"] = entry
+        if not entry:
+            return None
+        route = gemm_gather_route if entry == "vptq_quant_gemm_gather" else gemm_gatherx_route
+        if not route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
                 (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
             return None
         cache = self._descriptor()
         desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
-        ok = self.__dict__.get("_gg_ok")
+        ok = self.__dict__.get("_bd_ok")
         if ok is None or ok[0] != cache.generation:
-            ok = (cache.generation, bool(B.lib().vptq_quant_gemm_gather_supported(desc, GEMM_GATHER_MAX_TOKENS)))
-            self.__dict__["_gg_ok"] = ok
+            ok = (cache.generation, bool(getattr(B.lib(), entry + "_supported")(desc, GEMM_GATHER_MAX_TOKENS)))
+            self.__dict__["_bd_ok"] = ok
         if not ok[1] or x.shape[-1] != self.in_features or x.dtype != wdtype or x.device != dev:
             return None   # (the other routes raise the shape / dtype / device errors)
         if not x.is_contiguous():
@@ -1057,46 +1056,9 @@ class VQuantLinear(nn.Module):
             sp = B.current_stream_ptr(dev)
             if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
                 desc = self._repacked_desc(desc, dev_index, sp)
-            rc = B.lib().vptq_quant_gemm_gather(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
+            rc = getattr(B.lib(), entry)(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
         if rc:
-            B.check(rc, "vptq_quant_gemm_gather")
-        return y
-
-    def _gemm_gatherx_cached(self, x: torch.Tensor, tokens: int):
-        """5 - 16 tokens of a large-codebook layer `gemm_gather_route` does not own in ONE launch of `vptq_quant_gemm_gatherx`, where
-        `gemm_gatherx_route` gives the layer's (format, shape, tokens) to it and the library serves the layer; None: the caller's other
-        routes.  Compact layers hand it the repacked stream, exactly as `_gemm_gather_cached` does."""
-        if "_ggx_cand" not in self.__dict__:
-            # (static module configuration: decided once, every other layer pays one dict look-up per call)
-            self.__dict__["_ggx_cand"] = bool(self.vector_len in (8, 16) and 16384 <= self.num_centroids <= 65536 and
-                                              self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm and
-                                              getattr(B.lib(), "vptq_quant_gemm_gatherx", None) is not None)
-            if not self.__dict__["_ggx_cand"]:
-                return None
-        if not gemm_gatherx_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
-                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
-            return None
-        cache = self._descriptor()
-        desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
-        ok = self.__dict__.get("_ggx_ok")
-        if ok is None or ok[0] != cache.generation:
-            ok = (cache.generation, bool(B.lib().vptq_quant_gemm_gatherx_supported(desc, GEMM_GATHER_MAX_TOKENS)))
-            self.__dict__["_ggx_ok"] = ok
-        if not ok[1] or x.shape[-1] != self.in_features or x.dtype != wdtype or x.device != dev:
-            return None   # (the other routes raise the shape / dtype / device errors)
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if x.data_ptr() % 16:
-            return None
-        y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
-        cp = self.__dict__.get("_compact")
-        with torch.cuda.device(dev):
-            sp = B.current_stream_ptr(dev)
-            if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
-                desc = self._repacked_desc(desc, dev_index, sp)
-            rc = B.lib().vptq_quant_gemm_gatherx(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
-        if rc:
-            B.check(rc, "vptq_quant_gemm_gatherx")
+            B.check(rc, entry)
         return y
 
     def _dense_cached(self, x: torch.Tensor) -> torch.Tensor:

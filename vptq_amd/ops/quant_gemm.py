@@ -201,19 +201,15 @@ def quant_gemm(
         gdesc = desc
         if tokens > B.GEMV_ANY_FORMAT_TOKENS and tokens > B.lib().vptq_quant_gemv_max_tokens(desc):
             desc = None  # 9-16 tokens: only the canonical format's GEMV still beats dequant + GEMM
-        # the large-codebook formats' batched decode (gemm_gather.hip): the token counts `gemm_gather_route` gives it, as
-        # `VQuantLinear.forward` routes them
-        from vptq_amd.layers.vqlinear import gemm_gather_route
-        if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
-                gemm_gather_route(vector_len, num_centroids, num_res_centroids if enable_residual else 0, out_features, in_features, tokens) and \
-                B.lib().vptq_quant_gemm_gather_supported(gdesc, tokens):
-            return quant_gemm_gather(x, gdesc, out_features)
-        # ... and its generic sibling (gemm_gatherx.hip) for the large-codebook formats that one does not own
-        from vptq_amd.layers.vqlinear import gemm_gatherx_route
-        if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
-                gemm_gatherx_route(vector_len, num_centroids, num_res_centroids if enable_residual else 0, out_features, in_features, tokens) and \
-                B.lib().vptq_quant_gemm_gatherx_supported(gdesc, tokens):
-            return quant_gemm_gatherx(x, gdesc, out_features)
+        # the large-codebook formats' batched decode (gemm_gather.hip, then its generic sibling gemm_gatherx.hip for the formats that
+        # one does not own): the token counts the kernel's route function gives it, as `VQuantLinear.forward` routes them
+        from vptq_amd.layers.vqlinear import gemm_gather_route, gemm_gatherx_route
+        kr = num_res_centroids if enable_residual else 0
+        for route, entry in ((gemm_gather_route, "vptq_quant_gemm_gather"), (gemm_gatherx_route, "vptq_quant_gemm_gatherx")):
+            if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
+                    route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
+                    getattr(B.lib(), entry + "_supported")(gdesc, tokens):
+                return _quant_gemm_batched(entry, x, gdesc, out_features)
     if desc is not None:
         y = torch.empty(x.shape[:-1] + (out_features,), dtype=x.dtype, device=dev)
         flags = _FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
@@ -275,20 +271,25 @@ def quant_gemm_fused(x: torch.Tensor, desc, out_features: int) -> torch.Tensor:
     return y
 
 
-def quant_gemm_gather(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
-    """y = x @ W^T + bias for 1 - 16 tokens of a large-codebook layer (v = 8, 65536 main centroids, 0 / 256 / 65536 residual
-    centroids) in ONE launch (`vptq_quant_gemm_gather`, gemm_gather.hip: centroid rows gathered from L2, the contraction on the
-    matrix pipe, the reference's roundings; replaces dequant + F.linear for 9 - 16 tokens).  `desc` = a LayerDesc of a layer
-    `vptq_quant_gemm_gather_supported` accepts; out_f32: the un-rounded fp32 sums."""
+def _quant_gemm_batched(entry: str, x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """1 - 16 tokens in ONE launch of a batched-decode entry of the large-codebook formats (`quant_gemm_gather` / `quant_gemm_gatherx`)"""
     tokens = x.numel() // x.shape[-1]
     dev = x.device
     if not x.is_contiguous():
         x = x.contiguous()
     y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
     with torch.cuda.device(dev):
-        B.check(B.lib().vptq_quant_gemm_gather(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
-                                               B.current_stream_ptr(dev)), "vptq_quant_gemm_gather")
+        B.check(getattr(B.lib(), entry)(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
+                                        B.current_stream_ptr(dev)), entry)
     return y
+
+
+def quant_gemm_gather(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 1 - 16 tokens of a large-codebook layer (v = 8, 65536 main centroids, 0 / 256 / 65536 residual
+    centroids) in ONE launch (`vptq_quant_gemm_gather`, gemm_gather.hip: centroid rows gathered from L2, the contraction on the
+    matrix pipe, the reference's roundings; replaces dequant + F.linear for 9 - 16 tokens).  `desc` = a LayerDesc of a layer
+    `vptq_quant_gemm_gather_supported` accepts; out_f32: the un-rounded fp32 sums."""
+    return _quant_gemm_batched("vptq_quant_gemm_gather", x, desc, out_features, out_f32)
 
 
 def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
@@ -296,15 +297,7 @@ def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool =
     65536 main centroids, any residual codebook) in ONE launch (`vptq_quant_gemm_gatherx`, gemm_gatherx.hip: the same structure with an
     index path for any total width and 32-byte entries; the reference's roundings).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gatherx_supported` accepts; out_f32: the un-rounded fp32 sums."""
-    tokens = x.numel() // x.shape[-1]
-    dev = x.device
-    if not x.is_contiguous():
-        x = x.contiguous()
-    y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
-    with torch.cuda.device(dev):
-        B.check(B.lib().vptq_quant_gemm_gatherx(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
-                                                B.current_stream_ptr(dev)), "vptq_quant_gemm_gatherx")
-    return y
+    return _quant_gemm_batched("vptq_quant_gemm_gatherx", x, desc, out_features, out_f32)
 
 
 def quant_gemv_v2(
