@@ -1225,3 +1225,19 @@ def test_layer_cache_record_keeps_its_positions(monkeypatch):
     assert cache.max_tokens == B.lib().vptq_quant_gemv_max_tokens(cache.desc)
     stand_in = LayerCache(*range(11))
     assert stand_in[1] is stand_in.desc and stand_in[9] == stand_in.arithmetic_flags == 9
+
+
+def test_csrc_states_its_shared_idioms_once():
+    """the host idioms and the MFMA wrapper every kernel file used to re-state live in one file each: the dynamic-LDS opt-in and the
+    CU query in one header, the environment behind tune_env.h, the 16x16x32 f16 MFMA builtin in common.h"""
+    csrc = os.path.join(ROOT, "vptq_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    assert len(text) > 20, sorted(text)
+
+    def holders(word):
+        return [f for f, s in text.items() if word in s]
+
+    assert len(holders("hipFuncSetAttribute")) == 1, holders("hipFuncSetAttribute")
+    assert len(holders("multiProcessorCount")) == 1, holders("multiProcessorCount")
+    assert holders("getenv") == ["tune_env.h"]
+    assert holders("__builtin_amdgcn_mfma_f32_16x16x32_f16") == ["common.h"]

@@ -40,7 +40,6 @@
 #include "common.h"
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 using namespace vptq;
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
 
 // ---- hwmon sampling -----------------------------------------------------------------------------------------
 static std::string g_hwmon;

@@ -13,10 +13,6 @@ using namespace vptq;
 typedef _Float16 h8v_t __attribute__((ext_vector_type(8)));
 enum { RD = 1, MF = 2, XR = 4, PLAIN = 8, AH2 = 16, OLD = 32 };
 
-static __device__ __forceinline__ u32x2 lds_tr8(uint32_t a) {
-  typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(uintptr_t)a));
-}
 static __device__ __forceinline__ u32x2 lds_ld8(uint32_t a) {
   typedef __attribute__((address_space(3))) u32x2 lds_u2_t;
   return *(const lds_u2_t*)(uintptr_t)a;

@@ -142,10 +142,10 @@ int vptq_quant_gemv_max_tokens(const VptqLayerDesc* d) {
 enum Route { kRouteNone, kRouteGemmK256T, kRouteGemmK256, kRouteK256, kRouteGather, kRouteLds, kRouteGatherX, kRouteGeneric };
 
 static int batch_min_tokens() {
-  static std::atomic<int> v{-1};  // VPTQ_GEMM_MIN_TOKENS: smallest token count that takes the batched-decode kernel
-  // (at most 16: vptq_quant_gemv_max_tokens promises the batched kernel for 17+ tokens of such layers)
-  if (v < 0) { const char* ev = vptq::tune_env("VPTQ_GEMM_MIN_TOKENS"); const int w = ev ? atoi(ev) : 5; v = w > 16 ? 16 : (w < 1 ? 1 : w); }
-  return v;
+  // smallest token count that takes the batched-decode kernel (at most 16: vptq_quant_gemv_max_tokens promises the batched
+  // kernel for 17+ tokens of such layers)
+  static const int w = vptq::tune_int("VPTQ_GEMM_MIN_TOKENS", 5);
+  return w > 16 ? 16 : (w < 1 ? 1 : w);
 }
 
 // Smallest token count that takes the one-pass batched-decode kernel (gemm_k256t.hip).  Measured at 8192^2 / 4096^2
@@ -154,14 +154,9 @@ static int batch_min_tokens() {
 // tokens on gemm_k256 and 18-39 us for bf16 as launches of <= 4 tokens: the default route from 5 tokens for both
 // dtypes.  VPTQ_GEMMT_MIN_TOKENS_F16 / _BF16 override (tuning), VPTQ_GEMV_FORCE_BATCHED forces.
 static int batch_t_min_tokens(int dtype) {
-  static std::atomic<int> vf{-1}, vb{-1};
-  std::atomic<int>& v = dtype == VPTQ_DTYPE_F16 ? vf : vb;
-  if (v < 0) {
-    const char* ev = vptq::tune_env(dtype == VPTQ_DTYPE_F16 ? "VPTQ_GEMMT_MIN_TOKENS_F16" : "VPTQ_GEMMT_MIN_TOKENS_BF16");
-    const int w = ev ? atoi(ev) : 5;
-    v = w < 1 ? 1 : w;
-  }
-  return v;
+  static const int wf = vptq::tune_int("VPTQ_GEMMT_MIN_TOKENS_F16", 5), wb = vptq::tune_int("VPTQ_GEMMT_MIN_TOKENS_BF16", 5);
+  const int w = dtype == VPTQ_DTYPE_F16 ? wf : wb;
+  return w < 1 ? 1 : w;
 }
 
 // gemv_lds.hip: every token of one call in the same arithmetic - the one-token MFMA form only for one-token calls
@@ -347,20 +342,9 @@ int vptq_quant_gemv_grouped(const VptqLayerDesc* descs, int n, const void* const
 // ---- which instantiation a call would launch, as text (vptq_quant_gemv*_instance): the decisions above and the kernels' own
 // decide functions (gemv_k256.hip:k256_decide, gemv_k256m_decide, gemm_k256_decide, gemm_k256t_decide, gemv_k256c_mode), printed
 namespace {
-struct Text {
-  char* buf; size_t bytes, used; bool fits;
-  void add(const char* fmt, ...) {
-    if (!fits) return;
-    va_list ap;
-    va_start(ap, fmt);
-    const int w = vsnprintf(buf + used, bytes - used, fmt, ap);
-    va_end(ap);
-    if (w < 0 || (size_t)w >= bytes - used) { fits = false; return; }
-    used += (size_t)w;
-  }
-};
-int text_done(const Text& t) { return t.fits ? VPTQ_OK : fail(VPTQ_E_WORKSPACE, "instance: buffer of %zu bytes too small", t.bytes); }
-const char* dt_text(int dtype) { return dtype == VPTQ_DTYPE_F16 ? "f16" : "bf16"; }
+using vptq::Text;
+using vptq::dt_text;
+int instance_done(const Text& t) { return text_done(t) == 0 ? VPTQ_OK : fail(VPTQ_E_WORKSPACE, "instance: buffer of %zu bytes too small", t.bytes); }
 
 // launches of the canonical format's one-layer kernels for (descs, n, tokens): appended to t
 int add_k256(Text& t, const VptqLayerDesc* descs, int n, int tokens, int flags) {
@@ -376,10 +360,10 @@ int add_k256(Text& t, const VptqLayerDesc* descs, int n, int tokens, int flags) 
 void add_lds(Text& t, const vptq::LdsDecision& D) {
   if (!D.ok) { t.add("none"); return; }
   if (D.mfma)
-    t.add("gemv_lds_mfma dt=%s fmt=%s rw=%d stages=%d dma=%d perm=%d", D.f16 ? "f16" : "bf16", vptq::gemv_lds_fmt_text(D.fmt), D.rw, D.stages,
+    t.add("gemv_lds_mfma dt=%s fmt=%s rw=%d stages=%d dma=%d perm=%d", dt_text(D.f16), vptq::gemv_lds_fmt_text(D.fmt), D.rw, D.stages,
           (int)D.dma, (int)D.perm);
   else
-    t.add("gemv_lds dt=%s fmt=%s tok=%d rw=%d dma=%d perm=%d", D.f16 ? "f16" : "bf16", vptq::gemv_lds_fmt_text(D.fmt), D.tok, D.rw, (int)D.dma,
+    t.add("gemv_lds dt=%s fmt=%s tok=%d rw=%d dma=%d perm=%d", dt_text(D.f16), vptq::gemv_lds_fmt_text(D.fmt), D.tok, D.rw, (int)D.dma,
           (int)D.perm);
 }
 
@@ -388,16 +372,17 @@ int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
   const int kflags = drop_redundant_selective(flags);
   flags = selective_as_exact(flags);
   const Route r = route_gemv(d, tokens, flags, nullptr, true);
+  const char* const dt = dt_text(d.dtype == VPTQ_DTYPE_F16);
   switch (r) {
     case kRouteGemmK256T: {
       const vptq::GemmK256TDecision D = vptq::gemm_k256t_decide(d);
-      t.add("gemm_k256t dt=%s perm=%d tok=%d sweeps=%d rgs=%d", dt_text(d.dtype), (int)D.perm, tokens > 16 ? 16 : tokens, D.n_sweeps,
+      t.add("gemm_k256t dt=%s perm=%d tok=%d sweeps=%d rgs=%d", dt, (int)D.perm, tokens > 16 ? 16 : tokens, D.n_sweeps,
             D.groups_per_wg);
       return VPTQ_OK;
     }
     case kRouteGemmK256: {
       const vptq::GemmK256Decision D = vptq::gemm_k256_decide(d);
-      t.add("gemm_k256 dt=%s perm=%d tok=%d passes=", dt_text(d.dtype), (int)D.perm, tokens > 16 ? 16 : tokens);
+      t.add("gemm_k256 dt=%s perm=%d tok=%d passes=", dt, (int)D.perm, tokens > 16 ? 16 : tokens);
       bool first = true;
       for (int nrg = 4; nrg >= 1; nrg >>= 1)
         if (D.passes & nrg) { t.add("%s%d", first ? "" : "+", nrg); first = false; }
@@ -412,7 +397,7 @@ int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
     // the other families: the first launch of the call, as vptq_quant_gemv's own switch chunks it
     case kRouteGather: {
       const vptq::GatherDecision D = vptq::gemv_gather_decide(d, tokens > 8 ? 8 : tokens);
-      t.add("gemv_gather dt=%s t=%d rows=%d tok=%d perm=%d wide=%d", dt_text(d.dtype), D.T, D.rows, D.tok, (int)D.perm, (int)D.wide);
+      t.add("gemv_gather dt=%s t=%d rows=%d tok=%d perm=%d wide=%d", dt, D.T, D.rows, D.tok, (int)D.perm, (int)D.wide);
       return VPTQ_OK;
     }
     case kRouteLds: {
@@ -423,7 +408,7 @@ int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
     case kRouteGatherX: {
       const int step = vptq::gemv_gatherx_max_chunk(d);
       const vptq::GatherXDecision D = vptq::gemv_gatherx_decide(d, tokens > step ? step : tokens);
-      t.add("gemv_gatherx dt=%s v=%d tok=%d perm=%d reslds=%d outl=", dt_text(d.dtype), D.v, D.tok, (int)D.perm, (int)D.res_lds);
+      t.add("gemv_gatherx dt=%s v=%d tok=%d perm=%d reslds=%d outl=", dt, D.v, D.tok, (int)D.perm, (int)D.res_lds);
       if (D.ov == 0) t.add("0");
       else if (D.ov == D.v) t.add("same");
       else t.add("%d", D.ov);
@@ -432,7 +417,7 @@ int add_one(Text& t, const VptqLayerDesc& d, int tokens, int flags) {
     }
     case kRouteGeneric: {
       const vptq::GenericDecision D = vptq::gemv_generic_decide(d, tokens > 8 ? 8 : tokens);
-      t.add("gemv_generic dt=%s v=%d tok=%d", dt_text(d.dtype), D.v, D.tok);
+      t.add("gemv_generic dt=%s v=%d tok=%d", dt, D.v, D.tok);
       return VPTQ_OK;
     }
   }
@@ -448,7 +433,7 @@ int vptq_quant_gemv_instance(const VptqLayerDesc* d, int tokens, int flags, char
   if (tokens < 1 || tokens > VPTQ_GEMV_MAX_TOKENS) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, %d]", tokens, VPTQ_GEMV_MAX_TOKENS);
   Text t = {buf, bytes, 0, true};
   rc = add_one(t, *d, tokens, flags);
-  return rc ? rc : text_done(t);
+  return rc ? rc : instance_done(t);
 }
 
 int vptq_quant_gemv_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes) {
@@ -472,7 +457,7 @@ int vptq_quant_gemv_grouped_instance(const VptqLayerDesc* descs, int n, int toke
     const int rc = route == kGroupPerLayer ? add_one(t, descs[i0], tokens, flags) : add_k256(t, descs + i0, m, tokens, flags);
     if (rc) return rc;
   }
-  return text_done(t);
+  return instance_done(t);
 }
 
 // ---- chain: one persistent launch per <= 32 layers (gemv_k256c.hip), else layer by layer ----
@@ -680,7 +665,7 @@ int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens
     const int rc = vptq_quant_gemv_grouped_instance(descs, n, tokens, lflags & ~VPTQ_GEMV_FORCE_MFMA, one, sizeof(one));
     if (rc) return rc;
     t.add("grouped: %s", one);
-    return text_done(t);
+    return instance_done(t);
   }
   if (route == kChainPerLayer) {
     t.add("per-layer: ");
@@ -689,19 +674,19 @@ int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens
       const int rc = add_one(t, descs[i], tokens, lflags & ~VPTQ_GEMV_FORCE_MFMA);
       if (rc) return rc;
     }
-    return text_done(t);
+    return instance_done(t);
   }
   static const char* const mode_text[3] = {"folded", "exact", "selective"};
   for (int i0 = 0; i0 < n; i0 += 32) {   // one persistent launch per <= 32 layers
     const int m = n - i0 < 32 ? n - i0 : 32;
     const int mode = vptq::gemv_k256c_mode(lflags, dependent);
     if (mode < 0 || mode > 2) return fail(VPTQ_E_UNSUPPORTED, "instance: no gemv_k256c instantiation for flags 0x%x", flags);
-    t.add("%sgemv_k256c dt=%s dep=%d mode=%s layers=%d sweeps=", i0 ? " | " : "", dt_text(descs[0].dtype), (int)dependent, mode_text[mode], m);
+    t.add("%sgemv_k256c dt=%s dep=%d mode=%s layers=%d sweeps=", i0 ? " | " : "", dt_text(descs[0].dtype == VPTQ_DTYPE_F16), (int)dependent, mode_text[mode], m);
     for (int i = 0; i < m; ++i) t.add("%s%d", i ? "," : "", vptq::gemv_k256c_sweeps(run[i0 + i]));
     t.add(" perm=");
     for (int i = 0; i < m; ++i) t.add("%s%d", i ? "," : "", descs[i0 + i].perm ? 1 : 0);
   }
-  return text_done(t);
+  return instance_done(t);
 }
 
 int vptq_quant_gemv_chain(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
@@ -1128,7 +1113,7 @@ int vptq_quant_gemv_sliced_instance(const VptqLayerDesc* descs, const VptqSliced
   if (const int rc = vptq::gemv_sliced_instance(descs, layouts, n, 1, flags & ~VPTQ_GEMV_SELECTIVE, sel, one, sizeof(one)))
     return sliced_instance_rc(rc, bytes);
   t.add("%s", one);
-  return text_done(t);
+  return instance_done(t);
 }
 
 int vptq_quant_gemv_sliced_tokens_instance(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens, int flags,
@@ -1154,7 +1139,7 @@ int vptq_quant_gemv_sliced_tokens_instance(const VptqLayerDesc* descs, const Vpt
   if (const int rc = vptq::gemv_sliced_tok_instance(descs, layouts, n, tokens, flags, one, sizeof(one))) return sliced_instance_rc(rc, bytes);
   Text t = {buf, bytes, 0, true};
   t.add("%s", one);
-  return text_done(t);
+  return instance_done(t);
 }
 
 size_t vptq_quant_gemm_workspace_bytes(const VptqLayerDesc* d, int tokens) {
@@ -1193,11 +1178,11 @@ struct BatchedDecode {
 };
 static void print_gemm_gather(Text& t, const VptqLayerDesc& d, int tokens) {
   const vptq::GemmGatherDecision D = vptq::gemm_gather_decide(d, tokens);
-  t.add("gemm_gather dt=%s t=%d perm=%d tok=%d tiles=%d rgs=%d", D.f16 ? "f16" : "bf16", D.T, (int)D.perm, D.tok, D.tiles, D.rgs);
+  t.add("gemm_gather dt=%s t=%d perm=%d tok=%d tiles=%d rgs=%d", dt_text(D.f16), D.T, (int)D.perm, D.tok, D.tiles, D.rgs);
 }
 static void print_gemm_gatherx(Text& t, const VptqLayerDesc& d, int tokens) {
   const vptq::GemmGatherXDecision D = vptq::gemm_gatherx_decide(d, tokens);
-  t.add("gemm_gatherx dt=%s v=%d ib=%d rb=%d res=%s perm=%d tok=%d tiles=%d wgcu=%d rgs=%d", D.f16 ? "f16" : "bf16", D.v, D.ib, D.rb,
+  t.add("gemm_gatherx dt=%s v=%d ib=%d rb=%d res=%s perm=%d tok=%d tiles=%d wgcu=%d rgs=%d", dt_text(D.f16), D.v, D.ib, D.rb,
         D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", (int)D.perm, D.tok, D.tiles, D.wgcu, D.rgs);
 }
 static const BatchedDecode kGemmGather = {
@@ -1239,7 +1224,7 @@ static int batched_instance(const BatchedDecode& k, const VptqLayerDesc* d, int 
   Text t = {buf, bytes, 0, true};
   k.print(t, *d, tokens);
   if (!t.fits) buf[0] = 0;
-  return text_done(t);
+  return instance_done(t);
 }
 
 int vptq_quant_gemm_gather_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmGather, d, tokens); }
@@ -1351,9 +1336,9 @@ int vptq_quant_gemv_v2_instance(const VptqV2Desc* d, int tokens, int flags, char
     add_lds(t, vptq::gemv_lds_v2_decide(*d, tokens > step ? step : tokens, lds_launch_flags(tokens, flags)));
   } else {
     const vptq::V2Decision D = vptq::gemv_v2_decide(*d, tokens > 8 ? 8 : tokens);
-    t.add("gemv_v2 dt=%s v=%d tok=%d", D.f16 ? "f16" : "bf16", D.v, D.tok);
+    t.add("gemv_v2 dt=%s v=%d tok=%d", dt_text(D.f16), D.v, D.tok);
   }
-  return text_done(t);
+  return instance_done(t);
 }
 
 }  // extern "C"

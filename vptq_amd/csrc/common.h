@@ -3,6 +3,7 @@
 #include <stdlib.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/vptq_hip.h"
 #include "tune_env.h"
@@ -21,6 +22,13 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
 typedef short s4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
+typedef __bf16 b8_t __attribute__((ext_vector_type(8)));
+// loads the compiler may assume 4-byte alignment for only (index words at any word offset of a row)
+typedef uint32_t u32_a4 __attribute__((aligned(4)));
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr int kWave = 64;
 
@@ -280,6 +288,11 @@ static __device__ __forceinline__ T* as_global(T* p) {
   typedef T __attribute__((address_space(1))) global_t;
   return (T*)(global_t*)(uintptr_t)p;
 }
+// 16 bytes at base + byte_off: a 32-bit zero-extended offset against a wave-uniform base selects the scalar-base addressing
+// form (no 64-bit vector add per load)
+static __device__ __forceinline__ u32x4 ld16(const void* base, uint32_t byte_off) {
+  return *(const u32x4*)as_global((const char*)base + byte_off);
+}
 // broadcast one 16-bit element into both halves of a register
 static __device__ __forceinline__ uint32_t splat16(uint16_t v) {
   return (uint32_t)v * 0x00010001u;
@@ -294,6 +307,34 @@ static __device__ __forceinline__ u32x4 lds_load16(uint32_t byte_addr) {
 static __device__ __forceinline__ void lds_store16(uint32_t byte_addr, u32x4 v) {
   *(lds_u32x4_t*)(uintptr_t)byte_addr = v;  // ds_write_b128
 }
+
+// ds_read_b64_tr_b16: the transposing LDS load that feeds the 16x16x32 MFMA's operands
+static __device__ __forceinline__ u32x2 lds_tr8(uint32_t byte_addr) {
+  typedef __attribute__((address_space(3))) s4_t lds_s4_t;
+  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(uintptr_t)byte_addr));
+}
+
+// D = A B + C, 16x16x32, fp32 accumulate, 8 packed 16-bit elements per operand and lane: v_mfma_f32_16x16x32_f16 / _bf16
+template <typename DT>
+static __device__ __forceinline__ f32x4 mfma16x16x32(u32x4 a, u32x4 b, f32x4 c) {
+  if constexpr (std::is_same<DT, F16>::value)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_t, a), __builtin_bit_cast(h8_t, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8_t, a), __builtin_bit_cast(b8_t, b), c, 0, 0, 0);
+}
+
+// f(I0), ... f(I1 - 1) / f(0), ... f(N - 1) with the argument as a compile-time constant (std::integral_constant): the slots of
+// a load queue held in registers
+template <int I0, int I1, typename F>
+static __device__ __forceinline__ void for_range(F&& f) {
+  if constexpr (I1 - I0 == 1) f(std::integral_constant<int, I0>{});
+  else {
+    for_range<I0, (I0 + I1) / 2>(f);
+    for_range<(I0 + I1) / 2, I1>(f);
+  }
+}
+template <int N, typename F>
+static __device__ __forceinline__ void for_slots(F&& f) { for_range<0, N>(f); }
 
 // ---- wave64 reductions -------------------------------------------------------
 
@@ -389,6 +430,20 @@ struct WaveReduce {
 // Reads word wi and, only when the element straddles, word wi+1 (which then
 // exists inside the row): never touches memory past the row, unlike the
 // reference's iterator (csrc/util/cuda_utils.cuh:131).
+// element e of a lane's word group w: elements of T = 16 / 24 / 32 bits, packed (24 bits: 4 elements in 3 words)
+template <int T, int NW>
+static __device__ __forceinline__ uint32_t packed_elem(const uint32_t (&w)[NW], int e) {
+  if (T == 16) return (e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu);
+  if (T == 32) return w[e];
+  const int b = (e >> 2) * 3;
+  switch (e & 3) {
+    case 0: return w[b] & 0xffffffu;
+    case 1: return __builtin_amdgcn_alignbit(w[b + 1], w[b], 24) & 0xffffffu;
+    case 2: return __builtin_amdgcn_alignbit(w[b + 2], w[b + 1], 16) & 0xffffffu;
+    default: return w[b + 2] >> 8;
+  }
+}
+
 static __device__ __forceinline__ uint32_t unpack_elem(const uint32_t* __restrict__ row, int g,
                                                        int T) {
   const uint32_t bit = (uint32_t)g * (uint32_t)T;

@@ -32,9 +32,6 @@ namespace vptq {
 // The launch decision (TAB, grid) and the path predicates (full, vec_norm, vec_idx, win_idx, need5): dequant_paths.h, shared with
 // dequant_instance below.
 
-typedef uint32_t dq_u32_a4 __attribute__((aligned(4)));
-typedef uint32_t dq_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
 template <typename DT, int V, int TAB>
 __global__ __launch_bounds__(256) void dequant_kernel(const VptqLayerDesc d,
                                                       uint16_t* __restrict__ W, const int col_blocks) {
@@ -91,8 +88,8 @@ __global__ __launch_bounds__(256) void dequant_kernel(const VptqLayerDesc d,
       for (int k = 0; k < 2; ++k) {
         const uint32_t bit = (uint32_t)(g + 4 * k) * (uint32_t)T;
         const uint32_t w0 = bit >> 5, off = bit & 31u;
-        const dq_u32x4_a4 a = *(const dq_u32x4_a4*)(row + w0);
-        const uint32_t w4 = need5 ? *(const dq_u32_a4*)(row + w0 + 4) : 0u;
+        const u32x4_a4 a = *(const u32x4_a4*)(row + w0);
+        const uint32_t w4 = need5 ? *(const u32_a4*)(row + w0 + 4) : 0u;
         nwin[k][0] = __builtin_amdgcn_alignbit(a[1], a[0], off);
         nwin[k][1] = __builtin_amdgcn_alignbit(a[2], a[1], off);
         nwin[k][2] = __builtin_amdgcn_alignbit(a[3], a[2], off);
@@ -253,16 +250,17 @@ int dequant_instance(const VptqLayerDesc& d, const void* W, char* buf, size_t by
     ++n_idx[cls];
   }
   static const char* const kIdx[4] = {"vec", "win", "win5", "elem"};
-  char idx[96];
-  size_t used = 0;
+  char idx_buf[96] = "";
+  Text idx = {idx_buf, sizeof(idx_buf), 0, true};
   for (int c = 0; c < 4; ++c)
-    if (n_idx[c]) used += (size_t)snprintf(idx + used, sizeof(idx) - used, "%s%s:%lld", used ? "," : "", kIdx[c], n_idx[c]);
+    if (n_idx[c]) idx.add("%s%s:%lld", idx.used ? "," : "", kIdx[c], n_idx[c]);
   const char* norm = !d.weight_scale ? "none" : n_norm == chunks ? "vec" : n_norm == 0 ? "scalar" : "mixed";
   const char* store = n_store == chunks ? "vec" : n_store == 0 ? "scalar" : "mixed";
-  const int w = snprintf(buf, bytes, "dequant dt=%s v=%d tab=%d lds=%d colblocks=%d t=%d norm=%s store=%s idx=%s perm=%d outl=%d groups=%d ragged=%d",
-                         D.f16 ? "f16" : "bf16", D.v, D.tab, D.lds, D.col_blocks, T, norm, store, idx, (int)(d.inv_perm != nullptr),
-                         d.outlier_size > 0 ? d.outlier_vector_len : 0, d.num_codebooks, (int)((I & 7) != 0));
-  return w < 0 || (size_t)w >= bytes ? -2 : 0;
+  Text t = {buf, bytes, 0, true};
+  t.add("dequant dt=%s v=%d tab=%d lds=%d colblocks=%d t=%d norm=%s store=%s idx=%s perm=%d outl=%d groups=%d ragged=%d", dt_text(D.f16),
+        D.v, D.tab, D.lds, D.col_blocks, T, norm, store, idx_buf, (int)(d.inv_perm != nullptr),
+        d.outlier_size > 0 ? d.outlier_vector_len : 0, d.num_codebooks, (int)((I & 7) != 0));
+  return text_done(t);
 }
 
 }  // namespace vptq

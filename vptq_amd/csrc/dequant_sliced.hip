@@ -207,8 +207,7 @@ __global__ __launch_bounds__(kDSThreads) void dequant_sliced_kernel(const DSArgs
 
 // largest tile in columns for vector length v: the image of 2 v bytes per column within kDSImageMax
 int ds_max_tile(int v) {
-  static std::atomic<int> knob{-1};   // VPTQ_DQS_TILE: columns of the largest v = 8 tile (v = 16: half), A/B
-  if (knob < 0) { const char* e = vptq::tune_env("VPTQ_DQS_TILE"); knob = e ? atoi(e) : 0; }
+  static const int knob = tune_int("VPTQ_DQS_TILE", 0);   // columns of the largest v = 8 tile (v = 16: half), A/B
   int t = kDSImageMax / (2 * v);
   if (knob >= 128) t = min(t, knob * 8 / v);
   return max(t / 128 * 128, 128);
@@ -216,12 +215,7 @@ int ds_max_tile(int v) {
 
 template <typename DT, int V, int SIDE, bool RLDS>
 hipError_t ds_launch(const DSArgs& a, size_t lds, hipStream_t st) {
-  static std::atomic<int> attr{0};
-  if (!attr.load()) {
-    const hipError_t e = hipFuncSetAttribute((const void*)dequant_sliced_kernel<DT, V, SIDE, RLDS>, hipFuncAttributeMaxDynamicSharedMemorySize, kDSMaxLds);
-    if (e != hipSuccess) return e;
-    attr = 1;
-  }
+  if (const hipError_t e = allow_dynamic_lds<dequant_sliced_kernel<DT, V, SIDE, RLDS>>(kDSMaxLds); e != hipSuccess) return e;
   hipLaunchKernelGGL((dequant_sliced_kernel<DT, V, SIDE, RLDS>), dim3((unsigned)(a.N * a.tiles)), dim3(kDSThreads), lds, st, a);
   return hipGetLastError();
 }

@@ -406,26 +406,13 @@ hipError_t launch_gemm_fused(const VptqLayerDesc& d, const void* x, void* y, int
                        (float*)workspace, xs, tokens, d.group_size);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   }
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  static std::atomic<int> cus[64];
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  static std::atomic<bool> attr_set[64];
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_fused_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, kFLds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)gemm_fused_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, kFLds);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  if (const hipError_t e = f16 ? allow_dynamic_lds<gemm_fused_kernel<F16>>(kFLds) : allow_dynamic_lds<gemm_fused_kernel<BF16>>(kFLds); e != hipSuccess)
+    return e;
   const int n_tiles = P.tiles_m * P.tiles_n;
   // one workgroup per CU; kept a multiple of 8 (the XCD count) for the tile walk
-  const int ncu = cus[dev].load();
+  const int ncu = device_cus();
   int grid = n_tiles < ncu ? (n_tiles + 7) / 8 * 8 : ncu;
-  if (grid > cus[dev]) grid = cus[dev];
+  if (grid > ncu) grid = ncu;
   if (f16) hipLaunchKernelGGL((gemm_fused_kernel<F16>), dim3(grid), dim3(kFThreads), kFLds, st, P);
   else hipLaunchKernelGGL((gemm_fused_kernel<BF16>), dim3(grid), dim3(kFThreads), kFLds, st, P);
   return hipGetLastError();

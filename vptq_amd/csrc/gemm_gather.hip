@@ -20,20 +20,6 @@ namespace vptq {
 constexpr int kMRows = 2;                         // vector-rows per row group (16 outputs)
 constexpr int kMWgPerCu = 4;
 
-// element e of 8 elements of T bits in T / 4 words (gemv_gather.hip: elem)
-template <int T>
-static __device__ __forceinline__ uint32_t mg_elem(const uint32_t (&w)[T / 4], int e) {
-  if (T == 16) return (e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu);
-  if (T == 32) return w[e];
-  const int b = (e >> 2) * 3;
-  switch (e & 3) {
-    case 0: return w[b] & 0xffffffu;
-    case 1: return __builtin_amdgcn_alignbit(w[b + 1], w[b], 24) & 0xffffffu;
-    case 2: return __builtin_amdgcn_alignbit(w[b + 2], w[b + 1], 16) & 0xffffffu;
-    default: return w[b + 2] >> 8;
-  }
-}
-
 template <typename DT, int T, bool PERM>
 __global__ __launch_bounds__(kGTThreads) void gemm_gather_kernel(const GemmGatherParams P) {
   constexpr int NW = T / 4;   // index words of 8 elements
@@ -78,7 +64,7 @@ __global__ __launch_bounds__(kGTThreads) void gemm_gather_kernel(const GemmGathe
     auto gather = [&](const uint32_t (&w)[NW]) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const uint32_t v = mg_elem<T>(w, e);
+        const uint32_t v = packed_elem<T>(w, e);
         cv[e] = *(const u32x4*)(P.cent + (size_t)(v & 0xffffu) * 16);
         if constexpr (T == 24) rv[e] = rtab[(v >> 16) & 0xffu];
         if constexpr (T == 32) rv[e] = *(const u32x4*)(P.rcent + (size_t)(v >> 16) * 16);
@@ -113,7 +99,7 @@ __global__ __launch_bounds__(kGTThreads) void gemm_gather_kernel(const GemmGathe
         const bool live = mj < tokens && t * kGTTile + (mch0 + i) * 8 < G;
         const u32x4 a = {live ? xa[i][0] : 0u, live ? xa[i][1] : 0u, live ? xa[i][2] : 0u, live ? xa[i][3] : 0u};
         const u32x4 b = tile[(mch0 + i) * 16 + (mj ^ i)];   // ((mch0 + i) & 7 == i)
-        acc = gt_mfma<DT>(a, b, acc);
+        acc = mfma16x16x32<DT>(a, b, acc);
       }
     }
     gt_epilogue<DT>(P, tid, lane, wave, (float*)tile, rg, acc);

@@ -14,7 +14,7 @@
 //    one lane of the 16x16x32 MFMA supplies as B operand: 8 ds_write_b128 into the tile [column chunk][output][16 bytes], the
 //    output slot XOR-ed with the chunk's low bits so that the 8 lanes of a write group cover all 32 banks; the B reads
 //    (ds_read_b128, 16 outputs of a chunk contiguous) are conflict free: gt_write_tile.
-//  * MFMA phase (gt_load_a, then the kernel's own loop over gt_mfma): the tile's 32 K-steps are dealt to the 4 waves; lane (token, k group kg) of wave w takes
+//  * MFMA phase (gt_load_a, then the kernel's own loop over mfma16x16x32): the tile's 32 K-steps are dealt to the 4 waves; lane (token, k group kg) of wave w takes
 //    chunk 32 w + 8 kg + i in step i, so that its 8 A operands (raw x, loaded from L2) are 64 CONSECUTIVE columns - one 128-byte line
 //    per token (gemm_k256.hip: K-steps of adjacent columns cost 4x the L2 traffic).  Token rows past `tokens` are zero.
 //  * the gathers of tile t + 1 are issued before the MFMA phase of tile t, its index words and scale / bias one tile earlier; two
@@ -35,16 +35,6 @@ constexpr int kGTThreads = 256;
 constexpr int kGTTile = 1024;                      // columns per tile: kGTThreads / 2 chunks of 8
 constexpr int kGTChunks = kGTTile / 8;
 constexpr int kGTTileBytes = kGTChunks * 16 * 16;  // [chunk][16 outputs][16 bytes]: 32 KiB
-
-typedef _Float16 gt_h8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 gt_b8_t __attribute__((ext_vector_type(8)));
-template <typename DT>
-static __device__ __forceinline__ f32x4 gt_mfma(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<DT, F16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gt_h8_t, a), __builtin_bit_cast(gt_h8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(gt_b8_t, a), __builtin_bit_cast(gt_b8_t, b), c, 0, 0, 0);
-}
 
 // first column of chunk dch of tile t (tiles past the end clamp to the last chunk of the row)
 static __device__ __forceinline__ int gt_dcol(int t, int dch, int G) { const int c = t * kGTTile + dch * 8; return c < G ? c : G - 8; }

@@ -26,9 +26,6 @@ constexpr int kGXResLdsMax = 32768;                // (gemv_gatherx.hip: kXResLd
 constexpr int kGXLdsPerCu = 160 * 1024;
 constexpr int kGXMaxWgPerCu = 4;                   // 16 waves per CU: 128 VGPRs per lane
 
-typedef uint32_t gx_u32_a4 __attribute__((aligned(4)));
-typedef uint32_t gx_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
 // element E (compile time) of T bits (wave uniform) out of the normalised window n[0..7]: it sits at bit E * T, word (E * T) >> 5 <= E
 template <int E>
 static __device__ __forceinline__ uint32_t gx_elem(const uint32_t (&n)[8], int T, uint32_t mask) {
@@ -86,14 +83,14 @@ __global__ __launch_bounds__(kGTThreads) void gemm_gatherx_kernel(const GemmGath
       const uint32_t off = (cb & 3u) * 8u;
       uint32_t w[9];
       if (w0 + 8 <= last) {
-        const gx_u32x4_a4 a = *(const gx_u32x4_a4*)(irow + w0);
-        const gx_u32x4_a4 b = *(const gx_u32x4_a4*)(irow + w0 + 4);
+        const u32x4_a4 a = *(const u32x4_a4*)(irow + w0);
+        const u32x4_a4 b = *(const u32x4_a4*)(irow + w0 + 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) { w[j] = a[j]; w[4 + j] = b[j]; }
-        w[8] = need9 ? *(const gx_u32_a4*)(irow + w0 + 8) : 0u;
+        w[8] = need9 ? *(const u32_a4*)(irow + w0 + 8) : 0u;
       } else {
 #pragma unroll
-        for (int j = 0; j < 9; ++j) w[j] = *(const gx_u32_a4*)(irow + (w0 + j < last ? w0 + j : last));
+        for (int j = 0; j < 9; ++j) w[j] = *(const u32_a4*)(irow + (w0 + j < last ? w0 + j : last));
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) n[j] = __builtin_amdgcn_alignbit(w[j + 1], w[j], off);
@@ -139,7 +136,7 @@ __global__ __launch_bounds__(kGTThreads) void gemm_gatherx_kernel(const GemmGath
         const bool live = mj < tokens && t * kGTTile + (mch0 + i) * 8 < G;
         const u32x4 a = {live ? xa[i][0] : 0u, live ? xa[i][1] : 0u, live ? xa[i][2] : 0u, live ? xa[i][3] : 0u};
         const u32x4 b = tile[(mch0 + i) * 16 + (mj ^ i)];   // ((mch0 + i) & 7 == i)
-        acc = gt_mfma<DT>(a, b, acc);
+        acc = mfma16x16x32<DT>(a, b, acc);
       }
     }
     gt_epilogue<DT>(P, tid, lane, wave, (float*)gx_smem, rg, acc);

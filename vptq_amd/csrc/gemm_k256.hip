@@ -311,6 +311,13 @@ GemmK256Decision gemm_k256_decide(const VptqLayerDesc& d) {
   return D;
 }
 
+template <typename DT, bool PERM>
+static hipError_t launch_g(const GemmK256Params& P, int grid, hipStream_t st) {
+  if (const hipError_t e = allow_dynamic_lds<gemm_k256_kernel<DT, PERM>>(kGLds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((gemm_k256_kernel<DT, PERM>), dim3(grid), dim3(kGThreads), kGLds, st, P);
+  return hipGetLastError();
+}
+
 hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
                             hipStream_t st) {
   const GemmK256Decision D = gemm_k256_decide(d);
@@ -328,21 +335,8 @@ hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int 
   P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
   P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
   P.n_groups = D.n_groups;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  const int grid = D.grid;
-  auto go = [&](auto kern, std::atomic<bool>& done) -> hipError_t {
-    if (!done) {
-      if (hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kGLds); e != hipSuccess) return e;
-      done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kGThreads), kGLds, st, P);
-    return hipGetLastError();
-  };
-  static std::atomic<bool> attr_set[4][64];
-  if (D.f16)
-    return D.perm ? go(gemm_k256_kernel<F16, true>, attr_set[0][dev]) : go(gemm_k256_kernel<F16, false>, attr_set[1][dev]);
-  return D.perm ? go(gemm_k256_kernel<BF16, true>, attr_set[2][dev]) : go(gemm_k256_kernel<BF16, false>, attr_set[3][dev]);
+  if (D.f16) return D.perm ? launch_g<F16, true>(P, D.grid, st) : launch_g<F16, false>(P, D.grid, st);
+  return D.perm ? launch_g<BF16, true>(P, D.grid, st) : launch_g<BF16, false>(P, D.grid, st);
 }
 
 }  // namespace vptq

@@ -78,20 +78,6 @@ struct GemmK256TParams {
   int n_sweeps;            // sweeps per row group
 };
 
-typedef _Float16 bt_h8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bt_b8_t __attribute__((ext_vector_type(8)));
-template <typename DT>
-static __device__ __forceinline__ f32x4 bt_mfma(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<DT, F16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(bt_h8_t, a), __builtin_bit_cast(bt_h8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bt_b8_t, a), __builtin_bit_cast(bt_b8_t, b), c, 0, 0, 0);
-}
-static __device__ __forceinline__ u32x2 bt_lds_tr8(uint32_t byte_addr) {
-  typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(uintptr_t)byte_addr));
-}
-
 // Operand-ordered activations in the workspace: per 128-column block 4 KiB = [K-step p][lane group kg][token
 // slot m (16)][t][e] halves, column = 8 (4 kg + e) + 2 p + t of the block: lane group kg of the MFMA covers the
 // 8-column chunks 4 kg + e (e = 0..3 = the gather source lanes), K-step p takes columns 2p, 2p + 1 (= t) of every
@@ -156,15 +142,6 @@ __global__ __launch_bounds__(kBTPrepThreads) void gemm_k256t_prep(const uint16_t
     *(u32x4*)(xp + ((size_t)(sw * 16 + blk) * 4096 + (size_t)p * 1024 + (size_t)kg * 256 + (size_t)m * 16) / 4) = o;
   }
   if (tid == 0) bdot[m * n_sweeps + sw] = (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// f(slot 0), ... f(slot kBTDepth - 1) with the slot as a compile-time constant
-template <typename F>
-static __device__ __forceinline__ void bt_for_slots(F&& f) {
-  f(std::integral_constant<int, 0>{});
-  f(std::integral_constant<int, 1>{});
-  if constexpr (kBTDepth > 2) f(std::integral_constant<int, (kBTDepth > 2 ? 2 : 0)>{});
-  if constexpr (kBTDepth > 3) f(std::integral_constant<int, (kBTDepth > 3 ? 3 : 0)>{});
 }
 
 template <typename DT>
@@ -294,10 +271,10 @@ __global__ __launch_bounds__(kBTThreads) void gemm_k256t_kernel(const GemmK256TP
           g[p & 1][t][0][0] = u32x2{w, aX}; g[p & 1][t][0][1] = u32x2{aX, w};
           g[p & 1][t][1][0] = u32x2{w, aY}; g[p & 1][t][1][1] = u32x2{aY, w};
         } else {
-          g[p & 1][t][0][0] = bt_lds_tr8(aX);
-          g[p & 1][t][0][1] = bt_lds_tr8(aX ^ 8u);
-          g[p & 1][t][1][0] = bt_lds_tr8(aY);
-          g[p & 1][t][1][1] = bt_lds_tr8(aY ^ 8u);
+          g[p & 1][t][0][0] = lds_tr8(aX);
+          g[p & 1][t][0][1] = lds_tr8(aX ^ 8u);
+          g[p & 1][t][1][0] = lds_tr8(aY);
+          g[p & 1][t][1][1] = lds_tr8(aY ^ 8u);
         }
       }
     };
@@ -316,7 +293,7 @@ __global__ __launch_bounds__(kBTThreads) void gemm_k256t_kernel(const GemmK256TP
           const u32x2 t0 = g[p & 1][0][r][h], t1 = g[p & 1][1][r][h];
           const u32x4 b = u32x4{t0[0], t0[1], t1[0], t1[1]};
           if constexpr ((VPTQ_K256BT_ABLATE & 1) != 0) asm volatile("" :: "v"(a), "v"(b));
-          else acc[h] = bt_mfma<DT>(a, b, acc[h]);
+          else acc[h] = mfma16x16x32<DT>(a, b, acc[h]);
         }
       }
     }
@@ -376,7 +353,7 @@ __global__ __launch_bounds__(kBTThreads) void gemm_k256t_kernel(const GemmK256TP
   };
 
   // ---- prologue: first D sweeps requested, then the image has landed (older than those loads)
-  bt_for_slots([&](auto slot_c) {
+  for_slots<kBTDepth>([&](auto slot_c) {
     issue(slot_c);
     __builtin_amdgcn_sched_barrier(0);   // (the slots in issue order: the counted waits of the loop rely on it)
   });
@@ -392,7 +369,7 @@ __global__ __launch_bounds__(kBTThreads) void gemm_k256t_kernel(const GemmK256TP
     if (--c_left == 0) row_group_done();
   };
   do {
-    bt_for_slots(step);
+    for_slots<kBTDepth>(step);
   } while (!done);
 }
 
@@ -417,15 +394,8 @@ size_t gemm_k256t_workspace_bytes(const VptqLayerDesc& d) {
 template <typename DT>
 static hipError_t launch_bt(const VptqLayerDesc& d, const GemmK256TParams& P, const void* x, void* ws, int grid,
                             hipStream_t st) {
-  auto kern = gemm_k256t_kernel<DT>;
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBTLds);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = gemm_k256t_kernel<DT>;
+  if (const hipError_t e = allow_dynamic_lds<kern>((int)kBTLds); e != hipSuccess) return e;
   hipLaunchKernelGGL(gemm_k256t_prep<DT>, dim3(P.tokens, P.n_sweeps), dim3(kBTPrepThreads), 0, st, (const uint16_t*)x,
                      (const uint16_t*)d.weight_scale, (const uint16_t*)d.weight_bias, (const uint16_t*)d.perm,
                      (uint32_t*)ws, (float*)P.bdot, d.in_features, d.group_size, P.n_sweeps);

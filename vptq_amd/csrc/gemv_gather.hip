@@ -45,20 +45,6 @@ template <bool W> struct Fmt<16, W> { static constexpr int NW = 4, E = 8; };
 template <bool W> struct Fmt<24, W> { static constexpr int E = W ? 8 : 4, NW = E * 3 / 4; };
 template <bool W> struct Fmt<32, W> { static constexpr int NW = 4, E = 4; };
 
-template <int T, int NW>
-static __device__ __forceinline__ uint32_t elem(const uint32_t (&w)[NW], int e) {
-  if (T == 16) return (e & 1) ? (w[e >> 1] >> 16) : (w[e >> 1] & 0xffffu);
-  if (T == 32) return w[e];
-  // T == 24: 4 elements in 3 words
-  const int b = (e >> 2) * 3;
-  switch (e & 3) {
-    case 0: return w[b] & 0xffffffu;
-    case 1: return __builtin_amdgcn_alignbit(w[b + 1], w[b], 24) & 0xffffffu;
-    case 2: return __builtin_amdgcn_alignbit(w[b + 2], w[b + 1], 16) & 0xffffffu;
-    default: return w[b + 2] >> 8;
-  }
-}
-
 // A/B knob (tools/gpu_r2_gather.sh): 1 = centroid gathers bypass the vector L1 (nt), 2 = the index
 // words too.  Measured: 79 / 63 us per 8192^2 layer against 39.6 us with plain loads - the 9.5 % of
 // gathers that hit in L1 and the L1's request merging matter; off.
@@ -141,7 +127,7 @@ __global__ __launch_bounds__(kGThreads) void gemv_gather_kernel(const GatherPara
       u32x4 cv[E], rv[E];
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        const uint32_t v = elem<T, NW>(w[r], e);
+        const uint32_t v = packed_elem<T>(w[r], e);
         if (VPTQ_GATHER_NT) cv[e] = __builtin_nontemporal_load((const u32x4*)(P.cent + (size_t)(v & 0xffffu) * 16));
         else cv[e] = *(const u32x4*)(P.cent + (size_t)(v & 0xffffu) * 16);
         if constexpr (kResLds) rv[e] = rtab[(v >> 16) & 0xffu];

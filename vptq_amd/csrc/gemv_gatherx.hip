@@ -53,17 +53,12 @@ struct GatherXParams {
 
 constexpr int kXResLdsMax = 32768;
 
-typedef uint32_t u32_a4 __attribute__((aligned(4)));
-typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
 // one codebook entry (V halves = V / 2 words): 16-byte loads; the 24-byte entries of vector
 // length 12 are only 8-byte aligned: one 16-byte load at that alignment + one 8-byte load (three
 // 8-byte loads were slower than the generic kernel: the gathers are bound by lane addresses per
 // clock, not by bytes)
 typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
 typedef uint32_t u32x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
 template <int V>
 static __device__ __forceinline__ void load_entry(uint32_t (&w)[V / 2], const char* p) {
   if constexpr (V == 12) {

@@ -12,7 +12,6 @@
 //     hold what they touch - and stores sum w x per output (float32, zeros without a hot block) as `corr`, which the folded launch
 //     adds before its one rounding (SlicedParams::corr).
 // Replaces, for those columns, the reference's global gathers of both entries (csrc/kernels/quant_gemv.cuh:114-125).
-#include <cstdio>
 #include <type_traits>
 
 #include "common.h"
@@ -237,11 +236,6 @@ bool gemv_hot_eligible(const VptqLayerDesc& d) {
 size_t gemv_hot_bytes(const VptqLayerDesc& d) {
   return 256 + ((size_t)d.in_features * 2 + 255) / 256 * 256 + ((size_t)d.num_indices * d.vector_len * 4 + 255) / 256 * 256;
 }
-static float gh_kappa() {
-  static std::atomic<int> milli{-1};
-  if (milli < 0) { const char* e = tune_env("VPTQ_SELECTIVE_KAPPA"); const double v = e ? atof(e) : 0.0; milli = v > 0.0 ? (int)(v * 1000.0) : 6000; }
-  return (float)milli.load() * 1e-3f;
-}
 // decide, then launch: which instantiation serves the layer (gemv_hot_instance prints it)
 HotDecision gemv_hot_decide(const VptqLayerDesc& d) {
   return HotDecision{gemv_hot_eligible(d), d.dtype == VPTQ_DTYPE_F16, d.vector_len};
@@ -249,8 +243,9 @@ HotDecision gemv_hot_decide(const VptqLayerDesc& d) {
 int gemv_hot_instance(const VptqLayerDesc& d, char* buf, size_t bytes) {
   const HotDecision D = gemv_hot_decide(d);
   if (!D.ok) return -1;
-  const int w = snprintf(buf, bytes, "gemv_hot dt=%s v=%d", D.f16 ? "f16" : "bf16", D.v);
-  return w < 0 || (size_t)w >= bytes ? -2 : 0;
+  Text t = {buf, bytes, 0, true};
+  t.add("gemv_hot dt=%s v=%d", dt_text(D.f16), D.v);
+  return text_done(t);
 }
 template <typename DT, int V>
 static hipError_t launch_hot(const HotDecision& D, const HotParams& P, int grid, hipStream_t st) {
@@ -275,7 +270,7 @@ hipError_t launch_gemv_hot(const VptqLayerDesc& d, const void* x, void* extra, c
   P.corr = (float*)((char*)extra + 256 + ((size_t)d.in_features * 2 + 255) / 256 * 256);
   P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
   P.T = d.index_bits + d.res_bits;
-  P.kappa = gh_kappa();
+  P.kappa = selective_kappa();
   if ((((uintptr_t)P.cent | (uintptr_t)P.rcent) & 15) != 0) return hipErrorInvalidValue;
   const int grid = (d.num_indices + kGHRows - 1) / kGHRows;
   *x_masked = P.xm;

@@ -36,7 +36,6 @@
 //  * two entry points share the body: gemv_k256_kernel (layer = blockIdx.y, grouped
 //    launches, 2-4 tokens) and gemv_k256_kernel_1 (one layer, one token: the arguments the
 //    first loads need are preloaded into SGPRs at wave launch).
-#include <cstdio>
 
 #include "common.h"
 #include "kernels.h"
@@ -64,12 +63,6 @@ static __device__ __forceinline__ void gather(uint32_t w, int h, uint32_t baseC,
 
 // 16-byte load of 8 consecutive 16-bit values, or (PERM) a gather of 8 values through
 // the permutation: column c of the quantised matrix multiplies input feature perm[c].
-// 16 bytes at base + byte_off: 32-bit zero-extended offset against a wave-uniform base
-// selects the scalar-base addressing form (no 64-bit vector add per load).
-static __device__ __forceinline__ u32x4 ld16(const void* base, uint32_t byte_off) {
-  return *(const u32x4*)as_global((const char*)base + byte_off);
-}
-
 template <bool PERM>
 static __device__ __forceinline__ u32x4 load8(const uint16_t* __restrict__ p, int col0,
                                               const u32x4& pv) {
@@ -373,8 +366,7 @@ bool gemv_k256_eligible(const VptqLayerDesc& d, int tokens) {
 // ROWS per workgroup: 2 when that still leaves >= 512 workgroups (two per CU) and
 // the instantiation stays spill-free under the 128-VGPR budget (f16, one token).
 static int pick_rows(int n_rows_total, int tok, bool f16) {
-  static std::atomic<int> forced{-1};  // VPTQ_K256_ROWS=1|2: tuning override
-  if (forced < 0) { const char* e = vptq::tune_env("VPTQ_K256_ROWS"); forced = e ? atoi(e) : 0; }
+  static const int forced = tune_int("VPTQ_K256_ROWS", 0);  // 1|2: tuning override
   if (forced == 2 && f16 && tok == 1) return 2;
   if (forced == 1) return 1;
   return (f16 && tok == 1 && (n_rows_total + 1) / 2 >= 512) ? 2 : 1;
@@ -383,21 +375,11 @@ static int pick_rows(int n_rows_total, int tok, bool f16) {
 template <typename DT, int ROWS, int TOK, int SW, bool PERM, bool FAST>
 static hipError_t launch_inst(const K256Params& P, int grid, int entry, hipStream_t st) {
   constexpr int lds = kScratchOff + kWaves * (TOK * ROWS * 8 + TOK) * 4;
-  // > 64 KiB of dynamic LDS must be enabled once per device (benign race: idempotent)
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  auto allow_lds = [&](const void* kern, std::atomic<bool>& done) {
-    if (done) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    done = e == hipSuccess;
-    return e;
-  };
   if constexpr (TOK == 1) {
     if (entry == 1) {  // the preloaded-argument entry point
       if (P.n_layers != 1) return hipErrorInvalidValue;
-      auto kern = gemv_k256_kernel_1<DT, ROWS, SW, PERM, FAST>;
-      static std::atomic<bool> attr_set[64];
-      if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
+      constexpr auto kern = gemv_k256_kernel_1<DT, ROWS, SW, PERM, FAST>;
+      if (const hipError_t e = allow_dynamic_lds<kern>(lds); e != hipSuccess) return e;
       const K256Layer& L0 = P.layer[0];
       hipLaunchKernelGGL(kern, dim3(grid, 1), dim3(kThreads), lds, st, L0.cent, L0.rcent, L0.idx, L0.x,
                          L0.scale, L0.wbias, L0.N, L0.G, P);
@@ -405,9 +387,8 @@ static hipError_t launch_inst(const K256Params& P, int grid, int entry, hipStrea
     }
   }
   if (entry != 0) return hipErrorInvalidValue;
-  auto kern = gemv_k256_kernel<DT, ROWS, TOK, SW, PERM, FAST>;
-  static std::atomic<bool> attr_set[64];
-  if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
+  constexpr auto kern = gemv_k256_kernel<DT, ROWS, TOK, SW, PERM, FAST>;
+  if (const hipError_t e = allow_dynamic_lds<kern>(lds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid, P.n_layers), dim3(kThreads), lds, st, P);
   return hipGetLastError();
 }
@@ -458,11 +439,7 @@ struct K256Choice {
 };
 
 static K256Choice choose_kernel(const VptqLayerDesc* descs, int n, int tokens, int flags) {
-  static std::atomic<int> forced{-1};
-  if (forced < 0) {
-    const char* e = vptq::tune_env("VPTQ_K256_KERNEL");
-    forced = !e ? 0 : (e[0] == 'v' ? 1 : e[0] == 'm' ? 2 : 0);
-  }
+  static const int forced = [] { const char* e = tune_env("VPTQ_K256_KERNEL"); return !e ? 0 : e[0] == 'v' ? 1 : e[0] == 'm' ? 2 : 0; }();
   const int tok = tokens > 2 ? 4 : tokens;
   const bool f16 = descs[0].dtype == VPTQ_DTYPE_F16;
   // SELECTIVE without a kernel that implements it = the reference's roundings (EXACT wins when both are set)
@@ -629,30 +606,22 @@ static hipError_t k256_for_each_launch(const VptqLayerDesc* descs, int n, int to
   return fn(descs, n, at, flags);
 }
 
-static const char* dt_name(bool f16) { return f16 ? "f16" : "bf16"; }
-
 // the launches vptq_quant_gemv / _grouped make for these layers, one instance string per launch, joined by " | "
 int gemv_k256_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes) {
-  size_t used = 0;
-  bool fits = true;
+  Text t = {buf, bytes, 0, true};
   const hipError_t e = k256_for_each_launch(descs, n, tokens, flags, [&](const VptqLayerDesc* d, int m, const int*, int fl) {
     const K256Decision D = k256_decide(d, m, tokens, fl);
-    char one[192];
-    if (D.choice.mfma) {
-      if (!D.m.ok) return hipErrorInvalidValue;
-      snprintf(one, sizeof(one), "gemv_k256m dt=%s ns=%d nst=%d perm=%d fast=%d tok=%d sb=%d entry=%d slots=%d units=%d sel=%d",
-               dt_name(D.m.f16), D.m.ns, D.m.nst, (int)D.m.perm, (int)D.m.fast, D.m.tok, (int)D.m.sb, D.m.entry, D.m.slots, D.m.units,
-               (int)D.m.selective);
-    } else {
-      snprintf(one, sizeof(one), "gemv_k256 dt=%s rows=%d tok=%d sw=%d perm=%d fast=%d entry=%d", dt_name(D.f16), D.rows, D.tok, D.sw,
-               (int)D.perm, (int)D.choice.fast, D.entry);
-    }
-    const int w = snprintf(buf + used, bytes - used, "%s%s", used ? " | " : "", one);
-    if (w < 0 || (size_t)w >= bytes - used) { fits = false; return hipErrorInvalidValue; }
-    used += (size_t)w;
-    return hipSuccess;
+    if (D.choice.mfma && !D.m.ok) return hipErrorInvalidValue;
+    if (t.used) t.add(" | ");
+    if (D.choice.mfma)
+      t.add("gemv_k256m dt=%s ns=%d nst=%d perm=%d fast=%d tok=%d sb=%d entry=%d slots=%d units=%d sel=%d", dt_text(D.m.f16), D.m.ns, D.m.nst,
+            (int)D.m.perm, (int)D.m.fast, D.m.tok, (int)D.m.sb, D.m.entry, D.m.slots, D.m.units, (int)D.m.selective);
+    else
+      t.add("gemv_k256 dt=%s rows=%d tok=%d sw=%d perm=%d fast=%d entry=%d", dt_text(D.f16), D.rows, D.tok, D.sw, (int)D.perm,
+            (int)D.choice.fast, D.entry);
+    return t.fits ? hipSuccess : hipErrorInvalidValue;
   });
-  return e == hipSuccess ? 0 : fits ? -1 : -2;
+  return e == hipSuccess ? 0 : t.fits ? -1 : -2;
 }
 
 static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, int flags,
@@ -702,9 +671,8 @@ static hipError_t launch_gemv_k256_one(const VptqLayerDesc* descs, int n, const 
     long long chunk = d.prefetch ? (d.prefetch_bytes + n_wg - 1) / n_wg : 0;
     chunk = (chunk + 127) / 128 * 128;
     Ly.pf_chunk = (int)chunk;
-    static std::atomic<int> pf_cap{-1};  // VPTQ_PF_BYTES: cap on the bytes each workgroup reads ahead
-    if (pf_cap < 0) { const char* e = vptq::tune_env("VPTQ_PF_BYTES"); pf_cap = e ? atoi(e) : 1 << 30; }
-    const long long cap = pf_cap.load();
+    static const int pf_cap = tune_int("VPTQ_PF_BYTES", 1 << 30);  // cap on the bytes each workgroup reads ahead
+    const long long cap = pf_cap;
     long long len = chunk < cap ? chunk : cap;
     if (len > wg_threads * 128) len = wg_threads * 128;  // one line per thread
     Ly.pf_len = (int)len;

@@ -263,7 +263,8 @@ static __device__ __forceinline__ CIssueL c_issue_of(const CLayerArgs& L) {
 }
 static __device__ __forceinline__ CConsL c_cons_of(const CLayerArgs& L) { return CConsL{L.y, L.bias, L.N, L.G, L.O}; }
 
-// f(slot 0), f(slot 1), ... f(slot kCDepth - 1) with the slot as a compile-time constant
+// f(slot 0), f(slot 1), ... f(slot kCDepth - 1) with the slot as a compile-time constant.  (Not common.h's for_slots<kCDepth>: its
+// halving recursion leaves the compiler another order of a few scalar instructions in this kernel - profiles/r18/README.md.)
 template <typename F>
 static __device__ __forceinline__ void c_for_slots(F&& f) {
   f(std::integral_constant<int, 0>{});
@@ -1350,11 +1351,6 @@ size_t gemv_k256c_selective_bytes(const VptqLayerDesc* descs, int n) {
   for (int i = 0; i < n; ++i) b += ((size_t)descs[i].num_indices * 8 * 4 + 255) / 256 * 256;
   return b;
 }
-static float c_kappa() {
-  static std::atomic<int> milli{-1};
-  if (milli < 0) { const char* e = vptq::tune_env("VPTQ_SELECTIVE_KAPPA"); const double v = e ? atof(e) : 0.0; milli = v > 0.0 ? (int)(v * 1000.0) : 6000; }
-  return (float)milli.load() * 1e-3f;
-}
 
 // ---- host side -------------------------------------------------------------------
 bool gemv_k256c_eligible(const VptqLayerDesc& d, int tokens) {
@@ -1402,9 +1398,7 @@ static long long c_blocks(const VptqLayerDesc* descs, int n, int cus, int visit)
 
 // workgroups > 0: that many (a plan query); 0: what a launch uses
 static int c_workgroups(bool dependent, int workgroups = 0) {
-  static std::atomic<int> forced_wgs{-1};  // VPTQ_K256C_WGS: tuning override of the workgroup count
-  if (forced_wgs < 0) { const char* e = vptq::tune_env("VPTQ_K256C_WGS"); forced_wgs = e ? atoi(e) : 0; }
-  const int fw = forced_wgs.load();
+  static const int fw = tune_int("VPTQ_K256C_WGS", 0);  // tuning override of the workgroup count
   const int cus = workgroups > 0 ? workgroups : fw > 0 ? fw : device_cus();
   return dependent && cus > kCFlagStride ? kCFlagStride : cus;
 }
@@ -1425,16 +1419,9 @@ bool gemv_k256c_fills_device(const VptqLayerDesc* descs, int n, bool dependent) 
 
 template <typename DT, bool DEP, int MODE = kCModeFolded>
 static hipError_t launch_c(const K256CParams& P, int grid, hipStream_t st) {
-  auto kern = gemv_k256c_kernel<DT, DEP, MODE>;
+  constexpr auto kern = gemv_k256c_kernel<DT, DEP, MODE>;
   constexpr uint32_t lds = c_lds_bytes(MODE);
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  if (const hipError_t e = allow_dynamic_lds<kern>((int)lds); e != hipSuccess) return e;
   if (DEP) {
     // A dependent chain's workgroups wait for each other INSIDE the launch (arrival flags per layer): every one of them
     // must be resident at once, or the waiting ones starve the rest.  The grid is one workgroup per CU; refuse it unless
@@ -1442,7 +1429,8 @@ static hipError_t launch_c(const K256CParams& P, int grid, hipStream_t st) {
     // CUs it reports.  (A device shared with another CU-pinning kernel, a CU mask or a partition mode the runtime does
     // not reflect here can still break the assumption: the library's advice for dependent layers is one launch per
     // layer)
-    static std::atomic<int> resident[64];
+    static std::atomic<int> resident[kMaxDevices];
+    const int dev = device_slot();
     if (!resident[dev]) {
       int per_cu = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, kCThreads, lds) != hipSuccess) per_cu = 0;
@@ -1612,7 +1600,7 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
       off += ((size_t)descs[i].num_indices * 8 * 4 + 255) / 256 * 256;
       max_rows = descs[i].num_indices > max_rows ? descs[i].num_indices : max_rows;
     }
-    H.kappa = c_kappa();
+    H.kappa = selective_kappa();
     if (f16) hipLaunchKernelGGL(k256c_hot_kernel<F16>, dim3((max_rows + kHotRows - 1) / kHotRows, n), dim3(256), 0, st, P, H);
     else hipLaunchKernelGGL(k256c_hot_kernel<BF16>, dim3((max_rows + kHotRows - 1) / kHotRows, n), dim3(256), 0, st, P, H);
     const hipError_t e = hipGetLastError();

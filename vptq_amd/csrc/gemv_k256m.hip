@@ -104,10 +104,6 @@ constexpr bool kAblQuarterMfma = (VPTQ_K256M_ABLATE & 32) != 0;
 constexpr bool kAblNoBias = (VPTQ_K256M_ABLATE & 64) != 0;    // the per-column bias values are not loaded
 constexpr bool kAblNoScale = (VPTQ_K256M_ABLATE & 128) != 0;  // the per-column scales are not loaded
 
-static __device__ __forceinline__ u32x4 ldg16(const void* base, uint32_t byte_off) {
-  return *(const u32x4*)as_global((const char*)base + byte_off);
-}
-
 // Queue load: 16 bytes at (wave-uniform base) + (32-bit lane offset).  An ordinary load whose
 // wait the compiler places (see the file comment).  A version with inline-assembly loads and
 // hand-written s_waitcnt counts was faster to write and unsafe: nothing stops the register
@@ -462,7 +458,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
     if (!STAGE) {
       // the queue carries x and scale but not the bias: sum b * x in one pass over the columns
       for (int c = tid * 8; c < G; c += kStageCols) {
-        const u32x4 xv = ldg16(Ly.x, (uint32_t)c * 2u), bv = ldg16(bp, (uint32_t)c * 2u);
+        const u32x4 xv = ld16(Ly.x, (uint32_t)c * 2u), bv = ld16(bp, (uint32_t)c * 2u);
 #pragma unroll
         for (int q = 0; q < 4; ++q) accb[0] = DT::dot2(xv[q], bv[q], accb[0]);
       }
@@ -1107,20 +1103,11 @@ static hipError_t launch_m(const K256Params& P, const K256MDecision& D, hipStrea
   if (slots < 1 || slots > kMMaxSlots || (P.layer[0].slots & 0xff) != slots) return hipErrorInvalidValue;
   const int lds = fixed + slots * kMRedSlot * TOK;
   if (lds > kMMaxLds) return hipErrorInvalidValue;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  auto allow_lds = [&](const void* kern, std::atomic<bool>& done) {
-    if (done) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, kMMaxLds);
-    done = e == hipSuccess;
-    return e;
-  };
   if constexpr (TOK == 1) {
     if (D.entry == 1) {  // the preloaded-argument entry point
       if (P.n_layers != 1) return hipErrorInvalidValue;
-      auto kern = gemv_k256m_kernel_1<DT, NS, NST, PERM, FAST>;
-      static std::atomic<bool> attr_set[64];
-      if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
+      constexpr auto kern = gemv_k256m_kernel_1<DT, NS, NST, PERM, FAST>;
+      if (const hipError_t e = allow_dynamic_lds<kern>(kMMaxLds); e != hipSuccess) return e;
       const K256Layer& L0 = P.layer[0];
       hipLaunchKernelGGL(kern, dim3(D.gx, 1), dim3(kMThreads), lds, st, L0.cent, L0.rcent, L0.x, L0.scale,
                          L0.N, L0.G, L0.O, L0.row_words, L0.wgs, L0.slots, P);
@@ -1128,9 +1115,8 @@ static hipError_t launch_m(const K256Params& P, const K256MDecision& D, hipStrea
     }
   }
   if (D.entry != 0) return hipErrorInvalidValue;
-  auto kern = gemv_k256m_kernel<DT, NS, NST, PERM, FAST, TOK>;
-  static std::atomic<bool> attr_set[64];
-  if (hipError_t e = allow_lds((const void*)kern, attr_set[dev]); e != hipSuccess) return e;
+  constexpr auto kern = gemv_k256m_kernel<DT, NS, NST, PERM, FAST, TOK>;
+  if (const hipError_t e = allow_dynamic_lds<kern>(kMMaxLds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(D.gx, P.n_layers), dim3(kMThreads), lds, st, P);
   return hipGetLastError();
 }
@@ -1268,9 +1254,7 @@ static void m_shares(const int* groups, int n, int cus, int* share) {
   }
 }
 static int m_cus() {
-  static std::atomic<int> forced_wgs{-1};  // VPTQ_K256M_WGS: tuning override of the CU count
-  if (forced_wgs < 0) { const char* e = vptq::tune_env("VPTQ_K256M_WGS"); forced_wgs = e ? atoi(e) : 0; }
-  const int fw = forced_wgs.load();
+  static const int fw = tune_int("VPTQ_K256M_WGS", 0);  // tuning override of the CU count
   return fw > 0 ? fw : device_cus();
 }
 int gemv_k256m_launch_units(const int* n_rows, int n) {

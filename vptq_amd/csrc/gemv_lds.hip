@@ -666,20 +666,8 @@ __global__ __launch_bounds__(kLThreads) void gemv_lds_mfma_kernel(const LdsParam
 }
 
 // ---- host side ------------------------------------------------------------------------
-static int lds_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0
-                   ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 static int lds_rows_per_group(int N) {
-  const int cus = lds_cus();
+  const int cus = device_cus();
   int RW = kLWaves;
   while (RW > 1 && (N + RW - 1) / RW < cus) RW >>= 1;
   return RW;
@@ -696,15 +684,8 @@ static bool lds_fmt_ok(int fmt) {
 
 template <typename DT, int FMT, int TOK>
 static hipError_t launch_lds_t(const LdsParams& P, int grid, int lds, hipStream_t st) {
-  auto kern = gemv_lds_kernel<DT, FMT, TOK>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  static std::atomic<bool> attr_set[64];
-  if (!attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLMaxLds);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = gemv_lds_kernel<DT, FMT, TOK>;
+  if (const hipError_t e = allow_dynamic_lds<kern>(kLMaxLds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kLThreads), lds, st, P);
   return hipGetLastError();
 }
@@ -735,15 +716,8 @@ static hipError_t launch_lds_dt(const LdsParams& P, int fmt, int tok, int grid, 
 
 template <typename DT, int FMT>
 static hipError_t launch_lds_mfma_t(const LdsParams& P, int grid, int lds, hipStream_t st) {
-  auto kern = gemv_lds_mfma_kernel<DT, FMT>;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  static std::atomic<bool> attr_set[64];
-  if (!attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, kLMaxLds);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = gemv_lds_mfma_kernel<DT, FMT>;
+  if (const hipError_t e = allow_dynamic_lds<kern>(kLMaxLds); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kLThreads), lds, st, P);
   return hipGetLastError();
 }
@@ -765,12 +739,8 @@ static hipError_t launch_lds_mfma_dt(const LdsParams& P, int fmt, int grid, int 
 
 // one token in the default arithmetic on a layer with row groups of >= 4 vector-rows: the MFMA kernel
 static bool lds_use_mfma(const LdsParams& P, int RW, bool exact) {
-  static std::atomic<int> force{-1};   // VPTQ_LDS_KERNEL=valu|mfma (A/B runs)
-  if (force < 0) {
-    const char* ev = vptq::tune_env("VPTQ_LDS_KERNEL");
-    force = ev && ev[0] == 'v' ? 1 : 0;
-  }
-  return force != 1 && P.tokens == 1 && !exact && RW >= 4 && P.G <= kLMStageIt * kLThreads * 8 &&
+  static const bool valu = [] { const char* e = tune_env("VPTQ_LDS_KERNEL"); return e && e[0] == 'v'; }();   // =valu|mfma (A/B runs)
+  return !valu && P.tokens == 1 && !exact && RW >= 4 && P.G <= kLMStageIt * kLThreads * 8 &&
          lds_mfma_bytes(P.k, P.kr, P.G) <= kLMaxLds && (((uintptr_t)P.x | (uintptr_t)P.scale | (uintptr_t)P.wbias_plain | (uintptr_t)P.perm) & 15) == 0;
 }
 
@@ -786,7 +756,7 @@ static LdsDecision lds_decide(const LdsParams& P, int fmt, bool f16, bool exact)
   D.tok = P.tokens > 2 ? 4 : P.tokens;
   D.lds = lds_bytes(P.k, P.kr, D.tok);
   if (D.lds > kLMaxLds || !lds_fmt_ok(fmt)) return D;
-  const int cus = lds_cus();
+  const int cus = device_cus();
   D.rw = lds_rows_per_group(P.N);
   D.n_groups = (P.N + D.rw - 1) / D.rw;
   D.grid = D.n_groups < cus ? D.n_groups : cus;

@@ -31,7 +31,6 @@
 //                         c f16(s x) and r f16(s x) from different workgroups)
 //   reference roundings (VPTQ_GEMV_EXACT, template EX): w = f16(f16(f16(c + r) * s) + b) per weight, y = sum w x + bias -
 //                         the product default since round 5; one table only (none or the 256-entry residual codebook)
-#include <cstdio>
 #include <cstring>
 
 #include "sliced.h"
@@ -473,7 +472,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
     if constexpr (RG) rq[S] = *(const uint16_t*)(rp + b64 * 2 + (size_t)lane_r);
     ++i_next;
   };
-  sl_for_slots<kSLQueue>([&](auto slot_c) {
+  for_slots<kSLQueue>([&](auto slot_c) {
     issue(slot_c);
     __builtin_amdgcn_sched_barrier(0);
   });
@@ -509,7 +508,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
     }
   };
   if constexpr (RG) {
-    sl_for_slots<kSLQueue>([&](auto slot_c) {
+    for_slots<kSLQueue>([&](auto slot_c) {
       gather(slot_c);
       __builtin_amdgcn_sched_barrier(0);
       issue(slot_c);
@@ -795,7 +794,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
     row_step();
   };
   while (!done) {   // (waves without elements skip it; ONE exit for the others)
-    sl_for_slots<kSLQueue>(step);
+    for_slots<kSLQueue>(step);
   }
 
   // ---- the rows whose words are still on their way: the last arriver of every output rounds and stores it
@@ -817,15 +816,8 @@ static hipError_t launch_sl(const SlicedDecision& D, const SlicedGroupParams& P,
   if (D.f16 != std::is_same<DT, F16>::value || D.nsl != NSL || D.res != RES || D.v != V || D.two != TWO || D.ex != EX || D.rg != RG ||
       D.tok != TOK || D.wpt != WPT)
     return hipErrorInvalidValue;
-  auto kern = gemv_sliced_kernel<DT, NSL, RES, V, TWO, EX, RG, TOK, WPT>;
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSLLdsLimit);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = gemv_sliced_kernel<DT, NSL, RES, V, TWO, EX, RG, TOK, WPT>;
+  if (const hipError_t e = allow_dynamic_lds<kern>((int)kSLLdsLimit); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(P.start[P.n]), dim3(kSLThreads), lds, st, P);
   return hipGetLastError();
 }
@@ -906,8 +898,7 @@ static uint32_t sl_operand_bytes(const VptqLayerDesc& d, bool exact, int tokens 
 // v = 16: 16 slices up to 14336 columns, else 32.  Reference roundings (6 bytes per column): v = 8: 8 slices up to 5376 columns
 // (4704), 16 up to 16288 (15616); v = 16: 16 / 32 at the same widths; wider layers: 0 (not served: gemv_gather)
 int gemv_sliced_slices(const VptqLayerDesc& d, bool exact) {
-  static std::atomic<int> force16{-1};   // VPTQ_SLICED_SLICES=16: the larger slice count for every layer (A/B)
-  if (force16 < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_SLICES"); force16 = (e && atoi(e) == 16) ? 1 : 0; }
+  static const int force16 = tune_int("VPTQ_SLICED_SLICES", 0) == 16;   // =16: the larger slice count for every layer (A/B)
   const int small = d.vector_len == 16 ? 16 : 8;
   if (!exact) {
     if (force16 == 1) return 2 * small;
@@ -919,8 +910,7 @@ int gemv_sliced_slices(const VptqLayerDesc& d, bool exact) {
   // with 128 KiB slices.  Measured on the Llama-3-8B shapes in v8-k65536-256 (profiles/r05/sliced_exact_slices_16_for_narrow_layers.txt):
   // 2 sequences 198.6 -> 210.7 tokens/s, 3: 270.6 -> 277.3, ONE: 127.1 -> 125.4 (the layers' own time +5 %) - one token is the
   // default's business, so the default stays "8 slices wherever one token fits".
-  static std::atomic<int> room2{-1};
-  if (room2 < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_SLICES"); room2 = (e && strcmp(e, "room2") == 0) ? 1 : 0; }
+  static const int room2 = [] { const char* e = tune_env("VPTQ_SLICED_SLICES"); return e && strcmp(e, "room2") == 0; }();
   for (int nsl = (force16 == 1 ? 2 * small : small); nsl <= 2 * small; nsl *= 2) {
     const uint32_t tab = (uint32_t)(d.num_centroids / nsl) * (uint32_t)d.vector_len * 2u;
     if ((tab + 15u) / 16u * 16u + sl_operand_bytes(d, true, (nsl == small && room2 == 1 && d.vector_len == 8) ? 2 : 1) <= kSLLdsLimit) return nsl;
@@ -1012,8 +1002,8 @@ VptqLayerDesc sl_part_desc(const VptqLayerDesc& d, int parts, int p) {
 // the column parts the reference's roundings are served with: 1 where the layer fits in one piece, else 2 or 3 equal parts of a
 // multiple of 8 columns whose slices' arrivals one accumulator word counts; 0 = none
 static int sl_exact_parts(const VptqLayerDesc& d) {
-  const char* e = vptq::tune_env("VPTQ_SLICED_PARTS");   // (A/B: at least this many parts where the columns divide)
-  const int least = e && atoi(e) > 1 ? atoi(e) : 1;
+  static const int knob = tune_int("VPTQ_SLICED_PARTS", 1);   // (A/B: at least this many parts where the columns divide)
+  const int least = knob > 1 ? knob : 1;
   const bool whole = gemv_sliced_eligible(d, true);
   if (whole && least <= 1) return 1;
   for (int parts = 2; parts <= 3; ++parts) {
@@ -1160,8 +1150,7 @@ int gemv_sliced_exact_tokens_parts(const VptqLayerDesc& d, int tokens) {
   if (nsl == 0) return 0;
   const uint32_t tab = (sl_tab_bytes(d, d.num_centroids, 0, true) + 15u) / 16u * 16u;
   if (tab + sl_operand_bytes(d, true, tokens) <= kSLLdsLimit) return 1;
-  static std::atomic<int> on{-1};
-  if (on < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_WINDOW_PARTS"); on = (e && e[0] == '0') ? 0 : 1; }
+  static const bool on = [] { const char* e = tune_env("VPTQ_SLICED_WINDOW_PARTS"); return !(e && e[0] == '0'); }();
   if (!on || d.vector_len != 8 || sl_two(d)) return 0;
   const int wc = sl_window_cols(d);
   for (int wparts = 2; wparts <= kSLWindows; wparts *= 2) {
@@ -1245,10 +1234,11 @@ int gemv_sliced_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int 
   SlicedDecision D;
   uint32_t lds = 0;
   if (sl_decide(d, L, n, some, ys, flags, wss, tokens, corr ? (const float*)some : nullptr, GP, lds, D) != hipSuccess) return -1;
-  const int w = snprintf(buf, bytes, "gemv_sliced dt=%s nsl=%d res=%d v=%d two=%d ex=%d rg=%d tok=%d wpt=%d wparts=%d parts=%d n=%d rpw=%d "
-                         "arrivals=%d whole1=%d side=%d perm=%d corr=%d", D.f16 ? "f16" : "bf16", D.nsl, (int)D.res, D.v, (int)D.two, (int)D.ex,
-                         (int)D.rg, D.tok, (int)D.wpt, D.wparts, D.parts, D.n, D.rpw, D.arrivals, D.whole1, D.side, (int)D.perm, (int)D.corr);
-  return w < 0 || (size_t)w >= bytes ? -2 : 0;
+  Text t = {buf, bytes, 0, true};
+  t.add("gemv_sliced dt=%s nsl=%d res=%d v=%d two=%d ex=%d rg=%d tok=%d wpt=%d wparts=%d parts=%d n=%d rpw=%d "
+        "arrivals=%d whole1=%d side=%d perm=%d corr=%d", dt_text(D.f16), D.nsl, (int)D.res, D.v, (int)D.two, (int)D.ex,
+        (int)D.rg, D.tok, (int)D.wpt, D.wparts, D.parts, D.n, D.rpw, D.arrivals, D.whole1, D.side, (int)D.perm, (int)D.corr);
+  return text_done(t);
 }
 hipError_t launch_gemv_sliced(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int flags,
                               void* ws, hipStream_t st, const float* corr) {

@@ -24,7 +24,6 @@
 // (it then waits for vmcnt(0) in every step - the activations of a phase are loaded by ONE asm statement with its own wait,
 // a layer's permutation is applied by a pre-pass), a load that is issued on some paths only (the waits then shrink down the
 // unrolled round), 64-bit booleans and index -> address arithmetic in the scalar bookkeeping.
-#include <cstdio>
 
 #include "sliced.h"
 
@@ -43,20 +42,6 @@ template <int NV> constexpr int st_queue() { return NV >= 64 ? 4 : VPTQ_ST_QUEUE
 #ifndef VPTQ_ST_ABLATE
 #define VPTQ_ST_ABLATE 0
 #endif
-
-typedef _Float16 st_h8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 st_b8_t __attribute__((ext_vector_type(8)));
-template <typename DT>
-static __device__ __forceinline__ f32x4 st_mfma(u32x4 a, u32x4 b, f32x4 c) {
-  if constexpr (std::is_same<DT, F16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(st_h8_t, a), __builtin_bit_cast(st_h8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(st_b8_t, a), __builtin_bit_cast(st_b8_t, b), c, 0, 0, 0);
-}
-static __device__ __forceinline__ u32x2 st_lds_tr8(uint32_t byte_addr) {   // ds_read_b64_tr_b16
-  typedef __attribute__((address_space(3))) s4_t lds_s4_t;
-  return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(uintptr_t)byte_addr));
-}
 
 struct SlicedTokParams {
   SlicedParams p;            // as for one token; x / y: token 0, rows_per_wave / n_rowblocks: this launch's
@@ -510,15 +495,15 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
 #pragma unroll
       for (int i = 0; i < EW; ++i) {
         const uint32_t e = eq[S][i];
-        bt[i] = st_lds_tr8((e >> 16) * kEntry + q8);
+        bt[i] = lds_tr8((e >> 16) * kEntry + q8);
         const uint32_t cc = (e & 0xffffu) - c0;
         uint32_t ci = cc | qmask;
         ci = ci < wlen ? ci : wlen;
-        at[i] = st_lds_tr8(kXOff + ci * kXStride + xq);
-        if constexpr (RES) rt[i] = st_lds_tr8(TP.res_off + (rq[S][i] << 4) + q8);
+        at[i] = lds_tr8(kXOff + ci * kXStride + xq);
+        if constexpr (RES) rt[i] = lds_tr8(TP.res_off + (rq[S][i] << 4) + q8);
         if constexpr (EX) {   // EVERY chunk's lanes bring their element's scale and bias (the zero column's: 0, 0)
           // lanes with m = lane & 3 even receive the four elements' scales, odd ones their biases; the neighbour has the other
-          const u32x2 t = st_lds_tr8(TP.sb_off + (cc < wlen ? cc : wlen) * 8u);
+          const u32x2 t = lds_tr8(TP.sb_off + (cc < wlen ? cc : wlen) * 8u);
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t[h], 0xB1 /* quad_perm [1, 0, 3, 2] */, 0xf, 0xf, true);
@@ -541,8 +526,8 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
 #pragma unroll
       for (int i = 0; i < EW; i += 2) {
         const u32x4 A = {at[i][0], at[i][1], at[i + 1][0], at[i + 1][1]};
-        accm = st_mfma<DT>(A, u32x4{bt[i][0], bt[i][1], bt[i + 1][0], bt[i + 1][1]}, accm);
-        if constexpr (RES && !EX) accm = st_mfma<DT>(A, u32x4{rt[i][0], rt[i][1], rt[i + 1][0], rt[i + 1][1]}, accm);
+        accm = mfma16x16x32<DT>(A, u32x4{bt[i][0], bt[i][1], bt[i + 1][0], bt[i + 1][1]}, accm);
+        if constexpr (RES && !EX) accm = mfma16x16x32<DT>(A, u32x4{rt[i][0], rt[i][1], rt[i + 1][0], rt[i + 1][1]}, accm);
       }
       return;
     }
@@ -672,11 +657,11 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
   };
 
   iq_advance();
-  sl_for_slots<kSTQueue>([&](auto slot_c) { issue(slot_c); __builtin_amdgcn_sched_barrier(0); });
+  for_slots<kSTQueue>([&](auto slot_c) { issue(slot_c); __builtin_amdgcn_sched_barrier(0); });
   asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kSTQueue * (RES ? 2 : 1) * EW) : "memory");   // the DMA'd table: older than the queue's loads
   enter_phase(0);
   cq_advance();
-  while (done == 0) sl_for_slots<kSTQueue>(step);
+  while (done == 0) for_slots<kSTQueue>(step);
 
   // ---- partial sums of this (table, slice): [token][NSLT][N x V]; sum b x rides with slice 0
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
@@ -775,15 +760,8 @@ static hipError_t launch_st(const SlicedTokDecision& D, const SlicedTokGroupPara
   // this instantiation is the one the decision names (st_decide)
   if (D.f16 != std::is_same<DT, F16>::value || D.nsl != NSL || D.res != RES || D.v != V || D.two != TWO || D.tok != TOK || D.ex != EX)
     return hipErrorInvalidValue;
-  auto kern = gemv_sliced_tok_kernel<DT, NSL, RES, V, TWO, TOK, EX>;
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!attr_set[dev]) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSLLdsLimit);
-    if (e != hipSuccess) return e;
-    attr_set[dev] = true;
-  }
+  constexpr auto kern = gemv_sliced_tok_kernel<DT, NSL, RES, V, TWO, TOK, EX>;
+  if (const hipError_t e = allow_dynamic_lds<kern>((int)kSLLdsLimit); e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kSLThreads), lds, st, P);
   return hipGetLastError();
 }
@@ -856,9 +834,8 @@ size_t gemv_sliced_tok_workspace_bytes(const VptqLayerDesc& d, int tokens) {
 }
 // VPTQ_SLICED_ONE_PASS=0: 2 / 3 exact tokens through the column-phase kernel as well (A/B runs)
 static bool st_one_pass(const VptqLayerDesc& d, int tokens, bool exact) {
-  static std::atomic<int> on{-1};
-  if (on < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_ONE_PASS"); on = (e && atoi(e) == 0 && e[0] == '0') ? 0 : 1; }
-  return exact && on == 1 && gemv_sliced_exact_tokens_ok(d, tokens);
+  static const bool on = [] { const char* e = tune_env("VPTQ_SLICED_ONE_PASS"); return !(e && atoi(e) == 0 && e[0] == '0'); }();
+  return exact && on && gemv_sliced_exact_tokens_ok(d, tokens);
 }
 
 // rows per wave: one round of workgroups (slices x tables x row blocks of 16 waves ~ the CUs)
@@ -877,8 +854,7 @@ static bool st_plan(const VptqLayerDesc& d, const VptqSlicedLayout* L, int token
   if (tokens < 2 || tokens > 8) return false;
   const bool res = sl_res256(d), two = sl_two(d);
   if (exact && !st_exact_ok(d)) return false;
-  static std::atomic<int> tok4{-1};   // VPTQ_SLICED_TOK4=1: 2 tokens through the 4-slot (matrix-pipe) kernel too (A/B runs)
-  if (tok4 < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_TOK4"); tok4 = (e && atoi(e) == 1) ? 1 : 0; }
+  static const bool tok4 = tune_flag("VPTQ_SLICED_TOK4");   // =1: 2 tokens through the 4-slot (matrix-pipe) kernel too (A/B runs)
   pl.tok = tokens > 4 ? 8 : (tokens == 2 && !tok4 && !exact) ? 2 : 4;   // (the reference's roundings: matrix-pipe mode only)
   uint32_t tab = sl_tab_bytes(d, d.num_centroids, 0, exact);
   if (two) {
@@ -888,10 +864,9 @@ static bool st_plan(const VptqLayerDesc& d, const VptqSlicedLayout* L, int token
   pl.x_off = (tab + 15u) & ~15u;
   const int G = d.group_size;
   const int wcols = (G + kSTWindows * 8 - 1) / (kSTWindows * 8) * 8;
-  static std::atomic<int> min_phases{-1};   // VPTQ_SLICED_MIN_PHASES=2 / 4: more phases than the LDS asks for (A/B runs)
-  if (min_phases < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_MIN_PHASES"); const int v = e ? atoi(e) : 1; min_phases = (v == 2 || v == 4) ? v : 1; }
-  static std::atomic<int> no_reg_sums{-1};  // VPTQ_SLICED_LDS_SUMS=1: the rows' sums in LDS in every mode (A/B runs)
-  if (no_reg_sums < 0) { const char* e = vptq::tune_env("VPTQ_SLICED_LDS_SUMS"); no_reg_sums = (e && atoi(e) == 1) ? 1 : 0; }
+  static const int phases_knob = tune_int("VPTQ_SLICED_MIN_PHASES", 1);   // =2 / 4: more phases than the LDS asks for (A/B runs)
+  const int min_phases = (phases_knob == 2 || phases_knob == 4) ? phases_knob : 1;
+  static const bool no_reg_sums = tune_flag("VPTQ_SLICED_LDS_SUMS");  // =1: the rows' sums in LDS in every mode (A/B runs)
   for (int rpw = rpw0 > 0 ? rpw0 : st_rows_per_wave(d, exact); rpw >= 1; rpw = rpw > 1 ? (rpw + 1) / 2 : 0) {
     for (int phases = min_phases; phases <= kSTWindows; phases *= 2) {
       const int wmax = (kSTWindows / phases) * wcols < G ? (kSTWindows / phases) * wcols : G;   // columns of the widest phase
@@ -1091,10 +1066,10 @@ int gemv_sliced_tok_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, 
   void* acc[kSTMaxGroup];
   if (st_decide(d, L, n, some, ys, tokens, flags, wss, one_pass, acc, GP, jobs, lds, D) != hipSuccess) return -1;
   if (one_pass) return gemv_sliced_instance(d, L, n, tokens, flags, false, buf, bytes);
-  const int w = snprintf(buf, bytes, "gemv_sliced_tok dt=%s nsl=%d res=%d v=%d two=%d tok=%d ex=%d phases=%d rpw=%d regsums=%d n=%d whole1=%d perm=%d",
-                         D.f16 ? "f16" : "bf16", D.nsl, (int)D.res, D.v, (int)D.two, D.tok, (int)D.ex, D.phases, D.rpw, D.reg_sums, D.n, D.whole1,
-                         (int)D.perm);
-  return w < 0 || (size_t)w >= bytes ? -2 : 0;
+  Text t = {buf, bytes, 0, true};
+  t.add("gemv_sliced_tok dt=%s nsl=%d res=%d v=%d two=%d tok=%d ex=%d phases=%d rpw=%d regsums=%d n=%d whole1=%d perm=%d", dt_text(D.f16),
+        D.nsl, (int)D.res, D.v, (int)D.two, D.tok, (int)D.ex, D.phases, D.rpw, D.reg_sums, D.n, D.whole1, (int)D.perm);
+  return text_done(t);
 }
 hipError_t launch_gemv_sliced_tok(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int tokens, int flags,
                                   void* ws, hipStream_t st) {

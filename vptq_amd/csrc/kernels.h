@@ -1,25 +1,11 @@
 // Internal launcher prototypes (one per .hip translation unit).
 #pragma once
-#include <atomic>
 #include <hip/hip_runtime.h>
 
 #include "../../include/vptq_hip.h"
-#include "tune_env.h"
+#include "launch.h"
 
 namespace vptq {
-
-// CUs of the current device, looked up once per device; 256 (MI355X) where there is no device to ask - the host-only
-// queries (kernel names, chain plans, instances) then answer for that
-inline int device_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (!cus[dev]) {
-    hipDeviceProp_t p;
-    cus[dev] = hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0 ? p.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
 
 // What one launch of the remaining GEMV families IS - the instantiation's template arguments and the launch-shape facts: each
 // family's *_decide is read by its launcher AND printed by vptq_quant_gemv_instance / vptq_quant_gemv_v2_instance (abi.hip), so the
@@ -114,6 +100,11 @@ int gemv_sliced_whole_table(const VptqLayerDesc& d, int table);   // VptqSlicedL
 size_t gemv_sliced_workspace_bytes(const VptqLayerDesc& d);
 // gemv_hot.hip - VPTQ_GEMV_SELECTIVE over the sliced layouts: thresholds, x with the hot blocks zeroed, the hot blocks' exact products
 bool gemv_hot_eligible(const VptqLayerDesc& d);
+// the threshold factor kappa of VPTQ_GEMV_SELECTIVE (here and in gemv_k256c.hip): 6, or VPTQ_SELECTIVE_KAPPA (to a thousandth)
+inline float selective_kappa() {
+  static const int milli = [] { const char* e = tune_env("VPTQ_SELECTIVE_KAPPA"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? (int)(v * 1000.0) : 6000; }();
+  return (float)milli * 1e-3f;
+}
 size_t gemv_hot_bytes(const VptqLayerDesc& d);
 hipError_t launch_gemv_hot(const VptqLayerDesc& d, const void* x, void* extra, const void** x_masked, const float** corr, hipStream_t st);
 hipError_t launch_gemv_sliced(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int flags,

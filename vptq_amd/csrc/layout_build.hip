@@ -270,12 +270,7 @@ hipError_t launch_layout_plan(const LayoutBuildParams& a, hipStream_t st) {
 }
 
 hipError_t launch_layout_fill(const LayoutBuildParams& a, hipStream_t st) {
-  static std::atomic<int> attr{0};
-  if (!attr.load()) {
-    const hipError_t e = hipFuncSetAttribute((const void*)layout_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    if (e != hipSuccess) return e;
-    attr = 1;
-  }
+  if (const hipError_t e = allow_dynamic_lds<layout_fill_kernel>(131072); e != hipSuccess) return e;
   if (a.total_blocks <= 0) {
     hipLaunchKernelGGL(layout_pad_block_kernel, dim3(1), dim3(64), 0, st, a);
     return hipGetLastError();

@@ -96,12 +96,7 @@ __global__ __launch_bounds__(kRPThreads) void sliced_repack_kernel(RepackArgs a)
 size_t sliced_repack_lds_bytes(const VptqLayerDesc& d) { return (size_t)((d.row_words + 3) / 4) * 16; }
 
 hipError_t launch_sliced_repack(const VptqLayerDesc& d, const VptqSlicedLayout* L, int parts, int side_bytes, void* out, hipStream_t st) {
-  static std::atomic<int> attr{0};
-  if (!attr.load()) {
-    const hipError_t e = hipFuncSetAttribute((const void*)sliced_repack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kRPMaxLds);
-    if (e != hipSuccess) return e;
-    attr = 1;
-  }
+  if (const hipError_t e = allow_dynamic_lds<sliced_repack_kernel>(kRPMaxLds); e != hipSuccess) return e;
   RepackArgs a = {};
   const int G = d.group_size, width = G / parts;
   for (int p = 0; p < parts; ++p) {

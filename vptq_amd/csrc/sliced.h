@@ -54,18 +54,6 @@ struct SlicedParams {
 };
 constexpr int kSLWindows = VPTQ_SLICED_WINDOWS;
 
-// f(slot 0), ... f(slot kSLQueue - 1) with the slot as a compile-time constant
-template <int I0, int I1, typename F>
-static __device__ __forceinline__ void sl_for_range(F&& f) {
-  if constexpr (I1 - I0 == 1) f(std::integral_constant<int, I0>{});
-  else {
-    sl_for_range<I0, (I0 + I1) / 2>(f);
-    sl_for_range<(I0 + I1) / 2, I1>(f);
-  }
-}
-template <int Q, typename F>
-static __device__ __forceinline__ void sl_for_slots(F&& f) { sl_for_range<0, Q>(f); }
-
 // ---- host side (gemv_sliced.hip)
 bool sl_res256(const VptqLayerDesc& d);   // v = 8 with the 256-entry residual table: a byte per element beside the main layout
 bool sl_two(const VptqLayerDesc& d);      // any other residual table: a second table with a layout of its own

@@ -11,5 +11,12 @@ static inline const char* tune_env(const char* name) {
   static const bool on = [] { const char* e = getenv("VPTQ_TUNING"); return e && e[0] == '1'; }();
   return on ? getenv(name) : nullptr;
 }
+// A knob's value, for `static const int v = tune_int(...)` at its one site of use: read once per process, at first use.
+// tune_int: atoi of the string, `fallback` where the knob is not set; tune_flag: set to exactly the integer 1
+static inline int tune_int(const char* name, int fallback) {
+  const char* e = tune_env(name);
+  return e ? atoi(e) : fallback;
+}
+static inline bool tune_flag(const char* name) { return tune_int(name, 0) == 1; }
 
 }  // namespace vptq
