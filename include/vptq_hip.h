@@ -580,6 +580,30 @@ VPTQ_API int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* desc, int to
 VPTQ_API int vptq_quant_gemm_gatherx(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of the canonical format for 17 - 64 tokens in ONE launch (gemm_k256w_kernel in gemm_k256.hip; added within ABI 12;
+ * present when the symbols are).  The layers vptq_quant_gemv serves with gemm_k256_kernel - v = 8, 256 main + 256 residual centroids,
+ * one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and bias_permuted), group_size ==
+ * in_features (a multiple of 8) - with the tokens as tb = ceil(tokens / 16) blocks of the M dimension of a 16x16x16 MFMA: the indices
+ * are read, gathered and rebuilt once for all blocks, where vptq_quant_gemv runs tb launches of 16 tokens.  The reference's roundings
+ * per weight (w = r16(r16(r16(c + r) * s) + b): vptq_dequant's bits); the K-step -> wave mapping and the order of the fp32 sums are
+ * gemm_k256_kernel's and do not depend on the token count or on a token's slot: a token's output bits are the same in every slot of
+ * every batch, and equal those of vptq_quant_gemv where it launches gemm_k256_kernel.  No workspace, no atomics; graph-capturable.
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags: VPTQ_GEMV_OUT_F32 stores the fp32 sums (y is float32);
+ *   VPTQ_GEMV_FAST_MATH / _EXACT / _SELECTIVE are accepted and change nothing.
+ * vptq_quant_gemm_k256w_supported: 1 where the call serves (desc, tokens) - such a layer and 17 <= tokens <= 64 - else 0; host logic.
+ * vptq_quant_gemm_k256w: NULL desc / x / y VPTQ_E_NULL; tokens outside [17, 64], or an x that is not 16-byte aligned, VPTQ_E_TOKENS; a
+ *   layer it does not serve VPTQ_E_UNSUPPORTED; nothing is launched then.
+ * vptq_quant_gemm_k256w_instance: the instantiation of gemm_k256w_kernel<DT, PERM, TB> and the launch shape, as one line (the launcher's
+ *   own decision; host logic, without a device the CU count is taken as 256):
+ *   gemm_k256w dt=f16|bf16 perm=0|1 tok=N tb=2|3|4 rgs=N pass=1x2|1x3|1x4
+ *       tok the tokens of the launch, tb its token blocks, rgs the most row groups (4 vector-rows) one workgroup walks, pass the
+ *       instantiation <NRG, TB> of gemm_k256's pass it runs per row group (NRG row groups x TB token blocks share the 32 accumulator
+ *       registers; NRG is 1).  Returns as vptq_quant_gemm_gather_instance does.
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens (48) and vptq_quant_gemv_kernel_name do not route here: callers choose this entry. */
+VPTQ_API int vptq_quant_gemm_k256w_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_k256w(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
+VPTQ_API int vptq_quant_gemm_k256w_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
 /* Diagnostic (ABI 12): WHICH INSTANTIATION of dequant_kernel<DT, V, TAB> vptq_dequant(desc, W) would launch and which paths its

@@ -38,6 +38,7 @@ GEMV_MAX_TOKENS = 64       # most vptq_quant_gemv accepts (any layer: 16); per l
 GEMV_ANY_FORMAT_TOKENS = 8  # the fused GEMV is the faster path for every format up to here
 GEMV_CHAIN_DEPENDENT = 1 << 6  # vptq_quant_gemv_chain: layer i + 1 reads what layer i wrote
 GEMV_FORCE_BATCHED = 1 << 7    # the one-pass batched-decode kernel wherever eligible (tests, A/B)
+GEMV_FORCE_ANY = GEMV_FORCE_GENERIC | GEMV_FORCE_MFMA | GEMV_FORCE_VALU | GEMV_FORCE_BATCHED
 GEMV_COLUMN_PARTS = 1 << 8     # vptq_quant_gemv_sliced_grouped: the descriptors are column ranges of ONE layer (shared y / workspace)
 GEMV_SELECTIVE = 1 << 9        # folded form + the reference's roundings on the activation columns that dominate the token (ABI 10)
 # return codes (include/vptq_hip.h)
@@ -162,6 +163,10 @@ EXPORTS = {
     "vptq_quant_gemm_gatherx_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gatherx": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
     "vptq_quant_gemm_gatherx_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 17 - 64 tokens of the canonical format in one launch (gemm_k256w_kernel, gemm_k256.hip)
+    "vptq_quant_gemm_k256w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_k256w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
+    "vptq_quant_gemm_k256w_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

@@ -1167,9 +1167,11 @@ int vptq_quant_gemm(const VptqLayerDesc* d, const void* x, void* y, int tokens, 
 
 // ---- gemm_gather.hip / gemm_gatherx.hip: 1 - 16 tokens of the large-codebook formats in one launch (added within ABI 12).  A layer
 // has one of the two kernels; the entries of both are the three shapes below, given the kernel's name, what it serves, its
-// eligibility function and its launcher
+// eligibility function and its launcher.  gemm_k256w (gemm_k256.hip): the same three shapes for 17 - 64 tokens of the canonical format
 struct BatchedDecode {
   const char* name;
+  int tok_lo, tok_hi;        // the token counts of one launch
+  int misaligned;            // the code of an x that is not 16-byte aligned
   const char* launch_what;   // hip_fail's "what" of a failed launch
   const char* serves;
   bool (*eligible)(const VptqLayerDesc&, int);
@@ -1185,14 +1187,23 @@ static void print_gemm_gatherx(Text& t, const VptqLayerDesc& d, int tokens) {
   t.add("gemm_gatherx dt=%s v=%d ib=%d rb=%d res=%s perm=%d tok=%d tiles=%d wgcu=%d rgs=%d", dt_text(D.f16), D.v, D.ib, D.rb,
         D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", (int)D.perm, D.tok, D.tiles, D.wgcu, D.rgs);
 }
+static void print_gemm_k256w(Text& t, const VptqLayerDesc& d, int tokens) {
+  const vptq::GemmK256WDecision D = vptq::gemm_k256w_decide(d, tokens);
+  t.add("gemm_k256w dt=%s perm=%d tok=%d tb=%d rgs=%d pass=1x%d", dt_text(D.f16), (int)D.perm, D.tok, D.tb, D.rgs, D.tb);
+}
 static const BatchedDecode kGemmGather = {
-  "gemm_gather", "gemm_gather launch", "v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids, one codebook, no outlier columns, scale and bias, "
+  "gemm_gather", 1, 16, VPTQ_E_UNSUPPORTED, "gemm_gather launch", "v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids, one codebook, no outlier columns, scale and bias, "
   "group_size == in_features (a multiple of 8), 16-byte aligned tables", vptq::gemm_gather_eligible, vptq::launch_gemm_gather,
   print_gemm_gather};
 static const BatchedDecode kGemmGatherX = {
-  "gemm_gatherx", "gemm_gatherx launch", "v = 8 / 16, 16384 ... 65536 main centroids, any residual codebook (index_bits + res_bits <= 32), one codebook, no "
+  "gemm_gatherx", 1, 16, VPTQ_E_UNSUPPORTED, "gemm_gatherx launch", "v = 8 / 16, 16384 ... 65536 main centroids, any residual codebook (index_bits + res_bits <= 32), one codebook, no "
   "outlier columns, scale and bias, group_size == in_features (a multiple of 8), 16-byte aligned tables - and not the layers gemm_gather "
   "serves", vptq::gemm_gatherx_eligible, vptq::launch_gemm_gatherx, print_gemm_gatherx};
+
+static const BatchedDecode kGemmK256W = {
+  "gemm_k256w", 17, 64, VPTQ_E_TOKENS, "gemm_k256w launch", "the canonical format (v = 8, 256 + 256 centroids, one codebook, no outlier columns, "
+  "scale and bias, group_size == in_features (a multiple of 8), with perm: scale_permuted and bias_permuted)", vptq::gemm_k256w_eligible,
+  vptq::launch_gemm_k256w, print_gemm_k256w};
 
 static int batched_supported(const BatchedDecode& k, const VptqLayerDesc* d, int tokens) {
   return validate_layer(d) == VPTQ_OK && k.eligible(*d, tokens) ? 1 : 0;
@@ -1200,7 +1211,7 @@ static int batched_supported(const BatchedDecode& k, const VptqLayerDesc* d, int
 
 // the checks of an entry and its `_instance` on the token count and the layer
 static int batched_validate(const BatchedDecode& k, const VptqLayerDesc* d, int tokens) {
-  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
+  if (tokens < k.tok_lo || tokens > k.tok_hi) return fail(VPTQ_E_TOKENS, "tokens %d outside [%d, %d]", tokens, k.tok_lo, k.tok_hi);
   if (!k.eligible(*d, tokens)) return fail(VPTQ_E_UNSUPPORTED, "%s serves %s", k.name, k.serves);
   return VPTQ_OK;
 }
@@ -1210,7 +1221,7 @@ static int batched_launch(const BatchedDecode& k, const VptqLayerDesc* d, const 
   if (const int rc = validate_layer(d)) return rc;
   if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
   if (const int rc = batched_validate(k, d, tokens)) return rc;
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "%s: x must be 16-byte aligned", k.name);
+  if ((((uintptr_t)x) & 15) != 0) return fail(k.misaligned, "%s: x must be 16-byte aligned", k.name);
   const hipError_t e = k.launch(*d, x, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, (hipStream_t)stream);
   if (e != hipSuccess) return hip_fail(e, k.launch_what);
   return VPTQ_OK;
@@ -1233,6 +1244,9 @@ int vptq_quant_gemm_gather_instance(const VptqLayerDesc* d, int tokens, int, cha
 int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmGatherX, d, tokens); }
 int vptq_quant_gemm_gatherx(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmGatherX, d, x, y, tokens, flags, stream); }
 int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmGatherX, d, tokens, buf, bytes); }
+int vptq_quant_gemm_k256w_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmK256W, d, tokens); }
+int vptq_quant_gemm_k256w(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmK256W, d, x, y, tokens, flags, stream); }
+int vptq_quant_gemm_k256w_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmK256W, d, tokens, buf, bytes); }
 
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {

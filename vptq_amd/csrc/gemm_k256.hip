@@ -27,6 +27,11 @@
 // gathers + 16 bytes of LDS writes + 16 bytes of LDS operand reads; the MFMA work is 1 / 16 of
 // the instruction stream.  bf16 (round 6): the same tile, its roundings as blocks of v_dot2_f32_bf16 (common.h: BF16::add4 /
 // scale_bias4 - 44 instructions per index instead of 12) and v_mfma_f32_16x16x16_bf16; before, bf16 kept the <= 4-token launches.
+//
+// 17 - 64 tokens (gemm_k256w_kernel, vptq_quant_gemm_k256w): the same pass over TB = 2 ... 4 blocks of 16 tokens.  Image, tile, index
+// queue and epilogue are shared; only the MFMA phase knows about TB (one B read feeds TB MFMAs, TB x 2 accumulators, the x of the
+// blocks past the first requested once the tile is written).  The weights are unpacked, gathered and rebuilt once per launch where
+// vptq_quant_gemv runs TB launches of 16 tokens; x (from L2, one 128-byte line per lane and token) is the only traffic that grows.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -73,7 +78,11 @@ static __device__ __forceinline__ uint32_t tile_row(int nb, int wq, int i, int k
   return (uint32_t)((((nb * 16 + wq) * 4 + i) * 4) + kg);
 }
 
-template <typename DT, bool PERM, int NRG>
+// One pass: NRG row groups x TB blocks of 16 tokens (NRG * TB <= 4: the 32 accumulator registers).  TB = 1 is gemm_k256_kernel's
+// pass; TB = 2 ... 4 are gemm_k256w_kernel's, which differ in the MFMA phase only: every B operand read from the tile is used for
+// the TB token blocks, and the x operands of the blocks past the first are requested AFTER the tile has been written (the 16
+// registers of the rebuilt weights are free by then) instead of being held through the dequantisation.
+template <typename DT, bool PERM, int NRG, int TB = 1>
 static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, unsigned char* gsmem,
                                                       const int rg0) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -98,9 +107,12 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
   // ---- MFMA role: wave wq = wave, lane (output j / token, k group)
   const int mj = lane & 15, mkg = lane >> 4;
 
-  f32x4 acc[NRG][2];
+  static_assert(NRG * TB <= 4, "32 accumulator registers");
+  f32x4 acc[NRG][TB][2];
 #pragma unroll
-  for (int g = 0; g < NRG; ++g) { acc[g][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[g][1] = acc[g][0]; }
+  for (int g = 0; g < NRG; ++g)
+#pragma unroll
+    for (int t = 0; t < TB; ++t) { acc[g][t][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[g][t][1] = acc[g][t][0]; }
 
   // A pass is a flat sequence of steps (tile, row group), row groups fastest; the step loop is
   // unrolled by kQ = 4 (NRG divides it), so every register-queue slot, the row group and "is
@@ -118,8 +130,11 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
     const uint32_t coff = (uint32_t)(col < G ? col : G - 4) * 2u;
     return __builtin_nontemporal_load((const u32x2*)as_global((const char*)P.idx + (size_t)roff + coff));
   };
-  const uint16_t* const xrow = as_global(P.x + (size_t)(mj < tokens ? mj : tokens - 1) * G);
-  auto load_x = [&](int tile, u32x4& lo, u32x4& hi4) {
+  // (token block t: rows 16 t + mj; a row past `tokens` reads the last row and is zeroed in the MFMA phase)
+  const uint16_t* const xrow0 = as_global(P.x + (size_t)(mj < tokens ? mj : tokens - 1) * G);
+  auto load_x = [&](int tile, int t, u32x4& lo, u32x4& hi4) {
+    const int row = t * 16 + mj;
+    const uint16_t* const xrow = t == 0 ? xrow0 : as_global(P.x + (size_t)(row < tokens ? row : tokens - 1) * G);
     const int col = tile * kGTileCols + wave * 64 + mkg * 16;
     const int c0 = col < G ? col : G - 8, c1 = col + 8 < G ? col + 8 : G - 8;
     if constexpr (PERM) {
@@ -147,7 +162,9 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
   u32x2 iq[kQ];
 #pragma unroll
   for (int k = 0; k < kQ; ++k) iq[k] = load_idx(k);
-  u32x4 xa_lo = {0, 0, 0, 0}, xa_hi = {0, 0, 0, 0};
+  u32x4 xa_lo[TB], xa_hi[TB];
+#pragma unroll
+  for (int t = 0; t < TB; ++t) { xa_lo[t] = u32x4{0, 0, 0, 0}; xa_hi[t] = xa_lo[t]; }
 
   auto do_step = [&](auto kc, int step) {
     constexpr int K = decltype(kc)::value;
@@ -159,7 +176,7 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
       // (used in the MFMA phase, ~1000 cycles from here)
       sv = sv_next; bv = bv_next;
       __builtin_amdgcn_sched_barrier(0);
-      load_x(tile, xa_lo, xa_hi);
+      load_x(tile, 0, xa_lo[0], xa_hi[0]);
     }
     if constexpr (g == NRG - 1) load_sb(tile + 1 < n_tiles ? tile + 1 : tile, sv_next, bv_next);
     __builtin_amdgcn_sched_barrier(0);
@@ -200,26 +217,40 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
                        __builtin_amdgcn_perm(w2[3][p], w2[2][p], 0x07060302u)};
       lds_store16(tile_wr + (((uint32_t)p ^ (uint32_t)di) << 4), v);
     }
+    if constexpr (TB > 1) {
+      // the other token blocks' x: requested here, where the registers of the rebuilt weights are free, and waited for behind the barrier
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int t = 1; t < TB; ++t) load_x(tile, t, xa_lo[t], xa_hi[t]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     __syncthreads();  // tile complete
     // ---- MFMA: this wave's 64 columns = 4 K-steps x 2 output blocks, into row group g
     const int colw = tile * kGTileCols + wave * 64 + mkg * 16;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const bool live = mj < tokens && colw + 4 * i < G;
-      const u32x4& xs4 = i < 2 ? xa_lo : xa_hi;
-      const u32x2 av = {live ? xs4[(i & 1) * 2] : 0u, live ? xs4[(i & 1) * 2 + 1] : 0u};
+      u32x2 av[TB];
+#pragma unroll
+      for (int t = 0; t < TB; ++t) {
+        const bool live = t * 16 + mj < tokens && colw + 4 * i < G;
+        const u32x4& xs4 = i < 2 ? xa_lo[t] : xa_hi[t];
+        av[t] = u32x2{live ? xs4[(i & 1) * 2] : 0u, live ? xs4[(i & 1) * 2 + 1] : 0u};
+      }
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         const uint32_t pair = ((uint32_t)mj >> 1) ^ (uint32_t)i;
         typedef __attribute__((address_space(3))) const u32x2 lds_u32x2_t;
         const u32x2 b = *(lds_u32x2_t*)(uintptr_t)(kGImage + tile_row(nb, wave, i, mkg) * 128u + pair * 16u +
                                                    ((uint32_t)mj & 1u) * 8u);
-        if constexpr (std::is_same<DT, F16>::value)
-          acc[g][nb] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(h4v_t, av),
-                                                             __builtin_bit_cast(h4v_t, b), acc[g][nb], 0, 0, 0);
-        else
-          acc[g][nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4_t, av),
-                                                                 __builtin_bit_cast(s4_t, b), acc[g][nb], 0, 0, 0);
+#pragma unroll
+        for (int t = 0; t < TB; ++t) {
+          if constexpr (std::is_same<DT, F16>::value)
+            acc[g][t][nb] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(h4v_t, av[t]),
+                                                                  __builtin_bit_cast(h4v_t, b), acc[g][t][nb], 0, 0, 0);
+          else
+            acc[g][t][nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s4_t, av[t]),
+                                                                      __builtin_bit_cast(s4_t, b), acc[g][t][nb], 0, 0, 0);
+        }
       }
     }
   };
@@ -229,15 +260,16 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
     if (step + 2 < n_steps) do_step(std::integral_constant<int, 2>{}, step + 2);
     if (step + 3 < n_steps) do_step(std::integral_constant<int, 3>{}, step + 3);
   }
-  // ---- sum the 16 waves' partial D and store, one row group at a time (tile area as scratch)
+  // ---- sum the 16 waves' partial D and store, one row group and token block at a time (tile area as scratch)
   float* const scr = (float*)(gsmem + kGImage);  // [nb][reg][wave][lane]
 #pragma unroll
-  for (int g = 0; g < NRG; ++g) {
+  for (int gt = 0; gt < NRG * TB; ++gt) {
+    const int g = gt / TB, t = gt % TB;
     __syncthreads();
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) scr[((nb * 4 + r) * kGWaves + wave) * 64 + lane] = acc[g][nb][r];
+      for (int r = 0; r < 4; ++r) scr[((nb * 4 + r) * kGWaves + wave) * 64 + lane] = acc[g][t][nb][r];
     __syncthreads();
     if (tid < 512) {
       // D element (token = (l >> 4) * 4 + r, output = l & 15) of block nb
@@ -245,7 +277,7 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
       float sum = 0.f;
 #pragma unroll
       for (int w = 0; w < kGWaves; ++w) sum += scr[((nb * 4 + r) * kGWaves + w) * 64 + l];
-      const int token = (l >> 4) * 4 + r;
+      const int token = t * 16 + (l >> 4) * 4 + r;
       const int o = (rg0 + g * grid) * (kGRows * 8) + nb * 16 + (l & 15);
       if (token < tokens && o < O) {
         if (P.bias) sum += DT::to_float(as_global(P.bias)[o]);
@@ -257,15 +289,14 @@ static __device__ __forceinline__ void gemm_k256_pass(const GemmK256Params& P, u
   __syncthreads();
 }
 
-template <typename DT, bool PERM>
-__global__ __launch_bounds__(kGThreads) void gemm_k256_kernel(const GemmK256Params P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char gsmem[];
+// ---- codebook image (see gemv_k256m.hip): row e = 8 main replicas | 8 residual replicas
+static __device__ __forceinline__ void gemm_k256_image(const GemmK256Params& P) {
   {
     typedef __attribute__((address_space(3))) unsigned char lds_u8_t;
+    extern __shared__ __attribute__((aligned(16))) unsigned char gsmem[];
     if ((uint32_t)(uintptr_t)(lds_u8_t*)gsmem != 0u) __builtin_trap();  // absolute LDS addressing
   }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // ---- codebook image (see gemv_k256m.hip): row e = 8 main replicas | 8 residual replicas
   {
     const char* const tab = __builtin_amdgcn_readfirstlane(wave) < 8 ? (const char*)P.cent : (const char*)P.rcent;
     const u32x4 centry = *(const u32x4*)as_global(tab + (uint32_t)((tid >> 1) & 255) * 16u);
@@ -275,6 +306,12 @@ __global__ __launch_bounds__(kGThreads) void gemm_k256_kernel(const GemmK256Para
     for (int q = 0; q < 4; ++q) lds_store16(rowp + (((q + (lane >> 1)) & 3) << 4), centry);
   }
   __syncthreads();  // image complete
+}
+
+template <typename DT, bool PERM>
+__global__ __launch_bounds__(kGThreads) void gemm_k256_kernel(const GemmK256Params P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gsmem[];
+  gemm_k256_image(P);
   // this workgroup's row groups bid, bid + grid, ...: passes of 4, 2, 1 (the x operands of a
   // column block are loaded once per pass and reused for every row group of the pass)
   const int grid = (int)gridDim.x;
@@ -283,6 +320,21 @@ __global__ __launch_bounds__(kGThreads) void gemm_k256_kernel(const GemmK256Para
   for (; left >= 4; left -= 4, rg += 4 * grid) gemm_k256_pass<DT, PERM, 4>(P, gsmem, rg);
   if (left >= 2) { gemm_k256_pass<DT, PERM, 2>(P, gsmem, rg); left -= 2; rg += 2 * grid; }
   if (left >= 1) gemm_k256_pass<DT, PERM, 1>(P, gsmem, rg);
+}
+
+// 17 - 64 tokens: TB = 2 ... 4 blocks of 16 tokens in one pass over the indices.  The image, the tile, the K-step -> wave mapping and
+// the order of every sum are gemm_k256_kernel's and do not depend on the token count or on a token's block, so a token's output
+// bits are those of the 16-token kernel in any slot of any batch.  One row group per pass, <NRG, TB> = <1, 2>, <1, 3>, <1, 4>: a pass
+// <2, 2> (the x of a column block shared by two row groups) spilled 24 - 50 registers and was measured slower in every cell
+// (profiles/r19/README.md).
+template <typename DT, bool PERM, int TB>
+__global__ __launch_bounds__(kGThreads) void gemm_k256w_kernel(const GemmK256Params P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gsmem[];
+  gemm_k256_image(P);
+  const int grid = (int)gridDim.x;
+  int left = ((int)P.n_groups - (int)blockIdx.x + grid - 1) / grid;
+  int rg = blockIdx.x;
+  for (; left >= 1; --left, rg += grid) gemm_k256_pass<DT, PERM, 1, TB>(P, gsmem, rg);
 }
 
 // ---- host side -------------------------------------------------------------------
@@ -318,10 +370,7 @@ static hipError_t launch_g(const GemmK256Params& P, int grid, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
-                            hipStream_t st) {
-  const GemmK256Decision D = gemm_k256_decide(d);
-  if (D.grid < 1) return hipErrorInvalidValue;
+static GemmK256Params gemm_k256_params(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, int n_groups) {
   GemmK256Params P = {};
   P.idx = (const uint32_t*)d.indices;
   P.cent = (const uint32_t*)d.centroids;
@@ -334,9 +383,59 @@ hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int 
   P.perm = d.perm;
   P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features; P.row_words = d.row_words;
   P.tokens = tokens; P.out_f32 = out_f32 ? 1 : 0;
-  P.n_groups = D.n_groups;
+  P.n_groups = n_groups;
+  return P;
+}
+
+hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
+                            hipStream_t st) {
+  const GemmK256Decision D = gemm_k256_decide(d);
+  if (D.grid < 1) return hipErrorInvalidValue;
+  const GemmK256Params P = gemm_k256_params(d, x, y, tokens, out_f32, D.n_groups);
   if (D.f16) return D.perm ? launch_g<F16, true>(P, D.grid, st) : launch_g<F16, false>(P, D.grid, st);
   return D.perm ? launch_g<BF16, true>(P, D.grid, st) : launch_g<BF16, false>(P, D.grid, st);
+}
+
+// ---- 17 - 64 tokens (gemm_k256w_kernel)
+bool gemm_k256w_eligible(const VptqLayerDesc& d, int tokens) {
+  return gemm_k256_eligible(d, 16, 0) && tokens >= 17 && tokens <= 64;
+}
+
+// tb token blocks; the row groups and the grid are gemm_k256_decide's; rgs: the row groups (= passes <1, tb>) of the busiest workgroup
+GemmK256WDecision gemm_k256w_decide(const VptqLayerDesc& d, int tokens) {
+  const GemmK256Decision B = gemm_k256_decide(d);
+  GemmK256WDecision D = {};
+  D.f16 = B.f16; D.perm = B.perm; D.n_groups = B.n_groups; D.grid = B.grid;
+  D.tok = tokens;
+  D.tb = (tokens + 15) / 16;
+  if (D.grid < 1) return D;
+  D.rgs = (D.n_groups + D.grid - 1) / D.grid;   // (gemm_k256w_kernel, blockIdx.x = 0)
+  return D;
+}
+
+template <typename DT, bool PERM, int TB>
+static hipError_t launch_gw(const GemmK256Params& P, int grid, hipStream_t st) {
+  if (const hipError_t e = allow_dynamic_lds<gemm_k256w_kernel<DT, PERM, TB>>(kGLds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((gemm_k256w_kernel<DT, PERM, TB>), dim3(grid), dim3(kGThreads), kGLds, st, P);
+  return hipGetLastError();
+}
+
+template <typename DT, bool PERM>
+static hipError_t launch_gw_tb(const GemmK256Params& P, int tb, int grid, hipStream_t st) {
+  switch (tb) {
+    case 2: return launch_gw<DT, PERM, 2>(P, grid, st);
+    case 3: return launch_gw<DT, PERM, 3>(P, grid, st);
+    case 4: return launch_gw<DT, PERM, 4>(P, grid, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_gemm_k256w(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st) {
+  const GemmK256WDecision D = gemm_k256w_decide(d, tokens);
+  if (D.grid < 1 || D.tb < 2 || D.tb > 4) return hipErrorInvalidValue;
+  const GemmK256Params P = gemm_k256_params(d, x, y, tokens, out_f32, D.n_groups);
+  if (D.f16) return D.perm ? launch_gw_tb<F16, true>(P, D.tb, D.grid, st) : launch_gw_tb<F16, false>(P, D.tb, D.grid, st);
+  return D.perm ? launch_gw_tb<BF16, true>(P, D.tb, D.grid, st) : launch_gw_tb<BF16, false>(P, D.tb, D.grid, st);
 }
 
 }  // namespace vptq

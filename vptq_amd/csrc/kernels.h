@@ -189,6 +189,14 @@ struct GemmK256Decision { bool f16, perm; int n_groups, grid, passes; };
 GemmK256Decision gemm_k256_decide(const VptqLayerDesc& d);
 hipError_t launch_gemm_k256(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32,
                             hipStream_t st);
+// the same file: gemm_k256_eligible's layers, 17 - 64 tokens in one launch as tb = 2 ... 4 blocks of 16 tokens of gemm_k256's pass
+// (reference roundings; gemm_k256's K-step -> wave mapping and order of sums: a token's bits are the 16-token kernel's)
+bool gemm_k256w_eligible(const VptqLayerDesc& d, int tokens);
+// what launch_gemm_k256w launches: gemm_k256w_kernel<DT, PERM, TB>, whose passes are gemm_k256_pass<DT, PERM, 1, TB>; rgs: the row
+// groups the busiest workgroup walks
+struct GemmK256WDecision { bool f16, perm; int tok, tb, n_groups, grid, rgs; };
+GemmK256WDecision gemm_k256w_decide(const VptqLayerDesc& d, int tokens);
+hipError_t launch_gemm_k256w(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
 
 // gemm_gather.hip - gemv_gather's layers (v = 8, k = 65536, residual 0 / 256 / 65536), up to 16 tokens in one launch (tokens = MFMA M;
 // centroid rows gathered from L2, the rebuilt tile in LDS in operand order; reference roundings; no workspace).  The kernels'

@@ -168,6 +168,36 @@ def gemm_gatherx_route(vector_len: int, num_centroids: int, num_res_centroids: i
         _batched_decode_route(_GEMM_GATHERX_MODE, _GEMM_GATHERX_CELLS, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
 
 
+# WHICH (shape, token count) of the canonical format (v = 8, 256 + 256 centroids) take `vptq_quant_gemm_k256w` - 17 - 64 tokens in ONE
+# launch (gemm_k256w_kernel, gemm_k256.hip) - in place of the route they had (17 - 48 tokens: launches of 16 of gemm_k256_kernel; 49 -
+# 64: the dense route): the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.  Only layers whose arithmetic is the
+# reference's roundings (`LayerCache.arithmetic_flags` has GEMV_EXACT) are asked: the kernel has no other.  A cell is (least index
+# elements = vector-rows x columns, least tokens, most tokens), routed by the rule above (beats its parent by more than the larger of
+# 5 % and three times the larger spread, in every measured cell of the region, in both dtypes; the routed token counts of a layer
+# are one interval); tools/gemm_k256w_bench.py writes the table.  VPTQ_GEMM_K256W=1 / 0 (with VPTQ_TUNING=1): every supported layer
+# from 17 to 64 tokens / none.
+#
+# profiles/r19/table.md, profiles/r19/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 17 / 24 / 32 / 33 / 48 /
+# 49 / 64): at 17 - 48 tokens the kernel beats the launches of 16 in every measured cell (0.47 - 0.79 of their time), so 17 - 48 tokens
+# are routed from the smallest measured layer (4096 x 4096 = 2 M index elements) up.  At 49 - 64 tokens (four token blocks, 23 - 41
+# registers spilled) it beats the dense route at 8192 x 8192 and 8192 x 28672 in fp16 (0.68 - 0.83) but not by the rule in bf16 at 64
+# tokens (0.94 - 0.96), and loses on the 14336-wide layers (0.95 - 1.40): no region wins in every cell, so 49 - 64 keep the dense route.
+_GEMM_K256W_CELLS = ((2 << 20, 17, 48),)
+GEMM_K256W_MIN_TOKENS, GEMM_K256W_MAX_TOKENS = 17, 64
+_GEMM_K256W_MODE = (B.tune_env("VPTQ_GEMM_K256W", "auto") or "auto").strip().lower()
+
+
+def gemm_k256w_route(out_features: int, in_features: int, tokens: int) -> bool:
+    """does a canonical-format layer of this shape take `vptq_quant_gemm_k256w` for `tokens` tokens?  Pure: no device, no library
+    (whether the library serves the layer is `vptq_quant_gemm_k256w_supported`'s answer, the arithmetic the caller's)."""
+    if _GEMM_K256W_MODE in ("0", "off") or not GEMM_K256W_MIN_TOKENS <= tokens <= GEMM_K256W_MAX_TOKENS:
+        return False
+    if _GEMM_K256W_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + 7) // 8) * in_features
+    return any(n_el >= min_el and min_tok <= tokens <= max_tok for min_el, min_tok, max_tok in _GEMM_K256W_CELLS)
+
+
 def _dense_from_layout(layer) -> bool:
     """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (a library without the entry, added within ABI 11:
     never - the repack route stays)"""
@@ -554,6 +584,10 @@ class VQuantLinear(nn.Module):
             y = self._batched_decode_cached(x, tokens)   # (the large-codebook formats' batched decode, where the layer's route function says so)
             if y is not None:
                 return y
+        if GEMM_K256W_MIN_TOKENS <= tokens <= GEMM_K256W_MAX_TOKENS and x.is_cuda and self.__dict__.get("_k256w", True):
+            y = self._gemm_k256w_cached(x, tokens)   # (the canonical format in the reference's roundings, where `gemm_k256w_route` says so)
+            if y is not None:
+                return y
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
                 (tokens <= B.GEMV_ANY_FORMAT_TOKENS or tokens <= self._descriptor().max_tokens):
             return self._gemv_cached(x, tokens)
@@ -667,7 +701,7 @@ class VQuantLinear(nn.Module):
 
     # derived, device-bound state (ctypes descriptors, the sliced layout, sibling links) is rebuilt on demand: it is
     # neither pickled nor deep-copied with the module (torch.save(model), copy.deepcopy(model))
-    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_ok")
+    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_ok", "_k256w_ok")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -1038,12 +1072,29 @@ class VQuantLinear(nn.Module):
         if not route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
                 (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
             return None
+        return self._batched_entry_launch(entry, "_bd_ok", GEMM_GATHER_MAX_TOKENS, x, tokens)
+
+    def _gemm_k256w_cached(self, x: torch.Tensor, tokens: int):
+        """17 - 64 tokens of a canonical-format layer in ONE launch of `vptq_quant_gemm_k256w` where `gemm_k256w_route` gives the
+        layer's (shape, tokens) to it, the layer's arithmetic is the reference's roundings, no FORCE_* flag is set and the library
+        serves the layer; None: the routes of before (launches of 16 tokens, the dense route)."""
+        if "_k256w" not in self.__dict__:   # (static module configuration: decided once)
+            self.__dict__["_k256w"] = (self.vector_len, self.num_centroids, _res_centroids(self)) == (8, 256, 256) and \
+                self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm
+        if not self.__dict__["_k256w"] or not gemm_k256w_route(self.out_features, self.in_features, tokens) or \
+                (ops.quant_gemm_flags() & B.GEMV_FORCE_ANY) or not (self._descriptor().arithmetic_flags & B.GEMV_EXACT):
+            return None
+        return self._batched_entry_launch("vptq_quant_gemm_k256w", "_k256w_ok", GEMM_K256W_MAX_TOKENS, x, tokens)
+
+    def _batched_entry_launch(self, entry: str, ok_key: str, ask_tokens: int, x: torch.Tensor, tokens: int):
+        """one launch of a batched-decode entry; `_supported`'s answer cached per descriptor generation under `ok_key`.  None: the
+        library does not serve the layer, or x is not what the entry takes (the other routes raise the shape / dtype / device errors)"""
         cache = self._descriptor()
         desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
-        ok = self.__dict__.get("_bd_ok")
+        ok = self.__dict__.get(ok_key)
         if ok is None or ok[0] != cache.generation:
-            ok = (cache.generation, bool(getattr(B.lib(), entry + "_supported")(desc, GEMM_GATHER_MAX_TOKENS)))
-            self.__dict__["_bd_ok"] = ok
+            ok = (cache.generation, bool(getattr(B.lib(), entry + "_supported")(desc, ask_tokens)))
+            self.__dict__[ok_key] = ok
         if not ok[1] or x.shape[-1] != self.in_features or x.dtype != wdtype or x.device != dev:
             return None   # (the other routes raise the shape / dtype / device errors)
         if not x.is_contiguous():

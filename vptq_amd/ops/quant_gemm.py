@@ -5,7 +5,7 @@ hand-written HIP kernels through the C ABI in include/vptq_hip.h.
 Differences from the reference, on purpose:
 * no torch fallback — a missing library or a CPU tensor raises;
 * the fused GEMV serves 1..8 tokens, the canonical 256+256 format 1..16 (`vptq_quant_gemv_max_tokens`;
-  the reference: < 3, quant_gemm.py:213)
+  the reference: < 3, quant_gemm.py:213) and, in the reference's roundings, 17..48 in one launch (`quant_gemm_k256w`)
   because one workgroup reuses each rebuilt weight for every token, the
   kernel stays HBM-bound; above that, dequant + `F.linear` (hipBLASLt);
 * `argsort(perm)` is cached instead of recomputed per call (quant_gemm.py:208-211).
@@ -20,7 +20,7 @@ from torch.nn import functional as F
 
 from vptq_amd import _backend as B
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gatherx", "quant_gemv_v2"]
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gatherx", "quant_gemm_k256w", "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
 # says (`_backend.set_arithmetic`: "reference" is the default since round 5, "folded" the opt-in fast form)
@@ -210,6 +210,14 @@ def quant_gemm(
                     route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
                     getattr(B.lib(), entry + "_supported")(gdesc, tokens):
                 return _quant_gemm_batched(entry, x, gdesc, out_features)
+        # the canonical format's 17 - 64 tokens in one launch, in the reference's roundings only (gemm_k256w_kernel)
+        from vptq_amd.layers.vqlinear import gemm_k256w_route
+        if (vector_len, num_centroids, kr) == (8, 256, 256) and gemm_k256w_route(out_features, in_features, tokens) and \
+                not (_FLAGS & B.GEMV_FORCE_ANY) and x.data_ptr() % 16 == 0 and \
+                B.lib().vptq_quant_gemm_k256w_supported(gdesc, tokens) and \
+                ((_FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
+                                       gdesc, in_features, out_features)) & B.GEMV_EXACT):
+            return _quant_gemm_batched("vptq_quant_gemm_k256w", x, gdesc, out_features)
     if desc is not None:
         y = torch.empty(x.shape[:-1] + (out_features,), dtype=x.dtype, device=dev)
         flags = _FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
@@ -272,7 +280,8 @@ def quant_gemm_fused(x: torch.Tensor, desc, out_features: int) -> torch.Tensor:
 
 
 def _quant_gemm_batched(entry: str, x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
-    """1 - 16 tokens in ONE launch of a batched-decode entry of the large-codebook formats (`quant_gemm_gather` / `quant_gemm_gatherx`)"""
+    """the tokens of ONE launch of a batched-decode entry: 1 - 16 of the large-codebook formats (`quant_gemm_gather` / `quant_gemm_gatherx`),
+    17 - 64 of the canonical format (`quant_gemm_k256w`)"""
     tokens = x.numel() // x.shape[-1]
     dev = x.device
     if not x.is_contiguous():
@@ -298,6 +307,14 @@ def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool =
     index path for any total width and 32-byte entries; the reference's roundings).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gatherx_supported` accepts; out_f32: the un-rounded fp32 sums."""
     return _quant_gemm_batched("vptq_quant_gemm_gatherx", x, desc, out_features, out_f32)
+
+
+def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 17 - 64 tokens of a canonical-format layer (v = 8, 256 + 256 centroids, scale and bias) in ONE launch
+    (`vptq_quant_gemm_k256w`, gemm_k256.hip: 2 - 4 blocks of 16 tokens share one pass over the indices; the reference's roundings, a
+    token's bits those of the 16-token kernel; replaces 2 - 3 launches of 16 tokens, and dequant + F.linear from 49).  `desc` = a
+    LayerDesc of a layer `vptq_quant_gemm_k256w_supported` accepts; out_f32: the un-rounded fp32 sums."""
+    return _quant_gemm_batched("vptq_quant_gemm_k256w", x, desc, out_features, out_f32)
 
 
 def quant_gemv_v2(
