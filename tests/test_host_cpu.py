@@ -1241,3 +1241,32 @@ def test_csrc_states_its_shared_idioms_once():
     assert len(holders("multiProcessorCount")) == 1, holders("multiProcessorCount")
     assert holders("getenv") == ["tune_env.h"]
     assert holders("__builtin_amdgcn_mfma_f32_16x16x32_f16") == ["common.h"]
+
+
+# every compile-time switch of vptq_amd/csrc: a settled A/B experiment leaves a constant and two comment lines behind, not a switch
+# (tools/README.md, "Compile-time knobs"); a new one is added here AND documented there, or this fails
+_CSRC_KNOBS = {
+    # instruments: what a tool or a bring-up build measures
+    "VPTQ_K256C_PROF", "VPTQ_K256_TRACE", "VPTQ_SLICED_TRACE", "VPTQ_K256C_SPIN_LIMIT", "VPTQ_FUSED_DBG",
+    "VPTQ_K256C_ABLATE", "VPTQ_K256M_ABLATE", "VPTQ_SLICED_ABLATE", "VPTQ_ST_ABLATE", "VPTQ_K256BT_ABLATE",
+    # the chain kernel's geometry
+    "VPTQ_K256C_WAVES", "VPTQ_K256C_SPLIT", "VPTQ_K256C_SUB", "VPTQ_K256C_AHEAD", "VPTQ_K256C_DEPTH", "VPTQ_K256C_MIN_STEPS",
+    # units compiled in parts
+    "VPTQ_K256M_PART", "VPTQ_SL_PART", "VPTQ_ST_PART",
+    # two A/Bs that stay: no result on record; a settled one whose removal changes its kernel's register allocation
+    "VPTQ_K256M_SB_ALL", "VPTQ_LDS_MFMA_DEPTH",
+}
+
+
+def test_csrc_compile_time_knobs_are_listed_and_documented():
+    csrc = os.path.join(ROOT, "vptq_amd", "csrc")
+    found = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            for line in open(os.path.join(csrc, f)):
+                if re.match(r"\s*#\s*(ifndef|ifdef|if|elif)\b", line):   # (#ifndef X, #if X, #if !defined(X) || X == 3: every spelling)
+                    found |= set(re.findall(r"\bVPTQ_\w+", line))
+    assert found == _CSRC_KNOBS, (sorted(found - _CSRC_KNOBS), sorted(_CSRC_KNOBS - found))
+    readme = open(os.path.join(ROOT, "tools", "README.md")).read()
+    missing = sorted(k for k in _CSRC_KNOBS if not re.search(r"\b%s\b" % k, readme))
+    assert not missing, missing

@@ -1,6 +1,6 @@
 """CPU only: where the default (folded) arithmetic's distance to the reference comes from.  numpy emulation of
   folded:      y = sum (c + r) * r16(s x) + sum b x          (what the GPU kernels compute, fp32 sums)
-  pre-added:   y = sum r16(c + r) * r16(s x) + sum b x       (the reference's first rounding kept; -DVPTQ_K256C_PREADD)
+  pre-added:   y = sum r16(c + r) * r16(s x) + sum b x       (the reference's first rounding kept; a retired kernel variant: tools/README.md, VPTQ_K256C_PREADD)
 against the oracle (reference: r16(r16(r16(c + r) s) + b), then x W^T), max-normalised as in the parity tests.
   python tools/fold_error_study.py"""
 import os, sys, numpy as np

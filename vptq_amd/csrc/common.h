@@ -308,6 +308,17 @@ static __device__ __forceinline__ void lds_store16(uint32_t byte_addr, u32x4 v) 
   *(lds_u32x4_t*)(uintptr_t)byte_addr = v;  // ds_write_b128
 }
 
+// LDS-DMA (global_load_lds_dwordx4): every lane brings the 16 bytes at its global address `gaddr` straight to LDS byte
+// lds_base + 16 * lane - 1 KiB per wave and instruction, no registers, no ds_write.  lds_base is wave-uniform (an SGPR:
+// readfirstlane it) and goes through M0, which belongs to the compiler: saved and restored inside the statement.  Inline
+// assembly because a DMA the compiler can see makes it wait for every load in flight; the caller waits with
+// s_waitcnt vmcnt before the barrier that publishes the bytes.
+static __device__ __forceinline__ void lds_dma16(uint32_t lds_base, uint64_t gaddr) {
+  uint32_t keep_m0;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep_m0) : "v"(gaddr), "s"(lds_base) : "memory");
+}
+
 // ds_read_b64_tr_b16: the transposing LDS load that feeds the 16x16x32 MFMA's operands
 static __device__ __forceinline__ u32x2 lds_tr8(uint32_t byte_addr) {
   typedef __attribute__((address_space(3))) s4_t lds_s4_t;

@@ -47,11 +47,7 @@ constexpr int kBTTokens = 16;                          // token slots = rows of 
 // sweeps in flight per wave.  2: a row group of 8192 columns is 4 sweeps = two rounds of the unrolled loop exactly;
 // with 3 the loop ran 6 steps for 4 sweeps and requested 15 loads ahead: 19.9 against 15.6 us per 8192^2 layer at 16
 // tokens, same box (profiles/r03/tokens_k256t_depth_ab.txt); 4 spills registers (25.6 us)
-#ifndef VPTQ_K256BT_DEPTH
-#define VPTQ_K256BT_DEPTH 2
-#endif
-constexpr int kBTDepth = VPTQ_K256BT_DEPTH;
-static_assert(kBTDepth >= 2 && kBTDepth <= 4, "queue depth");
+constexpr int kBTDepth = 2;
 constexpr uint32_t kBTImgBytes = 65536;                // 256 rows x 16 units x 16 B
 constexpr uint32_t kBTRedOff = kBTImgBytes;            // [2][wave][token][32 outputs] floats
 constexpr uint32_t kBTRedBuf = kBTWaves * kBTTokens * 32 * 4;
@@ -193,9 +189,7 @@ __global__ __launch_bounds__(kBTThreads) void gemm_k256t_kernel(const GemmK256TP
     for (int i = 0; i < 4; ++i) {
       const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dst + (uint32_t)i * 1024u));
       const uint64_t v = va + (uint64_t)(i * 64);
-      uint32_t keep_m0;   // (M0 belongs to the compiler: saved and restored inside the statement)
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+      lds_dma16(d, v);
     }
   }
 

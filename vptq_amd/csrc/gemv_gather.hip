@@ -45,16 +45,8 @@ template <bool W> struct Fmt<16, W> { static constexpr int NW = 4, E = 8; };
 template <bool W> struct Fmt<24, W> { static constexpr int E = W ? 8 : 4, NW = E * 3 / 4; };
 template <bool W> struct Fmt<32, W> { static constexpr int NW = 4, E = 4; };
 
-// A/B knob (tools/gpu_r2_gather.sh): 1 = centroid gathers bypass the vector L1 (nt), 2 = the index
-// words too.  Measured: 79 / 63 us per 8192^2 layer against 39.6 us with plain loads - the 9.5 % of
-// gathers that hit in L1 and the L1's request merging matter; off.
-#ifndef VPTQ_GATHER_NT
-#define VPTQ_GATHER_NT 0
-#endif
-
-#ifndef VPTQ_GATHER_RES_LDS
-#define VPTQ_GATHER_RES_LDS 1
-#endif
+// (centroid gathers that bypass the vector L1 (nt) / the index words too: 79 / 63 us per 8192^2 layer against 39.6 us with
+// plain loads - the 9.5 % of gathers that hit in L1 and the L1's request merging matter; profiles/r02/gather_nt_ab.txt)
 
 template <typename DT, int T, int ROWS, int TOK, bool PERM, bool WIDE = false>
 __global__ __launch_bounds__(kGThreads) void gemv_gather_kernel(const GatherParams P) {
@@ -75,8 +67,9 @@ __global__ __launch_bounds__(kGThreads) void gemv_gather_kernel(const GatherPara
 
   // T = 24 ("v8-k65536-256"): the 256-entry residual table (4 KiB) is copied into LDS once per
   // workgroup and gathered from there.  These kernels are bound by lane ADDRESSES per clock in the
-  // vector-memory pipe (one per CU and cycle): the residual gathers were a third of them.
-  constexpr bool kResLds = T == 24 && VPTQ_GATHER_RES_LDS;
+  // vector-memory pipe (one per CU and cycle): the residual gathers were a third of them (with wide pieces: 49.0 -> 42.3 us
+  // per 8192^2 layer, profiles/r02/formats_8192_gatherx.txt).
+  constexpr bool kResLds = T == 24;
   __shared__ u32x4 rtab[kResLds ? 256 : 1];
   if constexpr (kResLds) {
     rtab[tid] = *(const u32x4*)(P.rcent + (size_t)tid * 16);   // kGThreads == 256 entries
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(kGThreads) void gemv_gather_kernel(const GatherPara
       const int row = row0 + r < N ? row0 + r : N - 1;
       const uint32_t* src = P.idx + (size_t)row * P.row_words + (size_t)col0 * T / 32;
 #pragma unroll
-      for (int q = 0; q < NW; ++q) w[r][q] = VPTQ_GATHER_NT == 2 ? __builtin_nontemporal_load(src + q) : src[q];
+      for (int q = 0; q < NW; ++q) w[r][q] = src[q];
     }
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
@@ -128,10 +121,9 @@ __global__ __launch_bounds__(kGThreads) void gemv_gather_kernel(const GatherPara
 #pragma unroll
       for (int e = 0; e < E; ++e) {
         const uint32_t v = packed_elem<T>(w[r], e);
-        if (VPTQ_GATHER_NT) cv[e] = __builtin_nontemporal_load((const u32x4*)(P.cent + (size_t)(v & 0xffffu) * 16));
-        else cv[e] = *(const u32x4*)(P.cent + (size_t)(v & 0xffffu) * 16);
+        cv[e] = *(const u32x4*)(P.cent + (size_t)(v & 0xffffu) * 16);
         if constexpr (kResLds) rv[e] = rtab[(v >> 16) & 0xffu];
-        else if (RES) rv[e] = *(const u32x4*)(P.rcent + (size_t)(T == 24 ? (v >> 16) & 0xffu : v >> 16) * 16);
+        else if (RES) rv[e] = *(const u32x4*)(P.rcent + (size_t)(v >> 16) * 16);
       }
 #pragma unroll
       for (int e = 0; e < E; ++e) {

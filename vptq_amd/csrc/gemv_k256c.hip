@@ -134,23 +134,11 @@ constexpr int kCFlagStride = 256;   // DEP: arrival flags per layer (one per wor
 #ifndef VPTQ_K256C_SPIN_LIMIT
 #define VPTQ_K256C_SPIN_LIMIT 0
 #endif
-#ifndef VPTQ_K256C_BALANCE
-#define VPTQ_K256C_BALANCE 1
-#endif
-// 1: everything outside the consume phase runs at issue priority 3: those instructions compete with the
-// other waves' MFMAs for the issue port and hold nothing another wave needs (measured: 4.91 -> 4.67 us)
-#ifndef VPTQ_K256C_LDS_FENCE
-#define VPTQ_K256C_LDS_FENCE 1
-#endif
-#ifndef VPTQ_K256C_PREADD
-#define VPTQ_K256C_PREADD 0
-#endif
-#ifndef VPTQ_K256C_STAGGER
-#define VPTQ_K256C_STAGGER 0
-#endif
-#ifndef VPTQ_K256C_PRIO
-#define VPTQ_K256C_PRIO 1
-#endif
+// Issue priorities: everything outside the consume phase runs at priority 3 - those instructions compete with the
+// other waves' MFMAs for the issue port and hold nothing another wave needs (measured: 4.91 -> 4.67 us) - and the
+// consume phase at 0 / 1 / 2 by arrival order at the previous row group (finish()).
+// (s_setprio 0-3 by arrival order for the whole wave: chain32 4.83 -> 4.90 us; no balancing: 5.00 us;
+// profiles/r03/chain_bench_variants.txt "prio0" / "nobal")
 
 // One layer of the launch: 88 bytes of kernel arguments (the K256Layer of the other kernels carries
 // fields this one has no use for, and 32 of those + the search table would not fit 4 KiB).
@@ -510,23 +498,16 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
     for (int i = 0; i < (int)(kRowsW / 4u); ++i) {
       const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dst + (uint32_t)i * 1024u));
       const uint64_t v = va + (uint64_t)(i * 64);
-      uint32_t keep_m0;   // (M0 belongs to the compiler: saved and restored inside the statement)
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+      lds_dma16(d, v);
     }
   };
   // Hand-over between the waves goes through LDS only, and a wave's LDS operations execute in
   // order: fences restricted to the local address space.  An ordinary workgroup-scope release also
   // waits for every global load in flight (s_waitcnt vmcnt(0)) - here the whole queue of index
   // words requested ahead.
-  // (VPTQ_K256C_LDS_FENCE=0: the release is a compiler barrier only.  The fence makes the wave wait for its LDS
-  // writes to complete - one LDS round trip behind 16 waves' gathers - before it issues the counter update; the LDS
-  // executes one wave's operations in the order they were issued, so the update cannot overtake the writes.)
-#if VPTQ_K256C_LDS_FENCE
+  // (the release as a compiler barrier only - the LDS executes one wave's operations in the order they were issued,
+  // so the counter update cannot overtake the writes - saved nothing: profiles/r03/chain_rowsplit_ldsfence_ab.txt)
   auto lds_release = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); };
-#else
-  auto lds_release = [&]() { asm volatile("" ::: "memory"); };
-#endif
   auto lds_acquire = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); };
   auto lds_inc = [&](uint32_t* p) __attribute__((always_inline)) {
     lds_release();
@@ -655,7 +636,7 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
   bool fin_pending = false;    // this wave still has to sum and store row group fin_rg (slot fin_slot)
   int fin_rg = 0;
   uint32_t fin_slot = 0, fin_q = 0;
-  int bal = 1;                 // VPTQ_K256C_PRIO: issue priority of this wave's consume phase
+  int bal = 1;                 // issue priority of this wave's consume phase
   uint32_t arrived_v = 0;      // lane 0: this wave's arrival number at its last row group (in flight until looked at)
   auto finalize = [&]() __attribute__((always_inline)) {
     const uint32_t slot = fin_slot;
@@ -775,19 +756,10 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
       const float sb = wave_sum(accb);
       if (lane == 0) red_b[slot * kCWaves + wave] = sb;
     }
-#if VPTQ_K256C_BALANCE
     // issue priority for the next row group by arrival order at the PREVIOUS one (its number has
     // come back by now): the early ones yield
     const uint32_t before = (uint32_t)__builtin_amdgcn_readfirstlane((int)arrived_v);
-#if VPTQ_K256C_PRIO
     bal = before * (16u / (uint32_t)kCWaves) < 5u ? 0 : before * (16u / (uint32_t)kCWaves) < 11u ? 1 : 2;
-#else
-    if (before < 4u) __builtin_amdgcn_s_setprio(0);
-    else if (before < 8u) __builtin_amdgcn_s_setprio(1);
-    else if (before < 12u) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
-#endif
-#endif
     lds_release();
     if (lane == 0)
       arrived_v = __hip_atomic_fetch_add(&slot_cnt[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -925,14 +897,9 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
         }
       } else if constexpr ((VPTQ_K256C_ABLATE & 1) != 0) {
         asm volatile("" :: "v"(c), "v"(r), "v"(xo));
-      } else if constexpr (VPTQ_K256C_PREADD != 0 && std::is_same<DT, F16>::value) {
-        // (experiment) f16(c + r) first - the reference's own first rounding (csrc/kernels/quant_gemv.cuh) - then 2
-        // instead of 4 MFMAs per index: the MFMAs are the larger part of the energy, and the kernel runs at the
-        // package power limit
-        const u32x4 w = u32x4{DT::add2(c[0], r[0]), DT::add2(c[1], r[1]), DT::add2(c[2], r[2]), DT::add2(c[3], r[3])};
-        acc[q][0] = DT::mfma4(xo, u32x2{w[0], w[1]}, acc[q][0]);
-        acc[q][1] = DT::mfma4(xo, u32x2{w[2], w[3]}, acc[q][1]);
       } else {
+        // (f16(c + r) first - the reference's own first rounding - then 2 instead of 4 MFMAs per index: 5.93 against
+        // 5.90-5.94 us per layer at the package power limit, profiles/r03/chain_preadd_ab.txt)
         acc[q][0] = DT::mfma4(xo, u32x2{c[0], c[1]}, acc[q][0]);
         acc[q][1] = DT::mfma4(xo, u32x2{c[2], c[3]}, acc[q][1]);
         acc[q][0] = DT::mfma4(xo, u32x2{r[0], r[1]}, acc[q][0]);
@@ -1081,11 +1048,8 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
 #if VPTQ_K256C_PROF
   pf_t0 = now(0);
 #endif
-#if VPTQ_K256C_STAGGER
-  // (experiment) the four waves of a SIMD (wave & 3 = SIMD) start a fraction of a step apart, so that one wave's
-  // bookkeeping falls into the others' consume phases
-  for (int g = 0; g < (wave >> 2); ++g) __builtin_amdgcn_s_sleep(VPTQ_K256C_STAGGER);
-#endif
+  // (the four waves of a SIMD started a fraction of a step apart, so that one wave's bookkeeping falls into the others'
+  // consume phases: -3 % on a box whose run-to-run spread was +-8 %, not adopted - docs/history/DESIGN_rounds1-4.md)
   // ---- main loop: one step = wait for sweep k, consume it, request sweep k + D into its queue slot
   auto step = [&](auto slot_c) __attribute__((always_inline)) {
     __builtin_amdgcn_sched_barrier(0);
@@ -1101,17 +1065,13 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
     const unsigned long long tb = now(iw[SS][0][0]);
     pf_wait += tb - ta;
 #endif
-#if VPTQ_K256C_PRIO
     if (bal == 0) __builtin_amdgcn_s_setprio(0);
     else if (bal == 1) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(2);
-#endif
     // (after the workgroup's last row group the remaining steps of the loop iteration only keep the loads counted:
     // no gathers, no MFMAs - the kernel runs at the package power limit, energy spent on sums nobody stores is time)
     if (!done) consume(slot_c);
-#if VPTQ_K256C_PRIO
     __builtin_amdgcn_s_setprio(3);
-#endif
     __builtin_amdgcn_sched_barrier(0);
 #if VPTQ_K256C_PROF
     const unsigned long long tc = now(__float_as_uint(acc[0][0][0] + acc[0][1][0]));

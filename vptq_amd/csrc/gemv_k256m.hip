@@ -55,6 +55,7 @@ constexpr int kMSweepCols = kMWaves * 16 * 8;  // 2048: 16 blocks (column chunks
 constexpr int kMTableBytes = 65536;  // 256 rows x (8 main + 8 residual replicas) x 16 B
 constexpr int kMMaxLds = 163840;   // 160 KiB per CU
 constexpr int kMMaxCols = 14336;   // staged activations must fit beside the image
+constexpr int kMXBytes = 2;        // staged bytes per column and token
 constexpr int kMRedSlot = kMWaves * 32 * 4;   // one row group's cross-wave partials, per token
 constexpr int kMMaxSlots = 4;
 // VPTQ_GEMV_SELECTIVE (round 6; one token, fp16, folded instantiations; K256Layer::slots bit 8): the folded form, with the reference's
@@ -72,20 +73,12 @@ constexpr int kMSelMaxHot = 16;            // hot blocks per layer the correctio
                                            // "dominant" blocks is a dense one - the folded form's regime - and the corrections are latency-bound work: the
                                            // 14336-column down projection of a decoder, silu(gate) * up as input, had 50 of 112 blocks hot: 49 us for a 6 us launch)
 constexpr int kMSelBytes = 2 * kMSelMaxBlocks + 4 * kMSelRowGroups * 32 * 4;   // block magnitudes + corr [4 quarters of the hot blocks][row groups][32]
-// VPTQ_K256M_XDUP: one token - the staged activations are kept as DUPLICATED pairs (x, x), one
-// dword per column, so that the MFMA x operand (x * e_j) is two v_and_b32 with per-lane
-// constant masks instead of two v_perm_b32 (a three-source VOP3: ~5.5 vs ~3.3 cycles per
-// wave-instruction, tools/ubench.hip).  Costs 2 more bytes of LDS per column.
-#ifndef VPTQ_K256M_XDUP
-#define VPTQ_K256M_XDUP 0
-#endif
-// VPTQ_K256M_SB_ALL (A/B): every exact instantiation stages scale and bias in LDS (default: bf16, and fp16 from 6 sweeps on)
+// VPTQ_K256M_SB_ALL (A/B, no result on record): every exact instantiation stages scale and bias in LDS (default: bf16, and fp16 from 6 sweeps on)
 #ifndef VPTQ_K256M_SB_ALL
 #define VPTQ_K256M_SB_ALL 0
 #endif
-constexpr int kMXBytes1 = VPTQ_K256M_XDUP ? 4 : 2;  // staged bytes per column, one token
 
-// Timing-only ablations (tools/gpu_ablate.sh; the RESULTS of such a build are wrong): bit 0 no
+// Timing-only ablations (make variant EXTRA=-DVPTQ_K256M_ABLATE=bits, tools/ab_libs.py --no-parity; the RESULTS of such a build are wrong): bit 0 no
 // MFMAs, bit 1 no LDS gathers (the addresses are still computed), bit 2 no epilogue, bit 3 no
 // index loads, bit 4 only the two main-table MFMAs, bit 5 only one MFMA per index, bit 6 no bias
 // load (sum b x), bit 7 no scale load.  What they
@@ -114,16 +107,9 @@ static __device__ __forceinline__ void q_load(u32x4& dst, const void* sbase, uin
 }
 // The packed index words are read exactly once per launch, by one CU: non-temporal, so that
 // they do not push the codebooks / activations / scales every workgroup re-reads out of L2
-// (guide, "nt-weights": -5...10 % per decode layer).
-#ifndef VPTQ_K256M_NT
-#define VPTQ_K256M_NT 1
-#endif
+// (guide, "nt-weights": -5...10 % per decode layer; same-box A/B against plain loads: -2...4 %, profiles/r02/k256m_nt_ab_box3.txt).
 static __device__ __forceinline__ void q_load_stream(u32x4& dst, const void* sbase, uint32_t voff) {
-#if VPTQ_K256M_NT
   dst = __builtin_nontemporal_load((const u32x4*)as_global((const char*)sbase + voff));
-#else
-  q_load(dst, sbase, voff);
-#endif
 }
 
 // The kernel proper; Ly = this workgroup's layer, however its arguments arrived (see the two
@@ -139,25 +125,18 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
   }
   // sweeps in flight per wave.  Bandwidth x latency is ~35 KB per CU; 2 sweeps (32 KiB) cover
   // it; a deeper queue in the steady state changes nothing (3 or 4 sweeps: same launch time,
-  // same grouped time - the loop is bound by instruction issue, not by bytes in flight).
+  // same grouped time - the loop is bound by instruction issue, not by bytes in flight;
+  // profiles/r02/k256m_loop_variants_ab.txt).
   // In the PROLOGUE every index load that is in flight before a wave's activations have arrived
   // delays them, and with them the barrier all 16 waves wait at: requesting the first sweep
-  // right behind the image (DP = 1, the round-1 order had DP = 2) costs 0.2-0.5 us per launch
+  // right behind the image (the round-1 order: both sweeps there) costs 0.2-0.5 us per launch
   // against requesting it once the wave has staged its activations (DS); two sweeps at that
   // point, or none before the barrier, are slower again (same-box A/B of all five orders:
   // profiles/r02/k256m_prologue_order_ab.txt; 8192^2 single launch 7.6-8.8 -> 7.0-7.7 us).
-#ifndef VPTQ_K256M_DEPTH
-#define VPTQ_K256M_DEPTH 2
-#endif
-#ifndef VPTQ_K256M_DEPTH_PROLOGUE
-#define VPTQ_K256M_DEPTH_PROLOGUE 0
-#endif
-#ifndef VPTQ_K256M_DEPTH_STAGED
-#define VPTQ_K256M_DEPTH_STAGED 1
-#endif
-  constexpr int D = NS < VPTQ_K256M_DEPTH ? NS : VPTQ_K256M_DEPTH;  // steady state
-  constexpr int DP = D < VPTQ_K256M_DEPTH_PROLOGUE ? D : VPTQ_K256M_DEPTH_PROLOGUE;  // behind the image
-  constexpr int DS = DP + VPTQ_K256M_DEPTH_STAGED < D ? DP + VPTQ_K256M_DEPTH_STAGED : D;  // + behind the staging
+  constexpr int kDepth = 2;          // sweeps in flight in the steady state
+  constexpr int kDepthStaged = 1;    // ... of them requested once the wave has staged its activations (none behind the image)
+  constexpr int D = NS < kDepth ? NS : kDepth;  // steady state
+  constexpr int DS = kDepthStaged < D ? kDepthStaged : D;  // behind the staging
   // NST = 0: activations are NOT staged in LDS (more than 14336 columns do not fit beside the
   // image): the queue carries scale and x next to the index words, a row group is walked in
   // column blocks of NS sweeps, and the folded form only.
@@ -215,13 +194,11 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
   // LDS map: [0, 64 KiB) codebook image | per token: G staged activations + 8 zeros (the
   // operand of columns past G) + a 16-byte dump slot | cross-wave scratch
   const uint32_t xs_off = kMTableBytes;
-  constexpr bool kXDup = VPTQ_K256M_XDUP && TOK == 1 && STAGE;
-  constexpr uint32_t kXB = kXDup ? 4u : 2u;  // staged bytes per column
-  const uint32_t xs_stride = (uint32_t)G * kXB + 32u;
+  // (staged as duplicated pairs (x, x), 4 bytes per column, the x operand is two v_and_b32 with lane masks instead of two
+  // v_perm_b32: slower, hot 6.3-6.4 -> 7.0-7.1 us per layer, profiles/r02/k256m_variants_ab_box2.txt "ntx")
+  const uint32_t xs_stride = (uint32_t)G * kMXBytes + 32u;
   // bf16 exact form: the one-hot first operand e_j (1.0 at position j)
   const u32x2 bf_id = u32x2{__builtin_amdgcn_perm(0x3f803f80u, 0u, selA[0]), __builtin_amdgcn_perm(0x3f803f80u, 0u, selB[0])};
-  const uint32_t maskA = j == 0 ? 0x0000ffffu : j == 1 ? 0xffff0000u : 0u;
-  const uint32_t maskB = j == 2 ? 0x0000ffffu : j == 3 ? 0xffff0000u : 0u;
   const uint32_t sb_off = xs_off + (uint32_t)TOK * xs_stride;   // (kSB) scale plane, then the bias plane: the activations' layout
   const uint32_t red_off = xs_off + (STAGE ? TOK * xs_stride : 0u) + (kSB ? 2u * xs_stride : 0u);
   float* const red_b = (float*)(smem + red_off);        // [TOK][kMWaves]: sum b * x per wave
@@ -271,7 +248,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
   //    f16(s * x) and sums b * x; the exact form stages x itself.
   // Order (tools/trace_k256m.py): the codebook entry and the activations are requested
   // together (two cold misses overlap), the image is written as soon as the entry is there,
-  // the activations are staged, and only then does the index queue go out (DP / DS above) - a
+  // the activations are staged, and only then does the index queue go out (DS above) - a
   // wave issues in order, and behind a backed-up vector-memory queue the image and the
   // activations, which all 16 waves wait for, arrived 0.5-3 us later.  (An LDS-DMA fill,
   // global_load_lds_dwordx4, was slower still.)
@@ -320,8 +297,6 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
       __builtin_amdgcn_sched_barrier(0);
       write_image();
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s = 0; s < DP; ++s) issue_sweep(s, bid, 0);
       if (kLateB) {
 #pragma unroll
         for (int k = 0; k < NST; ++k) {
@@ -385,17 +360,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
           }
           if constexpr (kSelOk) sel_xp[k] = v;
         }
-        if constexpr (kXDup) {
-          // (x_c, x_c) per column: 32 bytes per thread
-          const uint32_t a = xs_off + (uint32_t)(valid ? want : G + 4) * 4u;
-          lds_store16(a, u32x4{__builtin_amdgcn_perm(v[0], v[0], 0x01000100u), __builtin_amdgcn_perm(v[0], v[0], 0x03020302u),
-                               __builtin_amdgcn_perm(v[1], v[1], 0x01000100u), __builtin_amdgcn_perm(v[1], v[1], 0x03020302u)});
-          if (valid)
-            lds_store16(a + 16u, u32x4{__builtin_amdgcn_perm(v[2], v[2], 0x01000100u), __builtin_amdgcn_perm(v[2], v[2], 0x03020302u),
-                                       __builtin_amdgcn_perm(v[3], v[3], 0x01000100u), __builtin_amdgcn_perm(v[3], v[3], 0x03020302u)});
-        } else {
-          lds_store16(xs_off + t * xs_stride + (uint32_t)(valid ? want : G + 8) * 2u, v);
-        }
+        lds_store16(xs_off + t * xs_stride + (uint32_t)(valid ? want : G + 8) * 2u, v);
       }
       if constexpr (kSB) {
         lds_store16(sb_off + (uint32_t)(valid ? want : G + 8) * 2u, st_s[k]);
@@ -463,7 +428,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
         for (int q = 0; q < 4; ++q) accb[0] = DT::dot2(xv[q], bv[q], accb[0]);
       }
     }
-    if (STAGE && tid < TOK) lds_store16(xs_off + tid * xs_stride + (uint32_t)G * kXB, u32x4{0, 0, 0, 0});
+    if (STAGE && tid < TOK) lds_store16(xs_off + tid * xs_stride + (uint32_t)G * 2u, u32x4{0, 0, 0, 0});
     if (kSB && tid < 2) lds_store16(sb_off + tid * xs_stride + (uint32_t)G * 2u, u32x4{0, 0, 0, 0});   // columns past G: weight 0
     if (tid < 2 * kMMaxSlots) slot_cnt[tid] = 0u;
     if (FAST && !kLateB) {
@@ -488,7 +453,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
   };
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int s = DP; s < DS; ++s) issue_sweep(s, bid, 0);  // this wave's activations are staged
+  for (int s = 0; s < DS; ++s) issue_sweep(s, bid, 0);  // this wave's activations are staged
   __builtin_amdgcn_sched_barrier(0);  // nothing that waits for index words above the barrier
   K256_STAMP(kMWaves, 7, tid);        // (trace build) this wave is at the barrier
   __syncthreads();
@@ -534,8 +499,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
             const int blk = want >> 7;
             const bool hot = (((blk < 64 ? m0 : m1) >> (blk & 63)) & 1ull) != 0ull;
             if (hot) {
-              lds_store16(xs_off + (uint32_t)want * kXB, u32x4{0u, 0u, 0u, 0u});
-              if constexpr (kXDup) lds_store16(xs_off + (uint32_t)want * kXB + 16u, u32x4{0u, 0u, 0u, 0u});
+              lds_store16(xs_off + (uint32_t)want * 2u, u32x4{0u, 0u, 0u, 0u});
               late_x[k] = u32x4{0u, 0u, 0u, 0u};
             }
           }
@@ -623,26 +587,15 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
   // walks several row groups builds them during the first one (2 v_perm_b32 per index) and
   // keeps them in registers (16 per sweep) - afterwards an index costs 2 perms + 4 MFMA.
   // Only while they fit beside the rest (<= 4 sweeps, folded form).
-#ifndef VPTQ_K256M_CACHE_XO
-#define VPTQ_K256M_CACHE_XO 1
-#endif
-  constexpr bool kCacheXo = VPTQ_K256M_CACHE_XO && FAST && STAGE && NS <= 4 && TOK == 1;
+  // (without the cache: grouped 5.53 -> 5.75 us per layer, profiles/r02/k256m_loop_variants_ab.txt "nc2")
+  constexpr bool kCacheXo = FAST && STAGE && NS <= 4 && TOK == 1;
   u32x2 xo_cache[kCacheXo ? NS : 1][8];
   // one token: acc.a[0 / 1][i] = output 0-3 / 4-7 of this lane's vector-row; several tokens:
   // acc.a[e][t] = output e of this lane's vector-row for token t
-  // VPTQ_K256M_ACC4: the four MFMAs of an index go to four accumulators (main / residual x
-  // low / high half), joined in finish(): no MFMA reads the result of the one two places
-  // before it.  VPTQ_K256M_ADDFORM: c + r by four v_pk_add_f16 (the reference's first rounding),
-  // then two MFMAs.
-#ifndef VPTQ_K256M_ACC4
-#define VPTQ_K256M_ACC4 0
-#endif
-#ifndef VPTQ_K256M_ADDFORM
-#define VPTQ_K256M_ADDFORM 0
-#endif
-  constexpr bool kAcc4 = VPTQ_K256M_ACC4 && FAST && TOK == 1 && !VPTQ_K256M_ADDFORM;
+  // (the four MFMAs of an index into four accumulators, joined in finish(): hot 6.4 -> 7.9 us; c + r by four
+  // v_pk_add_f16, then two MFMAs: hot + 0.1-0.2 us - profiles/r02/k256m_variants_ab_box1.txt, _box2.txt)
   // (several tokens, reference roundings: a[2 t] / a[2 t + 1] = outputs 0-3 / 4-7 of token t, the one-token layout per token)
-  constexpr int kNAcc = TOK == 1 ? (kAcc4 ? 4 : 2) : (FAST ? 8 : 2 * TOK);
+  constexpr int kNAcc = TOK == 1 ? 2 : (FAST ? 8 : 2 * TOK);
   struct Acc { f32x4 a[kNAcc]; };
   // Several tokens (TOK = 2 / 4): here the 4x4x4 MFMA is a real contraction.  Lane i of a block
   // supplies token i's f16(s * x) of TWO columns, twice (A row i = {x'[c0], x'[c1], x'[c0],
@@ -705,7 +658,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
     f32x4& acc1 = acc.a[1];
     constexpr bool kBuild = !kCacheXo || decltype(first_c)::value;
     const int want = (cb * NS + s) * kMSweepCols + lane_cols;
-    u32x4 xq = u32x4{0, 0, 0, 0}, xq2 = u32x4{0, 0, 0, 0};
+    u32x4 xq = u32x4{0, 0, 0, 0};
     [[maybe_unused]] u32x4 xqt[TOK > 1 ? TOK - 1 : 1];
     // (reference roundings, several tokens) the weight operands of an index serve every token: one more pair of MFMAs + 2 v_perm_b32 each
     auto more_tokens = [&](int q, int h, u32x2 wa, u32x2 wb) {
@@ -719,13 +672,10 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
       }
     };
     if (STAGE) {
-      if (kBuild) {
-        xq = lds_load16(xs_off + (uint32_t)(want < G ? want : G) * kXB);  // past G: zeros
-        if (kXDup) xq2 = want < G ? lds_load16(xs_off + (uint32_t)want * 4u + 16u) : xq;
-      }
+      if (kBuild) xq = lds_load16(xs_off + (uint32_t)(want < G ? want : G) * 2u);  // past G: zeros
       if constexpr (TOK > 1) {   // (reference roundings) the further tokens' activations of these 8 columns
 #pragma unroll
-        for (int t = 1; t < TOK; ++t) xqt[t - 1] = lds_load16(xs_off + (uint32_t)t * xs_stride + (uint32_t)(want < G ? want : G) * kXB);
+        for (int t = 1; t < TOK; ++t) xqt[t - 1] = lds_load16(xs_off + (uint32_t)t * xs_stride + (uint32_t)(want < G ? want : G) * 2u);
       }
     } else {
       const uint32_t keep = want < G ? 0xffffffffu : 0u;  // columns past G contribute 0
@@ -734,18 +684,10 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
         xq[q] = DT::mul2(b_raw[NQ > 1 ? s : 0][q] & keep, s_raw[NQ > 1 ? s : 0][q]);  // f16(s * x)
     }
     const u32x4 words = iw[s];
-#ifndef VPTQ_K256M_AHEAD
-#define VPTQ_K256M_AHEAD 2
-#endif
     // indices whose gathers are in flight ahead of the MFMAs (the exact form has 12 more
     // registers of scale / bias per sweep in its queue: one less)
-#ifndef VPTQ_K256M_SB_UNFENCED
-#define VPTQ_K256M_SB_UNFENCED 0
-#endif
-#ifndef VPTQ_K256M_AHEAD_SB
-#define VPTQ_K256M_AHEAD_SB 1
-#endif
-    constexpr int kAhead = FAST ? VPTQ_K256M_AHEAD : kSB ? VPTQ_K256M_AHEAD_SB : VPTQ_K256M_AHEAD - 1;
+    // (3 ahead in the folded form: hot 6.4 -> 7.7 us per layer, profiles/r02/k256m_variants_ab_box1.txt "ahead3")
+    constexpr int kAhead = FAST ? 2 : 1;
     u32x4 cv[kAhead + 1], rv[kAhead + 1];
     auto gather = [&](int u) {
       const uint32_t w = words[u >> 1];
@@ -766,44 +708,29 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       // fenced: left alone, the scheduler sinks the gathers next to their use and the loop
-      // runs with one gather in flight (s_waitcnt lgkmcnt(1)), i.e. at LDS latency
-#ifndef VPTQ_K256M_FENCE_UNITS
-#define VPTQ_K256M_FENCE_UNITS 1
-#endif
-      if (VPTQ_K256M_FENCE_UNITS && !(kSB && VPTQ_K256M_SB_UNFENCED)) __builtin_amdgcn_sched_barrier(0);
+      // runs with one gather in flight (s_waitcnt lgkmcnt(1)), i.e. at LDS latency (the fences: 2-4 % on
+      // grouped launches and tall layers, round 1)
+      __builtin_amdgcn_sched_barrier(0);
       if (u + kAhead < 8) gather(u + kAhead);
-      if (VPTQ_K256M_FENCE_UNITS && !(kSB && VPTQ_K256M_SB_UNFENCED)) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
       const int q = u >> 1, h = u & 1;
       const u32x4 c = cv[u % (kAhead + 1)], r = rv[u % (kAhead + 1)];
       u32x2 xo;
       if (kBuild) {
-        if constexpr (kXDup) {
-          const uint32_t xd = u < 4 ? xq[u & 3] : xq2[u & 3];  // (x_u, x_u)
-          xo = u32x2{xd & maskA, xd & maskB};
-        } else {
-          xo = u32x2{__builtin_amdgcn_perm(xq[q], 0u, selA[h]),
-                     __builtin_amdgcn_perm(xq[q], 0u, selB[h])};
-        }
+        xo = u32x2{__builtin_amdgcn_perm(xq[q], 0u, selA[h]),
+                   __builtin_amdgcn_perm(xq[q], 0u, selB[h])};
         if (kCacheXo) xo_cache[kCacheXo ? s : 0][u] = xo;
       } else {
         xo = xo_cache[kCacheXo ? s : 0][u];
       }
-      if (FAST && VPTQ_K256M_ADDFORM && std::is_same<DT, F16>::value) {
-        uint32_t w2[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) w2[p] = DT::add2(c[p], r[p]);
-        acc0 = DT::mfma4(xo, u32x2{w2[0], w2[1]}, acc0);
-        acc1 = DT::mfma4(xo, u32x2{w2[2], w2[3]}, acc1);
-      } else if (FAST && kAblNoMfma) {
+      if (FAST && kAblNoMfma) {
         asm volatile("" :: "v"(c), "v"(r), "v"(xo));
       } else if (FAST) {
-        f32x4& acc2 = acc.a[kAcc4 ? 2 : 0];
-        f32x4& acc3 = acc.a[kAcc4 ? 3 : 1];
         acc0 = DT::mfma4(xo, u32x2{c[0], c[1]}, acc0);
         if constexpr (!kAblQuarterMfma) acc1 = DT::mfma4(xo, u32x2{c[2], c[3]}, acc1);
         if constexpr (!kAblHalfMfma && !kAblQuarterMfma) {
-          acc2 = DT::mfma4(xo, u32x2{r[0], r[1]}, acc2);
-          acc3 = DT::mfma4(xo, u32x2{r[2], r[3]}, acc3);
+          acc0 = DT::mfma4(xo, u32x2{r[0], r[1]}, acc0);
+          acc1 = DT::mfma4(xo, u32x2{r[2], r[3]}, acc1);
         } else {
           asm volatile("" :: "v"(r), "v"(c));
         }
@@ -828,7 +755,7 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
           // values into NaN as well: 0 x inf).  11 MFMAs + 12 conversions + 8 v_perm_b32 per index; 8192^2: 21.7 -> 11.9 us per launch, 9.98 us
           // per layer in a grouped launch.  Counters (profiles/r06/bf16_exact_mfma_pmc.json): the matrix pipe is 42 % busy and the time is
           // 8 cycles per MFMA + 4 per VALU instruction, added up - an A/B without the per-unit fences and with a deeper gather lookahead
-          // (VPTQ_K256M_SB_UNFENCED, VPTQ_K256M_AHEAD_SB) changes nothing: issue bound, not latency bound.
+          // changes nothing: issue bound, not latency bound.
           const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
           const u32x2 so = u32x2{__builtin_amdgcn_perm(sv[q], 0u, selA[h]), __builtin_amdgcn_perm(sv[q], 0u, selB[h])};   // s e_j
           f32x4 d0 = DT::mfma4(bf_id, u32x2{c[0], c[1]}, z);
@@ -885,8 +812,8 @@ static __device__ __forceinline__ void gemv_k256m_body(const K256Layer& Ly, cons
     if constexpr (TOK == 1) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        v[i] = kAcc4 ? acc.a[0][i] + acc.a[kAcc4 ? 2 : 0][i] : acc.a[0][i];
-        v[4 + i] = kAcc4 ? acc.a[1][i] + acc.a[kAcc4 ? 3 : 1][i] : acc.a[1][i];
+        v[i] = acc.a[0][i];
+        v[4 + i] = acc.a[1][i];
       }
     } else {
 #pragma unroll
@@ -1087,8 +1014,7 @@ __global__ __launch_bounds__(kMThreads) void gemv_k256m_kernel_1(
 // unstaged) and the per-wave sum b * x + slot counters
 // sb: scale and bias planes behind the activations (bf16 exact form)
 static int lds_fixed_bytes(int staged_cols, int tok, bool sb) {
-  const int xb = tok == 1 ? kMXBytes1 : 2;
-  return kMTableBytes + (staged_cols > 0 ? (tok + (sb ? 2 : 0)) * (staged_cols * xb + 32) : 0) + tok * kMWaves * 4 + 64 + (tok == 1 && !sb ? kMSelBytes : 0);   // (sb: no selective form, no corrections)
+  return kMTableBytes + (staged_cols > 0 ? (tok + (sb ? 2 : 0)) * (staged_cols * kMXBytes + 32) : 0) + tok * kMWaves * 4 + 64 + (tok == 1 && !sb ? kMSelBytes : 0);   // (sb: no selective form, no corrections)
 }
 
 template <typename DT, int NS, int NST, bool PERM, bool FAST, int TOK>

@@ -180,23 +180,17 @@ static __device__ __forceinline__ void decode_elem(const IdxDecoded<FMT>& d, con
 }
 
 // ---- the kernel -----------------------------------------------------------------------
-// Main codebook into LDS by LDS-DMA (global_load_lds_dwordx4: 1 KiB per instruction and wave, no registers, no
-// ds_write): k x 16 bytes, k a multiple of 64.  Issued as inline assembly (a DMA the compiler can see makes it wait
-// for every load in flight); M0 belongs to the compiler: saved and restored inside the statement.  The caller waits
+// Main codebook into LDS by LDS-DMA (common.h:lds_dma16): k x 16 bytes, k a multiple of 64.  The caller waits
 // with s_waitcnt vmcnt(0) before the barrier that publishes the tables.  (Round 3: the copy through registers,
-// 2 x 4 loads + 8 ds_write_b128 per thread for k = 8192, kept the first index away for ~4 us per launch.)
-#ifndef VPTQ_LDS_DMA
-#define VPTQ_LDS_DMA 1
-#endif
+// 2 x 4 loads + 8 ds_write_b128 per thread for k = 8192, kept the first index away for ~4 us per launch;
+// k = 8192 + 256: 13.9 -> 13.0 us, profiles/r03/lds_dma_copy_ab.txt.)
 static __device__ __forceinline__ void lds_dma_table(const uint32_t* cent, int k, int wave, int lane, int n_waves) {
   const int chunks = k >> 6;   // KiB
   const uint64_t base = (uint64_t)(uintptr_t)as_global(cent) + (uint64_t)lane * 16u;
   for (int j = wave; j < chunks; j += n_waves) {
     const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane(j * 1024);
     const uint64_t v = base + (uint64_t)j * 1024u;
-    uint32_t keep_m0;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+    lds_dma16(d, v);
   }
 }
 
@@ -223,7 +217,7 @@ __global__ __launch_bounds__(kLThreads) void gemv_lds_kernel(const LdsParams P) 
   // ---- prologue: both codebooks into LDS: the main one by LDS-DMA, the residual one (<= 8 KiB, any size) through
   // registers, 4 entries per thread in flight
   {
-    const bool dma = VPTQ_LDS_DMA && (P.k & 63) == 0;
+    const bool dma = (P.k & 63) == 0;
     if (dma) lds_dma_table(P.cent, P.k, __builtin_amdgcn_readfirstlane(wave), lane, kLWaves);
     const int total = P.k + P.kr;
     for (int i0 = (dma ? P.k : 0) + tid; i0 < total; i0 += 4 * kLThreads) {
@@ -330,10 +324,8 @@ __global__ __launch_bounds__(kLThreads) void gemv_lds_kernel(const LdsParams P) 
       normalise_window<FMT>(dec, cur, P, rowc, g0);
       // gathers kGB elements at a time: all 16 gathers of a chunk in flight for one fp16 token
       // (+1...5 % over 8 in flight), fewer with more token accumulators (no spills)
-#ifndef VPTQ_LDS_GB1
-#define VPTQ_LDS_GB1 8
-#endif
-      constexpr int kGB = kF16 ? (TOK == 4 ? 2 : TOK == 1 ? VPTQ_LDS_GB1 : 4) : (TOK == 1 ? 4 : 2);
+      constexpr int kGB1 = 8;
+      constexpr int kGB = kF16 ? (TOK == 4 ? 2 : TOK == 1 ? kGB1 : 4) : (TOK == 1 ? 4 : 2);
       auto batch = [&](auto e0c) {
         constexpr int e0 = decltype(e0c)::value;
         u32x4 cv[kGB], rv[kGB];
@@ -473,7 +465,7 @@ __global__ __launch_bounds__(kLThreads) void gemv_lds_mfma_kernel(const LdsParam
   // passes while the codebooks are copied, changed nothing: +-0.3 us either way over four formats)
   // ---- prologue: codebooks into LDS (the main one by LDS-DMA, the residual one through registers), activations staged
   {
-    const bool dma = VPTQ_LDS_DMA && (P.k & 63) == 0;
+    const bool dma = (P.k & 63) == 0;
     if (dma) lds_dma_table(P.cent, P.k, __builtin_amdgcn_readfirstlane(wave), lane, kLWaves);
     const int total = P.k + P.kr;
     for (int i0 = (dma ? P.k : 0) + tid; i0 < total; i0 += 4 * kLThreads) {
@@ -573,6 +565,8 @@ __global__ __launch_bounds__(kLThreads) void gemv_lds_mfma_kernel(const LdsParam
     // measured SLOWER, 14.9 vs 13.7 us at k = 8192 + 256: as in gemv_k256m.hip, a deeper request burst at the
     // start of a short kernel delays the first data more than it hides later latency;
     // profiles/r02/gemv_lds_mfma_ab.txt)
+    // (the switch stays although the experiment is settled: without the second window's declaration the compiler numbers this
+    // kernel's registers differently - same instructions, another listing: profiles/r20/README.md)
 #ifndef VPTQ_LDS_MFMA_DEPTH
 #define VPTQ_LDS_MFMA_DEPTH 1
 #endif
@@ -760,7 +754,7 @@ static LdsDecision lds_decide(const LdsParams& P, int fmt, bool f16, bool exact)
   D.rw = lds_rows_per_group(P.N);
   D.n_groups = (P.N + D.rw - 1) / D.rw;
   D.grid = D.n_groups < cus ? D.n_groups : cus;
-  D.dma = VPTQ_LDS_DMA && (P.k & 63) == 0;   // the kernels' own test: the main table by LDS-DMA, else through registers
+  D.dma = (P.k & 63) == 0;   // the kernels' own test: the main table by LDS-DMA, else through registers
   D.mfma = lds_use_mfma(P, D.rw, exact);
   if (D.mfma) {
     D.lds = lds_mfma_bytes(P.k, P.kr, P.G);

@@ -41,10 +41,7 @@ namespace vptq {
 // 16.2 / 21.2 us per 8192^2 layer - the unrolled loop runs ceil(blocks / depth) * depth steps, and a wave's stream is
 // only ~34 blocks long: the steps past its end cost as much as real ones (8- and 16-byte loads per lane made no
 // difference: it is the steps, not the load instructions or the bytes).
-#ifndef VPTQ_SLICED_QUEUE
-#define VPTQ_SLICED_QUEUE 8
-#endif
-constexpr int kSLQueueWords = VPTQ_SLICED_QUEUE;
+constexpr int kSLQueueWords = 8;
 // timing-only ablations (results wrong): bit 0 no gathers / FMAs, bit 1 no slice copy, bit 2 no activation staging
 #ifndef VPTQ_SLICED_ABLATE
 #define VPTQ_SLICED_ABLATE 0
@@ -66,24 +63,13 @@ constexpr int kSLMaxGroup = 3;
 #ifndef VPTQ_SLICED_TRACE
 #define VPTQ_SLICED_TRACE 0
 #endif
-// A/B: issue priority by wave age (the phase stamps show the 4 waves of a SIMD finishing 1.3 us apart, oldest first):
-// 1 = the youngest wave of a SIMD gets the highest priority, 2 = the oldest
-#ifndef VPTQ_SLICED_PRIO
-#define VPTQ_SLICED_PRIO 0
-#endif
-// 1: a block's LDS gathers are issued one step ahead of its arithmetic (two register sets); 0: gather, wait, compute per step
-// RG: blocks per queue stage (A/B)
+// (issue priority by wave age - the phase stamps show the 4 waves of a SIMD finishing 1.3 us apart, oldest first - youngest
+// or oldest wave first: 14.5 / 14.3 against 14.3 us at 8192^2, profiles/r05/sliced_priority_and_16_slices_ab.txt)
+// RG: blocks per queue stage
 // (measured, profiles/r05/sliced_exact_two_table_queue_ab.txt: 8 / 4 / 2 blocks = 65.8 / 61.2 / 60.1 us at 8192^2 v8-k65536-65536 - the
-// L1 miss path of a CU is the limit, more gathers in flight only queue up in front of the element words)
-#ifndef VPTQ_SLICED_RGQ
-#define VPTQ_SLICED_RGQ 2
-#endif
-#ifndef VPTQ_SLICED_RGNT
-#define VPTQ_SLICED_RGNT 0
-#endif
-#ifndef VPTQ_SLICED_PIPE
-#define VPTQ_SLICED_PIPE 1
-#endif
+// L1 miss path of a CU is the limit, more gathers in flight only queue up in front of the element words; non-temporal
+// residual gathers: 59.9 -> 89.3 us, same file)
+constexpr int kSLQueueRG = 2;
 // accumulator word of one output: bits [0, 7) arrivals, [7, 14) arrivals whose partial sum could not be represented (NaN, infinite,
 // beyond the field), [14, 64) the sum in units of 2^-F as a 50-bit two's-complement number: |sum| < 2^(49 - F).  F = 30 for fp16
 // layers: sums below 2^19, resolution 9.3e-10 - a 16-bit output of magnitude 1e-4 still gets its sum to 1e-5 relative per arrival;
@@ -171,13 +157,11 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
   static_assert(((V == 8 && (NSL == 8 || NSL == 16)) || (V == 16 && (NSL == 16 || NSL == 32))) && (V == 8 || !RES) && !(TWO && RES) &&
                 !(EX && TWO) && (!RG || (EX && !RES && !TWO)) && (TOK == 1 || ((TOK == 2 || TOK == 3) && EX)) && (!WPT || (TOK > 1 && !RG)), "slices");
   constexpr int NSLT = TWO ? 2 * NSL : NSL;   // workgroups per row block: one per (table, slice)
-  constexpr int EPL = 1;   // element words per lane and block (2 and 4 - 8 / 16-byte loads - were measured: no difference)
   constexpr uint32_t kEntry = V * 2u;                          // bytes of a codebook entry
   const uint32_t kSLXOff = P.x_off;                          // staged activations: (G + 64) halves, behind the table
-  typedef uint32_t evec_t __attribute__((ext_vector_type(EPL)));
   constexpr int kLoadsPerStep = (RES || RG) ? 2 : 1;
-  // blocks in flight per wave (RG, v = 16: 4 - the gathered residual entries of the second stage are 8 registers each)
-  constexpr int kSLQueue = RG ? (V == 16 && VPTQ_SLICED_RGQ > 4 ? 4 : VPTQ_SLICED_RGQ) : (kSLQueueWords / EPL < 2 ? 2 : kSLQueueWords / EPL);
+  // blocks in flight per wave: one element word per lane and block
+  constexpr int kSLQueue = RG ? kSLQueueRG : kSLQueueWords;
   constexpr int W4 = V / 8;   // 16-byte pieces of an entry
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   {
@@ -229,9 +213,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
       const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
       if (off + (uint32_t)lane * 16u < tab) {
         const uint64_t v = va + (uint64_t)off;
-        uint32_t keep_m0;   // (M0 belongs to the compiler: saved and restored inside the statement)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+        lds_dma16(d, v);
       }
     }
   }
@@ -246,9 +228,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
     if (wave < 4) {
       const uint64_t v = (uint64_t)(uintptr_t)as_global(P.rcent) + (uint64_t)wave * 1024u + (uint64_t)lane * 16u;
       const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(res_off + (uint32_t)wave * 1024u));
-      uint32_t keep_m0;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+      lds_dma16(d, v);
     }
   }
   // (2) staging loads of the first kSLPre rounds of the staging loop (16376 columns: every layer of the published
@@ -420,6 +400,9 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
   }
 
   // (4) element queue: block k of the stream -> slot k % kSLQueue
+  // (one element word per lane and block, as a one-element vector: declared uint32_t, the compiler numbers the registers of
+  // the same instructions differently)
+  typedef uint32_t evec_t __attribute__((ext_vector_type(1)));
   evec_t eq[kSLQueue];
   uint32_t rq[(RES || RG) ? kSLQueue : 1];
   // (a wave without blocks still issues its counted loads: of block 0 of the layout, which always exists - behind the last
@@ -427,9 +410,9 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
   // found by tools/gpu_fuzz.py --sliced with every element in one slice, round 5)
   const size_t fb = (!WPT && total > 0) ? (size_t)first_block : 0;   // (WPT: absolute block indices)
   // (wave-uniform base + the lane's 32-bit byte offset: the scalar-base addressing form - no 64-bit vector add per load)
-  const char* const ep = (const char*)(as_global(elems_t) + fb * (64 * EPL));
+  const char* const ep = (const char*)(as_global(elems_t) + fb * 64);
   const char* const rp = (RES || RG) ? (const char*)as_global(P.res) + fb * 64 * (RG ? 2 : 1) : nullptr;
-  const uint32_t lane4 = (uint32_t)lane * 4u * EPL, lane_r = (uint32_t)lane * (RG ? 2u : 1u);
+  const uint32_t lane4 = (uint32_t)lane * 4u, lane_r = (uint32_t)lane * (RG ? 2u : 1u);
   const int last = total > 0 ? total - 1 : 0;
   int i_next = 0;
   // (past the end of the stream a step still issues its load - every step the same instructions, so the waits
@@ -456,7 +439,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
   auto issue = [&](auto slot_c) __attribute__((always_inline)) {
     constexpr int S = decltype(slot_c)::value;
     if constexpr (WPT) {
-      eq[S] = __builtin_nontemporal_load((const evec_t*)(ep + iq_b64 * (4 * EPL) + (size_t)lane4));
+      eq[S] = __builtin_nontemporal_load((const evec_t*)(ep + iq_b64 * 4 + (size_t)lane4));
       if constexpr (RES) rq[S] = *(const uint8_t*)(rp + iq_b64 + (size_t)lane_r);
       if (--iq_left == 0) {
         ++iq_row;
@@ -467,7 +450,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
       return;
     }
     const size_t b64 = (size_t)(i_next < last ? i_next : last) * 64;
-    eq[S] = __builtin_nontemporal_load((const evec_t*)(ep + b64 * (4 * EPL) + (size_t)lane4));
+    eq[S] = __builtin_nontemporal_load((const evec_t*)(ep + b64 * 4 + (size_t)lane4));
     if constexpr (RES) rq[S] = *(const uint8_t*)(rp + b64 + (size_t)lane_r);
     if constexpr (RG) rq[S] = *(const uint16_t*)(rp + b64 * 2 + (size_t)lane_r);
     ++i_next;
@@ -499,13 +482,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
     ew[S] = eq[S][0];
     const char* const ra = (const char*)as_global(P.rcent) + (size_t)rq[S] * kEntry;
 #pragma unroll
-    for (int w = 0; w < W4; ++w) {
-#if VPTQ_SLICED_RGNT
-      rgq[S][w] = __builtin_nontemporal_load((const u32x4*)(ra + 16 * w));
-#else
-      rgq[S][w] = *(const u32x4*)(ra + 16 * w);
-#endif
-    }
+    for (int w = 0; w < W4; ++w) rgq[S][w] = *(const u32x4*)(ra + 16 * w);
   };
   if constexpr (RG) {
     for_slots<kSLQueue>([&](auto slot_c) {
@@ -544,17 +521,6 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
 #pragma unroll
     for (int i = 0; i < 4; ++i) bdot += __uint_as_float(q3[i]);
   }
-#if VPTQ_SLICED_PRIO == 1
-  __builtin_amdgcn_s_setprio(3);   // (A/B, round 5) constants only: the instruction takes an immediate
-  if (wave < 12) __builtin_amdgcn_s_setprio(2);
-  if (wave < 8) __builtin_amdgcn_s_setprio(1);
-  if (wave < 4) __builtin_amdgcn_s_setprio(0);
-#elif VPTQ_SLICED_PRIO == 2
-  __builtin_amdgcn_s_setprio(0);
-  if (wave < 12) __builtin_amdgcn_s_setprio(1);
-  if (wave < 8) __builtin_amdgcn_s_setprio(2);
-  if (wave < 4) __builtin_amdgcn_s_setprio(3);
-#endif
   float acc[TOK][V];
 #pragma unroll
   for (int t = 0; t < TOK; ++t)
@@ -648,14 +614,14 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
     }
   }
   // ---- a block's work in two halves: FETCH (its element word -> LDS addresses -> the gathers go out) and MATH (on what a fetch
-  // brought).  VPTQ_SLICED_PIPE (round 5): block k's gathers are issued BEFORE block k - 1's arithmetic, into the other of two
+  // brought).  Pipelined (round 5): block k's gathers are issued BEFORE block k - 1's arithmetic, into the other of two
   // register sets - a wave then covers its own LDS latency instead of leaving that to the 3 other waves of its SIMD (the
   // phase stamps showed the SIMD's issue bandwidth half idle: 100 cycles per step for 52 cycles of vector work).
   typedef __attribute__((address_space(3))) uint16_t lds_h_t;
   typedef __attribute__((address_space(3))) uint32_t lds_w_t;
   // (measured, profiles/r05/sliced_pipe_ab.txt: -1 ... -3 % without the 256-entry residual table, + 4 % with it - its third
   // gather per block and 8 more live registers: those instantiations keep gather, wait, compute)
-  constexpr bool kPipe = VPTQ_SLICED_PIPE != 0 && !RES && !RG;
+  constexpr bool kPipe = !RES && !RG;
   constexpr int kBufs = kPipe ? 2 : 1;
   u32x4 g_ent[kBufs][W4];
   u32x4 g_rent[kBufs];
@@ -759,7 +725,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
       if (row_i >= n_rows) { done = true; left = 0x7fffffff; }
     }
   };
-  static_assert(kSLQueue % 2 == 0 && EPL == 1, "two register sets alternate over an even number of slots");
+  static_assert(kSLQueue % 2 == 0, "two register sets alternate over an even number of slots");
   // pipelined: block 0's gathers go out in front of the loop; the loop's step for slot S fetches THAT slot's block and then
   // does the arithmetic of the block before it (slot S - 1): slots are walked 1, 2, ... Q - 1, 0
   if constexpr (kPipe) {

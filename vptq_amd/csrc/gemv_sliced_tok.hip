@@ -32,10 +32,9 @@ namespace vptq {
 constexpr int kSTWindows = VPTQ_SLICED_WINDOWS;
 constexpr int kSTRegRows = 4;   // rows per wave whose sums (4 registers each in matrix-pipe mode) are kept in registers
 // element blocks in flight per wave (4 where a lane carries 64 sums: v = 16 with 4 tokens would spill at 8)
-#ifndef VPTQ_ST_QUEUE
-#define VPTQ_ST_QUEUE 8
-#endif
-template <int NV> constexpr int st_queue() { return NV >= 64 ? 4 : VPTQ_ST_QUEUE; }
+// (4 / 8 / 16 for every instantiation: the same times, profiles/r04/sliced_tokens_queue_depth.txt)
+constexpr int kSTQueue = 8;
+template <int NV> constexpr int st_queue() { return NV >= 64 ? 4 : kSTQueue; }
 
 // timing-only ablations (results wrong): bit 0 no FMAs, bit 1 no reduction at the end of a (row, phase) part, bit 2 no LDS gathers,
 // bit 3 no staging of a later phase's activations (its barriers stay), bit 4 none of a later phase's barriers either
@@ -136,9 +135,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
       const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)off);
       if (off + (uint32_t)lane * 16u < tab) {
         const uint64_t v = va + (uint64_t)off;
-        uint32_t keep_m0;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+        lds_dma16(d, v);
       }
     }
   }
@@ -146,9 +143,7 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
     if (wave < 4) {
       const uint64_t v = (uint64_t)(uintptr_t)as_global(P.rcent) + (uint64_t)wave * 1024u + (uint64_t)lane * 16u;
       const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(TP.res_off + (uint32_t)wave * 1024u));
-      uint32_t keep_m0;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep_m0) : "v"(v), "s"(d) : "memory");
+      lds_dma16(d, v);
     }
   }
   // ---- sum b x per token (the workgroups of slice 0: it rides in their partial sums), x in input-feature order
