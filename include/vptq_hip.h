@@ -78,7 +78,21 @@ enum {
    * r16(r16(r16(c+r)*scale)+bias) in the 16-bit type (bit-identical to vptq_dequant and to
    * the reference's torch path), then x*w is accumulated in fp32 and rounded once.  All
    * other kernels (other formats, small layers with 3+ tokens or bf16) always work this way;
-   * bf16 layers of the LDS-resident formats are routed to the L2-gather kernel for it. */
+   * bf16 layers of the LDS-resident formats are routed to the L2-gather kernel for it.
+   * Held weight by weight (tests/test_weight_bits_gpu.py: one-hot activations read W back through every kernel and compare it
+   * with vptq_dequant's bits - signed zeros apart - on a table of subnormals, ties and underflowing products).  What a kernel may
+   * read differently, all of it bf16: the dot-instruction kernels (gemv_k256, gemm_k256, gemm_k256w, gemm_gather, gemm_gatherx)
+   * may flush a weight in the bf16 subnormal range to zero (on an MI355X they do not); the one-pass sliced kernel (gemv_sliced)
+   * reads a weight below 2^-21 as zero - its accumulator word counts in units of 2^-28.  fp16 subnormal weights and activations
+   * are exact in every kernel, the 16-bit MFMA operands of gemv_k256m, gemv_k256c, gemm_k256 and gemv_sliced_tok included.
+   * Weights that are not finite (finite codebooks whose sum or product overflows the 16-bit type): the outputs of a row that
+   * holds one are not finite and every other output is unaffected, but where the reference has an infinity a kernel may have
+   * NaN - wherever it pairs the rebuilt weight with a ZERO (0 x inf): the one-hot MFMA operands of gemv_k256m / gemv_k256c, the
+   * zero column of gemv_sliced_tok (lanes without a token, elements of another column phase), the other half of a bf16 dot
+   * instruction's pair, the accumulator word of gemv_sliced (which holds no infinity), and the tail lanes of gemv_k256 /
+   * gemv_gather, which read the last chunk of 8 columns again against zero activations.  The padding elements of the sliced
+   * layouts rebuild entry 0 of a slice plus residual entry 0 against a scale of zero: a layer in which THAT sum overflows has
+   * NaN in every output of the rows that carry padding. */
   VPTQ_GEMV_EXACT = 1 << 2,
   /* canonical format only: pick the persistent MFMA kernel wherever it is instantiated /
    * never pick it (testing / A-B; the default chooses by launch size) */
