@@ -1243,6 +1243,144 @@ def test_csrc_states_its_shared_idioms_once():
     assert holders("__builtin_amdgcn_mfma_f32_16x16x32_f16") == ["common.h"]
 
 
+# the three kernel files that are compiled in parts, and the only host functions of the shared headers each may define: the
+# dispatchers that pick one of its instantiations (declared in sliced.h / k256.h, called from sliced_host.hip / k256m_host.hip)
+_PART_COMPILED_DISPATCHERS = {
+    "gemv_sliced.hip": {"launch_sl_one", "launch_sl_tokens", "launch_sl_tokens_wpt"},
+    "gemv_sliced_tok.hip": {"launch_st_tok24", "launch_st_tok8", "launch_st_ex4", "launch_st_ex8"},
+    "gemv_k256m.hip": {"k256m_f16_fast", "k256m_f16_exact", "k256m_bf16", "k256m_f16_tokens", "k256m_bf16_tokens", "k256m_bf16_exact",
+                       "k256m_f16_tokens_exact", "k256m_bf16_tokens_exact"},
+}
+_HOST_UNITS = ("sliced_host.hip", "k256m_host.hip")
+
+
+def _toplevel_functions(text, defined_only):
+    """names of the functions a source text declares (or, defined_only, defines) at namespace level: a line that starts in column 0
+    with a return type and `name(`, read up to the `;` or `{` that ends its head"""
+    names = set()
+    for m in re.finditer(r"^(?!\s|//|#|struct\b|enum\b|constexpr\b|namespace\b|typedef\b|template\b|using\b|\})[\w:\*& <>,]*?\b([A-Za-z_]\w*)\s*\(", text, re.M):
+        end = re.search(r"[;{]", text[m.end():])
+        if end and (end.group() == "{" or not defined_only):
+            names.add(m.group(1))
+    return names
+
+
+def test_part_compiled_kernel_files_hold_no_host_policy():
+    """gemv_sliced.hip, gemv_sliced_tok.hip and gemv_k256m.hip - compiled 3 / 4 / 6 times - read no tuning knob and define none of the
+    functions kernels.h / sliced.h / k256.h declare except their instantiation dispatchers; the rules live in the host units, which hold
+    no device code"""
+    csrc = os.path.join(ROOT, "vptq_amd", "csrc")
+    read = lambda f: open(os.path.join(csrc, f)).read()
+    declared = set().union(*(_toplevel_functions(read(h), False) for h in ("kernels.h", "sliced.h", "k256.h")))
+    # (the reader finds what it is there to find: rules of each family, and every dispatcher)
+    assert {"gemv_sliced_eligible", "sl_layout_set", "sl_check_layouts", "gemv_sliced_tok_groupable", "launch_gemv_sliced_tok_group",
+            "gemv_k256m_decide", "launch_gemv_k256m", "gemv_k256m_supported"} <= declared
+    assert set().union(*_PART_COMPILED_DISPATCHERS.values()) <= declared
+    for f, dispatchers in _PART_COMPILED_DISPATCHERS.items():
+        text = read(f)
+        assert not re.search(r"\btune_(env|int|flag)\s*\(", text), f
+        assert _toplevel_functions(text, True) & declared == dispatchers, (f, sorted(_toplevel_functions(text, True) & declared))
+    host = "".join(read(f) for f in _HOST_UNITS)
+    assert not re.search(r"__global__|__device__", host)
+    moved = declared & _toplevel_functions(host, True)
+    assert {"gemv_sliced_eligible", "gemv_sliced_slices", "gemv_sliced_whole_table", "sl_piece_set", "sl_part_desc", "sl_layout_set", "sl_check_layouts",
+            "sl_parts_share", "gemv_sliced_instance", "gemv_sliced_tok_eligible", "gemv_sliced_tok_groupable", "gemv_sliced_tok_instance",
+            "launch_gemv_sliced_group", "launch_gemv_sliced", "launch_gemv_sliced_tok_group", "launch_gemv_sliced_tok", "gemv_k256m_supported",
+            "gemv_k256m_row_groups", "gemv_k256m_launch_units", "gemv_k256m_selective_ok", "gemv_k256m_decide", "launch_gemv_k256m"} <= moved
+    mk = read("Makefile")
+    assert all(re.search(r"^SRCS\s*:=.*\b%s\b" % re.escape(f), mk, re.M) for f in _HOST_UNITS)
+
+
+def _sliced_entry_and_query_cells(lib):
+    """(name, entry code, query code) per bad input of `test_sliced_entries_and_their_instance_queries_turn_down_the_same_calls`: the
+    launching entry gets fake aligned x / y / workspace pointers (nothing is launched or read: every input is one it rejects), the
+    query the same descriptors, layouts, n, tokens and flags"""
+    import ctypes as C
+    EX, PARTS, GEN = B.GEMV_EXACT, B.GEMV_COLUMN_PARTS, B.GEMV_FORCE_GENERIC
+    P, X, Y, WS = 16 << 20, 17 << 20, 18 << 20, 32 << 20
+    d, other = _family_desc(8192, 8192, 8, 65536, 256), _family_desc(8192, 8192, 8, 65536, 0)
+    s = B.SlicedLayoutSet()
+    assert lib.vptq_sliced_layout_set(d, EX, s) == 0 and (s.parts, s.tables, s.side_bytes) == (1, 1, 1)
+    buf = C.create_string_buffer(512)
+
+    def args(n, descs, share, change):
+        dd = (B.LayerDesc * 4)(*(descs or (d, d, d, d)))
+        lay = [B.SlicedLayout(P, P, P, P, 2, 1, s.n_slices, 0, P) for _ in range(max(n, 1))]
+        for k, val in change.items():
+            setattr(lay[-1], k, val)
+        yp = (C.c_void_p * 4)(*[Y if share else Y + (i << 20) for i in range(4)])
+        wp = (C.c_void_p * 4)(*[WS if share else WS + (i << 23) for i in range(4)])
+        return dd, (B.SlicedLayout * len(lay))(*lay), yp, wp
+
+    def one(n=2, flags=EX, single=False, descs=None, share=False, **change):
+        dd, lay, yp, wp = args(n, descs, share, change)
+        need = lib.vptq_quant_gemv_sliced_workspace_bytes(d)
+        e = (lib.vptq_quant_gemv_sliced(dd[0], lay, X, Y, flags, WS, need, None) if single else
+             lib.vptq_quant_gemv_sliced_grouped(dd, lay, n, X, yp, flags, wp, (C.c_size_t * 4)(*[need] * 4), None))
+        return e, lib.vptq_quant_gemv_sliced_instance(dd, lay, n, 1, flags, buf, 512)
+
+    def tok(n=2, tokens=4, flags=EX, single=False, descs=None, share=False, **change):
+        dd, lay, yp, wp = args(n, descs, share, change)
+        need = lib.vptq_quant_gemv_sliced_tokens_workspace_bytes(d, min(max(tokens, 2), 8))
+        e = (lib.vptq_quant_gemv_sliced_tokens(dd[0], lay, X, Y, tokens, flags, WS, need, None) if single else
+             lib.vptq_quant_gemv_sliced_tokens_grouped(dd, lay, n, X, yp, tokens, flags, wp, (C.c_size_t * 4)(*[need] * 4), None))
+        return e, lib.vptq_quant_gemv_sliced_tokens_instance(dd, lay, n, tokens, flags, buf, 512)
+    # (the table's base is a call the queries take: what each cell breaks is the only thing wrong with it)
+    dd, lay, _, _ = args(2, None, False, {})
+    assert lib.vptq_quant_gemv_sliced_instance(dd, lay, 2, 1, EX, buf, 512) == 0 and lib.vptq_quant_gemv_sliced_instance(dd, lay, 1, 1, EX, buf, 512) == 0
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(dd, lay, 2, 4, EX, buf, 512) == 0 and buf.value.startswith(b"gemv_sliced_tok ")
+    assert lib.vptq_quant_gemv_sliced_tokens_instance(dd, lay, 1, 4, EX, buf, 512) == 0
+    cells = []
+    for shape, call in (("one", one), ("tokens", tok)):
+        for who, kw in (("single", dict(n=1, single=True)), ("grouped", {})):
+            cells += [(f"{shape}:{who}:force_generic", *call(flags=EX | GEN, **kw)),
+                      (f"{shape}:{who}:n_slices", *call(n_slices=2 * s.n_slices, **kw)), (f"{shape}:{who}:whole_table", *call(whole_table=1, **kw)),
+                      (f"{shape}:{who}:rows_per_wave", *call(rows_per_wave=0, **kw)), (f"{shape}:{who}:res_missing", *call(res=None, **kw))]
+        cells += [(f"{shape}:grouped:n_0", *call(n=0)), (f"{shape}:grouped:n_4", *call(n=4)),
+                  (f"{shape}:grouped:parts_without_exact", *call(flags=PARTS, share=True)),
+                  (f"{shape}:grouped:two_formats", *call(descs=(d, other, d, d)))]
+    cells += [(f"tokens:{who}:tokens_{t}", *tok(tokens=t, **kw)) for t in (1, 9) for who, kw in (("single", dict(n=1, single=True)), ("grouped", {}))]
+    return cells
+
+
+# Where the query's code is NOT the launching entry's, by the ABI as it stands (every return code is the one these functions gave before
+# they shared their check sequence - recorded from a build of that commit, like _TURN_DOWN_CODES): the several-token query names a bad
+# n (VPTQ_E_SHAPE) and a bad token count (VPTQ_E_TOKENS), which the launching entries turn down as VPTQ_E_UNSUPPORTED with everything
+# else their kernels do not take; and what only the parameter fill of the launch holds a struct to (whole_table, rows_per_wave, the
+# side stream) comes back from the launching entry as 1 = hipErrorInvalidValue - before anything is launched - where the query, which has
+# no launch to fail, says VPTQ_E_UNSUPPORTED.  Every other cell: equal codes.
+_ENTRY_QUERY_PAIRS = dict(
+    [(f"tokens:grouped:n_{n}", (B.E_UNSUPPORTED, B.E_SHAPE)) for n in (0, 4)] +
+    [(f"tokens:{who}:tokens_{t}", (B.E_UNSUPPORTED, B.E_TOKENS)) for t in (1, 9) for who in ("single", "grouped")] +
+    [(f"tokens:{who}:{what}", (1, B.E_UNSUPPORTED)) for who in ("single", "grouped") for what in ("whole_table", "rows_per_wave", "res_missing")])
+
+
+def test_sliced_entries_and_their_instance_queries_turn_down_the_same_calls():
+    """per sliced entry shape (one token; several tokens), the launching entries - vptq_quant_gemv_sliced / _grouped, _sliced_tokens /
+    _tokens_grouped - and their query - vptq_quant_gemv_sliced_instance / _tokens_instance - run ONE check sequence: over a table of bad
+    inputs (wrong n, wrong tokens, VPTQ_GEMV_FORCE_GENERIC, VPTQ_GEMV_COLUMN_PARTS without VPTQ_GEMV_EXACT, a layout with the wrong
+    n_slices / whole_table / rows_per_wave, a missing `res`, members of two formats) both turn the call down, with equal codes - except
+    the cells of _ENTRY_QUERY_PAIRS, whose two codes are pinned"""
+    lib = B.lib()
+    cells = _sliced_entry_and_query_cells(lib)
+    assert len(cells) == 2 * (2 * 5 + 4) + 4 and len({n for n, _, _ in cells}) == len(cells)
+    assert set(_ENTRY_QUERY_PAIRS) <= {n for n, _, _ in cells}
+    rejected = {B.E_SHAPE, B.E_UNSUPPORTED, B.E_TOKENS, 1}     # (1: the launch's parameter fill; any other code would be a launch attempt)
+    for name, entry, query in cells:
+        assert entry in rejected and query in rejected, (name, entry, query)
+        want = _ENTRY_QUERY_PAIRS.get(name)
+        assert (entry, query) == want if want else entry == query, (name, entry, query, want)
+    # one-token shape, per cell: n out of range is VPTQ_E_SHAPE, every other cell VPTQ_E_UNSUPPORTED; its query alone has a token count
+    for name, entry, _ in cells:
+        if name.startswith("one:"):
+            assert entry == (B.E_SHAPE if ":n_" in name and "slices" not in name else B.E_UNSUPPORTED), (name, entry)
+    import ctypes as C
+    buf = C.create_string_buffer(512)
+    d = _family_desc(8192, 8192, 8, 65536, 256)
+    lay = (B.SlicedLayout * 1)(B.SlicedLayout(16 << 20, 16 << 20, 16 << 20, 16 << 20, 2, 1, 16, 0, 16 << 20))
+    assert lib.vptq_quant_gemv_sliced_instance((B.LayerDesc * 1)(d), lay, 1, 2, B.GEMV_EXACT, buf, 512) == B.E_TOKENS
+
+
 # every compile-time switch of vptq_amd/csrc: a settled A/B experiment leaves a constant and two comment lines behind, not a switch
 # (tools/README.md, "Compile-time knobs"); a new one is added here AND documented there, or this fails
 _CSRC_KNOBS = {

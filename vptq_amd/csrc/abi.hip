@@ -801,34 +801,75 @@ size_t vptq_quant_gemv_sliced_workspace_bytes(const VptqLayerDesc* d) {
   return validate_layer(d) == VPTQ_OK && vptq::gemv_sliced_eligible(*d) ? vptq::gemv_sliced_workspace_bytes(*d) : 0;
 }
 
+// ---- the sliced entries' check sequences: ONE per entry shape (one token; several tokens), run by the launching entries AND by their
+// *_instance queries, so a check cannot be added to one and forgotten in the other.  io: the call's x / y / workspaces - NULL in a
+// query, which skips the lines that read them; everything else runs for both, in the order the launching entries have always tested
+// things (their return codes depend on it).  single: the one-layer entry, whose differences from the grouped one stand here, line by
+// line.  *flags: in as the caller passed them, out as the launch takes them.
+struct SlicedBuffers { const void* x; void* const* y; void* const* ws; const size_t* ws_bytes; };
+static bool x_misaligned(const SlicedBuffers* io) { return io && (((uintptr_t)io->x) & 15) != 0; }
+static const char* const kGroupNull = "descs / layouts / x / y / workspaces is NULL";
+
+// tokens: the query's own argument (the launching entries have none: 1)
+static int check_sliced_one(const char* who, bool single, const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens,
+                            int* flags, const SlicedBuffers* io) {
+  if (!single) {
+    if (!descs || !layouts || (io && (!io->x || !io->y || !io->ws || !io->ws_bytes))) return fail(VPTQ_E_NULL, kGroupNull);
+    if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
+  }
+  if (tokens != 1) return fail(VPTQ_E_TOKENS, "tokens %d: the one-token entries (several tokens: vptq_quant_gemv_sliced_tokens_instance)", tokens);
+  for (int i = 0; i < n; ++i) {
+    if (int rc = validate_layer(&descs[i])) return rc;
+    if (!single && io && !io->y[i]) return fail(VPTQ_E_NULL, "y[%d] is NULL", i);
+  }
+  if (single && (!layouts || (io && (!io->x || !io->y[0])))) return fail(VPTQ_E_NULL, "x / y / layout is NULL");
+  // (the one-layer entry has a selective form; the grouped launch has none: the reference's roundings)
+  *flags = single ? drop_redundant_selective(*flags) : selective_as_exact(*flags);
+  const bool exact = (*flags & VPTQ_GEMV_EXACT) != 0, sel = (*flags & VPTQ_GEMV_SELECTIVE) != 0;
+  if (*flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_FORCE_GENERIC: use vptq_quant_gemv");
+  if (single) {
+    if (sel && !vptq::gemv_hot_eligible(descs[0]))
+      return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_SELECTIVE over a sliced layout: fp16 layers the folded sliced kernel serves, with scale and bias "
+                                      "(vptq_quant_gemv_sliced_selective_supported); ask for VPTQ_GEMV_EXACT over an exact layout instead");
+    if (!vptq::gemv_sliced_eligible(descs[0], exact))
+      return fail(VPTQ_E_UNSUPPORTED, exact ? "VPTQ_GEMV_EXACT over a sliced layout: v = 8 / 16, 16384 ... 65536 main centroids, no residual "
+                                              "codebook or the 256-entry one of v = 8, scale / bias / x of every column beside a slice in LDS "
+                                              "(vptq_sliced_layout_supported_for)"
+                                            : "the sliced layout serves v = 8 / 16 layers with 16384 ... 65536 main centroids, group_size <= 32768");
+  } else {
+    if ((*flags & VPTQ_GEMV_COLUMN_PARTS) && (!exact || (io && !vptq::sl_parts_share(descs, io->y, io->ws, n)))) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
+    if (!vptq::gemv_sliced_groupable(descs, n, exact))
+      return fail(VPTQ_E_UNSUPPORTED, "a sliced group takes layers of ONE format, dtype and input width that vptq_sliced_layout_supported_for() accepts");
+    if (x_misaligned(io)) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
+  }
+  for (int i = 0; i < n; ++i) {
+    if (io) {   // (selective: the pre-pass's buffers behind the accumulator words, 256-byte aligned)
+      const size_t acc = vptq::gemv_sliced_workspace_bytes(descs[i]);
+      const size_t need = sel ? (acc + 255) / 256 * 256 + vptq::gemv_hot_bytes(descs[i]) : acc;
+      if (!io->ws[i] || io->ws_bytes[i] < need || (((uintptr_t)io->ws[i]) & (sel ? 255 : 15)) != 0)
+        return single ? fail(VPTQ_E_WORKSPACE, "workspace of %zu bytes (%d-byte aligned) needed", need, sel ? 256 : 16)
+                      : fail(VPTQ_E_WORKSPACE, "layer %d: workspace of %zu bytes (16-byte aligned) needed", i, need);
+    }
+    // (folded, two tables: one layout per table, consecutive structs; the reference's roundings: always ONE layout; one format: the
+    // same table count for every member)
+    const vptq::SlicedLayoutSet S = vptq::sl_piece_set(descs[i], exact);
+    int which = 0;
+    if (const unsigned faults = vptq::sl_check_layouts(descs[i], S, layouts + (size_t)i * S.tables, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole,
+                                                       layouts[0].rows_per_wave, &which))
+      return layout_fail(faults, true, who, i, which, S);
+  }
+  if (single && x_misaligned(io)) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
+  return VPTQ_OK;
+}
+
 int vptq_quant_gemv_sliced(const VptqLayerDesc* d, const VptqSlicedLayout* layout, const void* x, void* y, int flags,
                            void* workspace, size_t workspace_bytes, void* stream) {
-  int rc = validate_layer(d);
-  if (rc) return rc;
-  if (!x || !y || !layout) return fail(VPTQ_E_NULL, "x / y / layout is NULL");
-  flags = drop_redundant_selective(flags);
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  const bool sel = (flags & VPTQ_GEMV_SELECTIVE) != 0;
-  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_FORCE_GENERIC: use vptq_quant_gemv");
-  if (sel && !vptq::gemv_hot_eligible(*d))
-    return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_SELECTIVE over a sliced layout: fp16 layers the folded sliced kernel serves, with scale and bias "
-                                    "(vptq_quant_gemv_sliced_selective_supported); ask for VPTQ_GEMV_EXACT over an exact layout instead");
-  if (!vptq::gemv_sliced_eligible(*d, exact))
-    return fail(VPTQ_E_UNSUPPORTED, exact ? "VPTQ_GEMV_EXACT over a sliced layout: v = 8 / 16, 16384 ... 65536 main centroids, no residual "
-                                            "codebook or the 256-entry one of v = 8, scale / bias / x of every column beside a slice in LDS "
-                                            "(vptq_sliced_layout_supported_for)"
-                                          : "the sliced layout serves v = 8 / 16 layers with 16384 ... 65536 main centroids, group_size <= 32768");
-  const size_t acc_bytes = (vptq::gemv_sliced_workspace_bytes(*d) + 255) / 256 * 256;
-  const size_t need = sel ? acc_bytes + vptq::gemv_hot_bytes(*d) : vptq::gemv_sliced_workspace_bytes(*d);
-  if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & (sel ? 255 : 15)) != 0)
-    return fail(VPTQ_E_WORKSPACE, "workspace of %zu bytes (%d-byte aligned) needed", need, sel ? 256 : 16);
-  // (folded, two tables: one layout per table, consecutive structs; the reference's roundings: always ONE layout)
-  const vptq::SlicedLayoutSet S = vptq::sl_piece_set(*d, exact);
-  int which = 0;
-  if (const unsigned faults = vptq::sl_check_layouts(*d, S, layout, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole, layout[0].rows_per_wave, &which))
-    return layout_fail(faults, true, "vptq_quant_gemv_sliced", 0, which, S);
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
-  if (sel) {
+  void* const ys[1] = {y};
+  void* const wss[1] = {workspace};
+  const SlicedBuffers io = {x, ys, wss, &workspace_bytes};
+  if (int rc = check_sliced_one("vptq_quant_gemv_sliced", true, d, layout, 1, 1, &flags, &io)) return rc;
+  if (flags & VPTQ_GEMV_SELECTIVE) {
+    const size_t acc_bytes = (vptq::gemv_sliced_workspace_bytes(*d) + 255) / 256 * 256;
     // the pre-pass (gemv_hot.hip): threshold, x with the hot blocks' features zeroed, the hot blocks' exact products - behind the
     // accumulator words of the same workspace; then the folded launch over x_masked, which adds the products before its rounding
     const void* xm = nullptr;
@@ -998,50 +1039,58 @@ size_t vptq_quant_gemv_sliced_tokens_workspace_bytes(const VptqLayerDesc* d, int
              ? vptq::gemv_sliced_tok_workspace_bytes(*d, tokens) : 0;
 }
 
+// ... for several tokens (as check_sliced_one: one sequence for the launching entries and the query).  The query names what the
+// launching entries turn down together with everything else their kernels do not take: n as VPTQ_E_SHAPE, the token count as VPTQ_E_TOKENS.
+static int check_sliced_tokens(bool single, const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, int tokens, int* flags,
+                               const SlicedBuffers* io) {
+  *flags = selective_as_exact(*flags);   // (no selective form over several tokens: the reference's roundings)
+  if (!single) {
+    if (!descs || !layouts || (io && (!io->x || !io->y || !io->ws || !io->ws_bytes))) return fail(VPTQ_E_NULL, kGroupNull);
+    if (n < 1 || n > 3) return io ? fail(VPTQ_E_UNSUPPORTED, "a sliced group takes 1 .. 3 layers") : fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
+  }
+  if (!io && (tokens < 2 || tokens > 8)) return fail(VPTQ_E_TOKENS, "tokens %d outside [2, 8]", tokens);
+  for (int i = 0; i < n; ++i) {
+    if (int rc = validate_layer(&descs[i])) return rc;
+    if (!single && io && !io->y[i]) return fail(VPTQ_E_NULL, "y[%d] is NULL", i);
+  }
+  if (single && (!layouts || (io && (!io->x || !io->y[0])))) return fail(VPTQ_E_NULL, "layout, x and y must be set");
+  if (*flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
+  const bool exact = (*flags & VPTQ_GEMV_EXACT) != 0;
+  if (!single && (*flags & VPTQ_GEMV_COLUMN_PARTS)) {   // (as vptq_quant_gemv_sliced_grouped: parts of ONE layer; 2 / 3 tokens, where every part takes them in one pass)
+    if (!exact || (io && !vptq::sl_parts_share(descs, io->y, io->ws, n))) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
+    for (int i = 0; i < n; ++i)
+      if (!vptq::gemv_sliced_tok_one_pass_parts(descs[i], tokens, true)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
+  }
+  // (one layer: gemv_sliced_eligible and gemv_sliced_tok_eligible, which is what a group of one is held to)
+  if (!vptq::gemv_sliced_tok_groupable(descs, layouts, n, tokens, exact))
+    return fail(VPTQ_E_UNSUPPORTED, single ? "sliced layouts with column windows (wstart), 2 - 8 tokens, and activations that fit the LDS beside the slice"
+                                             " (VPTQ_GEMV_EXACT: one-table formats, a layout of vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT) slices)"
+                                           : "a sliced group of 2 - 4 tokens takes layers of ONE format, dtype and input width whose layouts carry wstart");
+  if (!single && x_misaligned(io)) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
+  for (int i = 0; io && i < n; ++i) {
+    const size_t need = vptq::gemv_sliced_tok_workspace_bytes(descs[i], tokens);
+    if (!io->ws[i] || io->ws_bytes[i] < need || (((uintptr_t)io->ws[i]) & 15) != 0)
+      return single ? fail(VPTQ_E_WORKSPACE, "the sliced path for %d tokens needs %zu bytes of 16-byte aligned, zero-initialised workspace", tokens, need)
+                    : fail(VPTQ_E_WORKSPACE, "layer %d: workspace of %zu bytes (16-byte aligned, zero-initialised) needed for %d tokens", i, need, tokens);
+  }
+  if (single && x_misaligned(io)) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
+  return VPTQ_OK;
+}
+
 int vptq_quant_gemv_sliced_tokens(const VptqLayerDesc* d, const VptqSlicedLayout* layout, const void* x, void* y, int tokens,
                                   int flags, void* workspace, size_t workspace_bytes, void* stream) {
-  flags = selective_as_exact(flags);   // (no selective form over several tokens: the reference's roundings)
-  if (int rc = validate_layer(d)) return rc;
-  if (!layout || !x || !y) return fail(VPTQ_E_NULL, "layout, x and y must be set");
-  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  if (!vptq::gemv_sliced_eligible(*d, exact) || !vptq::gemv_sliced_tok_eligible(*d, layout, tokens, exact))
-    return fail(VPTQ_E_UNSUPPORTED, "sliced layouts with column windows (wstart), 2 - 8 tokens, and activations that fit the LDS beside the slice"
-                                    " (VPTQ_GEMV_EXACT: one-table formats, a layout of vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT) slices)");
-  const size_t need = vptq::gemv_sliced_tok_workspace_bytes(*d, tokens);
-  if (!workspace || workspace_bytes < need || (((uintptr_t)workspace) & 15) != 0)
-    return fail(VPTQ_E_WORKSPACE, "the sliced path for %d tokens needs %zu bytes of 16-byte aligned, zero-initialised workspace", tokens, need);
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
+  void* const ys[1] = {y};
+  void* const wss[1] = {workspace};
+  const SlicedBuffers io = {x, ys, wss, &workspace_bytes};
+  if (int rc = check_sliced_tokens(true, d, layout, 1, tokens, &flags, &io)) return rc;
   const hipError_t e = vptq::launch_gemv_sliced_tok(*d, layout, x, y, tokens, flags, workspace, (hipStream_t)stream);
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced_tok launch");
 }
 
 int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, const void* x,
                                    void* const* y, int flags, void* const* workspaces, const size_t* workspace_bytes, void* stream) {
-  flags = selective_as_exact(flags);   // (the grouped launch has no selective form: the reference's roundings)
-  if (!descs || !layouts || !x || !y || !workspaces || !workspace_bytes) return fail(VPTQ_E_NULL, "descs / layouts / x / y / workspaces is NULL");
-  if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
-  for (int i = 0; i < n; ++i) {
-    const int rc = validate_layer(&descs[i]);
-    if (rc) return rc;
-    if (!y[i]) return fail(VPTQ_E_NULL, "y[%d] is NULL", i);
-  }
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_FORCE_GENERIC: use vptq_quant_gemv");
-  if ((flags & VPTQ_GEMV_COLUMN_PARTS) && (!exact || !vptq::sl_parts_share(descs, y, workspaces, n))) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
-  if (!vptq::gemv_sliced_groupable(descs, n, exact))
-    return fail(VPTQ_E_UNSUPPORTED, "a sliced group takes layers of ONE format, dtype and input width that vptq_sliced_layout_supported_for() accepts");
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
-  for (int i = 0; i < n; ++i) {
-    const size_t need = vptq::gemv_sliced_workspace_bytes(descs[i]);
-    if (!workspaces[i] || workspace_bytes[i] < need || (((uintptr_t)workspaces[i]) & 15) != 0)
-      return fail(VPTQ_E_WORKSPACE, "layer %d: workspace of %zu bytes (16-byte aligned) needed", i, need);
-    const vptq::SlicedLayoutSet S = vptq::sl_piece_set(descs[i], exact);   // (one format: the same table count for every member)
-    int which = 0;
-    if (const unsigned faults = vptq::sl_check_layouts(descs[i], S, layouts + (size_t)i * S.tables, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole,
-                                                       layouts[0].rows_per_wave, &which))
-      return layout_fail(faults, true, "vptq_quant_gemv_sliced_grouped", i, which, S);
-  }
+  const SlicedBuffers io = {x, y, workspaces, workspace_bytes};
+  if (int rc = check_sliced_one("vptq_quant_gemv_sliced_grouped", false, descs, layouts, n, 1, &flags, &io)) return rc;
   const hipError_t e = vptq::launch_gemv_sliced_group(descs, layouts, n, x, y, flags, workspaces, (hipStream_t)stream);
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced grouped launch");
 }
@@ -1049,34 +1098,15 @@ int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const VptqSlicedL
 int vptq_quant_gemv_sliced_tokens_grouped(const VptqLayerDesc* descs, const VptqSlicedLayout* layouts, int n, const void* x,
                                           void* const* y, int tokens, int flags, void* const* workspaces, const size_t* workspace_bytes,
                                           void* stream) {
-  flags = selective_as_exact(flags);
-  if (!descs || !layouts || !x || !y || !workspaces || !workspace_bytes) return fail(VPTQ_E_NULL, "descs / layouts / x / y / workspaces is NULL");
-  if (n < 1 || n > 3) return fail(VPTQ_E_UNSUPPORTED, "a sliced group takes 1 .. 3 layers");
-  for (int i = 0; i < n; ++i) {
-    if (int rc = validate_layer(descs + i)) return rc;
-    if (!y[i]) return fail(VPTQ_E_NULL, "y[%d] is NULL", i);
-  }
-  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
-  if (flags & VPTQ_GEMV_COLUMN_PARTS) {   // (as vptq_quant_gemv_sliced_grouped: parts of ONE layer; 2 / 3 tokens, where every part takes them in one pass)
-    if (!(flags & VPTQ_GEMV_EXACT) || !vptq::sl_parts_share(descs, y, workspaces, n)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
-    for (int i = 0; i < n; ++i)
-      if (!vptq::gemv_sliced_tok_one_pass_parts(descs[i], tokens, true)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
-  }
-  if (!vptq::gemv_sliced_tok_groupable(descs, layouts, n, tokens, (flags & VPTQ_GEMV_EXACT) != 0))
-    return fail(VPTQ_E_UNSUPPORTED, "a sliced group of 2 - 4 tokens takes layers of ONE format, dtype and input width whose layouts carry wstart");
-  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "x must be 16-byte aligned");
-  for (int i = 0; i < n; ++i) {
-    const size_t need = vptq::gemv_sliced_tok_workspace_bytes(descs[i], tokens);
-    if (!workspaces[i] || workspace_bytes[i] < need || (((uintptr_t)workspaces[i]) & 15) != 0)
-      return fail(VPTQ_E_WORKSPACE, "layer %d: workspace of %zu bytes (16-byte aligned, zero-initialised) needed for %d tokens", i, need, tokens);
-  }
+  const SlicedBuffers io = {x, y, workspaces, workspace_bytes};
+  if (int rc = check_sliced_tokens(false, descs, layouts, n, tokens, &flags, &io)) return rc;
   const hipError_t e = vptq::launch_gemv_sliced_tok_group(descs, layouts, n, x, y, tokens, flags, workspaces, (hipStream_t)stream);
   return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemv_sliced_tok grouped launch");
 }
 
-// ---- which instantiation a sliced call would launch (vptq_quant_gemv_sliced_instance / _tokens_instance): the entries' own checks of
-// the descriptors, layouts and flags in their order (x, y and the workspaces are not there to check), then the text of the very
-// decide functions the launches run (gemv_sliced.hip:sl_decide, gemv_sliced_tok.hip:st_decide, gemv_hot_decide)
+// ---- which instantiation a sliced call would launch (vptq_quant_gemv_sliced_instance / _tokens_instance): the launching entries' own
+// check sequence (check_sliced_one / check_sliced_tokens without x, y and the workspaces), then the text of the very decide functions
+// the launches run (sliced_host.hip: sl_decide, st_decide; gemv_hot_decide)
 static int sliced_instance_rc(int rc, size_t bytes) {
   if (rc == -2) return fail(VPTQ_E_WORKSPACE, "instance: buffer of %zu bytes too small", bytes);
   return rc ? fail(VPTQ_E_UNSUPPORTED, "instance: no sliced launch serves this call") : VPTQ_OK;
@@ -1085,25 +1115,9 @@ int vptq_quant_gemv_sliced_instance(const VptqLayerDesc* descs, const VptqSliced
                                     size_t bytes) {
   if (!descs || !layouts || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / layouts / buf is NULL");
   buf[0] = 0;
-  if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
-  if (tokens != 1) return fail(VPTQ_E_TOKENS, "tokens %d: the one-token entries (several tokens: vptq_quant_gemv_sliced_tokens_instance)", tokens);
-  for (int i = 0; i < n; ++i)
-    if (int rc = validate_layer(&descs[i])) return rc;
-  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_FORCE_GENERIC: use vptq_quant_gemv");
-  const bool single = n == 1 && !(flags & VPTQ_GEMV_COLUMN_PARTS);   // vptq_quant_gemv_sliced
-  flags = single ? drop_redundant_selective(flags) : selective_as_exact(flags);
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0, sel = (flags & VPTQ_GEMV_SELECTIVE) != 0;
-  if (sel && !vptq::gemv_hot_eligible(descs[0])) return fail(VPTQ_E_UNSUPPORTED, "VPTQ_GEMV_SELECTIVE over a sliced layout: not served for this layer");
-  if ((flags & VPTQ_GEMV_COLUMN_PARTS) && !exact) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
-  if (!vptq::gemv_sliced_groupable(descs, n, exact))
-    return fail(VPTQ_E_UNSUPPORTED, "a sliced launch takes layers of ONE format, dtype and input width that vptq_sliced_layout_supported_for() accepts");
-  for (int i = 0; i < n; ++i) {
-    const vptq::SlicedLayoutSet S = vptq::sl_piece_set(descs[i], exact);
-    int which = 0;
-    if (const unsigned faults = vptq::sl_check_layouts(descs[i], S, layouts + (size_t)i * S.tables, S.tables, vptq::kSLNeedRows | vptq::kSLNeedWhole,
-                                                       layouts[0].rows_per_wave, &which))
-      return layout_fail(faults, true, "vptq_quant_gemv_sliced_instance", i, which, S);
-  }
+  const bool single = n == 1 && !(flags & VPTQ_GEMV_COLUMN_PARTS);   // vptq_quant_gemv_sliced, else vptq_quant_gemv_sliced_grouped
+  if (int rc = check_sliced_one("vptq_quant_gemv_sliced_instance", single, descs, layouts, n, tokens, &flags, nullptr)) return rc;
+  const bool sel = (flags & VPTQ_GEMV_SELECTIVE) != 0;
   Text t = {buf, bytes, 0, true};
   char one[384];
   if (sel) {
@@ -1120,21 +1134,7 @@ int vptq_quant_gemv_sliced_tokens_instance(const VptqLayerDesc* descs, const Vpt
                                            char* buf, size_t bytes) {
   if (!descs || !layouts || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / layouts / buf is NULL");
   buf[0] = 0;
-  if (n < 1 || n > 3) return fail(VPTQ_E_SHAPE, "n %d outside [1, 3]", n);
-  if (tokens < 2 || tokens > 8) return fail(VPTQ_E_TOKENS, "tokens %d outside [2, 8]", tokens);
-  flags = selective_as_exact(flags);
-  for (int i = 0; i < n; ++i)
-    if (int rc = validate_layer(&descs[i])) return rc;
-  if (flags & VPTQ_GEMV_FORCE_GENERIC) return fail(VPTQ_E_UNSUPPORTED, "the sliced path is not the generic kernel: use vptq_quant_gemv");
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  if (flags & VPTQ_GEMV_COLUMN_PARTS) {
-    if (!exact) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
-    for (int i = 0; i < n; ++i)
-      if (!vptq::gemv_sliced_tok_one_pass_parts(descs[i], tokens, true)) return fail(VPTQ_E_UNSUPPORTED, kPartsShare);
-  }
-  if (!vptq::gemv_sliced_groupable(descs, n, exact) || !vptq::gemv_sliced_tok_groupable(descs, layouts, n, tokens, exact))
-    return fail(VPTQ_E_UNSUPPORTED, "sliced layouts with column windows (wstart), 2 - 8 tokens, layers of ONE format, dtype and input width whose "
-                                    "activations fit the LDS beside the slice");
+  if (int rc = check_sliced_tokens(false, descs, layouts, n, tokens, &flags, nullptr)) return rc;
   char one[384];
   if (const int rc = vptq::gemv_sliced_tok_instance(descs, layouts, n, tokens, flags, one, sizeof(one))) return sliced_instance_rc(rc, bytes);
   Text t = {buf, bytes, 0, true};

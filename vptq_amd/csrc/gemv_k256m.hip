@@ -49,15 +49,7 @@
 
 namespace vptq {
 
-constexpr int kMThreads = 1024;
-constexpr int kMWaves = kMThreads / 64;
-constexpr int kMSweepCols = kMWaves * 16 * 8;  // 2048: 16 blocks (column chunks of 8) per wave
-constexpr int kMTableBytes = 65536;  // 256 rows x (8 main + 8 residual replicas) x 16 B
-constexpr int kMMaxLds = 163840;   // 160 KiB per CU
-constexpr int kMMaxCols = 14336;   // staged activations must fit beside the image
-constexpr int kMXBytes = 2;        // staged bytes per column and token
-constexpr int kMRedSlot = kMWaves * 32 * 4;   // one row group's cross-wave partials, per token
-constexpr int kMMaxSlots = 4;
+// (the launch geometry both this file and its host side read - kMThreads ... kMMaxSlots, kMSel*, lds_fixed_bytes: k256.h)
 // VPTQ_GEMV_SELECTIVE (round 6; one token, fp16, folded instantiations; K256Layer::slots bit 8): the folded form, with the reference's
 // roundings on the blocks of 128 columns an activation dominates - see gemv_k256c.hip.  Here everything happens inside the launch:
 // while a wave stages its 512 columns it takes the rms of ITS f16(s x), marks the blocks that hold a column at or above
@@ -65,18 +57,9 @@ constexpr int kMMaxSlots = 4;
 // leaves them out); behind the prologue barrier the workgroup rebuilds the hot blocks' weights of its own row groups as the
 // reference rounds them and leaves sum w x in `corr` (LDS), which finish() adds before the one rounding.  Nothing in the loop changes.
 constexpr float kMSelKappa = 6.0f;
-constexpr int kMSelBit = 0x100;            // K256Layer::slots: selective roundings
-constexpr int kMSelMaxBlocks = 128;        // 16384 columns (staged: <= 14336)
-constexpr int kMSelRowGroups = 16;         // row groups per workgroup the corrections cover (16 waves = 4 x 4 rows per round; gate / up of an
-                                           // 8B model in one grouped launch: 14 per workgroup)
 constexpr int kMSelMaxHot = 16;            // hot blocks per layer the corrections cover: the most dominant ones (a token with dozens of
                                            // "dominant" blocks is a dense one - the folded form's regime - and the corrections are latency-bound work: the
                                            // 14336-column down projection of a decoder, silu(gate) * up as input, had 50 of 112 blocks hot: 49 us for a 6 us launch)
-constexpr int kMSelBytes = 2 * kMSelMaxBlocks + 4 * kMSelRowGroups * 32 * 4;   // block magnitudes + corr [4 quarters of the hot blocks][row groups][32]
-// VPTQ_K256M_SB_ALL (A/B, no result on record): every exact instantiation stages scale and bias in LDS (default: bf16, and fp16 from 6 sweeps on)
-#ifndef VPTQ_K256M_SB_ALL
-#define VPTQ_K256M_SB_ALL 0
-#endif
 
 // Timing-only ablations (make variant EXTRA=-DVPTQ_K256M_ABLATE=bits, tools/ab_libs.py --no-parity; the RESULTS of such a build are wrong): bit 0 no
 // MFMAs, bit 1 no LDS gathers (the addresses are still computed), bit 2 no epilogue, bit 3 no
@@ -1009,14 +992,7 @@ __global__ __launch_bounds__(kMThreads) void gemv_k256m_kernel_1(
   gemv_k256m_body<DT, NS, NST, PERM, FAST, 1>(Ly, P.tokens);
 }
 
-// ---- host side -------------------------------------------------------------------
-// LDS bytes before the partial-sum slots: image + per token the staged activations (0 columns:
-// unstaged) and the per-wave sum b * x + slot counters
-// sb: scale and bias planes behind the activations (bf16 exact form)
-static int lds_fixed_bytes(int staged_cols, int tok, bool sb) {
-  return kMTableBytes + (staged_cols > 0 ? (tok + (sb ? 2 : 0)) * (staged_cols * kMXBytes + 32) : 0) + tok * kMWaves * 4 + 64 + (tok == 1 && !sb ? kMSelBytes : 0);   // (sb: no selective form, no corrections)
-}
-
+// ---- launchers: the instantiation a decision names (the decision itself - gemv_k256m_decide - and launch_gemv_k256m: k256m_host.hip)
 template <typename DT, int NS, int NST, bool PERM, bool FAST, int TOK>
 static hipError_t launch_m(const K256Params& P, const K256MDecision& D, hipStream_t st) {
   // this instantiation is the one the decision names (kSB: the kernel's own rule, gemv_k256m_body)
@@ -1066,28 +1042,18 @@ static hipError_t launch_m_shape(const K256Params& P, const K256MDecision& D, hi
   return hipErrorInvalidValue;
 }
 
-// partial-sum slots that fit beside everything else (0: the shape does not fit at all)
-static int lds_slots(int tok, int max_cols, bool sb) {
-  const int left = kMMaxLds - lds_fixed_bytes(max_cols > kMMaxCols ? 0 : max_cols, tok, sb);
-  const int slots = left < 0 ? 0 : left / (kMRedSlot * tok);
-  return slots > kMMaxSlots ? kMMaxSlots : slots;
-}
-
-// The instantiations are spread over four translation units (Makefile: -DVPTQ_K256M_PART=1..4
-// on this same file) so that they compile side by side; PART 0 = everything in one.
+// The instantiations are spread over six translation units (Makefile: -DVPTQ_K256M_PART=1..6
+// on this same file) so that they compile side by side; PART 0 = everything in one.  Every part holds instantiation
+// dispatchers only - the k256m_* functions k256.h declares and launch_gemv_k256m (k256m_host.hip) calls.
 #ifndef VPTQ_K256M_PART
 #define VPTQ_K256M_PART 0
 #endif
 #define K256M_PART(n) (VPTQ_K256M_PART == 0 || VPTQ_K256M_PART == (n))
-hipError_t k256m_f16_fast(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_f16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_bf16(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_f16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_bf16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_bf16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_f16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
-hipError_t k256m_bf16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);
-
+#if K256M_PART(1)
+hipError_t k256m_f16_fast(const K256Params& P, const K256MDecision& D, hipStream_t st) {
+  return launch_m_shape<F16, true, 1>(P, D, st);
+}
+#endif
 #if K256M_PART(2)
 hipError_t k256m_f16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st) {
   return launch_m_shape<F16, false, 1>(P, D, st);
@@ -1123,128 +1089,5 @@ hipError_t k256m_bf16_tokens_exact(const K256Params& P, const K256MDecision& D, 
                   : launch_m_shape<BF16, false, 4>(P, D, st);
 }
 #endif
-#if K256M_PART(1)
-hipError_t k256m_f16_fast(const K256Params& P, const K256MDecision& D, hipStream_t st) {
-  return launch_m_shape<F16, true, 1>(P, D, st);
-}
-
-// exact form with scale and bias staged in LDS (kSB in the kernel): bf16, and fp16 from 6 sweeps on
-static bool sb_staged(bool f16, bool fast, int max_cols, int tok) {
-  return !fast && (!f16 || max_cols > 5 * kMSweepCols || tok > 1 || VPTQ_K256M_SB_ALL);
-}
-// tok = token slots of the instantiation (1, 2 or 4)
-bool gemv_k256m_supported(int tok, bool f16, bool fast, int max_cols, bool perm) {
-  // (the fp16 exact form queues scale and bias with the index words up to 5 sweeps; 6 and 7 sweeps - and bf16 - stage them in LDS: kSB)
-  // more columns than fit beside the image: unstaged variant (folded form, no permutation)
-  if (max_cols > kMMaxCols && (!fast || perm || tok > 1)) return false;
-  // several tokens: one staged copy of the activations per token slot (the reference's roundings: scale and bias staged as well)
-  if (tok != 1 && !(tok == 2 || tok == 4)) return false;
-  // ... in the reference's roundings (round 6): the 4-slot instantiations keep 32 accumulator registers and spill from 3 (fp16) /
-  // 2 (bf16) sweeps on; two passes of the 2-slot kernel lose against the VALU kernel (tools/tokens_exact_check.py: 4096 x 14336
-  // bf16 30.2 vs 26.7 us, 4096^2 17.8 vs 10.0)
-  if (tok == 4 && !fast && max_cols > (f16 ? 2 : 1) * kMSweepCols) return false;
-  if (lds_slots(tok, max_cols, sb_staged(f16, fast, max_cols, tok)) < 1) return false;
-  return true;
-}
-
-int gemv_k256m_row_groups(int n_rows) { return (n_rows + kMRows - 1) / kMRows; }
-
-// All layers of a grouped launch must have the same number of columns (checked by the
-// caller, launch_gemv_k256).  Fills in K256Layer::wgs: one workgroup per CU, shared out
-// between the layers in proportion to their row groups.
-// Workgroups per layer of one launch: one workgroup per CU (the LDS holds one), shared out in proportion to the layers' row
-// groups - and never more than `cus` in total: rounding every share up gave 3 x 86 = 258 workgroups for three equal layers
-// (q / k / v of an MHA model), two of which waited for a CU to come free (round 6).  While the sum is too large, the layer that
-// loses least - whose row groups per workgroup stay the lowest after giving one up - gives one up.
-static void m_shares(const int* groups, int n, int cus, int* share) {
-  long long total = 0;
-  for (int i = 0; i < n; ++i) total += groups[i];
-  long long sum = 0;
-  for (int i = 0; i < n; ++i) {
-    long long sh = total > cus ? ((long long)groups[i] * cus + total - 1) / total : groups[i];
-    if (sh < 1) sh = 1;
-    if (sh > groups[i]) sh = groups[i];
-    share[i] = (int)sh;
-    sum += sh;
-  }
-  while (sum > cus) {
-    int best = -1, best_units = 0;
-    for (int i = 0; i < n; ++i) {
-      if (share[i] <= 1) continue;
-      const int units = (groups[i] + share[i] - 2) / (share[i] - 1);   // row groups per workgroup with one workgroup less
-      if (best < 0 || units < best_units || (units == best_units && share[i] > share[best])) { best = i; best_units = units; }
-    }
-    if (best < 0) break;   // (more layers than CUs: cannot happen with kMaxGroup layers)
-    --share[best];
-    --sum;
-  }
-}
-static int m_cus() {
-  static const int fw = tune_int("VPTQ_K256M_WGS", 0);  // tuning override of the CU count
-  return fw > 0 ? fw : device_cus();
-}
-int gemv_k256m_launch_units(const int* n_rows, int n) {
-  if (n < 1 || n > kMaxGroup) return 0;
-  int groups[kMaxGroup], share[kMaxGroup], units = 0;
-  for (int i = 0; i < n; ++i) groups[i] = gemv_k256m_row_groups(n_rows[i]);
-  m_shares(groups, n, m_cus(), share);
-  for (int i = 0; i < n; ++i) {
-    const int u = (groups[i] + share[i] - 1) / share[i];
-    units = u > units ? u : units;
-  }
-  return units;
-}
-// VPTQ_GEMV_SELECTIVE in this kernel: one token, fp16, staged activations, the folded instantiation; every workgroup's row groups
-// must fit the corrections' LDS (kMSelRowGroups)
-bool gemv_k256m_selective_ok(const int* n_rows, int n, bool f16, int tok, int max_cols, bool perm) {
-  if (tok != 1 || max_cols > kMMaxCols || max_cols > kMSelMaxBlocks * 128 || !gemv_k256m_supported(1, f16, true, max_cols, perm)) return false;
-  if (n > kMaxGroup) return false;
-  int groups[kMaxGroup], share[kMaxGroup];
-  for (int i = 0; i < n; ++i) groups[i] = gemv_k256m_row_groups(n_rows[i]);
-  m_shares(groups, n, m_cus(), share);
-  for (int i = 0; i < n; ++i)
-    if ((groups[i] + share[i] - 1) / share[i] > kMSelRowGroups) return false;
-  return true;
-}
-
-// The decision for one launch: which instantiation (launch_m_shape picks exactly it) and how the launch is shaped.  Host
-// arithmetic and the CU-count look-up only.
-K256MDecision gemv_k256m_decide(const int* n_rows, int n, int tok, bool f16, bool fast, int max_cols, bool perm, bool selective) {
-  K256MDecision D = {};
-  D.f16 = f16; D.fast = fast; D.perm = perm; D.selective = selective; D.tok = tok; D.max_cols = max_cols;
-  if (n < 1 || n > kMaxGroup || !gemv_k256m_supported(tok, f16, fast, max_cols, perm)) return D;
-  if (selective && !(fast && tok == 1 && max_cols <= kMMaxCols)) return D;
-  const bool wide = max_cols > kMMaxCols;   // unstaged: column blocks of 2 sweeps
-  D.ns = wide ? 2 : (max_cols + kMSweepCols - 1) / kMSweepCols;
-  D.nst = wide ? 0 : D.ns <= 4 ? 1 : 2;
-  D.sb = sb_staged(f16, fast, max_cols, tok);
-  D.slots = lds_slots(tok, max_cols, D.sb);
-  D.entry = tok == 1 && n == 1 ? 1 : 0;
-  int groups[kMaxGroup];
-  for (int i = 0; i < n; ++i) groups[i] = gemv_k256m_row_groups(n_rows[i]);
-  m_shares(groups, n, m_cus(), D.share);
-  for (int i = 0; i < n; ++i) {
-    const int u = (groups[i] + D.share[i] - 1) / D.share[i];
-    D.units = u > D.units ? u : D.units;
-    D.gx = D.share[i] > D.gx ? D.share[i] : D.gx;
-  }
-  D.ok = D.ns >= 1 && D.ns <= 7 && D.slots >= 1;
-  return D;
-}
-
-hipError_t launch_gemv_k256m(K256Params& P, const K256MDecision& D, hipStream_t st) {
-  if (!D.ok || P.n_layers < 1 || P.n_layers > kMaxGroup) return hipErrorInvalidValue;
-  for (int i = 0; i < P.n_layers; ++i) {
-    P.layer[i].wgs = D.share[i];
-    P.layer[i].slots = D.slots | (D.selective ? kMSelBit : 0);
-  }
-  if (D.tok != 1) {
-    if (!D.fast) return D.f16 ? k256m_f16_tokens_exact(P, D, st) : k256m_bf16_tokens_exact(P, D, st);
-    return D.f16 ? k256m_f16_tokens(P, D, st) : k256m_bf16_tokens(P, D, st);
-  }
-  if (!D.f16) return D.fast ? k256m_bf16(P, D, st) : k256m_bf16_exact(P, D, st);
-  return D.fast ? k256m_f16_fast(P, D, st) : k256m_f16_exact(P, D, st);
-}
-#endif  // part 1
 
 }  // namespace vptq

@@ -31,8 +31,6 @@
 //                         c f16(s x) and r f16(s x) from different workgroups)
 //   reference roundings (VPTQ_GEMV_EXACT, template EX): w = f16(f16(f16(c + r) * s) + b) per weight, y = sum w x + bias -
 //                         the product default since round 5; one table only (none or the 256-entry residual codebook)
-#include <cstring>
-
 #include "sliced.h"
 
 namespace vptq {
@@ -46,10 +44,6 @@ constexpr int kSLQueueWords = 8;
 #ifndef VPTQ_SLICED_ABLATE
 #define VPTQ_SLICED_ABLATE 0
 #endif
-// Up to kSLMaxGroup layers that read the SAME activation (q / k / v, gate / up) in one launch: layer l owns the workgroups
-// [start[l], start[l + 1]).  One launch instead of n: the fixed part of a launch (boundary, slice copy, staging, the
-// cross-slice hand-over: ~7 of the 10 us of a 4096 x 4096 layer) is paid once.
-constexpr int kSLMaxGroup = 3;
 // How the slices of a row meet (round 5): ONE hop.  Every (slice, output) partial sum becomes a 64-bit fixed-point word
 // (count | value) that is added to the output's accumulator word with a returning device-scope atomic; integer adds commute, so
 // the sum does not depend on the order, and the lane whose add completes the count holds the total, rounds it once and stores y.
@@ -112,12 +106,6 @@ static __device__ __forceinline__ float sl_from_fixed(unsigned long long w) {
   const long long q = (long long)w >> kSLFixShift;
   return (float)((double)q * (1.0 / (double)(1ull << F)));   // |q| < 2^49: exact in fp64, ONE rounding to fp32
 }
-struct SlicedGroupParams {
-  int n;
-  int arrivals;   // workgroups that add into an output's accumulator word: (tables x) slices - x n where the "layers" are COLUMN PARTS of one
-  int start[kSLMaxGroup + 1];
-  SlicedParams p[kSLMaxGroup];
-};
 
 // EX (round 5): the reference's roundings per weight instead of the folded form - w = f16(f16(f16(c + r) * s) + b)
 // (vptq/ops/quant_gemm.py:121,155-156), y = sum w x in fp32: what gemv_gather computes, here with LDS-local gathers.  The
@@ -774,8 +762,9 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_kernel(const SlicedGro
 #endif
 }
 
-// ---- launchers (both parts of the build: the file is compiled twice, VPTQ_SL_PART = 1: the one-token instantiations + the host
-// side, 2: the 2 / 3-token instantiations of the reference's roundings)
+// ---- launchers.  The file is compiled three times, a share of the instantiations each: VPTQ_SL_PART = 1: one token, 2: 2 / 3 tokens
+// in the reference's roundings, 3: the same in window parts (not defined: all of them in one unit).  Every part's dispatcher is
+// declared in sliced.h and called from sliced_host.hip, where the family's host side - sl_decide and the rules it reads - lives.
 template <typename DT, int NSL, bool RES, int V, bool TWO, bool EX = false, bool RG = false, int TOK = 1, bool WPT = false>
 static hipError_t launch_sl(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
   // this instantiation is the one the decision names (sl_decide)
@@ -787,8 +776,6 @@ static hipError_t launch_sl(const SlicedDecision& D, const SlicedGroupParams& P,
   hipLaunchKernelGGL(kern, dim3(P.start[P.n]), dim3(kSLThreads), lds, st, P);
   return hipGetLastError();
 }
-hipError_t launch_sl_tokens(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);
-hipError_t launch_sl_tokens_wpt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);
 #if !defined(VPTQ_SL_PART) || VPTQ_SL_PART == 3
 // (window parts: v = 8, one table)
 template <typename DT, int TOK>
@@ -828,101 +815,6 @@ hipError_t launch_sl_tokens(const SlicedDecision& D, const SlicedGroupParams& P,
 #endif
 
 #if !defined(VPTQ_SL_PART) || VPTQ_SL_PART == 1
-// ---- host side -------------------------------------------------------------------
-// Large-codebook layers: v = 8 or 16, 16384 ... 65536 main centroids, one codebook group, no outlier columns, norm on.
-// Residual codebook: none; v = 8 with 256 entries (one launch, the table beside the slice, a byte per element); any other
-// size (2 ... 65536 entries) as a SECOND TABLE with a layout of its own in the same launch.
-static bool sl_pow2(int k) { return k > 0 && (k & (k - 1)) == 0; }
-bool sl_res256(const VptqLayerDesc& d) { return d.vector_len == 8 && d.num_res_centroids == 256; }
-bool sl_two(const VptqLayerDesc& d) { return d.num_res_centroids > 0 && !sl_res256(d); }
-int gemv_sliced_tables(const VptqLayerDesc& d) { return sl_two(d) ? 2 : 1; }
-static bool sl_shape_ok(const VptqLayerDesc& d, bool exact);
-bool gemv_sliced_eligible(const VptqLayerDesc& d, bool exact) {
-  const int T = d.index_bits + d.res_bits;
-  // the reference's roundings: bias in column order (c and r meet in one lane: a residual codebook other than v8's 256-entry
-  // one is gathered from L2 by a side stream of 16-bit indices - ONE layout, bucketed by the main index)
-  if (exact && d.perm != nullptr && (d.bias_permuted == nullptr || (((uintptr_t)d.bias_permuted) & 15) != 0)) return false;
-  return sl_shape_ok(d, exact) && (d.vector_len == 8 || d.vector_len == 16) && d.num_codebooks == 1 && d.outlier_size == 0 &&
-         d.num_centroids >= 16384 && d.num_centroids <= 65536 && sl_pow2(d.num_centroids) && (1 << d.index_bits) == d.num_centroids &&
-         (d.num_res_centroids == 0 || (d.num_res_centroids >= 2 && d.num_res_centroids <= 65536 && sl_pow2(d.num_res_centroids) &&
-                                       (1 << d.res_bits) == d.num_res_centroids)) &&
-         d.weight_scale != nullptr && d.weight_bias != nullptr &&
-         (d.perm == nullptr || d.scale_permuted != nullptr) && (d.group_size % 8) == 0 && d.group_size == d.in_features &&
-         d.group_size <= kSLMaxG16 && T <= 32 && (long long)d.row_words * 32 >= (long long)d.group_size * T &&
-         (((uintptr_t)d.centroids | (uintptr_t)d.res_centroids | (uintptr_t)d.weight_scale | (uintptr_t)d.weight_bias |
-           (uintptr_t)d.perm | (uintptr_t)d.scale_permuted) & 15) == 0;
-}
-
-// bytes of LDS behind the table: f16(s x) of every column (+ 64 padding columns) + 16 floats; the reference's roundings
-// stage x and a word {scale, bias} per column instead: 6 bytes per column; + the 4 KiB residual table of the 256-entry path
-static int sl_window_cols(const VptqLayerDesc& d) { return (d.group_size + kSLWindows * 8 - 1) / (kSLWindows * 8) * 8; }   // (the layout's window width)
-static uint32_t sl_operand_bytes(const VptqLayerDesc& d, bool exact, int tokens = 1, int columns = 0) {
-  return (uint32_t)((columns ? columns : d.group_size) + 64) * (exact ? 4u + 2u * (uint32_t)tokens : 2u) + 64u + (sl_res256(d) ? 4096u : 0u);
-}
-// slices a layout of this layer must have: the slice (table entries / slices, 2 v bytes each) + the staged operands must fit
-// the 160 KiB of LDS.  Folded arithmetic: v = 8: 8 slices up to 14336 columns (14080 with the 256-entry table), else 16;
-// v = 16: 16 slices up to 14336 columns, else 32.  Reference roundings (6 bytes per column): v = 8: 8 slices up to 5376 columns
-// (4704), 16 up to 16288 (15616); v = 16: 16 / 32 at the same widths; wider layers: 0 (not served: gemv_gather)
-int gemv_sliced_slices(const VptqLayerDesc& d, bool exact) {
-  static const int force16 = tune_int("VPTQ_SLICED_SLICES", 0) == 16;   // =16: the larger slice count for every layer (A/B)
-  const int small = d.vector_len == 16 ? 16 : 8;
-  if (!exact) {
-    if (force16 == 1) return 2 * small;
-    return d.group_size <= (sl_res256(d) ? kSLMaxG8Res : kSLMaxG8) ? small : 2 * small;
-  }
-  if (d.num_centroids <= 0 || d.vector_len <= 0) return 0;
-  // VPTQ_SLICED_SLICES=room2 (process-wide opt-in, v = 8): the smaller count only where the slice leaves room for TWO tokens'
-  // operands, so that 2 / 3 tokens take one pass of the one-token kernel (TOK) on 4096-column layers too - they miss that by 0.5 KiB
-  // with 128 KiB slices.  Measured on the Llama-3-8B shapes in v8-k65536-256 (profiles/r05/sliced_exact_slices_16_for_narrow_layers.txt):
-  // 2 sequences 198.6 -> 210.7 tokens/s, 3: 270.6 -> 277.3, ONE: 127.1 -> 125.4 (the layers' own time +5 %) - one token is the
-  // default's business, so the default stays "8 slices wherever one token fits".
-  static const int room2 = [] { const char* e = tune_env("VPTQ_SLICED_SLICES"); return e && strcmp(e, "room2") == 0; }();
-  for (int nsl = (force16 == 1 ? 2 * small : small); nsl <= 2 * small; nsl *= 2) {
-    const uint32_t tab = (uint32_t)(d.num_centroids / nsl) * (uint32_t)d.vector_len * 2u;
-    if ((tab + 15u) / 16u * 16u + sl_operand_bytes(d, true, (nsl == small && room2 == 1 && d.vector_len == 8) ? 2 : 1) <= kSLLdsLimit) return nsl;
-  }
-  return 0;
-}
-// bytes a workgroup of a table with k entries holds: its slice, or (whole != 0) the whole table
-uint32_t sl_tab_bytes(const VptqLayerDesc& d, int k, int whole, bool exact) {
-  const int nsl = gemv_sliced_slices(d, exact);
-  return (uint32_t)(whole || nsl == 0 ? k : k / nsl) * (uint32_t)d.vector_len * 2u;
-}
-// Does every workgroup of table t (0 main, 1 residual-as-second-table) hold the WHOLE table (element words then carry the
-// full index and a row's elements are split into column ranges)?  Only a second table whose slice would be under 16 KiB -
-// copied in 1 KiB pieces by 16 waves, a smaller slice is mostly partial pieces and its lists are short - and only while the
-// whole table still fits beside the staged activations.
-int gemv_sliced_whole_table(const VptqLayerDesc& d, int t) {
-  if (t != 1 || !sl_two(d)) return 0;
-  const uint32_t slice = sl_tab_bytes(d, d.num_res_centroids, 0), whole = sl_tab_bytes(d, d.num_res_centroids, 1);
-  const uint32_t main_slice = sl_tab_bytes(d, d.num_centroids, 0);
-  const uint32_t x_bytes = (uint32_t)(d.group_size + 64) * 2u + 64u;
-  if (d.num_res_centroids < gemv_sliced_slices(d)) return 1;   // (fewer entries than slices: no other way)
-  return slice < 16384u && ((whole > main_slice ? whole : main_slice) + 15u) / 16u * 16u + x_bytes <= kSLLdsLimit ? 1 : 0;
-}
-
-// the tables' parts + the staged operands fit the LDS
-static bool sl_shape_ok(const VptqLayerDesc& d, bool exact) {
-  if (!(d.vector_len == 8 || d.vector_len == 16) || d.group_size <= 0 || d.group_size > kSLMaxG16 || d.num_centroids < 16384) return false;
-  if (exact) return gemv_sliced_slices(d, true) != 0;
-  uint32_t tab = sl_tab_bytes(d, d.num_centroids, 0);
-  if (sl_two(d)) {
-    const uint32_t t1 = sl_tab_bytes(d, d.num_res_centroids, gemv_sliced_whole_table(d, 1));
-    tab = t1 > tab ? t1 : tab;
-  }
-  return (tab + 15u) / 16u * 16u + sl_operand_bytes(d, false) <= kSLLdsLimit;
-}
-
-// one 64-bit accumulator word per output (N x v of them), which must be ZERO before the first launch; every launch leaves
-// them zero.  (Rounds 3-4 kept [tables x slices][N x v] float partial sums + arrival counters here; the size the ABI asks for
-// is still that one - callers' buffers stay valid, tools/sliced_trace.py stamps into the rest.)
-size_t gemv_sliced_workspace_bytes(const VptqLayerDesc& d) {
-  const size_t parts = (size_t)gemv_sliced_slices(d) * (sl_two(d) ? 2 : 1);
-  const size_t partial = (parts * d.num_indices * d.vector_len * sizeof(float) + 255) / 256 * 256;
-  const size_t counters = (((size_t)(d.num_indices + kSLWaves - 1) / kSLWaves) * sizeof(uint32_t) + 255) / 256 * 256;
-  return partial + counters;
-}
-
 template <typename DT>
 static hipError_t launch_sl_dt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
   const int v = D.v, nsl = D.nsl;
@@ -944,274 +836,9 @@ static hipError_t launch_sl_dt(const SlicedDecision& D, const SlicedGroupParams&
   if (nsl == 8) return res ? launch_sl<DT, 8, true, 8, false>(D, P, lds, st) : launch_sl<DT, 8, false, 8, false>(D, P, lds, st);
   return res ? launch_sl<DT, 16, true, 8, false>(D, P, lds, st) : launch_sl<DT, 16, false, 8, false>(D, P, lds, st);
 }
-
-SlicedLayoutSet sl_piece_set(const VptqLayerDesc& d, bool exact) {
-  // (the reference's roundings need c and r in one lane: always ONE layout, bucketed by the main index)
-  SlicedLayoutSet S = {};
-  S.parts = 1, S.tables = !exact && sl_two(d) ? 2 : 1, S.slices = gemv_sliced_slices(d, exact), S.exact = exact;
-  S.whole[1] = S.tables == 2 ? gemv_sliced_whole_table(d, 1) : 0;
-  S.side_bytes = d.num_res_centroids == 0 || S.tables == 2 ? 0 : (sl_res256(d) ? 1 : 2);
-  return S;
+hipError_t launch_sl_one(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st) {
+  return D.f16 ? launch_sl_dt<F16>(D, P, lds, st) : launch_sl_dt<BF16>(D, P, lds, st);
 }
-VptqLayerDesc sl_part_desc(const VptqLayerDesc& d, int parts, int p) {
-  VptqLayerDesc q = d;
-  const int w = d.group_size / parts;
-  q.in_features = q.group_size = w;
-  const size_t off = (size_t)2 * p * w;   // (16-bit column-order tensors)
-  if (q.weight_scale) q.weight_scale = (const char*)q.weight_scale + off;
-  if (q.weight_bias) q.weight_bias = (const char*)q.weight_bias + off;
-  if (q.perm) q.perm = (const uint16_t*)((const char*)q.perm + off);
-  if (q.scale_permuted) q.scale_permuted = (const char*)q.scale_permuted + off;
-  if (q.bias_permuted) q.bias_permuted = (const char*)q.bias_permuted + off;
-  return q;
-}
-// the column parts the reference's roundings are served with: 1 where the layer fits in one piece, else 2 or 3 equal parts of a
-// multiple of 8 columns whose slices' arrivals one accumulator word counts; 0 = none
-static int sl_exact_parts(const VptqLayerDesc& d) {
-  static const int knob = tune_int("VPTQ_SLICED_PARTS", 1);   // (A/B: at least this many parts where the columns divide)
-  const int least = knob > 1 ? knob : 1;
-  const bool whole = gemv_sliced_eligible(d, true);
-  if (whole && least <= 1) return 1;
-  for (int parts = 2; parts <= 3; ++parts) {
-    if (parts < least || d.group_size % (8 * parts) != 0) continue;
-    const VptqLayerDesc q = sl_part_desc(d, parts, 0);
-    if (gemv_sliced_eligible(q, true) && gemv_sliced_slices(q, true) * parts <= 127) return parts;
-  }
-  return least > 1 && whole ? 1 : 0;
-}
-SlicedLayoutSet sl_layout_set(const VptqLayerDesc& d, bool exact) {
-  const int parts = exact ? sl_exact_parts(d) : (gemv_sliced_eligible(d, false) ? 1 : 0);
-  if (parts == 0) return SlicedLayoutSet{};
-  SlicedLayoutSet S = sl_piece_set(parts > 1 ? sl_part_desc(d, parts, 0) : d, exact);   // (equal parts: one answer)
-  S.parts = parts;
-  return S;
-}
-
-unsigned sl_check_layouts(const VptqLayerDesc& d, const SlicedLayoutSet& S, const VptqSlicedLayout* L, int n, unsigned needs,
-                          int rows_per_wave, int* which) {
-  const bool launch = (needs & kSLNeedLaunch) != 0;
-  for (int i = 0; i < n; ++i) {
-    const VptqSlicedLayout& l = L[i];
-    const int t = S.tables == 2 ? i : 0;
-    const bool side = t == 0 && S.side_bytes != 0;
-    const uintptr_t e = (uintptr_t)l.elems, r = (uintptr_t)l.res;
-    unsigned f = 0;
-    if (!l.elems || !l.blocks || !l.first || ((needs & kSLNeedWstart) && !l.wstart)) f |= kSLFaultTensors;
-    if (((needs & kSLNeedRows) && l.n_slices == 0 ? 8 : l.n_slices) != S.slices) f |= kSLFaultSlices;
-    if ((needs & kSLNeedWhole) && l.whole_table != S.whole[t]) f |= kSLFaultWhole;
-    if (needs & kSLNeedBuilt) {
-      if (side != (l.res != nullptr)) f |= kSLFaultRes;
-      const uintptr_t words = (uintptr_t)l.blocks | (uintptr_t)l.first | r | ((needs & kSLNeedWstart) ? (uintptr_t)l.wstart : 0);
-      if ((e & 15) != 0 || (words & 3) != 0 || ((needs & kSLNeedRes8) && S.side_bytes == 2 && (r & 7) != 0)) f |= kSLFaultAlign;
-    } else if (side && (S.exact || launch)) {
-      // (WHO ASKS decides, as it did while each had its own copy: an entry holds the exact arithmetic's stream, uint8 or uint16, to "set,
-      // at an even address" and does not look at a folded one; the launch behind it needs every stream set and the uint16 one even)
-      if (!l.res || ((r & 1) != 0 && (!launch || S.side_bytes == 2))) f |= kSLFaultRes;
-    }
-    if ((needs & kSLNeedRows) && (l.rows_per_wave < 1 || l.rows_per_wave > kSLMaxRowsPerWave ||
-                                  (rows_per_wave != 0 && l.rows_per_wave != rows_per_wave)))
-      f |= kSLFaultRows;
-    if (launch) {
-      if (l.elems_per_lane != 0 && l.elems_per_lane != 1) f |= kSLFaultElemsPerLane;
-      if ((e & 3) != 0) f |= kSLFaultAlign;
-      // (a sliced table needs at least one entry per slice; whole = every workgroup of the table holds all of it)
-      if (!l.whole_table && (t ? d.num_res_centroids : d.num_centroids) < S.slices) f |= kSLFaultFewEntries;
-    }
-    if (f && which) *which = i;
-    if (f) return f;
-  }
-  return 0;
-}
-bool sl_parts_share(const VptqLayerDesc* d, void* const* y, void* const* ws, int n) {
-  for (int i = 1; i < n; ++i)
-    if (y[i] != y[0] || ws[i] != ws[0] || d[i].out_features != d[0].out_features || d[i].num_indices != d[0].num_indices ||
-        d[i].bias != d[0].bias || d[i].in_features != d[0].in_features)
-      return false;
-  return true;
-}
-
-// L: one layout (residual none / the 256-entry path of v = 8) or TWO consecutive ones (any other residual codebook: [0]
-// bucketed by the main index, [1] by the residual index).  (c + r) f16(s x) = c f16(s x) + r f16(s x): the residual table's
-// (slice, row block) workgroups run beside the main table's in the SAME launch and meet them in the output's accumulator
-// word - two launches, one per table, cost a second boundary, a second epilogue and half the workgroups in flight (8192^2: 27.2 us
-// against 21.2; 4096^2: 17.8 against 12.0)
-static hipError_t sl_fill(const VptqLayerDesc& d, const SlicedLayoutSet& S, const VptqSlicedLayout* L, const void* x, void* y, int flags,
-                          void* ws, SlicedParams& P, uint32_t& lds, int tokens = 1) {
-  const bool exact = S.exact;
-  if (tokens != 1 && !gemv_sliced_exact_tokens_ok(d, tokens)) return hipErrorInvalidValue;
-  const bool res = S.side_bytes == 1, rg = S.side_bytes == 2, two = S.tables == 2;
-  if (S.slices == 0 || sl_check_layouts(d, S, L, S.tables, kSLNeedRows | kSLNeedWhole | kSLNeedLaunch, L[0].rows_per_wave) != 0 ||
-      !ws || (((uintptr_t)x) & 15) != 0)
-    return hipErrorInvalidValue;
-  P = SlicedParams{};
-  P.elems = (const uint32_t*)L[0].elems;
-  P.res = (res || rg) ? (const uint8_t*)L[0].res : nullptr;   // (rg: uint16 per element)
-  P.rcent = (res || rg) ? (const uint32_t*)d.res_centroids : nullptr;
-  P.blocks = (const int32_t*)L[0].blocks;
-  P.first = (const int32_t*)L[0].first;
-  P.cent = (const uint32_t*)d.centroids;
-  P.tab0 = sl_tab_bytes(d, d.num_centroids, L[0].whole_table, exact);
-  P.stride0 = L[0].whole_table ? 0u : P.tab0;
-  if (two) {
-    P.elems2 = (const uint32_t*)L[1].elems;
-    P.blocks2 = (const int32_t*)L[1].blocks;
-    P.first2 = (const int32_t*)L[1].first;
-    P.cent2 = (const uint32_t*)d.res_centroids;
-    P.tab1 = sl_tab_bytes(d, d.num_res_centroids, L[1].whole_table);
-    P.stride1 = L[1].whole_table ? 0u : P.tab1;
-  }
-  P.x_off = ((P.tab0 > P.tab1 ? P.tab0 : P.tab1) + 15u) & ~15u;
-  P.x = (const uint16_t*)x;
-  P.scale = (const uint16_t*)(d.perm ? d.scale_permuted : d.weight_scale);
-  P.wbias = (const uint16_t*)d.weight_bias;
-  P.cbias = (const uint16_t*)(d.perm ? d.bias_permuted : d.weight_bias);
-  P.perm = (const uint16_t*)d.perm;
-  P.bias = (const uint16_t*)d.bias;
-  P.partial = (float*)ws;
-  P.y = y;
-  P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features;
-  P.rows_per_wave = L[0].rows_per_wave;
-  const int rows_per_wg = kSLWaves * L[0].rows_per_wave;
-  P.n_rowblocks = (d.num_indices + rows_per_wg - 1) / rows_per_wg;
-  P.out_f32 = (flags & VPTQ_GEMV_OUT_F32) ? 1 : 0;
-  P.x_stride = d.in_features; P.y_stride = d.out_features; P.acc_stride = d.num_indices * d.vector_len;
-  P.wparts = 1;
-  if (tokens != 1) {
-    P.wparts = gemv_sliced_exact_tokens_parts(d, tokens);
-    if (P.wparts > 1) {
-      if (!L[0].wstart) return hipErrorInvalidValue;
-      P.wstart = (const int32_t*)L[0].wstart;
-      P.wcols = sl_window_cols(d);
-      P.wstage = (kSLWindows / P.wparts) * P.wcols < d.group_size ? (kSLWindows / P.wparts) * P.wcols : d.group_size;
-      // (one round of workgroups: the rows per wave grow with the parts)
-      const int rpw = L[0].rows_per_wave * P.wparts;
-      P.rows_per_wave = rpw > kSLMaxRowsPerWave ? kSLMaxRowsPerWave : rpw;
-      const int rows_per_wg2 = kSLWaves * P.rows_per_wave;
-      P.n_rowblocks = (d.num_indices + rows_per_wg2 - 1) / rows_per_wg2;
-    }
-  }
-  lds = P.x_off + sl_operand_bytes(d, exact, tokens, P.wparts > 1 ? P.wstage : 0);
-  return lds > kSLLdsLimit ? hipErrorInvalidValue : hipSuccess;
-}
-
-// n <= kSLMaxGroup layers of ONE format (vector length, slices, residual kind, dtype) and one input width reading the same x:
-// layouts = the layers' layout structs one after the other (1 or 2 each); one launch
-bool gemv_sliced_groupable(const VptqLayerDesc* d, int n, bool exact) {
-  if (n < 1 || n > kSLMaxGroup) return false;
-  for (int i = 0; i < n; ++i) {
-    if (!gemv_sliced_eligible(d[i], exact)) return false;
-    if (d[i].dtype != d[0].dtype || d[i].vector_len != d[0].vector_len || d[i].group_size != d[0].group_size ||
-        gemv_sliced_slices(d[i], exact) != gemv_sliced_slices(d[0], exact) || sl_res256(d[i]) != sl_res256(d[0]) || sl_two(d[i]) != sl_two(d[0]))
-      return false;
-  }
-  return true;
-}
-// 2 / 3 tokens in one pass of the exact kernel (TOK): one-table formats whose slice + (2 tokens + 4) bytes per column fit the LDS.
-// Measured (profiles/r05/sliced_exact_tokens_one_pass.txt) where the 16 (v = 16: 32) slice layouts are: wider than ~5000 columns.
-// ... in how many WINDOW PARTS (workgroups per (slice, row block), each staging its column windows alone): 1 where all columns
-// fit, else - v = 8, one table; the layout must carry `wstart` - 2 or 4; 0 = not served.  VPTQ_SLICED_WINDOW_PARTS=0: never more than 1 (A/B)
-int gemv_sliced_exact_tokens_parts(const VptqLayerDesc& d, int tokens) {
-  if (tokens < 2 || tokens > (d.vector_len == 16 ? 2 : 3) || !gemv_sliced_eligible(d, true) || (sl_two(d) && d.vector_len != 8)) return 0;
-  const int nsl = gemv_sliced_slices(d, true);
-  if (nsl == 0) return 0;
-  const uint32_t tab = (sl_tab_bytes(d, d.num_centroids, 0, true) + 15u) / 16u * 16u;
-  if (tab + sl_operand_bytes(d, true, tokens) <= kSLLdsLimit) return 1;
-  static const bool on = [] { const char* e = tune_env("VPTQ_SLICED_WINDOW_PARTS"); return !(e && e[0] == '0'); }();
-  if (!on || d.vector_len != 8 || sl_two(d)) return 0;
-  const int wc = sl_window_cols(d);
-  for (int wparts = 2; wparts <= kSLWindows; wparts *= 2) {
-    const int wmax = (kSLWindows / wparts) * wc < d.group_size ? (kSLWindows / wparts) * wc : d.group_size;
-    if (tab + sl_operand_bytes(d, true, tokens, wmax) <= kSLLdsLimit && nsl * wparts <= 127) return wparts;
-  }
-  return 0;
-}
-bool gemv_sliced_exact_tokens_ok(const VptqLayerDesc& d, int tokens) { return gemv_sliced_exact_tokens_parts(d, tokens) >= 1; }
-// accumulator words of such a launch: [tokens][N x v], zero before the first launch, left zero by every launch
-size_t gemv_sliced_exact_tokens_workspace_bytes(const VptqLayerDesc& d, int tokens) {
-  return ((size_t)tokens * d.num_indices * d.vector_len * sizeof(unsigned long long) + 255) / 256 * 256;
-}
-// VPTQ_GEMV_COLUMN_PARTS: the n "layers" are the column ranges [i G / n, (i + 1) G / n) of ONE layer too wide for the LDS (28672
-// columns in the reference's roundings: 6 bytes per column) - descriptors with in_features = group_size = G / n and the column
-// order tensors (scale, bias, permutation) advanced to the part's first column, a layout per part built from those columns of
-// the index matrix; x is the WHOLE activation (part i reads it from column i G / n on, or through its slice of the permutation),
-// y and the accumulator words are shared: an output is complete after n x slices arrivals.
-// ---- decide, then launch (as gemv_k256.hip): sl_decide says what one call is - the parameter blocks, the LDS, the instantiation's
-// template arguments and the launch shape; launch_gemv_sliced_group launches exactly that and gemv_sliced_instance prints it, so the
-// two cannot disagree.  Nothing is dereferenced: the query passes placeholder x / y / workspace pointers.
-static hipError_t sl_decide(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y, int flags,
-                            void* const* ws, int tokens, const float* corr, SlicedGroupParams& GP, uint32_t& lds, SlicedDecision& D) {
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  const bool parts = (flags & VPTQ_GEMV_COLUMN_PARTS) != 0;
-  if (!gemv_sliced_groupable(d, n, exact) || (tokens != 1 && !exact)) return hipErrorInvalidValue;
-  // (the folded form stages 32768 columns in one piece: no parts needed)
-  if (parts && (!exact || !sl_parts_share(d, y, ws, n))) return hipErrorInvalidValue;
-  GP = SlicedGroupParams{};
-  GP.n = n;
-  lds = 0;
-  const SlicedLayoutSet S0 = sl_piece_set(d[0], exact);   // (one format: one table and slice count for every member)
-  const int tables = S0.tables, nsl = S0.slices, nslt = nsl * tables;
-  bool perm = false;
-  for (int i = 0; i < n; ++i) {
-    uint32_t l = 0;
-    // (a part without a permutation reads its own columns of x; with one, its slice of `perm` indexes the whole activation)
-    const void* const xi = (parts && d[i].perm == nullptr) ? (const void*)((const uint16_t*)x + (size_t)i * d[i].in_features) : x;
-    const hipError_t e = sl_fill(d[i], i ? sl_piece_set(d[i], exact) : S0, L + (size_t)i * tables, xi, y[i], flags, ws[i], GP.p[i], l, tokens);
-    if (e != hipSuccess) return e;
-    if (parts) GP.p[i].x_stride = n * d[i].in_features;   // (tokens of the WHOLE activation: a part's columns lie one row of all parts apart)
-    GP.p[i].corr = (n == 1 && tokens == 1 && !exact) ? corr : nullptr;   // (selective roundings: one layer, one token, folded form)
-    lds = l > lds ? l : lds;
-    GP.start[i + 1] = GP.start[i] + nslt * GP.p[i].wparts * GP.p[i].n_rowblocks;
-    if (GP.p[i].wparts != GP.p[0].wparts) return hipErrorInvalidValue;   // (one input width: one answer)
-    perm = perm || d[i].perm != nullptr;
-  }
-  for (int i = n; i < kSLMaxGroup; ++i) GP.start[i + 1] = GP.start[n];
-  GP.arrivals = nslt * (parts ? n : 1) * GP.p[0].wparts;
-  if (GP.arrivals > 127) return hipErrorInvalidValue;   // (7 bits of the accumulator word count them)
-  D = SlicedDecision{};
-  D.f16 = d[0].dtype == VPTQ_DTYPE_F16;
-  D.nsl = nsl; D.v = d[0].vector_len; D.tok = tokens;
-  D.res = sl_res256(d[0]); D.two = !exact && sl_two(d[0]); D.ex = exact; D.rg = exact && sl_two(d[0]);
-  D.wpt = tokens != 1 && GP.p[0].wparts > 1;
-  D.wparts = GP.p[0].wparts; D.parts = parts ? n : 1; D.n = parts ? 1 : n;
-  D.rpw = GP.p[0].rows_per_wave; D.arrivals = GP.arrivals;
-  D.whole1 = tables == 2 ? L[1].whole_table : 0; D.side = S0.side_bytes;
-  D.perm = perm; D.corr = GP.p[0].corr != nullptr;
-  return hipSuccess;
-}
-hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
-                                    int flags, void* const* ws, hipStream_t st, int tokens, const float* corr) {
-  SlicedGroupParams GP;
-  SlicedDecision D;
-  uint32_t lds = 0;
-  if (const hipError_t e = sl_decide(d, L, n, x, y, flags, ws, tokens, corr, GP, lds, D); e != hipSuccess) return e;
-  if (D.wpt) return launch_sl_tokens_wpt(D, GP, lds, st);
-  if (D.tok != 1) return launch_sl_tokens(D, GP, lds, st);
-  return D.f16 ? launch_sl_dt<F16>(D, GP, lds, st) : launch_sl_dt<BF16>(D, GP, lds, st);
-}
-// the instantiation launch_gemv_sliced_group would launch for (d, L, n, tokens, flags), as text; corr: with the hot blocks' products of
-// the selective pre-pass.  0, -1: no launch, -2: buffer too small
-int gemv_sliced_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, int flags, bool corr, char* buf, size_t bytes) {
-  if (n < 1 || n > kSLMaxGroup) return -1;
-  // placeholders: aligned, never dereferenced (column parts share one y and one workspace, as the call requires)
-  void* const some = (void*)(uintptr_t)4096;
-  void* ys[kSLMaxGroup] = {some, some, some};
-  void* wss[kSLMaxGroup] = {some, some, some};
-  SlicedGroupParams GP;
-  SlicedDecision D;
-  uint32_t lds = 0;
-  if (sl_decide(d, L, n, some, ys, flags, wss, tokens, corr ? (const float*)some : nullptr, GP, lds, D) != hipSuccess) return -1;
-  Text t = {buf, bytes, 0, true};
-  t.add("gemv_sliced dt=%s nsl=%d res=%d v=%d two=%d ex=%d rg=%d tok=%d wpt=%d wparts=%d parts=%d n=%d rpw=%d "
-        "arrivals=%d whole1=%d side=%d perm=%d corr=%d", dt_text(D.f16), D.nsl, (int)D.res, D.v, (int)D.two, (int)D.ex,
-        (int)D.rg, D.tok, (int)D.wpt, D.wparts, D.parts, D.n, D.rpw, D.arrivals, D.whole1, D.side, (int)D.perm, (int)D.corr);
-  return text_done(t);
-}
-hipError_t launch_gemv_sliced(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int flags,
-                              void* ws, hipStream_t st, const float* corr) {
-  void* const ys[1] = {y};
-  void* const wss[1] = {ws};
-  return launch_gemv_sliced_group(&d, L, 1, x, ys, flags, wss, st, 1, corr);
-}
-#endif   // part 1
+#endif
 
 }  // namespace vptq

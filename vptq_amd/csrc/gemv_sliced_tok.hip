@@ -29,8 +29,6 @@
 
 namespace vptq {
 
-constexpr int kSTWindows = VPTQ_SLICED_WINDOWS;
-constexpr int kSTRegRows = 4;   // rows per wave whose sums (4 registers each in matrix-pipe mode) are kept in registers
 // element blocks in flight per wave (4 where a lane carries 64 sums: v = 16 with 4 tokens would spill at 8)
 // (4 / 8 / 16 for every instantiation: the same times, profiles/r04/sliced_tokens_queue_depth.txt)
 constexpr int kSTQueue = 8;
@@ -42,29 +40,7 @@ template <int NV> constexpr int st_queue() { return NV >= 64 ? 4 : kSTQueue; }
 #define VPTQ_ST_ABLATE 0
 #endif
 
-struct SlicedTokParams {
-  SlicedParams p;            // as for one token; x / y: token 0, rows_per_wave / n_rowblocks: this launch's
-  const int32_t* wstart;     // [slices][N][kSTWindows + 1]
-  const int32_t* wstart2;    // second table
-  const uint16_t* xs;        // the activations in COLUMN order: p.x, or the pre-pass's x[perm] (p.scale is in column order too)
-  int tokens;                // 2 .. TOK
-  int phases;                // 1, 2 or 4
-  int wcols;                 // columns per layout window
-  int x_stride, x_in_stride, y_stride;    // elements between two tokens of xs / p.x / y
-  uint32_t bd_off, res_off, sum_off;   // LDS: sum b x parts [TOK][16 waves] floats; 256-entry residual table; row sums
-  uint32_t sb_off;           // EX: LDS, per staged column 8 bytes {s, b, s, b} (and the zero column's zeros)
-  int reg_sums;              // (matrix-pipe mode, <= kSTRegRows rows per wave) the rows' sums stay in registers: no LDS for them
-};
-
-// Up to kSTMaxGroup layers that read the SAME activations (q / k / v, gate / up) in one launch, as in gemv_sliced.hip: layer l
-// owns the workgroups [start[l], start[l + 1]); the fixed part of a launch is paid once.
-constexpr int kSTMaxGroup = 3;
-struct SlicedTokGroupParams {
-  int n;
-  int start[kSTMaxGroup + 1];
-  SlicedTokParams p[kSTMaxGroup];
-};
-
+// (the parameter blocks SlicedTokParams / SlicedTokGroupParams: sliced.h)
 // EX: the reference's roundings (vptq/ops/quant_gemm.py:121,155-156): every weight rebuilt as f16(f16(f16(c + r) s) + b) before it
 // meets the RAW activations - matrix-pipe mode only (4 / 8 token slots), one table (+ the 256-entry residual table): the
 // transposing gather that hands a lane component m of four elements' entries hands it the four elements' scales (m even) or biases
@@ -747,9 +723,10 @@ __global__ __launch_bounds__(kSLThreads) void gemv_sliced_tok_kernel(const Slice
   }
 }
 
-// ---- launchers (every part of the build: the file is compiled four times, VPTQ_ST_PART = 1: 2 and 4 token slots + the host
-// side, 2: the 8-slot instantiations, 3 / 4: 4 / 8 slots with the reference's roundings - minutes of compile time as one
-// translation unit)
+// ---- launchers.  The file is compiled four times, a share of the instantiations each: VPTQ_ST_PART = 1: 2 and 4 token slots, 2: the
+// 8-slot instantiations, 3 / 4: 4 / 8 slots with the reference's roundings - minutes of compile time as one translation unit (not
+// defined: all of them in one).  Every part's dispatcher is declared in sliced.h and called from sliced_host.hip, where the family's
+// host side - st_plan, st_decide and the rules they read - lives.
 template <typename DT, int NSL, bool RES, int V, bool TWO, int TOK, bool EX = false>
 static hipError_t launch_st(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
   // this instantiation is the one the decision names (st_decide)
@@ -781,8 +758,6 @@ static hipError_t launch_st_ex(const SlicedTokDecision& D, const SlicedTokGroupP
   if (nsl == 8) return res ? launch_st<DT, 8, true, 8, false, TOK, true>(D, P, grid, lds, st) : launch_st<DT, 8, false, 8, false, TOK, true>(D, P, grid, lds, st);
   return res ? launch_st<DT, 16, true, 8, false, TOK, true>(D, P, grid, lds, st) : launch_st<DT, 16, false, 8, false, TOK, true>(D, P, grid, lds, st);
 }
-hipError_t launch_st_ex4(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
-hipError_t launch_st_ex8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
 #if !defined(VPTQ_ST_PART) || VPTQ_ST_PART == 3
 hipError_t launch_st_ex4(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
   return D.f16 ? launch_st_ex<F16, 4>(D, P, grid, lds, st) : launch_st_ex<BF16, 4>(D, P, grid, lds, st);
@@ -793,286 +768,16 @@ hipError_t launch_st_ex8(const SlicedTokDecision& D, const SlicedTokGroupParams&
   return D.f16 ? launch_st_ex<F16, 8>(D, P, grid, lds, st) : launch_st_ex<BF16, 8>(D, P, grid, lds, st);
 }
 #endif
-
-hipError_t launch_st_tok8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
 #if !defined(VPTQ_ST_PART) || VPTQ_ST_PART == 2
 hipError_t launch_st_tok8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
   return D.f16 ? launch_st_dt<F16, 8>(D, P, grid, lds, st) : launch_st_dt<BF16, 8>(D, P, grid, lds, st);
 }
 #endif
-
 #if !defined(VPTQ_ST_PART) || VPTQ_ST_PART == 1
-// ---- host side -------------------------------------------------------------------
-static bool st_exact_ok(const VptqLayerDesc& d) { return !sl_two(d) && gemv_sliced_eligible(d, true); }
-static size_t st_partial_bytes(const VptqLayerDesc& d, int tokens, bool exact) {
-  const SlicedLayoutSet S = sl_piece_set(d, exact);
-  const size_t parts = (size_t)S.slices * S.tables;
-  return ((size_t)tokens * parts * d.num_indices * d.vector_len * sizeof(float) + 255) / 256 * 256;
+hipError_t launch_st_tok24(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st) {
+  if (D.f16) return D.tok == 2 ? launch_st_dt<F16, 2>(D, P, grid, lds, st) : launch_st_dt<F16, 4>(D, P, grid, lds, st);
+  return D.tok == 2 ? launch_st_dt<BF16, 2>(D, P, grid, lds, st) : launch_st_dt<BF16, 4>(D, P, grid, lds, st);
 }
-static size_t st_counter_bytes(const VptqLayerDesc& d) {
-  return (((size_t)(d.num_indices + kSLWaves - 1) / kSLWaves) * sizeof(uint32_t) + 255) / 256 * 256;
-}
-// ... + (a layer with an input permutation) x[perm] of every token: the kernel stages activations in COLUMN order and a load
-// the compiler can see inside its stream loop costs it the counted waits, so the gather is a pre-pass (gemv_k256c.hip:
-// permute_x_kernel, one workgroup per 2048 columns and token)
-static size_t st_perm_bytes(const VptqLayerDesc& d, int tokens) { return (size_t)tokens * gemv_k256c_perm_bytes(d); }
-// (one size for both arithmetics: the exact layouts may have twice the slices)
-static size_t st_partial_bytes_max(const VptqLayerDesc& d, int tokens) {
-  const size_t a = gemv_sliced_eligible(d) ? st_partial_bytes(d, tokens, false) : 0, b = st_exact_ok(d) ? st_partial_bytes(d, tokens, true) : 0;
-  return a > b ? a : b;
-}
-// ... and, in front of the partial sums (a fixed place whatever the token count), the accumulator words of the ONE-PASS route:
-// 2 / 3 tokens in the reference's roundings through the one-token kernel (gemv_sliced.hip, TOK), zero between launches
-static size_t st_acc_bytes(const VptqLayerDesc& d) { return gemv_sliced_eligible(d, true) ? gemv_sliced_exact_tokens_workspace_bytes(d, 3) : 0; }
-size_t gemv_sliced_tok_workspace_bytes(const VptqLayerDesc& d, int tokens) {
-  return st_counter_bytes(d) + st_acc_bytes(d) + st_partial_bytes_max(d, tokens) + st_perm_bytes(d, tokens);
-}
-// VPTQ_SLICED_ONE_PASS=0: 2 / 3 exact tokens through the column-phase kernel as well (A/B runs)
-static bool st_one_pass(const VptqLayerDesc& d, int tokens, bool exact) {
-  static const bool on = [] { const char* e = tune_env("VPTQ_SLICED_ONE_PASS"); return !(e && atoi(e) == 0 && e[0] == '0'); }();
-  return exact && on && gemv_sliced_exact_tokens_ok(d, tokens);
-}
-
-// rows per wave: one round of workgroups (slices x tables x row blocks of 16 waves ~ the CUs)
-static int st_rows_per_wave(const VptqLayerDesc& d, bool exact) {
-  const SlicedLayoutSet S = sl_piece_set(d, exact);
-  const long long nslt = (long long)S.slices * S.tables;
-  long long r = ((long long)d.num_indices * nslt + kSLWaves * 256 - 1) / (kSLWaves * 256);
-  return (int)(r < 1 ? 1 : r > kSLMaxRowsPerWave ? kSLMaxRowsPerWave : r);
-}
-
-struct StPlan { int tok, phases, rpw, reg_sums; uint32_t x_off, bd_off, res_off, sum_off, sb_off, lds; };
-// the template's token count (2 or 4), the fewest phases whose activations fit beside the table, and the LDS map.  The rows'
-// sums (16 waves x rows per wave x tokens x v floats) must fit too: where one round of workgroups does not leave room for
-// them even with 4 phases (v = 16 with two tables: 64 floats per row), fewer rows per wave - more workgroups - do.
-static bool st_plan(const VptqLayerDesc& d, const VptqSlicedLayout* L, int tokens, bool exact, StPlan& pl, int rpw0 = 0) {
-  if (tokens < 2 || tokens > 8) return false;
-  const bool res = sl_res256(d), two = sl_two(d);
-  if (exact && !st_exact_ok(d)) return false;
-  static const bool tok4 = tune_flag("VPTQ_SLICED_TOK4");   // =1: 2 tokens through the 4-slot (matrix-pipe) kernel too (A/B runs)
-  pl.tok = tokens > 4 ? 8 : (tokens == 2 && !tok4 && !exact) ? 2 : 4;   // (the reference's roundings: matrix-pipe mode only)
-  uint32_t tab = sl_tab_bytes(d, d.num_centroids, 0, exact);
-  if (two) {
-    const uint32_t t1 = sl_tab_bytes(d, d.num_res_centroids, L[1].whole_table);
-    tab = t1 > tab ? t1 : tab;
-  }
-  pl.x_off = (tab + 15u) & ~15u;
-  const int G = d.group_size;
-  const int wcols = (G + kSTWindows * 8 - 1) / (kSTWindows * 8) * 8;
-  static const int phases_knob = tune_int("VPTQ_SLICED_MIN_PHASES", 1);   // =2 / 4: more phases than the LDS asks for (A/B runs)
-  const int min_phases = (phases_knob == 2 || phases_knob == 4) ? phases_knob : 1;
-  static const bool no_reg_sums = tune_flag("VPTQ_SLICED_LDS_SUMS");  // =1: the rows' sums in LDS in every mode (A/B runs)
-  for (int rpw = rpw0 > 0 ? rpw0 : st_rows_per_wave(d, exact); rpw >= 1; rpw = rpw > 1 ? (rpw + 1) / 2 : 0) {
-    for (int phases = min_phases; phases <= kSTWindows; phases *= 2) {
-      const int wmax = (kSTWindows / phases) * wcols < G ? (kSTWindows / phases) * wcols : G;   // columns of the widest phase
-      uint32_t o = pl.x_off + (uint32_t)(wmax + 8) * (uint32_t)pl.tok * 2u;
-      o = (o + 15u) & ~15u;
-      pl.sb_off = o; o += exact ? (uint32_t)(wmax + 8) * 8u : 0u;
-      pl.bd_off = o; o += (uint32_t)pl.tok * kSLWaves * 4u;
-      pl.res_off = o; o += res ? 4096u : 0u;
-      const int reg_sums = pl.tok >= 4 && rpw <= kSTRegRows && !no_reg_sums;   // (matrix-pipe mode: 4 registers per row)
-      pl.sum_off = o; o += reg_sums ? 0u : (uint32_t)kSLWaves * (uint32_t)rpw * (uint32_t)(pl.tok * d.vector_len) * 4u;
-      if (o <= kSLLdsLimit) { pl.phases = phases; pl.rpw = rpw; pl.reg_sums = reg_sums; pl.lds = o; return true; }
-    }
-  }
-  return false;
-}
-
-int gemv_sliced_tok_one_pass_parts(const VptqLayerDesc& d, int tokens, bool exact) { return st_one_pass(d, tokens, exact) ? gemv_sliced_exact_tokens_parts(d, tokens) : 0; }
-bool gemv_sliced_tok_eligible(const VptqLayerDesc& d, const VptqSlicedLayout* L, int tokens, bool exact) {
-  StPlan pl;
-  if (!L) return false;
-  // (ONE pass of the one-token kernel: also the two-table formats of v = 8, their residual entries gathered once for all tokens)
-  // (no column windows needed - unless the columns are taken in window parts)
-  if (st_one_pass(d, tokens, exact))
-    return L[0].n_slices == gemv_sliced_slices(d, true) && (!sl_two(d) || L[0].res) && (gemv_sliced_exact_tokens_parts(d, tokens) == 1 || L[0].wstart);
-  if (!(exact ? st_exact_ok(d) : gemv_sliced_eligible(d))) return false;
-  const int n = exact ? 1 : gemv_sliced_tables(d);
-  for (int i = 0; i < n; ++i)
-    if (!L[i].wstart || L[i].n_slices != gemv_sliced_slices(d, exact)) return false;   // (the arithmetic's own slice count)
-  return st_plan(d, L, tokens, exact, pl);
-}
-
-// one layer's parameter block (its permutation pre-pass is queued into perm_*: one launch for the whole group)
-struct StPermJobs { VptqLayerDesc d[8 * kSTMaxGroup]; const void* xin[8 * kSTMaxGroup]; void* xout[8 * kSTMaxGroup]; int n; };
-static hipError_t st_fill(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int tokens, int flags, void* ws,
-                          int rpw0, SlicedTokParams& TP, StPlan& pl, StPermJobs& jobs) {
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  if (!gemv_sliced_tok_eligible(d, L, tokens, exact) || !st_plan(d, L, tokens, exact, pl, rpw0)) return hipErrorInvalidValue;
-  const SlicedLayoutSet S = sl_piece_set(d, exact);
-  const bool res = S.side_bytes == 1, two = S.tables == 2;
-  // (the kernel takes its rows per wave from the plan: the structs' own need not agree)
-  if (sl_check_layouts(d, S, L, S.tables, kSLNeedRows | kSLNeedWhole | kSLNeedLaunch) != 0 || !ws || (((uintptr_t)x) & 15) != 0 || (d.in_features % 8) != 0)
-    return hipErrorInvalidValue;
-  TP = SlicedTokParams{};
-  SlicedParams& P = TP.p;
-  P.elems = (const uint32_t*)L[0].elems;
-  P.res = res ? (const uint8_t*)L[0].res : nullptr;
-  P.rcent = res ? (const uint32_t*)d.res_centroids : nullptr;
-  P.blocks = (const int32_t*)L[0].blocks;
-  P.first = (const int32_t*)L[0].first;
-  P.cent = (const uint32_t*)d.centroids;
-  P.tab0 = sl_tab_bytes(d, d.num_centroids, 0, exact);
-  P.stride0 = P.tab0;
-  TP.wstart = (const int32_t*)L[0].wstart;
-  if (two) {
-    P.elems2 = (const uint32_t*)L[1].elems;
-    P.blocks2 = (const int32_t*)L[1].blocks;
-    P.first2 = (const int32_t*)L[1].first;
-    P.cent2 = (const uint32_t*)d.res_centroids;
-    P.tab1 = sl_tab_bytes(d, d.num_res_centroids, L[1].whole_table);
-    P.stride1 = L[1].whole_table ? 0u : P.tab1;
-    TP.wstart2 = (const int32_t*)L[1].wstart;
-  }
-  P.x_off = pl.x_off;
-  P.x = (const uint16_t*)x;
-  P.scale = (const uint16_t*)(d.perm ? d.scale_permuted : d.weight_scale);
-  P.wbias = (const uint16_t*)d.weight_bias;
-  P.cbias = (const uint16_t*)(d.perm ? d.bias_permuted : d.weight_bias);
-  P.perm = nullptr;
-  TP.xs = (const uint16_t*)x;
-  TP.x_stride = d.in_features;
-  if (d.perm) {
-    char* const base = (char*)ws + st_counter_bytes(d) + st_acc_bytes(d) + st_partial_bytes_max(d, tokens);
-    for (int t = 0; t < tokens; ++t) {
-      jobs.d[jobs.n] = d;
-      jobs.xin[jobs.n] = (const uint16_t*)x + (size_t)t * d.in_features;
-      jobs.xout[jobs.n] = base + (size_t)t * gemv_k256c_perm_bytes(d);
-      ++jobs.n;
-    }
-    TP.xs = (const uint16_t*)base;
-    TP.x_stride = (int)(gemv_k256c_perm_bytes(d) / 2);
-  }
-  P.bias = (const uint16_t*)d.bias;
-  // (the arrival counters FIRST: a workspace sized - and zeroed once - for 4 tokens serves 2 and 3 as well)
-  P.arrived = (uint32_t*)ws;
-  P.partial = (float*)((char*)ws + st_counter_bytes(d) + st_acc_bytes(d));
-  P.y = y;
-  P.N = d.num_indices; P.G = d.group_size; P.O = d.out_features;
-  P.rows_per_wave = pl.rpw;
-  const int rows_per_wg = kSLWaves * pl.rpw;
-  P.n_rowblocks = (d.num_indices + rows_per_wg - 1) / rows_per_wg;
-  P.out_f32 = (flags & VPTQ_GEMV_OUT_F32) ? 1 : 0;
-  TP.tokens = tokens;
-  TP.phases = pl.phases;
-  TP.wcols = (d.group_size + kSTWindows * 8 - 1) / (kSTWindows * 8) * 8;
-  TP.x_in_stride = d.in_features;
-  TP.y_stride = d.out_features;
-  TP.bd_off = pl.bd_off; TP.res_off = pl.res_off; TP.sum_off = pl.sum_off; TP.sb_off = pl.sb_off;
-  TP.reg_sums = pl.reg_sums;
-  return hipSuccess;
-}
-
-// n <= kSTMaxGroup layers of ONE format (vector length, slices, residual kind, dtype) and one input width reading the same x
-bool gemv_sliced_tok_groupable(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, bool exact) {
-  if (n < 1 || n > kSTMaxGroup || !gemv_sliced_groupable(d, n, exact)) return false;
-  const int tables = exact ? 1 : gemv_sliced_tables(d[0]);
-  for (int i = 0; i < n; ++i)
-    if (!gemv_sliced_tok_eligible(d[i], L + (size_t)i * tables, tokens, exact)) return false;
-  return true;
-}
-
-// ---- decide, then launch (as gemv_sliced.hip:sl_decide): what one call is.  one_pass: the call is a launch of the one-token kernel over
-// the accumulator words acc[] (2 / 3 tokens in the reference's roundings) - nothing else is filled; else the column-phase kernel's
-// parameter blocks, the permutation pre-pass's jobs, grid, LDS and the instantiation.  Nothing is dereferenced.
-static hipError_t st_decide(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y, int tokens, int flags,
-                            void* const* ws, bool& one_pass, void** acc, SlicedTokGroupParams& GP, StPermJobs& jobs, uint32_t& lds,
-                            SlicedTokDecision& D) {
-  const bool exact = (flags & VPTQ_GEMV_EXACT) != 0;
-  if (!gemv_sliced_tok_groupable(d, L, n, tokens, exact)) return hipErrorInvalidValue;
-  {   // 2 / 3 tokens in the reference's roundings: ONE pass of the one-token kernel where every member's operands fit its LDS
-    one_pass = true;
-    for (int i = 0; i < n; ++i) one_pass = one_pass && st_one_pass(d[i], tokens, exact);
-    if (one_pass) {
-      for (int i = 0; i < n; ++i) acc[i] = (char*)ws[i] + st_counter_bytes(d[i]);
-      return hipSuccess;
-    }
-    // (column parts of one layer share their output and accumulator words: the one pass only - the column-phase kernel below keeps
-    // partial sums and counters per layer)
-    if (flags & VPTQ_GEMV_COLUMN_PARTS) return hipErrorInvalidValue;
-  }
-  GP = SlicedTokGroupParams{};
-  GP.n = n;
-  jobs.n = 0;
-  const SlicedLayoutSet S0 = sl_piece_set(d[0], exact);
-  const int tables = S0.tables, nsl = S0.slices, nslt = nsl * tables;
-  // rows per wave: one round of workgroups over ALL members
-  long long rows = 0;
-  for (int i = 0; i < n; ++i) rows += d[i].num_indices;
-  long long r0 = (rows * nslt + kSLWaves * 256 - 1) / (kSLWaves * 256);
-  int rpw0 = n == 1 ? 0 : (int)(r0 < 1 ? 1 : r0 > kSLMaxRowsPerWave ? kSLMaxRowsPerWave : r0);
-  // (3 - 4 tokens: rather a second round of workgroups than the rows' sums out of the registers - gate / up of an 8B model,
-  // 2 x 14336 outputs, v8-k65536-256: 7 rows per wave 55.5 us, 4 rows per wave 52.3 - but not a third and fourth round: the
-  // two-table format of the same layers, 14 rows per wave 72.9 us, 4 rows per wave 90.9)
-  if (tokens > 2 && rpw0 > kSTRegRows && rpw0 <= 2 * kSTRegRows) rpw0 = kSTRegRows;
-  lds = 0;
-  D = SlicedTokDecision{};
-  for (int i = 0; i < n; ++i) {
-    StPlan pl;
-    const hipError_t e = st_fill(d[i], L + (size_t)i * tables, x, y[i], tokens, flags, ws[i], rpw0, GP.p[i], pl, jobs);
-    if (e != hipSuccess) return e;
-    lds = pl.lds > lds ? pl.lds : lds;
-    D.tok = pl.tok;
-    if (i == 0) { D.phases = pl.phases; D.rpw = pl.rpw; D.reg_sums = pl.reg_sums; }
-    GP.start[i + 1] = GP.start[i] + nslt * GP.p[i].p.n_rowblocks;
-  }
-  for (int i = n; i < kSTMaxGroup; ++i) GP.start[i + 1] = GP.start[n];
-  D.f16 = d[0].dtype == VPTQ_DTYPE_F16;
-  D.nsl = nsl; D.v = d[0].vector_len;
-  D.res = S0.side_bytes == 1; D.two = S0.tables == 2; D.ex = exact;
-  D.n = n; D.whole1 = tables == 2 ? L[1].whole_table : 0;
-  D.perm = jobs.n > 0;
-  return hipSuccess;
-}
-
-// x: [tokens][in_features], y[i]: [tokens][out_features of layer i] (fp32 with VPTQ_GEMV_OUT_F32); ws[i]:
-// gemv_sliced_tok_workspace_bytes of layer i, zero before its first use (every launch leaves the counters zero)
-hipError_t launch_gemv_sliced_tok_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
-                                        int tokens, int flags, void* const* ws, hipStream_t st) {
-  SlicedTokGroupParams GP;
-  StPermJobs jobs = {};
-  SlicedTokDecision D;
-  uint32_t lds = 0;
-  bool one_pass = false;
-  void* acc[kSTMaxGroup];
-  if (const hipError_t e = st_decide(d, L, n, x, y, tokens, flags, ws, one_pass, acc, GP, jobs, lds, D); e != hipSuccess) return e;
-  if (one_pass) return launch_gemv_sliced_group(d, L, n, x, y, flags, acc, st, tokens);
-  if (jobs.n > 0) {
-    const hipError_t e = launch_permute_x(jobs.d, jobs.n, jobs.xin, jobs.xout, st);
-    if (e != hipSuccess) return e;
-  }
-  const int grid = GP.start[n];
-  if (D.ex) return D.tok == 8 ? launch_st_ex8(D, GP, grid, lds, st) : launch_st_ex4(D, GP, grid, lds, st);
-  if (D.tok == 8) return launch_st_tok8(D, GP, grid, lds, st);
-  if (D.f16) return D.tok == 2 ? launch_st_dt<F16, 2>(D, GP, grid, lds, st) : launch_st_dt<F16, 4>(D, GP, grid, lds, st);
-  return D.tok == 2 ? launch_st_dt<BF16, 2>(D, GP, grid, lds, st) : launch_st_dt<BF16, 4>(D, GP, grid, lds, st);
-}
-// what launch_gemv_sliced_tok_group would launch, as text: the column-phase kernel's instance, or (one pass) gemv_sliced's
-int gemv_sliced_tok_instance(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, int tokens, int flags, char* buf, size_t bytes) {
-  if (n < 1 || n > kSTMaxGroup) return -1;
-  void* const some = (void*)(uintptr_t)4096;   // placeholders: aligned, never dereferenced
-  void* ys[kSTMaxGroup] = {some, some, some};
-  void* wss[kSTMaxGroup] = {some, some, some};
-  SlicedTokGroupParams GP;
-  StPermJobs jobs = {};
-  SlicedTokDecision D;
-  uint32_t lds = 0;
-  bool one_pass = false;
-  void* acc[kSTMaxGroup];
-  if (st_decide(d, L, n, some, ys, tokens, flags, wss, one_pass, acc, GP, jobs, lds, D) != hipSuccess) return -1;
-  if (one_pass) return gemv_sliced_instance(d, L, n, tokens, flags, false, buf, bytes);
-  Text t = {buf, bytes, 0, true};
-  t.add("gemv_sliced_tok dt=%s nsl=%d res=%d v=%d two=%d tok=%d ex=%d phases=%d rpw=%d regsums=%d n=%d whole1=%d perm=%d", dt_text(D.f16),
-        D.nsl, (int)D.res, D.v, (int)D.two, D.tok, (int)D.ex, D.phases, D.rpw, D.reg_sums, D.n, D.whole1, (int)D.perm);
-  return text_done(t);
-}
-hipError_t launch_gemv_sliced_tok(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int tokens, int flags,
-                                  void* ws, hipStream_t st) {
-  void* const ys[1] = {y};
-  void* const wss[1] = {ws};
-  return launch_gemv_sliced_tok_group(&d, L, 1, x, ys, tokens, flags, wss, st);
-}
-
-#endif   // part 1
+#endif
 
 }  // namespace vptq

@@ -98,8 +98,39 @@ static __device__ __forceinline__ K256Layer load_layer_args(int& tokens) {
 #define K256_STAMP(nwaves, k, dep) do { } while (0)
 #endif
 
-// gemv_k256m.hip
+// ---- gemv_k256m.hip (the kernel) and k256m_host.hip (its host side): what both read
 constexpr int kMRows = 4;  // vector-rows per workgroup of the MFMA kernel
+constexpr int kMThreads = 1024;
+constexpr int kMWaves = kMThreads / 64;
+constexpr int kMSweepCols = kMWaves * 16 * 8;  // 2048: 16 blocks (column chunks of 8) per wave
+constexpr int kMTableBytes = 65536;  // 256 rows x (8 main + 8 residual replicas) x 16 B
+constexpr int kMMaxLds = 163840;   // 160 KiB per CU
+constexpr int kMMaxCols = 14336;   // staged activations must fit beside the image
+constexpr int kMXBytes = 2;        // staged bytes per column and token
+constexpr int kMRedSlot = kMWaves * 32 * 4;   // one row group's cross-wave partials, per token
+constexpr int kMMaxSlots = 4;
+// VPTQ_GEMV_SELECTIVE inside the launch (gemv_k256m.hip has the account): the LDS it takes and the launches it covers
+constexpr int kMSelBit = 0x100;            // K256Layer::slots: selective roundings
+constexpr int kMSelMaxBlocks = 128;        // 16384 columns (staged: <= 14336)
+constexpr int kMSelRowGroups = 16;         // row groups per workgroup the corrections cover (16 waves = 4 x 4 rows per round; gate / up of an
+                                           // 8B model in one grouped launch: 14 per workgroup)
+constexpr int kMSelBytes = 2 * kMSelMaxBlocks + 4 * kMSelRowGroups * 32 * 4;   // block magnitudes + corr [4 quarters of the hot blocks][row groups][32]
+// VPTQ_K256M_SB_ALL (A/B, no result on record): every exact instantiation stages scale and bias in LDS (default: bf16, and fp16 from 6 sweeps on)
+#ifndef VPTQ_K256M_SB_ALL
+#define VPTQ_K256M_SB_ALL 0
+#endif
+// LDS bytes before the partial-sum slots: image + per token the staged activations (0 columns:
+// unstaged) and the per-wave sum b * x + slot counters
+// sb: scale and bias planes behind the activations (bf16 exact form)
+inline int lds_fixed_bytes(int staged_cols, int tok, bool sb) {
+  return kMTableBytes + (staged_cols > 0 ? (tok + (sb ? 2 : 0)) * (staged_cols * kMXBytes + 32) : 0) + tok * kMWaves * 4 + 64 + (tok == 1 && !sb ? kMSelBytes : 0);   // (sb: no selective form, no corrections)
+}
+// partial-sum slots that fit beside everything else (0: the shape does not fit at all)
+inline int lds_slots(int tok, int max_cols, bool sb) {
+  const int left = kMMaxLds - lds_fixed_bytes(max_cols > kMMaxCols ? 0 : max_cols, tok, sb);
+  const int slots = left < 0 ? 0 : left / (kMRedSlot * tok);
+  return slots > kMMaxSlots ? kMMaxSlots : slots;
+}
 bool gemv_k256m_supported(int tok, bool f16, bool fast, int max_cols, bool perm);
 int gemv_k256m_row_groups(int n_rows);
 // What one launch of the persistent MFMA kernel is: the template arguments of the instantiation and the launch-shape facts.
@@ -120,6 +151,16 @@ struct K256MDecision {
 };
 K256MDecision gemv_k256m_decide(const int* n_rows, int n, int tok, bool f16, bool fast, int max_cols, bool perm, bool selective);
 hipError_t launch_gemv_k256m(K256Params& P, const K256MDecision& D, hipStream_t st);
+// the instantiation dispatchers of gemv_k256m.hip, one family of instantiations each (its six compile parts): the only way from
+// launch_gemv_k256m into the kernel file; each launches the instantiation the decision names
+hipError_t k256m_f16_fast(const K256Params& P, const K256MDecision& D, hipStream_t st);            // part 1
+hipError_t k256m_f16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);           // part 2
+hipError_t k256m_bf16(const K256Params& P, const K256MDecision& D, hipStream_t st);                // part 2
+hipError_t k256m_f16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st);          // part 3
+hipError_t k256m_bf16_tokens(const K256Params& P, const K256MDecision& D, hipStream_t st);         // part 4
+hipError_t k256m_bf16_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);          // part 4
+hipError_t k256m_f16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);    // part 5
+hipError_t k256m_bf16_tokens_exact(const K256Params& P, const K256MDecision& D, hipStream_t st);   // part 6
 bool gemv_k256m_selective_ok(const int* n_rows, int n, bool f16, int tok, int max_cols, bool perm);
 // most row groups any workgroup of one launch of these layers walks (the launch's duration in units of one row group)
 int gemv_k256m_launch_units(const int* n_rows, int n);

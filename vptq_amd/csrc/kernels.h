@@ -90,7 +90,8 @@ bool gemv_lds_v2_eligible(const VptqV2Desc& d, int tokens);
 hipError_t launch_gemv_lds_v2(const VptqV2Desc& d, const void* x, void* y, int tokens, bool out_f32,
                               int flags, hipStream_t st);
 
-// gemv_sliced.hip - v8-k65536-0, one token, over the load-time derived sliced layout (LDS-local gathers)
+// gemv_sliced.hip - v8-k65536-0, one token, over the load-time derived sliced layout (LDS-local gathers); the rules and launchers
+// declared here are its host side's (sliced_host.hip; more of them, for the library's own use, in sliced.h)
 // exact: the reference's roundings per weight (VPTQ_GEMV_EXACT) - scale and bias staged per column beside the activations
 // (6 instead of 2 bytes of LDS per column: more slices for wide layers), one table only
 bool gemv_sliced_eligible(const VptqLayerDesc& d, bool exact = false);
@@ -110,7 +111,7 @@ hipError_t launch_gemv_hot(const VptqLayerDesc& d, const void* x, void* extra, c
 hipError_t launch_gemv_sliced(const VptqLayerDesc& d, const VptqSlicedLayout* L, const void* x, void* y, int flags,
                               void* ws, hipStream_t st, const float* corr = nullptr);
 // up to 3 layers of one format reading the same x (q / k / v, gate / up) in one launch
-// gemv_sliced_tok.hip - 2 - 4 tokens over the same layouts (column windows of every list, phase by phase)
+// gemv_sliced_tok.hip - 2 - 8 tokens over the same layouts (column windows of every list, phase by phase); host side: sliced_host.hip
 bool gemv_sliced_tok_eligible(const VptqLayerDesc& d, const VptqSlicedLayout* L, int tokens, bool exact = false);
 int gemv_sliced_tok_one_pass_parts(const VptqLayerDesc& d, int tokens, bool exact);   // 0: column phases / not served; 1, 2, 4: one pass, that many window parts
 size_t gemv_sliced_tok_workspace_bytes(const VptqLayerDesc& d, int tokens);
@@ -123,7 +124,7 @@ bool gemv_sliced_groupable(const VptqLayerDesc* d, int n, bool exact = false);
 hipError_t launch_gemv_sliced_group(const VptqLayerDesc* d, const VptqSlicedLayout* L, int n, const void* x, void* const* y,
                                     int flags, void* const* ws, hipStream_t st, int tokens = 1, const float* corr = nullptr);
 // what one launch of the sliced family IS - the instantiation's template arguments and the launch shape: decided once per call
-// (gemv_sliced.hip:sl_decide, gemv_sliced_tok.hip:st_decide, gemv_hot_decide), checked by the launchers against their template arguments
+// (sliced_host.hip: sl_decide, st_decide; gemv_hot_decide), checked by the launchers against their template arguments
 // and printed by the *_instance functions (vptq_quant_gemv_sliced_instance / _tokens_instance): 0, -1: no launch, -2: buffer too small
 struct SlicedDecision {
   bool f16, res, two, ex, rg, wpt;   // gemv_sliced_kernel<DT, NSL, RES, V, TWO, EX, RG, TOK, WPT>

@@ -1,5 +1,6 @@
-// Shared by gemv_sliced.hip (one token) and gemv_sliced_tok.hip (2 - 4 tokens): launch constants, the parameter block of
-// one layer and the host-side helpers that say what a layer's layout looks like.
+// Shared by gemv_sliced.hip (one token), gemv_sliced_tok.hip (2 - 8 tokens) and sliced_host.hip (the family's host side: which layouts
+// serve a layer, what makes one valid, what one launch is): launch constants, the kernels' parameter blocks, the host rules the rest
+// of the library reads and the instantiation dispatchers the host side launches through.
 #pragma once
 #include <type_traits>
 
@@ -53,8 +54,54 @@ struct SlicedParams {
   int wparts, wcols, wstage;
 };
 constexpr int kSLWindows = VPTQ_SLICED_WINDOWS;
+// Up to kSLMaxGroup layers that read the SAME activation (q / k / v, gate / up) in one launch: layer l owns the workgroups
+// [start[l], start[l + 1]).  One launch instead of n: the fixed part of a launch (boundary, slice copy, staging, the
+// cross-slice hand-over: ~7 of the 10 us of a 4096 x 4096 layer) is paid once.
+constexpr int kSLMaxGroup = 3;
+struct SlicedGroupParams {
+  int n;
+  int arrivals;   // workgroups that add into an output's accumulator word: (tables x) slices - x n where the "layers" are COLUMN PARTS of one
+  int start[kSLMaxGroup + 1];
+  SlicedParams p[kSLMaxGroup];
+};
 
-// ---- host side (gemv_sliced.hip)
+// ---- gemv_sliced_tok.hip: 2 - 8 tokens in column phases
+constexpr int kSTWindows = VPTQ_SLICED_WINDOWS;
+constexpr int kSTRegRows = 4;   // rows per wave whose sums (4 registers each in matrix-pipe mode) are kept in registers
+struct SlicedTokParams {
+  SlicedParams p;            // as for one token; x / y: token 0, rows_per_wave / n_rowblocks: this launch's
+  const int32_t* wstart;     // [slices][N][kSTWindows + 1]
+  const int32_t* wstart2;    // second table
+  const uint16_t* xs;        // the activations in COLUMN order: p.x, or the pre-pass's x[perm] (p.scale is in column order too)
+  int tokens;                // 2 .. TOK
+  int phases;                // 1, 2 or 4
+  int wcols;                 // columns per layout window
+  int x_stride, x_in_stride, y_stride;    // elements between two tokens of xs / p.x / y
+  uint32_t bd_off, res_off, sum_off;   // LDS: sum b x parts [TOK][16 waves] floats; 256-entry residual table; row sums
+  uint32_t sb_off;           // EX: LDS, per staged column 8 bytes {s, b, s, b} (and the zero column's zeros)
+  int reg_sums;              // (matrix-pipe mode, <= kSTRegRows rows per wave) the rows' sums stay in registers: no LDS for them
+};
+// Up to kSTMaxGroup layers that read the SAME activations (q / k / v, gate / up) in one launch, as in gemv_sliced.hip: layer l
+// owns the workgroups [start[l], start[l + 1]); the fixed part of a launch is paid once.
+constexpr int kSTMaxGroup = 3;
+struct SlicedTokGroupParams {
+  int n;
+  int start[kSTMaxGroup + 1];
+  SlicedTokParams p[kSTMaxGroup];
+};
+
+// ---- instantiation dispatchers: the ONLY way from the host side (sliced_host.hip) into the kernel files.  Each launches the
+// instantiation the decision names (and turns a decision down that names none of its own); gemv_sliced.hip, parts 1 / 2 / 3 ...
+hipError_t launch_sl_one(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);          // one token
+hipError_t launch_sl_tokens(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);       // 2 / 3 tokens, reference roundings
+hipError_t launch_sl_tokens_wpt(const SlicedDecision& D, const SlicedGroupParams& P, uint32_t lds, hipStream_t st);   // ... in window parts
+// ... gemv_sliced_tok.hip, parts 1 / 2 / 3 / 4: 2 and 4 token slots, 8 slots, 4 / 8 slots in the reference's roundings
+hipError_t launch_st_tok24(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
+hipError_t launch_st_tok8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
+hipError_t launch_st_ex4(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
+hipError_t launch_st_ex8(const SlicedTokDecision& D, const SlicedTokGroupParams& P, int grid, uint32_t lds, hipStream_t st);
+
+// ---- host side (sliced_host.hip)
 bool sl_res256(const VptqLayerDesc& d);   // v = 8 with the 256-entry residual table: a byte per element beside the main layout
 bool sl_two(const VptqLayerDesc& d);      // any other residual table: a second table with a layout of its own
 uint32_t sl_tab_bytes(const VptqLayerDesc& d, int k, int whole, bool exact = false);   // bytes a workgroup of a k-entry table holds

@@ -233,7 +233,7 @@ def rows_per_wave_for(n_rows: int, slices: int = 8, workgroups: int = 256) -> in
 def part_desc(desc, c0: int, c1: int):
     """copy of a layer's descriptor that stands for its columns [c0, c1) alone (`VPTQ_GEMV_COLUMN_PARTS`, include/vptq_hip.h): widths
     and the column-order tensors advanced to c0 (16-bit elements).  The tensors stay owned by the layer's own descriptor.  The twin of
-    the library's `sl_part_desc` (vptq_amd/csrc/gemv_sliced.hip), which the part rule of `vptq_sliced_layout_set` is stated with."""
+    the library's `sl_part_desc` (vptq_amd/csrc/sliced_host.hip), which the part rule of `vptq_sliced_layout_set` is stated with."""
     d = B.LayerDesc.from_buffer_copy(desc)
     d.in_features = d.group_size = c1 - c0
     for f in ("weight_scale", "weight_bias", "perm", "scale_permuted", "bias_permuted"):
