@@ -618,6 +618,32 @@ VPTQ_API int vptq_quant_gemm_k256w_supported(const VptqLayerDesc* desc, int toke
 VPTQ_API int vptq_quant_gemm_k256w(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_k256w_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of the large-codebook formats for 17 - 48 tokens in ONE launch (gemm_gatherw_kernel in gemm_gatherw.hip; added within
+ * ABI 12; present when the symbols are).  The layers vptq_quant_gemm_gather serves - v = 8, 65536 main centroids, 0 / 256 / 65536
+ * residual centroids, one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and
+ * bias_permuted), group_size == in_features (a multiple of 8), indices and codebooks 16-byte aligned - with the tokens as tb =
+ * ceil(tokens / 16) blocks of the M dimension of a 16x16x32 MFMA: the indices are read, gathered and rebuilt once for all blocks,
+ * where 17+ tokens had no kernel (vptq_dequant + a dense GEMM).  The reference's roundings per weight (bit-identical to
+ * vptq_dequant's W), fp32 sums added in a fixed order, one rounding of the output, the output bias added in fp32.  The order of the
+ * sums is gemm_gather_kernel's and does not depend on the token count or on a token's slot: a token's output bits are the same in
+ * every slot of every batch, and equal those vptq_quant_gemm_gather gives that token in a launch of up to 16.  No workspace, no
+ * atomics; graph-capturable.
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags: VPTQ_GEMV_OUT_F32 stores the fp32 sums (y is float32);
+ *   VPTQ_GEMV_FAST_MATH / _EXACT / _SELECTIVE are accepted and change nothing.
+ * vptq_quant_gemm_gatherw_supported: 1 where the call serves (desc, tokens) - such a layer and 17 <= tokens <= 48 - else 0; host logic.
+ * vptq_quant_gemm_gatherw: NULL desc / x / y VPTQ_E_NULL; tokens outside [17, 48], or an x that is not 16-byte aligned, VPTQ_E_TOKENS
+ *   (the tokens are checked before the layer); a layer it does not serve VPTQ_E_UNSUPPORTED; nothing is launched then.
+ * vptq_quant_gemm_gatherw_instance: the instantiation of gemm_gatherw_kernel<DT, T, PERM, TB> and the launch shape, as one line (the
+ *   launcher's own decision; host logic, without a device the CU count is taken as 256):
+ *   gemm_gatherw dt=f16|bf16 t=16|24|32 perm=0|1 tok=N tb=2|3 tiles=N rgs=N
+ *       t the index width, tok the tokens of the launch, tb its token blocks, tiles the column tiles (1024 columns) per row group (2
+ *       vector-rows), rgs the most row groups one workgroup walks.  Returns as vptq_quant_gemm_gather_instance does.
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens, vptq_quant_gemv_kernel_name and vptq_quant_gemm_gather* (1 - 16 tokens) are what they
+ * were: callers choose this entry. */
+VPTQ_API int vptq_quant_gemm_gatherw_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gatherw(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
+VPTQ_API int vptq_quant_gemm_gatherw_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
 /* Diagnostic (ABI 12): WHICH INSTANTIATION of dequant_kernel<DT, V, TAB> vptq_dequant(desc, W) would launch and which paths its

@@ -167,6 +167,10 @@ EXPORTS = {
     "vptq_quant_gemm_k256w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_k256w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
     "vptq_quant_gemm_k256w_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 17 - 48 tokens of gemm_gather's formats in one launch (gemm_gatherw_kernel, gemm_gatherw.hip)
+    "vptq_quant_gemm_gatherw_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gatherw": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
+    "vptq_quant_gemm_gatherw_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

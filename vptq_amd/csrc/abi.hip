@@ -1167,7 +1167,8 @@ int vptq_quant_gemm(const VptqLayerDesc* d, const void* x, void* y, int tokens, 
 
 // ---- gemm_gather.hip / gemm_gatherx.hip: 1 - 16 tokens of the large-codebook formats in one launch (added within ABI 12).  A layer
 // has one of the two kernels; the entries of both are the three shapes below, given the kernel's name, what it serves, its
-// eligibility function and its launcher.  gemm_k256w (gemm_k256.hip): the same three shapes for 17 - 64 tokens of the canonical format
+// eligibility function and its launcher.  gemm_k256w (gemm_k256.hip): the same three shapes for 17 - 64 tokens of the canonical format;
+// gemm_gatherw (gemm_gatherw.hip): for 17 - 48 tokens of gemm_gather's layers
 struct BatchedDecode {
   const char* name;
   int tok_lo, tok_hi;        // the token counts of one launch
@@ -1191,6 +1192,10 @@ static void print_gemm_k256w(Text& t, const VptqLayerDesc& d, int tokens) {
   const vptq::GemmK256WDecision D = vptq::gemm_k256w_decide(d, tokens);
   t.add("gemm_k256w dt=%s perm=%d tok=%d tb=%d rgs=%d pass=1x%d", dt_text(D.f16), (int)D.perm, D.tok, D.tb, D.rgs, D.tb);
 }
+static void print_gemm_gatherw(Text& t, const VptqLayerDesc& d, int tokens) {
+  const vptq::GemmGatherWDecision D = vptq::gemm_gatherw_decide(d, tokens);
+  t.add("gemm_gatherw dt=%s t=%d perm=%d tok=%d tb=%d tiles=%d rgs=%d", dt_text(D.f16), D.T, (int)D.perm, D.tok, D.tb, D.tiles, D.rgs);
+}
 static const BatchedDecode kGemmGather = {
   "gemm_gather", 1, 16, VPTQ_E_UNSUPPORTED, "gemm_gather launch", "v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids, one codebook, no outlier columns, scale and bias, "
   "group_size == in_features (a multiple of 8), 16-byte aligned tables", vptq::gemm_gather_eligible, vptq::launch_gemm_gather,
@@ -1204,6 +1209,12 @@ static const BatchedDecode kGemmK256W = {
   "gemm_k256w", 17, 64, VPTQ_E_TOKENS, "gemm_k256w launch", "the canonical format (v = 8, 256 + 256 centroids, one codebook, no outlier columns, "
   "scale and bias, group_size == in_features (a multiple of 8), with perm: scale_permuted and bias_permuted)", vptq::gemm_k256w_eligible,
   vptq::launch_gemm_k256w, print_gemm_k256w};
+
+// gemm_gatherw (gemm_gatherw.hip): gemm_gather's layers, 17 - 48 tokens
+static const BatchedDecode kGemmGatherW = {
+  "gemm_gatherw", 17, 48, VPTQ_E_TOKENS, "gemm_gatherw launch", "v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids, one codebook, no outlier columns, scale and bias, "
+  "group_size == in_features (a multiple of 8), 16-byte aligned tables", vptq::gemm_gatherw_eligible, vptq::launch_gemm_gatherw,
+  print_gemm_gatherw};
 
 static int batched_supported(const BatchedDecode& k, const VptqLayerDesc* d, int tokens) {
   return validate_layer(d) == VPTQ_OK && k.eligible(*d, tokens) ? 1 : 0;
@@ -1247,6 +1258,9 @@ int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* d, int tokens, int, ch
 int vptq_quant_gemm_k256w_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmK256W, d, tokens); }
 int vptq_quant_gemm_k256w(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmK256W, d, x, y, tokens, flags, stream); }
 int vptq_quant_gemm_k256w_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmK256W, d, tokens, buf, bytes); }
+int vptq_quant_gemm_gatherw_supported(const VptqLayerDesc* d, int tokens) { return batched_supported(kGemmGatherW, d, tokens); }
+int vptq_quant_gemm_gatherw(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmGatherW, d, x, y, tokens, flags, stream); }
+int vptq_quant_gemm_gatherw_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmGatherW, d, tokens, buf, bytes); }
 
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {

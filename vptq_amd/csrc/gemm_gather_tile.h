@@ -67,6 +67,30 @@ static __device__ __forceinline__ void gt_load_a(const uint16_t* perm, const uin
   }
 }
 
+// one K-step of gt_load_a for gemm_gatherw.hip, which requests the A operands of its later token blocks step by step: the 16 bytes
+// of x from column col on (clamped as above) of the token row that starts rowoff BYTES into x.  Addresses are the uniform base plus
+// a 32-bit lane offset (x is at most 48 rows): one address register per load where a per-lane row pointer takes two - with a
+// permutation that is 8 loads a step, and what keeps that kernel's permuted forms under 256 registers.
+template <bool PERM>
+static __device__ __forceinline__ u32x4 gt_load_a1(const uint16_t* perm, const uint16_t* x, uint32_t rowoff, int G, int col) {
+  const int cc = col < G ? col : G - 8;
+  const char* const xb = (const char*)x;
+  if constexpr (PERM) {
+    const uint32_t* p32 = (const uint32_t*)((const char*)perm + (uint32_t)(cc * 2));
+    u32x4 a;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t pv = p32[q];
+      const uint32_t lo = *(const uint16_t*)(xb + (rowoff + 2u * (pv & 0xffffu)));
+      const uint32_t hi = *(const uint16_t*)(xb + (rowoff + 2u * (pv >> 16)));
+      a[q] = lo | (hi << 16);
+    }
+    return a;
+  } else {
+    return *(const u32x4*)(xb + (rowoff + (uint32_t)(cc * 2)));
+  }
+}
+
 // rebuild 8 columns x 8 outputs in place: c + r, * s, + b, each rounded to 16 bits; columns past the row end become 0
 template <typename DT, bool RES>
 static __device__ __forceinline__ void gt_rebuild(u32x4 (&cv)[8], const u32x4 (&rv)[RES ? 8 : 1], const uint32_t (&sp)[4],

@@ -209,6 +209,14 @@ struct GemmGatherDecision { bool f16, perm; int T, tok, tiles, n_groups, grid, r
 GemmGatherDecision gemm_gather_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gather(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
 
+// gemm_gatherw.hip - gemm_gather's layers, 17 - 48 tokens in one launch as tb = 2 / 3 blocks of 16 tokens over gemm_gather's tile
+// pipeline (its K-step -> wave mapping and order of sums: a token's bits are the 16-token kernel's)
+bool gemm_gatherw_eligible(const VptqLayerDesc& d, int tokens);
+// what launch_gemm_gatherw launches: gemm_gatherw_kernel<DT, T, PERM, TB>; tiles and rgs as above
+struct GemmGatherWDecision { bool f16, perm; int T, tok, tb, tiles, n_groups, grid, rgs; };
+GemmGatherWDecision gemm_gatherw_decide(const VptqLayerDesc& d, int tokens);
+hipError_t launch_gemm_gatherw(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+
 // gemm_gatherx.hip - the large-codebook layers gemm_gather does not take (v = 8 / 16, 16384 ... 65536 main centroids, any residual
 // codebook, any total index width), up to 16 tokens in one launch: gemm_gather's structure with gemv_gatherx's index path
 bool gemm_gatherx_eligible(const VptqLayerDesc& d, int tokens);

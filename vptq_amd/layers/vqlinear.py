@@ -198,6 +198,41 @@ def gemm_k256w_route(out_features: int, in_features: int, tokens: int) -> bool:
     return any(n_el >= min_el and min_tok <= tokens <= max_tok for min_el, min_tok, max_tok in _GEMM_K256W_CELLS)
 
 
+# WHICH (format, shape, token count) of gemm_gather's formats (v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids) take
+# `vptq_quant_gemm_gatherw` - 17 - 48 tokens in ONE launch (gemm_gatherw_kernel, gemm_gatherw.hip) - in place of the dense route
+# they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.  A cell is (residual centroids, least index elements
+# = vector-rows x columns, least tokens, most tokens), routed by the rule above `_GEMM_GATHER_CELLS` (beats its parent by more than
+# the larger of 5 % and three times the run-to-run spread, in every measured cell of the region, in both dtypes; the routed token
+# counts of a layer are one interval); tools/gemm_gatherw_bench.py writes the table.  No cell starts below 4 M index elements: a
+# compacted 4096 x 4096 layer keeps its dense route, which needs no repack there (`_dense_from_layout`).  VPTQ_GEMM_GATHERW=1 / 0
+# (with VPTQ_TUNING=1): every supported layer from 17 to 48 tokens / none.
+#
+# profiles/r23/table.md, profiles/r23/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 17 / 24 / 32 / 33 / 40 /
+# 48, layers without a permutation): at 17 - 24 tokens the kernel beats the dense route in every measured cell of the three formats
+# (0.66 - 0.92 of its time), so 17 - 24 tokens are routed from the smallest measured layer above 4 M elements (14336 x 4096 = 7 M) up.
+# From 32 tokens it does not win on 14336 x 4096 (0.98 - 1.25) and is level at 8192 x 8192 (0.88 - 1.13), and wins in every cell only at
+# 8192 x 28672 (28 M elements: 0.70 - 0.88 at 32 - 48 tokens), so 25 - 48 tokens are routed from that size up.  LAYERS WITH A COLUMN
+# PERMUTATION ARE NEVER ROUTED (only the knob reaches them): the kernel gathers a permuted x two bytes at a time in every row group and
+# took 1.8 - 6.8 times the dense route's time at 8192 x 8192 and 14336 x 4096 (profiles/r23/table_perm.md).
+_GEMM_GATHERW_CELLS = tuple((kr, el, lo, hi) for kr in (0, 256, 65536) for el, lo, hi in ((7 << 20, 17, 24), (28 << 20, 17, 48)))
+GEMM_GATHERW_MIN_TOKENS, GEMM_GATHERW_MAX_TOKENS = 17, 48
+GEMM_GATHERW_MIN_ELEMENTS = 4 << 20
+_GEMM_GATHERW_MODE = (B.tune_env("VPTQ_GEMM_GATHERW", "auto") or "auto").strip().lower()
+
+
+def gemm_gatherw_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
+    """does a layer of this format and shape take `vptq_quant_gemm_gatherw` for `tokens` tokens?  Pure: no device, no library
+    (whether the library serves the layer is `vptq_quant_gemm_gatherw_supported`'s answer)."""
+    if _GEMM_GATHERW_MODE in ("0", "off") or not GEMM_GATHERW_MIN_TOKENS <= tokens <= GEMM_GATHERW_MAX_TOKENS or \
+            _batched_decode_entry(vector_len, num_centroids, num_res_centroids) != "vptq_quant_gemm_gather":
+        return False
+    if _GEMM_GATHERW_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any(kr == num_res_centroids and n_el >= max(min_el, GEMM_GATHERW_MIN_ELEMENTS) and min_tok <= tokens <= max_tok
+               for kr, min_el, min_tok, max_tok in _GEMM_GATHERW_CELLS)
+
+
 def _dense_from_layout(layer) -> bool:
     """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (a library without the entry, added within ABI 11:
     never - the repack route stays)"""
@@ -588,6 +623,10 @@ class VQuantLinear(nn.Module):
             y = self._gemm_k256w_cached(x, tokens)   # (the canonical format in the reference's roundings, where `gemm_k256w_route` says so)
             if y is not None:
                 return y
+        if GEMM_GATHERW_MIN_TOKENS <= tokens <= GEMM_GATHERW_MAX_TOKENS and x.is_cuda and self.__dict__.get("_gatherw", True):
+            y = self._gemm_gatherw_cached(x, tokens)   # (gemm_gather's formats, where `gemm_gatherw_route` says so)
+            if y is not None:
+                return y
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
                 (tokens <= B.GEMV_ANY_FORMAT_TOKENS or tokens <= self._descriptor().max_tokens):
             return self._gemv_cached(x, tokens)
@@ -701,7 +740,7 @@ class VQuantLinear(nn.Module):
 
     # derived, device-bound state (ctypes descriptors, the sliced layout, sibling links) is rebuilt on demand: it is
     # neither pickled nor deep-copied with the module (torch.save(model), copy.deepcopy(model))
-    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_ok", "_k256w_ok")
+    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_ok", "_k256w_ok", "_gatherw_ok")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -1085,6 +1124,22 @@ class VQuantLinear(nn.Module):
                 (ops.quant_gemm_flags() & B.GEMV_FORCE_ANY) or not (self._descriptor().arithmetic_flags & B.GEMV_EXACT):
             return None
         return self._batched_entry_launch("vptq_quant_gemm_k256w", "_k256w_ok", GEMM_K256W_MAX_TOKENS, x, tokens)
+
+    def _gemm_gatherw_cached(self, x: torch.Tensor, tokens: int):
+        """17 - 48 tokens of a layer of gemm_gather's formats in ONE launch of `vptq_quant_gemm_gatherw` where `gemm_gatherw_route`
+        gives the layer's (format, shape, tokens) to it, the layer has no column permutation (or the knob is on), GEMV_FORCE_GENERIC
+        is not set and the library serves the layer; None: the routes of before.  Compact layers hand it the repacked stream, as the 5 - 16 token route does."""
+        if "_gatherw" not in self.__dict__:   # (static module configuration: decided once)
+            self.__dict__["_gatherw"] = _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self)) == "vptq_quant_gemm_gather" and \
+                self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm and \
+                getattr(B.lib(), "vptq_quant_gemm_gatherw", None) is not None
+        if not self.__dict__["_gatherw"] or \
+                not gemm_gatherw_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
+                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
+            return None
+        if self.enable_perm and _GEMM_GATHERW_MODE not in ("1", "on"):   # (measured 1.8 - 6.8 times the dense route: the comment above the cells)
+            return None
+        return self._batched_entry_launch("vptq_quant_gemm_gatherw", "_gatherw_ok", GEMM_GATHERW_MAX_TOKENS, x, tokens)
 
     def _batched_entry_launch(self, entry: str, ok_key: str, ask_tokens: int, x: torch.Tensor, tokens: int):
         """one launch of a batched-decode entry; `_supported`'s answer cached per descriptor generation under `ok_key`.  None: the

@@ -20,7 +20,7 @@ from torch.nn import functional as F
 
 from vptq_amd import _backend as B
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gatherx", "quant_gemm_k256w", "quant_gemv_v2"]
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w", "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
 # says (`_backend.set_arithmetic`: "reference" is the default since round 5, "folded" the opt-in fast form)
@@ -210,6 +210,14 @@ def quant_gemm(
                     route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
                     getattr(B.lib(), entry + "_supported")(gdesc, tokens):
                 return _quant_gemm_batched(entry, x, gdesc, out_features)
+        # gemm_gather's formats, 17 - 48 tokens in one launch (gemm_gatherw_kernel), where its route function says so
+        # (never a layer with a column permutation, unless the knob is on: 1.8 - 6.8 times the dense route, profiles/r23)
+        from vptq_amd.layers import vqlinear as _vq
+        from vptq_amd.layers.vqlinear import gemm_gatherw_route
+        if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and (perm is None or _vq._GEMM_GATHERW_MODE in ("1", "on")) and \
+                gemm_gatherw_route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
+                B.lib().vptq_quant_gemm_gatherw_supported(gdesc, tokens):
+            return _quant_gemm_batched("vptq_quant_gemm_gatherw", x, gdesc, out_features)
         # the canonical format's 17 - 64 tokens in one launch, in the reference's roundings only (gemm_k256w_kernel)
         from vptq_amd.layers.vqlinear import gemm_k256w_route
         if (vector_len, num_centroids, kr) == (8, 256, 256) and gemm_k256w_route(out_features, in_features, tokens) and \
@@ -281,7 +289,7 @@ def quant_gemm_fused(x: torch.Tensor, desc, out_features: int) -> torch.Tensor:
 
 def _quant_gemm_batched(entry: str, x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
     """the tokens of ONE launch of a batched-decode entry: 1 - 16 of the large-codebook formats (`quant_gemm_gather` / `quant_gemm_gatherx`),
-    17 - 64 of the canonical format (`quant_gemm_k256w`)"""
+    17 - 48 of `quant_gemm_gather`'s formats (`quant_gemm_gatherw`), 17 - 64 of the canonical format (`quant_gemm_k256w`)"""
     tokens = x.numel() // x.shape[-1]
     dev = x.device
     if not x.is_contiguous():
@@ -299,6 +307,14 @@ def quant_gemm_gather(x: torch.Tensor, desc, out_features: int, out_f32: bool = 
     matrix pipe, the reference's roundings; replaces dequant + F.linear for 9 - 16 tokens).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gather_supported` accepts; out_f32: the un-rounded fp32 sums."""
     return _quant_gemm_batched("vptq_quant_gemm_gather", x, desc, out_features, out_f32)
+
+
+def quant_gemm_gatherw(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 17 - 48 tokens of a layer `quant_gemm_gather` serves (v = 8, 65536 main centroids, 0 / 256 / 65536
+    residual centroids) in ONE launch (`vptq_quant_gemm_gatherw`, gemm_gatherw.hip: 2 / 3 blocks of 16 tokens share one pass over the
+    indices, gathers and rebuilt tiles; the reference's roundings, a token's bits those of the 16-token kernel; replaces dequant +
+    F.linear).  `desc` = a LayerDesc of a layer `vptq_quant_gemm_gatherw_supported` accepts; out_f32: the un-rounded fp32 sums."""
+    return _quant_gemm_batched("vptq_quant_gemm_gatherw", x, desc, out_features, out_f32)
 
 
 def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
