@@ -26,6 +26,13 @@
  *               per thread in vptq_last_error().  The reference throws
  *               c10::Error via TORCH_CHECK (csrc/util/common.h:11-19).
  * Threading ... re-entrant; no globals besides one-time kernel attribute setup.
+ * Alignment ... every pointer is aligned to its ELEMENT at least (2 bytes for fp16 / bf16 / uint16, 4 for int32 / float32, 1 for
+ *               uint8); `indices`, `centroids` and `res_centroids` of a VptqLayerDesc to 4 bytes (VPTQ_E_ALIGN).  What an entry or
+ *               one of its kernels needs beyond that is stated at the entry ("Alignment:").  Where a kernel's rule is not met the
+ *               call does not fail: it takes the next kernel that can read the operands (the order is given there), down to one
+ *               that takes element alignment - same results within that kernel's arithmetic.  No kernel reads or writes outside
+ *               the tensors' extents as declared here, whatever surrounds them, and results do not depend on the alignment beyond
+ *               the rule of the kernel that runs (tests/test_operand_placement_gpu.py holds every entry to both).
  */
 #ifndef VPTQ_HIP_H
 #define VPTQ_HIP_H
@@ -235,6 +242,16 @@ VPTQ_API const char* vptq_last_error(void);
  * over the indices, fp16 and bf16; its pre-pass writes the operand-ordered activations there).
  * With NULL / fewer bytes the call uses the kernels that need none (same results within the
  * parity bar).  Launches of one call and calls on one stream may share a workspace.
+ * Alignment: the entry takes element-aligned x, y (2 bytes; float32 y: 4), weight_scale, weight_bias, bias, perm, outlier_indices and
+ * outlier_centroids and 4-byte indices / codebooks - served by gemv_generic.  The kernels in front of it, in the order they are tried,
+ * and what each needs (a rule that is not met hands the call to the next one; y and bias are element-aligned for all of them):
+ *   gemm_k256t, gemm_k256, gemv_k256, gemv_k256m   indices, centroids, res_centroids, weight_scale, weight_bias, perm (and
+ *                 scale_permuted, bias_permuted) 16 bytes; x 16 bytes (gemm_k256t: 2); the workspace 16 bytes
+ *   gemv_gather   indices, centroids, res_centroids 16 bytes; weight_scale, weight_bias, perm (scale_permuted, bias_permuted), x 4
+ *   gemv_lds, gemv_lds_mfma   centroids, res_centroids, weight_scale, weight_bias, perm (scale_permuted, bias_permuted), x 16 bytes
+ *   gemv_gatherx  centroids, res_centroids, outlier_centroids: the largest power of two that divides an entry (2 v bytes), at most 16;
+ *                 indices, weight_scale, weight_bias, perm (scale_permuted, bias_permuted), x 4 bytes; outlier_indices 2
+ * vptq_quant_gemv_instance / _kernel_name see the descriptor only: they answer for an x that meets the rule.
  */
 VPTQ_API int vptq_quant_gemv(const VptqLayerDesc* desc, const void* x, void* y, int tokens,
                     int flags, void* workspace, size_t workspace_bytes, void* stream);
@@ -257,6 +274,8 @@ VPTQ_API int vptq_quant_gemv_max_tokens(const VptqLayerDesc* desc);
  * layer, or any batch of VQuantLinear GEMVs).  descs is a HOST array; x[i], y[i]
  * are device pointers for layer i.  Every layer must be eligible for the same
  * kernel family (checked); n <= VPTQ_GROUP_MAX.
+ * Alignment: per layer as vptq_quant_gemv states it - the group takes gemv_k256 / gemv_k256m where EVERY member and every x[i] meets
+ * their rule (16 bytes), else the members are served one by one ("per-layer"); y[i] and bias element-aligned.
  */
 #define VPTQ_GROUP_MAX 64
 VPTQ_API int vptq_quant_gemv_grouped(const VptqLayerDesc* descs, int n, const void* const* x,
@@ -281,6 +300,13 @@ VPTQ_API int vptq_quant_gemv_grouped(const VptqLayerDesc* descs, int n, const vo
  * vptq_quant_gemv_grouped launch ("grouped": faster than the persistent launch up to 8 layers; it serves members it
  * has no common kernel for one by one); a single layer, mixed dtypes and dependent lists the persistent kernel does
  * not take are executed as n vptq_quant_gemv calls ("per-layer").  descs is a HOST array; x[i], y[i] device pointers.
+ * Alignment: the persistent launch takes layers that meet gemv_k256's rule (indices, codebooks, weight_scale, weight_bias, perm,
+ * scale_permuted, bias_permuted 16 bytes) with every x[i] 4-byte aligned - in a dependent list that holds for y[i] = x[i + 1] too;
+ * y[i] otherwise and bias element-aligned.  A list that misses the rule goes to the grouped / per-layer calls and their rules.
+ * Workspace: dependent lists 4-byte aligned (VPTQ_E_WORKSPACE otherwise), contents don't matter (cleared by the call); the
+ * permutation / selective workspace of vptq_quant_gemv_chain_workspace_bytes_for 256-byte aligned, contents don't matter - with a
+ * smaller or less aligned one the call takes the routes that need none.  vptq_quant_gemv_chain_instance / _kernel_name see the
+ * descriptors only: they answer for x[i] and a workspace that meet the rules.
  */
 #define VPTQ_CHAIN_MAX 1024
 VPTQ_API int vptq_quant_gemv_chain(const VptqLayerDesc* descs, int n, const void* const* x,
@@ -315,6 +341,8 @@ VPTQ_API int vptq_quant_gemv_chain_plan(const VptqLayerDesc* descs, int n, int f
  * r16(r16(r16(c+r)*s)+b), fp32 accumulate; bf16: folded form.  bf16 needs a workspace of
  * vptq_quant_gemm_workspace_bytes() (tokens floats).  vptq_quant_gemm_supported() = 1 when a
  * fused kernel exists for the layer; otherwise use vptq_dequant + a dense GEMM.
+ * Alignment: the layer by gemv_k256's rule (indices, codebooks, weight_scale, weight_bias 16 bytes: part of "supported"); x 16 bytes
+ * (VPTQ_E_ALIGN); the workspace 16 bytes, contents don't matter; y and bias element-aligned.
  */
 VPTQ_API int vptq_quant_gemm_supported(const VptqLayerDesc* desc);
 VPTQ_API size_t vptq_quant_gemm_workspace_bytes(const VptqLayerDesc* desc, int tokens);
@@ -349,6 +377,13 @@ VPTQ_API int vptq_quant_gemm(const VptqLayerDesc* desc, const void* x, void* y, 
  * bit-equivalent); VPTQ_GEMV_EXACT (ABI >= 8) the reference's roundings per weight over a layout with the slice count
  * vptq_sliced_layout_supported_for(desc, VPTQ_GEMV_EXACT) answers.
  * Layers this path takes: group_size <= 32768; a permutation is applied while the activations are staged.
+ * Alignment (every sliced entry: vptq_quant_gemv_sliced, _tokens, _grouped, _tokens_grouped): centroids, res_centroids, weight_scale,
+ * weight_bias, perm and scale_permuted 16 bytes (VPTQ_GEMV_EXACT with a permutation: bias_permuted too) - a layer that misses this has
+ * no layout (vptq_sliced_layout_supported* answer 0, the calls VPTQ_E_UNSUPPORTED); indices 4 bytes (set, not read); bias and y
+ * element-aligned; x 16 bytes (VPTQ_E_UNSUPPORTED: take vptq_quant_gemv); the layout's elems, blocks, first and wstart 4 bytes, res
+ * at an even address (uint8 and uint16 alike; a folded layout's uint8 res: any address), VPTQ_E_UNSUPPORTED otherwise; the workspace 16 bytes -
+ * the VPTQ_GEMV_SELECTIVE one 256 - (VPTQ_E_WORKSPACE).  The column parts of VPTQ_GEMV_COLUMN_PARTS advance weight_scale, weight_bias,
+ * perm, scale_permuted and bias_permuted by 2 x the part's first column bytes: a multiple of 16, so the parts keep the layer's alignment.
  */
 typedef struct VptqSlicedLayout {
   const void* elems;
@@ -485,7 +520,9 @@ VPTQ_API int vptq_quant_gemv_sliced_grouped(const VptqLayerDesc* descs, const Vp
  * a scratch buffer.  Folded layouts (two
  * tables, whole tables) are not taken.  Errors: NULL layouts / out (VPTQ_E_NULL), `parts` other than the layer's
  * (VPTQ_E_SHAPE), a part's n_slices other than vptq_sliced_layout_supported_for(part, VPTQ_GEMV_EXACT) (VPTQ_E_SHAPE), an out
- * pointer not 16-byte aligned (VPTQ_E_ALIGN); nothing is launched then.  One workgroup per row, the row assembled in LDS. */
+ * pointer not 16-byte aligned (VPTQ_E_ALIGN); nothing is launched then.  One workgroup per row, the row assembled in LDS.
+ * Alignment: the descriptor as the sliced entries take it; indices_out 16 bytes; elems 16 bytes, blocks / first / wstart 4 bytes, a
+ * uint8 res 4 bytes, a uint16 res 8 bytes (VPTQ_E_ALIGN). */
 VPTQ_API int vptq_sliced_layout_repack(const VptqLayerDesc* desc, const VptqSlicedLayout* layouts, int parts, void* indices_out,
                                        void* stream);
 
@@ -499,7 +536,9 @@ VPTQ_API int vptq_sliced_layout_repack(const VptqLayerDesc* desc, const VptqSlic
  * not read.  The kernel reads desc->perm (column g of the quantised matrix is column perm[g] of W), never desc->inv_perm: any
  * descriptor of the layer that its exact layouts are valid for serves, the one of the sliced entries and the dense one alike.  A
  * layout's `wstart`, where set (4-byte aligned), bounds the walk of a column tile; NULL is accepted.  One workgroup per vector-row
- * and column tile, the tile assembled in LDS and stored in 16-byte pieces; no workspace, no allocation: graph-capturable. */
+ * and column tile, the tile assembled in LDS and stored in 16-byte pieces; no workspace, no allocation: graph-capturable.
+ * Alignment: the descriptor as the sliced entries take it; W 16 bytes; the layout
+ * tensors as vptq_sliced_layout_repack takes them (elems 16, blocks / first / wstart 4, uint8 res 4, uint16 res 8 bytes: VPTQ_E_ALIGN). */
 VPTQ_API int vptq_dequant_sliced(const VptqLayerDesc* desc, const VptqSlicedLayout* layouts, int parts, void* W, void* stream);
 
 /* Build a sliced layout from the packed indices ON THE DEVICE: the forward direction of vptq_sliced_layout_repack, and byte for
@@ -530,7 +569,8 @@ VPTQ_API int vptq_dequant_sliced(const VptqLayerDesc* desc, const VptqSlicedLayo
  * wstart / res not 4-byte, total_blocks not 8-byte, elems not 16-byte aligned (VPTQ_E_ALIGN).  No allocation, no synchronisation.
  * flags | VPTQ_LAYOUT_ANY_SHAPE: the spec is taken as written - any slice count of 8 / 16 / 32, any 1 - 3 parts that divide the
  * columns, any table, whole_table and side_bytes the index widths allow - for layouts no GEMV entry of this
- * library takes (tests of the builder against its model, tools); everything that guards memory is still checked. */
+ * library takes (tests of the builder against its model, tools); everything that guards memory is still checked.
+ * Alignment: desc->indices 4 bytes (the only tensor of the descriptor the builder reads); the outputs as listed under Errors. */
 #define VPTQ_LAYOUT_ANY_SHAPE (1 << 16)
 typedef struct VptqSlicedLayoutSpec {
   int32_t flags;
@@ -564,7 +604,9 @@ VPTQ_API int vptq_sliced_layout_fill(const VptqLayerDesc* desc, const VptqSliced
  *   gemm_gather dt=f16|bf16 t=16|24|32 perm=0|1 tok=N tiles=N rgs=N
  *       t the index width, tok the tokens of the launch, tiles the column tiles (1024 columns) per row group (2 vector-rows), rgs the
  *       most row groups one workgroup walks.  Returns VPTQ_OK, the call's own validation error, or VPTQ_E_WORKSPACE (buf too small).
- * vptq_quant_gemv, vptq_quant_gemv_max_tokens and vptq_quant_gemv_kernel_name do not route here: callers choose this entry. */
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens and vptq_quant_gemv_kernel_name do not route here: callers choose this entry.
+ * Alignment (vptq_quant_gemm_gather, _gatherx, _gatherw): indices, centroids, res_centroids 16 bytes and weight_scale, weight_bias, perm,
+ * scale_permuted, bias_permuted 4 bytes (part of "supported"); x 16 bytes (the code given above); y and bias element-aligned. */
 VPTQ_API int vptq_quant_gemm_gather_supported(const VptqLayerDesc* desc, int tokens);
 VPTQ_API int vptq_quant_gemm_gather(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_gather_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
@@ -613,7 +655,9 @@ VPTQ_API int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* desc, int tok
  *       tok the tokens of the launch, tb its token blocks, rgs the most row groups (4 vector-rows) one workgroup walks, pass the
  *       instantiation <NRG, TB> of gemm_k256's pass it runs per row group (NRG row groups x TB token blocks share the 32 accumulator
  *       registers; NRG is 1).  Returns as vptq_quant_gemm_gather_instance does.
- * vptq_quant_gemv, vptq_quant_gemv_max_tokens (48) and vptq_quant_gemv_kernel_name do not route here: callers choose this entry. */
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens (48) and vptq_quant_gemv_kernel_name do not route here: callers choose this entry.
+ * Alignment: the layer by gemv_k256's rule (indices, codebooks, weight_scale, weight_bias, perm, scale_permuted, bias_permuted 16 bytes:
+ * part of "supported"); x 16 bytes (VPTQ_E_TOKENS, as above); y and bias element-aligned. */
 VPTQ_API int vptq_quant_gemm_k256w_supported(const VptqLayerDesc* desc, int tokens);
 VPTQ_API int vptq_quant_gemm_k256w(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_k256w_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
@@ -644,7 +688,10 @@ VPTQ_API int vptq_quant_gemm_gatherw_supported(const VptqLayerDesc* desc, int to
 VPTQ_API int vptq_quant_gemm_gatherw(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherw_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
-/* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits. */
+/* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits.
+ * Alignment: indices and codebooks 4 bytes; everything else - W included - element-aligned.  16-byte aligned W, weight_scale /
+ * weight_bias and indices let the kernel store, read the norm tensors and read the index stream in 16-byte pieces (store= / norm= / idx=
+ * of vptq_dequant_instance); the bits written do not depend on it. */
 VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
 /* Diagnostic (ABI 12): WHICH INSTANTIATION of dequant_kernel<DT, V, TAB> vptq_dequant(desc, W) would launch and which paths its
  * threads take, as one line of `dequant key=value ...` - the launcher's own decision and the kernel's own predicates, evaluated on
@@ -660,6 +707,9 @@ VPTQ_API int vptq_dequant(const VptqLayerDesc* desc, void* W, void* stream);
  * Returns VPTQ_OK, vptq_dequant's own validation error, or VPTQ_E_WORKSPACE when buf (bytes long, NUL included) is too small. */
 VPTQ_API int vptq_dequant_instance(const VptqLayerDesc* desc, const void* W, char* buf, size_t bytes);
 
+/* Alignment: every pointer element-aligned (gemv_v2).  The LDS-resident kernels (gemv_lds / gemv_lds_mfma fmt=v2*: v = 8, k <= 8192,
+ * kr <= 512, in_features a multiple of 8) are taken where indices, centroids and res_centroids are 16-byte, res_indices 8-byte and x
+ * 16-byte aligned (gemv_lds_mfma: scale_weights and scale_bias 16 bytes too); vptq_quant_gemv_v2_instance answers for such an x. */
 VPTQ_API int vptq_quant_gemv_v2(const VptqV2Desc* desc, const void* x, void* y, int tokens,
                        int flags, void* stream);
 

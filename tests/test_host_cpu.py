@@ -293,6 +293,52 @@ def test_validation_errors_without_gpu():
     assert lib.vptq_quant_gemv_v2(v2, 16, 16, 16, 0, None) == -5           # tokens < 16
 
 
+def test_alignment_rules_of_the_header_without_gpu():
+    """The "Alignment:" statements of include/vptq_hip.h as return codes and route names, with fake pointers (nothing is launched
+    or read): a kernel's rule that is not met hands the call to the next kernel, down to gemv_generic at element alignment; what an
+    ENTRY needs is refused with the documented code (tests/test_operand_placement_gpu.py launches every minimum on a device)."""
+    lib = B.lib()
+    name = lambda d, tokens=1, flags=0: lib.vptq_quant_gemv_kernel_name(d, tokens, flags)   # noqa: E731
+    fields = ("indices", "centroids", "res_centroids", "weight_scale", "weight_bias", "perm", "scale_permuted", "bias_permuted")
+
+    def shifted(d, by, only=None):
+        q = B.LayerDesc.from_buffer_copy(d)
+        for f in only or fields:
+            if getattr(q, f):
+                setattr(q, f, getattr(q, f) + by)
+        return q
+    # the canonical format: gemv_k256 / gemv_k256m need 16 bytes; 4-byte operands take gemv_gatherx; 2-byte ones gemv_generic
+    for perm in (False, True):
+        d = _canonical_desc(4096, 264, perm=perm)
+        assert name(d, flags=B.GEMV_EXACT) == b"gemv_k256_kernel"
+        assert name(shifted(d, 16), flags=B.GEMV_EXACT) == b"gemv_k256_kernel"          # 16 bytes and no more
+        for f in ("indices", "centroids", "res_centroids", "weight_scale", "weight_bias") + (("perm", "scale_permuted", "bias_permuted") if perm else ()):
+            # (gemv_gatherx reads a 16-byte codebook entry of v = 8 whole: codebooks that miss 16 bytes take gemv_generic)
+            want = b"gemv_generic_kernel" if f in ("centroids", "res_centroids") else b"gemv_gatherx_kernel"
+            assert name(shifted(d, 8, (f,)), flags=B.GEMV_EXACT) == want, f
+        assert name(shifted(d, 4, ("indices", "weight_scale", "weight_bias", "perm", "scale_permuted", "bias_permuted")),
+                    flags=B.GEMV_EXACT) == b"gemv_gatherx_kernel"
+        for f in ("weight_scale", "weight_bias") + (("perm",) if perm else ()):
+            assert name(shifted(d, 2, (f,)), flags=B.GEMV_EXACT) == b"gemv_generic_kernel", f
+        # tables that are not 4-byte aligned: refused, nothing launched
+        for f in ("indices", "centroids", "res_centroids"):
+            assert lib.vptq_quant_gemv(shifted(d, 2, (f,)), 1 << 24, 1 << 25, 1, 0, None, 0, None) == B.E_ALIGN, f
+            assert name(shifted(d, 2, (f,))) is None
+    # a large-codebook layer: gemv_gather needs 16-byte tables and 4-byte norm tensors; with less gemv_gatherx (4) / gemv_generic (2)
+    g = _format_desc(8, 65536, 256, 4096, 264)
+    assert name(g) == b"gemv_gather_kernel" and name(shifted(g, 4, ("weight_scale", "weight_bias"))) == b"gemv_gather_kernel"
+    assert name(shifted(g, 8, ("indices",))) == b"gemv_gatherx_kernel"
+    assert name(shifted(g, 8, ("centroids",))) == b"gemv_generic_kernel"                 # (gemv_gatherx: 16-byte entries of v = 8)
+    assert name(shifted(g, 2, ("weight_scale",))) == b"gemv_generic_kernel"
+    # LDS-resident codebooks: 16-byte codebooks and norm tensors, the index stream 4 bytes
+    l = _format_desc(8, 4096, 256, 4096, 264)
+    assert name(l, flags=B.GEMV_EXACT) == b"gemv_lds_kernel" == name(shifted(l, 4, ("indices",)), flags=B.GEMV_EXACT)
+    assert name(shifted(l, 8, ("weight_scale",)), flags=B.GEMV_EXACT) == b"gemv_gatherx_kernel"
+    # the fused GEMM: x 16 bytes (VPTQ_E_ALIGN)
+    d = _canonical_desc(4096, 264)
+    assert lib.vptq_quant_gemm(d, (1 << 24) + 8, 1 << 25, 32, 0, None, 0, None) == B.E_ALIGN
+
+
 def test_cpu_tensors_raise_no_silent_fallback():
     L, x, y, cfg, _ = load_golden("canon_k256x2")
     m = spec_to_module(L, "cpu")
