@@ -688,6 +688,40 @@ VPTQ_API int vptq_quant_gemm_gatherw_supported(const VptqLayerDesc* desc, int to
 VPTQ_API int vptq_quant_gemm_gatherw(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherw_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of layers WITH a column permutation: x[perm] gathered once per call into a workspace (gemm_gather_px.hip; added
+ * within ABI 12; present when the symbols are).  The three entries above read a permuted x two bytes at a time in every row group of
+ * 16 outputs.  This entry writes xp[t][c] = x[t][perm[c]] once (permute_x_tokens_kernel: a thread owns 8 columns and up to 4 tokens,
+ * one 16-byte store per token) and then launches the layer's own kernel - gemm_gather_kernel or gemm_gatherx_kernel for 1 - 16 tokens,
+ * gemm_gatherw_kernel for 17 - 48 - in its form WITHOUT a permutation over xp, scale_permuted and bias_permuted.  Both launches go to
+ * `stream`; nothing is allocated: graph-capturable.  The outputs are BIT-IDENTICAL to those vptq_quant_gemm_gather / _gatherx /
+ * _gatherw give for the same descriptor, and carry their guarantees.  A layer without a permutation is served too: the plain launch
+ * alone, the workspace is not touched and may be NULL.
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags as the three entries take them.
+ * vptq_quant_gemm_gather_px_workspace_bytes: tokens * group_size * 2 rounded up to 256; 0 for a layer without a permutation and
+ *   where vptq_quant_gemm_gather_px_supported answers 0.
+ * vptq_quant_gemm_gather_px_supported: 1 exactly where the layer's own entry answers 1 for that token count
+ *   (vptq_quant_gemm_gather_supported or vptq_quant_gemm_gatherx_supported for 1 - 16 tokens, vptq_quant_gemm_gatherw_supported for
+ *   17 - 48), else 0; host logic.
+ * vptq_quant_gemm_gather_px: NULL desc / x / y VPTQ_E_NULL; tokens outside [1, 48] VPTQ_E_TOKENS; a layer it does not serve
+ *   VPTQ_E_UNSUPPORTED; an x that is not 16-byte aligned the code of the layer's own entry (VPTQ_E_UNSUPPORTED up to 16 tokens,
+ *   VPTQ_E_TOKENS from 17); then, for a layer with a permutation, a NULL workspace or fewer workspace_bytes than the query answers
+ *   VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned VPTQ_E_ALIGN; nothing is launched then.
+ * vptq_quant_gemm_gather_px_instance: both launches as one line (host logic, without a device the CU count is taken as 256):
+ *   permute_x_tokens g=N tok=N grid=XxY tpt=4 | <inner>      with a permutation
+ *   none | <inner>                                           without one
+ *       g the columns, tok the tokens, grid X workgroups of 64 threads (8 columns each) x Y token slices, tpt the tokens per thread;
+ *       <inner> the line vptq_quant_gemm_gather_instance / _gatherx_instance / _gatherw_instance prints for the descriptor without
+ *       its permutation (always perm=0).  Returns as vptq_quant_gemm_gather_instance does.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: the layer as vptq_quant_gemm_gather, _gatherx, _gatherw take it (indices, centroids, res_centroids 16 bytes and
+ * weight_scale, weight_bias, perm, scale_permuted, bias_permuted 4 bytes: part of "supported"); x 16 bytes (the code given above); the
+ * workspace 16 bytes (VPTQ_E_ALIGN); y and bias element-aligned. */
+VPTQ_API size_t vptq_quant_gemm_gather_px_workspace_bytes(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gather_px_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gather_px(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gather_px_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits.
  * Alignment: indices and codebooks 4 bytes; everything else - W included - element-aligned.  16-byte aligned W, weight_scale /
  * weight_bias and indices let the kernel store, read the norm tensors and read the index stream in 16-byte pieces (store= / norm= / idx=

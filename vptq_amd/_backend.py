@@ -171,6 +171,12 @@ EXPORTS = {
     "vptq_quant_gemm_gatherw_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gatherw": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
     "vptq_quant_gemm_gatherw_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 48 tokens of a layer of those three entries with x[perm] written once into a workspace, then the
+    # layer's kernel in its form without a permutation (gemm_gather_px.hip): workspace query, query, call, instance text
+    "vptq_quant_gemm_gather_px_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gather_px_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gather_px": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather_px_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

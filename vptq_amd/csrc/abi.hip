@@ -1262,6 +1262,72 @@ int vptq_quant_gemm_gatherw_supported(const VptqLayerDesc* d, int tokens) { retu
 int vptq_quant_gemm_gatherw(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* stream) { return batched_launch(kGemmGatherW, d, x, y, tokens, flags, stream); }
 int vptq_quant_gemm_gatherw_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) { return batched_instance(kGemmGatherW, d, tokens, buf, bytes); }
 
+// ---- gemm_gather_px.hip (added within ABI 12): 1 - 48 tokens of a layer of the three entries above with x[perm] written once into a
+// workspace, then the layer's own kernel in its form without a permutation.  The entry of a (layer, token count): gemm_gather or
+// gemm_gatherx up to 16 tokens (a layer has one of the two), gemm_gatherw from 17; NULL where none serves it
+static const BatchedDecode* px_inner(const VptqLayerDesc& d, int tokens) {
+  if (tokens > kGemmGather.tok_hi) return kGemmGatherW.eligible(d, tokens) ? &kGemmGatherW : nullptr;
+  if (kGemmGather.eligible(d, tokens)) return &kGemmGather;
+  return kGemmGatherX.eligible(d, tokens) ? &kGemmGatherX : nullptr;
+}
+// the checks of the entry and its `_instance` on the token count and the layer; *k: the inner entry
+static int px_validate(const VptqLayerDesc* d, int tokens, const BatchedDecode** k) {
+  if (tokens < kGemmGather.tok_lo || tokens > kGemmGatherW.tok_hi)
+    return fail(VPTQ_E_TOKENS, "tokens %d outside [%d, %d]", tokens, kGemmGather.tok_lo, kGemmGatherW.tok_hi);
+  *k = px_inner(*d, tokens);
+  if (!*k) return fail(VPTQ_E_UNSUPPORTED, "gemm_gather_px serves the layers of gemm_gather / gemm_gatherx (1 - 16 tokens) and gemm_gatherw (17 - 48)");
+  return VPTQ_OK;
+}
+
+size_t vptq_quant_gemm_gather_px_workspace_bytes(const VptqLayerDesc* d, int tokens) {
+  if (validate_layer(d) != VPTQ_OK || tokens < kGemmGather.tok_lo || tokens > kGemmGatherW.tok_hi || !px_inner(*d, tokens)) return 0;
+  return vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+}
+
+int vptq_quant_gemm_gather_px_supported(const VptqLayerDesc* d, int tokens) {
+  return validate_layer(d) == VPTQ_OK && tokens >= kGemmGather.tok_lo && tokens <= kGemmGatherW.tok_hi && px_inner(*d, tokens) ? 1 : 0;
+}
+
+int vptq_quant_gemm_gather_px(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  const BatchedDecode* k = nullptr;
+  if (const int rc = px_validate(d, tokens, &k)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(k->misaligned, "gemm_gather_px (%s): x must be 16-byte aligned", k->name);
+  const size_t need = vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+  if (need > 0) {
+    if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gather_px: workspace of %zu bytes needed", need);
+    if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather_px: the workspace must be 16-byte aligned");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+  if (need == 0) {   // no permutation: the layer's own launch, the workspace is not touched
+    const hipError_t e = k->launch(*d, x, y, tokens, out_f32, st);
+    return e == hipSuccess ? VPTQ_OK : hip_fail(e, k->launch_what);
+  }
+  hipError_t e = vptq::launch_permute_x_tokens(*d, x, workspace, tokens, st);
+  if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  const VptqLayerDesc plain = vptq::gemm_gather_px_plain(*d);
+  e = k->launch(plain, workspace, y, tokens, out_f32, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, k->launch_what);
+}
+
+int vptq_quant_gemm_gather_px_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  const BatchedDecode* k = nullptr;
+  if (const int rc = px_validate(d, tokens, &k)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const vptq::GemmGatherPxDecision D = vptq::gemm_gather_px_decide(*d, tokens);
+  if (D.perm) t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d | ", D.g, D.tok, D.grid_x, D.grid_y, D.tpt);
+  else t.add("none | ");
+  k->print(t, vptq::gemm_gather_px_plain(*d), tokens);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {
   int rc = validate_layer(d);

@@ -226,6 +226,16 @@ struct GemmGatherXDecision { bool f16, perm; int v, ib, rb, res, res_bytes, tok,
 GemmGatherXDecision gemm_gatherx_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gatherx(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
 
+// gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
+// x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)
+// - scale_permuted / bias_permuted as scale / bias, no permutation - with x = xp: the bits of the layer's own entry
+size_t gemm_gather_px_workspace_bytes(const VptqLayerDesc& d, int tokens);   // 0 without a permutation
+// what launch_permute_x_tokens launches: grid_x workgroups of 64 chunks of 8 columns x grid_y slices of tpt tokens
+struct GemmGatherPxDecision { bool perm; int g, tok, tpt, grid_x, grid_y; };
+GemmGatherPxDecision gemm_gather_px_decide(const VptqLayerDesc& d, int tokens);
+VptqLayerDesc gemm_gather_px_plain(const VptqLayerDesc& d);
+hipError_t launch_permute_x_tokens(const VptqLayerDesc& d, const void* x, void* xp, int tokens, hipStream_t st);
+
 // gemm_fused.hip - canonical format, many tokens: dequantised tile -> LDS -> 32x32x16 MFMA
 bool gemm_fused_eligible(const VptqLayerDesc& d);
 size_t gemm_fused_workspace_bytes(const VptqLayerDesc& d, int tokens);

@@ -233,6 +233,57 @@ def gemm_gatherw_route(vector_len: int, num_centroids: int, num_res_centroids: i
                for kr, min_el, min_tok, max_tok in _GEMM_GATHERW_CELLS)
 
 
+# WHICH (format, shape, token count) of the three kernels' layers WITH A COLUMN PERMUTATION take `vptq_quant_gemm_gather_px` - x[perm]
+# written once per call into the stream's workspace, then the layer's kernel in its form without a permutation (gemm_gather_px.hip),
+# 5 - 48 tokens - in place of the route a permuted layer has: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`
+# ahead of the three route functions above (which are what they were; layers without a permutation never come here).  A cell is
+# (vector length, main centroids, residual centroids, least index elements, least tokens, most tokens), routed by the rule above
+# `_GEMM_GATHER_CELLS`: px beats the route a permuted layer takes WITHOUT it (5 - 8 tokens: the gemv_gather / gemv_gatherx launches;
+# 9 - 16: the in-kernel permuted gemm_gather / gemm_gatherx where their cells route it, else the dense route; 17 - 48: the dense
+# route) by more than the larger of 5 % and three times the larger run-to-run spread, in every measured cell of the region, in both
+# dtypes; the routed token counts of a layer are one interval; no cell lies under GEMM_GATHERW_MIN_ELEMENTS (4 M index elements).
+# tools/gemm_gather_px_bench.py writes the table.  VPTQ_GEMM_GATHER_PX=1 / 0 (with VPTQ_TUNING=1): every supported permuted layer
+# from 5 to 48 tokens / none.
+#
+# profiles/r25/table.md, profiles/r25/README.md (one MI355X, fp16 and bf16, permuted layers of 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 /
+# 9 / 12 / 16 / 17 / 24 / 32 / 33 / 40 / 48; 530 cells, px has the bits of the layer's own entry in every one, 526 win; run-to-run spreads
+# under 3 % in all but two cells):
+#   v8-k65536-0 / -256 / -65536   5 - 8 tokens 0.16 - 0.77 of the gemv_gather launches, 9 - 16 tokens 0.18 - 0.64 of the in-kernel permuted
+#                                 gemm_gather (itself 1.05 - 2.6 times the dense route), 17 - 40 tokens 0.37 - 0.93 of the dense route: every
+#                                 cell of every shape wins.  48 tokens: 4096 x 14336 (7 M elements) loses or is level in -0 and -256
+#                                 (0.92 - 1.09), the other layers from 7 M up win (0.49 - 0.81), -65536 wins everywhere (0.54 - 0.93).  So
+#                                 5 - 40 tokens from 7 M index elements, 5 - 48 from 8 M (8192 x 8192); -65536: 5 - 48 from 7 M.
+#   v16-k65536-0 / -1024          5 - 16 tokens 0.17 - 0.69 of the in-kernel permuted gemm_gatherx in every cell: routed from the floor
+#                                 (8192 x 8192 = 4 M elements of v = 16) up
+#   v8-k32768-0, v8-k65536-4096   5 - 16 tokens 0.19 - 0.72 of gemv_gatherx (5 - 8, under 8 M) / the permuted gemm_gatherx: from 7 M up
+# 4096 x 4096 (and the 3.5 M-element v = 16 layers) win too (0.30 - 0.88; one bf16 cell at 48 tokens short of the rule) but lie under the
+# floor: they keep their routes - at 9 - 16 tokens that is the in-kernel permuted kernel, measured here at 1.05 - 3.0 times the dense route
+# (STATUS.md, item 4c(b)).
+_GEMM_GATHER_PX_CELLS = (
+    (8, 65536, 0, 7 << 20, 5, 40), (8, 65536, 0, 8 << 20, 5, 48), (8, 65536, 256, 7 << 20, 5, 40), (8, 65536, 256, 8 << 20, 5, 48),
+    (8, 65536, 65536, 7 << 20, 5, 48),
+    (16, 65536, 0, 4 << 20, 5, 16), (16, 65536, 1024, 4 << 20, 5, 16), (8, 32768, 0, 7 << 20, 5, 16), (8, 65536, 4096, 7 << 20, 5, 16),
+)
+GEMM_GATHER_PX_MIN_TOKENS, GEMM_GATHER_PX_MAX_TOKENS = 5, 48
+_GEMM_GATHER_PX_MODE = (B.tune_env("VPTQ_GEMM_GATHER_PX", "auto") or "auto").strip().lower()
+
+
+def gemm_gather_px_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
+    """does a layer WITH a column permutation of this format and shape take `vptq_quant_gemm_gather_px` for `tokens` tokens?  Pure:
+    no device, no library (whether the library serves the layer is `vptq_quant_gemm_gather_px_supported`'s answer; that the layer
+    has a permutation is the caller's)."""
+    if _GEMM_GATHER_PX_MODE in ("0", "off") or not GEMM_GATHER_PX_MIN_TOKENS <= tokens <= GEMM_GATHER_PX_MAX_TOKENS:
+        return False
+    entry = _batched_decode_entry(vector_len, num_centroids, num_res_centroids)
+    if entry is None or (tokens > GEMM_GATHER_MAX_TOKENS and entry != "vptq_quant_gemm_gather") or in_features % 8:
+        return False   # (17 - 48 tokens: gemm_gatherw's formats only)
+    if _GEMM_GATHER_PX_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and n_el >= max(min_el, GEMM_GATHERW_MIN_ELEMENTS) and
+               min_tok <= tokens <= max_tok for v, k, kr, min_el, min_tok, max_tok in _GEMM_GATHER_PX_CELLS)
+
+
 def _dense_from_layout(layer) -> bool:
     """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (a library without the entry, added within ABI 11:
     never - the repack route stays)"""
@@ -335,9 +386,12 @@ def compact_model(model: nn.Module, force: bool = False) -> dict:
 def prepare_model(model: nn.Module, stream=None) -> dict:
     """`VQuantLinear.prepare(stream)` over every layer of `model`: the sliced layouts of the large-codebook formats are built now (by
     the library's builder, layer by layer) instead of inside the first decode step, and every layer has its one-token workspace for
-    `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  Returns {"layers": {name: {"built", "bytes",
-    "seconds"}}, "built": layers with a layout, "bytes", "seconds"}."""
+    `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  The stream's `B.gemv_workspace` is grown to
+    the largest x[perm] copy (`vptq_quant_gemm_gather_px_workspace_bytes` at 48 tokens) of the permuted layers `gemm_gather_px_route`
+    routes, so a 5 - 48 token step captured afterwards keeps that route.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
+    "built": layers with a layout, "bytes", "seconds"}."""
     rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
+    px = {}   # device index -> (device, most workspace bytes of its routed permuted layers)
     for name, m in model.named_modules():
         if not isinstance(m, VQuantLinear):
             continue
@@ -346,6 +400,17 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
         rep["built"] += int(r["built"] in ("exact", "folded", "selective"))
         rep["bytes"] += r["bytes"]
         rep["seconds"] += r["seconds"]
+        need = m._gemm_gather_px_workspace_bytes()
+        if need:
+            cache = m._descriptor()
+            px[cache.device_index] = (cache.device, max(need, px.get(cache.device_index, (None, 0))[1]))
+    if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
+        return rep
+    for dev_index, (dev, need) in px.items():
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream(dev) if stream is None else stream
+            with torch.cuda.stream(s):
+                B.gemv_workspace(dev_index, s.cuda_stream, need)
     return rep
 
 
@@ -615,6 +680,10 @@ class VQuantLinear(nn.Module):
                 "path, which is outside this inference package; construct the layer with "
                 "enable_proxy_error=False (HF does).")
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        if self.enable_perm and GEMM_GATHER_PX_MIN_TOKENS <= tokens <= GEMM_GATHER_PX_MAX_TOKENS and x.is_cuda and self.__dict__.get("_px", True):
+            y = self._gemm_gather_px_cached(x, tokens)   # (x[perm] once, then the layer's kernel without a permutation, where `gemm_gather_px_route` says so)
+            if y is not None:
+                return y
         if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_bd_entry", True):
             y = self._batched_decode_cached(x, tokens)   # (the large-codebook formats' batched decode, where the layer's route function says so)
             if y is not None:
@@ -1141,9 +1210,46 @@ class VQuantLinear(nn.Module):
             return None
         return self._batched_entry_launch("vptq_quant_gemm_gatherw", "_gatherw_ok", GEMM_GATHERW_MAX_TOKENS, x, tokens)
 
-    def _batched_entry_launch(self, entry: str, ok_key: str, ask_tokens: int, x: torch.Tensor, tokens: int):
+    def _gemm_gather_px_cached(self, x: torch.Tensor, tokens: int):
+        """5 - 48 tokens of a large-codebook layer WITH a column permutation in one call of `vptq_quant_gemm_gather_px` (x[perm]
+        once into the stream's workspace, then the layer's kernel in its form without a permutation) where `gemm_gather_px_route`
+        gives the layer's (format, shape, tokens) to it, GEMV_FORCE_GENERIC is not set and the library serves the layer; None: the
+        routes of before - also where a stream capture is in progress and the stream's workspace is too small (`prepare_model`
+        sizes it).  Compact layers hand it the repacked stream, as the other batched entries do."""
+        if "_px" not in self.__dict__:   # (static module configuration: decided once)
+            self.__dict__["_px"] = bool(self.enable_perm) and _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self)) is not None and \
+                self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm and \
+                getattr(B.lib(), "vptq_quant_gemm_gather_px", None) is not None
+        if not self.__dict__["_px"] or \
+                not gemm_gather_px_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
+                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
+            return None
+        # (`_supported` is asked for the token window of the call: the inner kernel changes at 17 tokens)
+        wide = tokens > GEMM_GATHER_MAX_TOKENS
+        return self._batched_entry_launch("vptq_quant_gemm_gather_px", "_px_ok_w" if wide else "_px_ok", GEMM_GATHER_PX_MAX_TOKENS if wide else GEMM_GATHER_MAX_TOKENS,
+                                          x, tokens, workspace=True)
+
+    def _gemm_gather_px_workspace_bytes(self) -> int:
+        """bytes of stream workspace the largest call `_gemm_gather_px_cached` can route for this layer needs (`prepare_model` grows
+        the stream's buffer to it); 0: the layer never takes that route"""
+        if not self.enable_perm or _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self)) is None or \
+                self.num_codebooks != 1 or self.enable_outlier or not self.enable_norm:
+            return 0
+        cp = self.__dict__.get("_compact")
+        if cp is None and not self._parameters["indices"].is_cuda:
+            return 0
+        routed = [t for t in range(GEMM_GATHER_PX_MIN_TOKENS, GEMM_GATHER_PX_MAX_TOKENS + 1)
+                  if gemm_gather_px_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, t)]
+        query = getattr(B.lib(), "vptq_quant_gemm_gather_px_workspace_bytes", None)
+        if not routed or query is None:
+            return 0
+        return int(query(self._descriptor().desc, routed[-1]))
+
+    def _batched_entry_launch(self, entry: str, ok_key: str, ask_tokens: int, x: torch.Tensor, tokens: int, workspace: bool = False):
         """one launch of a batched-decode entry; `_supported`'s answer cached per descriptor generation under `ok_key`.  None: the
-        library does not serve the layer, or x is not what the entry takes (the other routes raise the shape / dtype / device errors)"""
+        library does not serve the layer, or x is not what the entry takes (the other routes raise the shape / dtype / device errors).
+        workspace: the entry takes (workspace, workspace_bytes) in front of the stream - `B.gemv_workspace` of this (device, stream),
+        sized by the entry's `_workspace_bytes` query; None too where that buffer is too small and cannot grow (a stream capture)"""
         cache = self._descriptor()
         desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
         ok = self.__dict__.get(ok_key)
@@ -1156,13 +1262,19 @@ class VQuantLinear(nn.Module):
             x = x.contiguous()
         if x.data_ptr() % 16:
             return None
-        y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
         cp = self.__dict__.get("_compact")
         with torch.cuda.device(dev):
             sp = B.current_stream_ptr(dev)
+            ws_args = ()
+            if workspace:
+                need = getattr(B.lib(), entry + "_workspace_bytes")(desc, tokens)
+                ws_args = B.gemv_workspace(dev_index, sp, need)
+                if need and ws_args[0] is None:
+                    return None
+            y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
             if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
                 desc = self._repacked_desc(desc, dev_index, sp)
-            rc = getattr(B.lib(), entry)(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, sp)
+            rc = getattr(B.lib(), entry)(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, *ws_args, sp)
         if rc:
             B.check(rc, entry)
         return y

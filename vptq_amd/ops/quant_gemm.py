@@ -20,7 +20,8 @@ from torch.nn import functional as F
 
 from vptq_amd import _backend as B
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w", "quant_gemv_v2"]
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w",
+           "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
 # says (`_backend.set_arithmetic`: "reference" is the default since round 5, "folded" the opt-in fast form)
@@ -205,6 +206,15 @@ def quant_gemm(
         # one does not own): the token counts the kernel's route function gives it, as `VQuantLinear.forward` routes them
         from vptq_amd.layers.vqlinear import gemm_gather_route, gemm_gatherx_route
         kr = num_res_centroids if enable_residual else 0
+        # a layer with a column permutation: x[perm] once into the stream's workspace, then the plain form of the layer's kernel
+        # (gemm_gather_px.hip), where its own route function says so; None (a capture with too small a workspace): the routes below
+        from vptq_amd.layers.vqlinear import gemm_gather_px_route
+        if perm is not None and not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
+                gemm_gather_px_route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
+                B.lib().vptq_quant_gemm_gather_px_supported(gdesc, tokens):
+            y = _quant_gemm_px(x, gdesc, out_features)
+            if y is not None:
+                return y
         for route, entry in ((gemm_gather_route, "vptq_quant_gemm_gather"), (gemm_gatherx_route, "vptq_quant_gemm_gatherx")):
             if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
                     route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
@@ -323,6 +333,40 @@ def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool =
     index path for any total width and 32-byte entries; the reference's roundings).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gatherx_supported` accepts; out_f32: the un-rounded fp32 sums."""
     return _quant_gemm_batched("vptq_quant_gemm_gatherx", x, desc, out_features, out_f32)
+
+
+def _quant_gemm_px(x: torch.Tensor, desc, out_features: int, out_f32: bool = False, flags: int = 0):
+    """one call of `vptq_quant_gemm_gather_px` with this (device, stream)'s `B.gemv_workspace`; None where the layer needs a
+    workspace and there is none: a stream capture is in progress and the buffer is too small (nothing is allocated then)"""
+    tokens = x.numel() // x.shape[-1]
+    dev = x.device
+    if not x.is_contiguous():
+        x = x.contiguous()
+    with torch.cuda.device(dev):
+        sp = B.current_stream_ptr(dev)
+        need = B.lib().vptq_quant_gemm_gather_px_workspace_bytes(desc, tokens)
+        ws, wsb = B.gemv_workspace(dev.index if dev.index is not None else torch.cuda.current_device(), sp, need)
+        if need and ws is None:
+            return None
+        y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
+        B.check(B.lib().vptq_quant_gemm_gather_px(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | flags | (B.GEMV_OUT_F32 if out_f32 else 0),
+                                                  ws, wsb, sp), "vptq_quant_gemm_gather_px")
+    return y
+
+
+def quant_gemm_gather_px(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 1 - 48 tokens of a large-codebook layer WITH a column permutation (`vptq_quant_gemm_gather_px`,
+    gemm_gather_px.hip): x[:, perm] is written once into this stream's workspace (`B.gemv_workspace`), then the layer's
+    batched-decode kernel runs in its form without a permutation - the bits of `quant_gemm_gather` / `quant_gemm_gatherx` (1 - 16
+    tokens) / `quant_gemm_gatherw` (17 - 48) on the same descriptor, without their two-byte gathers of x in every row group.  A layer
+    without a permutation takes the plain launch alone.  `desc` = a LayerDesc of a layer `vptq_quant_gemm_gather_px_supported`
+    accepts; out_f32: the un-rounded fp32 sums.  Raises where a stream capture is in progress and the workspace is too small
+    (`prepare_model` sizes it beforehand)."""
+    y = _quant_gemm_px(x, desc, out_features, out_f32)
+    if y is None:
+        raise RuntimeError("quant_gemm_gather_px: the stream's workspace is too small and cannot grow during a capture "
+                           "(call it once, or vptq_amd.prepare_model, before capturing)")
+    return y
 
 
 def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
