@@ -151,6 +151,7 @@ def test_census_of_the_instantiations():
 
 
 def test_route_function_is_pure_and_bounded(monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     route = vq.gemm_gather_route
     # formats the kernel does not have never route, whatever the shape and token count
@@ -166,8 +167,8 @@ def test_route_function_is_pure_and_bounded(monkeypatch):
             on = [t for t in range(5, 17) if route(8, 65536, kr, O, I, t)]
             assert on == list(range(on[0], 17)) if on else True      # from some token count on, up to 16
     # the knob: every supported format from 5 tokens / none
-    monkeypatch.setattr(vq, "_GEMM_GATHER_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_MODE", "1")
     assert all(route(8, 65536, 256, 512, 2048, t) for t in range(5, 17)) and not route(8, 65536, 256, 512, 2048, 4)
     assert not route(8, 65536, 256, 512, 2048, 17) and not route(16, 65536, 0, 512, 2048, 12)
-    monkeypatch.setattr(vq, "_GEMM_GATHER_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_MODE", "0")
     assert not any(route(8, 65536, kr, 8192, 8192, t) for kr in (0, 256, 65536) for t in range(0, 20))

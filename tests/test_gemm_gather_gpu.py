@@ -215,6 +215,7 @@ class _Spy:
 @pytest.mark.parametrize("T,dt", [(24, "f16"), (16, "bf16")])
 def test_module_takes_the_entry_where_the_route_says_so(T, dt, dev, monkeypatch):
     from vptq_amd import _backend as B
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     L = layer(2048, 512, T, dt, bias=1)
     m = spec_to_module(L, dev)
@@ -232,7 +233,7 @@ def test_module_takes_the_entry_where_the_route_says_so(T, dt, dev, monkeypatch)
     if routed:
         am.check_outputs(_np(y), mm, aa, dt, False, what="VQuantLinear.forward, 12 tokens")
     # the route function on: the entry itself, and a compact layer against its packed twin
-    monkeypatch.setattr(vq, "_GEMM_GATHER_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_MODE", "1")
     y1 = m(xt)
     am.check_outputs(_np(y1), mm, aa, dt, False, what="VQuantLinear.forward, 12 tokens, routed")
     m2 = spec_to_module(L, dev)

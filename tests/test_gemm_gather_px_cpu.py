@@ -182,10 +182,11 @@ def test_instance_line_is_the_permute_shape_and_the_inner_kernels_own_line():
 
 
 def test_route_function_is_pure_follows_its_own_cells_and_obeys_its_knob(monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     route = vq.gemm_gather_px_route
     assert (vq.GEMM_GATHER_PX_MIN_TOKENS, vq.GEMM_GATHER_PX_MAX_TOKENS) == (5, 48)
-    assert vq._GEMM_GATHER_PX_MODE == "auto"
+    assert bd._GEMM_GATHER_PX_MODE == "auto"
     shapes = ((8192, 8192), (4096, 4096), (14336, 4096), (4096, 14336), (28672, 8192), (512, 2048), (36, 1032))
 
     def by_the_cells(cells, v, k, kr, O, I, t):
@@ -205,50 +206,51 @@ def test_route_function_is_pure_follows_its_own_cells_and_obeys_its_knob(monkeyp
                 assert not on, (O, I, v, k, kr)                             # no cell under 4 M index elements
 
     # the committed table: well-formed, nothing under the floor `GEMM_GATHERW_MIN_ELEMENTS` states, and followed exactly
-    assert vq.GEMM_GATHERW_MIN_ELEMENTS == 4 << 20
-    assert all(len(c) == 6 and c[3] >= 4 << 20 and 5 <= c[4] <= c[5] <= 48 for c in vq._GEMM_GATHER_PX_CELLS)
-    check(vq._GEMM_GATHER_PX_CELLS)
+    assert bd.GEMM_GATHERW_MIN_ELEMENTS == 4 << 20
+    assert all(len(c) == 6 and c[3] >= 4 << 20 and 5 <= c[4] <= c[5] <= 48 for c in bd._GEMM_GATHER_PX_CELLS)
+    check(bd._GEMM_GATHER_PX_CELLS)
     # a monkeypatched table is followed exactly - cells of other formats, sizes under the floor and inner kernels that end at 16 included
     cells = ((8, 65536, 256, 7 << 20, 9, 40), (8, 65536, 0, 1 << 20, 17, 48), (16, 65536, 0, 4 << 20, 5, 48), (8, 32768, 0, 28 << 20, 12, 16),
              (8, 256, 256, 4 << 20, 5, 48))
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_CELLS", cells)
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_CELLS", cells)
     check(cells)
     assert route(8, 65536, 256, 8192, 8192, 9) and route(8, 65536, 256, 8192, 8192, 40) and not route(8, 65536, 256, 8192, 8192, 41)
     assert not route(8, 65536, 256, 4096, 4096, 20) and not route(8, 65536, 0, 4096, 4096, 20)      # 2 M elements: under the floor
     assert route(16, 65536, 0, 8192, 8192, 16) and not route(16, 65536, 0, 8192, 8192, 17)          # gemm_gatherx ends at 16 tokens
     assert not route(8, 65536, 256, 8192, 8196, 20)                                                   # in_features % 8
     # the knob: 1 - every layer of the three kernels from 5 tokens; 0 - none
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", "1")
     assert all(route(8, 65536, kr, 36, 1032, t) for kr in KRS for t in range(5, 49))
     assert all(route(v, k, kr, 36, 1032, t) for v, k, kr in GATHERX for t in range(5, 17))
     assert not any(route(v, k, kr, 8192, 8192, t) for v, k, kr in GATHERX for t in range(17, 49))
     assert not any(route(v, k, kr, 8192, 8192, t) for v, k, kr in OTHER for t in range(0, 70))
     assert not route(8, 65536, 256, 8192, 8192, 4) and not route(8, 65536, 256, 8192, 8192, 49)
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", "0")
     assert not any(route(v, k, kr, O, I, t) for O, I in shapes for v, k, kr in GATHER + GATHERX for t in range(0, 70))
 
 
 def test_the_knob_is_read_through_tune_env_only():
-    src = open(os.path.join(ROOT, "vptq_amd", "layers", "vqlinear.py")).read()
+    src = open(os.path.join(ROOT, "vptq_amd", "batched_decode.py")).read()
     assert src.count("VPTQ_GEMM_GATHER_PX\"") == 1
     assert '_GEMM_GATHER_PX_MODE = (B.tune_env("VPTQ_GEMM_GATHER_PX", "auto") or "auto").strip().lower()' in src
-    for f in ("vptq_amd/ops/quant_gemm.py", "vptq_amd/_backend.py", "vptq_amd/csrc/gemm_gather_px.hip", "vptq_amd/csrc/abi.hip"):
+    for f in ("vptq_amd/layers/vqlinear.py", "vptq_amd/ops/quant_gemm.py", "vptq_amd/_backend.py", "vptq_amd/csrc/gemm_gather_px.hip", "vptq_amd/csrc/abi.hip"):
         assert "VPTQ_GEMM_GATHER_PX" not in open(os.path.join(ROOT, f)).read(), f
 
 
 def test_the_sibling_route_functions_answer_as_before():
     """gemm_gather_route, gemm_gatherx_route and gemm_gatherw_route do not know the new table: their answers are their own cells'"""
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
-    assert vq._GEMM_GATHER_CELLS == ((8, 65536, 0, 2 << 20, 9), (8, 65536, 256, 2 << 20, 9), (8, 65536, 65536, 2 << 20, 9))
-    assert vq._GEMM_GATHERX_CELLS == ((16, 65536, 0, 1 << 20, 5), (16, 65536, 1024, 1 << 20, 5), (8, 32768, 0, 2 << 20, 9), (8, 32768, 0, 8 << 20, 5),
+    assert bd._GEMM_GATHER_CELLS == ((8, 65536, 0, 2 << 20, 9), (8, 65536, 256, 2 << 20, 9), (8, 65536, 65536, 2 << 20, 9))
+    assert bd._GEMM_GATHERX_CELLS == ((16, 65536, 0, 1 << 20, 5), (16, 65536, 1024, 1 << 20, 5), (8, 32768, 0, 2 << 20, 9), (8, 32768, 0, 8 << 20, 5),
                                       (8, 65536, 4096, 2 << 20, 9), (8, 65536, 4096, 8 << 20, 5))
-    assert vq._GEMM_GATHERW_CELLS == tuple((kr, el, lo, hi) for kr in KRS for el, lo, hi in ((7 << 20, 17, 24), (28 << 20, 17, 48)))
+    assert bd._GEMM_GATHERW_CELLS == tuple((kr, el, lo, hi) for kr in KRS for el, lo, hi in ((7 << 20, 17, 24), (28 << 20, 17, 48)))
     shapes = ((8192, 8192), (4096, 4096), (14336, 4096), (28672, 8192), (512, 2048))
     for (O, I), (v, k, kr), t in itertools.product(shapes, GATHER + GATHERX + OTHER, range(0, 66)):
         n_el = ((O + v - 1) // v) * I
-        g = (v, k, kr) in GATHER and 5 <= t <= 16 and any(c[:3] == (v, k, kr) and n_el >= c[3] and t >= c[4] for c in vq._GEMM_GATHER_CELLS)
-        gx = (v, k, kr) in GATHERX and 5 <= t <= 16 and any(c[:3] == (v, k, kr) and n_el >= c[3] and t >= c[4] for c in vq._GEMM_GATHERX_CELLS)
-        gw = (v, k, kr) in GATHER and any(c[0] == kr and n_el >= max(c[1], 4 << 20) and c[2] <= t <= c[3] for c in vq._GEMM_GATHERW_CELLS)
+        g = (v, k, kr) in GATHER and 5 <= t <= 16 and any(c[:3] == (v, k, kr) and n_el >= c[3] and t >= c[4] for c in bd._GEMM_GATHER_CELLS)
+        gx = (v, k, kr) in GATHERX and 5 <= t <= 16 and any(c[:3] == (v, k, kr) and n_el >= c[3] and t >= c[4] for c in bd._GEMM_GATHERX_CELLS)
+        gw = (v, k, kr) in GATHER and any(c[0] == kr and n_el >= max(c[1], 4 << 20) and c[2] <= t <= c[3] for c in bd._GEMM_GATHERW_CELLS)
         assert vq.gemm_gather_route(v, k, kr, O, I, t) == g and vq.gemm_gatherx_route(v, k, kr, O, I, t) == gx, (v, k, kr, O, I, t)
         assert vq.gemm_gatherw_route(v, k, kr, O, I, t) == gw, (v, k, kr, O, I, t)
 

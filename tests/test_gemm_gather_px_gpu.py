@@ -336,11 +336,11 @@ def _spied(m, xt, monkeypatch):
 
 def _route_everything(monkeypatch):
     """cells that hand every layer of the three kernels to px (the committed cells lie over 4 M index elements: test layers are small)"""
-    from vptq_amd.layers import vqlinear as vq
-    monkeypatch.setattr(vq, "GEMM_GATHERW_MIN_ELEMENTS", 0)
+    from vptq_amd import batched_decode as bd
+    monkeypatch.setattr(bd, "GEMM_GATHERW_MIN_ELEMENTS", 0)
     cells = tuple((8, 65536, kr, 0, 5, 48) for kr in (0, 256, 65536)) + tuple(FMT[f] + (0, 5, 16) for f in XFMTS)
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_CELLS", cells)
-    return vq
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_CELLS", cells)
+    return bd
 
 
 def _stream_without_a_workspace(dev):
@@ -356,7 +356,7 @@ def _stream_without_a_workspace(dev):
 
 def test_module_under_a_capture_with_too_small_a_workspace_takes_the_dense_route(dev, monkeypatch):
     from vptq_amd import _backend as B
-    vq = _route_everything(monkeypatch)
+    bd = _route_everything(monkeypatch)
     tokens, I, O = 24, 2048, 512
     L = make_layer(24, I, O, "f16", perm="random", bias=1)
     m = spec_to_module(L, dev)
@@ -368,13 +368,13 @@ def test_module_under_a_capture_with_too_small_a_workspace_takes_the_dense_route
     assert calls == ["vptq_quant_gemm_gather_px"], calls
     s = _stream_without_a_workspace(dev)
     s.wait_stream(torch.cuda.current_stream(dev))
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", "0")
     del calls[:]
     with torch.cuda.stream(s):
         y_dense = m(xt)                                            # the dense route warmed up on s, no px call: no workspace grows
     assert calls == ["vptq_dequant"], calls
     assert (m._descriptor().device_index, s.cuda_stream) not in B._GEMV_WS
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", "auto")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", "auto")
     del calls[:]
     g = torch.cuda.CUDAGraph()
     with torch.cuda.stream(s):
@@ -394,6 +394,7 @@ def test_module_under_a_capture_with_too_small_a_workspace_takes_the_dense_route
 # ---------------------------------------------------------------------------------------------- 6. the module
 @pytest.mark.parametrize("kind,dt,tokens", [(24, "f16", 24), (16, "bf16", 12), (32, "f16", 48), ("v16-k65536-1024", "bf16", 5)])
 def test_module_takes_px_where_its_route_says_so(kind, dt, tokens, dev, monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     I, O = 2048, 512
     L = make_layer(kind, I, O, dt, perm="random", bias=1)
@@ -435,13 +436,13 @@ def test_module_takes_px_where_its_route_says_so(kind, dt, tokens, dev, monkeypa
     assert calls == ["vptq_quant_gemm_gather_px"], calls
     assert torch.equal(_bits(y1), _bits(y2))
     # the knob off: the calls of today (a fresh module: routes cache what they built)
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", "0")
     y0, calls = _spied(spec_to_module(L, dev), xt, monkeypatch)
     assert calls == today, (calls, today)
     assert torch.equal(_bits(y0), _bits(y_today))
     # the knob on, the committed cells: px again
     monkeypatch.undo()
-    monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", "1")
     y3, calls = _spied(spec_to_module(L, dev), xt, monkeypatch)
     assert calls == ["vptq_quant_gemm_gather_px"], calls
     assert torch.equal(_bits(y3), _bits(y1))
@@ -459,6 +460,7 @@ def _op_keywords(m):
 
 @pytest.mark.parametrize("kind,dt,tokens", [(24, "f16", 24), (24, "f16", 12), ("v16-k65536-1024", "bf16", 5)])
 def test_an_unpermuted_twin_never_calls_px(kind, dt, tokens, dev, monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     I, O = 2048, 512
     plain = make_layer(kind, I, O, dt, perm=None, bias=1)
@@ -466,7 +468,7 @@ def test_an_unpermuted_twin_never_calls_px(kind, dt, tokens, dev, monkeypatch):
     y_today, today = _spied(spec_to_module(plain, dev), xt, monkeypatch)
     for mode in ("auto", "1"):
         _route_everything(monkeypatch)
-        monkeypatch.setattr(vq, "_GEMM_GATHER_PX_MODE", mode)
+        monkeypatch.setattr(bd, "_GEMM_GATHER_PX_MODE", mode)
         y, calls = _spied(spec_to_module(plain, dev), xt, monkeypatch)
         assert calls == today and "vptq_quant_gemm_gather_px" not in calls, (mode, calls, today)
         assert torch.equal(_bits(y), _bits(y_today))

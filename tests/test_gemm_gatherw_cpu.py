@@ -146,10 +146,11 @@ def test_census_of_the_instantiations_and_the_makefile_entry():
 
 
 def test_route_function_is_pure_and_follows_the_cells(monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     route = vq.gemm_gatherw_route
     assert (vq.GEMM_GATHERW_MIN_TOKENS, vq.GEMM_GATHERW_MAX_TOKENS) == (17, 48)
-    assert all(len(c) == 4 and c[0] in KRS and c[1] >= 4 << 20 and 17 <= c[2] <= c[3] <= 48 for c in vq._GEMM_GATHERW_CELLS)
+    assert all(len(c) == 4 and c[0] in KRS and c[1] >= 4 << 20 and 17 <= c[2] <= c[3] <= 48 for c in bd._GEMM_GATHERW_CELLS)
     shapes = ((8192, 8192), (4096, 4096), (14336, 4096), (4096, 14336), (28672, 8192), (512, 2048), (36, 1032))
     for (O, I), kr in itertools.product(shapes, KRS):
         for tokens in (-1, 0, 1, 5, 16, 49, 64, 128):
@@ -161,17 +162,18 @@ def test_route_function_is_pure_and_follows_the_cells(monkeypatch):
             assert not on, (O, I, kr)                                  # no cell under 4 M index elements
         for t in range(17, 49):                                        # auto: the committed cells, nothing else
             assert route(8, 65536, kr, O, I, t) == any(
-                c == kr and n_el >= max(e, 4 << 20) and lo <= t <= hi for c, e, lo, hi in vq._GEMM_GATHERW_CELLS)
+                c == kr and n_el >= max(e, 4 << 20) and lo <= t <= hi for c, e, lo, hi in bd._GEMM_GATHERW_CELLS)
     for t in range(17, 49):   # other formats: never
         assert not route(8, 256, 256, 8192, 8192, t) and not route(16, 65536, 0, 8192, 8192, t) and not route(8, 65536, 4096, 8192, 8192, t)
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_MODE", "1")
     assert all(route(8, 65536, kr, 36, 1032, t) for kr in KRS for t in range(17, 49))
     assert not route(8, 65536, 256, 36, 1032, 16) and not route(8, 65536, 256, 8192, 8192, 49) and not route(16, 65536, 0, 8192, 8192, 32)
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_MODE", "0")
     assert not any(route(8, 65536, kr, O, I, t) for O, I in shapes for kr in KRS for t in range(0, 70))
 
 
 def test_the_16_token_entry_and_its_route_are_what_they_were():
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     lib = B.lib()
     for dtype, kr in itertools.product((0, 1), KRS):

@@ -275,6 +275,7 @@ def _spied(m, xt, monkeypatch):
 
 @pytest.mark.parametrize("T,dt", [(24, "f16"), (16, "bf16"), (32, "f16")])
 def test_module_takes_the_entry_where_the_route_says_so(T, dt, dev, monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     L = layer(2048, 512, T, dt, bias=1)
     tokens = 24
@@ -287,7 +288,7 @@ def test_module_takes_the_entry_where_the_route_says_so(T, dt, dev, monkeypatch)
     y, calls = _spied(m, xt, monkeypatch)
     assert calls == (["vptq_quant_gemm_gatherw"] if routed else ["vptq_dequant"]), calls
     # the knob on: the entry and nothing else, and the bits of the direct call
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_MODE", "1")
     y1, calls = _spied(m, xt, monkeypatch)
     assert calls == ["vptq_quant_gemm_gatherw"], calls
     direct = call(desc, xt.reshape(tokens, 2048), 512)
@@ -302,18 +303,19 @@ def test_module_takes_the_entry_where_the_route_says_so(T, dt, dev, monkeypatch)
     assert "vptq_quant_gemm_gatherw" in calls and "vptq_dequant" not in calls, calls
     assert torch.equal(_bits(y1), _bits(y2))
     # the knob off: never (a fresh module: `m` holds the first spy's vptq_dequant in its dense-route cache)
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_MODE", "0")
     y0, calls = _spied(spec_to_module(L, dev), xt, monkeypatch)
     assert "vptq_quant_gemm_gatherw" not in calls and calls == ["vptq_dequant"], calls
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_MODE", "auto")
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_MODE", "auto")
 
 
 def test_module_never_routes_a_permuted_layer_unless_the_knob_is_on(dev, monkeypatch):
     """the permuted forms were measured at 1.8 - 6.8 times the dense route (profiles/r23): with cells that route every size, a layer
     without a permutation takes the entry and its permuted twin keeps the dense route; the knob reaches both"""
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
-    monkeypatch.setattr(vq, "GEMM_GATHERW_MIN_ELEMENTS", 0)
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_CELLS", ((256, 0, 17, 48),))
+    monkeypatch.setattr(bd, "GEMM_GATHERW_MIN_ELEMENTS", 0)
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_CELLS", ((256, 0, 17, 48),))
     tokens = 24
     xt = bits_to_tensor(_dense(2048, tokens, "f16", 9)[0], "f16", dev).reshape(1, tokens, 2048)
     plain, permuted = (spec_to_module(layer(2048, 512, 24, "f16", perm=p, bias=1), dev) for p in (0, 1))
@@ -321,7 +323,7 @@ def test_module_never_routes_a_permuted_layer_unless_the_knob_is_on(dev, monkeyp
     assert _spied(plain, xt, monkeypatch)[1] == ["vptq_quant_gemm_gatherw"]
     y0, calls = _spied(permuted, xt, monkeypatch)
     assert calls == ["vptq_dequant"], calls
-    monkeypatch.setattr(vq, "_GEMM_GATHERW_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHERW_MODE", "1")
     y1, calls = _spied(permuted, xt, monkeypatch)
     assert calls == ["vptq_quant_gemm_gatherw"], calls
     assert rel_err(tensor_to_bits(y1), tensor_to_bits(y0), "f16") <= TOL["f16"]

@@ -169,11 +169,12 @@ SHAPES = ((8192, 8192), (4096, 4096), (14336, 4096), (4096, 14336), (8192, 28672
 
 
 def test_route_function_is_pure_and_bounded(monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     route = vq.gemm_gatherx_route
-    assert vq._GEMM_GATHERX_MODE == "auto"          # (the knob is read with VPTQ_TUNING=1 only)
+    assert bd._GEMM_GATHERX_MODE == "auto"          # (the knob is read with VPTQ_TUNING=1 only)
     for mode in ("auto", "1", "0"):
-        monkeypatch.setattr(vq, "_GEMM_GATHERX_MODE", mode)
+        monkeypatch.setattr(bd, "_GEMM_GATHERX_MODE", mode)
         for tokens in range(0, 20):
             for v, k, kr in GATHER_OWNED:           # the formats gemm_gather owns never route here
                 assert not route(v, k, kr, 8192, 8192, tokens)
@@ -184,9 +185,9 @@ def test_route_function_is_pure_and_bounded(monkeypatch):
         for (v, k, kr), (O, I) in itertools.product(FORMATS, SHAPES):
             for tokens in (0, 1, 4, 17, 64):
                 assert not route(v, k, kr, O, I, tokens)          # outside 5 .. 16: never
-    monkeypatch.setattr(vq, "_GEMM_GATHERX_MODE", "auto")
-    for cells in (vq._GEMM_GATHERX_CELLS, ((16, 65536, 1024, 4 << 20, 9), (16, 65536, 1024, 16 << 20, 5), (8, 32768, 0, 0, 12))):
-        monkeypatch.setattr(vq, "_GEMM_GATHERX_CELLS", cells)
+    monkeypatch.setattr(bd, "_GEMM_GATHERX_MODE", "auto")
+    for cells in (bd._GEMM_GATHERX_CELLS, ((16, 65536, 1024, 4 << 20, 9), (16, 65536, 1024, 16 << 20, 5), (8, 32768, 0, 0, 12))):
+        monkeypatch.setattr(bd, "_GEMM_GATHERX_CELLS", cells)
         for (v, k, kr), (O, I) in itertools.product(FORMATS, SHAPES):
             on = [t for t in range(0, 20) if route(v, k, kr, O, I, t)]
             assert on == (list(range(on[0], 17)) if on else []) and (not on or on[0] >= 5)   # from some token count on, up to 16
@@ -195,24 +196,25 @@ def test_route_function_is_pure_and_bounded(monkeypatch):
                 assert len(cell) == 5
             first = min((c[4] for c in cells if c[:3] == (v, k, kr) and ((O + v - 1) // v) * I >= c[3]), default=None)
             assert (on[0] if on else None) == (None if first is None else max(first, 5))
-    monkeypatch.setattr(vq, "_GEMM_GATHERX_CELLS", ((16, 65536, 1024, 4 << 20, 9),))
+    monkeypatch.setattr(bd, "_GEMM_GATHERX_CELLS", ((16, 65536, 1024, 4 << 20, 9),))
     assert route(16, 65536, 1024, 8192, 8192, 9) and not route(16, 65536, 1024, 8192, 8192, 8)
     assert not route(16, 65536, 1024, 4096, 4096, 16) and not route(16, 65536, 256, 8192, 8192, 16)
     # the knob: every format of the kernel from 5 tokens / none
-    monkeypatch.setattr(vq, "_GEMM_GATHERX_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHERX_MODE", "1")
     for v, k, kr in FORMATS:
         assert all(route(v, k, kr, 512, 2048, t) for t in range(5, 17)) and not route(v, k, kr, 512, 2048, 4)
         assert not route(v, k, kr, 512, 2048, 17)
-    monkeypatch.setattr(vq, "_GEMM_GATHERX_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_GATHERX_MODE", "0")
     assert not any(route(v, k, kr, 8192, 8192, t) for v, k, kr in FORMATS for t in range(0, 20))
     # gemm_gather_route is what it was: it never takes a format of this kernel
-    monkeypatch.setattr(vq, "_GEMM_GATHER_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHER_MODE", "1")
     assert not any(vq.gemm_gather_route(v, k, kr, 8192, 8192, t) for v, k, kr in FORMATS for t in range(0, 20))
 
 
 def test_knob_is_read_only_under_tuning(monkeypatch):
     """VPTQ_GEMM_GATHERX reaches the module through tune_env alone: without VPTQ_TUNING=1 it is ignored"""
-    src = open(os.path.join(ROOT, "vptq_amd", "layers", "vqlinear.py")).read()
+    assert "VPTQ_GEMM_GATHERX" not in open(os.path.join(ROOT, "vptq_amd", "layers", "vqlinear.py")).read()
+    src = open(os.path.join(ROOT, "vptq_amd", "batched_decode.py")).read()
     assert re.findall(r"VPTQ_GEMM_GATHERX\b[^=]", src.replace("VPTQ_GEMM_GATHERX=1 / 0", "")) == ['VPTQ_GEMM_GATHERX"']   # read once ...
     assert '_GEMM_GATHERX_MODE = (B.tune_env("VPTQ_GEMM_GATHERX", "auto") or "auto").strip().lower()' in src              # ... like this
     monkeypatch.setenv("VPTQ_GEMM_GATHERX", "1")

@@ -213,6 +213,7 @@ def test_two_launches_and_a_graph_replay_give_the_same_bits(fmt, dt, dev):
 @pytest.mark.parametrize("fmt,dt", [("v16-k65536-1024", "f16"), ("v16-k65536-0", "bf16"), ("v8-k65536-4096", "bf16")])
 def test_module_takes_the_entry_where_the_route_says_so(fmt, dt, dev, monkeypatch):
     from vptq_amd import _backend as B
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     v, k, kr = FMT[fmt]
     L = layer(2048, 512, fmt, dt, bias=1)
@@ -231,7 +232,7 @@ def test_module_takes_the_entry_where_the_route_says_so(fmt, dt, dev, monkeypatc
     if routed:
         am.check_outputs(_np(y), mm, aa, dt, False, what="VQuantLinear.forward, 12 tokens")
     # the route function on: always the entry itself ...
-    monkeypatch.setattr(vq, "_GEMM_GATHERX_MODE", "1")
+    monkeypatch.setattr(bd, "_GEMM_GATHERX_MODE", "1")
     calls1 = []
     monkeypatch.setattr(B, "lib", lambda: _Spy(real, calls1))
     y1 = m(xt)

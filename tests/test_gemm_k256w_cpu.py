@@ -127,6 +127,7 @@ def test_census_of_the_instantiations():
 
 
 def test_route_function_is_pure_and_follows_the_cells(monkeypatch):
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     route = vq.gemm_k256w_route
     shapes = ((8192, 8192), (4096, 4096), (14336, 4096), (4096, 14336), (28672, 8192), (512, 2048), (36, 1032))
@@ -137,10 +138,10 @@ def test_route_function_is_pure_and_follows_the_cells(monkeypatch):
         assert on == list(range(on[0], on[-1] + 1)) if on else True   # the routed token counts of a layer are one interval
         n_el = ((O + 7) // 8) * I
         for t in range(17, 65):                                     # auto: the committed cells, nothing else
-            assert route(O, I, t) == any(n_el >= e and lo <= t <= hi for e, lo, hi in vq._GEMM_K256W_CELLS)
-    monkeypatch.setattr(vq, "_GEMM_K256W_MODE", "1")
+            assert route(O, I, t) == any(n_el >= e and lo <= t <= hi for e, lo, hi in bd._GEMM_K256W_CELLS)
+    monkeypatch.setattr(bd, "_GEMM_K256W_MODE", "1")
     assert all(route(36, 1032, t) for t in range(17, 65)) and not route(36, 1032, 16) and not route(8192, 8192, 65)
-    monkeypatch.setattr(vq, "_GEMM_K256W_MODE", "0")
+    monkeypatch.setattr(bd, "_GEMM_K256W_MODE", "0")
     assert not any(route(O, I, t) for O, I in shapes for t in range(0, 70))
 
 

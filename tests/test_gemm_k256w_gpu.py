@@ -283,6 +283,7 @@ def _spied(m, xt, monkeypatch):
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
 def test_module_takes_the_entry_where_the_route_says_so(dt, dev, monkeypatch):
     import vptq_amd
+    from vptq_amd import batched_decode as bd
     from vptq_amd.layers import vqlinear as vq
     L = layer(2048, 512, dt, bias=1)
     assert vptq_amd.arithmetic() == "reference"
@@ -297,7 +298,7 @@ def test_module_takes_the_entry_where_the_route_says_so(dt, dev, monkeypatch):
         y, calls = _spied(m, xt, monkeypatch)
         assert calls == (["vptq_quant_gemm_k256w"] if routed else ["vptq_quant_gemv"] if tokens <= 48 else ["vptq_dequant"]), calls
         # the knob on: the entry and nothing else
-        monkeypatch.setattr(vq, "_GEMM_K256W_MODE", "1")
+        monkeypatch.setattr(bd, "_GEMM_K256W_MODE", "1")
         y1, calls = _spied(m, xt, monkeypatch)
         assert calls == ["vptq_quant_gemm_k256w"], calls
         am.check_outputs(_np(y1).reshape(mm.shape), mm, aa, dt, False, what=f"VQuantLinear.forward, {tokens} tokens, routed")
@@ -310,4 +311,4 @@ def test_module_takes_the_entry_where_the_route_says_so(dt, dev, monkeypatch):
             assert "vptq_quant_gemm_k256w" not in calls and calls, calls
         finally:
             vptq_amd.set_arithmetic("reference")
-        monkeypatch.setattr(vq, "_GEMM_K256W_MODE", "auto")
+        monkeypatch.setattr(bd, "_GEMM_K256W_MODE", "auto")

@@ -664,16 +664,21 @@ def test_module_copies_and_pickles_without_its_derived_state():
     m.__dict__["_desc_cache"] = ("stand-in", object())
     m.__dict__["_sliced"] = (1, object())
     m.__dict__["_sliced_cand"] = True
-    m.__dict__["_bd_ok"] = (7, True)   # the batched-decode route's cached (descriptor generation, supported) answer
+    # the batched-decode routing: the `_supported` answers of one descriptor generation, the routes this process's library has
+    from vptq_amd import batched_decode as bd
+    m.__dict__["_bd_supported"] = (7, {("vptq_quant_gemm_k256w", True): True})
+    m.__dict__["_bd_routes"] = bd.batched_decode_routes(8, 256, 256, 1, False, True, False)
+    assert [r.entry for r in m.__dict__["_bd_routes"]] == ["vptq_quant_gemm_k256w"]
     m.enable_sliced_layout(False)
-    assert "_bd_ok" not in m.__getstate__()
+    assert "_bd_supported" not in m.__getstate__() and "_bd_routes" not in m.__getstate__()
     m2 = copy.deepcopy(m)
     assert "_desc_cache" not in m2.__dict__ and "_sliced" not in m2.__dict__ and m2.__dict__["_sliced_on"] is False
-    assert "_bd_ok" not in m2.__dict__
+    assert "_bd_supported" not in m2.__dict__ and "_bd_routes" not in m2.__dict__
     assert m2.indices is not m.indices and torch.equal(m2.indices, m.indices)
     m.__dict__["_sliced"] = (1, object())
     m3 = pickle.loads(pickle.dumps(m))
-    assert "_desc_cache" not in m3.__dict__ and "_sliced" not in m3.__dict__ and "_bd_ok" not in m3.__dict__
+    assert "_desc_cache" not in m3.__dict__ and "_sliced" not in m3.__dict__
+    assert "_bd_supported" not in m3.__dict__ and "_bd_routes" not in m3.__dict__
     assert sorted(m3.state_dict()) == sorted(m.state_dict())
 
 

@@ -19,8 +19,7 @@ import argparse, ctypes, json, math, os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
 import vptq_amd  # noqa
-from vptq_amd import _backend as B  # noqa
-from vptq_amd.layers import vqlinear as vq  # noqa
+from vptq_amd import _backend as B, batched_decode  # noqa
 from _gpu_util import module_desc  # noqa
 from microbench import time_graph  # noqa
 from shape_bench import mk  # noqa
@@ -41,7 +40,7 @@ t_start = time.time()
 dev = torch.device("cuda", 0); g = torch.Generator(device=dev).manual_seed(0); lib = B.lib()
 box = f"{torch.cuda.get_device_name(0)}, {torch.cuda.get_device_properties(0).multi_processor_count} CUs"
 print(json.dumps(dict(box=box)), flush=True)
-vq._GEMM_GATHER_PX_MODE = "0"   # the modules of this process take the PARENT's route; px is called through the library
+batched_decode._GEMM_GATHER_PX_MODE = "0"   # the modules of this process take the PARENT's route; px is called through the library
 rows = []
 LAUNCHES = ("vptq_quant_gemm_gather_px", "vptq_quant_gemm_gatherw", "vptq_quant_gemm_gather", "vptq_quant_gemm_gatherx", "vptq_quant_gemv", "vptq_dequant")
 

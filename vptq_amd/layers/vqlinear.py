@@ -34,6 +34,12 @@ from torch.nn.parameter import Parameter
 
 from vptq_amd import _backend as B
 from vptq_amd import ops
+# the batched-decode rules live in vptq_amd/batched_decode.py; the route functions and the token windows are re-exported here (the
+# knobs and the cell tables are NOT: tests and tools assign to them, and an alias would keep the old value)
+from vptq_amd.batched_decode import (  # noqa: F401
+    BATCHED_DECODE_MAX_TOKENS, BATCHED_DECODE_MIN_TOKENS, GEMM_GATHER_MAX_TOKENS, GEMM_GATHER_PX_MAX_TOKENS, GEMM_GATHER_PX_MIN_TOKENS,
+    GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS, GEMM_K256W_MIN_TOKENS, batched_decode_routes,
+    batched_decode_takes, gemm_gather_px_route, gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_k256w_route)
 
 
 def chain_prefetch(layers, circular: bool = False):
@@ -91,197 +97,6 @@ _COMPACTED = weakref.WeakSet()   # compacted layers (their share of the compact-
 _DEQUANT_SLICED_MAX_ROWS = 4096
 _DEQUANT_SLICED_MAX_COLS = 4096
 _DEQUANT_SLICED_MODE = (B.tune_env("VPTQ_DEQUANT_SLICED", "auto") or "auto").strip().lower()
-
-
-# WHICH (format, shape, token count) take a batched-decode kernel of the large-codebook formats (1 - 16 tokens in one launch) in place
-# of the route they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.
-# A layer has ONE such kernel: v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids belong to `vptq_quant_gemm_gather`
-# (gemm_gather.hip), every other vector length 8 / 16, 16384 ... 65536 main centroids, any residual codebook to
-# `vptq_quant_gemm_gatherx` (gemm_gatherx.hip); `_batched_decode_entry` says which.  Each has a knob and a table of cells; a cell is
-# (vector length, main centroids, residual centroids, least index elements = vector-rows x columns, least tokens).  A cell is routed
-# only where the kernel was MEASURED to beat the route it replaces (5 - 8 tokens: the gemv_gather / gemv_gatherx launches; 9 - 16:
-# the dense route) by more than the larger of 5 % and three times the run-to-run spread, both in one process on one box
-# (tools/gemm_gather_bench.py writes the tables); a region is routed only where EVERY measured cell in it wins in both dtypes.
-# VPTQ_GEMM_GATHER=1 / 0, VPTQ_GEMM_GATHERX=1 / 0 (with VPTQ_TUNING=1): every supported layer of that kernel from 5 tokens / none -
-# what the bench tool, the tests and a user who has measured their own shapes use.
-#
-# gemm_gather (profiles/r15/table.md, profiles/r15/README.md: one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 /
-# 9 / 12 / 16): from 9 tokens the kernel beats the dense route in every measured cell of the three formats (0.51 - 0.86 of its time),
-# so 9 - 16 tokens are routed from the smallest measured layer (4096 x 4096 = 2 M index elements) up; at 5 - 8 tokens it is level
-# with gemv_gather in most cells (0.84 - 1.12), which stays.
-#
-# gemm_gatherx (profiles/r16/table.md: one MI355X, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16):
-#   v16-k65536-0, v16-k65536-1024     every cell wins (0.48 - 0.93 of the parent's time): 5 - 16 tokens from 4096 x 4096 (1 M elements) up
-#   v8-k32768-0, v8-k65536-4096       9 - 16 tokens: every cell (0.53 - 0.91); 5 - 8 tokens: only from 8192 x 8192 (8 M elements) up (0.73 - 0.94)
-#   v16-k65536-65536                  wins at 5 - 8 tokens (0.66 - 0.88) but is level with the dense route at 9 - 16 on the larger
-#                                     layers (0.94 - 1.05 at 8192 x 8192): a route has to be monotone in tokens, so nothing is routed
-# Formats that were not measured (v16-k65536-32768 / -256 / -64, v8-k65536-4, v8-k16384-0) and smaller layers are not routed.
-GEMM_GATHER_MAX_TOKENS = 16
-_GEMM_GATHER_MODE = (B.tune_env("VPTQ_GEMM_GATHER", "auto") or "auto").strip().lower()
-_GEMM_GATHER_CELLS = ((8, 65536, 0, 2 << 20, 9), (8, 65536, 256, 2 << 20, 9), (8, 65536, 65536, 2 << 20, 9))
-_GEMM_GATHERX_MODE = (B.tune_env("VPTQ_GEMM_GATHERX", "auto") or "auto").strip().lower()
-_GEMM_GATHERX_CELLS = (
-    (16, 65536, 0, 1 << 20, 5), (16, 65536, 1024, 1 << 20, 5),
-    (8, 32768, 0, 2 << 20, 9), (8, 32768, 0, 8 << 20, 5),
-    (8, 65536, 4096, 2 << 20, 9), (8, 65536, 4096, 8 << 20, 5),
-)
-
-
-def _pow2(n: int) -> bool:
-    return n > 0 and (n & (n - 1)) == 0
-
-
-def _batched_decode_entry(vector_len: int, num_centroids: int, num_res_centroids: int):
-    """the library entry whose kernel has this format ("vptq_quant_gemm_gather" / "vptq_quant_gemm_gatherx"), or None"""
-    if vector_len == 8 and num_centroids == 65536 and num_res_centroids in (0, 256, 65536):
-        return "vptq_quant_gemm_gather"
-    if vector_len in (8, 16) and _pow2(num_centroids) and 16384 <= num_centroids <= 65536 and \
-            (not num_res_centroids or (_pow2(num_res_centroids) and num_res_centroids <= 65536)):
-        return "vptq_quant_gemm_gatherx"
-    return None
-
-
-def _batched_decode_route(mode, cells, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens) -> bool:
-    """the tail both route functions share: the knob, the token window, the measured cells"""
-    if mode in ("0", "off") or not 5 <= tokens <= GEMM_GATHER_MAX_TOKENS:
-        return False
-    if mode in ("1", "on"):
-        return True
-    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
-    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and n_el >= min_el and tokens >= min_tok
-               for v, k, kr, min_el, min_tok in cells)
-
-
-def gemm_gather_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
-    """does a layer of this format (vector length, main / residual codebook entries) and shape take `vptq_quant_gemm_gather` for
-    `tokens` tokens?  Pure: no device, no library (whether the library serves the layer - one codebook group, no outliers, scale and
-    bias, alignment - is `vptq_quant_gemm_gather_supported`'s answer)."""
-    return _batched_decode_entry(vector_len, num_centroids, num_res_centroids) == "vptq_quant_gemm_gather" and \
-        _batched_decode_route(_GEMM_GATHER_MODE, _GEMM_GATHER_CELLS, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
-
-
-def gemm_gatherx_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
-    """does a layer of this format and shape take `vptq_quant_gemm_gatherx` for `tokens` tokens?  Pure: no device, no library (one
-    codebook group, no outliers, scale and bias, alignment: `vptq_quant_gemm_gatherx_supported`'s answer).  Never for the formats
-    `gemm_gather_route` owns (v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids): a layer has one batched-decode kernel."""
-    return _batched_decode_entry(vector_len, num_centroids, num_res_centroids) == "vptq_quant_gemm_gatherx" and in_features % 8 == 0 and \
-        _batched_decode_route(_GEMM_GATHERX_MODE, _GEMM_GATHERX_CELLS, vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
-
-
-# WHICH (shape, token count) of the canonical format (v = 8, 256 + 256 centroids) take `vptq_quant_gemm_k256w` - 17 - 64 tokens in ONE
-# launch (gemm_k256w_kernel, gemm_k256.hip) - in place of the route they had (17 - 48 tokens: launches of 16 of gemm_k256_kernel; 49 -
-# 64: the dense route): the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.  Only layers whose arithmetic is the
-# reference's roundings (`LayerCache.arithmetic_flags` has GEMV_EXACT) are asked: the kernel has no other.  A cell is (least index
-# elements = vector-rows x columns, least tokens, most tokens), routed by the rule above (beats its parent by more than the larger of
-# 5 % and three times the larger spread, in every measured cell of the region, in both dtypes; the routed token counts of a layer
-# are one interval); tools/gemm_k256w_bench.py writes the table.  VPTQ_GEMM_K256W=1 / 0 (with VPTQ_TUNING=1): every supported layer
-# from 17 to 64 tokens / none.
-#
-# profiles/r19/table.md, profiles/r19/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 17 / 24 / 32 / 33 / 48 /
-# 49 / 64): at 17 - 48 tokens the kernel beats the launches of 16 in every measured cell (0.47 - 0.79 of their time), so 17 - 48 tokens
-# are routed from the smallest measured layer (4096 x 4096 = 2 M index elements) up.  At 49 - 64 tokens (four token blocks, 23 - 41
-# registers spilled) it beats the dense route at 8192 x 8192 and 8192 x 28672 in fp16 (0.68 - 0.83) but not by the rule in bf16 at 64
-# tokens (0.94 - 0.96), and loses on the 14336-wide layers (0.95 - 1.40): no region wins in every cell, so 49 - 64 keep the dense route.
-_GEMM_K256W_CELLS = ((2 << 20, 17, 48),)
-GEMM_K256W_MIN_TOKENS, GEMM_K256W_MAX_TOKENS = 17, 64
-_GEMM_K256W_MODE = (B.tune_env("VPTQ_GEMM_K256W", "auto") or "auto").strip().lower()
-
-
-def gemm_k256w_route(out_features: int, in_features: int, tokens: int) -> bool:
-    """does a canonical-format layer of this shape take `vptq_quant_gemm_k256w` for `tokens` tokens?  Pure: no device, no library
-    (whether the library serves the layer is `vptq_quant_gemm_k256w_supported`'s answer, the arithmetic the caller's)."""
-    if _GEMM_K256W_MODE in ("0", "off") or not GEMM_K256W_MIN_TOKENS <= tokens <= GEMM_K256W_MAX_TOKENS:
-        return False
-    if _GEMM_K256W_MODE in ("1", "on"):
-        return True
-    n_el = ((out_features + 7) // 8) * in_features
-    return any(n_el >= min_el and min_tok <= tokens <= max_tok for min_el, min_tok, max_tok in _GEMM_K256W_CELLS)
-
-
-# WHICH (format, shape, token count) of gemm_gather's formats (v = 8, 65536 main centroids, 0 / 256 / 65536 residual centroids) take
-# `vptq_quant_gemm_gatherw` - 17 - 48 tokens in ONE launch (gemm_gatherw_kernel, gemm_gatherw.hip) - in place of the dense route
-# they had: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.  A cell is (residual centroids, least index elements
-# = vector-rows x columns, least tokens, most tokens), routed by the rule above `_GEMM_GATHER_CELLS` (beats its parent by more than
-# the larger of 5 % and three times the run-to-run spread, in every measured cell of the region, in both dtypes; the routed token
-# counts of a layer are one interval); tools/gemm_gatherw_bench.py writes the table.  No cell starts below 4 M index elements: a
-# compacted 4096 x 4096 layer keeps its dense route, which needs no repack there (`_dense_from_layout`).  VPTQ_GEMM_GATHERW=1 / 0
-# (with VPTQ_TUNING=1): every supported layer from 17 to 48 tokens / none.
-#
-# profiles/r23/table.md, profiles/r23/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 17 / 24 / 32 / 33 / 40 /
-# 48, layers without a permutation): at 17 - 24 tokens the kernel beats the dense route in every measured cell of the three formats
-# (0.66 - 0.92 of its time), so 17 - 24 tokens are routed from the smallest measured layer above 4 M elements (14336 x 4096 = 7 M) up.
-# From 32 tokens it does not win on 14336 x 4096 (0.98 - 1.25) and is level at 8192 x 8192 (0.88 - 1.13), and wins in every cell only at
-# 8192 x 28672 (28 M elements: 0.70 - 0.88 at 32 - 48 tokens), so 25 - 48 tokens are routed from that size up.  LAYERS WITH A COLUMN
-# PERMUTATION ARE NEVER ROUTED (only the knob reaches them): the kernel gathers a permuted x two bytes at a time in every row group and
-# took 1.8 - 6.8 times the dense route's time at 8192 x 8192 and 14336 x 4096 (profiles/r23/table_perm.md).
-_GEMM_GATHERW_CELLS = tuple((kr, el, lo, hi) for kr in (0, 256, 65536) for el, lo, hi in ((7 << 20, 17, 24), (28 << 20, 17, 48)))
-GEMM_GATHERW_MIN_TOKENS, GEMM_GATHERW_MAX_TOKENS = 17, 48
-GEMM_GATHERW_MIN_ELEMENTS = 4 << 20
-_GEMM_GATHERW_MODE = (B.tune_env("VPTQ_GEMM_GATHERW", "auto") or "auto").strip().lower()
-
-
-def gemm_gatherw_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
-    """does a layer of this format and shape take `vptq_quant_gemm_gatherw` for `tokens` tokens?  Pure: no device, no library
-    (whether the library serves the layer is `vptq_quant_gemm_gatherw_supported`'s answer)."""
-    if _GEMM_GATHERW_MODE in ("0", "off") or not GEMM_GATHERW_MIN_TOKENS <= tokens <= GEMM_GATHERW_MAX_TOKENS or \
-            _batched_decode_entry(vector_len, num_centroids, num_res_centroids) != "vptq_quant_gemm_gather":
-        return False
-    if _GEMM_GATHERW_MODE in ("1", "on"):
-        return True
-    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
-    return any(kr == num_res_centroids and n_el >= max(min_el, GEMM_GATHERW_MIN_ELEMENTS) and min_tok <= tokens <= max_tok
-               for kr, min_el, min_tok, max_tok in _GEMM_GATHERW_CELLS)
-
-
-# WHICH (format, shape, token count) of the three kernels' layers WITH A COLUMN PERMUTATION take `vptq_quant_gemm_gather_px` - x[perm]
-# written once per call into the stream's workspace, then the layer's kernel in its form without a permutation (gemm_gather_px.hip),
-# 5 - 48 tokens - in place of the route a permuted layer has: the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`
-# ahead of the three route functions above (which are what they were; layers without a permutation never come here).  A cell is
-# (vector length, main centroids, residual centroids, least index elements, least tokens, most tokens), routed by the rule above
-# `_GEMM_GATHER_CELLS`: px beats the route a permuted layer takes WITHOUT it (5 - 8 tokens: the gemv_gather / gemv_gatherx launches;
-# 9 - 16: the in-kernel permuted gemm_gather / gemm_gatherx where their cells route it, else the dense route; 17 - 48: the dense
-# route) by more than the larger of 5 % and three times the larger run-to-run spread, in every measured cell of the region, in both
-# dtypes; the routed token counts of a layer are one interval; no cell lies under GEMM_GATHERW_MIN_ELEMENTS (4 M index elements).
-# tools/gemm_gather_px_bench.py writes the table.  VPTQ_GEMM_GATHER_PX=1 / 0 (with VPTQ_TUNING=1): every supported permuted layer
-# from 5 to 48 tokens / none.
-#
-# profiles/r25/table.md, profiles/r25/README.md (one MI355X, fp16 and bf16, permuted layers of 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 /
-# 9 / 12 / 16 / 17 / 24 / 32 / 33 / 40 / 48; 530 cells, px has the bits of the layer's own entry in every one, 526 win; run-to-run spreads
-# under 3 % in all but two cells):
-#   v8-k65536-0 / -256 / -65536   5 - 8 tokens 0.16 - 0.77 of the gemv_gather launches, 9 - 16 tokens 0.18 - 0.64 of the in-kernel permuted
-#                                 gemm_gather (itself 1.05 - 2.6 times the dense route), 17 - 40 tokens 0.37 - 0.93 of the dense route: every
-#                                 cell of every shape wins.  48 tokens: 4096 x 14336 (7 M elements) loses or is level in -0 and -256
-#                                 (0.92 - 1.09), the other layers from 7 M up win (0.49 - 0.81), -65536 wins everywhere (0.54 - 0.93).  So
-#                                 5 - 40 tokens from 7 M index elements, 5 - 48 from 8 M (8192 x 8192); -65536: 5 - 48 from 7 M.
-#   v16-k65536-0 / -1024          5 - 16 tokens 0.17 - 0.69 of the in-kernel permuted gemm_gatherx in every cell: routed from the floor
-#                                 (8192 x 8192 = 4 M elements of v = 16) up
-#   v8-k32768-0, v8-k65536-4096   5 - 16 tokens 0.19 - 0.72 of gemv_gatherx (5 - 8, under 8 M) / the permuted gemm_gatherx: from 7 M up
-# 4096 x 4096 (and the 3.5 M-element v = 16 layers) win too (0.30 - 0.88; one bf16 cell at 48 tokens short of the rule) but lie under the
-# floor: they keep their routes - at 9 - 16 tokens that is the in-kernel permuted kernel, measured here at 1.05 - 3.0 times the dense route
-# (STATUS.md, item 4c(b)).
-_GEMM_GATHER_PX_CELLS = (
-    (8, 65536, 0, 7 << 20, 5, 40), (8, 65536, 0, 8 << 20, 5, 48), (8, 65536, 256, 7 << 20, 5, 40), (8, 65536, 256, 8 << 20, 5, 48),
-    (8, 65536, 65536, 7 << 20, 5, 48),
-    (16, 65536, 0, 4 << 20, 5, 16), (16, 65536, 1024, 4 << 20, 5, 16), (8, 32768, 0, 7 << 20, 5, 16), (8, 65536, 4096, 7 << 20, 5, 16),
-)
-GEMM_GATHER_PX_MIN_TOKENS, GEMM_GATHER_PX_MAX_TOKENS = 5, 48
-_GEMM_GATHER_PX_MODE = (B.tune_env("VPTQ_GEMM_GATHER_PX", "auto") or "auto").strip().lower()
-
-
-def gemm_gather_px_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int) -> bool:
-    """does a layer WITH a column permutation of this format and shape take `vptq_quant_gemm_gather_px` for `tokens` tokens?  Pure:
-    no device, no library (whether the library serves the layer is `vptq_quant_gemm_gather_px_supported`'s answer; that the layer
-    has a permutation is the caller's)."""
-    if _GEMM_GATHER_PX_MODE in ("0", "off") or not GEMM_GATHER_PX_MIN_TOKENS <= tokens <= GEMM_GATHER_PX_MAX_TOKENS:
-        return False
-    entry = _batched_decode_entry(vector_len, num_centroids, num_res_centroids)
-    if entry is None or (tokens > GEMM_GATHER_MAX_TOKENS and entry != "vptq_quant_gemm_gather") or in_features % 8:
-        return False   # (17 - 48 tokens: gemm_gatherw's formats only)
-    if _GEMM_GATHER_PX_MODE in ("1", "on"):
-        return True
-    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
-    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and n_el >= max(min_el, GEMM_GATHERW_MIN_ELEMENTS) and
-               min_tok <= tokens <= max_tok for v, k, kr, min_el, min_tok, max_tok in _GEMM_GATHER_PX_CELLS)
 
 
 def _dense_from_layout(layer) -> bool:
@@ -680,20 +495,8 @@ class VQuantLinear(nn.Module):
                 "path, which is outside this inference package; construct the layer with "
                 "enable_proxy_error=False (HF does).")
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        if self.enable_perm and GEMM_GATHER_PX_MIN_TOKENS <= tokens <= GEMM_GATHER_PX_MAX_TOKENS and x.is_cuda and self.__dict__.get("_px", True):
-            y = self._gemm_gather_px_cached(x, tokens)   # (x[perm] once, then the layer's kernel without a permutation, where `gemm_gather_px_route` says so)
-            if y is not None:
-                return y
-        if 5 <= tokens <= GEMM_GATHER_MAX_TOKENS and x.is_cuda and self.__dict__.get("_bd_entry", True):
-            y = self._batched_decode_cached(x, tokens)   # (the large-codebook formats' batched decode, where the layer's route function says so)
-            if y is not None:
-                return y
-        if GEMM_K256W_MIN_TOKENS <= tokens <= GEMM_K256W_MAX_TOKENS and x.is_cuda and self.__dict__.get("_k256w", True):
-            y = self._gemm_k256w_cached(x, tokens)   # (the canonical format in the reference's roundings, where `gemm_k256w_route` says so)
-            if y is not None:
-                return y
-        if GEMM_GATHERW_MIN_TOKENS <= tokens <= GEMM_GATHERW_MAX_TOKENS and x.is_cuda and self.__dict__.get("_gatherw", True):
-            y = self._gemm_gatherw_cached(x, tokens)   # (gemm_gather's formats, where `gemm_gatherw_route` says so)
+        if BATCHED_DECODE_MIN_TOKENS <= tokens <= BATCHED_DECODE_MAX_TOKENS and x.is_cuda and self.__dict__.get("_bd_routes", True):
+            y = self._batched_decode_cached(x, tokens)   # (5 - 64 tokens in one launch, where a route of vptq_amd/batched_decode.py takes the call)
             if y is not None:
                 return y
         if 1 <= tokens <= B.GEMV_MAX_TOKENS and x.is_cuda and \
@@ -808,8 +611,9 @@ class VQuantLinear(nn.Module):
         return x if x.is_contiguous() else x.contiguous()
 
     # derived, device-bound state (ctypes descriptors, the sliced layout, sibling links) is rebuilt on demand: it is
-    # neither pickled nor deep-copied with the module (torch.save(model), copy.deepcopy(model))
-    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_ok", "_k256w_ok", "_gatherw_ok")
+    # neither pickled nor deep-copied with the module (torch.save(model), copy.deepcopy(model)); the same holds for the batched-decode
+    # routes of THIS process's library and its `_supported` answers (descriptor generations restart at 0 in every process)
+    _DERIVED_STATE = ("_desc_cache", "_desc_dense", "_sliced", "_sliced_cand", "_siblings", "_bd_routes", "_bd_supported")
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -1162,122 +966,73 @@ class VQuantLinear(nn.Module):
             B.check(rc, "vptq_quant_gemv")
         return y
 
+    def _batched_decode_routes(self) -> tuple:
+        """the batched-decode routes that can ever serve this layer (`batched_decode_routes` of its static configuration) and whose
+        entry this process's library has: decided once per layer, so that every other layer pays one dict look-up per call"""
+        routes = self.__dict__.get("_bd_routes")
+        if routes is None:
+            lib = B.lib()
+            routes = tuple(r for r in batched_decode_routes(self.vector_len, self.num_centroids, _res_centroids(self), self.num_codebooks,
+                                                            self.enable_outlier, self.enable_norm, bool(self.enable_perm))
+                           if getattr(lib, r.entry, None) is not None)
+            self.__dict__["_bd_routes"] = routes
+        return routes
+
     def _batched_decode_cached(self, x: torch.Tensor, tokens: int):
-        """5 - 16 tokens of a large-codebook layer in ONE launch of the layer's batched-decode entry (`vptq_quant_gemm_gather` or
-        `vptq_quant_gemm_gatherx`: `_batched_decode_entry`) where that entry's route function gives the layer's (format, shape,
-        tokens) to it and the library serves the layer; None: the caller's other routes.  Compact layers hand it the repacked
-        stream, as the gather route does."""
-        entry = self.__dict__.get("_bd_entry")
-        if entry is None:
-            # (static module configuration: decided once, every other layer pays one dict look-up per call; False: no entry)
-            entry = _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self))
-            if entry is None or self.num_codebooks != 1 or self.enable_outlier or not self.enable_norm or getattr(B.lib(), entry, None) is None:
-                entry = False
-            self.__dict__["_bd_entry"] = entry
-        if not entry:
-            return None
-        route = gemm_gather_route if entry == "vptq_quant_gemm_gather" else gemm_gatherx_route
-        if not route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
-                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
-            return None
-        return self._batched_entry_launch(entry, "_bd_ok", GEMM_GATHER_MAX_TOKENS, x, tokens)
-
-    def _gemm_k256w_cached(self, x: torch.Tensor, tokens: int):
-        """17 - 64 tokens of a canonical-format layer in ONE launch of `vptq_quant_gemm_k256w` where `gemm_k256w_route` gives the
-        layer's (shape, tokens) to it, the layer's arithmetic is the reference's roundings, no FORCE_* flag is set and the library
-        serves the layer; None: the routes of before (launches of 16 tokens, the dense route)."""
-        if "_k256w" not in self.__dict__:   # (static module configuration: decided once)
-            self.__dict__["_k256w"] = (self.vector_len, self.num_centroids, _res_centroids(self)) == (8, 256, 256) and \
-                self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm
-        if not self.__dict__["_k256w"] or not gemm_k256w_route(self.out_features, self.in_features, tokens) or \
-                (ops.quant_gemm_flags() & B.GEMV_FORCE_ANY) or not (self._descriptor().arithmetic_flags & B.GEMV_EXACT):
-            return None
-        return self._batched_entry_launch("vptq_quant_gemm_k256w", "_k256w_ok", GEMM_K256W_MAX_TOKENS, x, tokens)
-
-    def _gemm_gatherw_cached(self, x: torch.Tensor, tokens: int):
-        """17 - 48 tokens of a layer of gemm_gather's formats in ONE launch of `vptq_quant_gemm_gatherw` where `gemm_gatherw_route`
-        gives the layer's (format, shape, tokens) to it, the layer has no column permutation (or the knob is on), GEMV_FORCE_GENERIC
-        is not set and the library serves the layer; None: the routes of before.  Compact layers hand it the repacked stream, as the 5 - 16 token route does."""
-        if "_gatherw" not in self.__dict__:   # (static module configuration: decided once)
-            self.__dict__["_gatherw"] = _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self)) == "vptq_quant_gemm_gather" and \
-                self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm and \
-                getattr(B.lib(), "vptq_quant_gemm_gatherw", None) is not None
-        if not self.__dict__["_gatherw"] or \
-                not gemm_gatherw_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
-                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
-            return None
-        if self.enable_perm and _GEMM_GATHERW_MODE not in ("1", "on"):   # (measured 1.8 - 6.8 times the dense route: the comment above the cells)
-            return None
-        return self._batched_entry_launch("vptq_quant_gemm_gatherw", "_gatherw_ok", GEMM_GATHERW_MAX_TOKENS, x, tokens)
-
-    def _gemm_gather_px_cached(self, x: torch.Tensor, tokens: int):
-        """5 - 48 tokens of a large-codebook layer WITH a column permutation in one call of `vptq_quant_gemm_gather_px` (x[perm]
-        once into the stream's workspace, then the layer's kernel in its form without a permutation) where `gemm_gather_px_route`
-        gives the layer's (format, shape, tokens) to it, GEMV_FORCE_GENERIC is not set and the library serves the layer; None: the
-        routes of before - also where a stream capture is in progress and the stream's workspace is too small (`prepare_model`
-        sizes it).  Compact layers hand it the repacked stream, as the other batched entries do."""
-        if "_px" not in self.__dict__:   # (static module configuration: decided once)
-            self.__dict__["_px"] = bool(self.enable_perm) and _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self)) is not None and \
-                self.num_codebooks == 1 and not self.enable_outlier and self.enable_norm and \
-                getattr(B.lib(), "vptq_quant_gemm_gather_px", None) is not None
-        if not self.__dict__["_px"] or \
-                not gemm_gather_px_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, tokens) or \
-                (ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC):
-            return None
-        # (`_supported` is asked for the token window of the call: the inner kernel changes at 17 tokens)
-        wide = tokens > GEMM_GATHER_MAX_TOKENS
-        return self._batched_entry_launch("vptq_quant_gemm_gather_px", "_px_ok_w" if wide else "_px_ok", GEMM_GATHER_PX_MAX_TOKENS if wide else GEMM_GATHER_MAX_TOKENS,
-                                          x, tokens, workspace=True)
+        """5 - 64 tokens in ONE launch of the first batched-decode route (vptq_amd/batched_decode.py) that takes this call: its route
+        function gives the layer's (format, shape, tokens) to it, its off-flags are not set, the layer's arithmetic is the
+        reference's roundings where the kernel has no other, and the library serves the layer.  None: the routes of before - also
+        where x is not what the entries take (the other routes raise the shape / dtype / device errors) or where a stream capture
+        is in progress and the stream's workspace is too small for x[perm] (`prepare_model` sizes it).  Compact layers hand the
+        entry the repacked stream, as the gather route does."""
+        D = self.__dict__
+        routes = D.get("_bd_routes")
+        if routes is None:
+            routes = self._batched_decode_routes()
+        cache, gf, kr, perm = None, ops.quant_gemm_flags(), _res_centroids(self), bool(self.enable_perm)
+        for r in routes:
+            if not batched_decode_takes(r, self.vector_len, self.num_centroids, kr, self.out_features, self.in_features, tokens, gf, perm):
+                continue
+            if cache is None:
+                cache = self._descriptor()
+                if x.shape[-1] != self.in_features or x.dtype != cache.dtype or x.device != cache.device:
+                    return None
+                if not x.is_contiguous():
+                    x = x.contiguous()
+                if x.data_ptr() % 16:
+                    return None
+                ok = D.get("_bd_supported")
+                if ok is None or ok[0] != cache.generation:
+                    ok = D["_bd_supported"] = (cache.generation, {})
+            if r.exact_only and not (cache.arithmetic_flags & B.GEMV_EXACT):
+                continue
+            # `_supported` is asked at the call's own token count, as `ops.quant_gemm` asks it: every entry's answer depends on the
+            # count only through its window, and through which side of 16 tokens it lies where the inner kernel changes there (px)
+            key = (r.entry, tokens > GEMM_GATHER_MAX_TOKENS)
+            served = ok[1].get(key)
+            if served is None:
+                served = ok[1][key] = bool(getattr(B.lib(), r.entry + "_supported")(cache.desc, tokens))
+            if served:
+                y = ops.quant_gemm_batched_launch(r.entry, cache.desc, x, self.out_features, gf | cache.arithmetic_flags, r.workspace,
+                                                  self._repacked_desc if "_compact" in D else None)
+                if y is not None:
+                    return y
+        return None
 
     def _gemm_gather_px_workspace_bytes(self) -> int:
-        """bytes of stream workspace the largest call `_gemm_gather_px_cached` can route for this layer needs (`prepare_model` grows
-        the stream's buffer to it); 0: the layer never takes that route"""
-        if not self.enable_perm or _batched_decode_entry(self.vector_len, self.num_centroids, _res_centroids(self)) is None or \
-                self.num_codebooks != 1 or self.enable_outlier or not self.enable_norm:
+        """bytes of stream workspace the largest call the permuted-layer route (`vptq_quant_gemm_gather_px`) can take for this
+        layer needs (`prepare_model` grows the stream's buffer to it); 0: the layer never takes that route"""
+        if "_compact" not in self.__dict__ and not self._parameters["indices"].is_cuda:
             return 0
-        cp = self.__dict__.get("_compact")
-        if cp is None and not self._parameters["indices"].is_cuda:
+        px = [r for r in self._batched_decode_routes() if r.workspace]
+        if not px:
             return 0
-        routed = [t for t in range(GEMM_GATHER_PX_MIN_TOKENS, GEMM_GATHER_PX_MAX_TOKENS + 1)
-                  if gemm_gather_px_route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, t)]
-        query = getattr(B.lib(), "vptq_quant_gemm_gather_px_workspace_bytes", None)
+        routed = [t for t in range(px[0].min_tokens, px[0].max_tokens + 1)
+                  if px[0].route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, t)]
+        query = getattr(B.lib(), px[0].entry + "_workspace_bytes", None)
         if not routed or query is None:
             return 0
         return int(query(self._descriptor().desc, routed[-1]))
-
-    def _batched_entry_launch(self, entry: str, ok_key: str, ask_tokens: int, x: torch.Tensor, tokens: int, workspace: bool = False):
-        """one launch of a batched-decode entry; `_supported`'s answer cached per descriptor generation under `ok_key`.  None: the
-        library does not serve the layer, or x is not what the entry takes (the other routes raise the shape / dtype / device errors).
-        workspace: the entry takes (workspace, workspace_bytes) in front of the stream - `B.gemv_workspace` of this (device, stream),
-        sized by the entry's `_workspace_bytes` query; None too where that buffer is too small and cannot grow (a stream capture)"""
-        cache = self._descriptor()
-        desc, dev, wdtype, dev_index = cache.desc, cache.device, cache.dtype, cache.device_index
-        ok = self.__dict__.get(ok_key)
-        if ok is None or ok[0] != cache.generation:
-            ok = (cache.generation, bool(getattr(B.lib(), entry + "_supported")(desc, ask_tokens)))
-            self.__dict__[ok_key] = ok
-        if not ok[1] or x.shape[-1] != self.in_features or x.dtype != wdtype or x.device != dev:
-            return None   # (the other routes raise the shape / dtype / device errors)
-        if not x.is_contiguous():
-            x = x.contiguous()
-        if x.data_ptr() % 16:
-            return None
-        cp = self.__dict__.get("_compact")
-        with torch.cuda.device(dev):
-            sp = B.current_stream_ptr(dev)
-            ws_args = ()
-            if workspace:
-                need = getattr(B.lib(), entry + "_workspace_bytes")(desc, tokens)
-                ws_args = B.gemv_workspace(dev_index, sp, need)
-                if need and ws_args[0] is None:
-                    return None
-            y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=wdtype, device=dev)
-            if cp is not None:   # (compact mode: the packed stream rebuilt into this stream's scratch first)
-                desc = self._repacked_desc(desc, dev_index, sp)
-            rc = getattr(B.lib(), entry)(desc, x.data_ptr(), y.data_ptr(), tokens, ops.quant_gemm_flags() | cache.arithmetic_flags, *ws_args, sp)
-        if rc:
-            B.check(rc, entry)
-        return y
 
     def _dense_cached(self, x: torch.Tensor) -> torch.Tensor:
         """Many tokens: `vptq_dequant` into a fresh dense W + `F.linear` (the reference's route,

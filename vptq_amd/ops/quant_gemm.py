@@ -19,6 +19,7 @@ import torch
 from torch.nn import functional as F
 
 from vptq_amd import _backend as B
+from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes
 
 __all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w",
            "quant_gemv_v2"]
@@ -202,40 +203,23 @@ def quant_gemm(
         gdesc = desc
         if tokens > B.GEMV_ANY_FORMAT_TOKENS and tokens > B.lib().vptq_quant_gemv_max_tokens(desc):
             desc = None  # 9-16 tokens: only the canonical format's GEMV still beats dequant + GEMM
-        # the large-codebook formats' batched decode (gemm_gather.hip, then its generic sibling gemm_gatherx.hip for the formats that
-        # one does not own): the token counts the kernel's route function gives it, as `VQuantLinear.forward` routes them
-        from vptq_amd.layers.vqlinear import gemm_gather_route, gemm_gatherx_route
+        # 5 - 64 tokens in one launch of a batched-decode entry: the first route of vptq_amd/batched_decode.py that takes the call, as
+        # `VQuantLinear.forward` routes it.  A route steps aside - the next one, then the routes below - where the library does not serve
+        # the layer, x is not 16-byte aligned, the layer's arithmetic is not the reference's roundings and the kernel has no other
+        # (asked last: it may cost a read-back), or a capture is in progress with too small a workspace.
         kr = num_res_centroids if enable_residual else 0
-        # a layer with a column permutation: x[perm] once into the stream's workspace, then the plain form of the layer's kernel
-        # (gemm_gather_px.hip), where its own route function says so; None (a capture with too small a workspace): the routes below
-        from vptq_amd.layers.vqlinear import gemm_gather_px_route
-        if perm is not None and not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
-                gemm_gather_px_route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
-                B.lib().vptq_quant_gemm_gather_px_supported(gdesc, tokens):
-            y = _quant_gemm_px(x, gdesc, out_features)
+        routes = batched_decode_routes(vector_len, num_centroids, kr, num_codebooks, enable_outlier, weight_scale is not None and
+                                       weight_bias is not None, perm is not None) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
+        for r in routes:
+            if not batched_decode_takes(r, vector_len, num_centroids, kr, out_features, in_features, tokens, _FLAGS, perm is not None) or \
+                    x.data_ptr() % 16 or not getattr(B.lib(), r.entry + "_supported")(gdesc, tokens):
+                continue
+            if r.exact_only and not ((_FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale,
+                                                           weight_bias, gdesc, in_features, out_features)) & B.GEMV_EXACT):
+                continue
+            y = quant_gemm_batched_launch(r.entry, gdesc, x, out_features, _FLAGS, r.workspace)
             if y is not None:
                 return y
-        for route, entry in ((gemm_gather_route, "vptq_quant_gemm_gather"), (gemm_gatherx_route, "vptq_quant_gemm_gatherx")):
-            if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and \
-                    route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
-                    getattr(B.lib(), entry + "_supported")(gdesc, tokens):
-                return _quant_gemm_batched(entry, x, gdesc, out_features)
-        # gemm_gather's formats, 17 - 48 tokens in one launch (gemm_gatherw_kernel), where its route function says so
-        # (never a layer with a column permutation, unless the knob is on: 1.8 - 6.8 times the dense route, profiles/r23)
-        from vptq_amd.layers import vqlinear as _vq
-        from vptq_amd.layers.vqlinear import gemm_gatherw_route
-        if not (_FLAGS & B.GEMV_FORCE_GENERIC) and x.data_ptr() % 16 == 0 and (perm is None or _vq._GEMM_GATHERW_MODE in ("1", "on")) and \
-                gemm_gatherw_route(vector_len, num_centroids, kr, out_features, in_features, tokens) and \
-                B.lib().vptq_quant_gemm_gatherw_supported(gdesc, tokens):
-            return _quant_gemm_batched("vptq_quant_gemm_gatherw", x, gdesc, out_features)
-        # the canonical format's 17 - 64 tokens in one launch, in the reference's roundings only (gemm_k256w_kernel)
-        from vptq_amd.layers.vqlinear import gemm_k256w_route
-        if (vector_len, num_centroids, kr) == (8, 256, 256) and gemm_k256w_route(out_features, in_features, tokens) and \
-                not (_FLAGS & B.GEMV_FORCE_ANY) and x.data_ptr() % 16 == 0 and \
-                B.lib().vptq_quant_gemm_k256w_supported(gdesc, tokens) and \
-                ((_FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
-                                       gdesc, in_features, out_features)) & B.GEMV_EXACT):
-            return _quant_gemm_batched("vptq_quant_gemm_k256w", x, gdesc, out_features)
     if desc is not None:
         y = torch.empty(x.shape[:-1] + (out_features,), dtype=x.dtype, device=dev)
         flags = _FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale, weight_bias,
@@ -297,17 +281,33 @@ def quant_gemm_fused(x: torch.Tensor, desc, out_features: int) -> torch.Tensor:
     return y
 
 
-def _quant_gemm_batched(entry: str, x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
-    """the tokens of ONE launch of a batched-decode entry: 1 - 16 of the large-codebook formats (`quant_gemm_gather` / `quant_gemm_gatherx`),
-    17 - 48 of `quant_gemm_gather`'s formats (`quant_gemm_gatherw`), 17 - 64 of the canonical format (`quant_gemm_k256w`)"""
-    tokens = x.numel() // x.shape[-1]
-    dev = x.device
+def quant_gemm_batched_launch(entry: str, desc, x: torch.Tensor, out_features: int, flags: int, workspace: bool = False, repack=None):
+    """ONE launch of a batched-decode entry (the wrappers below, the routes of vptq_amd/batched_decode.py) over all tokens of x, on x's
+    device and its current stream; `flags` are the launch's (GEMV_OUT_F32: y is float32).  workspace: the entry takes (workspace,
+    workspace_bytes) in front of the stream - this (device, stream)'s `B.gemv_workspace`, sized by `entry + "_workspace_bytes"`;
+    None where the entry needs one and there is none: a stream capture is in progress and the buffer is too small (nothing is
+    allocated or launched then).  repack(desc, device index, stream) -> the descriptor to launch with (compact mode)."""
+    shape, dev = x.shape, x.device
+    tokens = x.numel() // shape[-1]
     if not x.is_contiguous():
         x = x.contiguous()
-    y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
+    lib = B.lib()
     with torch.cuda.device(dev):
-        B.check(getattr(B.lib(), entry)(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0),
-                                        B.current_stream_ptr(dev)), entry)
+        sp = B.current_stream_ptr(dev)
+        ws_args = ()
+        if workspace or repack is not None:
+            dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
+        if workspace:
+            need = getattr(lib, entry + "_workspace_bytes")(desc, tokens)
+            ws_args = B.gemv_workspace(dev_index, sp, need)
+            if need and ws_args[0] is None:
+                return None
+        y = torch.empty(shape[:-1] + (out_features,), dtype=torch.float32 if flags & B.GEMV_OUT_F32 else x.dtype, device=dev)
+        if repack is not None:
+            desc = repack(desc, dev_index, sp)
+        rc = getattr(lib, entry)(desc, x.data_ptr(), y.data_ptr(), tokens, flags, *ws_args, sp)
+    if rc:
+        B.check(rc, entry)
     return y
 
 
@@ -316,7 +316,7 @@ def quant_gemm_gather(x: torch.Tensor, desc, out_features: int, out_f32: bool = 
     centroids) in ONE launch (`vptq_quant_gemm_gather`, gemm_gather.hip: centroid rows gathered from L2, the contraction on the
     matrix pipe, the reference's roundings; replaces dequant + F.linear for 9 - 16 tokens).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gather_supported` accepts; out_f32: the un-rounded fp32 sums."""
-    return _quant_gemm_batched("vptq_quant_gemm_gather", x, desc, out_features, out_f32)
+    return quant_gemm_batched_launch("vptq_quant_gemm_gather", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0))
 
 
 def quant_gemm_gatherw(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
@@ -324,7 +324,7 @@ def quant_gemm_gatherw(x: torch.Tensor, desc, out_features: int, out_f32: bool =
     residual centroids) in ONE launch (`vptq_quant_gemm_gatherw`, gemm_gatherw.hip: 2 / 3 blocks of 16 tokens share one pass over the
     indices, gathers and rebuilt tiles; the reference's roundings, a token's bits those of the 16-token kernel; replaces dequant +
     F.linear).  `desc` = a LayerDesc of a layer `vptq_quant_gemm_gatherw_supported` accepts; out_f32: the un-rounded fp32 sums."""
-    return _quant_gemm_batched("vptq_quant_gemm_gatherw", x, desc, out_features, out_f32)
+    return quant_gemm_batched_launch("vptq_quant_gemm_gatherw", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0))
 
 
 def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
@@ -332,26 +332,7 @@ def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool =
     65536 main centroids, any residual codebook) in ONE launch (`vptq_quant_gemm_gatherx`, gemm_gatherx.hip: the same structure with an
     index path for any total width and 32-byte entries; the reference's roundings).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gatherx_supported` accepts; out_f32: the un-rounded fp32 sums."""
-    return _quant_gemm_batched("vptq_quant_gemm_gatherx", x, desc, out_features, out_f32)
-
-
-def _quant_gemm_px(x: torch.Tensor, desc, out_features: int, out_f32: bool = False, flags: int = 0):
-    """one call of `vptq_quant_gemm_gather_px` with this (device, stream)'s `B.gemv_workspace`; None where the layer needs a
-    workspace and there is none: a stream capture is in progress and the buffer is too small (nothing is allocated then)"""
-    tokens = x.numel() // x.shape[-1]
-    dev = x.device
-    if not x.is_contiguous():
-        x = x.contiguous()
-    with torch.cuda.device(dev):
-        sp = B.current_stream_ptr(dev)
-        need = B.lib().vptq_quant_gemm_gather_px_workspace_bytes(desc, tokens)
-        ws, wsb = B.gemv_workspace(dev.index if dev.index is not None else torch.cuda.current_device(), sp, need)
-        if need and ws is None:
-            return None
-        y = torch.empty(x.shape[:-1] + (out_features,), dtype=torch.float32 if out_f32 else x.dtype, device=dev)
-        B.check(B.lib().vptq_quant_gemm_gather_px(desc, x.data_ptr(), y.data_ptr(), tokens, _FLAGS | flags | (B.GEMV_OUT_F32 if out_f32 else 0),
-                                                  ws, wsb, sp), "vptq_quant_gemm_gather_px")
-    return y
+    return quant_gemm_batched_launch("vptq_quant_gemm_gatherx", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0))
 
 
 def quant_gemm_gather_px(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
@@ -362,7 +343,7 @@ def quant_gemm_gather_px(x: torch.Tensor, desc, out_features: int, out_f32: bool
     without a permutation takes the plain launch alone.  `desc` = a LayerDesc of a layer `vptq_quant_gemm_gather_px_supported`
     accepts; out_f32: the un-rounded fp32 sums.  Raises where a stream capture is in progress and the workspace is too small
     (`prepare_model` sizes it beforehand)."""
-    y = _quant_gemm_px(x, desc, out_features, out_f32)
+    y = quant_gemm_batched_launch("vptq_quant_gemm_gather_px", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True)
     if y is None:
         raise RuntimeError("quant_gemm_gather_px: the stream's workspace is too small and cannot grow during a capture "
                            "(call it once, or vptq_amd.prepare_model, before capturing)")
@@ -374,7 +355,7 @@ def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = F
     (`vptq_quant_gemm_k256w`, gemm_k256.hip: 2 - 4 blocks of 16 tokens share one pass over the indices; the reference's roundings, a
     token's bits those of the 16-token kernel; replaces 2 - 3 launches of 16 tokens, and dequant + F.linear from 49).  `desc` = a
     LayerDesc of a layer `vptq_quant_gemm_k256w_supported` accepts; out_f32: the un-rounded fp32 sums."""
-    return _quant_gemm_batched("vptq_quant_gemm_k256w", x, desc, out_features, out_f32)
+    return quant_gemm_batched_launch("vptq_quant_gemm_k256w", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0))
 
 
 def quant_gemv_v2(
