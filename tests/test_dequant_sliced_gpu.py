@@ -134,7 +134,7 @@ class _Count:
         return self.fn(*a, **kw)
 
 
-# (the module takes the new kernel for layers of up to 4096 x 4096 - vptq_amd/layers/vqlinear.py:_dense_from_layout, by measurement;
+# (the module takes the new kernel for layers of up to 4096 x 4096 - vptq_amd/sliced_routes.py:dense_from_layout, by measurement;
 # 4096 x 8192 v16-k65536-65536 keeps the repack route, so the bf16 two-plane case runs at 4096 x 4096)
 @pytest.mark.parametrize("I,O,v,k,kr,dt", [(4096, 4096, 8, 65536, 256, F16), (4096, 4096, 16, 65536, 65536, BF16)],
                          ids=["4096x4096-v8-k65536-256-f16", "4096x4096-v16-k65536-65536-bf16"])

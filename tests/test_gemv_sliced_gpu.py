@@ -467,6 +467,29 @@ def test_module_forward_takes_the_sliced_layout_when_enabled(dev, folded_arithme
     assert m._sliced_gemv() is None
 
 
+def test_module_builds_the_layout_the_rule_names(dev):
+    """The reference arithmetic's one-token size rule (`sliced_routes.exact_route_is_large`) at its boundary, through the module:
+    v8-k65536-256 with 4096 columns and 2048 outputs is exactly 1 M index elements - an exact layout -, 2040 outputs is just under -
+    the gather kernel, until `enable_sliced_layout()` asks; the layout then serves one token to the oracle's tolerance"""
+    import vptq_amd
+    before = vptq_amd.arithmetic()
+    vptq_amd.set_arithmetic("reference")
+    try:
+        at = spec_to_module(vo.make_layer(4096, 2048, seed=41, dist="llm", num_centroids=65536, num_res_centroids=256), dev)
+        assert at.prepare()["built"] == "exact"
+        L = vo.make_layer(4096, 2040, seed=42, dist="llm", num_centroids=65536, num_res_centroids=256)
+        under = spec_to_module(L, dev)
+        assert under._sliced_gemv() is None
+        assert under.prepare()["built"].startswith("one token takes the gather kernel for this layer")
+        under.enable_sliced_layout()
+        assert under.prepare()["built"] == "exact" and under._sliced_gemv().exact
+        x1 = _x(4096, "f16", "llm", 6)
+        y = under(bits_to_tensor(x1, "f16", dev).reshape(x1.shape))
+        assert rel_err(tensor_to_bits(y), vo.forward(L, x1), "f16") <= 1e-3
+    finally:
+        vptq_amd.set_arithmetic(before)
+
+
 def test_sliced_route_falls_back_instead_of_failing(dev, folded_arithmetic):
     """the sliced one-token route is on by default and sits in front of the regular routing, so whatever it
     cannot take must fall through to it: an activation that is not 16-byte aligned, a capture on a stream the layer
@@ -622,9 +645,9 @@ def test_two_and_three_tokens_as_sliced_launches_per_token(dev, monkeypatch, fol
     """2 tokens of a LARGE large-codebook layer (the 4-bit format: 3) are served as one sliced launch per token
     (VQuantLinear._sliced_token_limit: the gather kernels cost as much for one token as for four, the sliced kernel a
     third to a half of that per token); smaller layers and more tokens keep the gather kernels"""
-    import vptq_amd.layers.vqlinear as vq
+    import vptq_amd.sliced_routes as R
     from oracle import c_oracle as co
-    monkeypatch.setattr(vq, "_SLICED_ONE_LAUNCH", "0")    # (the route of this test: one launch PER token)
+    monkeypatch.setattr(R, "_SLICED_ONE_LAUNCH", "0")    # (the route of this test: one launch PER token)
     L = vo.make_layer(8192, 6200, dist="llm", seed=41, num_centroids=65536, num_res_centroids=0)
     m = spec_to_module(L, dev)
     m.enable_sliced_layout()
@@ -650,7 +673,7 @@ def test_two_and_three_tokens_as_sliced_launches_per_token(dev, monkeypatch, fol
     ms(xst[:, :1].contiguous())
     sls = ms.__dict__["_sliced"][1]
     assert ms._sliced_token_limit(sls) == 1
-    monkeypatch.setattr(vq, "_SLICED_TOKENS_ENV", (3, 3))
+    monkeypatch.setattr(R, "_SLICED_TOKENS_ENV", (3, 3))
     sls.__dict__.pop("_token_limit")
     ys = ms(xst)
     for t in range(3):
@@ -816,7 +839,7 @@ def test_sliced_tokens_rejections(dev):
 def test_module_route_for_two_to_four_tokens_in_one_launch(dev, monkeypatch, folded_arithmetic):
     """the module's forward: 2 - 4 tokens of a large-codebook layer = ONE launch over the layouts (VQuantLinear._sliced_one_launch:
     where that was measured faster - not v = 16 with a small residual table, not tiny layers); switched off: the other routes"""
-    import vptq_amd.layers.vqlinear as vq
+    import vptq_amd.sliced_routes as R
     L = vo.make_layer(4096, 1024, dist="llm", seed=61, num_centroids=65536, num_res_centroids=256, bias=True)
     m = spec_to_module(L, dev)
     m.enable_sliced_layout()
@@ -833,12 +856,12 @@ def test_module_route_for_two_to_four_tokens_in_one_launch(dev, monkeypatch, fol
     y5 = m(xt)                                     # 5 tokens: the gather kernel
     assert rel_err(tensor_to_bits(y5), vo.forward(L, xs), "f16") <= 1e-3
     y2 = m(xt[:, :2].contiguous())
-    monkeypatch.setattr(vq, "_SLICED_ONE_LAUNCH", "0")
+    monkeypatch.setattr(R, "_SLICED_ONE_LAUNCH", "0")
     for T in (2, 3, 4):
         sl.__dict__.pop(("_one_launch", T), None)
     y2g = m(xt[:, :2].contiguous())                # the gather kernel (this layer is too small for a launch per token)
     assert rel_err(tensor_to_bits(y2g), vo.forward(L, xs[:, :2]), "f16") <= 1e-3
-    monkeypatch.setattr(vq, "_SLICED_ONE_LAUNCH", "auto")
+    monkeypatch.setattr(R, "_SLICED_ONE_LAUNCH", "auto")
     for T in (2, 3, 4):
         sl.__dict__.pop(("_one_launch", T), None)
     # v = 16 with a 1024-entry residual table: the gather kernel holds that table in LDS and is the faster one
@@ -868,7 +891,7 @@ def test_module_default_route_for_two_to_four_tokens_of_wide_layers(dev, monkeyp
     or the column-phase kernel (3 - 4 tokens) (VQuantLinear._sliced_one_launch / _sliced_token_limit: where each was measured
     faster than the gather kernel); everything else keeps the gather kernel; siblings share the launch"""
     import vptq_amd
-    import vptq_amd.layers.vqlinear as vq
+    import vptq_amd.sliced_routes as R
     from vptq_amd.layers.vqlinear import SiblingGroup
     assert vptq_amd.arithmetic() == "reference"
     L = vo.make_layer(8192, 6144, dist="llm", seed=71, num_centroids=65536, num_res_centroids=256, bias=True)
@@ -949,7 +972,7 @@ def test_module_default_route_for_two_to_four_tokens_of_wide_layers(dev, monkeyp
         assert rel_err(yb, w4, "f16") <= 1e-3 and float((yb.reshape(-1) == np.asarray(w4).reshape(-1)).mean()) >= 0.95
     assert torch.equal(m4(xt[:, :4].contiguous()).view(torch.int16), gemv_abi(m4, xt[:, :4].contiguous(), EXACT).view(torch.int16))
     # switched on for every layer the library takes ("1"): siblings of one format share one launch, each member's own bits
-    monkeypatch.setattr(vq, "_SLICED_ONE_LAUNCH", "1")
+    monkeypatch.setattr(R, "_SLICED_ONE_LAUNCH", "1")
     Lq = [vo.make_layer(8192, O, seed=80 + i, dist="llm", num_centroids=65536, num_res_centroids=256, bias=(i == 1)) for i, O in enumerate((1024, 264, 512))]
     mq = [spec_to_module(Li, dev) for Li in Lq]
     for mm in mq:
@@ -973,10 +996,10 @@ def test_sibling_layers_share_one_pass_in_window_parts(dev, monkeypatch):
     """q / k / v of a 4096-wide model, 3 tokens, reference roundings: ONE grouped launch of the one-pass kernel in two window parts
     (every member: half of the columns staged per workgroup), each member's result as from its own launch"""
     import vptq_amd
-    import vptq_amd.layers.vqlinear as vq
+    import vptq_amd.sliced_routes as R
     from vptq_amd.layers.vqlinear import SiblingGroup
     assert vptq_amd.arithmetic() == "reference"
-    monkeypatch.setattr(vq, "_SLICED_ONE_LAUNCH", "1")       # (small test layers: below the auto rule's size)
+    monkeypatch.setattr(R, "_SLICED_ONE_LAUNCH", "1")       # (small test layers: below the auto rule's size)
     xs = np.concatenate([_x(4096, "f16", "llm", 90 + i) for i in range(3)], axis=1)
     x3 = bits_to_tensor(xs, "f16", dev).reshape(xs.shape)
     Lq = [vo.make_layer(4096, O, seed=95 + i, dist="llm", num_centroids=65536, num_res_centroids=256, bias=(i == 1)) for i, O in enumerate((1024, 264, 512))]
@@ -1029,10 +1052,10 @@ def test_sibling_layers_share_one_launch_for_two_to_four_tokens(v, kr, dt, token
     (`vptq_quant_gemv_sliced_tokens_grouped` via `SiblingGroup.forward_sliced`): bit-identical to the layers' own launches where the
     rows per wave do not change the order of a row's sums (they do not: a row is summed by one wave, phase by phase), one
     member with a permutation (its own pre-pass), one with an output bias"""
-    import vptq_amd.layers.vqlinear as vq
+    import vptq_amd.sliced_routes as R
     from vptq_amd.layers.vqlinear import SiblingGroup
     from vptq_amd.utils.sliced import SlicedGemv
-    monkeypatch.setattr(vq, "_SLICED_ONE_LAUNCH", "1")       # (small test layers: below the auto rule's size)
+    monkeypatch.setattr(R, "_SLICED_ONE_LAUNCH", "1")       # (small test layers: below the auto rule's size)
     I = 2048
     outs = (1024, 33 * v, 512)
     Ls = [vo.make_layer(I, O, dist="llm", seed=170 + i + kr % 7 + tokens, dtype=dt, vector_len=v, num_centroids=65536, num_res_centroids=kr,

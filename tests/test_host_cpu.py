@@ -1131,129 +1131,6 @@ def test_sliced_tokens_plan_without_gpu():
     assert sup(_family_desc(8192, 8192, 12, 65536, 0), layouts(d), 2) == 0   # not a layer of the sliced path at all
 
 
-def test_one_launch_rule_for_two_to_four_tokens():
-    """VQuantLinear._sliced_one_launch: which layers send 2 - 4 tokens through the token kernel over the sliced layouts (the
-    measured table of profiles/r04/sliced_tokens_one_launch.txt as a rule) - host logic, no GPU"""
-    import types
-    import torch
-    from vptq_amd.layers.vqlinear import VQuantLinear
-
-    def layer(I, O, v, kr):
-        return types.SimpleNamespace(indices=torch.empty(1, O // v, 1), group_size=I, vector_len=v, out_features=O,
-                                     num_res_centroids=kr, enable_residual=kr > 0)
-
-    def rule(I, O, v, kr, tokens, supported=True, exact=False, slices=8, one_pass=False):
-        class SL:       # (stands in for vptq_amd.utils.sliced.SlicedGemv: what the library answers + the per-layout cache)
-            def tokens_supported(self, t):
-                return supported
-        sl = SL()
-        sl.exact, sl.slices = exact, slices
-        sl.tokens_one_pass = lambda t: bool(one_pass)
-        sl.tokens_window_parts = lambda t: int(one_pass)
-        return VQuantLinear._sliced_one_launch(layer(I, O, v, kr), sl, tokens)
-    for t in (2, 3, 4):
-        assert rule(8192, 8192, 8, 0, t) and rule(4096, 4096, 8, 256, t) and rule(4096, 14336, 8, 65536, t) and rule(8192, 8192, 16, 0, t)
-        assert not rule(2048, 512, 8, 256, t)                     # tiny: launch-bound on every route
-        assert not rule(8192, 8192, 16, 1024, t)                  # v = 16 with a small residual table: the gather kernel holds it in LDS
-        assert not rule(8192, 8192, 8, 0, t, supported=False)     # the library does not take it (no wstart, no room in LDS)
-    assert rule(4096, 14336, 16, 65536, 2) and not rule(4096, 14336, 16, 65536, 4) and rule(8192, 8192, 16, 65536, 4)
-    # the reference's roundings (profiles/r05/sliced_tokens_exact.txt): large v = 8 layers whose exact layout has 16 slices
-    assert not rule(8192, 8192, 8, 256, 2, exact=True, slices=16)      # 2 tokens: two launches of the one-token kernel instead
-    for t in (3, 4):
-        assert rule(8192, 8192, 8, 256, t, exact=True, slices=16) and rule(14336, 4096, 8, 0, t, exact=True, slices=16)
-        assert not rule(4096, 14336, 8, 256, t, exact=True, slices=8) and not rule(4096, 4096, 8, 0, t, exact=True, slices=8)
-        assert not rule(8192, 8192, 16, 0, t, exact=True, slices=32) and not rule(8192, 2048, 8, 0, t, exact=True, slices=16)
-        assert not rule(8192, 8192, 8, 256, t, exact=True, slices=16, supported=False)
-    # ... and 2 / 3 tokens in ONE PASS of the one-token kernel wherever the library takes that (16-slice layouts, any size)
-    for t in (2, 3):
-        assert rule(8192, 8192, 8, 256, t, exact=True, slices=16, one_pass=True) and rule(8192, 1024, 8, 0, t, exact=True, slices=16, one_pass=True)
-        assert not rule(2048, 8192, 8, 0, t, exact=True, slices=8, one_pass=True) and not rule(8192, 8192, 16, 0, t, exact=True, slices=32, one_pass=True)
-        # two tables of v = 8: large layers with >= 4096 residual centroids (the one-token rule's sizes)
-        assert rule(8192, 8192, 8, 65536, t, exact=True, slices=16, one_pass=True) and rule(8192, 8192, 8, 4096, t, exact=True, slices=16, one_pass=True)
-        assert not rule(8192, 1024, 8, 65536, t, exact=True, slices=16, one_pass=True) and not rule(8192, 8192, 8, 1024, t, exact=True, slices=16, one_pass=True)
-        assert not rule(8192, 8192, 8, 65536, t, exact=True, slices=16, one_pass=False)
-    assert not rule(8192, 8192, 8, 65536, 4, exact=True, slices=16, one_pass=True)
-    # ... and in WINDOW PARTS (the library's answer 2 / 4: half / a quarter of the columns staged per workgroup) on layers of >= 6 M index elements
-    for t in (2, 3):
-        assert rule(14336, 4096, 8, 256, t, exact=True, slices=16, one_pass=2) and rule(4096, 14336, 8, 0, t, exact=True, slices=8, one_pass=2)
-        assert not rule(4096, 4096, 8, 0, t, exact=True, slices=8, one_pass=2) and not rule(14336, 512, 8, 0, t, exact=True, slices=16, one_pass=2)
-
-
-def _rule_layer(I, O, v, kr, **more):
-    """stands in for a VQuantLinear in the sliced-route rules: what `_index_elements` / `_res_centroids` and the rules read"""
-    import types
-    return types.SimpleNamespace(indices=torch.empty(1, O // v, 1), group_size=I, vector_len=v, out_features=O,
-                                 num_res_centroids=kr, enable_residual=kr > 0, **more)
-
-
-def test_exact_route_size_rule_is_stated_once(monkeypatch):
-    """`_exact_route_is_large`, the one-token size rule of the reference arithmetic, at its boundaries (read from the constants), and
-    `_compact_refusal(force=False)` answering with that very function: compact mode keeps a layer's one-token speed BECAUSE it asks
-    the rule `_sliced_gemv` routes with - host logic, no GPU"""
-    import vptq_amd.layers.vqlinear as vq
-    import vptq_amd.utils.sliced as sliced
-    one, two = vq._SLICED_EXACT_MIN_ELEMENTS, vq._SLICED_EXACT_RG_MIN_ELEMENTS
-    assert (one, two) == (1 << 20, 2 << 20)
-    size_refusal = "one token takes the gather kernel for this layer (smaller than the exact sliced route's threshold; force=True compacts it)"
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    monkeypatch.setattr(sliced, "exact_column_parts", lambda desc, group_size: (1, 16))   # (the library serves every case: the size rule is asked)
-
-    class Indices:      # (packed indices "on a ROCm device", all zero: no bits past the end of a row)
-        is_cuda = True
-
-        def __init__(self, rows):
-            self.shape = (1, rows, 1)
-
-        def detach(self):
-            return torch.zeros(1, 1, 1, dtype=torch.int32)
-
-    def refusal(I, O, v, kr):
-        m = _rule_layer(I, O, v, kr, num_centroids=65536, num_codebooks=1, enable_outlier=False, enable_norm=True, total_index_bits=0)
-        m.indices = Indices(O // v)
-        m._parameters = {"indices": m.indices}
-        cache = vq.LayerCache("key", _family_desc(I, O, v, 65536, kr), [], torch.device("cpu"), None, 16, 1, torch.float16, 0, B.GEMV_EXACT, 0)
-        m._descriptor = lambda: cache
-        return vq.VQuantLinear._compact_refusal(m, False)
-
-    # (v, kr, I, O, the bound the case sits AT (want) or just below (not want) - None: no size is large enough -, want)
-    cases = ((8, 0, 4096, 2048, one, True), (8, 0, 4096, 2040, one, False), (8, 256, 4096, 2048, one, True), (8, 256, 4096, 2040, one, False),
-             (8, 4096, 8192, 2048, two, True), (8, 4096, 8192, 2040, two, False),
-             (8, 1024, 8192, 8192, None, False),     # a residual table under 4096 entries: the gather kernel holds it in LDS
-             (16, 256, 8192, 8192, None, False))     # v = 16 has no byte side stream: the "other residual" branch
-    for v, kr, I, O, bound, want in cases:
-        m = _rule_layer(I, O, v, kr)
-        if bound is not None:
-            assert vq._index_elements(m) == bound if want else bound - bound // 256 <= vq._index_elements(m) < bound
-        assert vq._res_centroids(m) == kr
-        assert vq._exact_route_is_large(m) is want, (v, kr, I, O)
-        assert refusal(I, O, v, kr) == (None if want else size_refusal), (v, kr, I, O)
-    # one rule, not two that agree today: the refusal follows whatever the function says
-    for v, kr, I, O, _, _ in cases:
-        monkeypatch.setattr(vq, "_exact_route_is_large", lambda layer: True)
-        assert refusal(I, O, v, kr) is None
-        monkeypatch.setattr(vq, "_exact_route_is_large", lambda layer: False)
-        assert refusal(I, O, v, kr) == size_refusal
-
-
-def test_sliced_token_limit_rule(monkeypatch):
-    """VQuantLinear._sliced_token_limit: most tokens served as one sliced launch per token (profiles/r04/sliced_tokens.txt, profiles/r05/
-    sliced_tokens_exact.txt as a rule) - host logic, no GPU"""
-    import types
-    import vptq_amd.layers.vqlinear as vq
-    monkeypatch.setattr(vq, "_SLICED_TOKENS_ENV", None)   # (the tuning override of the folded layouts' rule)
-
-    def limit(I, O, v, kr, exact, slices, tables=1):
-        sl = types.SimpleNamespace(exact=exact, slices=slices, layout=[None] * tables)
-        return vq.VQuantLinear._sliced_token_limit(_rule_layer(I, O, v, kr), sl)
-    assert limit(8192, 8192, 8, 256, True, 16) == 2
-    assert limit(8192, 8192, 8, 256, True, 8) == 1 and limit(4096, 4096, 8, 256, True, 16) == 1
-    assert limit(8192, 8192, 8, 65536, False, 16, 2) == 3
-    assert limit(8192, 8192, 16, 65536, False, 16, 2) == 2
-    assert limit(8192, 8192, 16, 1024, False, 16, 2) == 1
-    sl = types.SimpleNamespace(exact=True, slices=16, layout=[None])
-    assert vq.VQuantLinear._sliced_token_limit(_rule_layer(8192, 8192, 8, 256), sl) == 2 and sl._token_limit == 2   # (remembered on the layout)
-
-
 def test_layer_cache_record_keeps_its_positions(monkeypatch):
     """`VQuantLinear._descriptor()` returns a `LayerCache`: eleven named fields in the order the positional readers depend on (the
     benchmark reads `[1]`, `_gemv_cached` unpacks all eleven) - built on the CPU, the device-only steps stood in for"""

@@ -3,7 +3,9 @@ us per call to ENQUEUE (the loop's wall time before the one synchronize) of
 
   * 1 token of an 8192 x 8192 canonical layer (v8-k256-256): the decode call, which pays the batched-decode guard and nothing else;
   * 12 and 24 tokens of a small v8-k65536-256 layer (2048 -> 512: the kernel is shorter than the Python in front of it) with the
-    knobs of `gemm_gather` and `gemm_gatherw` at "1".
+    knobs of `gemm_gather` and `gemm_gatherw` at "1";
+  * 1 and 3 tokens of another such layer over its sliced layout (`enable_sliced_layout()`, the one-launch knob at "1"): the path
+    of `_gemv_cached` in front of the gather kernels.
 
     python tools/batched_decode_overhead.py [--tree DIR] [--calls 2000] [--reps 7]
 
@@ -26,11 +28,19 @@ try:
 except ImportError:
     from vptq_amd.layers import vqlinear as rules  # (a checkout from before that module)
 rules._GEMM_GATHER_MODE = rules._GEMM_GATHERW_MODE = "1"
+try:
+    from vptq_amd import sliced_routes as sliced_rules   # the home of the sliced-route knobs
+except ImportError:
+    from vptq_amd.layers import vqlinear as sliced_rules  # (a checkout from before that module)
+sliced_rules._SLICED_ONE_LAUNCH = "1"
 
 dev = torch.device("cuda", 0); g = torch.Generator(device=dev).manual_seed(0)
 cases = [("v8-k256-256 8192x8192", mk(8192, 8192, dev, g), 1)]
 big = mk(2048, 512, dev, g, k=65536, kr=256)
 cases += [("v8-k65536-256 2048x512", big, 12), ("v8-k65536-256 2048x512", big, 24)]
+sliced = mk(2048, 512, dev, g, k=65536, kr=256)
+sliced.enable_sliced_layout()
+cases += [("v8-k65536-256 2048x512 sliced", sliced, 1), ("v8-k65536-256 2048x512 sliced", sliced, 3)]
 with torch.no_grad():
     for name, m, tokens in cases:
         x = torch.randn(1, tokens, m.in_features, device=dev, dtype=torch.float16)

@@ -123,7 +123,7 @@ def gemm_k256w_route(out_features: int, in_features: int, tokens: int) -> bool:
 # = vector-rows x columns, least tokens, most tokens), routed by the rule above `_GEMM_GATHER_CELLS` (beats its parent by more than
 # the larger of 5 % and three times the run-to-run spread, in every measured cell of the region, in both dtypes; the routed token
 # counts of a layer are one interval); tools/gemm_gatherw_bench.py writes the table.  No cell starts below 4 M index elements: a
-# compacted 4096 x 4096 layer keeps its dense route, which needs no repack there (`_dense_from_layout`).  VPTQ_GEMM_GATHERW=1 / 0
+# compacted 4096 x 4096 layer keeps its dense route, which needs no repack there (`sliced_routes.dense_from_layout`).  VPTQ_GEMM_GATHERW=1 / 0
 # (with VPTQ_TUNING=1): every supported layer from 17 to 48 tokens / none.
 #
 # profiles/r23/table.md, profiles/r23/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 17 / 24 / 32 / 33 / 40 /

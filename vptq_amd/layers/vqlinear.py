@@ -25,7 +25,6 @@ from __future__ import annotations
 import math
 from typing import NamedTuple, Sequence
 
-import os
 import weakref
 
 import torch
@@ -40,6 +39,10 @@ from vptq_amd.batched_decode import (  # noqa: F401
     BATCHED_DECODE_MAX_TOKENS, BATCHED_DECODE_MIN_TOKENS, GEMM_GATHER_MAX_TOKENS, GEMM_GATHER_PX_MAX_TOKENS, GEMM_GATHER_PX_MIN_TOKENS,
     GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS, GEMM_K256W_MIN_TOKENS, batched_decode_routes,
     batched_decode_takes, gemm_gather_px_route, gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_k256w_route)
+# the sliced-layout rules (1 - 4 tokens) live in vptq_amd/sliced_routes.py and are read through the module (`R.exact_route_is_large`:
+# one monkeypatch changes every reader); only import-time constants that nothing assigns to are imported by name, for the hot guard
+from vptq_amd import sliced_routes as R
+from vptq_amd.sliced_routes import _SLICED_FORMATS, _SLICED_LAYOUT_ENV, _SLICED_MAX_TOKENS
 
 
 def chain_prefetch(layers, circular: bool = False):
@@ -56,57 +59,7 @@ def _raw_stream(device_index: int) -> int:
     return torch._C._cuda_getCurrentRawStream(device_index)
 
 
-# VPTQ_SLICED_LAYOUT: "auto" (default) = every eligible large-codebook layer (v8-k65536-0 / -256) builds the sliced
-# layout at its first one-token call while that leaves a quarter of the device memory free (MI355X: 288 GB - the
-# layouts of a 70B 3-bit model are 45 GB); "1" = always; "0" = never (VQuantLinear.enable_sliced_layout per layer)
-_SLICED_LAYOUT_MODE = os.environ.get("VPTQ_SLICED_LAYOUT", "auto").strip().lower() or "auto"
-_SLICED_LAYOUT_ENV = _SLICED_LAYOUT_MODE not in ("0", "off", "false", "no")
-_SLICED_MIN_FREE_FRACTION = 0.25
-_SLICED_EXACT_MIN_ELEMENTS = 1 << 20   # vector-rows x columns from which the exact sliced kernel beats the gather kernel
-_SLICED_EXACT_RG_MIN_ELEMENTS = 2 << 20   # ... with the residual entries gathered from L2 (two-table formats)
-# most tokens served as one sliced launch PER TOKEN: decided per layer (VQuantLinear._sliced_token_limit);
-# VPTQ_SLICED_TOKENS="one-table,two-table" overrides it (tools/sliced_tokens_bench.py)
-_SLICED_TOKENS_ENV = tuple(int(v) for v in B.tune_env("VPTQ_SLICED_TOKENS").split(",")) if B.tune_env("VPTQ_SLICED_TOKENS") else None
-_SLICED_MAX_TOKENS = max(max(_SLICED_TOKENS_ENV) if _SLICED_TOKENS_ENV else 3, 4)
-# 2 - 4 tokens in ONE sliced launch (gemv_sliced_tok.hip): "auto" (default) = per layer where it was measured faster than the
-# gather kernels and than one sliced launch per token (VQuantLinear._sliced_one_launch); "1" = wherever the library takes the
-# layer; "0" = never
-_SLICED_ONE_LAUNCH = B.tune_env("VPTQ_SLICED_ONE_LAUNCH", "auto").strip().lower() or "auto"
-
-
-_SLICED_SELECTIVE_MIN_ELEMENTS = 6 << 20   # selective roundings over the folded sliced layouts (two-table formats): from 6 M index elements on
-_SLICED_OOM_RETRY_CALLS = 256   # calls of a layer before a sliced-layout build that ran out of memory is tried again
-_SLICED_FORMATS = "v = 8 / 16, 16384 ... 65536 main centroids, one codebook, no outliers, scale / bias"   # `_has_sliced_format` in words
-
-
 _COMPACTED = weakref.WeakSet()   # compacted layers (their share of the compact-mode scratch)
-
-
-# WHICH compacted layers build their dense W straight from the layout (`vptq_dequant_sliced`) instead of repack + `vptq_dequant`: the one
-# rule, read by `_dense_cached` and `dequant()`.  Measured on one MI355X, graph replays over a ring of 4 layers, the two routes in turns,
-# median us per layer, new / repack route (tools/dequant_sliced_bench.py, profiles/r12; spread of the repack route 0.2 - 1.3 us):
-#   rows x columns    v8-k65536-256     v8-k65536-0       v8-k65536-65536   v16-k65536-65536      (fp16 | bf16)
-#   4096 x 4096       0.70 | 0.83       0.74 | 0.85       0.72 | 0.84       0.84 | 0.87
-#   14336 x 4096      0.89 | 0.98       0.98 | 1.07       0.85 | 0.97       1.12 | 1.12
-#   4096 x 14336      1.01 | 1.04       1.09 | 1.13       0.98 | 1.01       1.02 | 1.06
-#   8192 x 8192       1.01 | 1.05       1.09 | 1.12       1.00 | 1.03       1.02 | 1.03
-#   4096 x 28672      0.99 | 1.03       1.21 | 1.27       0.96 | 1.01       1.16 | 1.22
-# The new kernel wins in every format and dtype only on layers of up to 4096 x 4096 (one round of workgroups: its gather and store
-# phases do not overlap inside a workgroup); larger layers keep the repack route.  VPTQ_DEQUANT_SLICED=1 / 0 (with VPTQ_TUNING=1):
-# every compacted layer / none (A/B, and a model that must not hold the repack scratch).
-_DEQUANT_SLICED_MAX_ROWS = 4096
-_DEQUANT_SLICED_MAX_COLS = 4096
-_DEQUANT_SLICED_MODE = (B.tune_env("VPTQ_DEQUANT_SLICED", "auto") or "auto").strip().lower()
-
-
-def _dense_from_layout(layer) -> bool:
-    """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (a library without the entry, added within ABI 11:
-    never - the repack route stays)"""
-    if getattr(B.lib(), "vptq_dequant_sliced", None) is None or _DEQUANT_SLICED_MODE in ("0", "off"):
-        return False
-    if _DEQUANT_SLICED_MODE in ("1", "on"):
-        return True
-    return layer.out_features <= _DEQUANT_SLICED_MAX_ROWS and layer.in_features <= _DEQUANT_SLICED_MAX_COLS
 
 
 class LayerCache(NamedTuple):
@@ -131,30 +84,6 @@ def _index_elements(layer) -> int:   # index elements per table: vector-rows x c
 
 def _res_centroids(layer) -> int:   # entries of the residual codebook; 0 without one
     return layer.num_res_centroids if layer.enable_residual else 0
-
-
-def _has_sliced_format(layer) -> bool:
-    """can a layer of this format have a sliced layout at all?  Static module configuration (a permutation may still be absorbed
-    later; the library decides: vptq_sliced_layout_supported)."""
-    return bool(layer.num_centroids >= 16384 and layer.vector_len in (8, 16) and layer.num_codebooks == 1 and
-                not layer.enable_outlier and layer.enable_norm)
-
-
-def _exact_route_is_large(layer) -> bool:
-    """The one-token size rule of the reference arithmetic: is the layer large enough for the exact sliced kernel to beat the
-    gather kernel?  (`enable_sliced_layout()` asks for the layout on any layer: `_sliced_gemv` adds that opt-in.)"""
-    n_el, kr = _index_elements(layer), _res_centroids(layer)
-    if kr > 0 and not (layer.vector_len == 8 and kr == 256):
-        # any other residual codebook: its entries are gathered from L2 behind the LDS-local main gathers (2 blocks per
-        # queue stage: the CU's L1 miss path is the limit) - us per layer, gather kernels -> sliced, profiles/r05/
-        # sliced_exact_two_table_queue_ab.txt: v8-k65536-65536 8192^2 78.0 -> 59.9, 14336 x 4096 68.5 -> 52.2, 4096^2 21.6 ->
-        # 21.2; v8-k65536-4096 69.9 -> 50.6 / 59.8 -> 44.3 / 20.5 -> 18.4; v16-k65536-65536 53.9 -> 46.7 / 52.3 -> 40.9 / 19.2 ->
-        # 18.3; small residual tables (v16-k65536-1024: the gather kernel holds them in LDS) stay there
-        return kr >= 4096 and n_el >= _SLICED_EXACT_RG_MIN_ELEMENTS
-    # (reference roundings, us per layer, gather -> exact sliced, profiles/r05/sliced_exact.txt: 8192^2 39.4 -> 17.2,
-    # 4096 x 14336 34.5 -> 17.0, 14336 x 4096 34.9 -> 14.7, 4096^2 12.6 -> 9.0, 4096 x 1024 7.8 -> 8.3: from 1 M index elements -
-    # 8 M weights - on)
-    return n_el >= _SLICED_EXACT_MIN_ELEMENTS
 
 
 def _compact_state_dict_hook(module, state_dict, prefix, local_metadata):
@@ -660,7 +589,7 @@ class VQuantLinear(nn.Module):
             why = "indices are not on a ROCm device"
         elif torch.cuda.is_current_stream_capturing():
             why = "inside a stream capture"
-        elif not _has_sliced_format(self):
+        elif not R.has_sliced_format(self.vector_len, self.num_centroids, self.num_codebooks, self.enable_outlier, self.enable_norm):
             self._descriptor()
             why = f"format has no sliced layout ({_SLICED_FORMATS})"
         if why is None:
@@ -673,8 +602,7 @@ class VQuantLinear(nn.Module):
                         sl._workspace(s.cuda_stream)
                         s.synchronize()   # (the layout and the zeroed workspace are complete before any other stream uses them)
             if sl is None:
-                on = self.__dict__.get("_sliced_on")
-                if not (_SLICED_LAYOUT_ENV if on is None else on):
+                if not self.__dict__.get("_sliced_on", _SLICED_LAYOUT_ENV):
                     why = "sliced layouts are switched off (VPTQ_SLICED_LAYOUT=0 / enable_sliced_layout(False))"
                 elif "_sliced_oom" in self.__dict__:
                     why = "out of device memory building the layout"
@@ -690,6 +618,10 @@ class VQuantLinear(nn.Module):
         return rep
 
     def _sliced_gemv(self):
+        """This layer's `SlicedGemv` in the current arithmetic, built at the first call and remembered under a stamp (the descriptor's
+        generation, the indices' version counter), or None: the regular route serves the layer.  Every outcome is stored under the
+        stamp but two: a "no" because a stream capture is in progress and a "no" of the out-of-memory back-off (`_sliced_build`) -
+        a later call asks again."""
         cp = self.__dict__.get("_compact")
         if cp is not None:
             # compact mode: the exact layout is the only copy of the indices - served in every arithmetic, whatever
@@ -698,9 +630,7 @@ class VQuantLinear(nn.Module):
             if cp["gen"] != cache.generation:
                 cp["sl"], cp["gen"] = cp["sl"].rebound(cache.desc), cache.generation
             return cp["sl"]
-        on = self.__dict__.get("_sliced_on")
-        if on is None:
-            on = _SLICED_LAYOUT_ENV
+        on = self.__dict__.get("_sliced_on", _SLICED_LAYOUT_ENV)   # (`enable_sliced_layout()`'s word, else VPTQ_SLICED_LAYOUT's)
         if not on:
             return None
         cache = self._descriptor()
@@ -711,157 +641,93 @@ class VQuantLinear(nn.Module):
             if torch.cuda.is_current_stream_capturing():
                 return None   # (no layout is built inside a capture - and the "no" is not remembered: a later call builds it)
             obj = None
-            from vptq_amd.utils.sliced import SlicedGemv, exact_column_parts
-            desc, flags, lib, n_el = cache.desc, cache.arithmetic_flags, B.lib(), _index_elements(self)
-            opted = "_sliced_on" in self.__dict__   # (enable_sliced_layout() asks for a layout on any layer)
-            # the layer's arithmetic (`arithmetic_flags`) decides the kind of layout, the kind's own rule whether one is wanted
-            if flags & B.GEMV_SELECTIVE and not flags & B.GEMV_EXACT and _res_centroids(self) >= 4096 and \
-                    (n_el >= _SLICED_SELECTIVE_MIN_ELEMENTS or opted) and \
-                    lib.vptq_quant_gemv_sliced_selective_supported(desc) and lib.vptq_sliced_layout_supported_for(desc, 0):
-                # selective roundings, two-table formats (v8-k65536-65536, v16-k65536-65536, ...: 59 / 46 us in the reference's roundings, the
-                # residual entry an L2 gather per element): the FOLDED layouts with VPTQ_GEMV_SELECTIVE - a pre-pass zeroes the blocks an activation
-                # dominates and hands their exact products to the folded launch (gemv_hot.hip): ~21 us (the pre-pass is a launch of its own, ~9 us
-                # at 8192^2: it pays on the large layers - from 6 M index elements on -; smaller two-table layers keep the exact layouts)
-                kind, wanted = "selective", True
-            elif flags & (B.GEMV_EXACT | B.GEMV_SELECTIVE):
-                # the reference's roundings (the default; selective: its one-table and smaller two-table layers) take the EXACT sliced kernel
-                # where the layer is large enough and served - too wide for the LDS in one piece, 28672 columns: as equal column parts
-                kind, wanted = "exact", (_exact_route_is_large(self) or opted) and bool(exact_column_parts(desc, self.group_size)[0])
-            else:   # the opt-in folded form: the folded layouts wherever the library has them
-                kind, wanted = "folded", bool(lib.vptq_sliced_layout_supported_for(desc, 0))
-            exact, selective = kind == "exact", kind == "selective"
+            kind, wanted = self._sliced_kind(cache)
             if wanted and self._sliced_fits(cache, on):
-                # (a build that ran out of device memory is retried only after a back-off: every attempt costs int64 / float64
-                # temporaries of ~160 bytes per element, an empty_cache() and a warning - per decode call, while memory stays tight)
-                oom = self.__dict__.get("_sliced_oom")
-                if oom is not None:
-                    oom[0] -= 1
-                    free = torch.cuda.mem_get_info(cache.device)[0] if oom[0] > 0 else 0
-                    if oom[0] > 0 and free < oom[1]:
-                        return None
-                try:
-                    obj = SlicedGemv(self, exact=exact, selective=selective)
-                    self.__dict__.pop("_sliced_oom", None)
-                except torch.cuda.OutOfMemoryError as e:
-                    # out of device memory while building: the regular route serves the calls until _SLICED_OOM_RETRY_CALLS further
-                    # ones have passed or the device reports twice the free bytes it had now.  Any other error is a bug and propagates.
-                    import warnings
-                    torch.cuda.empty_cache()
-                    if oom is None:   # (warn once per layer)
-                        warnings.warn(f"sliced layout of a {self.in_features} x {self.out_features} layer not built "
-                                      f"({str(e)[:120]}); the layer keeps the gather kernel for now", stacklevel=3)
-                    self.__dict__["_sliced_oom"] = [_SLICED_OOM_RETRY_CALLS, 2 * torch.cuda.mem_get_info(cache.device)[0] + (n_el * 160)]
-                    return None
-                # the kernel over the layouts evaluates the folded form: the same measured gate as every folded route
-                # (_backend.folded_form_is_safe) - its float32 outputs against the gather kernel's (the reference's roundings)
-                # on the probe activations
-                lim = None if exact else (B.SELECTIVE_MAX_PROBE_DISTANCE if selective else B.FOLDED_MAX_PROBE_DISTANCE).get(cache.dtype)
-                if lim is not None and self._parameters.get("weight_bias") is not None:
-                    run = obj
-
-                    def folded(xr, yr):
-                        return run(xr.view(1, 1, -1), yr.view(1, 1, -1), flags=B.GEMV_OUT_F32) is not None
-                    d = B.folded_probe_distance(desc, self.in_features, self.out_features, self._parameters["weight_bias"],
-                                                cache.dtype, cache.device, folded=folded)
-                    if not bool((d <= lim).item()):
-                        obj = None
-                        if selective:
-                            # the gate refused the selective form of this layer: the reference's roundings over an exact layout
-                            # (main entry from LDS, residual entry from L2), where that route serves it
-                            if exact_column_parts(desc, self.group_size)[0] and self._sliced_fits(cache, on):
-                                try:
-                                    obj = SlicedGemv(self, exact=True)
-                                except (torch.cuda.OutOfMemoryError, ValueError):
-                                    obj = None
-            st = (stamp, obj)
-            self.__dict__["_sliced"] = st
+                obj = self._sliced_build(cache, kind)
+                if obj is None:
+                    return None   # (the back-off of a build that ran out of device memory: not remembered either)
+                obj = self._sliced_gate(cache, kind, obj, on)
+            st = self.__dict__["_sliced"] = (stamp, obj)
         return st[1]
 
+    def _sliced_kind(self, cache):
+        """(kind, wanted) of `R.sliced_layout_kind` for this layer: its arithmetic, format and size, whether `enable_sliced_layout()`
+        asked, and the library's three answers (host-only queries without side effects, asked once per layout build)"""
+        from vptq_amd.utils.sliced import exact_column_parts
+        lib, desc = B.lib(), cache.desc
+        folded = bool(lib.vptq_sliced_layout_supported_for(desc, 0))   # (the folded layouts, which the selective form runs over as well)
+        return R.sliced_layout_kind(cache.arithmetic_flags, self.vector_len, _res_centroids(self), _index_elements(self),
+                                    "_sliced_on" in self.__dict__, bool(lib.vptq_quant_gemv_sliced_selective_supported(desc)) and folded,
+                                    bool(exact_column_parts(desc, self.group_size)[0]), folded)
+
+    def _sliced_build(self, cache, kind):
+        """The guarded build: a `SlicedGemv` of `kind`, or None - out of device memory now, or inside the back-off after that.  The
+        caller does NOT store that None under the stamp: every later call counts the back-off down here.  The warning is issued once
+        per layer; a successful build clears `_sliced_oom`."""
+        from vptq_amd.utils.sliced import SlicedGemv
+        # (a build that ran out of device memory is retried only after a back-off: every attempt costs int64 / float64
+        # temporaries of ~160 bytes per element, an empty_cache() and a warning - per decode call, while memory stays tight)
+        oom = self.__dict__.get("_sliced_oom")
+        if oom is not None:
+            oom[0] -= 1
+            if oom[0] > 0 and torch.cuda.mem_get_info(cache.device)[0] < oom[1]:
+                return None
+        try:
+            obj = SlicedGemv(self, exact=kind == "exact", selective=kind == "selective")
+            self.__dict__.pop("_sliced_oom", None)
+            return obj
+        except torch.cuda.OutOfMemoryError as e:
+            # out of device memory while building: the regular route serves the calls until _SLICED_OOM_RETRY_CALLS further
+            # ones have passed or the device reports twice the free bytes it had now.  Any other error is a bug and propagates.
+            import warnings
+            torch.cuda.empty_cache()
+            if oom is None:   # (warn once per layer)
+                warnings.warn(f"sliced layout of a {self.in_features} x {self.out_features} layer not built "
+                              f"({str(e)[:120]}); the layer keeps the gather kernel for now", stacklevel=4)
+            self.__dict__["_sliced_oom"] = [R._SLICED_OOM_RETRY_CALLS, 2 * torch.cuda.mem_get_info(cache.device)[0] + _index_elements(self) * R._SLICED_TORCH_BUILDER_BYTES]
+            return None
+
+    def _sliced_gate(self, cache, kind, obj, on):
+        """The load-time gate of a layout just built: `obj` where it passes (exact layouts are not asked), else - a selective layout
+        - an exact build where `exact_column_parts` and `_sliced_fits` allow one, else None.  `OutOfMemoryError` and `ValueError`
+        are swallowed in that fallback build only.  Whatever comes back is stored under the stamp."""
+        # the kernel over the layouts evaluates the folded form: the same measured gate as every folded route
+        # (_backend.folded_form_is_safe) - its float32 outputs against the gather kernel's (the reference's roundings)
+        # on the probe activations
+        lim = None if kind == "exact" else (B.SELECTIVE_MAX_PROBE_DISTANCE if kind == "selective" else B.FOLDED_MAX_PROBE_DISTANCE).get(cache.dtype)
+        if lim is None or self._parameters.get("weight_bias") is None:
+            return obj
+        from vptq_amd.utils.sliced import SlicedGemv, exact_column_parts
+        d = B.folded_probe_distance(cache.desc, self.in_features, self.out_features, self._parameters["weight_bias"], cache.dtype, cache.device,
+                                    folded=lambda xr, yr: obj(xr.view(1, 1, -1), yr.view(1, 1, -1), flags=B.GEMV_OUT_F32) is not None)
+        if bool((d <= lim).item()):
+            return obj
+        # the gate refused the selective form of this layer: the reference's roundings over an exact layout
+        # (main entry from LDS, residual entry from L2), where that route serves it
+        if kind == "selective" and exact_column_parts(cache.desc, self.group_size)[0] and self._sliced_fits(cache, on):
+            try:
+                return SlicedGemv(self, exact=True)
+            except (torch.cuda.OutOfMemoryError, ValueError):
+                pass
+        return None
+
     def _sliced_token_limit(self, sl) -> int:
-        """most tokens served as one sliced launch per token (measured, profiles/r04/sliced_tokens.txt: 8192^2 / 4096 x 14336 /
-        4096^2, us per layer, gather kernel against T sliced launches - v8-k65536-0: 2 tokens 39.6 / 36.2 / 13.2 against 26.4 /
-        27.1 / 17.0; v8-k65536-256: 41.4 / 36.7 / 13.4 against 34.0 / 34.5 / 19.5; v8-k65536-65536: 2 tokens 78.6 / 66.6 / 22.0
-        against 42.1 / 41.3 / 23.5, 3 tokens 80.9 / 69.1 against 62.2 / 61.7; v16-k65536-65536: 2 tokens 52.9 / 52.0 / 19.6
-        against 40.2 / 44.0 / 24.1; small residual tables of v = 16: never)"""
+        """most tokens served as one sliced launch per token: `R.sliced_token_limit` (the measured table is there) of this layer and
+        layout, remembered on the layout"""
         lim = sl.__dict__.get("_token_limit")
         if lim is None:
-            n_el, kr = _index_elements(self), _res_centroids(self)
-            if sl.exact:
-                # the reference's roundings: the gather kernels take 2 - 8 tokens for the price of one; TWO exact sliced launches beat
-                # them on large v = 8 one-table layers only (profiles/r05/sliced_tokens_exact.txt, gather -> 2 launches, v8-k65536-256 /
-                # -0: 8192^2 41.8 -> 40.0 / 41.4 -> 32.9; 14336 x 4096 37.0 -> 32.6 / 37.1 -> 27.9; 8192 x 28672 148.7 -> 94.8 / 135.1 ->
-                # 80.9; but 4096 x 14336 36.7 -> 37.4, 4096^2 13.5 -> 19.5)
-                lim = 2 if (self.vector_len == 8 and kr in (0, 256) and sl.slices >= 16 and n_el >= 6 << 20) else 1
-            elif _SLICED_TOKENS_ENV is not None:
-                lim = _SLICED_TOKENS_ENV[1 if len(sl.layout) == 2 else 0]
-            else:
-                lim = 1
-                if self.vector_len == 8 and kr in (0, 256) and n_el >= 6 << 20:
-                    lim = 2
-                elif kr >= 16384 and n_el >= 3 << 20:
-                    lim = 3 if (self.vector_len == 8 and kr == 65536 and n_el >= 6 << 20) else 2
-            sl.__dict__["_token_limit"] = lim
+            lim = sl.__dict__["_token_limit"] = R.sliced_token_limit(self.vector_len, _res_centroids(self), _index_elements(self),
+                                                                     sl.exact, sl.slices, len(sl.layout))
         return lim
 
     def _sliced_one_launch(self, sl, tokens: int) -> bool:
-        """2 - 4 tokens in ONE launch over the layouts (column phases; 3 - 4 tokens - in the reference's roundings: 2 - 4 - the
-        contraction on the matrix pipe - gemv_sliced_tok.hip)?  Measured against the gather kernels (profiles/r04/sliced_tokens_one_launch.txt; us per 8192^2 /
-        4096^2 / 14336 x 4096 layer, gather -> one launch): v8-k65536-0: 2 tokens 40.8 / 12.9 / 36.6 -> 21.4 / 11.5 / 19.0, 4 tokens
-        41.1 / 13.4 / 36.9 -> 26.0 / 13.5 / 22.8; -256: 40.9 / 13.2 / 36.8 -> 23.7 / 12.4 / 20.4 and 44.0 / 16.0 / 42.9 -> 29.4 / 14.8 / 23.9;
-        -65536: 78.2 / 21.5 / 68.8 -> 33.7 / 15.9 / 28.5 and 80.0 / 23.6 / 72.0 -> 39.8 / 18.5 / 43.6; v16-k65536-0: 27.7 / 13.7 / 33.5 ->
-        23.4 / 12.8 / 19.5 and 31.1 / 15.2 -> 25.6 / 14.4; v16-k65536-65536: 53.0 / 19.6 / 53.9 -> 37.7 / 17.8 / 36.1 and 55.8 / 21.0 ->
-        46.0 / 20.5 (4096 x 14336: 7 rows per wave - their sums in LDS, two rounds of workgroups: 57.2 -> 58.0, not taken).
-        v = 16 with a residual table of <= 1024 entries stays on the gather kernel, which holds that table in LDS (v16-k65536-1024,
-        2 tokens: 28.3 -> 36.1)."""
+        """2 - 4 tokens in ONE launch over the layouts?  `R.sliced_one_launch` (the measured table is there) of this layer, the layout
+        and the library's two answers for it, remembered on the layout per token count"""
         key = ("_one_launch", tokens)
         ok = sl.__dict__.get(key)
         if ok is None:
-            n_el, kr = _index_elements(self), _res_centroids(self)
-            if _SLICED_ONE_LAUNCH in ("0", "off", "false", "no") or not sl.tokens_supported(tokens):
-                ok = False
-            elif _SLICED_ONE_LAUNCH in ("1", "on", "true", "yes", "always"):
-                ok = True
-            elif sl.exact:
-                # the reference's roundings (gemv_sliced_tok.hip, EX; profiles/r05/sliced_tokens_exact.txt, gather -> one launch, us per
-                # layer, v8-k65536-256): 8192^2: 2 / 3 / 4 tokens 41.5 / 43.7 / 42.0 -> 37.5 / 36.0 / 36.8; 14336 x 4096: 36.7 / 41.0 / 41.3 ->
-                # 37.4 / 37.5 / 38.0; 8192 x 28672: 148.7 / 146.6 / 147.9 -> 122.0 / 124.5 / 127.0 (-0: 135 -> 82 - 86); but 4096^2: 13.5 / 15.8 / 15.7 -> 20.9 / 20.7 / 20.8 and 4096 x 14336: 36.7 / 36.8 / 37.0 -> 41.1 / 41.3 /
-                # 41.9 (8 slices of 128 KiB leave room for a quarter of the columns: 4 phases); v = 16: 28.5 -> 36.0.  5 - 8 tokens: never
-                # (8192^2: 44 - 46 -> 54 - 55)
-                # 2 tokens there: two launches of the one-token kernel are as fast or faster (_sliced_token_limit).
-                # 2 / 3 tokens of layers whose slice leaves room for (2 tokens + 4) bytes per column - 16-slice layouts up to ~12000 /
-                # ~9700 columns - take ONE PASS of the one-token kernel (gemv_sliced.hip, TOK; profiles/r05/sliced_exact_tokens_one_pass.txt,
-                # gather -> one pass, 2 / 3 tokens): 8192^2 42.1 / 44.9 -> 25.1 / 28.3; 8192 x 28672 149 / 147 -> 62 / 76; 8192 x 1024 13.0 / 18.0
-                # -> 11.0 / 12.9 (k65536-0: 41.3 / 42.2 -> 22.2 / 25.9, 134 / 135 -> 53 / 66); narrow layers that fit with 8 slices: parity
-                # (2048 x 8192: 13.5 / 16.0 -> 13.5 / 15.5), v = 16: slower (8192^2 28.6 -> 30.3) - both stay on the gather kernel
-                # two tables (v8-k65536-65536, -4096: the residual entries gathered from L2 ONCE for all tokens; profiles/r05/
-                # sliced_exact_tokens_one_pass.txt): 8192^2 77.8 -> 61.5 / 63.4, 8192 x 28672 255 -> 202 / 206, kr = 4096: 68 -> 53 / 54; small
-                # layers lose (8192 x 1024: 18.8 -> 21.1): the one-token rule's sizes
-                # ... in WINDOW PARTS where only half of the columns' operands fit beside the slice (WPT; profiles/r05/
-                # sliced_exact_tokens_window_parts.txt, gather -> one pass, 2 / 3 tokens, k65536-256 / -0): 14336 x 4096 37.0 / 42.6 -> 24.9 / 28.4
-                # and 36.9 / 35.3 -> 21.7 / 26.2; 4096 x 14336 37.1 / 38.2 -> 31.5 / 37.1 and 36.2 / 35.0 -> 27.9 / 34.2; smaller layers lose
-                # (4096^2 13.6 / 16.2 -> 14.8 / 16.7): from 6 M index elements on
-                if self.vector_len != 8:
-                    ok = False
-                elif kr not in (0, 256):
-                    ok = sl.slices >= 16 and tokens <= 3 and kr >= 4096 and n_el >= _SLICED_EXACT_RG_MIN_ELEMENTS and sl.tokens_one_pass(tokens)
-                else:
-                    wparts = sl.tokens_window_parts(tokens) if tokens <= 3 else 0
-                    if wparts == 1:
-                        ok = sl.slices >= 16
-                    elif wparts > 1:
-                        ok = n_el >= 6 << 20
-                    else:
-                        ok = sl.slices >= 16 and 3 <= tokens <= 4 and n_el >= 6 << 20
-            else:
-                if n_el < 1 << 19:       # (smaller layers are launch-bound on every route and were not measured)
-                    ok = False
-                elif self.vector_len == 8 or kr == 0:
-                    ok = True
-                elif kr <= 1024:
-                    ok = False
-                else:
-                    ok = tokens == 2 or self.out_features <= 8192
-            sl.__dict__[key] = ok
+            ok = sl.__dict__[key] = R.sliced_one_launch(self.vector_len, _res_centroids(self), _index_elements(self), self.out_features, tokens,
+                                                        sl.exact, sl.slices, sl.tokens_supported(tokens), sl.tokens_window_parts(tokens))
         return ok
 
     def _sliced_fits(self, cache, on) -> bool:
@@ -869,60 +735,54 @@ class VQuantLinear(nn.Module):
         _SLICED_MIN_FREE_FRACTION of the device memory free, and never inside a stream capture"""
         if torch.cuda.is_current_stream_capturing():
             return False
-        if on is True and "_sliced_on" in self.__dict__ or _SLICED_LAYOUT_MODE in ("1", "on", "true", "yes", "always"):
+        if on is True and "_sliced_on" in self.__dict__ or R._SLICED_LAYOUT_ALWAYS:
             return True
         free, total = torch.cuda.mem_get_info(cache.device)
-        elems = _index_elements(self)
-        two = B.lib().vptq_sliced_layout_tables(cache.desc) == 2   # (one layout per table)
         from vptq_amd.utils.sliced import device_builder_enabled
-        need = elems * (8 if two else 5)   # the layout; the torch recipe: + its int64 / float64 temporaries (the HIP builder has none)
-        if not device_builder_enabled(self._parameters["indices"]):
-            need += elems * 8 * 20
-        return free - need > _SLICED_MIN_FREE_FRACTION * total
+        need = R.sliced_build_bytes(_index_elements(self), B.lib().vptq_sliced_layout_tables(cache.desc) == 2,   # (one layout per table)
+                                    device_builder_enabled(self._parameters["indices"]))
+        return free - need > R._SLICED_MIN_FREE_FRACTION * total
+
+    def _sliced_cached(self, x: torch.Tensor, tokens: int):
+        """1 - 4 tokens over this layer's sliced layout(s): y, or None where they do not serve the call (no layout, a launch flag
+        that rules them out, a token count no rule routes, a launch that steps aside) - `_gemv_cached` goes on with its own route.
+        Siblings first, then the layer's own launch."""
+        if "_sliced_cand" not in self.__dict__:
+            # (static module configuration: decided once, so that every other layer pays one dict look-up per call)
+            self.__dict__["_sliced_cand"] = R.has_sliced_format(self.vector_len, self.num_centroids, self.num_codebooks, self.enable_outlier, self.enable_norm)
+        sl = self._sliced_gemv() if self.__dict__["_sliced_cand"] else None
+        gf = ops.quant_gemm_flags()
+        if sl is None or gf & B.GEMV_FORCE_GENERIC or not (sl.exact or not (gf & B.GEMV_EXACT)):
+            return None
+        if tokens == 1 or (tokens <= 4 and self._sliced_one_launch(sl, tokens) and x.is_contiguous()):
+            sib = self.__dict__.get("_siblings")
+            if sib is not None:      # q / k / v, gate / up: one sliced launch for the group
+                y = sib.forward_sliced(self, x, tokens)
+                if y is not None:
+                    return y
+            # (None: misaligned activation, capture on a stream the layer has not run on / without a workspace yet, ...)
+            return sl(x) if tokens == 1 else sl.forward_tokens(x)
+        if tokens <= self._sliced_token_limit(sl) and x.is_contiguous() and (self.in_features * x.element_size()) % 16 == 0:
+            # 2 (the 4-bit format: 3) tokens of a LARGE layer = one launch per token over the layouts: the gather
+            # kernels cost about as much for one token as for four (they are bound by the table gathers, not by
+            # the FMAs), the sliced kernel a third to a half of that per token (profiles/r04/sliced_tokens.txt)
+            x2 = x.reshape(tokens, self.in_features)
+            y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=x.dtype, device=x.device)
+            y2 = y.view(tokens, self.out_features)
+            for t in range(tokens):
+                if sl(x2[t], y2[t]) is None:
+                    return None
+            return y
+        return None
 
     def _gemv_cached(self, x: torch.Tensor, tokens: int) -> torch.Tensor:
         """Decode fast path: identical to `ops.quant_gemm` for 1..8 (canonical format: 16) tokens with a cached
         descriptor; layers linked by `link_siblings` share one grouped launch."""
         if tokens <= _SLICED_MAX_TOKENS and self.__dict__.get("_sliced_cand", True) and (_SLICED_LAYOUT_ENV or "_sliced_on" in self.__dict__ or
                                                                                          "_compact" in self.__dict__):
-            if "_sliced_cand" not in self.__dict__:
-                # (static module configuration: decided once, so that every other layer pays one dict look-up per call)
-                self.__dict__["_sliced_cand"] = _has_sliced_format(self)
-            sl = self._sliced_gemv() if self.__dict__["_sliced_cand"] else None
-            gf = ops.quant_gemm_flags()
-            if sl is not None and not (gf & B.GEMV_FORCE_GENERIC) and (sl.exact or not (gf & B.GEMV_EXACT)):
-                if tokens == 1:
-                    sib = self.__dict__.get("_siblings")
-                    if sib is not None:      # q / k / v, gate / up: one sliced launch for the group
-                        y = sib.forward_sliced(self, x)
-                        if y is not None:
-                            return y
-                    y = sl(x)
-                    if y is not None:   # (None: misaligned activation, capture on a stream the layer has not run on, ...)
-                        return y
-                elif tokens <= 4 and self._sliced_one_launch(sl, tokens) and x.is_contiguous():
-                    sib = self.__dict__.get("_siblings")
-                    if sib is not None:      # q / k / v, gate / up: one launch for the group
-                        y = sib.forward_sliced(self, x, tokens)
-                        if y is not None:
-                            return y
-                    y = sl.forward_tokens(x)
-                    if y is not None:   # (None: misaligned activation, capture on a stream without a workspace yet)
-                        return y
-                elif tokens <= self._sliced_token_limit(sl) and x.is_contiguous() and (self.in_features * x.element_size()) % 16 == 0:
-                    # 2 (the 4-bit format: 3) tokens of a LARGE layer = one launch per token over the layouts: the gather
-                    # kernels cost about as much for one token as for four (they are bound by the table gathers, not by
-                    # the FMAs), the sliced kernel a third to a half of that per token (profiles/r04/sliced_tokens.txt)
-                    x2 = x.reshape(tokens, self.in_features)
-                    y = torch.empty(x.shape[:-1] + (self.out_features,), dtype=x.dtype, device=x.device)
-                    y2 = y.view(tokens, self.out_features)
-                    ok = True
-                    for t in range(tokens):
-                        if sl(x2[t], y2[t]) is None:
-                            ok = False
-                            break
-                    if ok:
-                        return y
+            y = self._sliced_cached(x, tokens)   # (1 - 4 tokens over the sliced layouts, where a rule of vptq_amd/sliced_routes.py takes the call)
+            if y is not None:
+                return y
         group = self.__dict__.get("_siblings")
         if group is not None and tokens <= group.MAX_TOKENS:
             y = group.forward(self, x, tokens)
@@ -1055,8 +915,8 @@ class VQuantLinear(nn.Module):
         _, desc, _, dequant = dense
         W = torch.empty((self.out_features, self.in_features), dtype=wdtype, device=dev)
         cp = self.__dict__.get("_compact")
-        # (compact mode: W straight from the layout where that is the faster route - no repack, no scratch; `_dense_from_layout`)
-        sl = self._sliced_gemv() if cp is not None and _dense_from_layout(self) else None
+        # (compact mode: W straight from the layout where that is the faster route - no repack, no scratch; `R.dense_from_layout`)
+        sl = self._sliced_gemv() if cp is not None and self._dense_from_layout() else None
         if torch.cuda.current_device() != dev_index:
             with torch.cuda.device(dev):
                 sp = B.current_stream_ptr(dev)
@@ -1076,10 +936,15 @@ class VQuantLinear(nn.Module):
             B.check(rc, "vptq_dequant")
         return torch.nn.functional.linear(x, W, self._parameters.get("bias"))
 
+    def _dense_from_layout(self) -> bool:
+        """does this COMPACTED layer build its dense W with `vptq_dequant_sliced`?  (`R.dense_from_layout` of its shape and of whether
+        the library has the entry)"""
+        return R.dense_from_layout(self.out_features, self.in_features, getattr(B.lib(), "vptq_dequant_sliced", None) is not None)
+
     def dequant(self) -> torch.Tensor:
         """Dense W[out_features, in_features] (what the reference calls
         `ops.dequant(...)` with this layer's fields)."""
-        if "_compact" in self.__dict__ and _dense_from_layout(self):
+        if "_compact" in self.__dict__ and self._dense_from_layout():
             return self._sliced_gemv().dequant()   # (compact mode: straight from the layout, the same bits)
         return ops.dequant(
             indices=self.packed_indices(), centroids=self.centroids.weight,
@@ -1102,14 +967,14 @@ class VQuantLinear(nn.Module):
     # vptq_sliced_layout_repack), so a layer served from it at one token can drop its packed `indices`: about a third of the resident
     # weights of the large-codebook formats.  1 - 4 tokens take the sliced kernels as before; the dense route (many tokens) and
     # dequant() of layers up to 4096 x 4096 build W straight from the layout (vptq_dequant_sliced: the bits of vptq_dequant, no packed
-    # stream in between; `_dense_from_layout` above has the rule and its numbers); every path that still reads the packed stream (the
+    # stream in between; `dense_from_layout` in vptq_amd/sliced_routes.py has the rule and its numbers); every path that still reads the packed stream (the
     # gather kernels of 5 - 8 tokens, the dense route of larger layers, state_dict(), shards, copies) gets it rebuilt by the repack kernel - into a per-stream scratch buffer for launches,
     # into a fresh tensor otherwise.  `indices` is a meta-device parameter of the same shape meanwhile.
 
     def compact(self, force: bool = False) -> int:
         """Hold this layer's indices in its exact sliced layout only; returns the bytes freed (0: not compacted - the reason is
         `layer.compact_skipped`).  Without `force`, only layers the product already serves from an exact layout at one token
-        (the reference arithmetic's rule in `_sliced_gemv`): their one-token speed is unchanged by construction.  Refused, the
+        (the reference arithmetic's rule `R.exact_route_is_large`): their one-token speed is unchanged by construction.  Refused, the
         layer untouched, for: formats without an exact layout, non-zero bits past G T in a row, a stream capture, a layout build
         that runs out of device memory.  A compacted layer takes the reference's roundings in every arithmetic; `.to()` refuses
         it (`uncompact()` first); `load_state_dict` uncompacts it."""
@@ -1125,7 +990,7 @@ class VQuantLinear(nn.Module):
         """None, or why this layer cannot be compacted (nothing is changed here)"""
         from vptq_amd.utils.sliced import exact_column_parts, tail_bits_clear
         ind = self._parameters["indices"]
-        if not _has_sliced_format(self):
+        if not R.has_sliced_format(self.vector_len, self.num_centroids, self.num_codebooks, self.enable_outlier, self.enable_norm):
             return f"format has no exact sliced layout ({_SLICED_FORMATS})"
         if not tail_bits_clear(ind.detach(), self.group_size, self.total_index_bits):
             return "non-zero bits past group_size x index bits in a row of the packed indices: a layout cannot hold them"
@@ -1135,7 +1000,7 @@ class VQuantLinear(nn.Module):
             return "inside a stream capture"
         if not exact_column_parts(self._descriptor().desc, self.group_size)[0]:
             return "no exact sliced layout serves this layer (too wide, or the format's LDS budget)"
-        if not force and not _exact_route_is_large(self):
+        if not force and not R.exact_route_is_large(self.vector_len, _res_centroids(self), _index_elements(self)):
             return "one token takes the gather kernel for this layer (smaller than the exact sliced route's threshold; force=True compacts it)"
         return None
 
