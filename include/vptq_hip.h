@@ -332,6 +332,21 @@ VPTQ_API const char* vptq_quant_gemv_chain_kernel_name(const VptqLayerDesc* desc
  * vptq_quant_gemv_chain_kernel_name's answer). */
 VPTQ_API int vptq_quant_gemv_chain_plan(const VptqLayerDesc* descs, int n, int flags, int workgroups, int* visit,
                                         int* grid, int* first_wg, int* rows_per_wg);
+/* Diagnostic (added within ABI 12): the launch's SECOND geometry, "rows per wave" (gemv_k256c_rows_kernel; reported under the
+ * family name "gemv_k256c_kernel", vptq_quant_gemv_chain_instance appends " geom=rows").  A wave owns a row group of 8
+ * vector-rows across the layer's whole width, so no sum crosses the waves; a workgroup-task = 16 consecutive row groups of one
+ * layer, one per wave, walked in steps of 128 columns; task k of layer i goes to workgroup (first_wg[i] + k) mod *grid, *grid =
+ * the workgroups.  It serves fp16 layers, VPTQ_GEMV_EXACT, independent lists, 16-bit outputs (VPTQ_E_UNSUPPORTED otherwise, and
+ * for a list the persistent launch does not take); vptq_quant_gemv_chain_plan goes on describing the first geometry for every
+ * launch.  *taken = the rule's answer for a launch with `workgroups` workgroups (0: the device's): 1 where the tasks number at
+ * least the workgroups AND the busiest workgroup's steps longest[0] (a step = 128 columns x 8 vector-rows per wave in both
+ * geometries) do not exceed longest[1], those of the first geometry's plan for the same launch.  A launch follows the rule; the tuning
+ * knob VPTQ_K256C_ROWS (with VPTQ_TUNING=1) overrides it: 0 = never, 1 = wherever the geometry serves the launch.  Out per layer:
+ * tasks[i], steps[i] (per task).  An output's fp32 sum is formed per lane over all of its column blocks, then over 16 lanes in the first geometry's
+ * tree: the weights are bit for bit vptq_dequant's, the outputs need not equal the first geometry's to the bit.  Alignment:
+ * that of the chain call; y[i] is stored in 2-byte pieces. */
+VPTQ_API int vptq_quant_gemv_chain_rows_plan(const VptqLayerDesc* descs, int n, int flags, int workgroups, int* taken,
+                                             int* grid, int* first_wg, int* tasks, int* steps, int* longest);
 
 /*
  * Many tokens (prefill): y[tokens, O] = x[tokens, I] @ W^T + bias with the dequantisation FUSED

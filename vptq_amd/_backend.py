@@ -108,7 +108,9 @@ EXPORTS = {
     "vptq_quant_gemv_chain_kernel_name": (C.c_char_p, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
     "vptq_quant_gemv_chain_plan": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                              C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "vptq_dequant": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp]),
+    # (within ABI 12) the chain launch's second geometry: taken, grid, first_wg[], tasks[], steps[], longest[2]
+    "vptq_quant_gemv_chain_rows_plan": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 6),
+    "vptq_dequant":(C.c_int, [C.POINTER(LayerDesc), _vp, _vp]),
     # (ABI 12) which instantiation of dequant_kernel vptq_dequant would launch and the paths its threads take, as text
     "vptq_dequant_instance": (C.c_int, [C.POINTER(LayerDesc), _vp, C.c_char_p, C.c_size_t]),
     "vptq_sliced_layout_supported": (C.c_int, [C.POINTER(LayerDesc)]),

@@ -643,6 +643,25 @@ int vptq_quant_gemv_chain_plan(const VptqLayerDesc* descs, int n, int flags, int
   return VPTQ_OK;
 }
 
+int vptq_quant_gemv_chain_rows_plan(const VptqLayerDesc* descs, int n, int flags, int workgroups, int* taken, int* grid,
+                                    int* first_wg, int* tasks, int* steps, int* longest) {
+  if (!descs || !taken || !grid || !first_wg || !tasks || !steps || !longest)
+    return fail(VPTQ_E_NULL, "descs / taken / grid / first_wg / tasks / steps / longest is NULL");
+  if (n < 1 || n > 32) return fail(VPTQ_E_SHAPE, "n %d outside [1, 32] (one persistent launch)", n);
+  if (workgroups < 0) return fail(VPTQ_E_SHAPE, "workgroups %d < 0", workgroups);
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_layer(&descs[i]);
+    if (rc) return rc;
+  }
+  flags = drop_redundant_selective(flags);
+  if (!chain_kernel_takes(descs, n, nullptr, 1, flags))
+    return fail(VPTQ_E_UNSUPPORTED, "the persistent chain launch does not take these layers with flags 0x%x", flags);
+  const hipError_t e = vptq::gemv_k256c_rows_plan(descs, n, flags & ~VPTQ_GEMV_CHAIN_DEPENDENT, (flags & VPTQ_GEMV_CHAIN_DEPENDENT) != 0,
+                                                  workgroups, taken, grid, first_wg, tasks, steps, longest);
+  if (e != hipSuccess) return fail(VPTQ_E_UNSUPPORTED, "the rows geometry does not serve these layers with flags 0x%x", flags);
+  return VPTQ_OK;
+}
+
 // (chain_decide with the workspace ..._workspace_bytes_for asks for assumed, as vptq_quant_gemv_chain_kernel_name does)
 int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes) {
   if (!descs || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / buf is NULL");
@@ -685,6 +704,8 @@ int vptq_quant_gemv_chain_instance(const VptqLayerDesc* descs, int n, int tokens
     for (int i = 0; i < m; ++i) t.add("%s%d", i ? "," : "", vptq::gemv_k256c_sweeps(run[i0 + i]));
     t.add(" perm=");
     for (int i = 0; i < m; ++i) t.add("%s%d", i ? "," : "", descs[i0 + i].perm ? 1 : 0);
+    // (only where the launch takes its second geometry, gemv_k256c_rows_kernel: every other launch's text is what it was)
+    if (vptq::gemv_k256c_rows(run + i0, m, lflags, dependent)) t.add(" geom=rows");
   }
   return instance_done(t);
 }

@@ -45,10 +45,12 @@
 //    11.5 us per 8192^2 layer - the hand-over through memory costs ~6 us per layer, more than the
 //    kernel boundary it replaces (7.3 us with one launch per layer): exists for completeness.
 #include <type_traits>
+#include <vector>
 
 #include "common.h"
 #include "kernels.h"
 #include "k256.h"
+#include "k256c.h"
 
 namespace vptq {
 
@@ -100,7 +102,6 @@ static_assert(kCSub != 1 || (kCWaves == 16 && kCSplit == 1), "1 subgroup: the 16
 constexpr int kCDepth = VPTQ_K256C_DEPTH;
 static_assert(kCDepth >= 2 && kCDepth <= 6, "queue depth");
 constexpr int kCSlots = 4;                           // cross-wave partial-sum slots
-constexpr uint32_t kCImgBytes = 65536;               // 256 rows x 16 units x 16 B
 constexpr uint32_t kCXsOff = 2 * kCImgBytes;         // wave-private activation slots
 // arithmetic of a launch: folded (sum (c + r) f16(s x) + sum b x), the reference's roundings per weight, or SELECTIVE:
 // the folded form, with the reference's roundings wherever an activation column dominates (kCModeSel below)
@@ -140,100 +141,6 @@ constexpr int kCFlagStride = 256;   // DEP: arrival flags per layer (one per wor
 // (s_setprio 0-3 by arrival order for the whole wave: chain32 4.83 -> 4.90 us; no balancing: 5.00 us;
 // profiles/r03/chain_bench_variants.txt "prio0" / "nobal")
 
-// One layer of the launch: 88 bytes of kernel arguments (the K256Layer of the other kernels carries
-// fields this one has no use for, and 32 of those + the search table would not fit 4 KiB).
-struct CLayerArgs {
-  const uint32_t* idx;
-  const uint32_t* cent;
-  const uint32_t* rcent;
-  const uint16_t* x;
-  uint16_t* y;
-  const uint16_t* scale;
-  const uint16_t* wbias;
-  const uint16_t* bias;
-  int N, G, O, row_words;
-  int wgs;   // workgroup that owns block 0 of the layer
-  int rpw;   // row groups per block
-};
-constexpr int kCHeadPad = 4;   // the layer search reads 4 headers at a time
-struct K256CParams {
-  int n_layers;
-  int tokens;        // token count | kOutF32Bit
-  uint32_t* sync;    // DEP: kCFlagStride arrival flags per layer (zeroed before the launch)
-  CLayerArgs layer[kMaxGroup];
-  // what the search for a workgroup's next layer needs, 8 bytes per layer:
-  // {first workgroup | row groups per block << 16, row groups | sweeps per row group << 24}
-  uint32_t head[kMaxGroup + kCHeadPad][2];
-};
-static_assert(sizeof(CLayerArgs) == 88 && offsetof(K256CParams, layer) == 16 &&
-              offsetof(K256CParams, head) == 16 + kMaxGroup * 88 && sizeof(K256CParams) <= 4096, "kernarg layout");
-
-typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
-typedef const char __attribute__((address_space(4)))* kernarg_ptr_t;
-
-// Layer L of the kernel arguments in one batch of scalar loads.  Everything a wave looks up on its
-// way through the stream comes out of the kernel-argument segment through the scalar cache: the
-// LDS is the busiest unit of this kernel (a read issued behind 16 waves' gathers comes back late),
-// and indexing the by-value argument struct with a run-time index makes the compiler copy it to
-// scratch memory.
-static __device__ __forceinline__ CLayerArgs c_load_layer(int L) {
-  typedef int i16_t __attribute__((ext_vector_type(16)));
-  typedef int i4_t __attribute__((ext_vector_type(4)));
-  typedef int i2_t __attribute__((ext_vector_type(2)));
-  L = __builtin_amdgcn_readfirstlane(L);   // (wave-uniform by construction; the compiler cannot always prove it)
-  const kernarg_ptr_t lp = (kernarg_ptr_t)__builtin_amdgcn_kernarg_segment_ptr() + 16 + (size_t)L * sizeof(CLayerArgs);
-  i16_t a; i4_t b; i2_t c;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile(
-      "s_load_dwordx16 %0, %3, 0x0\n\t"
-      "s_load_dwordx4 %1, %3, 0x40\n\t"
-      "s_load_dwordx2 %2, %3, 0x50\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&s"(a), "=&s"(b), "=&s"(c)
-      : "s"(lp)
-      : "memory");
-#else
-  a = i16_t{}; b = i4_t{}; c = i2_t{}; (void)lp;
-#endif
-  CLayerArgs Ly;
-  __builtin_memcpy((char*)&Ly, &a, 64);
-  __builtin_memcpy((char*)&Ly + 64, &b, 16);
-  __builtin_memcpy((char*)&Ly + 80, &c, 8);
-  Ly.idx = as_global(Ly.idx); Ly.cent = as_global(Ly.cent); Ly.rcent = as_global(Ly.rcent);
-  Ly.x = as_global(Ly.x); Ly.y = as_global(Ly.y); Ly.scale = as_global(Ly.scale);
-  Ly.wbias = as_global(Ly.wbias); Ly.bias = as_global(Ly.bias);
-  return Ly;
-}
-// the two codebook pointers of layer L
-struct CFillL { const uint32_t* cent; const uint32_t* rcent; };
-static __device__ __forceinline__ CFillL c_load_fill(int L) {
-  typedef int i4_t __attribute__((ext_vector_type(4)));
-  L = __builtin_amdgcn_readfirstlane(L);
-  const kernarg_ptr_t lp = (kernarg_ptr_t)__builtin_amdgcn_kernarg_segment_ptr() + 16 + (size_t)L * sizeof(CLayerArgs);
-  i4_t a;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_load_dwordx4 %0, %1, 0x8\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a) : "s"(lp) : "memory");
-#else
-  a = i4_t{}; (void)lp;
-#endif
-  CFillL F;
-  __builtin_memcpy((char*)&F, &a, 16);
-  F.cent = as_global(F.cent); F.rcent = as_global(F.rcent);
-  return F;
-}
-// search headers of layers L .. L + 3 (the table is padded with kCHeadPad empty layers)
-typedef int c_head4_t __attribute__((ext_vector_type(8)));
-static __device__ __forceinline__ c_head4_t c_load_heads(int L) {
-  L = __builtin_amdgcn_readfirstlane(L);
-  const kernarg_ptr_t hp = (kernarg_ptr_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(K256CParams, head) + (size_t)L * 8;
-  c_head4_t h;
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm volatile("s_load_dwordx8 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(h) : "s"(hp) : "memory");
-#else
-  h = c_head4_t{}; (void)hp;
-#endif
-  return h;
-}
 
 // position in the workgroup's flat stream; everything is wave-uniform
 struct CCursor {
@@ -243,13 +150,6 @@ struct CCursor {
   int ns;   // sweeps per row group of layer L
   int ng;   // row groups of layer L
 };
-// the fields of a layer each side needs (the rest of a K256Layer dies right after the load)
-struct CIssueL { const uint32_t* idx; const uint16_t* x; const uint16_t* scale; const uint16_t* wbias; int N, G, row_words; };
-struct CConsL { uint16_t* y; const uint16_t* bias; int N, G, O; };
-static __device__ __forceinline__ CIssueL c_issue_of(const CLayerArgs& L) {
-  return CIssueL{L.idx, L.x, L.scale, L.wbias, L.N, L.G, L.row_words};
-}
-static __device__ __forceinline__ CConsL c_cons_of(const CLayerArgs& L) { return CConsL{L.y, L.bias, L.N, L.G, L.O}; }
 
 // f(slot 0), f(slot 1), ... f(slot kCDepth - 1) with the slot as a compile-time constant.  (Not common.h's for_slots<kCDepth>: its
 // halving recursion leaves the compiler another order of a few scalar instructions in this kernel - profiles/r18/README.md.)
@@ -1377,6 +1277,84 @@ bool gemv_k256c_fills_device(const VptqLayerDesc* descs, int n, bool dependent) 
   return 4 * c_blocks(descs, n, cus, c_visit(descs, n, cus, dependent)) >= 3ll * cus;
 }
 
+// ---- the second geometry of the launch, "rows per wave" (gemv_k256r.hip): a wave owns a row group across the
+// layer's whole width, so no sum crosses the waves.  A workgroup-task = kRTaskGroups consecutive row groups of one layer (one
+// per wave; the last task of a layer may leave waves idle), r_steps(layer) steps of 128 columns long; the tasks are dealt
+// round-robin over ALL `cus` workgroups, the layers continuing each other's round robin as above.
+static int r_tasks(const VptqLayerDesc& d) { return (c_groups(d) + kRTaskGroups - 1) / kRTaskGroups; }
+static int r_steps(const VptqLayerDesc& d) { return (d.group_size + kRStepCols - 1) / kRStepCols; }
+// fp16, the reference's roundings, independent layers, 16-bit outputs (and the build's geometry constants the kernel restates)
+static bool r_servable(const VptqLayerDesc* descs, int n, int flags, bool dependent) {
+  if (VPTQ_K256C_PROF != 0 || kCWaves != kRTaskGroups || kCRows != 8 || kCBlockCols != kRStepCols) return false;
+  if (n < 1 || n > kMaxGroup || dependent || (flags & VPTQ_GEMV_OUT_F32) || gemv_k256c_mode(flags, dependent) != kCModeExact) return false;
+  for (int i = 0; i < n; ++i)
+    if (descs[i].dtype != VPTQ_DTYPE_F16 || r_steps(descs[i]) > 0xffff) return false;
+  return true;
+}
+// steps of the busiest workgroup: a step is 128 columns x 8 vector-rows per wave in both geometries
+static long long r_longest(const VptqLayerDesc* descs, int n, int cus, int* first_wg, long long* total_out) {
+  std::vector<long long> steps((size_t)cus, 0);
+  long long first = 0;
+  for (int i = 0; i < n; ++i) {
+    if (first_wg) first_wg[i] = (int)(first % cus);
+    const int nt = r_tasks(descs[i]);
+    for (int k = 0; k < nt; ++k) steps[(size_t)((first + k) % cus)] += r_steps(descs[i]);
+    first += nt;
+  }
+  *total_out = first;
+  long long m = 0;
+  for (long long s : steps) m = s > m ? s : m;
+  return m;
+}
+static hipError_t c_plan(const VptqLayerDesc* descs, int n, bool dependent, int cus, int* visit_out, int* grid_out,
+                         int* first_wg, int* rows_per_wg);
+static long long c_longest(const VptqLayerDesc* descs, int n, int cus, bool dependent) {
+  int visit = 0, grid = 0, first_wg[kMaxGroup], rpws[kMaxGroup];
+  if (c_plan(descs, n, dependent, cus, &visit, &grid, first_wg, rpws) != hipSuccess || grid < 1) return -1;
+  std::vector<long long> steps((size_t)grid, 0);
+  for (int i = 0; i < n; ++i) {
+    const int ng = c_groups(descs[i]), ns = gemv_k256c_sweeps(descs[i]);
+    for (int k = 0; k * rpws[i] < ng; ++k) {
+      const int rows = (k + 1) * rpws[i] <= ng ? rpws[i] : ng - k * rpws[i];
+      steps[(size_t)((first_wg[i] + k) % grid)] += (long long)rows * ns;
+    }
+  }
+  long long m = 0;
+  for (long long s : steps) m = s > m ? s : m;
+  return m;
+}
+// THE RULE.  The rows geometry takes a launch it can serve when (a) there are at least as many workgroup-tasks as workgroups -
+// the launch fills the device in this geometry - and (b) its busiest workgroup walks no more steps than the busiest one of the
+// schedule above would for the same launch; both counts from the plans.  VPTQ_K256C_ROWS (VPTQ_TUNING=1): 0 never, 1 whenever
+// servable; VPTQ_K256C_WGS is honoured through c_workgroups.
+hipError_t gemv_k256c_rows_plan(const VptqLayerDesc* descs, int n, int flags, bool dependent, int workgroups, int* taken,
+                                int* grid, int* first_wg, int* tasks, int* steps, int* longest) {
+  if (!r_servable(descs, n, flags, dependent)) return hipErrorInvalidValue;
+  const int cus = c_workgroups(dependent, workgroups);
+  if (cus < 1 || cus > 0xffff) return hipErrorInvalidValue;
+  long long total = 0;
+  const long long lr = r_longest(descs, n, cus, first_wg, &total), lc = c_longest(descs, n, cus, dependent);
+  if (lc < 0 || lr > 0x7fffffff || lc > 0x7fffffff) return hipErrorInvalidValue;
+  for (int i = 0; i < n; ++i) {
+    if (tasks) tasks[i] = r_tasks(descs[i]);
+    if (steps) steps[i] = r_steps(descs[i]);
+  }
+  if (taken) *taken = (total >= cus && lr <= lc) ? 1 : 0;
+  if (grid) *grid = cus;
+  if (longest) { longest[0] = (int)lr; longest[1] = (int)lc; }
+  return hipSuccess;
+}
+// What a LAUNCH does: the rule above (headline ring, python bench.py, same box in turns: 2825 -> 2876 GB/s, + 1.8 %, the first
+// geometry's own spread 0.1 %; kernel mean 190.1 -> 186.9 us per 32 layers; profiles/r28/README.md).
+// VPTQ_K256C_ROWS (VPTQ_TUNING=1): 0 = never, 1 = whenever the geometry serves the launch, 2 / unset = the rule.
+bool gemv_k256c_rows(const VptqLayerDesc* descs, int n, int flags, bool dependent) {
+  static const int knob = tune_int("VPTQ_K256C_ROWS", 2);
+  if (knob != 1 && knob != 2) return false;
+  int rule = 0;
+  if (gemv_k256c_rows_plan(descs, n, flags, dependent, 0, &rule, nullptr, nullptr, nullptr, nullptr, nullptr) != hipSuccess) return false;
+  return knob == 1 || rule != 0;
+}
+
 template <typename DT, bool DEP, int MODE = kCModeFolded>
 static hipError_t launch_c(const K256CParams& P, int grid, hipStream_t st) {
   constexpr auto kern = gemv_k256c_kernel<DT, DEP, MODE>;
@@ -1514,7 +1492,10 @@ int gemv_k256c_mode(int flags, bool dependent) {
 hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
                              int flags, bool dependent, uint32_t* sync, hipStream_t st) {
   int visit = 0, grid = 0, first_wg[kMaxGroup], rpws[kMaxGroup];
-  {
+  int r_tasks_of[kMaxGroup];
+  const bool rows = gemv_k256c_rows(descs, n, flags, dependent) &&
+                    gemv_k256c_rows_plan(descs, n, flags, dependent, 0, nullptr, &grid, first_wg, r_tasks_of, rpws, nullptr) == hipSuccess;
+  if (!rows) {
     const hipError_t e = c_plan(descs, n, dependent, c_workgroups(dependent), &visit, &grid, first_wg, rpws);
     if (e != hipSuccess) return e;
   }
@@ -1542,8 +1523,9 @@ hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* cons
     Ly.wgs = first_wg[i];
     Ly.rpw = rpws[i];
     P.head[i][0] = (uint32_t)Ly.wgs | ((uint32_t)Ly.rpw << 16);
-    P.head[i][1] = (uint32_t)ng | ((uint32_t)ns << 24);
+    P.head[i][1] = rows ? (uint32_t)r_tasks_of[i] : (uint32_t)ng | ((uint32_t)ns << 24);
   }
+  if (rows) return launch_gemv_k256c_rows(P, grid, st);
   const bool f16 = descs[0].dtype == VPTQ_DTYPE_F16;
   const int mode = gemv_k256c_mode(flags, dependent);
   if (mode < 0) return hipErrorInvalidValue;   // (the caller routes those layer by layer / asks for EXACT)

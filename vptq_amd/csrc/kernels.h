@@ -63,6 +63,12 @@ int gemv_k256c_sweeps(const VptqLayerDesc& d);
 // how that launch deals its row groups (vptq_quant_gemv_chain_plan); workgroups = 0: what a launch uses
 hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
                            int* first_wg, int* rows_per_wg);
+// the launch's second geometry, "rows per wave" (gemv_k256c_rows_kernel, gemv_k256r.hip): does a launch of these layers take it
+// (the rule: gemv_k256c.hip, next to gemv_k256c_fills_device), and how it would deal its workgroup-tasks
+// (vptq_quant_gemv_chain_rows_plan; hipErrorInvalidValue: the geometry does not serve this launch).  Any out pointer may be null.
+bool gemv_k256c_rows(const VptqLayerDesc* descs, int n, int flags, bool dependent);
+hipError_t gemv_k256c_rows_plan(const VptqLayerDesc* descs, int n, int flags, bool dependent, int workgroups, int* taken,
+                                int* grid, int* first_wg, int* tasks, int* steps, int* longest);
 
 // gemv_gather.hip — v=8, k=65536 (+ residual 0 / 256 / 65536), C=1, no outliers:
 // centroid rows gathered from L2.
