@@ -1171,15 +1171,18 @@ def test_csrc_states_its_shared_idioms_once():
     assert holders("__builtin_amdgcn_mfma_f32_16x16x32_f16") == ["common.h"]
 
 
-# the three kernel files that are compiled in parts, and the only host functions of the shared headers each may define: the
-# dispatchers that pick one of its instantiations (declared in sliced.h / k256.h, called from sliced_host.hip / k256m_host.hip)
-_PART_COMPILED_DISPATCHERS = {
+# the three kernel files that are compiled in parts and the two of the chain family (heavy kernels, one unit each), and the only host
+# functions of the shared headers each may define: the dispatchers that pick one of its instantiations (declared in sliced.h / k256.h /
+# k256c.h, called from sliced_host.hip / k256m_host.hip / k256c_host.hip)
+_KERNEL_FILE_DISPATCHERS = {
     "gemv_sliced.hip": {"launch_sl_one", "launch_sl_tokens", "launch_sl_tokens_wpt"},
     "gemv_sliced_tok.hip": {"launch_st_tok24", "launch_st_tok8", "launch_st_ex4", "launch_st_ex8"},
     "gemv_k256m.hip": {"k256m_f16_fast", "k256m_f16_exact", "k256m_bf16", "k256m_f16_tokens", "k256m_bf16_tokens", "k256m_bf16_exact",
                        "k256m_f16_tokens_exact", "k256m_bf16_tokens_exact"},
+    "gemv_k256c.hip": {"k256c_chain", "k256c_hot", "k256c_permute_x"},
+    "gemv_k256r.hip": {"launch_gemv_k256c_rows"},
 }
-_HOST_UNITS = ("sliced_host.hip", "k256m_host.hip")
+_HOST_UNITS = ("sliced_host.hip", "k256m_host.hip", "k256c_host.hip")
 
 
 def _toplevel_functions(text, defined_only):
@@ -1194,27 +1197,33 @@ def _toplevel_functions(text, defined_only):
 
 
 def test_part_compiled_kernel_files_hold_no_host_policy():
-    """gemv_sliced.hip, gemv_sliced_tok.hip and gemv_k256m.hip - compiled 3 / 4 / 6 times - read no tuning knob and define none of the
-    functions kernels.h / sliced.h / k256.h declare except their instantiation dispatchers; the rules live in the host units, which hold
-    no device code"""
+    """gemv_sliced.hip, gemv_sliced_tok.hip and gemv_k256m.hip - compiled 3 / 4 / 6 times - and the chain family's gemv_k256c.hip and
+    gemv_k256r.hip read no tuning knob and define none of the functions kernels.h / sliced.h / k256.h / k256c.h declare except their
+    instantiation dispatchers; the rules live in the host units, which hold no device code"""
     csrc = os.path.join(ROOT, "vptq_amd", "csrc")
     read = lambda f: open(os.path.join(csrc, f)).read()
-    declared = set().union(*(_toplevel_functions(read(h), False) for h in ("kernels.h", "sliced.h", "k256.h")))
+    declared = set().union(*(_toplevel_functions(read(h), False) for h in ("kernels.h", "sliced.h", "k256.h", "k256c.h")))
     # (the reader finds what it is there to find: rules of each family, and every dispatcher)
     assert {"gemv_sliced_eligible", "sl_layout_set", "sl_check_layouts", "gemv_sliced_tok_groupable", "launch_gemv_sliced_tok_group",
-            "gemv_k256m_decide", "launch_gemv_k256m", "gemv_k256m_supported"} <= declared
-    assert set().union(*_PART_COMPILED_DISPATCHERS.values()) <= declared
-    for f, dispatchers in _PART_COMPILED_DISPATCHERS.items():
+            "gemv_k256m_decide", "launch_gemv_k256m", "gemv_k256m_supported", "gemv_k256c_rows_plan", "launch_gemv_k256c"} <= declared
+    assert set().union(*_KERNEL_FILE_DISPATCHERS.values()) <= declared
+    for f, dispatchers in _KERNEL_FILE_DISPATCHERS.items():
         text = read(f)
         assert not re.search(r"\btune_(env|int|flag)\s*\(", text), f
         assert _toplevel_functions(text, True) & declared == dispatchers, (f, sorted(_toplevel_functions(text, True) & declared))
+    assert all(not re.search(r"__global__|__device__", read(f)) for f in _HOST_UNITS)
     host = "".join(read(f) for f in _HOST_UNITS)
-    assert not re.search(r"__global__|__device__", host)
     moved = declared & _toplevel_functions(host, True)
     assert {"gemv_sliced_eligible", "gemv_sliced_slices", "gemv_sliced_whole_table", "sl_piece_set", "sl_part_desc", "sl_layout_set", "sl_check_layouts",
             "sl_parts_share", "gemv_sliced_instance", "gemv_sliced_tok_eligible", "gemv_sliced_tok_groupable", "gemv_sliced_tok_instance",
             "launch_gemv_sliced_group", "launch_gemv_sliced", "launch_gemv_sliced_tok_group", "launch_gemv_sliced_tok", "gemv_k256m_supported",
-            "gemv_k256m_row_groups", "gemv_k256m_launch_units", "gemv_k256m_selective_ok", "gemv_k256m_decide", "launch_gemv_k256m"} <= moved
+            "gemv_k256m_row_groups", "gemv_k256m_launch_units", "gemv_k256m_selective_ok", "gemv_k256m_decide", "launch_gemv_k256m",
+            "gemv_k256c_eligible", "gemv_k256c_sweeps", "gemv_k256c_fills_device", "gemv_k256c_exact_ok", "gemv_k256c_selective_ok",
+            "gemv_k256c_selective_bytes", "gemv_k256c_perm_bytes", "gemv_k256c_mode", "gemv_k256c_plan", "gemv_k256c_rows_plan",
+            "gemv_k256c_rows", "launch_gemv_k256c", "launch_permute_x"} <= moved
+    # ... and the chain family's static helpers with them
+    assert {"c_plan", "c_groups", "c_rows_per_wg", "c_blocks", "c_workgroups", "c_visit", "r_tasks", "r_steps", "r_servable", "r_longest",
+            "c_longest"} <= _toplevel_functions(read("k256c_host.hip"), True)
     mk = read("Makefile")
     assert all(re.search(r"^SRCS\s*:=.*\b%s\b" % re.escape(f), mk, re.M) for f in _HOST_UNITS)
 

@@ -773,7 +773,7 @@ int vptq_quant_gemv_chain(const VptqLayerDesc* descs, int n, const void* const* 
                                                            : (prof_ws ? (uint32_t*)workspace : nullptr), st);
     if (thr_ws) thr_ws += vptq::gemv_k256c_selective_bytes(descs + i0, m);
     if (dependent && e == hipErrorCooperativeLaunchTooLarge) {
-      // the runtime does not confirm that every workgroup of the dependent chain is resident at once (gemv_k256c.hip:launch_c):
+      // the runtime does not confirm that every workgroup of the dependent chain is resident at once (gemv_k256c.hip:launch_c, behind k256c_chain):
       // one launch per layer, stream order is the dependency - slower, never wrong (layers already walked are walked again)
       (void)hipGetLastError();
       const int pflags = lflags & ~VPTQ_GEMV_FORCE_MFMA;

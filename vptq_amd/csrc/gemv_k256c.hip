@@ -45,102 +45,22 @@
 //    11.5 us per 8192^2 layer - the hand-over through memory costs ~6 us per layer, more than the
 //    kernel boundary it replaces (7.3 us with one launch per layer): exists for completeness.
 #include <type_traits>
-#include <vector>
 
 #include "common.h"
 #include "kernels.h"
 #include "k256.h"
 #include "k256c.h"
 
+// (The build's knobs and geometry constants and the phases gemv_k256r.hip runs as well: k256c.h.  Which launches come here, how
+// they deal their row groups and the fill of the kernel arguments: k256c_host.hip, which reaches this file through the three
+// dispatchers k256c_chain, k256c_hot and k256c_permute_x.)
 namespace vptq {
 
-// profiling build (tools/chain_prof.py): every wave adds up the shader-clock cycles it spends
-// waiting for its index words, consuming a sweep, requesting the next one and in the rare paths,
-// and stores them at P.sync[(workgroup * waves + wave) * kCProfWords ...] (non-dependent launches); 2: + a timeline
-#ifndef VPTQ_K256C_PROF
-#define VPTQ_K256C_PROF 0
-#endif
-// waves per workgroup (= per CU): 16 (4 per SIMD, 128 registers each) or 8 (2 per SIMD, 256 registers: room for 4 row
-// subgroups per sweep and a deeper gather lookahead; a step then covers twice the indices per wave)
-#ifndef VPTQ_K256C_WAVES
-#define VPTQ_K256C_WAVES 16
-#endif
-constexpr int kCWaves = VPTQ_K256C_WAVES;
-constexpr int kCThreads = 64 * kCWaves;
-static_assert(kCWaves == 16 || kCWaves == 8, "waves per workgroup");
-constexpr int kCBlockCols = 128;                     // columns of one wave per sweep
-// The waves of a workgroup as kCSplit row parts x kCColWaves column blocks: a sweep covers kCColWaves x 128 columns
-// of kCSplit x 8 vector-rows.  2 parts: a row group of an 8192-column layer is 8 sweeps instead of 4, so the sums
-// at the end of a row group (cross-lane reduction, deposit, hand-over: ~1500 clocks per wave) come half as often;
-// the sum over the waves is over 8 instead of 16 partial sums.
-#ifndef VPTQ_K256C_SPLIT
-#define VPTQ_K256C_SPLIT 1
-#endif
-constexpr int kCSplit = VPTQ_K256C_SPLIT;
-static_assert(kCSplit == 1 || kCSplit == 2 || kCSplit == 4, "row parts");
-constexpr int kCColWaves = kCWaves / kCSplit;
-static_assert(kCColWaves >= 4, "the sum over the waves is a tree of groups of 4");
-constexpr int kCSweepCols = kCColWaves * kCBlockCols;   // 2048
-#ifndef VPTQ_K256C_SUB
-#define VPTQ_K256C_SUB 2
-#endif
-constexpr int kCSub = VPTQ_K256C_SUB;                // row subgroups (4 vector-rows each) per row group
-constexpr int kCRowsW = 4 * kCSub;                   // vector-rows of one wave
-constexpr int kCOutW = 8 * kCRowsW;                  // outputs of one wave
-constexpr int kCRows = kCRowsW * kCSplit;            // vector-rows per row group
-constexpr int kCOut = 8 * kCRows;                    // outputs per row group
-static_assert(kCSub == 1 || kCSub == 2 || kCSub == 4, "row subgroups per sweep");
-static_assert(kCSub != 1 || (kCWaves == 16 && kCSplit == 1), "1 subgroup: the 16-wave sum");
-// gathers requested ahead of the arithmetic, in units (one index of one subgroup)
-#ifndef VPTQ_K256C_AHEAD
-#define VPTQ_K256C_AHEAD 2
-#endif
-// sweeps in flight per wave: bandwidth x latency is ~48 KiB per CU
-#ifndef VPTQ_K256C_DEPTH
-#define VPTQ_K256C_DEPTH 3
-#endif
-constexpr int kCDepth = VPTQ_K256C_DEPTH;
-static_assert(kCDepth >= 2 && kCDepth <= 6, "queue depth");
-constexpr int kCSlots = 4;                           // cross-wave partial-sum slots
-constexpr uint32_t kCXsOff = 2 * kCImgBytes;         // wave-private activation slots
-// arithmetic of a launch: folded (sum (c + r) f16(s x) + sum b x), the reference's roundings per weight, or SELECTIVE:
-// the folded form, with the reference's roundings wherever an activation column dominates (kCModeSel below)
-constexpr int kCModeFolded = 0, kCModeExact = 1, kCModeSel = 2;
-// folded form (and selective): 256 bytes per wave (f16(s x) of its 128 columns); reference roundings: x, scale, bias side by side
-constexpr uint32_t c_xs_wave(int mode) { return mode == kCModeExact ? 768u : 256u; }
-constexpr uint32_t c_red_off(int mode) { return kCXsOff + kCWaves * c_xs_wave(mode); }
-constexpr uint32_t c_redb_off(int mode) { return c_red_off(mode) + kCSlots * kCWaves * kCOutW * 4; }
-constexpr uint32_t c_cnt_off(int mode) { return c_redb_off(mode) + kCSlots * kCWaves * 4; }
-// profiling build 2: consume start / end stamps of kCTlSteps steps per wave (a timeline of who computes when)
-[[maybe_unused]] constexpr int kCTlFirst = 16, kCTlSteps = 32;
-constexpr uint32_t c_tl_off(int mode) { return c_cnt_off(mode) + 64; }
-constexpr uint32_t c_lds_bytes(int mode) {
-#if VPTQ_K256C_PROF >= 2
-  return c_tl_off(mode) + kCWaves * kCTlSteps * 8;
-#else
-  return c_cnt_off(mode) + 64;
-#endif
-}
-[[maybe_unused]] constexpr int kCProfWords = 64;   // 8-byte words of profile output per wave
-static_assert(c_lds_bytes(kCModeFolded) <= 163840 && (VPTQ_K256C_PROF >= 2 || c_lds_bytes(kCModeExact) <= 163840), "LDS");
-constexpr int kCFlagStride = 256;   // DEP: arrival flags per layer (one per workgroup)
-
-// timing-only ablations (results wrong): bit 0 no MFMAs, bit 1 no gathers, bit 2 no x / scale /
-// bias loads, bit 3 no waits for the image hand-over between the waves, bit 4 no index loads
-#ifndef VPTQ_K256C_ABLATE
-#define VPTQ_K256C_ABLATE 0
-#endif
-// bring-up builds: give up a wait after that many polls, so that a protocol error shows as wrong
-// results instead of a hung GPU
-#ifndef VPTQ_K256C_SPIN_LIMIT
-#define VPTQ_K256C_SPIN_LIMIT 0
-#endif
 // Issue priorities: everything outside the consume phase runs at priority 3 - those instructions compete with the
 // other waves' MFMAs for the issue port and hold nothing another wave needs (measured: 4.91 -> 4.67 us) - and the
 // consume phase at 0 / 1 / 2 by arrival order at the previous row group (finish()).
 // (s_setprio 0-3 by arrival order for the whole wave: chain32 4.83 -> 4.90 us; no balancing: 5.00 us;
 // profiles/r03/chain_bench_variants.txt "prio0" / "nobal")
-
 
 // position in the workgroup's flat stream; everything is wave-uniform
 struct CCursor {
@@ -150,18 +70,6 @@ struct CCursor {
   int ns;   // sweeps per row group of layer L
   int ng;   // row groups of layer L
 };
-
-// f(slot 0), f(slot 1), ... f(slot kCDepth - 1) with the slot as a compile-time constant.  (Not common.h's for_slots<kCDepth>: its
-// halving recursion leaves the compiler another order of a few scalar instructions in this kernel - profiles/r18/README.md.)
-template <typename F>
-static __device__ __forceinline__ void c_for_slots(F&& f) {
-  f(std::integral_constant<int, 0>{});
-  f(std::integral_constant<int, 1>{});
-  if constexpr (kCDepth > 2) f(std::integral_constant<int, (kCDepth > 2 ? 2 : 0)>{});
-  if constexpr (kCDepth > 3) f(std::integral_constant<int, (kCDepth > 3 ? 3 : 0)>{});
-  if constexpr (kCDepth > 4) f(std::integral_constant<int, (kCDepth > 4 ? 4 : 0)>{});
-  if constexpr (kCDepth > 5) f(std::integral_constant<int, (kCDepth > 5 ? 5 : 0)>{});
-}
 
 // EXACT: every weight rebuilt with the reference CPU path's three roundings r16(r16(r16(c + r) s) + b)
 // (vptq/ops/quant_gemm.py:143-158; bit-identical to vptq_dequant), fp32 accumulation of x w by the same MFMAs
@@ -211,23 +119,9 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // ---- lane = (column chunk blk = lane >> 2, vector-row j = lane & 3).  The two gathers of an index
-  // are split across the lanes: in gather A the lanes with bit 3 clear fetch the main entry (unit
-  // lane & 7 of image row e), the others the residual entry (unit 8 + (lane & 7)); gather B is the
-  // complement: every 16-lane group of a ds_read_b128 touches 16 different units (gemv_k256m.hip).
-  // address = {0, base.byte2 = image buffer, index byte, base.byte0}; dword q of the index words holds
-  // columns 2q (bytes 0 = main, 1 = residual index) and 2q + 1 (bytes 2, 3)
-  const uint32_t jrow = (uint32_t)lane & 3u;
-  const uint32_t hi8 = ((uint32_t)lane >> 3) & 1u;
-  uint32_t baseA = ((hi8 << 3) | ((uint32_t)lane & 7u)) << 4;
-  uint32_t baseB = (((hi8 ^ 1u) << 3) | ((uint32_t)lane & 7u)) << 4;
-  const uint32_t selGA[2] = {0x0c020400u | (hi8 << 8), 0x0c020600u | (hi8 << 8)};
-  const uint32_t selGB[2] = {0x0c020400u | ((hi8 ^ 1u) << 8), 0x0c020600u | ((hi8 ^ 1u) << 8)};
-  // x operand of the 4x4x4 MFMA: x' * e_j as two packed pairs, cut out of a packed x' register
-  const uint32_t selA[2] = {jrow == 0 ? 0x0c0c0504u : jrow == 1 ? 0x05040c0cu : 0x0c0c0c0cu,
-                            jrow == 0 ? 0x0c0c0706u : jrow == 1 ? 0x07060c0cu : 0x0c0c0c0cu};
-  const uint32_t selB[2] = {jrow == 2 ? 0x0c0c0504u : jrow == 3 ? 0x05040c0cu : 0x0c0c0c0cu,
-                            jrow == 2 ? 0x0c0c0706u : jrow == 3 ? 0x07060c0cu : 0x0c0c0c0cu};
+  // ---- lane = (column chunk lane >> 2, vector-row jrow = lane & 3): gather address bases and selectors, x-operand selectors
+  uint32_t jrow, baseA, baseB, selGA[2], selGB[2], selA[2], selB[2];
+  c_lane_constants(lane, jrow, baseA, baseB, selGA, selGB, selA, selB);
 
   // ---- LDS map: [0, 64 Ki) image buffer 0 | [64 Ki, 128 Ki) image buffer 1 | per wave 256 B of
   // staged activations | partial-sum slots | counters | layer table
@@ -382,51 +276,16 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
   if (tid < 16) slot_cnt[tid] = 0u;
   __syncthreads();   // the only barrier: counters zeroed before anybody uses them
 
-  // ---- image fill by LDS-DMA: wave w brings rows 16 w .. 16 w + 15 (4 instructions of 4 rows; 8 waves: 32 rows, 8;
-  // lane l = unit l & 15 of row l >> 4: 16 bytes of entry (row) of table (unit >> 3)).  Invisible
-  // loads can only make the compiler's counted waits stricter, never looser (vmcnt retires in order).
-  auto fill_image = [&](const CFillL& F, uint32_t buf) __attribute__((always_inline)) {
-    const uint32_t unit = (uint32_t)lane & 15u, r4 = (uint32_t)lane >> 4;
-    // (table choice by arithmetic: as a per-lane select of two pointers the compiler built a two-entry
-    // array in scratch memory and indexed it - a scratch load, waited for with vmcnt(0))
-    const uint64_t tc = (uint64_t)(uintptr_t)F.cent, tr = (uint64_t)(uintptr_t)F.rcent;
-    const uint64_t pick = (unit >> 3) ? ~0ull : 0ull;
-    constexpr uint32_t kRowsW = 256u / (uint32_t)kCWaves;   // image rows per wave
-    const uint64_t va = tc + ((tr - tc) & pick) + (uint64_t)(((uint32_t)wave * kRowsW + r4) * 16u);
-    const uint32_t dst = buf * kCImgBytes + (uint32_t)wave * kRowsW * 256u;
-#pragma unroll
-    for (int i = 0; i < (int)(kRowsW / 4u); ++i) {
-      const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dst + (uint32_t)i * 1024u));
-      const uint64_t v = va + (uint64_t)(i * 64);
-      lds_dma16(d, v);
-    }
-  };
-  // Hand-over between the waves goes through LDS only, and a wave's LDS operations execute in
-  // order: fences restricted to the local address space.  An ordinary workgroup-scope release also
-  // waits for every global load in flight (s_waitcnt vmcnt(0)) - here the whole queue of index
-  // words requested ahead.
-  // (the release as a compiler barrier only - the LDS executes one wave's operations in the order they were issued,
-  // so the counter update cannot overtake the writes - saved nothing: profiles/r03/chain_rowsplit_ldsfence_ab.txt)
-  auto lds_release = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); };
-  auto lds_acquire = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); };
-  auto lds_inc = [&](uint32_t* p) __attribute__((always_inline)) {
-    lds_release();
-    if (lane == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
+  // hand-over between the waves: LDS counters, fences restricted to the local address space (k256c.h has the account; the image
+  // fill c_fill_image and the counted wait c_wait_all_but are there too)
+  CLdsRelease lds_release;
+  CLdsAcquire lds_acquire;
+  CLdsInc lds_inc{lds_release, lane};
   auto lds_wait_ge = [&](uint32_t* p, uint32_t need) __attribute__((always_inline)) {
     if constexpr ((VPTQ_K256C_ABLATE & 8) != 0) { if (p >= free_cnt && p < free_cnt + 4) return; }
-#if VPTQ_K256C_SPIN_LIMIT
-    for (int it = 0; it < VPTQ_K256C_SPIN_LIMIT; ++it) {
-      if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= need) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-#else
-    while (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need)
-      __builtin_amdgcn_s_sleep(1);
-#endif
+    c_lds_spin_ge(p, need);
     lds_acquire();
   };
-
 
   // ---- loads of one sweep
   u32x4 iw[D][kCSub];
@@ -489,21 +348,6 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
   constexpr int kCLand = 2;
   static_assert(kCLand <= D, "the fill is older than the sweeps of one queue");
   int land_steps = 0;          // > 0: a fill was requested kCLand - land_steps step ends ago
-  // "everything but the youngest n sweeps' loads has landed".  vmcnt retires in order: at the end
-  // of the j-th step after a fill the fill is older than j + 1 sweeps; at j = kCLand - 1 those are
-  // the kCLand youngest of the D sweeps in flight.
-  auto wait_all_but = [&](int steps) __attribute__((always_inline)) {
-    switch (steps) {
-      case 1: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 1) : "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 2) : "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 3) : "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 4) : "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 5) : "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kLPS * 6) : "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-  };
-  static_assert(kLPS * kCDepth <= 63, "vmcnt is a 6-bit counter");
   CCursor cf = cc;             // next layer with work (its image goes to buffer (use + 1) & 1)
   auto plan_fill = [&]() __attribute__((always_inline)) {
     cf = cc;
@@ -718,17 +562,7 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
                   kNB = kPairAhead ? 4 : kAhead + 1;
     u32x4 cv[kNB], rv[kNB];
     auto gather = [&](int t) {   // unit t = column t / kCSub of subgroup t % kCSub
-      const int u = t / kCSub, q = t % kCSub;
-      const uint32_t w = iw[S][q][u >> 1];
-      const uint32_t aC = __builtin_amdgcn_perm(w, baseA, selGA[u & 1]);
-      const uint32_t aR = __builtin_amdgcn_perm(w, baseB, selGB[u & 1]);
-      if constexpr ((VPTQ_K256C_ABLATE & 2) != 0) {
-        asm volatile("" :: "v"(aC), "v"(aR));
-        cv[t % kNB] = iw[S][q]; rv[t % kNB] = iw[S][q];
-      } else {
-        cv[t % kNB] = lds_load16(aC);
-        rv[t % kNB] = lds_load16(aR);
-      }
+      c_gather_index(iw[S][t % kCSub], t / kCSub, baseA, baseB, selGA, selGB, cv[t % kNB], rv[t % kNB]);
     };
 #pragma unroll
     for (int t = 0; t < kAhead; ++t) gather(t);
@@ -781,19 +615,7 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
         // operations back to back cost wait states); the scale / bias half of the column is picked by op_sel
         if ((q & 1) == 0) {   // (row subgroups q, q + 1)
           const u32x4 c1 = cv[(t + 1) % kNB], r1 = rv[(t + 1) % kNB];
-          uint32_t w[8];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) { w[k] = DT::add2(c[k], r[k]); w[4 + k] = DT::add2(c1[k], r1[k]); }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) w[k] = DT::mul2_bcast(w[k], sq[u >> 1], u & 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) w[k] = DT::add2_bcast(w[k], bq[u >> 1], u & 1);
-          acc[q][0] = DT::mfma4(xo, u32x2{w[0], w[1]}, acc[q][0]);
-          acc[q][1] = DT::mfma4(xo, u32x2{w[2], w[3]}, acc[q][1]);
-          acc[q + 1][0] = DT::mfma4(xo, u32x2{w[4], w[5]}, acc[q + 1][0]);
-          acc[q + 1][1] = DT::mfma4(xo, u32x2{w[6], w[7]}, acc[q + 1][1]);
+          c_round_pair<DT>(c, r, c1, r1, sq[u >> 1], bq[u >> 1], u & 1, xo, acc[q], acc[q + 1]);
         }
       } else if constexpr ((VPTQ_K256C_ABLATE & 1) != 0) {
         asm volatile("" :: "v"(c), "v"(r), "v"(xo));
@@ -845,23 +667,18 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
       constexpr int S = decltype(slot_c)::value;
       if (q_layer[S] == L) load_x(slot_c, xp, max2, q_col2[S]);
     };
-    reload(std::integral_constant<int, 0>{});
-    reload(std::integral_constant<int, 1>{});
-    if constexpr (D > 2) reload(std::integral_constant<int, (D > 2 ? 2 : 0)>{});
-    if constexpr (D > 3) reload(std::integral_constant<int, (D > 3 ? 3 : 0)>{});
-    if constexpr (D > 4) reload(std::integral_constant<int, (D > 4 ? 4 : 0)>{});
-    if constexpr (D > 5) reload(std::integral_constant<int, (D > 5 ? 5 : 0)>{});
+    c_for_slots(reload);
   };
 
   // ---- prologue: image of the first layer into buffer 0, first D sweeps requested
   PF_PRO(2);
-  fill_image(Lf, 0u);
+  c_fill_image<kCWaves>(Lf, 0u, lane, wave);
   c_for_slots([&](auto slot_c) {
     issue(slot_c);
     __builtin_amdgcn_sched_barrier(0);   // (the slots in issue order: the counted waits of the loop rely on it)
   });
   PF_PRO(3);
-  wait_all_but(D);   // the 4 fill instructions are older than the loads above
+  c_wait_all_but<kLPS>(D);   // the 4 fill instructions are older than the loads above
   PF_PRO(4);
   lds_inc(&ready_cnt[0]);
   plan_fill();
@@ -881,14 +698,14 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
     const uint32_t need = (uint32_t)kCWaves * ((use + 1u) >> 1);
     if (peeked(2 * kCSlots + nb) >= need) {
       lds_acquire();
-      fill_image(Lf, nb);
+      c_fill_image<kCWaves>(Lf, nb, lane, wave);
       fill_pending = false;
       land_steps = kCLand;
     }
   };
   auto fill_events_after_issue = [&]() __attribute__((always_inline)) {
     if (--land_steps == 0) {
-      wait_all_but(kCLand);
+      c_wait_all_but<kLPS>(kCLand);
       lds_inc(&ready_cnt[(use + 1u) & 1u]);
     }
   };
@@ -915,13 +732,13 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
     const uint32_t nb = (use + 1u) & 1u;
     if (fill_pending) {   // (rare: the buffer was not free at any step boundary)
       lds_wait_ge(&free_cnt[nb], (uint32_t)kCWaves * ((use + 1u) >> 1));
-      fill_image(Lf, nb);
+      c_fill_image<kCWaves>(Lf, nb, lane, wave);
       fill_pending = false;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       lds_inc(&ready_cnt[nb]);
     } else if (land_steps > 0) {
       // requested kCLand - land_steps step ends ago: that many sweeps are younger than the fill
-      wait_all_but(kCLand - land_steps);
+      c_wait_all_but<kLPS>(kCLand - land_steps);
       lds_inc(&ready_cnt[nb]);
       land_steps = 0;
     }
@@ -1037,15 +854,7 @@ __global__ __launch_bounds__(kCThreads) void gemv_k256c_kernel(const K256CParams
 // vector-rows as the reference rounds them - w = f16(f16(f16(c + r) s) + b), vptq/ops/quant_gemm.py:121,155-156 - and stores
 // sum w x (fp32) of those columns as the rows' corrections.  kappa: VPTQ_SELECTIVE_KAPPA; the study behind the 6:
 // tools/hybrid_error_study.py, profiles/r06/selective_*.txt.
-constexpr int kHotRows = 64;          // vector-rows per workgroup: 4 rounds of 16 (16 lanes per row, 8 columns per lane and hot block);
-                                      // every workgroup repeats the threshold / hot-block search (64 KiB out of the L2): 16 rows per
-                                      // workgroup made that search 10 us per launch of 32 layers (rocprofv3, round 6), 64: a quarter
-constexpr int kHotMaxBlocks = 256;    // 32768 columns
 constexpr int kHotMaxHot = 16;        // hot blocks per layer the corrections cover (the most dominant ones)
-struct CHotArgs {
-  uint32_t corr_off[kMaxGroup];   // byte offset of layer l's corrections from P.sync
-  float kappa;
-};
 template <typename DT>
 __global__ __launch_bounds__(256) void k256c_hot_kernel(const K256CParams P, const CHotArgs H) {
   __shared__ float part[4];
@@ -1205,156 +1014,17 @@ __global__ __launch_bounds__(256) void k256c_hot_kernel(const K256CParams P, con
   }
   }   // round
 }
-// bytes of a SEL launch's workspace: 16 per layer, then 4 per output
-size_t gemv_k256c_selective_bytes(const VptqLayerDesc* descs, int n) {
-  size_t b = ((size_t)n * 16 + 255) / 256 * 256;
-  for (int i = 0; i < n; ++i) b += ((size_t)descs[i].num_indices * 8 * 4 + 255) / 256 * 256;
-  return b;
-}
-
-// ---- host side -------------------------------------------------------------------
-bool gemv_k256c_eligible(const VptqLayerDesc& d, int tokens) {
-  return tokens == 1 && d.perm == nullptr && gemv_k256_eligible(d, 1) &&
-         (((uintptr_t)d.centroids | (uintptr_t)d.res_centroids) & 15) == 0 &&
-         d.num_indices <= 0xffffff && d.group_size <= 0xff * kCSweepCols;   // (the search header's fields)
-}
-
-// Row groups are dealt to the workgroups in blocks of consecutive ones, `rpw` per workgroup and
-// layer.  Independent layers: at least kCMinSteps sweeps per visit of a layer (the next layer's
-// image is requested at the start of the visit and lands kCLand sweeps later; a layer that gives every
-// workgroup one short row group would make all of them wait for it), so a small layer occupies
-// only some of the workgroups and the next layers run beside it.  Dependent layers follow each
-// other anyway: every layer is spread over all workgroups.
-// Longer visits, up to kCMaxSteps sweeps, while the blocks still give every workgroup two: every visit ends in a layer
-// switch - the layer's last sums stored at once, its image buffer handed over, and the fast waves waiting at the next
-// layer for the slowest one's part of its image (tools/chain_prof.py --exact: ~22 % of the wave time at 8 sweeps per
-// visit).  Ring of 32 8192^2 layers, reference roundings: 8 -> 16 -> 32 sweeps per visit 6.2 -> 5.8 -> 5.7 us per layer.
-#ifndef VPTQ_K256C_MIN_STEPS
-#define VPTQ_K256C_MIN_STEPS 8
+hipError_t k256c_hot(const K256CParams& P, const CHotArgs& H, bool f16, int chunks, hipStream_t st) {
+#if VPTQ_K256C_PROF == 0
+  if (f16) hipLaunchKernelGGL(k256c_hot_kernel<F16>, dim3(chunks, P.n_layers), dim3(256), 0, st, P, H);
+  else hipLaunchKernelGGL(k256c_hot_kernel<BF16>, dim3(chunks, P.n_layers), dim3(256), 0, st, P, H);
+  return hipGetLastError();
+#else
+  return hipErrorInvalidValue;
 #endif
-constexpr int kCMinSteps = VPTQ_K256C_MIN_STEPS;
-constexpr int kCMaxSteps = 4 * kCMinSteps;
-static int c_groups(const VptqLayerDesc& d) { return (d.num_indices + kCRows - 1) / kCRows; }
-// sweeps of 2048 columns of one layer: the header field every wave's column loop runs to
-int gemv_k256c_sweeps(const VptqLayerDesc& d) { return (d.group_size + kCSweepCols - 1) / kCSweepCols; }
-// visit = sweeps per visit a block is sized for (0: the layer's row groups spread over all workgroups)
-static int c_rows_per_wg(const VptqLayerDesc& d, int cus, int visit) {
-  const int ng = c_groups(d), ns = gemv_k256c_sweeps(d);
-  int rpw = (ng + cus - 1) / cus;
-  if (visit > 0) {
-    const int want = (visit + ns - 1) / ns;
-    rpw = want > rpw ? want : rpw;
-  }
-  return rpw < 1 ? 1 : rpw;
-}
-static long long c_blocks(const VptqLayerDesc* descs, int n, int cus, int visit) {
-  long long total = 0;
-  for (int i = 0; i < n; ++i) {
-    const int rpw = c_rows_per_wg(descs[i], cus, visit);
-    total += (c_groups(descs[i]) + rpw - 1) / rpw;
-  }
-  return total;
 }
 
-// workgroups > 0: that many (a plan query); 0: what a launch uses
-static int c_workgroups(bool dependent, int workgroups = 0) {
-  static const int fw = tune_int("VPTQ_K256C_WGS", 0);  // tuning override of the workgroup count
-  const int cus = workgroups > 0 ? workgroups : fw > 0 ? fw : device_cus();
-  return dependent && cus > kCFlagStride ? kCFlagStride : cus;
-}
-
-// wide blocks: the longest visit of kCMaxSteps, kCMaxSteps / 2, ... kCMinSteps sweeps whose blocks still give every
-// workgroup twice its share; 0 below that, and for a dependent chain
-static int c_visit(const VptqLayerDesc* descs, int n, int cus, bool dependent) {
-  if (dependent) return 0;
-  for (int v = kCMaxSteps; v >= kCMinSteps; v /= 2)
-    if (c_blocks(descs, n, cus, v) >= 2ll * cus) return v;
-  return 0;
-}
-// does one launch of these layers fill the device (>= 3/4 of the workgroups busy)?
-bool gemv_k256c_fills_device(const VptqLayerDesc* descs, int n, bool dependent) {
-  const int cus = c_workgroups(dependent);
-  return 4 * c_blocks(descs, n, cus, c_visit(descs, n, cus, dependent)) >= 3ll * cus;
-}
-
-// ---- the second geometry of the launch, "rows per wave" (gemv_k256r.hip): a wave owns a row group across the
-// layer's whole width, so no sum crosses the waves.  A workgroup-task = kRTaskGroups consecutive row groups of one layer (one
-// per wave; the last task of a layer may leave waves idle), r_steps(layer) steps of 128 columns long; the tasks are dealt
-// round-robin over ALL `cus` workgroups, the layers continuing each other's round robin as above.
-static int r_tasks(const VptqLayerDesc& d) { return (c_groups(d) + kRTaskGroups - 1) / kRTaskGroups; }
-static int r_steps(const VptqLayerDesc& d) { return (d.group_size + kRStepCols - 1) / kRStepCols; }
-// fp16, the reference's roundings, independent layers, 16-bit outputs (and the build's geometry constants the kernel restates)
-static bool r_servable(const VptqLayerDesc* descs, int n, int flags, bool dependent) {
-  if (VPTQ_K256C_PROF != 0 || kCWaves != kRTaskGroups || kCRows != 8 || kCBlockCols != kRStepCols) return false;
-  if (n < 1 || n > kMaxGroup || dependent || (flags & VPTQ_GEMV_OUT_F32) || gemv_k256c_mode(flags, dependent) != kCModeExact) return false;
-  for (int i = 0; i < n; ++i)
-    if (descs[i].dtype != VPTQ_DTYPE_F16 || r_steps(descs[i]) > 0xffff) return false;
-  return true;
-}
-// steps of the busiest workgroup: a step is 128 columns x 8 vector-rows per wave in both geometries
-static long long r_longest(const VptqLayerDesc* descs, int n, int cus, int* first_wg, long long* total_out) {
-  std::vector<long long> steps((size_t)cus, 0);
-  long long first = 0;
-  for (int i = 0; i < n; ++i) {
-    if (first_wg) first_wg[i] = (int)(first % cus);
-    const int nt = r_tasks(descs[i]);
-    for (int k = 0; k < nt; ++k) steps[(size_t)((first + k) % cus)] += r_steps(descs[i]);
-    first += nt;
-  }
-  *total_out = first;
-  long long m = 0;
-  for (long long s : steps) m = s > m ? s : m;
-  return m;
-}
-static hipError_t c_plan(const VptqLayerDesc* descs, int n, bool dependent, int cus, int* visit_out, int* grid_out,
-                         int* first_wg, int* rows_per_wg);
-static long long c_longest(const VptqLayerDesc* descs, int n, int cus, bool dependent) {
-  int visit = 0, grid = 0, first_wg[kMaxGroup], rpws[kMaxGroup];
-  if (c_plan(descs, n, dependent, cus, &visit, &grid, first_wg, rpws) != hipSuccess || grid < 1) return -1;
-  std::vector<long long> steps((size_t)grid, 0);
-  for (int i = 0; i < n; ++i) {
-    const int ng = c_groups(descs[i]), ns = gemv_k256c_sweeps(descs[i]);
-    for (int k = 0; k * rpws[i] < ng; ++k) {
-      const int rows = (k + 1) * rpws[i] <= ng ? rpws[i] : ng - k * rpws[i];
-      steps[(size_t)((first_wg[i] + k) % grid)] += (long long)rows * ns;
-    }
-  }
-  long long m = 0;
-  for (long long s : steps) m = s > m ? s : m;
-  return m;
-}
-// THE RULE.  The rows geometry takes a launch it can serve when (a) there are at least as many workgroup-tasks as workgroups -
-// the launch fills the device in this geometry - and (b) its busiest workgroup walks no more steps than the busiest one of the
-// schedule above would for the same launch; both counts from the plans.  VPTQ_K256C_ROWS (VPTQ_TUNING=1): 0 never, 1 whenever
-// servable; VPTQ_K256C_WGS is honoured through c_workgroups.
-hipError_t gemv_k256c_rows_plan(const VptqLayerDesc* descs, int n, int flags, bool dependent, int workgroups, int* taken,
-                                int* grid, int* first_wg, int* tasks, int* steps, int* longest) {
-  if (!r_servable(descs, n, flags, dependent)) return hipErrorInvalidValue;
-  const int cus = c_workgroups(dependent, workgroups);
-  if (cus < 1 || cus > 0xffff) return hipErrorInvalidValue;
-  long long total = 0;
-  const long long lr = r_longest(descs, n, cus, first_wg, &total), lc = c_longest(descs, n, cus, dependent);
-  if (lc < 0 || lr > 0x7fffffff || lc > 0x7fffffff) return hipErrorInvalidValue;
-  for (int i = 0; i < n; ++i) {
-    if (tasks) tasks[i] = r_tasks(descs[i]);
-    if (steps) steps[i] = r_steps(descs[i]);
-  }
-  if (taken) *taken = (total >= cus && lr <= lc) ? 1 : 0;
-  if (grid) *grid = cus;
-  if (longest) { longest[0] = (int)lr; longest[1] = (int)lc; }
-  return hipSuccess;
-}
-// What a LAUNCH does: the rule above (headline ring, python bench.py, same box in turns: 2825 -> 2876 GB/s, + 1.8 %, the first
-// geometry's own spread 0.1 %; kernel mean 190.1 -> 186.9 us per 32 layers; profiles/r28/README.md).
-// VPTQ_K256C_ROWS (VPTQ_TUNING=1): 0 = never, 1 = whenever the geometry serves the launch, 2 / unset = the rule.
-bool gemv_k256c_rows(const VptqLayerDesc* descs, int n, int flags, bool dependent) {
-  static const int knob = tune_int("VPTQ_K256C_ROWS", 2);
-  if (knob != 1 && knob != 2) return false;
-  int rule = 0;
-  if (gemv_k256c_rows_plan(descs, n, flags, dependent, 0, &rule, nullptr, nullptr, nullptr, nullptr, nullptr) != hipSuccess) return false;
-  return knob == 1 || rule != 0;
-}
-
+// ---- the dispatchers (k256c.h): filled arguments in, one instantiation launched ----
 template <typename DT, bool DEP, int MODE = kCModeFolded>
 static hipError_t launch_c(const K256CParams& P, int grid, hipStream_t st) {
   constexpr auto kern = gemv_k256c_kernel<DT, DEP, MODE>;
@@ -1379,29 +1049,23 @@ static hipError_t launch_c(const K256CParams& P, int grid, hipStream_t st) {
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kCThreads), lds, st, P);
   return hipGetLastError();
 }
-
-// the reference's roundings inside the chain launch: fp16, independent layers
-bool gemv_k256c_exact_ok(const VptqLayerDesc& d, bool dependent) {
-  (void)d;   // (bf16 since the end of round 6: its roundings on the matrix pipe)
-  return !dependent && VPTQ_K256C_PROF < 2;
-}
-// ... and where an activation column dominates only (VPTQ_GEMV_SELECTIVE): the same, + workspace (gemv_k256c_selective_bytes)
-bool gemv_k256c_selective_ok(const VptqLayerDesc& d, bool dependent) {
-  return !dependent && VPTQ_K256C_PROF == 0 && d.group_size <= kHotMaxBlocks * kCBlockCols;   // (fp16 and bf16: the corrections are VALU arithmetic)
+// the instantiation gemv_k256c_kernel<DT, DEP, MODE> of (f16, dependent, mode); hipErrorInvalidValue: the build has none
+hipError_t k256c_chain(const K256CParams& P, bool f16, bool dependent, int mode, int grid, hipStream_t st) {
+#if VPTQ_K256C_PROF == 0
+  if (mode == kCModeSel && !dependent) return f16 ? launch_c<F16, false, kCModeSel>(P, grid, st) : launch_c<BF16, false, kCModeSel>(P, grid, st);
+#endif
+#if VPTQ_K256C_PROF < 2
+  if (mode == kCModeExact && !dependent) return f16 ? launch_c<F16, false, kCModeExact>(P, grid, st) : launch_c<BF16, false, kCModeExact>(P, grid, st);
+#endif
+  if (mode != kCModeFolded) return hipErrorInvalidValue;
+  if (dependent) return f16 ? launch_c<F16, true>(P, grid, st) : launch_c<BF16, true>(P, grid, st);
+  return f16 ? launch_c<F16, false>(P, grid, st) : launch_c<BF16, false>(P, grid, st);
 }
 
 // ---- layers with an input permutation: x is gathered ONCE into the caller's workspace (xp[c] = x[perm[c]]) by a small
 // launch in front of the chain launch, which then runs on (xp, scale_permuted, bias_permuted) without a permutation: the
 // chain kernel's LDS is full (two 64 KiB codebook images), and a gather inside its load queue would put a dependent load -
 // perm, then x - in front of every sweep.  (The reference applies `perm` inline, csrc/kernels/quant_gemv.cuh:53-54.)
-struct PermXParams {
-  int n;
-  int start[kMaxGroup + 1];          // first workgroup of layer l
-  const uint16_t* x[kMaxGroup];
-  const uint16_t* perm[kMaxGroup];
-  uint16_t* out[kMaxGroup];
-  int I[kMaxGroup];
-};
 __global__ __launch_bounds__(256) void permute_x_kernel(const PermXParams P) {
   int l = 0;
   for (int i = 1; i < P.n; ++i)
@@ -1429,138 +1093,9 @@ __global__ __launch_bounds__(256) void permute_x_kernel(const PermXParams P) {
     r[q] = (uint32_t)as_global(x)[pv[q] & 0xffffu] | ((uint32_t)as_global(x)[pv[q] >> 16] << 16);
   *(u32x4*)(as_global(out) + c0) = r;
 }
-size_t gemv_k256c_perm_bytes(const VptqLayerDesc& d) { return d.perm ? ((size_t)d.in_features * 2 + 255) / 256 * 256 : 0; }
-hipError_t launch_permute_x(const VptqLayerDesc* descs, int n, const void* const* x, void* const* out, hipStream_t st) {
-  PermXParams P = {};
-  int blocks = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!descs[i].perm) continue;
-    if (P.n == kMaxGroup) return hipErrorInvalidValue;
-    P.start[P.n] = blocks;
-    P.x[P.n] = (const uint16_t*)x[i];
-    P.perm[P.n] = (const uint16_t*)descs[i].perm;
-    P.out[P.n] = (uint16_t*)out[i];
-    P.I[P.n] = descs[i].in_features;
-    blocks += (descs[i].in_features / 8 + 255) / 256;
-    ++P.n;
-  }
-  if (P.n == 0) return hipSuccess;
-  for (int i = P.n; i <= kMaxGroup; ++i) P.start[i] = blocks;
+hipError_t k256c_permute_x(const PermXParams& P, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(permute_x_kernel, dim3(blocks), dim3(256), 0, st, P);
   return hipGetLastError();
-}
-
-// How one launch deals its row groups: the grid, the visit length, and per layer the workgroup that owns block 0 and
-// the row groups per block (block k of layer i goes to workgroup (first[i] + k) mod grid).  The launch and the plan
-// query (gemv_k256c_plan) take their numbers from here.
-static hipError_t c_plan(const VptqLayerDesc* descs, int n, bool dependent, int cus, int* visit_out, int* grid_out,
-                         int* first_wg, int* rows_per_wg) {
-  if (n < 1 || n > kMaxGroup || cus < 1) return hipErrorInvalidValue;
-  const int visit = c_visit(descs, n, cus, dependent);
-  const long long total = c_blocks(descs, n, cus, visit);
-  const int grid = (int)(total < cus ? total : cus);
-  if (grid > 0xffff) return hipErrorInvalidValue;
-  long long first = 0;   // running total of blocks: the layers continue each other's round robin
-  for (int i = 0; i < n; ++i) {
-    const int rpw = c_rows_per_wg(descs[i], cus, visit);
-    const int ng = c_groups(descs[i]), ns = gemv_k256c_sweeps(descs[i]);
-    if (rpw > 0xffff || ng > 0xffffff || ns > 0xff) return hipErrorInvalidValue;
-    first_wg[i] = (int)(first % grid);
-    rows_per_wg[i] = rpw;
-    // dependent chain: every layer starts at workgroup 0 (all of its row groups wait anyway)
-    first = dependent ? 0 : first + (ng + rpw - 1) / rpw;
-  }
-  *visit_out = visit;
-  *grid_out = grid;
-  return hipSuccess;
-}
-hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
-                           int* first_wg, int* rows_per_wg) {
-  return c_plan(descs, n, dependent, c_workgroups(dependent, workgroups), visit, grid, first_wg, rows_per_wg);
-}
-
-// MODE of the instantiation gemv_k256c_kernel<DT, DEP, MODE> a launch with these flags takes: 0 folded, 1 the reference's
-// roundings, 2 selective; -1: none (the caller routes such a list elsewhere)
-int gemv_k256c_mode(int flags, bool dependent) {
-  if ((flags & VPTQ_GEMV_SELECTIVE) && !(flags & VPTQ_GEMV_EXACT)) return !dependent && VPTQ_K256C_PROF == 0 ? kCModeSel : -1;
-  if (flags & VPTQ_GEMV_EXACT) return !dependent && VPTQ_K256C_PROF < 2 ? kCModeExact : -1;
-  return kCModeFolded;
-}
-
-// n <= kMaxGroup layers, all gemv_k256c_eligible and of one dtype; sync = kCFlagStride flags per
-// layer (zeroed by the caller's memset node) when dependent
-hipError_t launch_gemv_k256c(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y,
-                             int flags, bool dependent, uint32_t* sync, hipStream_t st) {
-  int visit = 0, grid = 0, first_wg[kMaxGroup], rpws[kMaxGroup];
-  int r_tasks_of[kMaxGroup];
-  const bool rows = gemv_k256c_rows(descs, n, flags, dependent) &&
-                    gemv_k256c_rows_plan(descs, n, flags, dependent, 0, nullptr, &grid, first_wg, r_tasks_of, rpws, nullptr) == hipSuccess;
-  if (!rows) {
-    const hipError_t e = c_plan(descs, n, dependent, c_workgroups(dependent), &visit, &grid, first_wg, rpws);
-    if (e != hipSuccess) return e;
-  }
-  K256CParams P;
-  P.n_layers = n;
-  P.tokens = 1 | ((flags & VPTQ_GEMV_OUT_F32) ? kOutF32Bit : 0);
-  P.sync = sync;
-  for (int i = 0; i < kMaxGroup + kCHeadPad; ++i) P.head[i][0] = P.head[i][1] = 0u;
-  for (int i = 0; i < n; ++i) {
-    const VptqLayerDesc& d = descs[i];
-    CLayerArgs& Ly = P.layer[i];
-    Ly.idx = (const uint32_t*)d.indices;
-    Ly.cent = (const uint32_t*)d.centroids;
-    Ly.rcent = (const uint32_t*)d.res_centroids;
-    Ly.x = (const uint16_t*)x[i];
-    Ly.y = (uint16_t*)y[i];
-    Ly.scale = (const uint16_t*)d.weight_scale;
-    Ly.wbias = (const uint16_t*)d.weight_bias;
-    Ly.bias = (const uint16_t*)d.bias;
-    Ly.N = d.num_indices;
-    Ly.G = d.group_size;
-    Ly.O = d.out_features;
-    Ly.row_words = d.row_words;
-    const int ng = c_groups(d), ns = gemv_k256c_sweeps(d);
-    Ly.wgs = first_wg[i];
-    Ly.rpw = rpws[i];
-    P.head[i][0] = (uint32_t)Ly.wgs | ((uint32_t)Ly.rpw << 16);
-    P.head[i][1] = rows ? (uint32_t)r_tasks_of[i] : (uint32_t)ng | ((uint32_t)ns << 24);
-  }
-  if (rows) return launch_gemv_k256c_rows(P, grid, st);
-  const bool f16 = descs[0].dtype == VPTQ_DTYPE_F16;
-  const int mode = gemv_k256c_mode(flags, dependent);
-  if (mode < 0) return hipErrorInvalidValue;   // (the caller routes those layer by layer / asks for EXACT)
-  if (mode == kCModeSel) {
-    // sync = n thresholds, written by the launch in front of the chain launch (same stream)
-    if (!sync) return hipErrorInvalidValue;
-#if VPTQ_K256C_PROF == 0
-    CHotArgs H = {};
-    size_t off = ((size_t)n * 16 + 255) / 256 * 256;
-    int max_rows = 1;
-    for (int i = 0; i < n; ++i) {
-      if (descs[i].group_size > kHotMaxBlocks * kCBlockCols || off > 0xffffffffull) return hipErrorInvalidValue;
-      H.corr_off[i] = (uint32_t)off;
-      off += ((size_t)descs[i].num_indices * 8 * 4 + 255) / 256 * 256;
-      max_rows = descs[i].num_indices > max_rows ? descs[i].num_indices : max_rows;
-    }
-    H.kappa = selective_kappa();
-    if (f16) hipLaunchKernelGGL(k256c_hot_kernel<F16>, dim3((max_rows + kHotRows - 1) / kHotRows, n), dim3(256), 0, st, P, H);
-    else hipLaunchKernelGGL(k256c_hot_kernel<BF16>, dim3((max_rows + kHotRows - 1) / kHotRows, n), dim3(256), 0, st, P, H);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return f16 ? launch_c<F16, false, kCModeSel>(P, grid, st) : launch_c<BF16, false, kCModeSel>(P, grid, st);
-#else
-    return hipErrorInvalidValue;
-#endif
-  }
-  if (mode == kCModeExact) {
-#if VPTQ_K256C_PROF < 2
-    return f16 ? launch_c<F16, false, kCModeExact>(P, grid, st) : launch_c<BF16, false, kCModeExact>(P, grid, st);
-#else
-    return hipErrorInvalidValue;
-#endif
-  }
-  if (dependent) return f16 ? launch_c<F16, true>(P, grid, st) : launch_c<BF16, true>(P, grid, st);
-  return f16 ? launch_c<F16, false>(P, grid, st) : launch_c<BF16, false>(P, grid, st);
 }
 
 }  // namespace vptq

@@ -32,21 +32,10 @@
 
 namespace vptq {
 
-#ifndef VPTQ_K256C_DEPTH
-#define VPTQ_K256C_DEPTH 3
-#endif
-// timing-only ablations (results wrong), the bits of gemv_k256c.hip's knob that apply here: bit 0 no roundings / MFMAs, bit 1 no gathers
-#ifndef VPTQ_K256C_ABLATE
-#define VPTQ_K256C_ABLATE 0
-#endif
-// bring-up builds: give up a wait after that many polls, so that a protocol error shows as wrong results instead of a hung GPU
-#ifndef VPTQ_K256C_SPIN_LIMIT
-#define VPTQ_K256C_SPIN_LIMIT 0
-#endif
+// (the queue depth, the ablation mask - bit 0 no roundings / MFMAs and bit 1 no gathers apply here - and the spin limit of bring-up
+// builds are k256c.h's: one knob each for both geometries)
 constexpr int kRWaves = kRTaskGroups;               // one row group per wave
 constexpr int kRThreads = 64 * kRWaves;
-constexpr int kRDepth = VPTQ_K256C_DEPTH;            // steps in flight per wave
-static_assert(kRDepth >= 2 && kRDepth <= 6, "queue depth");
 constexpr int kRSub = 2;                             // row subgroups (4 vector-rows each) per row group
 constexpr int kRRows = 4 * kRSub;                    // vector-rows per row group
 constexpr uint32_t kRXsOff = 2 * kCImgBytes;         // wave-private x / scale / bias of a step's 128 columns
@@ -55,17 +44,6 @@ constexpr uint32_t kRCntOff = kRXsOff + kRWaves * kRXsWave;   // free_cnt[2], re
 constexpr uint32_t kRLdsBytes = kRCntOff + 64;
 static_assert(kRLdsBytes <= 163840, "LDS");
 constexpr int kRLPS = 3 + kRSub;                     // vector loads per step
-static_assert(kRLPS * kRDepth <= 63, "vmcnt is a 6-bit counter");
-
-template <typename F>
-static __device__ __forceinline__ void r_for_slots(F&& f) {
-  f(std::integral_constant<int, 0>{});
-  f(std::integral_constant<int, 1>{});
-  if constexpr (kRDepth > 2) f(std::integral_constant<int, (kRDepth > 2 ? 2 : 0)>{});
-  if constexpr (kRDepth > 3) f(std::integral_constant<int, (kRDepth > 3 ? 3 : 0)>{});
-  if constexpr (kRDepth > 4) f(std::integral_constant<int, (kRDepth > 4 ? 4 : 0)>{});
-  if constexpr (kRDepth > 5) f(std::integral_constant<int, (kRDepth > 5 ? 5 : 0)>{});
-}
 
 // position in the workgroup's flat stream of tasks; everything is wave-uniform
 struct RCursor {
@@ -82,23 +60,15 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
     typedef __attribute__((address_space(3))) unsigned char lds_u8_t;
     if ((uint32_t)(uintptr_t)(lds_u8_t*)smem != 0u) __builtin_trap();  // absolute LDS addressing
   }
-  constexpr int D = kRDepth;
+  constexpr int D = kCDepth;   // steps in flight per wave
   const int n_layers = P.n_layers;
   const int W = (int)gridDim.x, bid = (int)blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // ---- lane = (column chunk blk = lane >> 2, vector-row j = lane & 3); gather addresses and x operand as in gemv_k256c.hip
-  const uint32_t jrow = (uint32_t)lane & 3u;
-  const uint32_t hi8 = ((uint32_t)lane >> 3) & 1u;
-  uint32_t baseA = ((hi8 << 3) | ((uint32_t)lane & 7u)) << 4;
-  uint32_t baseB = (((hi8 ^ 1u) << 3) | ((uint32_t)lane & 7u)) << 4;
-  const uint32_t selGA[2] = {0x0c020400u | (hi8 << 8), 0x0c020600u | (hi8 << 8)};
-  const uint32_t selGB[2] = {0x0c020400u | ((hi8 ^ 1u) << 8), 0x0c020600u | ((hi8 ^ 1u) << 8)};
-  const uint32_t selA[2] = {jrow == 0 ? 0x0c0c0504u : jrow == 1 ? 0x05040c0cu : 0x0c0c0c0cu,
-                            jrow == 0 ? 0x0c0c0706u : jrow == 1 ? 0x07060c0cu : 0x0c0c0c0cu};
-  const uint32_t selB[2] = {jrow == 2 ? 0x0c0c0504u : jrow == 3 ? 0x05040c0cu : 0x0c0c0c0cu,
-                            jrow == 2 ? 0x0c0c0706u : jrow == 3 ? 0x07060c0cu : 0x0c0c0c0cu};
+  // ---- lane = (column chunk lane >> 2, vector-row jrow = lane & 3): gather address bases and selectors, x-operand selectors
+  uint32_t jrow, baseA, baseB, selGA[2], selGB[2], selA[2], selB[2];
+  c_lane_constants(lane, jrow, baseA, baseB, selGA, selGB, selA, selB);
 
   // ---- LDS map: [0, 64 Ki) image buffer 0 | [64 Ki, 128 Ki) image buffer 1 | per wave 768 B of staged x, scale, bias | counters
   const uint32_t xs_base = kRXsOff + (uint32_t)wave * kRXsWave;
@@ -191,40 +161,13 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
   if (tid < 4) free_cnt[tid] = 0u;
   __syncthreads();   // the only barrier: counters zeroed before anybody uses them
 
-  // ---- image fill by LDS-DMA: wave w brings rows 16 w .. 16 w + 15 (4 instructions of 4 rows; lane l = unit l & 15 of row
-  // l >> 4: 16 bytes of entry (row) of table (unit >> 3))
-  auto fill_image = [&](const CFillL& F, uint32_t buf) __attribute__((always_inline)) {
-    const uint32_t unit = (uint32_t)lane & 15u, r4 = (uint32_t)lane >> 4;
-    const uint64_t tc = (uint64_t)(uintptr_t)F.cent, tr = (uint64_t)(uintptr_t)F.rcent;
-    const uint64_t pick = (unit >> 3) ? ~0ull : 0ull;
-    constexpr uint32_t kRowsW = 256u / (uint32_t)kRWaves;   // image rows per wave
-    const uint64_t va = tc + ((tr - tc) & pick) + (uint64_t)(((uint32_t)wave * kRowsW + r4) * 16u);
-    const uint32_t dst = buf * kCImgBytes + (uint32_t)wave * kRowsW * 256u;
-#pragma unroll
-    for (int i = 0; i < (int)(kRowsW / 4u); ++i) {
-      const uint32_t d = (uint32_t)__builtin_amdgcn_readfirstlane((int)(dst + (uint32_t)i * 1024u));
-      const uint64_t v = va + (uint64_t)(i * 64);
-      lds_dma16(d, v);
-    }
-  };
-  // hand-over between the waves goes through LDS only: fences restricted to the local address space (an ordinary
-  // workgroup-scope release also waits for every global load in flight - here the whole queue)
-  auto lds_release = [&]() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); };
-  auto lds_acquire = [&]() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); };
-  auto lds_inc = [&](uint32_t* p) __attribute__((always_inline)) {
-    lds_release();
-    if (lane == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  };
+  // hand-over between the waves: LDS counters, fences restricted to the local address space (k256c.h has the account; the image
+  // fill c_fill_image and the counted wait c_wait_all_but are there too)
+  CLdsRelease lds_release;
+  CLdsAcquire lds_acquire;
+  CLdsInc lds_inc{lds_release, lane};
   auto lds_wait_ge = [&](uint32_t* p, uint32_t need) __attribute__((always_inline)) {
-#if VPTQ_K256C_SPIN_LIMIT
-    for (int it = 0; it < VPTQ_K256C_SPIN_LIMIT; ++it) {
-      if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= need) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-#else
-    while (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < need)
-      __builtin_amdgcn_s_sleep(1);
-#endif
+    c_lds_spin_ge(p, need);
     lds_acquire();
   };
 
@@ -264,17 +207,6 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
   constexpr int kRLand = 2;
   static_assert(kRLand <= D, "the fill is older than the steps of one queue");
   int land_steps = 0;          // > 0: a fill was requested kRLand - land_steps step ends ago
-  auto wait_all_but = [&](int steps) __attribute__((always_inline)) {
-    switch (steps) {
-      case 1: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRLPS * 1) : "memory"); break;
-      case 2: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRLPS * 2) : "memory"); break;
-      case 3: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRLPS * 3) : "memory"); break;
-      case 4: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRLPS * 4) : "memory"); break;
-      case 5: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRLPS * 5) : "memory"); break;
-      case 6: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kRLPS * 6) : "memory"); break;
-      default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-  };
   RCursor cf = cc;             // next layer with work (its image goes to buffer (use + 1) & 1)
   auto plan_fill = [&]() __attribute__((always_inline)) {
     cf = cc;
@@ -349,17 +281,7 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
     constexpr int kUnits = 8 * kRSub, kAhead = 2, kNB = 4;
     u32x4 cv[kNB], rv[kNB];
     auto gather = [&](int t) {   // unit t = column t / kRSub of subgroup t % kRSub
-      const int u = t / kRSub, q = t % kRSub;
-      const uint32_t w = iw[S][q][u >> 1];
-      const uint32_t aC = __builtin_amdgcn_perm(w, baseA, selGA[u & 1]);
-      const uint32_t aR = __builtin_amdgcn_perm(w, baseB, selGB[u & 1]);
-      if constexpr ((VPTQ_K256C_ABLATE & 2) != 0) {
-        asm volatile("" :: "v"(aC), "v"(aR));
-        cv[t % kNB] = iw[S][q]; rv[t % kNB] = iw[S][q];
-      } else {
-        cv[t % kNB] = lds_load16(aC);
-        rv[t % kNB] = lds_load16(aR);
-      }
+      c_gather_index(iw[S][t % kRSub], t / kRSub, baseA, baseB, selGA, selGB, cv[t % kNB], rv[t % kNB]);
     };
 #pragma unroll
     for (int t = 0; t < kAhead; ++t) gather(t);
@@ -379,31 +301,19 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
         if constexpr ((VPTQ_K256C_ABLATE & 1) != 0) {
           asm volatile("" :: "v"(c), "v"(r), "v"(c1), "v"(r1), "v"(xo), "v"(sq), "v"(bq));
         } else {
-          uint32_t w[8];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) { w[k] = DT::add2(c[k], r[k]); w[4 + k] = DT::add2(c1[k], r1[k]); }
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) w[k] = DT::mul2_bcast(w[k], sq[u >> 1], u & 1);
-          __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) w[k] = DT::add2_bcast(w[k], bq[u >> 1], u & 1);
-          acc[q][0] = DT::mfma4(xo, u32x2{w[0], w[1]}, acc[q][0]);
-          acc[q][1] = DT::mfma4(xo, u32x2{w[2], w[3]}, acc[q][1]);
-          acc[q + 1][0] = DT::mfma4(xo, u32x2{w[4], w[5]}, acc[q + 1][0]);
-          acc[q + 1][1] = DT::mfma4(xo, u32x2{w[6], w[7]}, acc[q + 1][1]);
+          c_round_pair<DT>(c, r, c1, r1, sq[u >> 1], bq[u >> 1], u & 1, xo, acc[q], acc[q + 1]);
         }
       }
     }
   };
 
   // ---- prologue: image of the first layer into buffer 0, first D steps requested
-  fill_image(Lf, 0u);
-  r_for_slots([&](auto slot_c) {
+  c_fill_image<kRWaves>(Lf, 0u, lane, wave);
+  c_for_slots([&](auto slot_c) {
     issue(slot_c);
     __builtin_amdgcn_sched_barrier(0);   // (the slots in issue order: the counted waits of the loop rely on it)
   });
-  wait_all_but(D);   // the 4 fill instructions are older than the loads above
+  c_wait_all_but<kRLPS>(D);   // the 4 fill instructions are older than the loads above
   lds_inc(&ready_cnt[0]);
   plan_fill();
   zero_acc();
@@ -417,14 +327,14 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
     const uint32_t need = (uint32_t)kRWaves * ((use + 1u) >> 1);
     if ((uint32_t)__builtin_amdgcn_readfirstlane((int)pre) >= need) {
       lds_acquire();
-      fill_image(Lf, nb);
+      c_fill_image<kRWaves>(Lf, nb, lane, wave);
       fill_pending = false;
       land_steps = kRLand;
     }
   };
   auto fill_events_after_issue = [&]() __attribute__((always_inline)) {
     if (--land_steps == 0) {
-      wait_all_but(kRLand);
+      c_wait_all_but<kRLPS>(kRLand);
       lds_inc(&ready_cnt[(use + 1u) & 1u]);
     }
   };
@@ -453,13 +363,13 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
     const uint32_t nb = (use + 1u) & 1u;
     if (fill_pending) {   // (rare: the buffer was not free at any step boundary)
       lds_wait_ge(&free_cnt[nb], (uint32_t)kRWaves * ((use + 1u) >> 1));
-      fill_image(Lf, nb);
+      c_fill_image<kRWaves>(Lf, nb, lane, wave);
       fill_pending = false;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       lds_inc(&ready_cnt[nb]);
     } else if (land_steps > 0) {
       // requested kRLand - land_steps step ends ago: that many steps are younger than the fill
-      wait_all_but(kRLand - land_steps);
+      c_wait_all_but<kRLPS>(kRLand - land_steps);
       lds_inc(&ready_cnt[nb]);
       land_steps = 0;
     }
@@ -495,7 +405,7 @@ __global__ __launch_bounds__(kRThreads) void gemv_k256c_rows_kernel(const K256CP
     if (--c_left == 0) task_done();
   };
   do {
-    r_for_slots(step);
+    c_for_slots(step);
   } while (!done);
 }
 

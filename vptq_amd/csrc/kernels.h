@@ -45,7 +45,8 @@ hipError_t launch_gemv_k256(const VptqLayerDesc* descs, int n, const void* const
 
 // gemv_k256c.hip - the same format, one token, no permutation: ONE persistent launch that walks a
 // chain of layers (next layer's codebook image, activations and index words requested while the current
-// one streams).  n <= 32 layers of one dtype per launch.
+// one streams).  n <= 32 layers of one dtype per launch.  The rules and launchers declared here are its host side's
+// (k256c_host.hip; the dispatchers into the kernel files, for that unit's own use, in k256c.h).
 bool gemv_k256c_eligible(const VptqLayerDesc& d, int tokens);
 bool gemv_k256c_fills_device(const VptqLayerDesc* descs, int n, bool dependent);
 bool gemv_k256c_exact_ok(const VptqLayerDesc& d, bool dependent);
@@ -64,7 +65,7 @@ int gemv_k256c_sweeps(const VptqLayerDesc& d);
 hipError_t gemv_k256c_plan(const VptqLayerDesc* descs, int n, bool dependent, int workgroups, int* visit, int* grid,
                            int* first_wg, int* rows_per_wg);
 // the launch's second geometry, "rows per wave" (gemv_k256c_rows_kernel, gemv_k256r.hip): does a launch of these layers take it
-// (the rule: gemv_k256c.hip, next to gemv_k256c_fills_device), and how it would deal its workgroup-tasks
+// (the rule: k256c_host.hip, gemv_k256c_rows_plan), and how it would deal its workgroup-tasks
 // (vptq_quant_gemv_chain_rows_plan; hipErrorInvalidValue: the geometry does not serve this launch).  Any out pointer may be null.
 bool gemv_k256c_rows(const VptqLayerDesc* descs, int n, int flags, bool dependent);
 hipError_t gemv_k256c_rows_plan(const VptqLayerDesc* descs, int n, int flags, bool dependent, int workgroups, int* taken,
