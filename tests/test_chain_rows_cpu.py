@@ -7,11 +7,16 @@ workgroup-task = 16 consecutive row groups of 8 vector-rows of one layer, ceil(G
 workgroups, the layers continuing each other's round robin.  Taken when the tasks number at least the workgroups AND the
 busiest workgroup walks no more steps than the busiest one of the first geometry's plan (vptq_quant_gemv_chain_plan) would.
 The rule is what the plan query answers and what a launch follows; the tuning knob VPTQ_K256C_ROWS overrides it (0: never, 1:
-wherever the geometry serves the launch)."""
+wherever the geometry serves the launch).
+
+The last section holds the schedule table of tests/test_chain_rows_gpu.py (tests/_chain_rows_run.py:TABLE) without a device: the
+deal its covers are computed from is the restatement's and the library's, every entry reaches the covers it names, a shortened
+chain loses them, and the rule takes the launch that test runs without a knob."""
 import ctypes as C
 
 import pytest
 
+import _chain_rows_run as run
 import _chain_schedule as cs
 from vptq_amd import _backend as B
 
@@ -228,3 +233,63 @@ def test_name_and_texts_of_the_launches_existing_tests_pin():
     assert instance(d, cs.MFMA | cs.EXACT) == "gemv_k256c dt=f16 dep=0 mode=exact layers=10 sweeps=1,2,4,4,5,6,7,1,3,1 perm=0,0,0,0,0,0,0,0,0,0"
     bits = cs.fake_descs([(4096, 72, {})] * 32)
     assert instance(bits, cs.MFMA | cs.EXACT).endswith("perm=" + perm)
+
+
+# ---------------------------------------------------------------------------------------------- the schedule table of the GPU test
+def _descs(shapes):
+    return cs.fake_descs([(I, O, dict(bias=b)) for I, O, b in shapes])
+
+
+@pytest.mark.parametrize("chain,w,covers", run.TABLE, ids=[f"{c}-wg{w}" for c, w, _ in run.TABLE])
+def test_table_entry_is_dealt_as_restated_and_covers_what_it_names(chain, w, covers):
+    """tests/test_chain_rows_gpu.py's table, no device: the deal the covers are computed from (tests/_chain_rows_run.py:deal) is
+    r_plan's and the library's at that workgroup count, and the entry reaches every cover it exists for"""
+    shapes = run.CHAINS[chain]
+    first, tasks, steps, per_wg = run.deal(shapes, w)
+    taken, f2, t2, s2, lr, lc = r_plan([(cdiv(O, 8), I) for I, O, _ in shapes], w)
+    assert (first, tasks, steps) == (f2, t2, s2)
+    assert max(sum(nt * ns for _, nt, ns in v) for v in per_wg) == lr
+    assert sorted((L, nt) for v in per_wg for L, nt, _ in v) == sorted(
+        (L, len(range(k, tasks[L], w))) for L in range(len(shapes)) for k in range(min(w, tasks[L])))   # every task dealt once
+    rc, got = lib_rows_plan(_descs(shapes), cs.EXACT | cs.MFMA, w)
+    assert rc == 0 and got == (taken, w, first, tasks, steps, lr, lc), got
+    f = run.facts(shapes, w)
+    for c in covers:
+        assert run.COVERS[c](f), f"{chain} at {w} workgroups does not cover {c}: {f}"
+
+
+def test_the_table_reaches_every_cover_and_notices_a_shortened_chain():
+    reached = {c for _, _, covers in run.TABLE for c in covers}
+    assert reached == set(run.COVERS), set(run.COVERS) ^ reached
+    at = lambda chain, w: {c for c, fn in run.COVERS.items() if fn(run.facts(run.CHAINS[chain], w))}   # noqa: E731
+    # the figures the chains were written for
+    assert "search2" in at("sparse32", 8) and {"search4", "late_start"} <= at("sparse32", 16)
+    assert all("tail" in at("sparse32", w) for w in (8, 16, 37)) and "ragged_n" in at("sparse30", 8) & at("sparse31", 8)
+    assert run.facts(run.CHAINS["sparse32"], 37)["idle"] == 5 and run.facts(run.CHAINS["sparse32"], 1)["entered"] == 32
+    assert run.facts(run.CHAINS["dense"], 1)["entered"] == 18 and run.facts(run.CHAINS["dense"], 1)["same3"] == 9
+    assert run.facts(run.CHAINS["dense"], 3)["same3"] == 3 and "visits" in at("dense", 2)
+    assert all("phases" in at("dense", w) for w in (1, 2, 3)) and "shapes" in at("dense", 1)
+    assert sum(run.tasks_of(O) for _, O, _ in run.CHAINS["dense"]) == 42 and len(run.CHAINS["sparse32"]) == 32
+    assert all(run.tasks_of(O) == 1 for _, O, _ in run.CHAINS["sparse32"])
+    # a chain cut short loses covers: without its last 4 layers sparse32 has no tail at any count, cut to 16 layers no workgroup of 16 has a second task
+    for w in (8, 16, 37):
+        assert not run.COVERS["tail"](run.facts(run.CHAINS["sparse32"][:28], w))
+    assert not run.COVERS["search4"](run.facts(run.CHAINS["sparse32"][:16], 16))
+    assert not run.COVERS["one_wg"](run.facts(run.CHAINS["dense"][:-1], 1))
+    # every pool layer stands in several launches (what the schedule-independence check compares) and alone in one
+    for c in run.POOL_ORDER:
+        assert sum(c in run.NAMED[chain] for chain, _, _ in run.TABLE if chain in run.NAMED) >= 2 and run.NAMED["one" + c] == [c]
+    assert max(I * O for I, O, _ in run.POOL.values()) < 16 << 20
+    assert set(run.WGS) == {1, 2, 3, 4, 8, 16, 37} and run.ONES_AT in run.WGS
+
+
+@pytest.mark.parametrize("cus", [64, 256, 304])
+def test_the_rule_takes_the_natural_launch(cus):
+    """the launch tests/test_chain_rows_gpu.py and tests/test_operand_placement_gpu.py run without a knob: the rule gives it to the
+    rows geometry at the workgroup counts of the devices the library knows"""
+    shapes = run.natural_shapes(cus)
+    assert len(shapes) == 32 and {I for I, _, _ in shapes} == {128, 136, 248, 264}
+    assert {O % 8 for _, O, _ in shapes} == {0, 4} and len({run.tasks_of(O) for _, O, _ in shapes}) == 2   # ragged last tasks
+    rc, got = lib_rows_plan(_descs(shapes), cs.EXACT, cus)
+    assert rc == 0 and got[0] == 1 and got[1] == cus and sum(got[3]) >= cus, got
+    assert got[:5] == (1, cus) + run.deal(shapes, cus)[:3]

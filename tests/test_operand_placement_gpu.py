@@ -30,6 +30,7 @@ import torch
 
 import _arena as ar
 import _arith_model as am
+import _chain_rows_run as rows
 import test_route_models_gpu as rm
 import test_route_models_k256_gpu as k256
 import test_route_models_other_gpu as other
@@ -734,6 +735,17 @@ for _dt in ("f16", "bf16"):
               instance=f"gemv_k256c dt={_dt} dep=1 mode=folded layers=10 ", chain_name_c="gemv_k256c_kernel",
               fallback=f"gemv_k256c dt={_dt} dep=1 mode=folded layers=10 "), f"chain-entry-min-dependent-y2-{_dt}")
 
+# ... and the launch the rule gives to the second geometry, "rows per wave" (gemv_k256r.hip): 32 narrow layers sized by the device's
+# compute units (tests/_chain_rows_run.py:natural_shapes; the device-less queries answer for 256), no knob.  The fp32 launch of the
+# same row is the first geometry's.  At the entry's minimum x sits at 2 bytes and the list goes to one grouped call of gemv_generic
+_ROWS_CUS = torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+_CHAIN_ROWS = tuple((I, O, 0, int(b)) for I, O, b in rows.natural_shapes(_ROWS_CUS))
+_row(dict(kind="chain", align="chain", shapes=_CHAIN_ROWS, dt="f16", tokens=1, flags=EXACT, arith="exact",
+          instance="gemv_k256c dt=f16 dep=0 mode=exact layers=32 ", instance_suffix=" geom=rows"), "chain-rows-natural-f16")
+_row(dict(kind="chain", align="chain", shapes=_CHAIN_ROWS, dt="f16", tokens=1, flags=EXACT, arith="exact", entry_min="generic",
+          instance="gemv_k256c dt=f16 dep=0 mode=exact layers=32 ", instance_suffix=" geom=rows", chain_name_c="grouped",
+          fallback="grouped: " + " | ".join(["gemv_generic dt=f16 v=8 tok=1"] * 32)), "chain-rows-natural-entry-min-f16")
+
 
 # the sliced entries: rows of the sliced census (1000-column layers, O = 72: ragged windows, short row blocks; 14080 / 16392-column
 # layers with O = 72 - 136 for window parts and column parts), every form and entry
@@ -817,6 +829,8 @@ def _expect_instance(e, got):
     want = e["instance"]
     if want == "gemm_gatherx want()":
         return got.startswith(f"gemm_gatherx dt={e['layer']().dtype} ") and f" tok={e['tokens']} " in got
+    if not got.endswith(e.get("instance_suffix", "")):
+        return False
     return got.startswith(want) if want.endswith(" ") else got == want
 
 
@@ -894,6 +908,8 @@ def test_the_table_reaches_every_entry_and_family():
     assert has(lambda e: e["kind"] == "grouped" and len(set(s[:3] for s in e["shapes"])) > 1)
     for frag in ("dep=0 mode=exact", "dep=0 mode=folded", "dep=0 mode=selective", "dep=1 mode=folded"):
         assert has(lambda e: e["kind"] == "chain" and frag in inst(e)), frag
+    assert has(lambda e: e["kind"] == "chain" and "dep=0 mode=exact" in inst(e) and e.get("instance_suffix") == " geom=rows" and not e.get("entry_min"))
+    assert has(lambda e: e["kind"] == "chain" and e.get("instance_suffix") == " geom=rows" and e.get("entry_min"))
     # sliced: folded, EX, EX+RG; column parts; one-pass window parts; the token kernel; gemv_hot; the four entries
     sl = [e for e in TABLE if e["kind"] == "sliced"]
     f = lambda e: dict(p.split("=") for p in inst(e).split(" | ")[-1].split()[1:])   # noqa: E731
