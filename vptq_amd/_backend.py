@@ -179,6 +179,13 @@ EXPORTS = {
     "vptq_quant_gemm_gather_px_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gather_px": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gather_px_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 16 tokens of 2 - 4 sibling layers of vptq_quant_gemm_gather in one launch, one x gather per distinct
+    # permutation (gemm_gather.hip's grouped kernel): query, workspace query, call (descs, n, x, y[], tokens, flags, workspace,
+    # workspace_bytes, stream), instance text
+    "vptq_quant_gemm_gather_grouped_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

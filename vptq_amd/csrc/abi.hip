@@ -1349,6 +1349,108 @@ int vptq_quant_gemm_gather_px_instance(const VptqLayerDesc* d, int tokens, int, 
   return instance_done(t);
 }
 
+// ---- gemm_gather.hip's grouped launch (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gather, 1 - 16 tokens, in ONE
+// launch of gemm_gather_grouped_kernel, behind one permute launch per DISTINCT perm pointer of the members.
+// What a grouped call IS, decided once for the workspace query, the launcher and the `_instance`: which xp block a member reads (-1:
+// the call's x), the members as the kernel takes them (without a permutation), the first member of every distinct permutation
+struct GroupedGatherPlan {
+  int n_perms;             // distinct non-NULL perm pointers
+  int slot[4];             // member -> xp block, -1 without a permutation
+  int owner[4];            // xp block -> the first member with that permutation
+  size_t block_bytes;      // one xp block (gemm_gather_px_workspace_bytes of any permuted member: the members share group_size)
+  VptqLayerDesc plain[4];
+};
+static GroupedGatherPlan grouped_gather_decide(const VptqLayerDesc* descs, int n, int tokens) {
+  GroupedGatherPlan G = {};
+  for (int m = 0; m < n; ++m) {
+    G.slot[m] = -1;
+    G.plain[m] = vptq::gemm_gather_px_plain(descs[m]);
+    if (!descs[m].perm) continue;
+    for (int j = 0; j < G.n_perms && G.slot[m] < 0; ++j)
+      if (descs[G.owner[j]].perm == descs[m].perm) G.slot[m] = j;
+    if (G.slot[m] < 0) { G.owner[G.n_perms] = m; G.slot[m] = G.n_perms++; }
+    G.block_bytes = vptq::gemm_gather_px_workspace_bytes(descs[m], tokens);
+  }
+  return G;
+}
+// the first reason the group is not served, or NULL: member and text for the message
+static const char* grouped_gather_refusal(const VptqLayerDesc* descs, int n, int tokens, int* member) {
+  *member = 0;
+  if (n < 2 || n > 4) return "a group has 2 - 4 members";
+  for (int m = 0; m < n; ++m) {
+    *member = m;
+    if (validate_layer(&descs[m]) != VPTQ_OK) return "not a valid layer";
+    if (!kGemmGather.eligible(descs[m], tokens)) return "not a layer vptq_quant_gemm_gather serves";
+    if (descs[m].dtype != descs[0].dtype) return "another dtype than member 0";
+    if (descs[m].group_size != descs[0].group_size) return "another group_size than member 0";
+    if (descs[m].num_res_centroids != descs[0].num_res_centroids) return "another residual codebook size than member 0";
+  }
+  return nullptr;
+}
+static int grouped_gather_validate(const VptqLayerDesc* descs, int n, int tokens) {
+  if (tokens < kGemmGather.tok_lo || tokens > kGemmGather.tok_hi)
+    return fail(VPTQ_E_TOKENS, "tokens %d outside [%d, %d]", tokens, kGemmGather.tok_lo, kGemmGather.tok_hi);
+  int member = 0;
+  if (const char* why = grouped_gather_refusal(descs, n, tokens, &member))
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gather_grouped (n = %d): member %d: %s", n, member, why);
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gather_grouped_supported(const VptqLayerDesc* descs, int n, int tokens) {
+  int member = 0;
+  return descs && tokens >= kGemmGather.tok_lo && tokens <= kGemmGather.tok_hi && !grouped_gather_refusal(descs, n, tokens, &member) ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gather_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens) {
+  if (!vptq_quant_gemm_gather_grouped_supported(descs, n, tokens)) return 0;
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  return G.block_bytes * (size_t)G.n_perms;
+}
+
+int vptq_quant_gemm_gather_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  if (!descs || !x || !y) return fail(VPTQ_E_NULL, "descs / x / y is NULL");
+  if (const int rc = grouped_gather_validate(descs, n, tokens)) return rc;
+  for (int m = 0; m < n; ++m)
+    if (!y[m]) return fail(VPTQ_E_NULL, "y[%d] is NULL", m);
+  if ((((uintptr_t)x) & 15) != 0) return fail(kGemmGather.misaligned, "gemm_gather_grouped: x must be 16-byte aligned");
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  const size_t need = G.block_bytes * (size_t)G.n_perms;
+  if (need > 0) {
+    if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gather_grouped: workspace of %zu bytes needed", need);
+    if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather_grouped: the workspace must be 16-byte aligned");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  for (int j = 0; j < G.n_perms; ++j) {   // one x gather per distinct permutation (block_bytes is a multiple of 256)
+    const hipError_t e = vptq::launch_permute_x_tokens(descs[G.owner[j]], x, (char*)workspace + (size_t)j * G.block_bytes, tokens, st);
+    if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  }
+  const void* xs[4] = {};
+  for (int m = 0; m < n; ++m) xs[m] = G.slot[m] < 0 ? x : (const char*)workspace + (size_t)G.slot[m] * G.block_bytes;
+  const hipError_t e = vptq::launch_gemm_gather_grouped(G.plain, n, xs, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather_grouped launch");
+}
+
+int vptq_quant_gemm_gather_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int, char* buf, size_t bytes) {
+  if (!descs || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = grouped_gather_validate(descs, n, tokens)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  if (G.n_perms > 0) {
+    const vptq::GemmGatherPxDecision D = vptq::gemm_gather_px_decide(descs[G.owner[0]], tokens);
+    t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d perms=%d | ", D.g, D.tok, D.grid_x, D.grid_y, D.tpt, G.n_perms);
+  } else {
+    t.add("none | ");
+  }
+  const vptq::GemmGatherGroupedDecision D = vptq::gemm_gather_grouped_decide(G.plain, n, tokens);
+  t.add("gemm_gather_grouped dt=%s t=%d tok=%d n=%d groups=", dt_text(D.f16), D.T, D.tok, D.n);
+  for (int m = 0; m < D.n; ++m) t.add(m ? "+%d" : "%d", D.groups[m]);
+  t.add(" tiles=%d grid=%d rgs=%d", D.tiles, D.grid, D.rgs);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {
   int rc = validate_layer(d);

@@ -215,6 +215,14 @@ bool gemm_gather_eligible(const VptqLayerDesc& d, int tokens);
 struct GemmGatherDecision { bool f16, perm; int T, tok, tiles, n_groups, grid, rgs; };
 GemmGatherDecision gemm_gather_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gather(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+// the same file: 2 - 4 sibling layers (one dtype, width and index width T) in ONE launch of gemm_gather_grouped_kernel<DT, T>, whose
+// workgroups walk the members' row groups as one list; plain form only - the caller hands a member with a permutation over as its
+// descriptor without one, with x[perm] for its x.  groups: row groups per member, first_group: their running sum; total, grid, rgs
+// over the whole list
+struct GemmGatherGroupedDecision { bool f16; int T, tok, n, tiles, total, grid, rgs, groups[4], first_group[5]; };
+GemmGatherGroupedDecision gemm_gather_grouped_decide(const VptqLayerDesc* descs, int n, int tokens);
+hipError_t launch_gemm_gather_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                      hipStream_t st);
 
 // gemm_gatherw.hip - gemm_gather's layers, 17 - 48 tokens in one launch as tb = 2 / 3 blocks of 16 tokens over gemm_gather's tile
 // pipeline (its K-step -> wave mapping and order of sums: a token's bits are the 16-token kernel's)

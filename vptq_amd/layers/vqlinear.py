@@ -39,6 +39,10 @@ from vptq_amd.batched_decode import (  # noqa: F401
     BATCHED_DECODE_MAX_TOKENS, BATCHED_DECODE_MIN_TOKENS, GEMM_GATHER_MAX_TOKENS, GEMM_GATHER_PX_MAX_TOKENS, GEMM_GATHER_PX_MIN_TOKENS,
     GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS, GEMM_K256W_MIN_TOKENS, batched_decode_routes,
     batched_decode_takes, gemm_gather_px_route, gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_k256w_route)
+# the batched-decode rule of a GROUP of siblings lives in vptq_amd/grouped_decode.py (its knob and cells are read there, at call time)
+from vptq_amd.grouped_decode import (  # noqa: F401
+    GEMM_GATHER_GROUPED_MAX_TOKENS as GROUPED_DECODE_MAX_TOKENS, GEMM_GATHER_GROUPED_MIN_TOKENS as GROUPED_DECODE_MIN_TOKENS,
+    gemm_gather_grouped_route, gemm_gather_grouped_tokens)
 # the sliced-layout rules (1 - 4 tokens) live in vptq_amd/sliced_routes.py and are read through the module (`R.exact_route_is_large`:
 # one monkeypatch changes every reader); only import-time constants that nothing assigns to are imported by name, for the hot guard
 from vptq_amd import sliced_routes as R
@@ -132,7 +136,8 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
     the library's builder, layer by layer) instead of inside the first decode step, and every layer has its one-token workspace for
     `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  The stream's `B.gemv_workspace` is grown to
     the largest x[perm] copy (`vptq_quant_gemm_gather_px_workspace_bytes` at 48 tokens) of the permuted layers `gemm_gather_px_route`
-    routes, so a 5 - 48 token step captured afterwards keeps that route.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
+    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` needs for the linked sibling groups `gemm_gather_grouped_route`
+    routes (at their largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
     "built": layers with a layout, "bytes", "seconds"}."""
     rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
     px = {}   # device index -> (device, most workspace bytes of its routed permuted layers)
@@ -150,6 +155,13 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
             px[cache.device_index] = (cache.device, max(need, px.get(cache.device_index, (None, 0))[1]))
     if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
         return rep
+    # ... and to the x[perm] copies of the sibling groups their batched-decode route takes, at the largest routed token count
+    groups = {id(g): g for g in (m.__dict__.get("_siblings") for m in model.modules() if isinstance(m, VQuantLinear)) if g is not None}
+    for g in groups.values():
+        if all(m._parameters["indices"].is_cuda for m in g.members if "_compact" not in m.__dict__):
+            need = g._batched_workspace_bytes()
+            if need is not None and need[2]:
+                px[need[1]] = (need[0], max(need[2], px.get(need[1], (None, 0))[1]))
     for dev_index, (dev, need) in px.items():
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -173,6 +185,9 @@ class SiblingGroup:
         self._version = -1
         self._out = {}
         self._arrays = None
+        self._bx = None       # forward_batched's leader tensor, its version and the followers' outputs
+        self._bversion = -1
+        self._bout = {}
 
     def forward_sliced(self, layer, x, tokens=1):
         """one token (2 - 4: `SlicedGroupGemv.forward_tokens`) of large-codebook siblings over their sliced layouts: ONE launch for the group
@@ -214,6 +229,108 @@ class SiblingGroup:
             return None
         self._sx, self._sversion, self._keep_sx = x, ver, x
         self._sout = {id(m): y for m, y in zip(self.members, ys) if m is not layer}
+        return ys[self.members.index(layer)]
+
+    def _batched_static(self):
+        """what the group's batched-decode route is asked with, from the members' static configuration: (vector length, main
+        centroids, residual centroids, output widths, input width, has_perm: True - every member has a permutation, False - none,
+        None - some), or None where the members do not share format and width or are not one-codebook layers with scale and bias"""
+        st = self.__dict__.get("_bstatic")
+        if st is None:
+            ms = self.members
+            fmt = {(m.vector_len, m.num_centroids, _res_centroids(m), m.in_features) for m in ms}
+            if len(fmt) != 1 or any(m.num_codebooks != 1 or m.enable_outlier or not m.enable_norm for m in ms):
+                st = (None,)
+            else:
+                perms = {bool(m.enable_perm) for m in ms}
+                v, k, kr, width = next(iter(fmt))
+                st = ((v, k, kr, tuple(m.out_features for m in ms), width, perms.pop() if len(perms) == 1 else None),)
+            self._bstatic = st
+        return st[0]
+
+    def _batched_plan(self):
+        """the descriptor array `vptq_quant_gemm_gather_grouped` is called with, (descs, caches), decided once per set of
+        descriptor generations - or None: a compacted member, a library without the entry, members on several devices or of
+        several dtypes, a group the library does not serve.  Members whose `perm` tensors are `torch.equal` get ONE perm pointer in
+        their descriptor copies (the first such member's): the entry then gathers x once for them.  Not decided inside a stream
+        capture (the comparison reads the device): the caller goes on alone and a later call asks again."""
+        caches = [m._descriptor() for m in self.members]
+        key = tuple(c.generation for c in caches)   # a rebuilt descriptor never matches
+        st = self.__dict__.get("_bplan")
+        if st is not None and st[0] == key:
+            return st[1]
+        plan = None
+        lib = B.lib()
+        if not any("_compact" in m.__dict__ for m in self.members) and getattr(lib, "vptq_quant_gemm_gather_grouped", None) is not None \
+                and len({(c.device, c.dtype) for c in caches}) == 1:
+            perms = [m._parameters.get("perm") if m.enable_perm else None for m in self.members]
+            if any(p is not None and p.is_cuda for p in perms) and torch.cuda.is_current_stream_capturing():
+                return None
+            n = len(caches)
+            descs = (B.LayerDesc * n)(*[B.LayerDesc.from_buffer_copy(c.desc) for c in caches])
+            first = []   # (perm tensor, perm pointer) of every distinct permutation so far
+            for i, p in enumerate(perms):
+                if p is None or not descs[i].perm:
+                    continue
+                for q, ptr in first:
+                    if p.shape == q.shape and torch.equal(p, q):
+                        descs[i].perm = ptr
+                        break
+                else:
+                    first.append((p, descs[i].perm))
+            if lib.vptq_quant_gemm_gather_grouped_supported(descs, n, GROUPED_DECODE_MIN_TOKENS):
+                plan = (descs, caches)   # (the caches keep what the descriptors point at alive)
+        self._bplan = (key, plan)
+        return plan
+
+    def _batched_workspace_bytes(self):
+        """(device, device index, bytes) of stream workspace the largest call the group's batched-decode route can take needs
+        (`prepare_model` grows the stream's buffer to it), or None: the group never takes that route"""
+        st = self._batched_static()
+        if st is None:
+            return None
+        routed = gemm_gather_grouped_tokens(*st)
+        plan = self._batched_plan() if routed else None
+        if plan is None:
+            return None
+        descs, caches = plan
+        return caches[0].device, caches[0].device_index, int(B.lib().vptq_quant_gemm_gather_grouped_workspace_bytes(descs, len(caches), routed[-1]))
+
+    def forward_batched(self, layer, x, tokens):
+        """5 - 16 tokens of large-codebook siblings: ONE launch for the group (`vptq_quant_gemm_gather_grouped`, one x gather per
+        distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
+        the first member called launches, the others pick their output up when they are called with the very same tensor at the
+        same version.  None = not this group's route (the route function says no, a compacted member, mixed formats or dtypes, a
+        group the library does not serve, an x that is not what the entry takes, a tensor without version counter, a capture with
+        too small a workspace): the caller goes on alone over the routes it had."""
+        D = self.__dict__
+        ver = B.tensor_version(x)
+        if ver >= 0 and D.get("_bx") is x and ver == self._bversion and id(layer) in self._bout:
+            y = self._bout.pop(id(layer))
+            if not self._bout:
+                self._bx = self._keep_bx = None
+            return y
+        st = self._batched_static()
+        if st is None or not gemm_gather_grouped_route(st[0], st[1], st[2], st[3], st[4], tokens, st[5]):
+            return None
+        if ver < 0 or ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC:
+            self._bx, self._bout = None, {}
+            return None
+        self._bx, self._bout = None, {}     # a new leader call: whatever an earlier one left unconsumed is stale
+        plan = self._batched_plan()
+        if plan is None:
+            return None
+        descs, caches = plan
+        if x.shape[-1] != st[4] or x.dtype != caches[0].dtype or x.device != caches[0].device:
+            return None   # (the member's own routes raise the shape / dtype / device errors)
+        xc = x if x.is_contiguous() else x.contiguous()
+        if xc.data_ptr() % 16:
+            return None
+        ys = ops.quant_gemm_gather_grouped(xc, descs, st[3])
+        if ys is None:
+            return None
+        self._bx, self._bversion, self._keep_bx = x, ver, xc
+        self._bout = {id(m): y for m, y in zip(self.members, ys) if m is not layer}
         return ys[self.members.index(layer)]
 
     def forward(self, layer, x, tokens):
@@ -290,7 +407,8 @@ SIBLING_PATTERNS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))
 def link_siblings(model: nn.Module, patterns=SIBLING_PATTERNS) -> int:
     """Find, under every sub-module of `model`, children named like one of `patterns` that are all
     `VQuantLinear` layers of the same input width and dtype, and make each set a
-    `SiblingGroup`.  Returns the number of groups.  Decode-time optimisation (1-4 tokens)."""
+    `SiblingGroup`.  Returns the number of groups.  Decode-time optimisation (1-4 tokens; 5-16 tokens of the large-codebook
+    formats where `gemm_gather_grouped_route` routes the group: `SiblingGroup.forward_batched`)."""
     n = 0
     for parent in model.modules():
         for names in patterns:
@@ -424,6 +542,12 @@ class VQuantLinear(nn.Module):
                 "path, which is outside this inference package; construct the layer with "
                 "enable_proxy_error=False (HF does).")
         tokens = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        if GROUPED_DECODE_MIN_TOKENS <= tokens <= GROUPED_DECODE_MAX_TOKENS and x.is_cuda:
+            group = self.__dict__.get("_siblings")
+            if group is not None:     # q / k / v, gate / up: one launch for the group where its route (vptq_amd/grouped_decode.py) takes the call
+                y = group.forward_batched(self, x, tokens)
+                if y is not None:
+                    return y
         if BATCHED_DECODE_MIN_TOKENS <= tokens <= BATCHED_DECODE_MAX_TOKENS and x.is_cuda and self.__dict__.get("_bd_routes", True):
             y = self._batched_decode_cached(x, tokens)   # (5 - 64 tokens in one launch, where a route of vptq_amd/batched_decode.py takes the call)
             if y is not None:

@@ -21,7 +21,7 @@ from torch.nn import functional as F
 from vptq_amd import _backend as B
 from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -348,6 +348,39 @@ def quant_gemm_gather_px(x: torch.Tensor, desc, out_features: int, out_f32: bool
         raise RuntimeError("quant_gemm_gather_px: the stream's workspace is too small and cannot grow during a capture "
                            "(call it once, or vptq_amd.prepare_model, before capturing)")
     return y
+
+
+def quant_gemm_gather_grouped(x: torch.Tensor, descs, out_features_list, out_f32: bool = False):
+    """[y_m = x @ W_m^T + bias_m] for 1 - 16 tokens of 2 - 4 sibling layers `quant_gemm_gather` serves (one dtype, input width and
+    residual codebook size; with or without a column permutation) in ONE launch (`vptq_quant_gemm_gather_grouped`, gemm_gather.hip's
+    grouped kernel) behind one x[:, perm] gather per DISTINCT `perm` pointer of the members, written into this stream's workspace
+    (`B.gemv_workspace`).  Every y_m has the bits of the member's own entry (`quant_gemm_gather_px` with a permutation,
+    `quant_gemm_gather` without).  `descs` = a ctypes array (or a sequence) of LayerDesc of a group
+    `vptq_quant_gemm_gather_grouped_supported` accepts; out_f32: the un-rounded fp32 sums.  Returns the list of outputs, or None
+    where a stream capture is in progress and the workspace is too small (nothing is allocated or launched then; `prepare_model`
+    sizes it beforehand)."""
+    import ctypes as C
+    n = len(out_features_list)
+    if not isinstance(descs, C.Array):
+        descs = (B.LayerDesc * n)(*descs)
+    shape, dev = x.shape, x.device
+    tokens = x.numel() // shape[-1]
+    if not x.is_contiguous():
+        x = x.contiguous()
+    lib = B.lib()
+    flags = _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0)
+    with torch.cuda.device(dev):
+        sp = B.current_stream_ptr(dev)
+        need = lib.vptq_quant_gemm_gather_grouped_workspace_bytes(descs, n, tokens)
+        ws, wsb = B.gemv_workspace(dev.index if dev.index is not None else torch.cuda.current_device(), sp, need)
+        if need and ws is None:
+            return None
+        ys = [torch.empty(shape[:-1] + (o,), dtype=torch.float32 if out_f32 else x.dtype, device=dev) for o in out_features_list]
+        yp = (C.c_void_p * n)(*[y.data_ptr() for y in ys])
+        rc = lib.vptq_quant_gemm_gather_grouped(descs, n, x.data_ptr(), yp, tokens, flags, ws, wsb, sp)
+    if rc:
+        B.check(rc, "vptq_quant_gemm_gather_grouped")
+    return ys
 
 
 def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
