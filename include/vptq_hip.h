@@ -772,6 +772,45 @@ VPTQ_API int vptq_quant_gemm_gather_grouped(const VptqLayerDesc* descs, int n, c
                                             void* workspace, size_t workspace_bytes, void* stream);
 VPTQ_API int vptq_quant_gemm_gather_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of SIBLING layers of the CANONICAL format (v = 8, 256 + 256 centroids) in one launch (gemm_k256_grouped_kernel in
+ * gemm_k256.hip; added within ABI 12; present when the symbols are).  descs[0 .. n) are 2 - 4 layers vptq_quant_gemm_k256w serves, of
+ * one dtype and one group_size; they may differ in out_features, in every tensor, and in whether they have a column permutation.
+ * gemm_k256_grouped_kernel<DT, TB> (TB = 1 / 2 / 3 blocks of 16 tokens for 1 - 16 / 17 - 32 / 33 - 48 tokens) walks the members' row
+ * groups of 32 outputs as ONE list (member 0's, then member 1's, ...) with one persistent workgroup per CU, which rebuilds its
+ * codebook image when it moves on to the next member.  The order of every sum depends neither on the grid nor on the workgroup that
+ * runs a row group, so y[m] is BIT-IDENTICAL to what member m's own entry gives for the same descriptor and x: vptq_quant_gemv with
+ * VPTQ_GEMV_EXACT for 1 - 16 tokens (where vptq_quant_gemv_kernel_name says "gemm_k256_kernel"), vptq_quant_gemm_k256w for 17 - 48.
+ * The entry has the reference's roundings only (w = r16(r16(r16(c + r) * s) + b), vptq_dequant's bits), like vptq_quant_gemm_k256w.
+ * Members with a permutation are read in the form without one (scale_permuted, bias_permuted) over xp = x[perm] in the workspace,
+ * written by one permute_x_tokens launch per DISTINCT perm pointer: members whose `perm` pointers are equal share one xp.  All launches
+ * go to `stream`; nothing is allocated: graph-capturable.
+ *   x [tokens][in_features] (one x for every member), y[m] [tokens][descs[m].out_features], the members' dtype; flags:
+ *   VPTQ_GEMV_OUT_F32 stores the fp32 sums (every y[m] is float32); every other flag is accepted and changes nothing.
+ * vptq_quant_gemm_k256_grouped_supported: 1 where 2 <= n <= 4, 1 <= tokens <= 48, every member is a valid layer of the canonical format
+ *   as vptq_quant_gemm_k256w takes it (with perm: scale_permuted and bias_permuted) and the members share dtype and group_size, else 0;
+ *   host logic.
+ * vptq_quant_gemm_k256_grouped_workspace_bytes: k blocks of tokens * group_size * 2 rounded up to 256, k the number of distinct
+ *   non-NULL perm pointers among the members; 0 where no member has a permutation and where `_supported` answers 0.
+ * vptq_quant_gemm_k256_grouped: NULL descs / x / y VPTQ_E_NULL; tokens outside [1, 48] VPTQ_E_TOKENS; n outside [2, 4] or a group it
+ *   does not serve VPTQ_E_UNSUPPORTED (vptq_last_error names the first member that rules it out and why); a NULL y[m] VPTQ_E_NULL; an x
+ *   that is not 16-byte aligned VPTQ_E_UNSUPPORTED; then, where a member has a permutation, a NULL workspace or fewer workspace_bytes
+ *   than the query answers VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned VPTQ_E_ALIGN; nothing is launched then.
+ * vptq_quant_gemm_k256_grouped_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   permute_x_tokens g=N tok=N grid=XxY tpt=4 perms=K | <inner>      K distinct permutations: K such launches
+ *   none | <inner>                                                  no member has a permutation
+ *   <inner> = gemm_k256_grouped dt=f16|bf16 tok=N tb=1|2|3 n=N groups=A+B[+C[+D]] grid=N rgs=N passes=P
+ *       groups the row groups (4 vector-rows) of every member, grid the workgroups (at most one per CU), rgs the most row groups one
+ *       workgroup walks, passes every gemm_k256_pass any workgroup runs in any member: tb = 1 the row groups per pass, largest first
+ *       ("4+2+1", "4+1", "1", ...), tb = 2 / 3 "1x2" / "1x3".  Returns as vptq_quant_gemm_gather_instance does.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: every member as vptq_quant_gemm_k256w takes it (part of "supported"); x 16 bytes (VPTQ_E_UNSUPPORTED); the workspace 16
+ * bytes (VPTQ_E_ALIGN); every y[m] and bias element-aligned. */
+VPTQ_API int vptq_quant_gemm_k256_grouped_supported(const VptqLayerDesc* descs, int n, int tokens);
+VPTQ_API size_t vptq_quant_gemm_k256_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens);
+VPTQ_API int vptq_quant_gemm_k256_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags,
+                                          void* workspace, size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_k256_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits.
  * Alignment: indices and codebooks 4 bytes; everything else - W included - element-aligned.  16-byte aligned W, weight_scale /
  * weight_bias and indices let the kernel store, read the norm tensors and read the index stream in 16-byte pieces (store= / norm= / idx=

@@ -186,6 +186,12 @@ EXPORTS = {
     "vptq_quant_gemm_gather_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
     "vptq_quant_gemm_gather_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gather_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 48 tokens of 2 - 4 sibling layers of the canonical format in one launch, one x gather per distinct
+    # permutation (gemm_k256.hip's grouped kernel): the same four shapes
+    "vptq_quant_gemm_k256_grouped_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_k256_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_k256_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_k256_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

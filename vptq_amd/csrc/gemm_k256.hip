@@ -337,6 +337,62 @@ __global__ __launch_bounds__(kGThreads) void gemm_k256w_kernel(const GemmK256Par
   for (; left >= 1; --left, rg += grid) gemm_k256_pass<DT, PERM, 1, TB>(P, gsmem, rg);
 }
 
+// ---- sibling layers (q / k / v, gate / up) in ONE launch: the row-group lists of up to kGKMembers layers, concatenated ----------------
+// gemm_k256_pass addresses its row groups as rg0 + g * gridDim.x and the order of every sum depends neither on the grid, nor on NRG,
+// nor on the workgroup that runs the row group (above): member m's row group rg has the bits gemm_k256_kernel<DT, false> (TB = 1) /
+// gemm_k256w_kernel<DT, false, TB> gives it in the member's own launch.  Plain form only: a member with a column permutation arrives
+// as its descriptor without one and x[perm] for x (gemm_gather_px.hip).
+constexpr int kGKMembers = 4;
+
+struct GemmK256GroupedParams {
+  GemmK256Params m[kGKMembers];
+  int first_group[kGKMembers + 1];   // member m owns the global row groups [first_group[m], first_group[m + 1])
+  int n, n_groups;
+};
+
+// A workgroup walks the global row groups g = blockIdx.x, + gridDim.x, ...: g rises, so the member never falls - the members are
+// visited in order.  The switch is uniform per workgroup: a local copy of the member's argument block (kernarg, uniform index) and the
+// member's codebook image, rebuilt only where the workgroup has a row group in the member.  No barrier around the rebuild beside the
+// image function's own: every pass ends in __syncthreads() (no wave still gathers from the previous image) and gemm_k256_image ends
+// in one (the image is complete before the first gather).  The image is built through gemm_k256_image_call (above).
+// NO static __shared__ object here: it would move the dynamic LDS base off 0 and gemm_k256_image traps (absolute LDS addressing).  All
+// member state lives in kernel arguments and registers; the only LDS is the dynamic kGLds block.
+// gemm_k256_image behind a call, given the two tables it reads.  Inlined into the member loop, the image's per-thread addresses are
+// loop invariants: the compiler keeps them in registers through every pass, and <F16, 2> then spills 3 registers where
+// gemm_k256w_kernel<F16, false, 2> has no scratch memory (profiles/r32/listings.md).  Behind the call they die with it; the call
+// runs once per member and workgroup.  (The callee finds the dynamic LDS base through the compiler's per-kernel table: 0 for these
+// kernels, which have no static LDS.)
+static __device__ __attribute__((noinline)) void gemm_k256_image_call(const uint32_t* cent, const uint32_t* rcent) {
+  GemmK256Params P = {};
+  P.cent = cent; P.rcent = rcent;
+  gemm_k256_image(P);
+}
+template <typename DT, int TB>
+__global__ __launch_bounds__(kGThreads) void gemm_k256_grouped_kernel(const GemmK256GroupedParams GP) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gsmem[];
+  const int grid = (int)gridDim.x;
+  int g = blockIdx.x;
+#pragma unroll 1
+  for (int m = 0; m < GP.n; ++m) {
+    const int first = GP.first_group[m], end = GP.first_group[m + 1];
+    if (g >= end) continue;   // (uniform: g is the workgroup's)
+    const GemmK256Params P = GP.m[m];
+    gemm_k256_image_call(P.cent, P.rcent);
+    int left = (end - g + grid - 1) / grid;   // this workgroup's row groups inside [first, end)
+    int rg = g - first;                       // member-local: rg, rg + grid, ...
+    g += left * grid;
+    if constexpr (TB == 1) {
+      // (gemm_k256_kernel's loop)
+      for (; left >= 4; left -= 4, rg += 4 * grid) gemm_k256_pass<DT, false, 4>(P, gsmem, rg);
+      if (left >= 2) { gemm_k256_pass<DT, false, 2>(P, gsmem, rg); left -= 2; rg += 2 * grid; }
+      if (left >= 1) gemm_k256_pass<DT, false, 1>(P, gsmem, rg);
+    } else {
+      // (gemm_k256w_kernel's loop)
+      for (; left >= 1; --left, rg += grid) gemm_k256_pass<DT, false, 1, TB>(P, gsmem, rg);
+    }
+  }
+}
+
 // ---- host side -------------------------------------------------------------------
 bool gemm_k256_eligible(const VptqLayerDesc& d, int tokens, int flags) {
   (void)flags;
@@ -436,6 +492,77 @@ hipError_t launch_gemm_k256w(const VptqLayerDesc& d, const void* x, void* y, int
   const GemmK256Params P = gemm_k256_params(d, x, y, tokens, out_f32, D.n_groups);
   if (D.f16) return D.perm ? launch_gw_tb<F16, true>(P, D.tb, D.grid, st) : launch_gw_tb<F16, false>(P, D.tb, D.grid, st);
   return D.perm ? launch_gw_tb<BF16, true>(P, D.tb, D.grid, st) : launch_gw_tb<BF16, false>(P, D.tb, D.grid, st);
+}
+
+// ---- 2 - 4 sibling layers, 1 - 48 tokens (gemm_k256_grouped_kernel)
+// what one grouped launch IS: the template arguments of gemm_k256_grouped_kernel<DT, TB>, every member's row groups and the launch
+// shape, decided once for the launcher and for vptq_quant_gemm_k256_grouped_instance.  The members share dtype and width (the caller's
+// check).  grid <= CUs, so rgs (the most row groups of any workgroup) and passes (the bit mask of every NRG any workgroup runs in any
+// member; tb > 1: NRG = 1 only) are found by walking every workgroup's list as the kernel does.
+GemmK256GroupedDecision gemm_k256_grouped_decide(const VptqLayerDesc* descs, int n, int tokens) {
+  GemmK256GroupedDecision D = {};
+  if (n < 1 || n > kGKMembers) return D;
+  D.f16 = descs[0].dtype == VPTQ_DTYPE_F16;
+  D.tok = tokens;
+  D.tb = (tokens + 15) / 16;
+  D.n = n;
+  for (int m = 0; m < n; ++m) {
+    D.groups[m] = (descs[m].num_indices + kGRows - 1) / kGRows;
+    D.first_group[m + 1] = D.first_group[m] + D.groups[m];
+  }
+  D.total = D.first_group[n];
+  const int ncu = device_cus();
+  D.grid = D.total < ncu ? D.total : ncu;
+  for (int b = 0; b < D.grid; ++b) {
+    int g = b, rgs = 0;
+    for (int m = 0; m < n; ++m) {
+      const int end = D.first_group[m + 1];
+      if (g >= end) continue;
+      int left = (end - g + D.grid - 1) / D.grid;
+      g += left * D.grid;
+      rgs += left;
+      if (D.tb > 1) { D.passes |= 1; continue; }
+      if (left >= 4) { D.passes |= 4; left %= 4; }
+      if (left >= 2) { D.passes |= 2; left -= 2; }
+      if (left >= 1) D.passes |= 1;
+    }
+    if (rgs > D.rgs) D.rgs = rgs;
+  }
+  return D;
+}
+
+template <typename DT, int TB>
+static hipError_t launch_gg(const GemmK256GroupedParams& GP, int grid, hipStream_t st) {
+  if (const hipError_t e = allow_dynamic_lds<gemm_k256_grouped_kernel<DT, TB>>(kGLds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((gemm_k256_grouped_kernel<DT, TB>), dim3(grid), dim3(kGThreads), kGLds, st, GP);
+  return hipGetLastError();
+}
+
+template <typename DT>
+static hipError_t launch_gg_tb(const GemmK256GroupedParams& GP, int tb, int grid, hipStream_t st) {
+  switch (tb) {
+    case 1: return launch_gg<DT, 1>(GP, grid, st);
+    case 2: return launch_gg<DT, 2>(GP, grid, st);
+    case 3: return launch_gg<DT, 3>(GP, grid, st);
+  }
+  return hipErrorInvalidValue;
+}
+
+// descs: the members WITHOUT a permutation (a permuted member as its plain form); x[m]: member m's activations in its own column order
+hipError_t launch_gemm_k256_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                    hipStream_t st) {
+  const GemmK256GroupedDecision D = gemm_k256_grouped_decide(descs, n, tokens);
+  if (D.n < 2 || D.grid < 1 || tokens < 1 || D.tb < 1 || D.tb > 3) return hipErrorInvalidValue;
+  GemmK256GroupedParams GP = {};
+  for (int m = 0; m < n; ++m) {
+    if (descs[m].perm || !x[m] || !y[m]) return hipErrorInvalidValue;
+    GP.m[m] = gemm_k256_params(descs[m], x[m], y[m], tokens, out_f32, D.groups[m]);
+    GP.first_group[m] = D.first_group[m];
+  }
+  for (int m = n; m <= kGKMembers; ++m) GP.first_group[m] = D.total;
+  GP.n = n;
+  GP.n_groups = D.total;
+  return D.f16 ? launch_gg_tb<F16>(GP, D.tb, D.grid, st) : launch_gg_tb<BF16>(GP, D.tb, D.grid, st);
 }
 
 }  // namespace vptq

@@ -205,6 +205,15 @@ bool gemm_k256w_eligible(const VptqLayerDesc& d, int tokens);
 struct GemmK256WDecision { bool f16, perm; int tok, tb, n_groups, grid, rgs; };
 GemmK256WDecision gemm_k256w_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_k256w(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+// the same file: 2 - 4 sibling layers of gemm_k256_eligible (one dtype and width), 1 - 48 tokens, in ONE launch of
+// gemm_k256_grouped_kernel<DT, TB>, whose workgroups walk the members' row groups as one list; plain form only - the caller hands a
+// member with a permutation over as gemm_gather_px_plain(d), with x[perm] for its x.  groups: row groups per member, first_group: their
+// running sum; total and grid = min(total, CUs) over the whole list; rgs: the most row groups of any workgroup; passes: bit mask of every
+// NRG = 4 / 2 / 1 pass any workgroup runs in any member (tb > 1: 1)
+struct GemmK256GroupedDecision { bool f16; int tok, tb, n, total, grid, rgs, passes, groups[4], first_group[5]; };
+GemmK256GroupedDecision gemm_k256_grouped_decide(const VptqLayerDesc* descs, int n, int tokens);
+hipError_t launch_gemm_k256_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                    hipStream_t st);
 
 // gemm_gather.hip - gemv_gather's layers (v = 8, k = 65536, residual 0 / 256 / 65536), up to 16 tokens in one launch (tokens = MFMA M;
 // centroid rows gathered from L2, the rebuilt tile in LDS in operand order; reference roundings; no workspace).  The kernels'

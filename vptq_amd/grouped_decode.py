@@ -1,15 +1,15 @@
 """The batched-decode route of a GROUP of sibling layers (q / k / v, gate / up): which (format, shapes, token count) take
 `vptq_quant_gemm_gather_grouped` - the members' row groups as one list in ONE launch, one x gather per distinct permutation - in
-place of one launch (and one x gather) per member.
+place of one launch (and one x gather) per member; for the canonical format, `vptq_quant_gemm_k256_grouped`.
 
-Pure rules - no device, no tensors, in the style of vptq_amd/batched_decode.py: one route function, its knob and its measured
-cells.  This route is a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
+Pure rules - no device, no tensors, in the style of vptq_amd/batched_decode.py: per route one route function, its knob and its
+measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group routes.  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
 is not routed here leaves every member on the routes it had.  `SiblingGroup.forward_batched` (vptq_amd/layers/vqlinear.py) and
 `prepare_model` decide through it.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 from vptq_amd import _backend as B
 from vptq_amd.batched_decode import _batched_decode_entry
@@ -71,3 +71,94 @@ def gemm_gather_grouped_tokens(vector_len: int, num_centroids: int, num_res_cent
     sizes the stream's workspace to the largest"""
     return tuple(t for t in range(GEMM_GATHER_GROUPED_MIN_TOKENS, GEMM_GATHER_GROUPED_MAX_TOKENS + 1)
                  if gemm_gather_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
+
+
+# WHICH groups of the CANONICAL format (v = 8, 256 + 256 centroids) take `vptq_quant_gemm_k256_grouped` (gemm_k256.hip's grouped
+# kernel: one persistent workgroup per CU over the members' row groups of 32 outputs as one list), 5 - 48 tokens (1 - 4 tokens are
+# `SiblingGroup.forward`'s; 49 - 64 are not the kernel's).  The kernel has the reference's roundings only, so the CALLER asks every
+# member's arithmetic (`exact_only` in the record below).  A cell is (has_perm, member count, least TOTAL index elements of the group
+# = the sum of vector-rows x columns over its members, most total index elements or None, least tokens, most tokens); has_perm as
+# above.  With a member count and a most size, a cell can route q / k / v without routing the 70B gate / up pair - what the gather
+# table above cannot say.  Routed by the same rule: the grouped launch beats the SUM of what the members take without it by more than
+# the larger of 5 % and three times the larger run-to-run spread, in every measured cell of the region, in both dtypes; the routed
+# token counts of a group are one interval; no cell lies under GEMM_K256_GROUPED_MIN_ELEMENTS (2 M total index elements).
+# tools/gemm_k256_grouped_bench.py writes the table.  VPTQ_GEMM_K256_GROUPED=1 / 0 (with VPTQ_TUNING=1): every group of the canonical
+# format from 5 to 48 tokens / none.
+#
+# profiles/r32/table.md, profiles/r32/README.md (one MI355X, fp16 and bf16, q / k / v and gate / up of the 8B and 70B shapes = 3 M, 10 M,
+# 14 M and 56 M total index elements, tokens 5 / 8 / 16 / 17 / 32 / 48, with one shared permutation and without; 96 cells, every member has
+# the bits of its own entry in every one, 77 win; run-to-run spreads under 8 % in all but one cell, 11 %):
+#   q / k / v        every cell wins: with a permutation 0.07 - 0.32 of the parent (three launches that gather x two bytes at a time),
+#                    without 0.25 - 0.67 (k and v alone keep 32 of 256 CUs busy)
+#   gate / up        with a permutation every cell wins (0.08 - 0.67); without one the 8B shapes are level (0.98 - 1.01, 0 of 12 cells) and
+#                    the 70B shapes gain 6 - 12 %, by the rule in 5 of 12 cells
+# A region reaches from its smallest to its largest MEASURED group (3 M ... 10 M for three members, 14 M ... 56 M for two) and no
+# further: a q / k / v group above 10 M, a group of four and a pair without a permutation are behind the knob.
+_GEMM_K256_GROUPED_CELLS = ((True, 3, 3 << 20, 10 << 20, 5, 48), (False, 3, 3 << 20, 10 << 20, 5, 48), (True, 2, 14 << 20, 56 << 20, 5, 48))
+GEMM_K256_GROUPED_MIN_TOKENS, GEMM_K256_GROUPED_MAX_TOKENS = 5, 48
+GEMM_K256_GROUPED_MIN_ELEMENTS = 2 << 20
+GEMM_K256_GROUPED_MAX_MEMBERS = 4
+_GEMM_K256_GROUPED_MODE = (B.tune_env("VPTQ_GEMM_K256_GROUPED", "auto") or "auto").strip().lower()
+
+
+def gemm_k256_grouped_route(out_features_tuple: Sequence[int], in_features: int, tokens: int, has_perm: Optional[bool]) -> bool:
+    """does a group of canonical-format sibling layers with these output widths take `vptq_quant_gemm_k256_grouped` for `tokens`
+    tokens?  has_perm: True - every member has a column permutation, False - none, None - some.  Pure: no device, no library (whether
+    the library serves the group is `vptq_quant_gemm_k256_grouped_supported`'s answer, the arithmetic the caller's)."""
+    if _GEMM_K256_GROUPED_MODE in ("0", "off") or not GEMM_K256_GROUPED_MIN_TOKENS <= tokens <= GEMM_K256_GROUPED_MAX_TOKENS:
+        return False
+    n = len(out_features_tuple)
+    if not 2 <= n <= GEMM_K256_GROUPED_MAX_MEMBERS or in_features % 8:
+        return False
+    if _GEMM_K256_GROUPED_MODE in ("1", "on"):
+        return True
+    if has_perm is None:
+        return False
+    n_el = sum((o + 7) // 8 for o in out_features_tuple) * in_features
+    return any(perm == has_perm and members == n and n_el >= max(min_el, GEMM_K256_GROUPED_MIN_ELEMENTS) and
+               (max_el is None or n_el <= max_el) and min_tok <= tokens <= max_tok
+               for perm, members, min_el, max_el, min_tok, max_tok in _GEMM_K256_GROUPED_CELLS)
+
+
+def gemm_k256_grouped_tokens(out_features_tuple: Sequence[int], in_features: int, has_perm: Optional[bool]) -> tuple:
+    """the token counts the route function gives to the grouped launch for this group, ascending (possibly none): `prepare_model`
+    sizes the stream's workspace to the largest"""
+    return tuple(t for t in range(GEMM_K256_GROUPED_MIN_TOKENS, GEMM_K256_GROUPED_MAX_TOKENS + 1)
+                 if gemm_k256_grouped_route(out_features_tuple, in_features, t, has_perm))
+
+
+class GroupedDecodeRoute(NamedTuple):
+    """what differs between the group routes; everything else is one code path in `SiblingGroup` (a third route is a record and a
+    route function).  `route` and `tokens` take the group's static configuration as `SiblingGroup._batched_static` states it:
+    (vector length, main centroids, residual centroids, output widths, input width, has_perm)."""
+    entry: str                                # the library entry (+ "_supported", "_workspace_bytes"); ops.<entry without "vptq_"> launches it
+    owns: Callable[[int, int, int], bool]     # (vector length, main centroids, residual centroids): is the format this route's?
+    route: Callable[..., bool]                # (v, k, kr, output widths, input width, tokens, has_perm)
+    tokens: Callable[..., tuple]              # (v, k, kr, output widths, input width, has_perm): the routed token counts, ascending
+    min_tokens: int                           # the token window of the route
+    max_tokens: int
+    off_flags: int                            # launch flags that switch the route off
+    exact_only: bool = False                  # the kernel has the reference's roundings only: every member's arithmetic must be GEMV_EXACT
+
+
+# (the formats are disjoint: a group has at most one route, and the order changes no answer)
+GROUPED_DECODE_ROUTES = (
+    GroupedDecodeRoute("vptq_quant_gemm_gather_grouped", lambda v, k, kr: _batched_decode_entry(v, k, kr) == "vptq_quant_gemm_gather",
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_gather_grouped_route(v, k, kr, outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_gather_grouped_tokens(v, k, kr, outs, width, has_perm),
+                       GEMM_GATHER_GROUPED_MIN_TOKENS, GEMM_GATHER_GROUPED_MAX_TOKENS, B.GEMV_FORCE_GENERIC),
+    GroupedDecodeRoute("vptq_quant_gemm_k256_grouped", lambda v, k, kr: (v, k, kr) == (8, 256, 256),
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_k256_grouped_route(outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_k256_grouped_tokens(outs, width, has_perm),
+                       GEMM_K256_GROUPED_MIN_TOKENS, GEMM_K256_GROUPED_MAX_TOKENS, B.GEMV_FORCE_ANY, exact_only=True),
+)
+GROUPED_DECODE_MIN_TOKENS = min(r.min_tokens for r in GROUPED_DECODE_ROUTES)   # the union of the windows: what a caller guards with
+GROUPED_DECODE_MAX_TOKENS = max(r.max_tokens for r in GROUPED_DECODE_ROUTES)
+
+
+def grouped_decode_route(vector_len: int, num_centroids: int, num_res_centroids: int) -> Optional[GroupedDecodeRoute]:
+    """the group route whose kernel has this format, or None.  No knob is read."""
+    for r in GROUPED_DECODE_ROUTES:
+        if r.owns(vector_len, num_centroids, num_res_centroids):
+            return r
+    return None

@@ -39,10 +39,11 @@ from vptq_amd.batched_decode import (  # noqa: F401
     BATCHED_DECODE_MAX_TOKENS, BATCHED_DECODE_MIN_TOKENS, GEMM_GATHER_MAX_TOKENS, GEMM_GATHER_PX_MAX_TOKENS, GEMM_GATHER_PX_MIN_TOKENS,
     GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS, GEMM_K256W_MIN_TOKENS, batched_decode_routes,
     batched_decode_takes, gemm_gather_px_route, gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_k256w_route)
-# the batched-decode rule of a GROUP of siblings lives in vptq_amd/grouped_decode.py (its knob and cells are read there, at call time)
+# the batched-decode rules of a GROUP of siblings live in vptq_amd/grouped_decode.py: `GROUPED_DECODE_ROUTES`, one record per group
+# route (the knobs and cells are read there, at call time); the guard's window is the union of the routes' windows
 from vptq_amd.grouped_decode import (  # noqa: F401
-    GEMM_GATHER_GROUPED_MAX_TOKENS as GROUPED_DECODE_MAX_TOKENS, GEMM_GATHER_GROUPED_MIN_TOKENS as GROUPED_DECODE_MIN_TOKENS,
-    gemm_gather_grouped_route, gemm_gather_grouped_tokens)
+    GROUPED_DECODE_MAX_TOKENS, GROUPED_DECODE_MIN_TOKENS, gemm_gather_grouped_route, gemm_gather_grouped_tokens, gemm_k256_grouped_route,
+    gemm_k256_grouped_tokens, grouped_decode_route)
 # the sliced-layout rules (1 - 4 tokens) live in vptq_amd/sliced_routes.py and are read through the module (`R.exact_route_is_large`:
 # one monkeypatch changes every reader); only import-time constants that nothing assigns to are imported by name, for the hot guard
 from vptq_amd import sliced_routes as R
@@ -136,8 +137,8 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
     the library's builder, layer by layer) instead of inside the first decode step, and every layer has its one-token workspace for
     `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  The stream's `B.gemv_workspace` is grown to
     the largest x[perm] copy (`vptq_quant_gemm_gather_px_workspace_bytes` at 48 tokens) of the permuted layers `gemm_gather_px_route`
-    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` needs for the linked sibling groups `gemm_gather_grouped_route`
-    routes (at their largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
+    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped` need for the linked sibling
+    groups their route (`gemm_gather_grouped_route` / `gemm_k256_grouped_route`) routes (at their largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
     "built": layers with a layout, "bytes", "seconds"}."""
     rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
     px = {}   # device index -> (device, most workspace bytes of its routed permuted layers)
@@ -234,7 +235,8 @@ class SiblingGroup:
     def _batched_static(self):
         """what the group's batched-decode route is asked with, from the members' static configuration: (vector length, main
         centroids, residual centroids, output widths, input width, has_perm: True - every member has a permutation, False - none,
-        None - some), or None where the members do not share format and width or are not one-codebook layers with scale and bias"""
+        None - some), or None where the members do not share format and width or are not one-codebook layers with scale and bias.
+        `_batched_route` is the record of `GROUPED_DECODE_ROUTES` (vptq_amd/grouped_decode.py) whose kernel has that format, or None."""
         st = self.__dict__.get("_bstatic")
         if st is None:
             ms = self.members
@@ -246,11 +248,15 @@ class SiblingGroup:
                 v, k, kr, width = next(iter(fmt))
                 st = ((v, k, kr, tuple(m.out_features for m in ms), width, perms.pop() if len(perms) == 1 else None),)
             self._bstatic = st
+            self._broute = grouped_decode_route(*st[0][:3]) if st[0] is not None else None
         return st[0]
 
+    def _batched_route(self):
+        return self._broute if self._batched_static() is not None else None
+
     def _batched_plan(self):
-        """the descriptor array `vptq_quant_gemm_gather_grouped` is called with, (descs, caches), decided once per set of
-        descriptor generations - or None: a compacted member, a library without the entry, members on several devices or of
+        """the descriptor array the group route's entry (`vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped`) is called
+        with, (descs, caches), decided once per set of descriptor generations - or None: no route has the format, a compacted member, a library without the entry, members on several devices or of
         several dtypes, a group the library does not serve.  Members whose `perm` tensors are `torch.equal` get ONE perm pointer in
         their descriptor copies (the first such member's): the entry then gathers x once for them.  Not decided inside a stream
         capture (the comparison reads the device): the caller goes on alone and a later call asks again."""
@@ -261,7 +267,8 @@ class SiblingGroup:
             return st[1]
         plan = None
         lib = B.lib()
-        if not any("_compact" in m.__dict__ for m in self.members) and getattr(lib, "vptq_quant_gemm_gather_grouped", None) is not None \
+        r = self._batched_route()
+        if r is not None and not any("_compact" in m.__dict__ for m in self.members) and getattr(lib, r.entry, None) is not None \
                 and len({(c.device, c.dtype) for c in caches}) == 1:
             perms = [m._parameters.get("perm") if m.enable_perm else None for m in self.members]
             if any(p is not None and p.is_cuda for p in perms) and torch.cuda.is_current_stream_capturing():
@@ -278,7 +285,7 @@ class SiblingGroup:
                         break
                 else:
                     first.append((p, descs[i].perm))
-            if lib.vptq_quant_gemm_gather_grouped_supported(descs, n, GROUPED_DECODE_MIN_TOKENS):
+            if getattr(lib, r.entry + "_supported")(descs, n, r.min_tokens):
                 plan = (descs, caches)   # (the caches keep what the descriptors point at alive)
         self._bplan = (key, plan)
         return plan
@@ -286,23 +293,27 @@ class SiblingGroup:
     def _batched_workspace_bytes(self):
         """(device, device index, bytes) of stream workspace the largest call the group's batched-decode route can take needs
         (`prepare_model` grows the stream's buffer to it), or None: the group never takes that route"""
-        st = self._batched_static()
-        if st is None:
+        st, r = self._batched_static(), self._batched_route()
+        if r is None:
             return None
-        routed = gemm_gather_grouped_tokens(*st)
+        routed = r.tokens(*st)
         plan = self._batched_plan() if routed else None
         if plan is None:
             return None
         descs, caches = plan
-        return caches[0].device, caches[0].device_index, int(B.lib().vptq_quant_gemm_gather_grouped_workspace_bytes(descs, len(caches), routed[-1]))
+        if r.exact_only and not all(c.arithmetic_flags & B.GEMV_EXACT for c in caches):
+            return None
+        return caches[0].device, caches[0].device_index, int(getattr(B.lib(), r.entry + "_workspace_bytes")(descs, len(caches), routed[-1]))
 
     def forward_batched(self, layer, x, tokens):
-        """5 - 16 tokens of large-codebook siblings: ONE launch for the group (`vptq_quant_gemm_gather_grouped`, one x gather per
+        """5 - 16 tokens of large-codebook siblings, 5 - 48 of canonical-format siblings: ONE launch for the group (the entry of the
+        group's record in `GROUPED_DECODE_ROUTES`: `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped`, one x gather per
         distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
         the first member called launches, the others pick their output up when they are called with the very same tensor at the
-        same version.  None = not this group's route (the route function says no, a compacted member, mixed formats or dtypes, a
-        group the library does not serve, an x that is not what the entry takes, a tensor without version counter, a capture with
-        too small a workspace): the caller goes on alone over the routes it had."""
+        same version.  None = not this group's route (no route has the format, the route function says no, a compacted member,
+        mixed formats or dtypes, a group the library does not serve, a member whose arithmetic is not the reference's roundings where
+        the kernel has no other, an x that is not what the entry takes, a tensor without version counter, a capture with too small a
+        workspace): the caller goes on alone over the routes it had."""
         D = self.__dict__
         ver = B.tensor_version(x)
         if ver >= 0 and D.get("_bx") is x and ver == self._bversion and id(layer) in self._bout:
@@ -310,10 +321,10 @@ class SiblingGroup:
             if not self._bout:
                 self._bx = self._keep_bx = None
             return y
-        st = self._batched_static()
-        if st is None or not gemm_gather_grouped_route(st[0], st[1], st[2], st[3], st[4], tokens, st[5]):
+        st, r = self._batched_static(), self._batched_route()
+        if r is None or not r.route(st[0], st[1], st[2], st[3], st[4], tokens, st[5]):
             return None
-        if ver < 0 or ops.quant_gemm_flags() & B.GEMV_FORCE_GENERIC:
+        if ver < 0 or ops.quant_gemm_flags() & r.off_flags:
             self._bx, self._bout = None, {}
             return None
         self._bx, self._bout = None, {}     # a new leader call: whatever an earlier one left unconsumed is stale
@@ -321,12 +332,14 @@ class SiblingGroup:
         if plan is None:
             return None
         descs, caches = plan
+        if r.exact_only and not all(c.arithmetic_flags & B.GEMV_EXACT for c in caches):
+            return None   # (set_arithmetic("folded" / "selective"), or a member the load-time gate moved: the members keep their routes)
         if x.shape[-1] != st[4] or x.dtype != caches[0].dtype or x.device != caches[0].device:
             return None   # (the member's own routes raise the shape / dtype / device errors)
         xc = x if x.is_contiguous() else x.contiguous()
         if xc.data_ptr() % 16:
             return None
-        ys = ops.quant_gemm_gather_grouped(xc, descs, st[3])
+        ys = getattr(ops, r.entry[len("vptq_"):])(xc, descs, st[3])
         if ys is None:
             return None
         self._bx, self._bversion, self._keep_bx = x, ver, xc
@@ -408,7 +421,8 @@ def link_siblings(model: nn.Module, patterns=SIBLING_PATTERNS) -> int:
     """Find, under every sub-module of `model`, children named like one of `patterns` that are all
     `VQuantLinear` layers of the same input width and dtype, and make each set a
     `SiblingGroup`.  Returns the number of groups.  Decode-time optimisation (1-4 tokens; 5-16 tokens of the large-codebook
-    formats where `gemm_gather_grouped_route` routes the group: `SiblingGroup.forward_batched`)."""
+    formats and 5-48 of the canonical format where the group's route of vptq_amd/grouped_decode.py routes the group:
+    `SiblingGroup.forward_batched`)."""
     n = 0
     for parent in model.modules():
         for names in patterns:

@@ -21,7 +21,7 @@ from torch.nn import functional as F
 from vptq_amd import _backend as B
 from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherx", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -359,6 +359,12 @@ def quant_gemm_gather_grouped(x: torch.Tensor, descs, out_features_list, out_f32
     `vptq_quant_gemm_gather_grouped_supported` accepts; out_f32: the un-rounded fp32 sums.  Returns the list of outputs, or None
     where a stream capture is in progress and the workspace is too small (nothing is allocated or launched then; `prepare_model`
     sizes it beforehand)."""
+    return _grouped_launch("vptq_quant_gemm_gather_grouped", x, descs, out_features_list, out_f32)
+
+
+def _grouped_launch(entry: str, x: torch.Tensor, descs, out_features_list, out_f32: bool):
+    """the plumbing of the grouped entries (`entry`, `entry`_workspace_bytes): the descriptor array, this stream's workspace, one
+    output per member; None under a capture whose workspace is too small"""
     import ctypes as C
     n = len(out_features_list)
     if not isinstance(descs, C.Array):
@@ -371,16 +377,28 @@ def quant_gemm_gather_grouped(x: torch.Tensor, descs, out_features_list, out_f32
     flags = _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0)
     with torch.cuda.device(dev):
         sp = B.current_stream_ptr(dev)
-        need = lib.vptq_quant_gemm_gather_grouped_workspace_bytes(descs, n, tokens)
+        need = getattr(lib, entry + "_workspace_bytes")(descs, n, tokens)
         ws, wsb = B.gemv_workspace(dev.index if dev.index is not None else torch.cuda.current_device(), sp, need)
         if need and ws is None:
             return None
         ys = [torch.empty(shape[:-1] + (o,), dtype=torch.float32 if out_f32 else x.dtype, device=dev) for o in out_features_list]
         yp = (C.c_void_p * n)(*[y.data_ptr() for y in ys])
-        rc = lib.vptq_quant_gemm_gather_grouped(descs, n, x.data_ptr(), yp, tokens, flags, ws, wsb, sp)
+        rc = getattr(lib, entry)(descs, n, x.data_ptr(), yp, tokens, flags, ws, wsb, sp)
     if rc:
-        B.check(rc, "vptq_quant_gemm_gather_grouped")
+        B.check(rc, entry)
     return ys
+
+
+def quant_gemm_k256_grouped(x: torch.Tensor, descs, out_features_list, out_f32: bool = False):
+    """[y_m = x @ W_m^T + bias_m] for 1 - 48 tokens of 2 - 4 sibling layers of the canonical format (v = 8, 256 + 256 centroids, scale
+    and bias; one dtype and input width; with or without a column permutation) in ONE launch (`vptq_quant_gemm_k256_grouped`,
+    gemm_k256.hip's grouped kernel) behind one x[:, perm] gather per DISTINCT `perm` pointer of the members, written into this
+    stream's workspace (`B.gemv_workspace`).  The reference's roundings only: every y_m has the bits of the member's own entry
+    (`vptq_quant_gemv` with GEMV_EXACT up to 16 tokens, `quant_gemm_k256w` for 17 - 48).  `descs` = a ctypes array (or a sequence) of
+    LayerDesc of a group `vptq_quant_gemm_k256_grouped_supported` accepts; out_f32: the un-rounded fp32 sums.  Returns the list of
+    outputs, or None where a stream capture is in progress and the workspace is too small (nothing is allocated or launched then;
+    `prepare_model` sizes it beforehand)."""
+    return _grouped_launch("vptq_quant_gemm_k256_grouped", x, descs, out_features_list, out_f32)
 
 
 def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
