@@ -240,6 +240,14 @@ bool gemm_gatherw_eligible(const VptqLayerDesc& d, int tokens);
 struct GemmGatherWDecision { bool f16, perm; int T, tok, tb, tiles, n_groups, grid, rgs; };
 GemmGatherWDecision gemm_gatherw_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gatherw(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+// gemm_gatherw_grouped.hip - 2 - 4 sibling layers of gemm_gatherw (one dtype, width and index width T), 17 - 48 tokens, in ONE launch
+// of gemm_gatherw_grouped_kernel<DT, T, TB>: gemm_gatherw's pass behind gemm_gather_grouped's member walk; plain form only - the caller
+// hands a member with a permutation over as its descriptor without one, with x[perm] for its x.  groups, first_group, total as
+// GemmGatherGroupedDecision's; grid = min(total, CUs x 4), rgs over the whole list
+struct GemmGatherWGroupedDecision { bool f16; int T, tok, tb, n, tiles, total, grid, rgs, groups[4], first_group[5]; };
+GemmGatherWGroupedDecision gemm_gatherw_grouped_decide(const VptqLayerDesc* descs, int n, int tokens);
+hipError_t launch_gemm_gatherw_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                       hipStream_t st);
 
 // gemm_gatherx.hip - the large-codebook layers gemm_gather does not take (v = 8 / 16, 16384 ... 65536 main centroids, any residual
 // codebook, any total index width), up to 16 tokens in one launch: gemm_gather's structure with gemv_gatherx's index path

@@ -1,9 +1,11 @@
 """The batched-decode route of a GROUP of sibling layers (q / k / v, gate / up): which (format, shapes, token count) take
 `vptq_quant_gemm_gather_grouped` - the members' row groups as one list in ONE launch, one x gather per distinct permutation - in
-place of one launch (and one x gather) per member; for the canonical format, `vptq_quant_gemm_k256_grouped`.
+place of one launch (and one x gather) per member; for the canonical format, `vptq_quant_gemm_k256_grouped`; for 17 - 48 tokens of
+the large-codebook formats, `vptq_quant_gemm_gatherw_grouped`.
 
 Pure rules - no device, no tensors, in the style of vptq_amd/batched_decode.py: per route one route function, its knob and its
-measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group routes.  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
+measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group routes (`GROUPED_DECODE_WIDE_ROUTES`: a format's routes
+beyond its first window).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
 is not routed here leaves every member on the routes it had.  `SiblingGroup.forward_batched` (vptq_amd/layers/vqlinear.py) and
 `prepare_model` decide through it.
 """
@@ -127,6 +129,74 @@ def gemm_k256_grouped_tokens(out_features_tuple: Sequence[int], in_features: int
                  if gemm_k256_grouped_route(out_features_tuple, in_features, t, has_perm))
 
 
+# WHICH groups of the large-codebook formats take `vptq_quant_gemm_gatherw_grouped` (gemm_gatherw_grouped.hip: gemm_gatherw's pass
+# behind gemm_gather_grouped's member walk), 17 - 48 tokens - the window beyond `vptq_quant_gemm_gather_grouped`'s.  Without it every
+# member goes out alone from the 17th token on: gemm_gatherw, gemm_gather_px (a permute launch, then gemm_gatherw) or vptq_dequant + a
+# dense GEMM, whichever `BATCHED_DECODE_ROUTES` gives a layer of its size.  A cell is the canonical group's plus the residual size:
+# (residual centroids, has_perm, member count, least TOTAL index elements of the group = the sum of vector-rows x columns over its
+# members, most total index elements or None, least tokens, most tokens); has_perm as above.  With the member count and the most size
+# q / k / v can be routed without the gate / up pair.  Routed by the rule of the two tables above: the grouped launch beats the SUM
+# of what the members take without it by more than the larger of 5 % and three times the larger run-to-run spread, in every measured
+# cell of the region, in both dtypes; a region reaches from its smallest to its largest measured group and no further; the routed
+# token counts of a group are one interval; no cell lies under GEMM_GATHERW_GROUPED_MIN_ELEMENTS (2 M total index elements).
+# tools/gemm_gatherw_grouped_bench.py writes the table.  VPTQ_GEMM_GATHERW_GROUPED=1 / 0 (with VPTQ_TUNING=1): every group of the
+# kernel's format from 17 to 48 tokens / none.
+#
+# profiles/r33/table.md, profiles/r33/README.md (one MI355X, fp16 and bf16, q / k / v and gate / up of the 8B and 70B shapes = 3 M, 10 M,
+# 14 M and 56 M total index elements, tokens 17 / 24 / 32 / 40 / 48, with one shared permutation and without; 240 cells, every member has
+# the bits of its own entry in every one, 141 win; run-to-run spreads under 3 % in all but two cells, 4.1 % the largest):
+#   q / k / v        8B shapes (the parent: three dense routes): every cell wins, -0 / -256 0.38 - 0.64 of the parent, -65536 0.58 - 0.80.
+#                    70B shapes: -0 / -256 with a permutation every cell (0.72 - 0.92), without one up to 40 tokens (0.76 - 0.90; level at
+#                    48, 0.96 - 1.03); -65536 is level (0.95 - 1.02 with a permutation, 0.98 - 1.20 without)
+#   gate / up        8B shapes with a permutation: -0 / -256 every cell (0.82 - 0.94), -65536 up to 32 tokens (0.90 - 0.94); without one
+#                    -0 up to 40 tokens and -256 up to 32 (0.86 - 0.93), beyond them the parent's dense route is faster (1.08 - 1.25 at
+#                    48), -65536 never (0.96 - 1.17).  70B shapes: level with two launches (0.94 - 1.04, 3 of 60 cells win)
+# A region reaches from its smallest to its largest MEASURED group (3 M ... 10 M for three members, or one of the two alone; 14 M for
+# two) and no further: a q / k / v group above 10 M, a group of four, a group of which only some members have a permutation and the
+# 70B gate / up pair are behind the knob.
+_GEMM_GATHERW_GROUPED_CELLS = (
+    (0, True, 3, 3 << 20, 10 << 20, 17, 48), (0, False, 3, 3 << 20, 10 << 20, 17, 40), (0, False, 3, 3 << 20, 3 << 20, 17, 48),
+    (256, True, 3, 3 << 20, 10 << 20, 17, 48), (256, False, 3, 3 << 20, 10 << 20, 17, 40), (256, False, 3, 3 << 20, 3 << 20, 17, 48),
+    (65536, True, 3, 3 << 20, 3 << 20, 17, 48), (65536, False, 3, 3 << 20, 3 << 20, 17, 48),
+    (0, True, 2, 14 << 20, 14 << 20, 17, 48), (0, False, 2, 14 << 20, 14 << 20, 17, 40),
+    (256, True, 2, 14 << 20, 14 << 20, 17, 48), (256, False, 2, 14 << 20, 14 << 20, 17, 32),
+    (65536, True, 2, 14 << 20, 14 << 20, 17, 32))
+GEMM_GATHERW_GROUPED_MIN_TOKENS, GEMM_GATHERW_GROUPED_MAX_TOKENS = 17, 48
+GEMM_GATHERW_GROUPED_MIN_ELEMENTS = 2 << 20
+GEMM_GATHERW_GROUPED_MAX_MEMBERS = 4
+_GEMM_GATHERW_GROUPED_MODE = (B.tune_env("VPTQ_GEMM_GATHERW_GROUPED", "auto") or "auto").strip().lower()
+
+
+def gemm_gatherw_grouped_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                               in_features: int, tokens: int, has_perm: Optional[bool]) -> bool:
+    """does a group of sibling layers of this format (shared by its members) with these output widths take
+    `vptq_quant_gemm_gatherw_grouped` for `tokens` tokens?  has_perm: True - every member has a column permutation, False - none,
+    None - some.  Pure: no device, no library (whether the library serves the group is `vptq_quant_gemm_gatherw_grouped_supported`'s
+    answer)."""
+    if _GEMM_GATHERW_GROUPED_MODE in ("0", "off") or not GEMM_GATHERW_GROUPED_MIN_TOKENS <= tokens <= GEMM_GATHERW_GROUPED_MAX_TOKENS:
+        return False
+    n = len(out_features_tuple)
+    if not 2 <= n <= GEMM_GATHERW_GROUPED_MAX_MEMBERS or in_features % 8 or \
+            _batched_decode_entry(vector_len, num_centroids, num_res_centroids) != "vptq_quant_gemm_gather":
+        return False
+    if _GEMM_GATHERW_GROUPED_MODE in ("1", "on"):
+        return True
+    if has_perm is None:
+        return False
+    n_el = sum((o + vector_len - 1) // vector_len for o in out_features_tuple) * in_features
+    return any(kr == num_res_centroids and perm == has_perm and members == n and
+               n_el >= max(min_el, GEMM_GATHERW_GROUPED_MIN_ELEMENTS) and (max_el is None or n_el <= max_el) and
+               min_tok <= tokens <= max_tok for kr, perm, members, min_el, max_el, min_tok, max_tok in _GEMM_GATHERW_GROUPED_CELLS)
+
+
+def gemm_gatherw_grouped_tokens(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                in_features: int, has_perm: Optional[bool]) -> tuple:
+    """the token counts the route function gives to the grouped launch for this group, ascending (possibly none): `prepare_model`
+    sizes the stream's workspace to the largest"""
+    return tuple(t for t in range(GEMM_GATHERW_GROUPED_MIN_TOKENS, GEMM_GATHERW_GROUPED_MAX_TOKENS + 1)
+                 if gemm_gatherw_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
+
+
 class GroupedDecodeRoute(NamedTuple):
     """what differs between the group routes; everything else is one code path in `SiblingGroup` (a third route is a record and a
     route function).  `route` and `tokens` take the group's static configuration as `SiblingGroup._batched_static` states it:
@@ -162,3 +232,22 @@ def grouped_decode_route(vector_len: int, num_centroids: int, num_res_centroids:
         if r.owns(vector_len, num_centroids, num_res_centroids):
             return r
     return None
+
+
+# a format's routes BEYOND its first window, in window order: the large-codebook formats' 17 - 48 tokens behind
+# `vptq_quant_gemm_gather_grouped`'s 5 - 16.  The windows of one format are disjoint, so a token count has at most one record.
+GROUPED_DECODE_WIDE_ROUTES = (
+    GroupedDecodeRoute("vptq_quant_gemm_gatherw_grouped", lambda v, k, kr: _batched_decode_entry(v, k, kr) == "vptq_quant_gemm_gather",
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_gatherw_grouped_route(v, k, kr, outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_gatherw_grouped_tokens(v, k, kr, outs, width, has_perm),
+                       GEMM_GATHERW_GROUPED_MIN_TOKENS, GEMM_GATHERW_GROUPED_MAX_TOKENS, B.GEMV_FORCE_GENERIC),
+)
+
+
+def grouped_decode_routes(vector_len: int, num_centroids: int, num_res_centroids: int) -> tuple:
+    """every group route whose kernel has this format, in window order: the owner of `GROUPED_DECODE_ROUTES`, then the records of
+    `GROUPED_DECODE_WIDE_ROUTES` (possibly none at all).  No knob is read."""
+    first = grouped_decode_route(vector_len, num_centroids, num_res_centroids)
+    if first is None:
+        return ()
+    return (first,) + tuple(r for r in GROUPED_DECODE_WIDE_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))

@@ -43,7 +43,7 @@ from vptq_amd.batched_decode import (  # noqa: F401
 # route (the knobs and cells are read there, at call time); the guard's window is the union of the routes' windows
 from vptq_amd.grouped_decode import (  # noqa: F401
     GROUPED_DECODE_MAX_TOKENS, GROUPED_DECODE_MIN_TOKENS, gemm_gather_grouped_route, gemm_gather_grouped_tokens, gemm_k256_grouped_route,
-    gemm_k256_grouped_tokens, grouped_decode_route)
+    gemm_k256_grouped_tokens, grouped_decode_route, grouped_decode_routes)
 # the sliced-layout rules (1 - 4 tokens) live in vptq_amd/sliced_routes.py and are read through the module (`R.exact_route_is_large`:
 # one monkeypatch changes every reader); only import-time constants that nothing assigns to are imported by name, for the hot guard
 from vptq_amd import sliced_routes as R
@@ -137,8 +137,9 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
     the library's builder, layer by layer) instead of inside the first decode step, and every layer has its one-token workspace for
     `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  The stream's `B.gemv_workspace` is grown to
     the largest x[perm] copy (`vptq_quant_gemm_gather_px_workspace_bytes` at 48 tokens) of the permuted layers `gemm_gather_px_route`
-    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped` need for the linked sibling
-    groups their route (`gemm_gather_grouped_route` / `gemm_k256_grouped_route`) routes (at their largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
+    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_gatherw_grouped` / `vptq_quant_gemm_k256_grouped`
+    need for the linked sibling groups their routes (`gemm_gather_grouped_route` / `gemm_gatherw_grouped_route` /
+    `gemm_k256_grouped_route`) route (the largest need over a format's records, each at its largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
     "built": layers with a layout, "bytes", "seconds"}."""
     rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
     px = {}   # device index -> (device, most workspace bytes of its routed permuted layers)
@@ -236,7 +237,8 @@ class SiblingGroup:
         """what the group's batched-decode route is asked with, from the members' static configuration: (vector length, main
         centroids, residual centroids, output widths, input width, has_perm: True - every member has a permutation, False - none,
         None - some), or None where the members do not share format and width or are not one-codebook layers with scale and bias.
-        `_batched_route` is the record of `GROUPED_DECODE_ROUTES` (vptq_amd/grouped_decode.py) whose kernel has that format, or None."""
+        `_batched_route` is the record of `GROUPED_DECODE_ROUTES` (vptq_amd/grouped_decode.py) whose kernel has that format, or None;
+        with a token count, the record of the format (`grouped_decode_routes`: the owner, then its wide routes) whose window holds it."""
         st = self.__dict__.get("_bstatic")
         if st is None:
             ms = self.members
@@ -249,25 +251,35 @@ class SiblingGroup:
                 st = ((v, k, kr, tuple(m.out_features for m in ms), width, perms.pop() if len(perms) == 1 else None),)
             self._bstatic = st
             self._broute = grouped_decode_route(*st[0][:3]) if st[0] is not None else None
+            self._broutes = grouped_decode_routes(*st[0][:3]) if st[0] is not None else ()
         return st[0]
 
-    def _batched_route(self):
-        return self._broute if self._batched_static() is not None else None
+    def _batched_route(self, tokens=None):
+        if self._batched_static() is None:
+            return None
+        if tokens is None:
+            return self._broute
+        for r in self._broutes:   # (the windows of one format are disjoint)
+            if r.min_tokens <= tokens <= r.max_tokens:
+                return r
+        return None
 
-    def _batched_plan(self):
+    def _batched_plan(self, r=None):
         """the descriptor array the group route's entry (`vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped`) is called
-        with, (descs, caches), decided once per set of descriptor generations - or None: no route has the format, a compacted member, a library without the entry, members on several devices or of
+        with, (descs, caches), decided once per entry (r: a record of the format, default its first) and per set of descriptor generations - or None: no route has the format, a compacted member, a library without the entry, members on several devices or of
         several dtypes, a group the library does not serve.  Members whose `perm` tensors are `torch.equal` get ONE perm pointer in
         their descriptor copies (the first such member's): the entry then gathers x once for them.  Not decided inside a stream
         capture (the comparison reads the device): the caller goes on alone and a later call asks again."""
         caches = [m._descriptor() for m in self.members]
         key = tuple(c.generation for c in caches)   # a rebuilt descriptor never matches
-        st = self.__dict__.get("_bplan")
+        if r is None:
+            r = self._batched_route()
+        plans = self.__dict__.setdefault("_bplan", {})   # entry -> (generations, plan)
+        st = plans.get(r.entry) if r is not None else plans.get(None)
         if st is not None and st[0] == key:
             return st[1]
         plan = None
         lib = B.lib()
-        r = self._batched_route()
         if r is not None and not any("_compact" in m.__dict__ for m in self.members) and getattr(lib, r.entry, None) is not None \
                 and len({(c.device, c.dtype) for c in caches}) == 1:
             perms = [m._parameters.get("perm") if m.enable_perm else None for m in self.members]
@@ -287,28 +299,34 @@ class SiblingGroup:
                     first.append((p, descs[i].perm))
             if getattr(lib, r.entry + "_supported")(descs, n, r.min_tokens):
                 plan = (descs, caches)   # (the caches keep what the descriptors point at alive)
-        self._bplan = (key, plan)
+        plans[r.entry if r is not None else None] = (key, plan)
         return plan
 
     def _batched_workspace_bytes(self):
         """(device, device index, bytes) of stream workspace the largest call the group's batched-decode route can take needs
-        (`prepare_model` grows the stream's buffer to it), or None: the group never takes that route"""
-        st, r = self._batched_static(), self._batched_route()
-        if r is None:
+        (`prepare_model` grows the stream's buffer to it) - the largest need over the format's records, each at its largest routed
+        token count - or None: the group never takes such a route"""
+        st = self._batched_static()
+        if self._batched_route() is None:
             return None
-        routed = r.tokens(*st)
-        plan = self._batched_plan() if routed else None
-        if plan is None:
-            return None
-        descs, caches = plan
-        if r.exact_only and not all(c.arithmetic_flags & B.GEMV_EXACT for c in caches):
-            return None
-        return caches[0].device, caches[0].device_index, int(getattr(B.lib(), r.entry + "_workspace_bytes")(descs, len(caches), routed[-1]))
+        best = None
+        for r in self._broutes:
+            routed = r.tokens(*st)
+            plan = self._batched_plan(r) if routed else None
+            if plan is None:
+                continue
+            descs, caches = plan
+            if r.exact_only and not all(c.arithmetic_flags & B.GEMV_EXACT for c in caches):
+                continue
+            need = int(getattr(B.lib(), r.entry + "_workspace_bytes")(descs, len(caches), routed[-1]))
+            if best is None or need > best[2]:
+                best = (caches[0].device, caches[0].device_index, need)
+        return best
 
     def forward_batched(self, layer, x, tokens):
-        """5 - 16 tokens of large-codebook siblings, 5 - 48 of canonical-format siblings: ONE launch for the group (the entry of the
-        group's record in `GROUPED_DECODE_ROUTES`: `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped`, one x gather per
-        distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
+        """5 - 48 tokens of large-codebook and of canonical-format siblings: ONE launch for the group (the entry of the group's record
+        whose window holds the token count: `vptq_quant_gemm_gather_grouped` up to 16 tokens / `vptq_quant_gemm_gatherw_grouped` from 17 /
+        `vptq_quant_gemm_k256_grouped`, one x gather per distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
         the first member called launches, the others pick their output up when they are called with the very same tensor at the
         same version.  None = not this group's route (no route has the format, the route function says no, a compacted member,
         mixed formats or dtypes, a group the library does not serve, a member whose arithmetic is not the reference's roundings where
@@ -321,14 +339,14 @@ class SiblingGroup:
             if not self._bout:
                 self._bx = self._keep_bx = None
             return y
-        st, r = self._batched_static(), self._batched_route()
+        st, r = self._batched_static(), self._batched_route(tokens)
         if r is None or not r.route(st[0], st[1], st[2], st[3], st[4], tokens, st[5]):
             return None
         if ver < 0 or ops.quant_gemm_flags() & r.off_flags:
             self._bx, self._bout = None, {}
             return None
         self._bx, self._bout = None, {}     # a new leader call: whatever an earlier one left unconsumed is stale
-        plan = self._batched_plan()
+        plan = self._batched_plan(r)
         if plan is None:
             return None
         descs, caches = plan
