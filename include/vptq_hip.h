@@ -847,6 +847,48 @@ VPTQ_API int vptq_quant_gemm_gatherw_grouped(const VptqLayerDesc* descs, int n, 
                                              void* workspace, size_t workspace_bytes, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherw_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of SIBLING layers of the large-codebook formats vptq_quant_gemm_gatherx serves (v = 8 / 16, 16384 ... 65536 main
+ * centroids, any residual codebook: v16-k65536-65536 / -32768 / -1024 / -0, v8-k65536-4096, v8-k32768-0, ...) in one launch
+ * (gemm_gatherx_grouped_kernel in gemm_gatherx_grouped.hip; added within ABI 12; present when the symbols are).  descs[0 .. n) are 2 - 4
+ * layers vptq_quant_gemm_gatherx serves, of one dtype, one group_size and one format (vector_len, num_centroids, num_res_centroids);
+ * they may differ in out_features, in every tensor, and in whether they have a column permutation.
+ * gemm_gatherx_grouped_kernel<DT, V, RES> (RES: no residual table / table in LDS / table gathered from L2) walks the members' row
+ * groups of 16 outputs as ONE list (member 0's, then member 1's, ...); a workgroup that moves on to the next member reloads its
+ * pointers, scale and bias and (table in LDS) stages its residual table.  A row group depends neither on the grid nor on the
+ * workgroup that runs it, so y[m] is BIT-IDENTICAL to what member m's own entry gives for the same descriptor and x -
+ * vptq_quant_gemm_gather_px for a member with a permutation, vptq_quant_gemm_gatherx for one without - and carries its guarantees.
+ * The entry has the reference's roundings only, like vptq_quant_gemm_gatherx.  Members with a permutation are read in the form
+ * without one (scale_permuted, bias_permuted) over xp = x[perm] in the workspace, written by one permute_x_tokens launch per DISTINCT
+ * perm pointer: members whose `perm` pointers are equal share one xp.  All launches go to `stream`; nothing is allocated, no atomics:
+ * graph-capturable.
+ *   x [tokens][in_features] (one x for every member), y[m] [tokens][descs[m].out_features], the members' dtype; flags:
+ *   VPTQ_GEMV_OUT_F32 stores the fp32 sums (every y[m] is float32); every other flag is accepted and changes nothing.
+ * vptq_quant_gemm_gatherx_grouped_supported: 1 where 2 <= n <= 4, 1 <= tokens <= 16, vptq_quant_gemm_gatherx_supported answers 1 for
+ *   every member and the members share dtype, group_size, vector_len, num_centroids and num_res_centroids, else 0; host logic.
+ * vptq_quant_gemm_gatherx_grouped_workspace_bytes: k blocks of tokens * group_size * 2 rounded up to 256, k the number of distinct
+ *   non-NULL perm pointers among the members; 0 where no member has a permutation and where `_supported` answers 0.
+ * vptq_quant_gemm_gatherx_grouped: NULL descs / x / y VPTQ_E_NULL; tokens outside [1, 16] VPTQ_E_TOKENS; n outside [2, 4] or a group
+ *   it does not serve VPTQ_E_UNSUPPORTED (vptq_last_error names the first member that rules it out and why); a NULL y[m] VPTQ_E_NULL;
+ *   an x that is not 16-byte aligned VPTQ_E_UNSUPPORTED; then, where a member has a permutation, a NULL workspace or fewer
+ *   workspace_bytes than the query answers VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned VPTQ_E_ALIGN; nothing is
+ *   launched then.
+ * vptq_quant_gemm_gatherx_grouped_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   permute_x_tokens g=N tok=N grid=XxY tpt=4 perms=K | <inner>      K distinct permutations: K such launches
+ *   none | <inner>                                                  no member has a permutation
+ *   <inner> = gemm_gatherx_grouped dt=f16|bf16 v=8|16 ib=N rb=N res=none|lds|l2 tok=N n=N groups=A+B[+C[+D]] tiles=N wgcu=N grid=N rgs=N
+ *       ib / rb the main / residual index widths, groups the row groups (16 outputs: one vector-row of v = 16, two of v = 8) of
+ *       every member, tiles the column tiles (1024 columns) per row group, wgcu the workgroups per CU the LDS need leaves (4 / 3 / 2 up
+ *       to 40 / 48 / 64 KiB: the 32 KiB tile + a table in LDS), grid = min(total row groups, CUs * wgcu) the workgroups, rgs the most
+ *       row groups one workgroup walks.  Returns as vptq_quant_gemm_gather_instance does.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: every member as vptq_quant_gemm_gatherx takes it (part of "supported"); x 16 bytes (VPTQ_E_UNSUPPORTED); the workspace 16
+ * bytes (VPTQ_E_ALIGN); every y[m] and bias element-aligned. */
+VPTQ_API int vptq_quant_gemm_gatherx_grouped_supported(const VptqLayerDesc* descs, int n, int tokens);
+VPTQ_API size_t vptq_quant_gemm_gatherx_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens);
+VPTQ_API int vptq_quant_gemm_gatherx_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags,
+                                             void* workspace, size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gatherx_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits.
  * Alignment: indices and codebooks 4 bytes; everything else - W included - element-aligned.  16-byte aligned W, weight_scale /
  * weight_bias and indices let the kernel store, read the norm tensors and read the index stream in 16-byte pieces (store= / norm= / idx=

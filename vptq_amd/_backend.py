@@ -198,6 +198,12 @@ EXPORTS = {
     "vptq_quant_gemm_gatherw_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
     "vptq_quant_gemm_gatherw_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gatherw_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 16 tokens of 2 - 4 sibling layers of vptq_quant_gemm_gatherx in one launch, one x gather per distinct
+    # permutation (gemm_gatherx_grouped.hip): the same four shapes
+    "vptq_quant_gemm_gatherx_grouped_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gatherx_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gatherx_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gatherx_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

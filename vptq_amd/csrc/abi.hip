@@ -1621,6 +1621,90 @@ int vptq_quant_gemm_gatherw_grouped_instance(const VptqLayerDesc* descs, int n, 
   return instance_done(t);
 }
 
+// ---- gemm_gatherx_grouped.hip (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gatherx, 1 - 16 tokens, in ONE launch of
+// gemm_gatherx_grouped_kernel, behind one permute launch per DISTINCT perm pointer of the members.  The plan is the gather group's
+// (grouped_gather_decide), the checks are its checks with gemm_gatherx's eligibility and the whole format shared.
+static const char* grouped_gatherx_refusal(const VptqLayerDesc* descs, int n, int tokens, int* member) {
+  *member = 0;
+  if (n < 2 || n > 4) return "a group has 2 - 4 members";
+  for (int m = 0; m < n; ++m) {
+    *member = m;
+    if (validate_layer(&descs[m]) != VPTQ_OK) return "not a valid layer";
+    if (!kGemmGatherX.eligible(descs[m], tokens)) return "not a layer vptq_quant_gemm_gatherx serves";
+    if (descs[m].dtype != descs[0].dtype) return "another dtype than member 0";
+    if (descs[m].group_size != descs[0].group_size) return "another group_size than member 0";
+    if (descs[m].vector_len != descs[0].vector_len) return "another vector length than member 0";
+    if (descs[m].num_centroids != descs[0].num_centroids) return "another main codebook size than member 0";
+    if (descs[m].num_res_centroids != descs[0].num_res_centroids) return "another residual codebook size than member 0";
+  }
+  return nullptr;
+}
+static int grouped_gatherx_validate(const VptqLayerDesc* descs, int n, int tokens) {
+  if (tokens < kGemmGatherX.tok_lo || tokens > kGemmGatherX.tok_hi)
+    return fail(VPTQ_E_TOKENS, "tokens %d outside [%d, %d]", tokens, kGemmGatherX.tok_lo, kGemmGatherX.tok_hi);
+  int member = 0;
+  if (const char* why = grouped_gatherx_refusal(descs, n, tokens, &member))
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherx_grouped (n = %d): member %d: %s", n, member, why);
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gatherx_grouped_supported(const VptqLayerDesc* descs, int n, int tokens) {
+  int member = 0;
+  return descs && tokens >= kGemmGatherX.tok_lo && tokens <= kGemmGatherX.tok_hi && !grouped_gatherx_refusal(descs, n, tokens, &member) ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gatherx_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens) {
+  if (!vptq_quant_gemm_gatherx_grouped_supported(descs, n, tokens)) return 0;
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  return G.block_bytes * (size_t)G.n_perms;
+}
+
+int vptq_quant_gemm_gatherx_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (!descs || !x || !y) return fail(VPTQ_E_NULL, "descs / x / y is NULL");
+  if (const int rc = grouped_gatherx_validate(descs, n, tokens)) return rc;
+  for (int m = 0; m < n; ++m)
+    if (!y[m]) return fail(VPTQ_E_NULL, "y[%d] is NULL", m);
+  if ((((uintptr_t)x) & 15) != 0) return fail(kGemmGatherX.misaligned, "gemm_gatherx_grouped: x must be 16-byte aligned");
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  const size_t need = G.block_bytes * (size_t)G.n_perms;
+  if (need > 0) {
+    if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gatherx_grouped: workspace of %zu bytes needed", need);
+    if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gatherx_grouped: the workspace must be 16-byte aligned");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  for (int j = 0; j < G.n_perms; ++j) {   // one x gather per distinct permutation (block_bytes is a multiple of 256)
+    const hipError_t e = vptq::launch_permute_x_tokens(descs[G.owner[j]], x, (char*)workspace + (size_t)j * G.block_bytes, tokens, st);
+    if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  }
+  const void* xs[4] = {};
+  for (int m = 0; m < n; ++m) xs[m] = G.slot[m] < 0 ? x : (const char*)workspace + (size_t)G.slot[m] * G.block_bytes;
+  const hipError_t e = vptq::launch_gemm_gatherx_grouped(G.plain, n, xs, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gatherx_grouped launch");
+}
+
+int vptq_quant_gemm_gatherx_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int, char* buf, size_t bytes) {
+  if (!descs || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = grouped_gatherx_validate(descs, n, tokens)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  if (G.n_perms > 0) {
+    const vptq::GemmGatherPxDecision D = vptq::gemm_gather_px_decide(descs[G.owner[0]], tokens);
+    t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d perms=%d | ", D.g, D.tok, D.grid_x, D.grid_y, D.tpt, G.n_perms);
+  } else {
+    t.add("none | ");
+  }
+  const vptq::GemmGatherXGroupedDecision D = vptq::gemm_gatherx_grouped_decide(G.plain, n, tokens);
+  t.add("gemm_gatherx_grouped dt=%s v=%d ib=%d rb=%d res=%s tok=%d n=%d groups=", dt_text(D.f16), D.v, D.ib, D.rb,
+        D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", D.tok, D.n);
+  for (int m = 0; m < D.n; ++m) t.add(m ? "+%d" : "%d", D.groups[m]);
+  t.add(" tiles=%d wgcu=%d grid=%d rgs=%d", D.tiles, D.wgcu, D.grid, D.rgs);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {
   int rc = validate_layer(d);

@@ -257,6 +257,15 @@ bool gemm_gatherx_eligible(const VptqLayerDesc& d, int tokens);
 struct GemmGatherXDecision { bool f16, perm; int v, ib, rb, res, res_bytes, tok, tiles, lds, wgcu, n_groups, grid, rgs; };
 GemmGatherXDecision gemm_gatherx_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gatherx(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+// gemm_gatherx_grouped.hip - 2 - 4 sibling layers of gemm_gatherx (one dtype, width and format: v, main and residual codebook size),
+// 1 - 16 tokens, in ONE launch of gemm_gatherx_grouped_kernel<DT, V, RES>: gemm_gatherx's row-group body behind gemm_gather_grouped's
+// member walk; plain form only - the caller hands a member with a permutation over as its descriptor without one, with x[perm] for
+// its x.  v ... wgcu: gemm_gatherx_decide's of the first member; groups, first_group, total as GemmGatherGroupedDecision's; grid =
+// min(total, CUs x wgcu), rgs over the whole list
+struct GemmGatherXGroupedDecision { bool f16; int v, ib, rb, res, res_bytes, tok, n, tiles, lds, wgcu, total, grid, rgs, groups[4], first_group[5]; };
+GemmGatherXGroupedDecision gemm_gatherx_grouped_decide(const VptqLayerDesc* descs, int n, int tokens);
+hipError_t launch_gemm_gatherx_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                       hipStream_t st);
 
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)

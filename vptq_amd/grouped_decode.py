@@ -1,11 +1,13 @@
 """The batched-decode route of a GROUP of sibling layers (q / k / v, gate / up): which (format, shapes, token count) take
 `vptq_quant_gemm_gather_grouped` - the members' row groups as one list in ONE launch, one x gather per distinct permutation - in
 place of one launch (and one x gather) per member; for the canonical format, `vptq_quant_gemm_k256_grouped`; for 17 - 48 tokens of
-the large-codebook formats, `vptq_quant_gemm_gatherw_grouped`.
+the large-codebook formats, `vptq_quant_gemm_gatherw_grouped`; for 5 - 16 tokens of the other large-codebook formats (gemm_gatherx's),
+`vptq_quant_gemm_gatherx_grouped`.
 
 Pure rules - no device, no tensors, in the style of vptq_amd/batched_decode.py: per route one route function, its knob and its
 measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group routes (`GROUPED_DECODE_WIDE_ROUTES`: a format's routes
-beyond its first window).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
+beyond its first window; `GROUPED_DECODE_X_ROUTES`: the routes of formats the first table has no owner for; `sibling_decode_routes`
+reads all three).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
 is not routed here leaves every member on the routes it had.  `SiblingGroup.forward_batched` (vptq_amd/layers/vqlinear.py) and
 `prepare_model` decide through it.
 """
@@ -197,6 +199,84 @@ def gemm_gatherw_grouped_tokens(vector_len: int, num_centroids: int, num_res_cen
                  if gemm_gatherw_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
 
 
+# WHICH groups of the large-codebook formats `vptq_quant_gemm_gatherx` serves (vector length 8 / 16, 16384 ... 65536 main centroids, any
+# residual codebook but gemm_gather's three formats: v16-k65536-65536 / -32768 / -1024 / -0, v8-k65536-4096, v8-k32768-0, ...) take
+# `vptq_quant_gemm_gatherx_grouped` (gemm_gatherx_grouped.hip: gemm_gatherx's row-group body behind gemm_gather_grouped's member
+# walk), 5 - 16 tokens (1 - 4 tokens are `SiblingGroup.forward` / `forward_sliced`'s; there is no wide kernel for these formats, so 17 -
+# 48 tokens keep the members' routes).  Without it every member goes out alone: gemm_gatherx, gemm_gather_px (a permute launch, then
+# gemm_gatherx), gemv_gatherx or vptq_dequant + a dense GEMM, whichever `BATCHED_DECODE_ROUTES` gives a layer of its format and size.
+# A cell is the wide group's plus the format: (vector length, main centroids, residual centroids, has_perm, member count, least TOTAL
+# index elements of the group = the sum of vector-rows x columns over its members, most total index elements or None, least tokens,
+# most tokens); has_perm as above.  Routed by the rule of the tables above: the grouped launch beats the SUM of what the members take
+# without it by more than the larger of 5 % and three times the larger run-to-run spread, in every measured cell of the region, in
+# both dtypes; a region reaches from its smallest to its largest measured group and no further; the routed token counts of a group
+# are one interval; no cell lies under GEMM_GATHERX_GROUPED_MIN_ELEMENTS (2 M total index elements).
+# tools/gemm_gatherx_grouped_bench.py writes the table.  VPTQ_GEMM_GATHERX_GROUPED=1 / 0 (with VPTQ_TUNING=1): every group of the
+# kernel's formats from 5 to 16 tokens / none.
+#
+# profiles/r34/table.md, profiles/r34/README.md (one MI355X, fp16 and bf16, q / k / v and gate / up of the 8B and 70B shapes = 1.5 M, 5 M,
+# 7 M and 28 M total index elements for v = 16 and 3 M, 10 M, 14 M and 56 M for v = 8, tokens 5 / 8 / 9 / 12 / 16, with one shared
+# permutation and without; 400 cells, every member has the bits of its own entry in every one, 316 win; run-to-run spreads under 1 %
+# in 95 % of the cells, 6.8 % the largest):
+#   q / k / v        every cell wins.  8B shapes 0.28 - 0.76 of the parent (one gemm_gatherx or gemm_gather_px launch plus two gemv_gatherx
+#                    launches or two dense routes; v16-k65536-65536: three of them), 70B shapes 0.40 - 0.89 - but v16-k65536-65536
+#                    without a permutation is level there from 9 tokens (0.99 - 1.07).  The 8B q / k / v of v = 16 (1.5 M elements)
+#                    lies under the floor and keeps its routes
+#   gate / up        8B shapes: v16-k65536-0 / -1024 with a permutation 0.22 - 0.46 (the parent is the in-kernel permuted gemm_gatherx:
+#                    7 M elements of v = 16 are under px's floor), without 0.84 - 0.93; v8-k32768-0 and v8-k65536-4096 0.78 - 0.90 (-4096
+#                    in fp16 without a permutation not by the rule at 12 tokens); v16-k65536-65536 0.57 - 0.82 with a permutation, without
+#                    only at 5 - 8 tokens (0.74 - 0.75; 1.04 - 1.10 from 9: the dense routes are faster).  70B shapes: level with two
+#                    launches (0.97 - 1.11) except v16-k65536-65536 (with a permutation 0.56 - 0.68; without 0.85 - 0.93 up to 12
+#                    tokens) and v8-k65536-4096 in bf16 alone (0.88 - 0.90; fp16 0.98 - 1.00: not routed)
+# A region reaches from its smallest to its largest MEASURED group of its member count (or is one of the two alone) and no further.
+_GEMM_GATHERX_GROUPED_CELLS = (
+    (16, 65536, 0, True, 3, 5 << 20, 5 << 20, 5, 16), (16, 65536, 0, False, 3, 5 << 20, 5 << 20, 5, 16),
+    (16, 65536, 0, True, 2, 7 << 20, 7 << 20, 5, 16), (16, 65536, 0, False, 2, 7 << 20, 7 << 20, 5, 16),
+    (16, 65536, 1024, True, 3, 5 << 20, 5 << 20, 5, 16), (16, 65536, 1024, False, 3, 5 << 20, 5 << 20, 5, 16),
+    (16, 65536, 1024, True, 2, 7 << 20, 7 << 20, 5, 16), (16, 65536, 1024, False, 2, 7 << 20, 7 << 20, 5, 16),
+    (16, 65536, 65536, True, 3, 5 << 20, 5 << 20, 5, 16), (16, 65536, 65536, False, 3, 5 << 20, 5 << 20, 5, 8),
+    (16, 65536, 65536, True, 2, 7 << 20, 28 << 20, 5, 16), (16, 65536, 65536, False, 2, 7 << 20, 28 << 20, 5, 8),
+    (16, 65536, 65536, False, 2, 28 << 20, 28 << 20, 5, 12),
+    (8, 32768, 0, True, 3, 3 << 20, 10 << 20, 5, 16), (8, 32768, 0, False, 3, 3 << 20, 10 << 20, 5, 16),
+    (8, 32768, 0, True, 2, 14 << 20, 14 << 20, 5, 16), (8, 32768, 0, False, 2, 14 << 20, 14 << 20, 5, 16),
+    (8, 65536, 4096, True, 3, 3 << 20, 10 << 20, 5, 16), (8, 65536, 4096, False, 3, 3 << 20, 10 << 20, 5, 16),
+    (8, 65536, 4096, True, 2, 14 << 20, 14 << 20, 5, 16), (8, 65536, 4096, False, 2, 14 << 20, 14 << 20, 5, 9))
+GEMM_GATHERX_GROUPED_MIN_TOKENS, GEMM_GATHERX_GROUPED_MAX_TOKENS = 5, 16
+GEMM_GATHERX_GROUPED_MIN_ELEMENTS = 2 << 20
+GEMM_GATHERX_GROUPED_MAX_MEMBERS = 4
+_GEMM_GATHERX_GROUPED_MODE = (B.tune_env("VPTQ_GEMM_GATHERX_GROUPED", "auto") or "auto").strip().lower()
+
+
+def gemm_gatherx_grouped_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                               in_features: int, tokens: int, has_perm: Optional[bool]) -> bool:
+    """does a group of sibling layers of this format (shared by its members) with these output widths take
+    `vptq_quant_gemm_gatherx_grouped` for `tokens` tokens?  has_perm: True - every member has a column permutation, False - none,
+    None - some.  Pure: no device, no library (whether the library serves the group is `vptq_quant_gemm_gatherx_grouped_supported`'s
+    answer).  Never for the formats `gemm_gather_grouped_route` owns or the canonical format: a group has one route."""
+    if _GEMM_GATHERX_GROUPED_MODE in ("0", "off") or not GEMM_GATHERX_GROUPED_MIN_TOKENS <= tokens <= GEMM_GATHERX_GROUPED_MAX_TOKENS:
+        return False
+    n = len(out_features_tuple)
+    if not 2 <= n <= GEMM_GATHERX_GROUPED_MAX_MEMBERS or in_features % 8 or \
+            _batched_decode_entry(vector_len, num_centroids, num_res_centroids) != "vptq_quant_gemm_gatherx":
+        return False
+    if _GEMM_GATHERX_GROUPED_MODE in ("1", "on"):
+        return True
+    if has_perm is None:
+        return False
+    n_el = sum((o + vector_len - 1) // vector_len for o in out_features_tuple) * in_features
+    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and perm == has_perm and members == n and
+               n_el >= max(min_el, GEMM_GATHERX_GROUPED_MIN_ELEMENTS) and (max_el is None or n_el <= max_el) and
+               min_tok <= tokens <= max_tok for v, k, kr, perm, members, min_el, max_el, min_tok, max_tok in _GEMM_GATHERX_GROUPED_CELLS)
+
+
+def gemm_gatherx_grouped_tokens(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                in_features: int, has_perm: Optional[bool]) -> tuple:
+    """the token counts the route function gives to the grouped launch for this group, ascending (possibly none): `prepare_model`
+    sizes the stream's workspace to the largest"""
+    return tuple(t for t in range(GEMM_GATHERX_GROUPED_MIN_TOKENS, GEMM_GATHERX_GROUPED_MAX_TOKENS + 1)
+                 if gemm_gatherx_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
+
+
 class GroupedDecodeRoute(NamedTuple):
     """what differs between the group routes; everything else is one code path in `SiblingGroup` (a third route is a record and a
     route function).  `route` and `tokens` take the group's static configuration as `SiblingGroup._batched_static` states it:
@@ -251,3 +331,24 @@ def grouped_decode_routes(vector_len: int, num_centroids: int, num_res_centroids
     if first is None:
         return ()
     return (first,) + tuple(r for r in GROUPED_DECODE_WIDE_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))
+
+
+# the routes of formats `GROUPED_DECODE_ROUTES` has no owner for: gemm_gatherx's formats, 5 - 16 tokens.  (A table of its own: the two
+# tables above and their readers keep every answer they gave before these formats had a group route.)  The window lies inside
+# GROUPED_DECODE_MIN_TOKENS ... GROUPED_DECODE_MAX_TOKENS, the guard callers already apply.
+GROUPED_DECODE_X_ROUTES = (
+    GroupedDecodeRoute("vptq_quant_gemm_gatherx_grouped", lambda v, k, kr: _batched_decode_entry(v, k, kr) == "vptq_quant_gemm_gatherx",
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_gatherx_grouped_route(v, k, kr, outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_gatherx_grouped_tokens(v, k, kr, outs, width, has_perm),
+                       GEMM_GATHERX_GROUPED_MIN_TOKENS, GEMM_GATHERX_GROUPED_MAX_TOKENS, B.GEMV_FORCE_GENERIC),
+)
+
+
+def sibling_decode_routes(vector_len: int, num_centroids: int, num_res_centroids: int) -> tuple:
+    """every group route a `SiblingGroup` of this format can take, in window order: `grouped_decode_routes` where that is non-empty,
+    else the records of `GROUPED_DECODE_X_ROUTES` that own the format (possibly none at all).  The formats of the tables are
+    disjoint.  No knob is read."""
+    routes = grouped_decode_routes(vector_len, num_centroids, num_res_centroids)
+    if routes:
+        return routes
+    return tuple(r for r in GROUPED_DECODE_X_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))

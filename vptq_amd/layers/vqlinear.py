@@ -43,7 +43,7 @@ from vptq_amd.batched_decode import (  # noqa: F401
 # route (the knobs and cells are read there, at call time); the guard's window is the union of the routes' windows
 from vptq_amd.grouped_decode import (  # noqa: F401
     GROUPED_DECODE_MAX_TOKENS, GROUPED_DECODE_MIN_TOKENS, gemm_gather_grouped_route, gemm_gather_grouped_tokens, gemm_k256_grouped_route,
-    gemm_k256_grouped_tokens, grouped_decode_route, grouped_decode_routes)
+    gemm_k256_grouped_tokens, grouped_decode_route, grouped_decode_routes, sibling_decode_routes)
 # the sliced-layout rules (1 - 4 tokens) live in vptq_amd/sliced_routes.py and are read through the module (`R.exact_route_is_large`:
 # one monkeypatch changes every reader); only import-time constants that nothing assigns to are imported by name, for the hot guard
 from vptq_amd import sliced_routes as R
@@ -137,9 +137,9 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
     the library's builder, layer by layer) instead of inside the first decode step, and every layer has its one-token workspace for
     `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  The stream's `B.gemv_workspace` is grown to
     the largest x[perm] copy (`vptq_quant_gemm_gather_px_workspace_bytes` at 48 tokens) of the permuted layers `gemm_gather_px_route`
-    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_gatherw_grouped` / `vptq_quant_gemm_k256_grouped`
-    need for the linked sibling groups their routes (`gemm_gather_grouped_route` / `gemm_gatherw_grouped_route` /
-    `gemm_k256_grouped_route`) route (the largest need over a format's records, each at its largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
+    routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_gatherw_grouped` / `vptq_quant_gemm_gatherx_grouped` /
+    `vptq_quant_gemm_k256_grouped` need for the linked sibling groups their routes (`gemm_gather_grouped_route` /
+    `gemm_gatherw_grouped_route` / `gemm_gatherx_grouped_route` / `gemm_k256_grouped_route`) route (the largest need over a format's records, each at its largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
     "built": layers with a layout, "bytes", "seconds"}."""
     rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
     px = {}   # device index -> (device, most workspace bytes of its routed permuted layers)
@@ -237,8 +237,9 @@ class SiblingGroup:
         """what the group's batched-decode route is asked with, from the members' static configuration: (vector length, main
         centroids, residual centroids, output widths, input width, has_perm: True - every member has a permutation, False - none,
         None - some), or None where the members do not share format and width or are not one-codebook layers with scale and bias.
-        `_batched_route` is the record of `GROUPED_DECODE_ROUTES` (vptq_amd/grouped_decode.py) whose kernel has that format, or None;
-        with a token count, the record of the format (`grouped_decode_routes`: the owner, then its wide routes) whose window holds it."""
+        `_batched_route` is the first record of the format's group routes (`sibling_decode_routes`, vptq_amd/grouped_decode.py: the
+        owner in `GROUPED_DECODE_ROUTES`, then its wide routes; for gemm_gatherx's formats the record of `GROUPED_DECODE_X_ROUTES`), or
+        None; with a token count, the record of the format whose window holds it."""
         st = self.__dict__.get("_bstatic")
         if st is None:
             ms = self.members
@@ -250,8 +251,8 @@ class SiblingGroup:
                 v, k, kr, width = next(iter(fmt))
                 st = ((v, k, kr, tuple(m.out_features for m in ms), width, perms.pop() if len(perms) == 1 else None),)
             self._bstatic = st
-            self._broute = grouped_decode_route(*st[0][:3]) if st[0] is not None else None
-            self._broutes = grouped_decode_routes(*st[0][:3]) if st[0] is not None else ()
+            self._broutes = sibling_decode_routes(*st[0][:3]) if st[0] is not None else ()
+            self._broute = self._broutes[0] if self._broutes else None
         return st[0]
 
     def _batched_route(self, tokens=None):
@@ -265,7 +266,8 @@ class SiblingGroup:
         return None
 
     def _batched_plan(self, r=None):
-        """the descriptor array the group route's entry (`vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_k256_grouped`) is called
+        """the descriptor array the group route's entry (`vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_gatherw_grouped` / `vptq_quant_gemm_gatherx_grouped` /
+        `vptq_quant_gemm_k256_grouped`) is called
         with, (descs, caches), decided once per entry (r: a record of the format, default its first) and per set of descriptor generations - or None: no route has the format, a compacted member, a library without the entry, members on several devices or of
         several dtypes, a group the library does not serve.  Members whose `perm` tensors are `torch.equal` get ONE perm pointer in
         their descriptor copies (the first such member's): the entry then gathers x once for them.  Not decided inside a stream
@@ -326,7 +328,7 @@ class SiblingGroup:
     def forward_batched(self, layer, x, tokens):
         """5 - 48 tokens of large-codebook and of canonical-format siblings: ONE launch for the group (the entry of the group's record
         whose window holds the token count: `vptq_quant_gemm_gather_grouped` up to 16 tokens / `vptq_quant_gemm_gatherw_grouped` from 17 /
-        `vptq_quant_gemm_k256_grouped`, one x gather per distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
+        `vptq_quant_gemm_gatherx_grouped` (gemm_gatherx's formats, up to 16 tokens) / `vptq_quant_gemm_k256_grouped`, one x gather per distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
         the first member called launches, the others pick their output up when they are called with the very same tensor at the
         same version.  None = not this group's route (no route has the format, the route function says no, a compacted member,
         mixed formats or dtypes, a group the library does not serve, a member whose arithmetic is not the reference's roundings where

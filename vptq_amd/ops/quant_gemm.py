@@ -21,7 +21,7 @@ from torch.nn import functional as F
 from vptq_amd import _backend as B
 from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -411,6 +411,24 @@ def quant_gemm_gatherw_grouped(x: torch.Tensor, descs, out_features_list, out_f3
     where a stream capture is in progress and the workspace is too small (nothing is allocated or launched then; `prepare_model`
     sizes it beforehand)."""
     return _grouped_launch("vptq_quant_gemm_gatherw_grouped", x, descs, out_features_list, out_f32)
+
+
+def quant_gemm_gatherx_grouped(x: torch.Tensor, descs, out_features_list, out_f32: bool = False):
+    """[y_m = x @ W_m^T + bias_m] for 1 - 16 tokens of 2 - 4 sibling layers `quant_gemm_gatherx` serves (one dtype, input width and
+    format: vector length, main and residual codebook size; with or without a column permutation) in ONE launch
+    (`vptq_quant_gemm_gatherx_grouped`, gemm_gatherx_grouped.hip) behind one x[:, perm] gather per DISTINCT `perm` pointer of the
+    members, written into this stream's workspace (`B.gemv_workspace`).  Every y_m has the bits of the member's own entry
+    (`quant_gemm_gather_px` with a permutation, `quant_gemm_gatherx` without).  `descs` = a ctypes array (or a sequence) of LayerDesc
+    of a group `vptq_quant_gemm_gatherx_grouped_supported` accepts; out_f32: the un-rounded fp32 sums.  Returns the list of outputs,
+    or None where the library does not serve the group or where a stream capture is in progress and the workspace is too small
+    (nothing is allocated or launched then; `prepare_model` sizes it beforehand)."""
+    import ctypes as C
+    n = len(out_features_list)
+    if not isinstance(descs, C.Array):
+        descs = (B.LayerDesc * n)(*descs)
+    if not B.lib().vptq_quant_gemm_gatherx_grouped_supported(descs, n, x.numel() // x.shape[-1]):
+        return None
+    return _grouped_launch("vptq_quant_gemm_gatherx_grouped", x, descs, out_features_list, out_f32)
 
 
 def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
