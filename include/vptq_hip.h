@@ -651,6 +651,42 @@ VPTQ_API int vptq_quant_gemm_gatherx_supported(const VptqLayerDesc* desc, int to
 VPTQ_API int vptq_quant_gemm_gatherx(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherx_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of vptq_quant_gemm_gatherx's layers for 17 - 48 tokens in ONE launch (gemm_gatherxw_kernel in gemm_gatherxw.hip; added
+ * within ABI 12; present when the symbols are).  The layers vptq_quant_gemm_gatherx serves, with or without a column permutation,
+ * with the tokens as tb = ceil(tokens / 16) blocks of the M dimension of a 16x16x32 MFMA: the index windows are read, the entries
+ * gathered and the weights rebuilt once for all blocks, where 17+ tokens of these formats had no kernel (vptq_dequant + a dense
+ * GEMM).  The kernel has no form with a permutation: for a layer with one, xp[t][c] = x[t][perm[c]] is written once into the
+ * workspace (permute_x_tokens_kernel, vptq_quant_gemm_gather_px's) and the kernel runs over xp, scale_permuted and bias_permuted; a layer
+ * without one ignores the workspace, which may be NULL / 0.  Both launches go to `stream`; nothing is allocated: graph-capturable.
+ * The reference's roundings per weight (bit-identical to vptq_dequant's W), fp32 sums added in a fixed order, one rounding of the
+ * output, the output bias added in fp32; no atomics.
+ * BIT CONTRACT: the order of the sums is gemm_gatherx_kernel's and does not depend on the token count or on a token's slot: a
+ * token's output bits are the same in every slot of every batch, and equal those vptq_quant_gemm_gatherx gives that token in a
+ * launch of up to 16 (vptq_quant_gemm_gather_px for a layer with a permutation).
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags: VPTQ_GEMV_OUT_F32 stores the fp32 sums (y is float32);
+ *   VPTQ_GEMV_FAST_MATH / _EXACT / _SELECTIVE are accepted and change nothing.
+ * vptq_quant_gemm_gatherxw_supported: 1 where 17 <= tokens <= 48 and vptq_quant_gemm_gatherx_supported(desc, 16) is 1, else 0.
+ * vptq_quant_gemm_gatherxw_workspace_bytes: tokens * group_size * 2 rounded up to 256 for a layer with a permutation; 0 without one
+ *   and where vptq_quant_gemm_gatherxw_supported answers 0.
+ * vptq_quant_gemm_gatherxw: NULL desc / x / y VPTQ_E_NULL; tokens outside [17, 48] VPTQ_E_TOKENS (checked before the layer); a layer
+ *   it does not serve, an x that is not 16-byte aligned and, for a layer with a permutation, a NULL workspace, fewer workspace_bytes
+ *   than the query answers or a workspace that is not 16-byte aligned VPTQ_E_UNSUPPORTED, with a vptq_last_error text; nothing is
+ *   launched then.
+ * vptq_quant_gemm_gatherxw_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   [permute_x_tokens g=N tok=N grid=XxY tpt=4 | ]gemm_gatherxw dt=f16|bf16 v=8|16 ib=N rb=N res=none|lds|l2 tok=N tb=2|3 tiles=N wgcu=N rgs=N
+ *       the permute launch as vptq_quant_gemm_gather_px_instance prints it, only for a layer with a permutation; ib ... rgs as
+ *       vptq_quant_gemm_gatherx_instance's, tb the token blocks.  Returns as vptq_quant_gemm_gather_instance does.
+ * vptq_quant_gemm_gatherx keeps its [1, 16] window and vptq_quant_gemm_gather_px still refuses these layers from 17 tokens.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: the layer as vptq_quant_gemm_gatherx takes it (indices, centroids, res_centroids 16 bytes and weight_scale, weight_bias,
+ * perm, scale_permuted, bias_permuted 4 bytes: part of "supported"); x 16 bytes and the workspace 16 bytes (VPTQ_E_UNSUPPORTED); y and
+ * bias element-aligned. */
+VPTQ_API int vptq_quant_gemm_gatherxw_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API size_t vptq_quant_gemm_gatherxw_workspace_bytes(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gatherxw(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gatherxw_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* Batched decode of the canonical format for 17 - 64 tokens in ONE launch (gemm_k256w_kernel in gemm_k256.hip; added within ABI 12;
  * present when the symbols are).  The layers vptq_quant_gemv serves with gemm_k256_kernel - v = 8, 256 main + 256 residual centroids,
  * one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and bias_permuted), group_size ==

@@ -165,6 +165,12 @@ EXPORTS = {
     "vptq_quant_gemm_gatherx_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gatherx": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),
     "vptq_quant_gemm_gatherx_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 17 - 48 tokens of vptq_quant_gemm_gatherx's layers in one launch, a permuted layer's x[perm] written into the
+    # workspace first (gemm_gatherxw.hip): query, workspace query, call, instance text
+    "vptq_quant_gemm_gatherxw_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gatherxw_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gatherxw": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gatherxw_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     # (added within ABI 12) 17 - 64 tokens of the canonical format in one launch (gemm_k256w_kernel, gemm_k256.hip)
     "vptq_quant_gemm_k256w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_k256w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),

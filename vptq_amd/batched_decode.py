@@ -3,7 +3,9 @@
 Pure rules - no device, no tensors: the five route functions with their knobs and measured cells, one ordered table of what differs
 between the routes (`BATCHED_DECODE_ROUTES`) and the two functions that read it, the static `batched_decode_routes` (per layer) and
 the per-call `batched_decode_takes`.  `VQuantLinear.forward` and `ops.quant_gemm` both decide through them.  A new route is a
-record in the table, a route function and a knob.
+record in the table, a route function and a knob.  Behind the first table stands `BATCHED_DECODE_WIDE_ROUTES` (read by
+`batched_decode_wide_routes`, walked after the first table's routes): a format's route beyond its first window - `gemm_gatherxw_route`,
+17 - 48 tokens of gemm_gatherx's formats.
 """
 from __future__ import annotations
 
@@ -203,6 +205,62 @@ def gemm_gather_px_route(vector_len: int, num_centroids: int, num_res_centroids:
                min_tok <= tokens <= max_tok for v, k, kr, min_el, min_tok, max_tok in _GEMM_GATHER_PX_CELLS)
 
 
+# WHICH (format, shape, token count) of gemm_gatherx's formats (v = 8 / 16, 16384 ... 65536 main centroids, any residual codebook -
+# the formats for which `_batched_decode_entry` says `vptq_quant_gemm_gatherx`) take `vptq_quant_gemm_gatherxw` - 17 - 48 tokens in
+# ONE launch (gemm_gatherxw_kernel, gemm_gatherxw.hip; a layer with a column permutation: x[perm] written once into the stream's
+# workspace in front of it) - in place of the dense route they had, permuted or not: the one rule, read by `VQuantLinear.forward` and
+# `ops.quant_gemm`.  A cell is (vector length, main centroids, residual centroids, has a permutation, least index elements = vector-rows
+# x columns, least tokens, most tokens), routed by the rule above `_GEMM_GATHER_CELLS` (beats its parent by more than the larger of
+# 5 % and three times the larger run-to-run spread, in every measured cell of the region, in both dtypes; the routed token counts of a
+# layer are one interval; no cell lies under GEMM_GATHERW_MIN_ELEMENTS, 4 M index elements); tools/gemm_gatherxw_bench.py writes the
+# table.  VPTQ_GEMM_GATHERXW=1 / 0 (with VPTQ_TUNING=1): every supported layer from 17 to 48 tokens / none.
+#
+# profiles/r35/table.md, profiles/r35/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672 and 28672 x 8192, tokens 17 / 24 /
+# 32 / 33 / 40 / 48, with and without a permutation; 864 cells, the 16-token entry's bits in every one, 516 win; spreads over 3 % in 17
+# cells).  v = 16 layers have 4 M index elements at 8192 x 8192 and 14 M at 8192 x 28672 / 28672 x 8192 (their 14336-wide layers, 3.5 M,
+# lie under the floor); v = 8 layers 7 M (14336-wide), 8 M and 28 M.  A cell's region is every measured layer from its size up:
+#   WITH a permutation (the parent gathers W's columns while it rebuilds it, and x[perm] costs 3 - 7 us here): v16-k65536-1024 /
+#     -32768 / -65536 win in every cell from 4 M up (0.46 - 0.94); v16-k65536-0 at 4 M only at 17 - 24 tokens (0.74 - 0.88; 0.91 - 1.21
+#     from 32), from 14 M everywhere (0.54 - 0.91); v8-k32768-0 from 7 M at 17 - 24 (0.57 - 0.87; 4096 x 14336 loses from 32: 1.01 -
+#     1.23), from 8 M everywhere (0.45 - 0.94); v8-k65536-4096 from 7 M up to 33 tokens (0.55 - 0.93; 4096 x 14336 at 40: 0.93 / 0.96),
+#     from 8 M everywhere (0.47 - 0.78)
+#   WITHOUT one: v16-k65536-0 only from 14 M, 17 - 40 tokens (0.68 - 0.94; 8192 x 28672 at 48: 1.02 / 1.05); v16-k65536-1024 from 4 M at
+#     17 - 24 (0.82 - 0.89), from 14 M at 17 - 40 (0.64 - 0.93); v16-k65536-32768 from 14 M at 17 - 24 (0.78 - 0.90); v16-k65536-65536
+#     nowhere (8192 x 8192: 1.08 - 1.37; 28672 x 8192: 0.93 - 1.11); v8-k32768-0 from 7 M at 17 tokens (0.82 - 0.89), from 8 M at 17 - 24
+#     (0.63 - 0.88), from 28 M at 17 - 40 (0.63 - 0.94); v8-k65536-4096 from 8 M at 17 tokens (4096 x 14336 does not win: 0.93 / 0.97),
+#     from 28 M at 17 - 24 (0.80 - 0.87)
+# Formats that were not measured (v16-k65536-256 / -64, v8-k65536-4, v8-k16384-0) are not routed.
+_GEMM_GATHERXW_CELLS = (
+    (16, 65536, 0, 1, 4 << 20, 17, 24), (16, 65536, 0, 1, 14 << 20, 17, 48), (16, 65536, 0, 0, 14 << 20, 17, 40),
+    (16, 65536, 1024, 1, 4 << 20, 17, 48), (16, 65536, 1024, 0, 4 << 20, 17, 24), (16, 65536, 1024, 0, 14 << 20, 17, 40),
+    (16, 65536, 32768, 1, 4 << 20, 17, 48), (16, 65536, 32768, 0, 14 << 20, 17, 24),
+    (16, 65536, 65536, 1, 4 << 20, 17, 48),
+    (8, 32768, 0, 1, 7 << 20, 17, 24), (8, 32768, 0, 1, 8 << 20, 17, 48),
+    (8, 32768, 0, 0, 7 << 20, 17, 17), (8, 32768, 0, 0, 8 << 20, 17, 24), (8, 32768, 0, 0, 28 << 20, 17, 40),
+    (8, 65536, 4096, 1, 7 << 20, 17, 33), (8, 65536, 4096, 1, 8 << 20, 17, 48),
+    (8, 65536, 4096, 0, 8 << 20, 17, 17), (8, 65536, 4096, 0, 28 << 20, 17, 24),
+)
+GEMM_GATHERXW_MIN_TOKENS, GEMM_GATHERXW_MAX_TOKENS = 17, 48
+_GEMM_GATHERXW_MODE = (B.tune_env("VPTQ_GEMM_GATHERXW", "auto") or "auto").strip().lower()
+
+
+def gemm_gatherxw_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int,
+                        has_perm: Optional[bool] = None) -> bool:
+    """does a layer of this format and shape take `vptq_quant_gemm_gatherxw` for `tokens` tokens?  has_perm: whether the layer has a
+    column permutation (the cells are measured per state); None: a layer of either state, i.e. whether ANY cell takes it - what a
+    caller that sizes a workspace asks.  Pure: no device, no library (whether the library serves the layer is
+    `vptq_quant_gemm_gatherxw_supported`'s answer).  Never for the formats `gemm_gather_route` owns."""
+    if _GEMM_GATHERXW_MODE in ("0", "off") or not GEMM_GATHERXW_MIN_TOKENS <= tokens <= GEMM_GATHERXW_MAX_TOKENS or in_features % 8 or \
+            _batched_decode_entry(vector_len, num_centroids, num_res_centroids) != "vptq_quant_gemm_gatherx":
+        return False
+    if _GEMM_GATHERXW_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and (has_perm is None or bool(p) == bool(has_perm)) and
+               n_el >= max(min_el, GEMM_GATHERW_MIN_ELEMENTS) and min_tok <= tokens <= max_tok
+               for v, k, kr, p, min_el, min_tok, max_tok in _GEMM_GATHERXW_CELLS)
+
+
 class BatchedDecodeRoute(NamedTuple):
     """what differs between the batched-decode routes; everything else is one code path in both callers"""
     entry: str                    # the library entry (`entry + "_supported"`: does the library serve this descriptor?)
@@ -215,6 +273,7 @@ class BatchedDecodeRoute(NamedTuple):
     off_flags: int                # launch flags that switch the route off
     exact_only: bool = False      # the kernel has the reference's roundings only: the CALLER asks the layer's arithmetic, last (it may cost a read-back)
     workspace: bool = False       # the entry takes (workspace, workspace_bytes) in front of the stream (`entry + "_workspace_bytes"` sizes it)
+    perm_cells: bool = False      # the route function takes whether the layer has a permutation as a seventh argument: cells per state
 
 
 def _entry_is(*entries):
@@ -239,6 +298,14 @@ BATCHED_DECODE_ROUTES = (
     BatchedDecodeRoute("vptq_quant_gemm_gatherw", GEMM_GATHERW_MIN_TOKENS, GEMM_GATHERW_MAX_TOKENS, _entry_is("vptq_quant_gemm_gather"),
                        gemm_gatherw_route, "_GEMM_GATHERW_MODE", False, B.GEMV_FORCE_GENERIC),
 )
+# The single-layer counterpart of `GROUPED_DECODE_WIDE_ROUTES`: routes a caller walks AFTER those of `BATCHED_DECODE_ROUTES`, in a table
+# of their own (the first table's records are what they were).  gemm_gatherxw owns gemm_gatherx's formats from the 17th token on, where
+# the only first-table route of those formats (px) ends at 16: no call is taken from a route above.  A permuted layer and a plain one
+# take the same entry (perm=None), which gathers x[perm] into the workspace itself.
+BATCHED_DECODE_WIDE_ROUTES = (
+    BatchedDecodeRoute("vptq_quant_gemm_gatherxw", GEMM_GATHERXW_MIN_TOKENS, GEMM_GATHERXW_MAX_TOKENS, _entry_is("vptq_quant_gemm_gatherx"),
+                       gemm_gatherxw_route, "_GEMM_GATHERXW_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True),
+)
 BATCHED_DECODE_MIN_TOKENS = min(r.min_tokens for r in BATCHED_DECODE_ROUTES)   # the union of the windows: what a caller guards with
 BATCHED_DECODE_MAX_TOKENS = max(r.max_tokens for r in BATCHED_DECODE_ROUTES)
 
@@ -247,10 +314,20 @@ def batched_decode_routes(vector_len: int, num_centroids: int, num_res_centroids
                           has_perm: bool) -> tuple:
     """the routes that can EVER serve a layer of this static configuration, in priority order (possibly none): one codebook, no
     outliers, scale and bias, the format the route's, a permutation where the route takes nothing else.  No knob is read."""
+    return _static_routes(BATCHED_DECODE_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm)
+
+
+def batched_decode_wide_routes(vector_len: int, num_centroids: int, num_res_centroids: int, num_codebooks: int, outliers: bool, norm: bool,
+                               has_perm: bool) -> tuple:
+    """`batched_decode_routes` over `BATCHED_DECODE_WIDE_ROUTES`: the same static filters; a caller walks these after the first
+    table's."""
+    return _static_routes(BATCHED_DECODE_WIDE_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm)
+
+
+def _static_routes(table, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm) -> tuple:
     if num_codebooks != 1 or outliers or not norm:
         return ()
-    return tuple(r for r in BATCHED_DECODE_ROUTES
-                 if r.owns(vector_len, num_centroids, num_res_centroids) and (has_perm or r.perm is not True))
+    return tuple(r for r in table if r.owns(vector_len, num_centroids, num_res_centroids) and (has_perm or r.perm is not True))
 
 
 def batched_decode_takes(route, vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int,
@@ -262,5 +339,6 @@ def batched_decode_takes(route, vector_len: int, num_centroids: int, num_res_cen
         return False
     if route.perm is not None and route.perm != has_perm and (route.perm or globals()[route.knob] not in ("1", "on")):
         return False
-    return route.route(vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
+    args = (vector_len, num_centroids, num_res_centroids, out_features, in_features, tokens)
+    return route.route(*args, has_perm) if route.perm_cells else route.route(*args)
 

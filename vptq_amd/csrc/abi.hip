@@ -1349,6 +1349,62 @@ int vptq_quant_gemm_gather_px_instance(const VptqLayerDesc* d, int tokens, int, 
   return instance_done(t);
 }
 
+// ---- gemm_gatherxw.hip (added within ABI 12): 17 - 48 tokens of vptq_quant_gemm_gatherx's layers in one launch of
+// gemm_gatherxw_kernel, which has no form with a permutation: a permuted layer's x[perm] is written into the workspace first
+// (gemm_gather_px.hip's permute launch) and the kernel runs on gemm_gather_px_plain(d).  vptq_quant_gemm_gather_px is what it was
+// and does not come here.
+static int gatherxw_validate(const VptqLayerDesc* d, int tokens) {
+  if (tokens < 17 || tokens > 48) return fail(VPTQ_E_TOKENS, "tokens %d outside [17, 48]", tokens);
+  if (!vptq::gemm_gatherxw_eligible(*d, tokens)) return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherxw serves %s", kGemmGatherX.serves);
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gatherxw_supported(const VptqLayerDesc* d, int tokens) {
+  return validate_layer(d) == VPTQ_OK && vptq::gemm_gatherxw_eligible(*d, tokens) ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gatherxw_workspace_bytes(const VptqLayerDesc* d, int tokens) {
+  if (!vptq_quant_gemm_gatherxw_supported(d, tokens)) return 0;
+  return vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+}
+
+int vptq_quant_gemm_gatherxw(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  if (const int rc = gatherxw_validate(d, tokens)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherxw: x must be 16-byte aligned");
+  const size_t need = vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+  if (need == 0) {   // no permutation: the kernel alone, the workspace is not touched
+    const hipError_t e = vptq::launch_gemm_gatherxw(*d, x, y, tokens, out_f32, st);
+    return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gatherxw launch");
+  }
+  if (!workspace || workspace_bytes < need) return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherxw: workspace of %zu bytes needed", need);
+  if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "gemm_gatherxw: the workspace must be 16-byte aligned");
+  hipError_t e = vptq::launch_permute_x_tokens(*d, x, workspace, tokens, st);
+  if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  e = vptq::launch_gemm_gatherxw(vptq::gemm_gather_px_plain(*d), workspace, y, tokens, out_f32, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gatherxw launch");
+}
+
+int vptq_quant_gemm_gatherxw_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  if (const int rc = gatherxw_validate(d, tokens)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const vptq::GemmGatherPxDecision X = vptq::gemm_gather_px_decide(*d, tokens);
+  if (X.perm) t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d | ", X.g, X.tok, X.grid_x, X.grid_y, X.tpt);
+  const vptq::GemmGatherXWDecision D = vptq::gemm_gatherxw_decide(vptq::gemm_gather_px_plain(*d), tokens);
+  t.add("gemm_gatherxw dt=%s v=%d ib=%d rb=%d res=%s tok=%d tb=%d tiles=%d wgcu=%d rgs=%d", dt_text(D.f16), D.v, D.ib, D.rb,
+        D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", D.tok, D.tb, D.tiles, D.wgcu, D.rgs);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // ---- gemm_gather.hip's grouped launch (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gather, 1 - 16 tokens, in ONE
 // launch of gemm_gather_grouped_kernel, behind one permute launch per DISTINCT perm pointer of the members.
 // What a grouped call IS, decided once for the workspace query, the launcher and the `_instance`: which xp block a member reads (-1:

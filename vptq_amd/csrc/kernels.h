@@ -267,6 +267,15 @@ GemmGatherXGroupedDecision gemm_gatherx_grouped_decide(const VptqLayerDesc* desc
 hipError_t launch_gemm_gatherx_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
                                        hipStream_t st);
 
+// gemm_gatherxw.hip - gemm_gatherx's layers, 17 - 48 tokens in one launch as tb = 2 / 3 blocks of 16 tokens over gemm_gatherx's tile
+// pipeline (its K-step -> wave mapping and order of sums: a token's bits are the 16-token kernel's); plain form only - a layer with a
+// permutation comes as gemm_gather_px_plain(d), with x[perm] for its x
+bool gemm_gatherxw_eligible(const VptqLayerDesc& d, int tokens);
+// what launch_gemm_gatherxw launches: gemm_gatherxw_kernel<DT, V, RES, TB>; v ... wgcu, n_groups, grid, rgs: gemm_gatherx_decide's
+struct GemmGatherXWDecision { bool f16; int v, ib, rb, res, res_bytes, tok, tb, tiles, lds, wgcu, n_groups, grid, rgs; };
+GemmGatherXWDecision gemm_gatherxw_decide(const VptqLayerDesc& d, int tokens);
+hipError_t launch_gemm_gatherxw(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)
 // - scale_permuted / bias_permuted as scale / bias, no permutation - with x = xp: the bits of the layer's own entry

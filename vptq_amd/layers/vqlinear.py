@@ -37,8 +37,9 @@ from vptq_amd import ops
 # knobs and the cell tables are NOT: tests and tools assign to them, and an alias would keep the old value)
 from vptq_amd.batched_decode import (  # noqa: F401
     BATCHED_DECODE_MAX_TOKENS, BATCHED_DECODE_MIN_TOKENS, GEMM_GATHER_MAX_TOKENS, GEMM_GATHER_PX_MAX_TOKENS, GEMM_GATHER_PX_MIN_TOKENS,
-    GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS, GEMM_K256W_MIN_TOKENS, batched_decode_routes,
-    batched_decode_takes, gemm_gather_px_route, gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_k256w_route)
+    GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_GATHERXW_MAX_TOKENS, GEMM_GATHERXW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS,
+    GEMM_K256W_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_wide_routes, gemm_gather_px_route,
+    gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_gatherxw_route, gemm_k256w_route)
 # the batched-decode rules of a GROUP of siblings live in vptq_amd/grouped_decode.py: `GROUPED_DECODE_ROUTES`, one record per group
 # route (the knobs and cells are read there, at call time); the guard's window is the union of the routes' windows
 from vptq_amd.grouped_decode import (  # noqa: F401
@@ -985,13 +986,15 @@ class VQuantLinear(nn.Module):
         return y
 
     def _batched_decode_routes(self) -> tuple:
-        """the batched-decode routes that can ever serve this layer (`batched_decode_routes` of its static configuration) and whose
-        entry this process's library has: decided once per layer, so that every other layer pays one dict look-up per call"""
+        """the batched-decode routes that can ever serve this layer (`batched_decode_routes` of its static configuration, then
+        `batched_decode_wide_routes`) and whose entry this process's library has: decided once per layer, so that every other layer
+        pays one dict look-up per call"""
         routes = self.__dict__.get("_bd_routes")
         if routes is None:
             lib = B.lib()
-            routes = tuple(r for r in batched_decode_routes(self.vector_len, self.num_centroids, _res_centroids(self), self.num_codebooks,
-                                                            self.enable_outlier, self.enable_norm, bool(self.enable_perm))
+            static = (self.vector_len, self.num_centroids, _res_centroids(self), self.num_codebooks, self.enable_outlier, self.enable_norm,
+                      bool(self.enable_perm))
+            routes = tuple(r for r in batched_decode_routes(*static) + batched_decode_wide_routes(*static)
                            if getattr(lib, r.entry, None) is not None)
             self.__dict__["_bd_routes"] = routes
         return routes
@@ -1038,19 +1041,21 @@ class VQuantLinear(nn.Module):
         return None
 
     def _gemm_gather_px_workspace_bytes(self) -> int:
-        """bytes of stream workspace the largest call the permuted-layer route (`vptq_quant_gemm_gather_px`) can take for this
-        layer needs (`prepare_model` grows the stream's buffer to it); 0: the layer never takes that route"""
+        """bytes of stream workspace the largest call any workspace route of this layer (`vptq_quant_gemm_gather_px`,
+        `vptq_quant_gemm_gatherxw`) can take needs (`prepare_model` grows the stream's buffer to it): the maximum over the routes, each
+        at the most tokens its route function gives it; 0: the layer never takes such a route"""
         if "_compact" not in self.__dict__ and not self._parameters["indices"].is_cuda:
             return 0
-        px = [r for r in self._batched_decode_routes() if r.workspace]
-        if not px:
-            return 0
-        routed = [t for t in range(px[0].min_tokens, px[0].max_tokens + 1)
-                  if px[0].route(self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features, t)]
-        query = getattr(B.lib(), px[0].entry + "_workspace_bytes", None)
-        if not routed or query is None:
-            return 0
-        return int(query(self._descriptor().desc, routed[-1]))
+        need, perm = 0, bool(self.enable_perm)
+        for r in self._batched_decode_routes():
+            query = getattr(B.lib(), r.entry + "_workspace_bytes", None) if r.workspace else None
+            if query is None:
+                continue
+            args = (self.vector_len, self.num_centroids, _res_centroids(self), self.out_features, self.in_features)
+            routed = [t for t in range(r.min_tokens, r.max_tokens + 1) if (r.route(*args, t, perm) if r.perm_cells else r.route(*args, t))]
+            if routed:
+                need = max(need, int(query(self._descriptor().desc, routed[-1])))
+        return need
 
     def _dense_cached(self, x: torch.Tensor) -> torch.Tensor:
         """Many tokens: `vptq_dequant` into a fresh dense W + `F.linear` (the reference's route,

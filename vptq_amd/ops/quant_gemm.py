@@ -19,9 +19,9 @@ import torch
 from torch.nn import functional as F
 
 from vptq_amd import _backend as B
-from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes
+from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_wide_routes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -208,8 +208,9 @@ def quant_gemm(
         # the layer, x is not 16-byte aligned, the layer's arithmetic is not the reference's roundings and the kernel has no other
         # (asked last: it may cost a read-back), or a capture is in progress with too small a workspace.
         kr = num_res_centroids if enable_residual else 0
-        routes = batched_decode_routes(vector_len, num_centroids, kr, num_codebooks, enable_outlier, weight_scale is not None and
-                                       weight_bias is not None, perm is not None) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
+        static = (vector_len, num_centroids, kr, num_codebooks, enable_outlier, weight_scale is not None and weight_bias is not None,
+                  perm is not None)
+        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
         for r in routes:
             if not batched_decode_takes(r, vector_len, num_centroids, kr, out_features, in_features, tokens, _FLAGS, perm is not None) or \
                     x.data_ptr() % 16 or not getattr(B.lib(), r.entry + "_supported")(gdesc, tokens):
@@ -333,6 +334,21 @@ def quant_gemm_gatherx(x: torch.Tensor, desc, out_features: int, out_f32: bool =
     index path for any total width and 32-byte entries; the reference's roundings).  `desc` = a LayerDesc of a layer
     `vptq_quant_gemm_gatherx_supported` accepts; out_f32: the un-rounded fp32 sums."""
     return quant_gemm_batched_launch("vptq_quant_gemm_gatherx", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0))
+
+
+def quant_gemm_gatherxw(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 17 - 48 tokens of a layer `quant_gemm_gatherx` serves (vector length 8 / 16, 16384 ... 65536 main
+    centroids, any residual codebook), with or without a column permutation, in ONE launch (`vptq_quant_gemm_gatherxw`,
+    gemm_gatherxw.hip: 2 / 3 blocks of 16 tokens share one pass over the index windows, gathers and rebuilt tiles; the reference's
+    roundings, a token's bits those of the 16-token entry; replaces dequant + F.linear).  For a layer with a permutation x[:, perm]
+    is written once into this stream's workspace (`B.gemv_workspace`) in front of it.  `desc` = a LayerDesc of a layer
+    `vptq_quant_gemm_gatherxw_supported` accepts; out_f32: the un-rounded fp32 sums.  Raises where a stream capture is in progress
+    and the workspace is too small (`prepare_model` sizes it beforehand)."""
+    y = quant_gemm_batched_launch("vptq_quant_gemm_gatherxw", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True)
+    if y is None:
+        raise RuntimeError("quant_gemm_gatherxw: the stream's workspace is too small and cannot grow during a capture "
+                           "(call it once, or vptq_amd.prepare_model, before capturing)")
+    return y
 
 
 def quant_gemm_gather_px(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
