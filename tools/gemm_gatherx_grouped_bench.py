@@ -13,7 +13,11 @@ median of --reps turns and their spread, (max - min) / median.  A cell "wins" wh
 of 5 % and three times the larger spread of the two.  `bits`: every member has the bits of its own entry on the same descriptor
 (first group of the ring).  One JSON line per cell; --md appends a markdown table, row by row; --budget-s stops before a new group
 once that many seconds have passed (what was measured stays).
-    python tools/gemm_gatherx_grouped_bench.py --md profiles/r34/table.md"""
+    python tools/gemm_gatherx_grouped_bench.py --md profiles/r34/table.md
+--entry gatherxw measures vptq_quant_gemm_gatherxw_grouped (gemm_gatherxw_grouped.hip, 17 - 48 tokens; default tokens 17,24,32,33,40,48)
+the same way: the parent is every member's own route with VPTQ_GEMM_GATHERXW_GROUPED=0 (gemm_gatherxw or the dense route), the own
+entry of the bit check vptq_quant_gemm_gatherxw, and a cell whose bits differ ends the run.
+    python tools/gemm_gatherx_grouped_bench.py --entry gatherxw --md profiles/r36/table.md"""
 import argparse, ctypes, json, os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -29,20 +33,24 @@ ap.add_argument("--groups", default="4096:4096,1024,1024;8192:8192,1024,1024;409
 ap.add_argument("--formats", default="16,65536,65536;16,65536,1024;16,65536,0;8,65536,4096;8,32768,0", help="v,k,kr;... (the five formats profiles/r16 measured)")
 ap.add_argument("--dtypes", default="f16,bf16")
 ap.add_argument("--perms", default="shared,none", help="shared: every member has one random column permutation; none")
-ap.add_argument("--tokens", default="5,8,9,12,16")
+ap.add_argument("--entry", default="gatherx", choices=("gatherx", "gatherxw"), help="gatherx: 5 - 16 tokens; gatherxw: 17 - 48")
+ap.add_argument("--tokens", default="", help="default 5,8,9,12,16 (gatherx) / 17,24,32,33,40,48 (gatherxw)")
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--ring-bytes", type=int, default=512 << 20)
 ap.add_argument("--budget-s", type=float, default=0.0)
 ap.add_argument("--md", default="")
 a = ap.parse_args()
+WIDE = a.entry == "gatherxw"
+ENTRY = f"vptq_quant_gemm_{a.entry}_grouped"
+a.tokens = a.tokens or ("17,24,32,33,40,48" if WIDE else "5,8,9,12,16")
 t_start = time.time()
 dev = torch.device("cuda", 0); g = torch.Generator(device=dev).manual_seed(0); lib = B.lib()
 box = f"{torch.cuda.get_device_name(0)}, {torch.cuda.get_device_properties(0).multi_processor_count} CUs"
 print(json.dumps(dict(box=box, arithmetic=vptq_amd.arithmetic())), flush=True)
-grouped_decode._GEMM_GATHERX_GROUPED_MODE = "0"   # the modules of this process take the PARENT's routes; the grouped entry is called through the library
+grouped_decode._GEMM_GATHERX_GROUPED_MODE = grouped_decode._GEMM_GATHERXW_GROUPED_MODE = "0"   # the modules of this process take the PARENT's routes; the grouped entry is called through the library
 rows = []
-LAUNCHES = ("vptq_quant_gemm_gatherx_grouped", "vptq_quant_gemm_gatherw_grouped", "vptq_quant_gemm_gather_grouped", "vptq_quant_gemm_gather_px", "vptq_quant_gemm_gatherw", "vptq_quant_gemm_gather", "vptq_quant_gemm_gatherx",
+LAUNCHES = ("vptq_quant_gemm_gatherxw_grouped", "vptq_quant_gemm_gatherxw", "vptq_quant_gemm_gatherx_grouped", "vptq_quant_gemm_gatherw_grouped", "vptq_quant_gemm_gather_grouped", "vptq_quant_gemm_gather_px", "vptq_quant_gemm_gatherw", "vptq_quant_gemm_gather", "vptq_quant_gemm_gatherx",
             "vptq_quant_gemv", "vptq_dequant")
 
 
@@ -128,20 +136,20 @@ for v, k, kr in [tuple(int(n) for n in p.split(",")) for p in a.formats.split(";
             groups = [mk_group(I, outs, v, k, kr, pname == "shared", dt) for _ in range(ring)]
             arrays = [group_array(ms) for ms in groups]
             for tok in [int(t) for t in a.tokens.split(",")]:
-                if lib.vptq_quant_gemm_gatherx_grouped_supported(arrays[0][0], n, tok) != 1:
+                if getattr(lib, ENTRY + "_supported")(arrays[0][0], n, tok) != 1:
                     continue
                 text = ctypes.create_string_buffer(320)
-                B.check(lib.vptq_quant_gemm_gatherx_grouped_instance(arrays[0][0], n, tok, 0, text, len(text)), "instance")
+                B.check(getattr(lib, ENTRY + "_instance")(arrays[0][0], n, tok, 0, text, len(text)), "instance")
                 x = torch.randn(1, tok, I, device=dev).to(dt)
                 ys = [torch.empty(1, tok, O, device=dev, dtype=dt) for O in outs]
                 yp = (ctypes.c_void_p * n)(*[y.data_ptr() for y in ys])
-                need = lib.vptq_quant_gemm_gatherx_grouped_workspace_bytes(arrays[0][0], n, tok)
+                need = getattr(lib, ENTRY + "_workspace_bytes")(arrays[0][0], n, tok)
                 ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
                 sp = lambda: torch.cuda.current_stream().cuda_stream   # noqa: E731
 
                 def run_grouped():
                     for descs, _, _ in arrays:
-                        B.check(lib.vptq_quant_gemm_gatherx_grouped(descs, n, x.data_ptr(), yp, tok, 0, ws.data_ptr(), need, sp()), "gemm_gatherx_grouped")
+                        B.check(getattr(lib, ENTRY)(descs, n, x.data_ptr(), yp, tok, 0, ws.data_ptr(), need, sp()), ENTRY)
 
                 def run_parent():
                     for ms in groups:
@@ -149,11 +157,15 @@ for v, k, kr in [tuple(int(n) for n in p.split(",")) for p in a.formats.split(";
                             m(x)
                 # (the first group of the ring: every member against its own entry, bit for bit; the entries the parent routes call)
                 descs, ds, _ = arrays[0]
-                B.check(lib.vptq_quant_gemm_gatherx_grouped(descs, n, x.data_ptr(), yp, tok, 0, ws.data_ptr(), need, sp()), "gemm_gatherx_grouped")
+                B.check(getattr(lib, ENTRY)(descs, n, x.data_ptr(), yp, tok, 0, ws.data_ptr(), need, sp()), ENTRY)
                 got = [y.clone() for y in ys]
                 same = True
                 for d, y, want in zip(ds, ys, got):
-                    if d.perm:
+                    if WIDE:
+                        pneed = lib.vptq_quant_gemm_gatherxw_workspace_bytes(d, tok)
+                        assert pneed <= ws.numel(), (pneed, ws.numel())
+                        B.check(lib.vptq_quant_gemm_gatherxw(d, x.data_ptr(), y.data_ptr(), tok, 0, ws.data_ptr(), pneed, sp()), "own entry")
+                    elif d.perm:
                         pneed = lib.vptq_quant_gemm_gather_px_workspace_bytes(d, tok)
                         assert pneed <= ws.numel(), (pneed, ws.numel())   # (the group's workspace serves the member's own call)
                         B.check(lib.vptq_quant_gemm_gather_px(d, x.data_ptr(), y.data_ptr(), tok, 0, ws.data_ptr(), pneed, sp()), "own entry")
@@ -161,6 +173,7 @@ for v, k, kr in [tuple(int(n) for n in p.split(",")) for p in a.formats.split(";
                         B.check(lib.vptq_quant_gemm_gatherx(d, x.data_ptr(), y.data_ptr(), tok, 0, sp()), "own entry")
                     torch.cuda.synchronize()
                     same = same and bool(torch.equal(want.view(torch.int16), y.view(torch.int16)))
+                assert same or not WIDE, f"{fmt} {dname} {spec} {pname} {tok} tokens: a member's bits differ from its own entry"
                 calls, real = [], B.lib
                 B.lib = lambda: Spy(lib, calls)
                 try:

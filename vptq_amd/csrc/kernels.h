@@ -275,6 +275,16 @@ bool gemm_gatherxw_eligible(const VptqLayerDesc& d, int tokens);
 struct GemmGatherXWDecision { bool f16; int v, ib, rb, res, res_bytes, tok, tb, tiles, lds, wgcu, n_groups, grid, rgs; };
 GemmGatherXWDecision gemm_gatherxw_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gatherxw(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+// gemm_gatherxw_grouped.hip - 2 - 4 sibling layers of gemm_gatherxw (one dtype, width and format: v, main and residual codebook size),
+// 17 - 48 tokens, in ONE launch of gemm_gatherxw_grouped_kernel<DT, V, RES, TB>: gemm_gatherxw's token-block pass behind
+// gemm_gatherx_grouped's member walk; plain form only - the caller hands a member with a permutation over as its descriptor without
+// one, with x[perm] for its x.  v ... lds: gemm_gatherx_decide's of the first member; wgcu: the RESIDENT workgroups per CU (the
+// smaller of that decision's LDS bound and the kernel's register bound); groups, first_group, total as GemmGatherGroupedDecision's;
+// grid = min(total, CUs x wgcu), rgs over the whole list
+struct GemmGatherXWGroupedDecision { bool f16; int v, ib, rb, res, res_bytes, tok, tb, n, tiles, lds, wgcu, total, grid, rgs, groups[4], first_group[5]; };
+GemmGatherXWGroupedDecision gemm_gatherxw_grouped_decide(const VptqLayerDesc* descs, int n, int tokens);
+hipError_t launch_gemm_gatherxw_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                        hipStream_t st);
 
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)

@@ -2,12 +2,13 @@
 `vptq_quant_gemm_gather_grouped` - the members' row groups as one list in ONE launch, one x gather per distinct permutation - in
 place of one launch (and one x gather) per member; for the canonical format, `vptq_quant_gemm_k256_grouped`; for 17 - 48 tokens of
 the large-codebook formats, `vptq_quant_gemm_gatherw_grouped`; for 5 - 16 tokens of the other large-codebook formats (gemm_gatherx's),
-`vptq_quant_gemm_gatherx_grouped`.
+`vptq_quant_gemm_gatherx_grouped`, and for their 17 - 48 tokens `vptq_quant_gemm_gatherxw_grouped`.
 
 Pure rules - no device, no tensors, in the style of vptq_amd/batched_decode.py: per route one route function, its knob and its
 measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group routes (`GROUPED_DECODE_WIDE_ROUTES`: a format's routes
 beyond its first window; `GROUPED_DECODE_X_ROUTES`: the routes of formats the first table has no owner for; `sibling_decode_routes`
-reads all three).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
+reads all three; `GROUPED_DECODE_X_WIDE_ROUTES`: those formats' routes beyond their first window, read behind the others by
+`sibling_group_routes`).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
 is not routed here leaves every member on the routes it had.  `SiblingGroup.forward_batched` (vptq_amd/layers/vqlinear.py) and
 `prepare_model` decide through it.
 """
@@ -202,8 +203,8 @@ def gemm_gatherw_grouped_tokens(vector_len: int, num_centroids: int, num_res_cen
 # WHICH groups of the large-codebook formats `vptq_quant_gemm_gatherx` serves (vector length 8 / 16, 16384 ... 65536 main centroids, any
 # residual codebook but gemm_gather's three formats: v16-k65536-65536 / -32768 / -1024 / -0, v8-k65536-4096, v8-k32768-0, ...) take
 # `vptq_quant_gemm_gatherx_grouped` (gemm_gatherx_grouped.hip: gemm_gatherx's row-group body behind gemm_gather_grouped's member
-# walk), 5 - 16 tokens (1 - 4 tokens are `SiblingGroup.forward` / `forward_sliced`'s; there is no wide kernel for these formats, so 17 -
-# 48 tokens keep the members' routes).  Without it every member goes out alone: gemm_gatherx, gemm_gather_px (a permute launch, then
+# walk), 5 - 16 tokens (1 - 4 tokens are `SiblingGroup.forward` / `forward_sliced`'s; 17 -
+# 48 tokens are `vptq_quant_gemm_gatherxw_grouped`'s, below).  Without it every member goes out alone: gemm_gatherx, gemm_gather_px (a permute launch, then
 # gemm_gatherx), gemv_gatherx or vptq_dequant + a dense GEMM, whichever `BATCHED_DECODE_ROUTES` gives a layer of its format and size.
 # A cell is the wide group's plus the format: (vector length, main centroids, residual centroids, has_perm, member count, least TOTAL
 # index elements of the group = the sum of vector-rows x columns over its members, most total index elements or None, least tokens,
@@ -275,6 +276,80 @@ def gemm_gatherx_grouped_tokens(vector_len: int, num_centroids: int, num_res_cen
     sizes the stream's workspace to the largest"""
     return tuple(t for t in range(GEMM_GATHERX_GROUPED_MIN_TOKENS, GEMM_GATHERX_GROUPED_MAX_TOKENS + 1)
                  if gemm_gatherx_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
+
+
+# WHICH groups of `vptq_quant_gemm_gatherx`'s formats take `vptq_quant_gemm_gatherxw_grouped` (gemm_gatherxw_grouped.hip: gemm_gatherxw's
+# token-block pass behind gemm_gatherx_grouped's member walk), 17 - 48 tokens - the window beyond `vptq_quant_gemm_gatherx_grouped`'s.
+# Without it every member goes out alone from the 17th token on: gemm_gatherxw (behind a permute launch of its own when permuted) or
+# vptq_dequant + a dense GEMM, whichever `BATCHED_DECODE_WIDE_ROUTES` gives a layer of its format and size.  A cell has
+# `_GEMM_GATHERX_GROUPED_CELLS`' format: (vector length, main centroids, residual centroids, has_perm, member count, least TOTAL index
+# elements of the group, most total index elements or None, least tokens, most tokens).  Routed by the rule of the tables above: the
+# grouped launch beats the SUM of what the members take without it by more than the larger of 5 % and three times the larger
+# run-to-run spread, in every measured cell of the region, in both dtypes; a region reaches from its smallest to its largest measured
+# group and no further; the routed token counts of a group are one interval; no cell lies under GEMM_GATHERXW_GROUPED_MIN_ELEMENTS (2 M
+# total index elements).  tools/gemm_gatherx_grouped_bench.py --entry gatherxw writes the table.  VPTQ_GEMM_GATHERXW_GROUPED=1 / 0 (with
+# VPTQ_TUNING=1): every group of the kernel's formats from 17 to 48 tokens / none.
+#
+# profiles/r36/table.md, profiles/r36/README.md (one MI355X, fp16 and bf16, the five formats of profiles/r34, q / k / v and gate / up of the
+# 8B and 70B shapes = 1.5 M, 5 M, 7 M and 28 M total index elements for v = 16 and 3 M, 10 M, 14 M and 56 M for v = 8, tokens 17 / 24 / 32 /
+# 33 / 40 / 48, with one shared permutation and without; 480 cells, every member has the bits of its own entry in every one, 275 win;
+# run-to-run spreads under 1.3 % in 95 % of the cells, 3.6 % the largest):
+#   q / k / v        8B shapes (the parent: three dense routes): every cell wins, 0.41 - 0.80 of the parent (v16-k65536-65536 0.67 - 0.94).
+#                    The 8B q / k / v of v = 16 (1.5 M elements) lies under the floor and keeps its routes.  70B shapes (the parent: one
+#                    gemm_gatherxw launch and two dense routes): with a permutation 0.77 - 0.95 up to 40 tokens (v16-k65536-1024 and
+#                    v8-k32768-0 up to 48), without one 0.78 - 0.91 up to 24 tokens (v16-k65536-1024 up to 32, v8-k32768-0 up to 40), level or
+#                    slower beyond; v16-k65536-65536 never (0.96 - 1.36)
+#   gate / up        8B shapes: with a permutation v16-k65536-1024 and v8-k65536-4096 in every cell (0.62 - 0.94), v8-k32768-0 up to 40
+#                    tokens, v16-k65536-65536 up to 32, v16-k65536-0 up to 24 (0.75 - 0.85); without one 17 - 24 tokens only (0.77 - 0.93; the
+#                    dense routes are faster from 32, up to 1.34) and v16-k65536-65536 never (1.09 - 1.42).  70B shapes: level with two
+#                    launches (0.85 - 1.20); in both dtypes only v16-k65536-1024 with a permutation wins by the rule, at 17 - 24 tokens (0.93 - 0.94)
+# A region reaches from its smallest to its largest MEASURED group of its member count (or is one of the two alone) and no further.
+_GEMM_GATHERXW_GROUPED_CELLS = (
+    (16, 65536, 0, True, 3, 5 << 20, 5 << 20, 17, 40), (16, 65536, 0, False, 3, 5 << 20, 5 << 20, 17, 24),
+    (16, 65536, 0, True, 2, 7 << 20, 7 << 20, 17, 24), (16, 65536, 0, False, 2, 7 << 20, 7 << 20, 17, 24),
+    (16, 65536, 1024, True, 3, 5 << 20, 5 << 20, 17, 48), (16, 65536, 1024, False, 3, 5 << 20, 5 << 20, 17, 32),
+    (16, 65536, 1024, True, 2, 7 << 20, 28 << 20, 17, 24), (16, 65536, 1024, True, 2, 7 << 20, 7 << 20, 17, 48),
+    (16, 65536, 1024, False, 2, 7 << 20, 7 << 20, 17, 24),
+    (16, 65536, 65536, True, 2, 7 << 20, 7 << 20, 17, 32),
+    (8, 32768, 0, True, 3, 3 << 20, 10 << 20, 17, 48), (8, 32768, 0, False, 3, 3 << 20, 10 << 20, 17, 40), (8, 32768, 0, False, 3, 3 << 20, 3 << 20, 17, 48),
+    (8, 32768, 0, True, 2, 14 << 20, 14 << 20, 17, 40), (8, 32768, 0, False, 2, 14 << 20, 14 << 20, 17, 24),
+    (8, 65536, 4096, True, 3, 3 << 20, 10 << 20, 17, 40), (8, 65536, 4096, True, 3, 3 << 20, 3 << 20, 17, 48),
+    (8, 65536, 4096, False, 3, 3 << 20, 10 << 20, 17, 24), (8, 65536, 4096, False, 3, 3 << 20, 3 << 20, 17, 48),
+    (8, 65536, 4096, True, 2, 14 << 20, 14 << 20, 17, 48), (8, 65536, 4096, False, 2, 14 << 20, 14 << 20, 17, 24))
+GEMM_GATHERXW_GROUPED_MIN_TOKENS, GEMM_GATHERXW_GROUPED_MAX_TOKENS = 17, 48
+GEMM_GATHERXW_GROUPED_MIN_ELEMENTS = 2 << 20
+GEMM_GATHERXW_GROUPED_MAX_MEMBERS = 4
+_GEMM_GATHERXW_GROUPED_MODE = (B.tune_env("VPTQ_GEMM_GATHERXW_GROUPED", "auto") or "auto").strip().lower()
+
+
+def gemm_gatherxw_grouped_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                in_features: int, tokens: int, has_perm: Optional[bool]) -> bool:
+    """does a group of sibling layers of this format (shared by its members) with these output widths take
+    `vptq_quant_gemm_gatherxw_grouped` for `tokens` tokens?  has_perm: True - every member has a column permutation, False - none,
+    None - some.  Pure: no device, no library (whether the library serves the group is `vptq_quant_gemm_gatherxw_grouped_supported`'s
+    answer).  Only for the formats `gemm_gatherx_grouped_route` owns: a group has one route per window."""
+    if _GEMM_GATHERXW_GROUPED_MODE in ("0", "off") or not GEMM_GATHERXW_GROUPED_MIN_TOKENS <= tokens <= GEMM_GATHERXW_GROUPED_MAX_TOKENS:
+        return False
+    n = len(out_features_tuple)
+    if not 2 <= n <= GEMM_GATHERXW_GROUPED_MAX_MEMBERS or in_features % 8 or \
+            _batched_decode_entry(vector_len, num_centroids, num_res_centroids) != "vptq_quant_gemm_gatherx":
+        return False
+    if _GEMM_GATHERXW_GROUPED_MODE in ("1", "on"):
+        return True
+    if has_perm is None:
+        return False
+    n_el = sum((o + vector_len - 1) // vector_len for o in out_features_tuple) * in_features
+    return any((v, k, kr) == (vector_len, num_centroids, num_res_centroids) and perm == has_perm and members == n and
+               n_el >= max(min_el, GEMM_GATHERXW_GROUPED_MIN_ELEMENTS) and (max_el is None or n_el <= max_el) and
+               min_tok <= tokens <= max_tok for v, k, kr, perm, members, min_el, max_el, min_tok, max_tok in _GEMM_GATHERXW_GROUPED_CELLS)
+
+
+def gemm_gatherxw_grouped_tokens(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                 in_features: int, has_perm: Optional[bool]) -> tuple:
+    """the token counts the route function gives to the grouped launch for this group, ascending (possibly none): `prepare_model`
+    sizes the stream's workspace to the largest"""
+    return tuple(t for t in range(GEMM_GATHERXW_GROUPED_MIN_TOKENS, GEMM_GATHERXW_GROUPED_MAX_TOKENS + 1)
+                 if gemm_gatherxw_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
 
 
 class GroupedDecodeRoute(NamedTuple):
@@ -352,3 +427,22 @@ def sibling_decode_routes(vector_len: int, num_centroids: int, num_res_centroids
     if routes:
         return routes
     return tuple(r for r in GROUPED_DECODE_X_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))
+
+
+# the routes of `GROUPED_DECODE_X_ROUTES`' formats BEYOND their first window, in window order: gemm_gatherx's formats, 17 - 48 tokens
+# behind `vptq_quant_gemm_gatherx_grouped`'s 5 - 16.  (Again a table of its own: the three tables above and their readers keep every
+# answer they gave before.)  The window lies inside GROUPED_DECODE_MIN_TOKENS ... GROUPED_DECODE_MAX_TOKENS.
+GROUPED_DECODE_X_WIDE_ROUTES = (
+    GroupedDecodeRoute("vptq_quant_gemm_gatherxw_grouped", lambda v, k, kr: _batched_decode_entry(v, k, kr) == "vptq_quant_gemm_gatherx",
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_gatherxw_grouped_route(v, k, kr, outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_gatherxw_grouped_tokens(v, k, kr, outs, width, has_perm),
+                       GEMM_GATHERXW_GROUPED_MIN_TOKENS, GEMM_GATHERXW_GROUPED_MAX_TOKENS, B.GEMV_FORCE_GENERIC),
+)
+
+
+def sibling_group_routes(vector_len: int, num_centroids: int, num_res_centroids: int) -> tuple:
+    """every group route a `SiblingGroup` of this format can take, in window order: `sibling_decode_routes`' answer, then the records
+    of `GROUPED_DECODE_X_WIDE_ROUTES` that own the format (none for any format but gemm_gatherx's).  What `SiblingGroup` reads.  No
+    knob is read."""
+    return sibling_decode_routes(vector_len, num_centroids, num_res_centroids) + \
+        tuple(r for r in GROUPED_DECODE_X_WIDE_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))
