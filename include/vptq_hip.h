@@ -687,6 +687,47 @@ VPTQ_API int vptq_quant_gemm_gatherxw(const VptqLayerDesc* desc, const void* x, 
                                       size_t workspace_bytes, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherxw_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of the large-codebook formats of VECTOR LENGTH 12 for 1 - 16 tokens in ONE launch (gemm_gather12_kernel in
+ * gemm_gather12.hip; added within ABI 12; present when the symbols are).  vector_len 12, 16384 ... 65536 main centroids, any residual
+ * codebook or none (index_bits + res_bits <= 32: "v12-k65536-4096", "-256", "-0", "v12-k32768-1024"), one codebook group, no outlier
+ * columns, weight_scale and weight_bias set (with perm: scale_permuted and bias_permuted), group_size == in_features (a multiple of
+ * 8), row_words * 32 >= group_size * (index_bits + res_bits), num_indices * 12 >= out_features.  A workgroup owns row groups of 4
+ * vector-rows = 48 outputs = three N blocks of a 16x16x32 MFMA (tokens are M) over tiles of 512 columns; a residual table of at most
+ * 32 KiB is held in LDS, a larger one is gathered from L2.  The kernel has no form with a permutation: for a layer with one, xp[t][c]
+ * = x[t][perm[c]] is written once into the workspace (permute_x_tokens_kernel, vptq_quant_gemm_gather_px's) and the kernel runs over
+ * xp, scale_permuted and bias_permuted; a layer without one ignores the workspace, which may be NULL / 0.  Both launches go to
+ * `stream`; nothing is allocated: graph-capturable.  The reference's roundings per weight (bit-identical to vptq_dequant's W), fp32
+ * sums added in a fixed order that depends on neither the token count nor the launch, one rounding of the output, the output bias
+ * added in fp32; no atomics.
+ *   x [tokens][in_features], y [tokens][out_features], desc->dtype; flags: VPTQ_GEMV_OUT_F32 stores the fp32 sums (y is float32);
+ *   VPTQ_GEMV_FAST_MATH / _EXACT / _SELECTIVE are accepted and change nothing.
+ * vptq_quant_gemm_gather12_supported: 1 where the call serves (desc, tokens), 1 <= tokens <= 16, else 0; host logic.
+ * vptq_quant_gemm_gather12_workspace_bytes: tokens * group_size * 2 rounded up to 256 for a layer with a permutation; 0 without one
+ *   and where vptq_quant_gemm_gather12_supported answers 0.
+ * vptq_quant_gemm_gather12: NULL desc / x / y VPTQ_E_NULL; tokens outside [1, 16] VPTQ_E_TOKENS (checked before the layer); a layer it
+ *   does not serve VPTQ_E_UNSUPPORTED; an x that is not 16-byte aligned VPTQ_E_ALIGN; then, for a layer with a permutation, a NULL
+ *   workspace or fewer workspace_bytes than the query answers VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned
+ *   VPTQ_E_ALIGN; nothing is launched then.
+ * vptq_quant_gemm_gather12_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   [permute_x_tokens g=N tok=N grid=XxY tpt=4 | ]gemm_gather12 dt=f16|bf16 ib=N rb=N res=none|lds|l2 tok=N tiles=N wgcu=N rgs=N
+ *       the permute launch as vptq_quant_gemm_gather_px_instance prints it, only for a layer with a permutation; ib / rb the main /
+ *       residual index widths, res where the residual entries come from, tiles the column tiles (512 columns) per row group (48
+ *       outputs), wgcu the resident workgroups per CU (the smaller of what 48 KiB + an LDS-held table leave and the kernel's register
+ *       bound, 2), rgs the most row groups one workgroup walks.  Returns as vptq_quant_gemm_gather_instance does.
+ * vptq_quant_gemv, vptq_quant_gemv_max_tokens, vptq_quant_gemv_kernel_name and the other vptq_quant_gemm_gather* entries are what they
+ * were: none of them takes a layer of vector length 12 beyond gemv_gatherx's 4 token slots.
+ * Special values: a NaN or infinite weight, scale, bias or activation propagates as IEEE arithmetic has it through the rebuild and
+ * the sums; a weight is multiplied with the ZERO of a token row past `tokens` or a column past group_size only in lanes whose result
+ * is never stored, so it cannot turn a stored output into NaN; every output of the call is either stored once or not touched.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: indices 16 bytes, centroids and res_centroids 8 bytes (24-byte entries), weight_scale, weight_bias, perm, scale_permuted,
+ * bias_permuted 4 bytes (part of "supported"); x 16 bytes and the workspace 16 bytes (VPTQ_E_ALIGN); y and bias element-aligned. */
+VPTQ_API int vptq_quant_gemm_gather12_supported(const VptqLayerDesc* desc, int tokens);
+VPTQ_API size_t vptq_quant_gemm_gather12_workspace_bytes(const VptqLayerDesc* desc, int tokens);
+VPTQ_API int vptq_quant_gemm_gather12(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, void* workspace,
+                                      size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gather12_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
+
 /* Batched decode of the canonical format for 17 - 64 tokens in ONE launch (gemm_k256w_kernel in gemm_k256.hip; added within ABI 12;
  * present when the symbols are).  The layers vptq_quant_gemv serves with gemm_k256_kernel - v = 8, 256 main + 256 residual centroids,
  * one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and bias_permuted), group_size ==

@@ -171,6 +171,12 @@ EXPORTS = {
     "vptq_quant_gemm_gatherxw_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gatherxw": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gatherxw_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 16 tokens of the large-codebook formats of vector length 12 in one launch, a permuted layer's x[perm]
+    # written into the workspace first (gemm_gather12.hip): the same four shapes
+    "vptq_quant_gemm_gather12_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gather12_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int]),
+    "vptq_quant_gemm_gather12": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather12_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     # (added within ABI 12) 17 - 64 tokens of the canonical format in one launch (gemm_k256w_kernel, gemm_k256.hip)
     "vptq_quant_gemm_k256w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_k256w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),

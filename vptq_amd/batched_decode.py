@@ -5,7 +5,8 @@ between the routes (`BATCHED_DECODE_ROUTES`) and the two functions that read it,
 the per-call `batched_decode_takes`.  `VQuantLinear.forward` and `ops.quant_gemm` both decide through them.  A new route is a
 record in the table, a route function and a knob.  Behind the first table stands `BATCHED_DECODE_WIDE_ROUTES` (read by
 `batched_decode_wide_routes`, walked after the first table's routes): a format's route beyond its first window - `gemm_gatherxw_route`,
-17 - 48 tokens of gemm_gatherx's formats.
+17 - 48 tokens of gemm_gatherx's formats - and behind that `BATCHED_DECODE_V12_ROUTES` (`batched_decode_v12_routes`): `gemm_gather12_route`,
+5 - 16 tokens of the vector-length-12 formats, which no record of the first two tables owns.
 """
 from __future__ import annotations
 
@@ -261,6 +262,57 @@ def gemm_gatherxw_route(vector_len: int, num_centroids: int, num_res_centroids: 
                for v, k, kr, p, min_el, min_tok, max_tok in _GEMM_GATHERXW_CELLS)
 
 
+# WHICH (format, shape, token count) of the large-codebook formats of VECTOR LENGTH 12 (16384 ... 65536 main centroids, any residual
+# codebook: "v12-k65536-4096" of the published checkpoints) take `vptq_quant_gemm_gather12` - 5 - 16 tokens in ONE launch
+# (gemm_gather12_kernel, gemm_gather12.hip: row groups of 48 outputs = three MFMA N blocks; a layer with a column permutation: x[perm]
+# written once into the stream's workspace in front of it) - in place of the route they had (5 - 8 tokens: two gemv_gatherx launches,
+# which stops at 4 token slots for v = 12; 9 - 16: the dense route): the one rule, read by `VQuantLinear.forward` and `ops.quant_gemm`.
+# `_batched_decode_entry` keeps answering None for v = 12 (the first two tables are what they were); the format test is `_v12_owns`.
+# A cell is (main centroids, residual centroids, has a permutation, least index elements = vector-rows x columns, least tokens, most
+# tokens), routed by the rule above `_GEMM_GATHER_CELLS` (beats its parent by more than the larger of 5 % and three times the larger
+# run-to-run spread, in every measured cell of the region, in both dtypes; the routed token counts of a layer are one interval);
+# tools/gemm_gather12_bench.py writes the table.  VPTQ_GEMM_GATHER12=1 / 0 (with VPTQ_TUNING=1): every supported layer from 5 to 16
+# tokens / none.
+#
+# profiles/r37/table.md, profiles/r37/README.md (one MI355X, fp16 and bf16, 4096 x 4096 ... 8192 x 28672, tokens 5 / 8 / 9 / 12 / 16, with
+# and without a permutation; 300 cells, the entry's bits checked in every one, 178 win; spreads over 3 % in 9 cells).  v = 12 layers
+# have 1.3 M index elements at 4096 x 4096, 4.7 M at 4096 x 14336 and 14336 x 4096 (columns x outputs), 5.3 M at 8192 x 8192 and 18.7 M
+# at 8192 x 28672.  A cell's region is every measured layer from its size up:
+#   4096 x 4096 loses nearly everywhere (1.03 - 1.65 of the parent's time; 29 row groups on 512 workgroup slots) and 14336 x 4096 (86
+#     row groups) loses at 9 - 16 tokens in every format (0.99 - 2.11), so no region reaches below 8192 x 8192 at 9 - 16 tokens
+#   WITH a permutation (the parents gather x or W's columns in every launch): all three formats win at 5 - 8 tokens from 4096 x 14336 /
+#     14336 x 4096 up (0.28 - 0.90) and at 5 - 16 tokens from 8192 x 8192 up (0.28 - 0.84)
+#   WITHOUT one: v12-k65536-4096 wins at 5 - 8 tokens from 8192 x 8192 up (0.50 - 0.92; 9 - 16 there: fp16 0.91, bf16 1.24) and at
+#     5 - 16 at 8192 x 28672 (0.50 - 0.79); v12-k65536-0 and -256 only at 8192 x 28672 (0.54 - 0.77; 8192 x 8192: -0 0.87 - 0.98 with
+#     one winning token count, -256 0.85 - 1.14)
+# v12-k32768-1024 and the other formats of the kernel were not measured and are not routed.
+_GEMM_GATHER12_CELLS = tuple(c for kr in (0, 256, 4096) for c in ((65536, kr, 1, 4 << 20, 5, 8), (65536, kr, 1, 5 << 20, 5, 16))) + (
+    (65536, 0, 0, 18 << 20, 5, 16), (65536, 256, 0, 18 << 20, 5, 16), (65536, 4096, 0, 5 << 20, 5, 8), (65536, 4096, 0, 18 << 20, 5, 16))
+GEMM_GATHER12_MIN_TOKENS, GEMM_GATHER12_MAX_TOKENS = 5, 16
+_GEMM_GATHER12_MODE = (B.tune_env("VPTQ_GEMM_GATHER12", "auto") or "auto").strip().lower()
+
+
+def _v12_owns(vector_len: int, num_centroids: int, num_res_centroids: int) -> bool:
+    """is the format `vptq_quant_gemm_gather12`'s?"""
+    return vector_len == 12 and _pow2(num_centroids) and 16384 <= num_centroids <= 65536 and \
+        (not num_res_centroids or (_pow2(num_res_centroids) and num_res_centroids <= 65536))
+
+
+def gemm_gather12_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int,
+                        has_perm: Optional[bool] = None) -> bool:
+    """does a layer of this format and shape take `vptq_quant_gemm_gather12` for `tokens` tokens?  has_perm: whether the layer has a
+    column permutation (the cells are measured per state); None: a layer of either state, i.e. whether ANY cell takes it.  Pure: no
+    device, no library (whether the library serves the layer is `vptq_quant_gemm_gather12_supported`'s answer)."""
+    if _GEMM_GATHER12_MODE in ("0", "off") or not GEMM_GATHER12_MIN_TOKENS <= tokens <= GEMM_GATHER12_MAX_TOKENS or in_features % 8 or \
+            not _v12_owns(vector_len, num_centroids, num_res_centroids):
+        return False
+    if _GEMM_GATHER12_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any((k, kr) == (num_centroids, num_res_centroids) and (has_perm is None or bool(p) == bool(has_perm)) and n_el >= min_el and
+               min_tok <= tokens <= max_tok for k, kr, p, min_el, min_tok, max_tok in _GEMM_GATHER12_CELLS)
+
+
 class BatchedDecodeRoute(NamedTuple):
     """what differs between the batched-decode routes; everything else is one code path in both callers"""
     entry: str                    # the library entry (`entry + "_supported"`: does the library serve this descriptor?)
@@ -306,6 +358,13 @@ BATCHED_DECODE_WIDE_ROUTES = (
     BatchedDecodeRoute("vptq_quant_gemm_gatherxw", GEMM_GATHERXW_MIN_TOKENS, GEMM_GATHERXW_MAX_TOKENS, _entry_is("vptq_quant_gemm_gatherx"),
                        gemm_gatherxw_route, "_GEMM_GATHERXW_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True),
 )
+# A third table, walked after the two above: the formats of vector length 12, which no record above owns (`_batched_decode_entry`
+# answers None for them), so no call is taken from a route above.  A permuted layer and a plain one take the same entry (perm=None),
+# which gathers x[perm] into the workspace itself.  17 - 48 tokens, sibling groups and v = 6 have no record: they keep their routes.
+BATCHED_DECODE_V12_ROUTES = (
+    BatchedDecodeRoute("vptq_quant_gemm_gather12", GEMM_GATHER12_MIN_TOKENS, GEMM_GATHER12_MAX_TOKENS, _v12_owns, gemm_gather12_route,
+                       "_GEMM_GATHER12_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True),
+)
 BATCHED_DECODE_MIN_TOKENS = min(r.min_tokens for r in BATCHED_DECODE_ROUTES)   # the union of the windows: what a caller guards with
 BATCHED_DECODE_MAX_TOKENS = max(r.max_tokens for r in BATCHED_DECODE_ROUTES)
 
@@ -322,6 +381,13 @@ def batched_decode_wide_routes(vector_len: int, num_centroids: int, num_res_cent
     """`batched_decode_routes` over `BATCHED_DECODE_WIDE_ROUTES`: the same static filters; a caller walks these after the first
     table's."""
     return _static_routes(BATCHED_DECODE_WIDE_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm)
+
+
+def batched_decode_v12_routes(vector_len: int, num_centroids: int, num_res_centroids: int, num_codebooks: int, outliers: bool, norm: bool,
+                              has_perm: bool) -> tuple:
+    """`batched_decode_routes` over `BATCHED_DECODE_V12_ROUTES`: the same static filters; a caller walks these after the other two
+    tables'."""
+    return _static_routes(BATCHED_DECODE_V12_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm)
 
 
 def _static_routes(table, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm) -> tuple:

@@ -1405,6 +1405,63 @@ int vptq_quant_gemm_gatherxw_instance(const VptqLayerDesc* d, int tokens, int, c
   return instance_done(t);
 }
 
+// ---- gemm_gather12.hip (added within ABI 12): 1 - 16 tokens of the large-codebook formats of vector length 12 in one launch of
+// gemm_gather12_kernel, which has no form with a permutation: a permuted layer's x[perm] is written into the workspace first
+// (gemm_gather_px.hip's permute launch) and the kernel runs on gemm_gather_px_plain(d), as vptq_quant_gemm_gatherxw does.
+static int gather12_validate(const VptqLayerDesc* d, int tokens) {
+  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
+  if (!vptq::gemm_gather12_eligible(*d, tokens))
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gather12 serves v = 12, 16384 ... 65536 main centroids, any residual codebook (index_bits + res_bits <= 32), one "
+                "codebook, no outlier columns, scale and bias, group_size == in_features (a multiple of 8), indices 16-byte and tables 8-byte aligned");
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gather12_supported(const VptqLayerDesc* d, int tokens) {
+  return validate_layer(d) == VPTQ_OK && vptq::gemm_gather12_eligible(*d, tokens) ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gather12_workspace_bytes(const VptqLayerDesc* d, int tokens) {
+  if (!vptq_quant_gemm_gather12_supported(d, tokens)) return 0;
+  return vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+}
+
+int vptq_quant_gemm_gather12(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  if (const int rc = gather12_validate(d, tokens)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12: x must be 16-byte aligned");
+  const size_t need = vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+  if (need == 0) {   // no permutation: the kernel alone, the workspace is not touched
+    const hipError_t e = vptq::launch_gemm_gather12(*d, x, y, tokens, out_f32, st);
+    return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12 launch");
+  }
+  if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gather12: workspace of %zu bytes needed", need);
+  if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12: the workspace must be 16-byte aligned");
+  hipError_t e = vptq::launch_permute_x_tokens(*d, x, workspace, tokens, st);
+  if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  e = vptq::launch_gemm_gather12(vptq::gemm_gather_px_plain(*d), workspace, y, tokens, out_f32, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12 launch");
+}
+
+int vptq_quant_gemm_gather12_instance(const VptqLayerDesc* d, int tokens, int, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  if (const int rc = gather12_validate(d, tokens)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const vptq::GemmGatherPxDecision X = vptq::gemm_gather_px_decide(*d, tokens);
+  if (X.perm) t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d | ", X.g, X.tok, X.grid_x, X.grid_y, X.tpt);
+  const vptq::GemmGather12Decision D = vptq::gemm_gather12_decide(vptq::gemm_gather_px_plain(*d), tokens);
+  t.add("gemm_gather12 dt=%s ib=%d rb=%d res=%s tok=%d tiles=%d wgcu=%d rgs=%d", dt_text(D.f16), D.ib, D.rb,
+        D.res == 0 ? "none" : D.res == 1 ? "lds" : "l2", D.tok, D.tiles, D.wgcu, D.rgs);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // ---- gemm_gather.hip's grouped launch (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gather, 1 - 16 tokens, in ONE
 // launch of gemm_gather_grouped_kernel, behind one permute launch per DISTINCT perm pointer of the members.
 // What a grouped call IS, decided once for the workspace query, the launcher and the `_instance`: which xp block a member reads (-1:

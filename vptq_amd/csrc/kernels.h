@@ -286,6 +286,16 @@ GemmGatherXWGroupedDecision gemm_gatherxw_grouped_decide(const VptqLayerDesc* de
 hipError_t launch_gemm_gatherxw_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
                                         hipStream_t st);
 
+// gemm_gather12.hip - the large-codebook formats of vector length 12 (16384 ... 65536 main centroids, any residual codebook), 1 - 16
+// tokens in one launch of gemm_gather12_kernel<DT, RES>: row groups of 4 vector-rows = 48 outputs = three MFMA N blocks over a tile of
+// 512 columns; plain form only - a layer with a permutation comes as gemm_gather_px_plain(d), with x[perm] for its x
+bool gemm_gather12_eligible(const VptqLayerDesc& d, int tokens);
+// what launch_gemm_gather12 launches: ib / rb the index widths, res 0 / 1 / 2 = no residual table / in LDS / from L2, tiles of 512
+// columns, lds bytes, wgcu the resident workgroups per CU (the smaller of the LDS and the register bound), the launch shape
+struct GemmGather12Decision { bool f16; int ib, rb, res, res_bytes, tok, tiles, lds, wgcu, n_groups, grid, rgs; };
+GemmGather12Decision gemm_gather12_decide(const VptqLayerDesc& d, int tokens);
+hipError_t launch_gemm_gather12(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
+
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)
 // - scale_permuted / bias_permuted as scale / bias, no permutation - with x = xp: the bits of the layer's own entry

@@ -19,9 +19,9 @@ import torch
 from torch.nn import functional as F
 
 from vptq_amd import _backend as B
-from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_wide_routes
+from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_routes, batched_decode_wide_routes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -210,7 +210,7 @@ def quant_gemm(
         kr = num_res_centroids if enable_residual else 0
         static = (vector_len, num_centroids, kr, num_codebooks, enable_outlier, weight_scale is not None and weight_bias is not None,
                   perm is not None)
-        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
+        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) + batched_decode_v12_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
         for r in routes:
             if not batched_decode_takes(r, vector_len, num_centroids, kr, out_features, in_features, tokens, _FLAGS, perm is not None) or \
                     x.data_ptr() % 16 or not getattr(B.lib(), r.entry + "_supported")(gdesc, tokens):
@@ -347,6 +347,21 @@ def quant_gemm_gatherxw(x: torch.Tensor, desc, out_features: int, out_f32: bool 
     y = quant_gemm_batched_launch("vptq_quant_gemm_gatherxw", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True)
     if y is None:
         raise RuntimeError("quant_gemm_gatherxw: the stream's workspace is too small and cannot grow during a capture "
+                           "(call it once, or vptq_amd.prepare_model, before capturing)")
+    return y
+
+
+def quant_gemm_gather12(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 1 - 16 tokens of a large-codebook layer of vector length 12 (16384 ... 65536 main centroids, any residual
+    codebook - "v12-k65536-4096"), with or without a column permutation, in ONE launch (`vptq_quant_gemm_gather12`, gemm_gather12.hip:
+    row groups of 4 vector-rows = 48 outputs = three MFMA N blocks, x read once per 48 outputs; the reference's roundings; replaces
+    two gemv_gatherx launches at 5 - 8 tokens and dequant + F.linear from 9).  For a layer with a permutation x[:, perm] is written once
+    into this stream's workspace (`B.gemv_workspace`) in front of it.  `desc` = a LayerDesc of a layer
+    `vptq_quant_gemm_gather12_supported` accepts; out_f32: the un-rounded fp32 sums.  Raises where a stream capture is in progress
+    and the workspace is too small (`prepare_model` sizes it beforehand)."""
+    y = quant_gemm_batched_launch("vptq_quant_gemm_gather12", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True)
+    if y is None:
+        raise RuntimeError("quant_gemm_gather12: the stream's workspace is too small and cannot grow during a capture "
                            "(call it once, or vptq_amd.prepare_model, before capturing)")
     return y
 
