@@ -728,6 +728,42 @@ VPTQ_API int vptq_quant_gemm_gather12(const VptqLayerDesc* desc, const void* x, 
                                       size_t workspace_bytes, void* stream);
 VPTQ_API int vptq_quant_gemm_gather12_instance(const VptqLayerDesc* desc, int tokens, int flags, char* buf, size_t bytes);
 
+/* The COLUMN-PARTS form of vptq_quant_gemm_gather12 for layers with few outputs (gemm_gather12c_kernel and gemm_gather12c_sum_kernel in
+ * gemm_gather12c.hip; added within ABI 12; present when the symbols are).  vptq_quant_gemm_gather12 gives a workgroup a row group of 48
+ * outputs over ALL columns, so a layer of 4096 outputs occupies 86 of 512 resident workgroups and its time follows the column count.
+ * Here the work item is (row group, column part): the tiles of 512 columns are cut into S parts of tpp tiles each (the last may be
+ * shorter, none is empty), a workgroup walks items blockIdx.x, + gridDim.x, ... of n_groups * S, and every item stores the raw fp32
+ * sums of its part - all live tokens, all 48 outputs of its group - into partials[p][token][n_groups * 48] in the workspace.  The
+ * second kernel, next on the stream, adds the S partial sums of an output in ASCENDING part order in fp32, adds the output bias in
+ * fp32 and rounds once.  No atomics, no counters, no workgroup waits for another: two calls give the same bits.  The layers, x, y,
+ * flags, the rebuilt weights (vptq_dequant's bits) and the treatment of a permutation (permute_x_tokens_kernel in front) are
+ * vptq_quant_gemm_gather12's; the sum of an output is added in a different order (per part, then over the parts), so its bits may
+ * differ from that entry's in the last place.  Nothing is allocated: graph-capturable.
+ *   parts > 0: a request - tpp = ceil(tiles / min(parts, tiles, 16)), S = ceil(tiles / tpp), tiles = ceil(group_size / 512).
+ *   parts == 0: the library's rule (gemm_gather12c_decide: chosen from the measured parts sweep of profiles/r38).  parts < 0: not served.
+ * vptq_quant_gemm_gather12c_supported: 1 where vptq_quant_gemm_gather12_supported(desc, tokens) is 1 and S >= 2 (a layer of one tile,
+ *   or parts == 1, stays with vptq_quant_gemm_gather12), else 0; host logic.
+ * vptq_quant_gemm_gather12c_workspace_bytes: two regions - for a layer with a permutation tokens * group_size * 2 rounded up to 256,
+ *   then S * tokens * n_groups * 48 * 4 bytes of partial sums (n_groups = ceil(num_indices / 4)); 0 where _supported answers 0.  A layer
+ *   without a permutation needs a workspace too.
+ * vptq_quant_gemm_gather12c: NULL desc / x / y VPTQ_E_NULL; tokens outside [1, 16] VPTQ_E_TOKENS (checked before the layer); a (layer,
+ *   parts) it does not serve VPTQ_E_UNSUPPORTED; an x that is not 16-byte aligned VPTQ_E_ALIGN; then a NULL workspace or fewer
+ *   workspace_bytes than the query answers VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned VPTQ_E_ALIGN; nothing is
+ *   launched then.
+ * vptq_quant_gemm_gather12c_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   [permute_x_tokens g=N tok=N grid=XxY tpt=4 | ]gemm_gather12c dt=f16|bf16 ib=N rb=N res=none|lds|l2 tok=N tiles=N parts=S tpp=N wgcu=N
+ *   rgs=N | gemm_gather12c_sum dt=f16|bf16 parts=S grid=XxY
+ *       the fields of vptq_quant_gemm_gather12_instance; parts / tpp the split, rgs the most ITEMS one workgroup walks (grid =
+ *       min(n_groups * S, CUs * wgcu)); the sum launch: a thread per output, grid = ceil(out_features / 256) x tokens.
+ * Special values and alignment: as vptq_quant_gemm_gather12 (an output's partial sums are added as IEEE arithmetic has it).
+ * Workspace: contents do not matter before a call - the second kernel reads only words the first wrote in the same call - and are
+ * undefined after it; calls on one stream may share it. */
+VPTQ_API int vptq_quant_gemm_gather12c_supported(const VptqLayerDesc* desc, int tokens, int parts);
+VPTQ_API size_t vptq_quant_gemm_gather12c_workspace_bytes(const VptqLayerDesc* desc, int tokens, int parts);
+VPTQ_API int vptq_quant_gemm_gather12c(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, int parts, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gather12c_instance(const VptqLayerDesc* desc, int tokens, int flags, int parts, char* buf, size_t bytes);
+
 /* Batched decode of the canonical format for 17 - 64 tokens in ONE launch (gemm_k256w_kernel in gemm_k256.hip; added within ABI 12;
  * present when the symbols are).  The layers vptq_quant_gemv serves with gemm_k256_kernel - v = 8, 256 main + 256 residual centroids,
  * one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and bias_permuted), group_size ==

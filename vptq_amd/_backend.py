@@ -177,6 +177,12 @@ EXPORTS = {
     "vptq_quant_gemm_gather12_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_gather12": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gather12_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) the column-parts form of the entry above for layers with few outputs (gemm_gather12c.hip): `parts` behind
+    # the tokens / the flags (0: the library's rule)
+    "vptq_quant_gemm_gather12c_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12c_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12c": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather12c_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     # (added within ABI 12) 17 - 64 tokens of the canonical format in one launch (gemm_k256w_kernel, gemm_k256.hip)
     "vptq_quant_gemm_k256w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_k256w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),

@@ -6,7 +6,9 @@ the per-call `batched_decode_takes`.  `VQuantLinear.forward` and `ops.quant_gemm
 record in the table, a route function and a knob.  Behind the first table stands `BATCHED_DECODE_WIDE_ROUTES` (read by
 `batched_decode_wide_routes`, walked after the first table's routes): a format's route beyond its first window - `gemm_gatherxw_route`,
 17 - 48 tokens of gemm_gatherx's formats - and behind that `BATCHED_DECODE_V12_ROUTES` (`batched_decode_v12_routes`): `gemm_gather12_route`,
-5 - 16 tokens of the vector-length-12 formats, which no record of the first two tables owns.
+5 - 16 tokens of the vector-length-12 formats, which no record of the first two tables owns.  IN FRONT OF that third table a caller walks
+`BATCHED_DECODE_V12_COLUMN_ROUTES` (`batched_decode_v12_column_routes`): `gemm_gather12c_route`, the column-parts form of the same
+kernel for v = 12 layers with few outputs.
 """
 from __future__ import annotations
 
@@ -313,6 +315,47 @@ def gemm_gather12_route(vector_len: int, num_centroids: int, num_res_centroids: 
                min_tok <= tokens <= max_tok for k, kr, p, min_el, min_tok, max_tok in _GEMM_GATHER12_CELLS)
 
 
+# WHICH v = 12 layers take `vptq_quant_gemm_gather12c` (gemm_gather12c.hip: gemm_gather12's kernel with the work split over (row group,
+# column part) and a second small kernel that adds the parts' fp32 sums in a fixed order) for 5 - 16 tokens, in place of the route they
+# have at the knob's "0" (`gemm_gather12_route`'s cells, else two gemv_gatherx launches / the dense route).  Whether a split helps is
+# decided by the ROW-GROUP count (few outputs: the parent kernel leaves most resident workgroups idle), so a cell carries a MOST bound
+# on the index elements beside the least one, like the canonical group's cells: (main centroids, residual centroids, has a permutation,
+# least index elements, most index elements, least tokens, most tokens).  No cell lies under 1 M index elements.  Routed by the rule
+# above `_GEMM_GATHER_CELLS`; tools/gemm_gather12c_bench.py writes the table.  VPTQ_GEMM_GATHER12C=1 / 0 (with VPTQ_TUNING=1): every
+# layer the library splits (`vptq_quant_gemm_gather12c_supported`: at least two 512-column tiles) from 5 to 16 tokens / none.
+#
+# profiles/r38/table.md, profiles/r38/README.md (one MI355X, v12-k65536-4096 / -256 / -0, fp16 and bf16, with and without a permutation,
+# 4096 x 4096 (1.3 M index elements, 86 row groups), 4096 x 1024 (0.3 M, 22), 14336 x 4096 (4.7 M, 86), 4096 x 14336 (4.7 M, 299) and 8192 x
+# 8192 (5.3 M, 171) (columns x outputs), tokens 5 / 8 / 9 / 12 / 16, parts = 0; 300 cells, the entry's bits checked in every one; spreads
+# over 3 % in 9 cells, the largest 5.8 %).  EVERY cell wins by the rule, in both dtypes: 0.40 - 0.93 of the parent-commit route -
+#   4096 x 4096 0.45 - 0.82 (v12-k65536-4096 fp16 with a permutation, 5 / 8 / 16 tokens: 25.2 / 25.2 / 25.7 us against 47.7 / 55.7 / 35.8)
+#   14336 x 4096 0.40 - 0.92 (64.3 / 64.1 / 65.1 against 137.4 / 137.6 (gemm_gather12, its routed cell) / 138.4 (dense))
+#   4096 x 14336 0.52 - 0.88, 8192 x 8192 0.64 - 0.93 (against gemm_gather12 where it is routed: 0.68 - 0.83)
+#   4096 x 1024 0.43 - 0.67, but 0.3 M index elements: under the 1 M floor of every cell, so only the knob reaches it
+# so one region per (format, permutation state): 1 M - 6 M index elements (the largest measured layer has 5.3 M), 5 - 16 tokens.  8192 x
+# 28672 (18.7 M, 598 row groups: more than the resident workgroups, nothing to fill) was not measured and stays with `gemm_gather12`;
+# so do v12-k32768-1024 and the other unmeasured formats.  The regions are by index elements, as every table of this file: a layer of
+# 1 - 6 M elements with many more row groups than the measured ones (2048 columns x 28672 outputs) is routed without having been measured.
+_GEMM_GATHER12C_CELLS = tuple((65536, kr, p, 1 << 20, 6 << 20, 5, 16) for kr in (0, 256, 4096) for p in (0, 1))
+_GEMM_GATHER12C_MODE = (B.tune_env("VPTQ_GEMM_GATHER12C", "auto") or "auto").strip().lower()
+
+
+def gemm_gather12c_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int,
+                         has_perm: Optional[bool] = None) -> bool:
+    """does a layer of this format and shape take `vptq_quant_gemm_gather12c` (parts = 0: the library's rule) for `tokens` tokens?
+    has_perm as in `gemm_gather12_route`.  Pure: no device, no library (whether the library splits the layer is
+    `vptq_quant_gemm_gather12c_supported`'s answer)."""
+    if _GEMM_GATHER12C_MODE in ("0", "off") or not GEMM_GATHER12_MIN_TOKENS <= tokens <= GEMM_GATHER12_MAX_TOKENS or in_features % 8 or \
+            not _v12_owns(vector_len, num_centroids, num_res_centroids):
+        return False
+    if _GEMM_GATHER12C_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any((k, kr) == (num_centroids, num_res_centroids) and (has_perm is None or bool(p) == bool(has_perm)) and
+               max(min_el, 1 << 20) <= n_el <= max_el and min_tok <= tokens <= max_tok
+               for k, kr, p, min_el, max_el, min_tok, max_tok in _GEMM_GATHER12C_CELLS)
+
+
 class BatchedDecodeRoute(NamedTuple):
     """what differs between the batched-decode routes; everything else is one code path in both callers"""
     entry: str                    # the library entry (`entry + "_supported"`: does the library serve this descriptor?)
@@ -326,6 +369,7 @@ class BatchedDecodeRoute(NamedTuple):
     exact_only: bool = False      # the kernel has the reference's roundings only: the CALLER asks the layer's arithmetic, last (it may cost a read-back)
     workspace: bool = False       # the entry takes (workspace, workspace_bytes) in front of the stream (`entry + "_workspace_bytes"` sizes it)
     perm_cells: bool = False      # the route function takes whether the layer has a permutation as a seventh argument: cells per state
+    extra: tuple = ()             # integer arguments the entry takes behind the tokens (`_supported`, `_workspace_bytes`) / the flags (the launch)
 
 
 def _entry_is(*entries):
@@ -365,6 +409,13 @@ BATCHED_DECODE_V12_ROUTES = (
     BatchedDecodeRoute("vptq_quant_gemm_gather12", GEMM_GATHER12_MIN_TOKENS, GEMM_GATHER12_MAX_TOKENS, _v12_owns, gemm_gather12_route,
                        "_GEMM_GATHER12_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True),
 )
+# A fourth table, walked IN FRONT OF the third: the column-parts form of the v = 12 kernel for layers with few outputs.  It owns the
+# third table's formats; a call it takes would otherwise go to the third table's record or to the routes behind it, and with its knob
+# at "0" every answer is that.  extra = (0,): `parts` = the library's rule.
+BATCHED_DECODE_V12_COLUMN_ROUTES = (
+    BatchedDecodeRoute("vptq_quant_gemm_gather12c", GEMM_GATHER12_MIN_TOKENS, GEMM_GATHER12_MAX_TOKENS, _v12_owns, gemm_gather12c_route,
+                       "_GEMM_GATHER12C_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True, extra=(0,)),
+)
 BATCHED_DECODE_MIN_TOKENS = min(r.min_tokens for r in BATCHED_DECODE_ROUTES)   # the union of the windows: what a caller guards with
 BATCHED_DECODE_MAX_TOKENS = max(r.max_tokens for r in BATCHED_DECODE_ROUTES)
 
@@ -388,6 +439,14 @@ def batched_decode_v12_routes(vector_len: int, num_centroids: int, num_res_centr
     """`batched_decode_routes` over `BATCHED_DECODE_V12_ROUTES`: the same static filters; a caller walks these after the other two
     tables'."""
     return _static_routes(BATCHED_DECODE_V12_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm)
+
+
+def batched_decode_v12_column_routes(vector_len: int, num_centroids: int, num_res_centroids: int, num_codebooks: int, outliers: bool,
+                                     norm: bool, has_perm: bool) -> tuple:
+    """`batched_decode_routes` over `BATCHED_DECODE_V12_COLUMN_ROUTES`: the same static filters; a caller walks these in front of
+    `batched_decode_v12_routes`'."""
+    return _static_routes(BATCHED_DECODE_V12_COLUMN_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm,
+                          has_perm)
 
 
 def _static_routes(table, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm, has_perm) -> tuple:

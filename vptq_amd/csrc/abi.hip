@@ -1462,6 +1462,66 @@ int vptq_quant_gemm_gather12_instance(const VptqLayerDesc* d, int tokens, int, c
   return instance_done(t);
 }
 
+// ---- gemm_gather12c.hip (added within ABI 12): vptq_quant_gemm_gather12's layers with few outputs, the work split over (row group,
+// column part): gemm_gather12c_kernel stores raw fp32 sums into the partials region of the workspace, gemm_gather12c_sum_kernel adds
+// them in a fixed order.  The workspace is [x[perm], only with a permutation][partials]; both regions start 256-byte aligned.
+static int gather12c_validate(const VptqLayerDesc* d, int tokens, int parts) {
+  if (tokens < 1 || tokens > 16) return fail(VPTQ_E_TOKENS, "tokens %d outside [1, 16]", tokens);
+  if (!vptq::gemm_gather12c_decide(*d, tokens, parts).serves)
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gather12c serves the layers of gemm_gather12 (v = 12, 16384 ... 65536 main centroids, ...) that split into at "
+                "least two column parts of whole 512-column tiles (parts >= 0; parts = %d)", parts);
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gather12c_supported(const VptqLayerDesc* d, int tokens, int parts) {
+  return validate_layer(d) == VPTQ_OK && tokens >= 1 && tokens <= 16 && vptq::gemm_gather12c_decide(*d, tokens, parts).serves ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gather12c_workspace_bytes(const VptqLayerDesc* d, int tokens, int parts) {
+  if (!vptq_quant_gemm_gather12c_supported(d, tokens, parts)) return 0;
+  return vptq::gemm_gather_px_workspace_bytes(*d, tokens) + vptq::gemm_gather12c_decide(*d, tokens, parts).partial_bytes;
+}
+
+int vptq_quant_gemm_gather12c(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, int parts, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  if (const int rc = gather12c_validate(d, tokens, parts)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12c: x must be 16-byte aligned");
+  const size_t xp_bytes = vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+  const size_t need = xp_bytes + vptq::gemm_gather12c_decide(*d, tokens, parts).partial_bytes;
+  if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gather12c: workspace of %zu bytes needed", need);
+  if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12c: the workspace must be 16-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+  void* const partials = (char*)workspace + xp_bytes;
+  if (xp_bytes == 0) {   // no permutation
+    const hipError_t e = vptq::launch_gemm_gather12c(*d, x, y, tokens, out_f32, parts, partials, st);
+    return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12c launch");
+  }
+  hipError_t e = vptq::launch_permute_x_tokens(*d, x, workspace, tokens, st);
+  if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  e = vptq::launch_gemm_gather12c(vptq::gemm_gather_px_plain(*d), workspace, y, tokens, out_f32, parts, partials, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12c launch");
+}
+
+int vptq_quant_gemm_gather12c_instance(const VptqLayerDesc* d, int tokens, int, int parts, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  if (const int rc = gather12c_validate(d, tokens, parts)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const vptq::GemmGatherPxDecision X = vptq::gemm_gather_px_decide(*d, tokens);
+  if (X.perm) t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d | ", X.g, X.tok, X.grid_x, X.grid_y, X.tpt);
+  const vptq::GemmGather12cDecision D = vptq::gemm_gather12c_decide(vptq::gemm_gather_px_plain(*d), tokens, parts);
+  t.add("gemm_gather12c dt=%s ib=%d rb=%d res=%s tok=%d tiles=%d parts=%d tpp=%d wgcu=%d rgs=%d | gemm_gather12c_sum dt=%s parts=%d grid=%dx%d",
+        dt_text(D.base.f16), D.base.ib, D.base.rb, D.base.res == 0 ? "none" : D.base.res == 1 ? "lds" : "l2", D.base.tok, D.base.tiles, D.parts,
+        D.tpp, D.base.wgcu, D.rgs, dt_text(D.base.f16), D.parts, D.sum_grid_x, D.sum_grid_y);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // ---- gemm_gather.hip's grouped launch (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gather, 1 - 16 tokens, in ONE
 // launch of gemm_gather_grouped_kernel, behind one permute launch per DISTINCT perm pointer of the members.
 // What a grouped call IS, decided once for the workspace query, the launcher and the `_instance`: which xp block a member reads (-1:

@@ -41,6 +41,7 @@
 // LDS: 48 KiB + the table.  Registers: g12_min_wg workgroups per CU; no instantiation has scratch (profiles/r37/listings.md).  No
 // atomics, no scratch, plain vector stores.
 // NOT HERE: 17 - 48 tokens (token blocks), sibling groups, v = 6 (8 vector-rows per 48 outputs), the folded / selective arithmetics.
+// gemm_gather12c.hip holds a COPY of the row-group body (the column-parts form): A CHANGE TO THE BODY HERE BELONGS THERE TOO.
 #include "gemm_gather_tile.h"
 #include "launch.h"
 

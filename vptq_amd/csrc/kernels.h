@@ -296,6 +296,22 @@ struct GemmGather12Decision { bool f16; int ib, rb, res, res_bytes, tok, tiles, 
 GemmGather12Decision gemm_gather12_decide(const VptqLayerDesc& d, int tokens);
 hipError_t launch_gemm_gather12(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, hipStream_t st);
 
+// gemm_gather12c.hip - the column-parts form of gemm_gather12 for layers with few outputs: the work item is (row group, column part),
+// S parts of tpp tiles per row group; gemm_gather12c_kernel<DT, RES> stores raw fp32 sums into partials [S][tokens][n_groups x 48] and
+// gemm_gather12c_sum_kernel<DT> adds them in ascending part order, adds the output bias and rounds once; plain form only.
+// parts > 0: a request (tpp = ceil(tiles / min(parts, tiles, 16)), S = ceil(tiles / tpp)); parts == 0: the library's rule.
+// base: the parent's decision; items = n_groups x parts, grid = min(items, CUs x wgcu), rgs the most items one workgroup walks, op the
+// row length of the partials, serves: the parent's eligibility and parts >= 2
+struct GemmGather12cDecision {
+  GemmGather12Decision base;
+  int parts, tpp, items, grid, rgs, op, sum_grid_x, sum_grid_y;
+  size_t partial_bytes;
+  bool serves;
+};
+GemmGather12cDecision gemm_gather12c_decide(const VptqLayerDesc& d, int tokens, int parts);
+hipError_t launch_gemm_gather12c(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, int parts, void* partials,
+                                 hipStream_t st);
+
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)
 // - scale_permuted / bias_permuted as scale / bias, no permutation - with x = xp: the bits of the layer's own entry

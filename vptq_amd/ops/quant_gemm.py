@@ -19,9 +19,9 @@ import torch
 from torch.nn import functional as F
 
 from vptq_amd import _backend as B
-from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_routes, batched_decode_wide_routes
+from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_wide_routes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12c", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -210,15 +210,15 @@ def quant_gemm(
         kr = num_res_centroids if enable_residual else 0
         static = (vector_len, num_centroids, kr, num_codebooks, enable_outlier, weight_scale is not None and weight_bias is not None,
                   perm is not None)
-        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) + batched_decode_v12_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
+        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) + batched_decode_v12_column_routes(*static) + batched_decode_v12_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
         for r in routes:
             if not batched_decode_takes(r, vector_len, num_centroids, kr, out_features, in_features, tokens, _FLAGS, perm is not None) or \
-                    x.data_ptr() % 16 or not getattr(B.lib(), r.entry + "_supported")(gdesc, tokens):
+                    x.data_ptr() % 16 or not getattr(B.lib(), r.entry + "_supported")(gdesc, tokens, *r.extra):
                 continue
             if r.exact_only and not ((_FLAGS | _safe_flags(indices, centroids, residual_centroids if enable_residual else None, weight_scale,
                                                            weight_bias, gdesc, in_features, out_features)) & B.GEMV_EXACT):
                 continue
-            y = quant_gemm_batched_launch(r.entry, gdesc, x, out_features, _FLAGS, r.workspace)
+            y = quant_gemm_batched_launch(r.entry, gdesc, x, out_features, _FLAGS, r.workspace, extra=r.extra)
             if y is not None:
                 return y
     if desc is not None:
@@ -282,12 +282,14 @@ def quant_gemm_fused(x: torch.Tensor, desc, out_features: int) -> torch.Tensor:
     return y
 
 
-def quant_gemm_batched_launch(entry: str, desc, x: torch.Tensor, out_features: int, flags: int, workspace: bool = False, repack=None):
+def quant_gemm_batched_launch(entry: str, desc, x: torch.Tensor, out_features: int, flags: int, workspace: bool = False, repack=None,
+                              extra: tuple = ()):
     """ONE launch of a batched-decode entry (the wrappers below, the routes of vptq_amd/batched_decode.py) over all tokens of x, on x's
     device and its current stream; `flags` are the launch's (GEMV_OUT_F32: y is float32).  workspace: the entry takes (workspace,
     workspace_bytes) in front of the stream - this (device, stream)'s `B.gemv_workspace`, sized by `entry + "_workspace_bytes"`;
     None where the entry needs one and there is none: a stream capture is in progress and the buffer is too small (nothing is
-    allocated or launched then).  repack(desc, device index, stream) -> the descriptor to launch with (compact mode)."""
+    allocated or launched then).  repack(desc, device index, stream) -> the descriptor to launch with (compact mode).  extra: integer
+    arguments the entry takes behind the tokens of its workspace query and behind the flags of the launch (gemm_gather12c: parts)."""
     shape, dev = x.shape, x.device
     tokens = x.numel() // shape[-1]
     if not x.is_contiguous():
@@ -299,14 +301,14 @@ def quant_gemm_batched_launch(entry: str, desc, x: torch.Tensor, out_features: i
         if workspace or repack is not None:
             dev_index = dev.index if dev.index is not None else torch.cuda.current_device()
         if workspace:
-            need = getattr(lib, entry + "_workspace_bytes")(desc, tokens)
+            need = getattr(lib, entry + "_workspace_bytes")(desc, tokens, *extra)
             ws_args = B.gemv_workspace(dev_index, sp, need)
             if need and ws_args[0] is None:
                 return None
         y = torch.empty(shape[:-1] + (out_features,), dtype=torch.float32 if flags & B.GEMV_OUT_F32 else x.dtype, device=dev)
         if repack is not None:
             desc = repack(desc, dev_index, sp)
-        rc = getattr(lib, entry)(desc, x.data_ptr(), y.data_ptr(), tokens, flags, *ws_args, sp)
+        rc = getattr(lib, entry)(desc, x.data_ptr(), y.data_ptr(), tokens, flags, *extra, *ws_args, sp)
     if rc:
         B.check(rc, entry)
     return y
@@ -362,6 +364,23 @@ def quant_gemm_gather12(x: torch.Tensor, desc, out_features: int, out_f32: bool 
     y = quant_gemm_batched_launch("vptq_quant_gemm_gather12", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True)
     if y is None:
         raise RuntimeError("quant_gemm_gather12: the stream's workspace is too small and cannot grow during a capture "
+                           "(call it once, or vptq_amd.prepare_model, before capturing)")
+    return y
+
+
+def quant_gemm_gather12c(x: torch.Tensor, desc, out_features: int, parts: int = 0, out_f32: bool = False) -> torch.Tensor:
+    """`quant_gemm_gather12` for a layer with FEW OUTPUTS (`vptq_quant_gemm_gather12c`, gemm_gather12c.hip): the same kernel body with the
+    work split over (row group of 48 outputs, column part) - so that a 4096-output layer fills the device's resident workgroups - and
+    a second small kernel that adds the parts' fp32 sums in ascending order, adds the output bias and rounds once; no atomics: two
+    calls give the same bits.  parts: the column parts asked for (the library cuts whole 512-column tiles, at most 16 parts); 0: the
+    library's rule.  The partial sums (and x[:, perm] of a layer with a permutation) go through this stream's workspace
+    (`B.gemv_workspace`).  `desc` = a LayerDesc of a layer `vptq_quant_gemm_gather12c_supported(desc, tokens, parts)` accepts;
+    out_f32: the un-rounded fp32 sums.  Raises where a stream capture is in progress and the workspace is too small (`prepare_model`
+    sizes it beforehand)."""
+    y = quant_gemm_batched_launch("vptq_quant_gemm_gather12c", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True,
+                                  extra=(int(parts),))
+    if y is None:
+        raise RuntimeError("quant_gemm_gather12c: the stream's workspace is too small and cannot grow during a capture "
                            "(call it once, or vptq_amd.prepare_model, before capturing)")
     return y
 
