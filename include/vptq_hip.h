@@ -764,6 +764,42 @@ VPTQ_API int vptq_quant_gemm_gather12c(const VptqLayerDesc* desc, const void* x,
                                        size_t workspace_bytes, void* stream);
 VPTQ_API int vptq_quant_gemm_gather12c_instance(const VptqLayerDesc* desc, int tokens, int flags, int parts, char* buf, size_t bytes);
 
+/* 17 - 48 TOKENS of vptq_quant_gemm_gather12's layers in ONE launch (gemm_gather12w_kernel and gemm_gather12w_sum_kernel in
+ * gemm_gather12w.hip; added within ABI 12; present when the symbols are): in place of vptq_dequant + a dense GEMM, which rebuilds the
+ * whole W in memory on every call.  TB = 2 (17 - 32 tokens) / 3 (33 - 48) blocks of 16 tokens share one pass over the index windows,
+ * gathers, rebuilt weights and tiles; a B operand read from the tile feeds every token block before the next read.  The work item is
+ * vptq_quant_gemm_gather12c's (row group, column part), with S >= 1 parts: at S == 1 the kernel adds the output bias, rounds and
+ * writes y itself and no second kernel runs; at S >= 2 every item stores raw fp32 sums into partials[p][token][n_groups * 48] and the
+ * second kernel adds them in ASCENDING part order in fp32, adds the output bias and rounds once.  No atomics: two calls give the same
+ * bits.  A token's bits depend neither on its place in the batch nor on the batch size: at S == 1 they are what
+ * vptq_quant_gemm_gather12 gives that token in a call of <= 16 tokens, at S >= 2 what vptq_quant_gemm_gather12c gives it with the same
+ * (S, tpp).  The layers, x, y, flags, the rebuilt weights (vptq_dequant's bits) and the treatment of a permutation
+ * (permute_x_tokens_kernel in front) are vptq_quant_gemm_gather12's.  Nothing is allocated: graph-capturable.
+ *   parts == 1: no split.  parts >= 2: a request - tpp = ceil(tiles / min(parts, tiles, 16)), S = ceil(tiles / tpp), tiles =
+ *   ceil(group_size / 512): vptq_quant_gemm_gather12c's split for the same request.  parts == 0: the library's rule
+ *   (gemm_gather12w_decide; profiles/r39).  parts < 0: not served.
+ * vptq_quant_gemm_gather12w_supported: 1 where vptq_quant_gemm_gather12_supported(desc, 16) is 1, 17 <= tokens <= 48 and parts >= 0,
+ *   else 0; host logic.
+ * vptq_quant_gemm_gather12w_workspace_bytes: two regions - for a layer with a permutation tokens * group_size * 2 rounded up to 256,
+ *   then, only when S >= 2, S * tokens * n_groups * 48 * 4 bytes of partial sums (n_groups = ceil(num_indices / 4)); both regions start
+ *   256-byte aligned; 0 where _supported answers 0 and for a layer without a permutation at S == 1.
+ * vptq_quant_gemm_gather12w: NULL desc / x / y VPTQ_E_NULL; tokens outside [17, 48] VPTQ_E_TOKENS (checked before the layer); a (layer,
+ *   parts) it does not serve VPTQ_E_UNSUPPORTED; an x that is not 16-byte aligned VPTQ_E_ALIGN; then, where the query answers more
+ *   than 0, a NULL workspace or fewer workspace_bytes than that VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned
+ *   VPTQ_E_ALIGN; nothing is launched then.
+ * vptq_quant_gemm_gather12w_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   [permute_x_tokens g=N tok=N grid=XxY tpt=4 | ]gemm_gather12w dt=f16|bf16 ib=N rb=N res=none|lds|l2 tok=N tb=2|3 tiles=N parts=S tpp=N
+ *   wgcu=N rgs=N[ | gemm_gather12w_sum dt=f16|bf16 parts=S grid=XxY]
+ *       the fields of vptq_quant_gemm_gather12c_instance; tb the token blocks; wgcu the resident workgroups per CU of this
+ *       instantiation (1 for tb=3 with a residual table); the sum launch only when S >= 2.
+ * Special values and alignment: as vptq_quant_gemm_gather12.  Workspace: contents do not matter before a call and are undefined
+ * after it; calls on one stream may share it. */
+VPTQ_API int vptq_quant_gemm_gather12w_supported(const VptqLayerDesc* desc, int tokens, int parts);
+VPTQ_API size_t vptq_quant_gemm_gather12w_workspace_bytes(const VptqLayerDesc* desc, int tokens, int parts);
+VPTQ_API int vptq_quant_gemm_gather12w(const VptqLayerDesc* desc, const void* x, void* y, int tokens, int flags, int parts, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gather12w_instance(const VptqLayerDesc* desc, int tokens, int flags, int parts, char* buf, size_t bytes);
+
 /* Batched decode of the canonical format for 17 - 64 tokens in ONE launch (gemm_k256w_kernel in gemm_k256.hip; added within ABI 12;
  * present when the symbols are).  The layers vptq_quant_gemv serves with gemm_k256_kernel - v = 8, 256 main + 256 residual centroids,
  * one codebook group, no outlier columns, weight_scale and weight_bias set (with perm: scale_permuted and bias_permuted), group_size ==

@@ -11,7 +11,11 @@ rule) - the sweep the rule is chosen from; a forced count the layer cannot be cu
 launch gives the same bits, and they lie within one unit of the last place + the fp32 summation bound of the product of the same x with
 vptq_dequant's W summed in fp64 (first layer of the ring).  One JSON line per row; --md appends a markdown table row per measured row;
 --budget-s: no new layer is started after that many seconds (the cells not reached are printed as "not measured").
-    python tools/gemm_gather12c_bench.py --md profiles/r38/table.md"""
+--wide: the 17 - 48 token entry instead (vptq_quant_gemm_gather12w: gemm_gather12w_kernel [+ gemm_gather12w_sum_kernel] in
+gemm_gather12w.hip) at 17 / 24 / 32 / 33 / 40 / 48 tokens unless --tokens says otherwise, against `VQuantLinear.forward` with ITS knob at 0
+(`_GEMM_GATHER12W_MODE = "0"`): the dense route; parts 1 = no split can be asked for beside 0 and the forced counts.
+    python tools/gemm_gather12c_bench.py --md profiles/r38/table.md
+    python tools/gemm_gather12c_bench.py --wide --md profiles/r39/table.md"""
 import argparse, ctypes, json, os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -25,7 +29,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--formats", default="65536,4096;65536,256;65536,0", help="k,kr;... (vector length 12)")
 ap.add_argument("--shapes", default="4096,4096;14336,4096;4096,1024;4096,14336;8192,8192", help="I,O;I,O;... (input columns, outputs)")
 ap.add_argument("--dtypes", default="f16,bf16")
-ap.add_argument("--tokens", default="5,8,9,12,16")
+ap.add_argument("--tokens", default="")
+ap.add_argument("--wide", action="store_true", help="time vptq_quant_gemm_gather12w (17 - 48 tokens) instead")
 ap.add_argument("--perms", default="0,1")
 ap.add_argument("--parts", default="0", help="part counts: 0 = the library's rule; the sweep: 0,2,3,4,6,8,14,16")
 ap.add_argument("--reps", type=int, default=3)
@@ -34,11 +39,13 @@ ap.add_argument("--ring-bytes", type=int, default=512 << 20)
 ap.add_argument("--budget-s", type=float, default=0.0)
 ap.add_argument("--md", default="")
 a = ap.parse_args()
+a.tokens = a.tokens or ("17,24,32,33,40,48" if a.wide else "5,8,9,12,16")
+NAME = "gemm_gather12w" if a.wide else "gemm_gather12c"
 t_start = time.time()
 dev = torch.device("cuda", 0); g = torch.Generator(device=dev).manual_seed(0); lib = B.lib()
 box = f"{torch.cuda.get_device_name(0)}, {torch.cuda.get_device_properties(0).multi_processor_count} CUs"
 print(json.dumps(dict(box=box)), flush=True)
-bd._GEMM_GATHER12C_MODE = "0"   # the parent is the route of the parent commit
+setattr(bd, "_GEMM_GATHER12W_MODE" if a.wide else "_GEMM_GATHER12C_MODE", "0")   # the parent is the route of the parent commit
 rows, skipped = [], []
 V = 12
 
@@ -106,7 +113,7 @@ for I, O, k, kr, perm, dname in cells:
         ref, mag = x[0].double() @ W0.t(), x[0].double().abs() @ W0.abs().t()
         # one rounding of the output + fp32 sums in the kernels' order (2^-18 of the sum of the terms' magnitudes, with room)
         bound = ref.abs() * (2.0 ** (-7 if dname == "bf16" else -10)) + mag * 2.0 ** -18 + 2.0 ** -24
-        parent_name = "gemm_gather12" if bd.gemm_gather12_route(V, k, kr, O, I, tok, bool(perm)) else "2 x gemv_gatherx" if tok <= 8 else "dense"
+        parent_name = "dense" if a.wide else "gemm_gather12" if bd.gemm_gather12_route(V, k, kr, O, I, tok, bool(perm)) else "2 x gemv_gatherx" if tok <= 8 else "dense"
 
         def run_parent():
             for m in layers:
@@ -114,24 +121,25 @@ for I, O, k, kr, perm, dname in cells:
         seen, t_par = set(), None
         for parts in [int(p) for p in a.parts.split(",")]:
             text = ctypes.create_string_buffer(320)
-            if lib.vptq_quant_gemm_gather12c_supported(d0, tok, parts) != 1:
+            if getattr(lib, f"vptq_quant_{NAME}_supported")(d0, tok, parts) != 1:
                 continue
-            B.check(lib.vptq_quant_gemm_gather12c_instance(d0, tok, 0, parts, text, len(text)), "instance")
+            B.check(getattr(lib, f"vptq_quant_{NAME}_instance")(d0, tok, 0, parts, text, len(text)), "instance")
             inst = text.value.decode()
             if parts and inst in seen:   # (a forced count that cuts the layer as a smaller one did)
                 continue
             seen.add(inst)
-            need = lib.vptq_quant_gemm_gather12c_workspace_bytes(d0, tok, parts)
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            need = getattr(lib, f"vptq_quant_{NAME}_workspace_bytes")(d0, tok, parts)
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            entry = getattr(lib, f"vptq_quant_{NAME}")
 
             def run_new():
                 for d, _ in descs:
-                    B.check(lib.vptq_quant_gemm_gather12c(d, x.data_ptr(), y.data_ptr(), tok, 0, parts, ws.data_ptr(), need, sp()), "gemm_gather12c")
+                    B.check(entry(d, x.data_ptr(), y.data_ptr(), tok, 0, parts, ws.data_ptr(), need, sp()), NAME)
             # (the first layer of the ring: the entry against dequant's W in fp64, and twice, the second time over a refilled workspace)
-            B.check(lib.vptq_quant_gemm_gather12c(d0, x.data_ptr(), y.data_ptr(), tok, 0, parts, ws.data_ptr(), need, sp()), "gemm_gather12c")
+            B.check(entry(d0, x.data_ptr(), y.data_ptr(), tok, 0, parts, ws.data_ptr(), need, sp()), NAME)
             got = y.clone()
             ws.fill_(0xCD)
-            B.check(lib.vptq_quant_gemm_gather12c(d0, x.data_ptr(), y.data_ptr(), tok, 0, parts, ws.data_ptr(), need, sp()), "gemm_gather12c")
+            B.check(entry(d0, x.data_ptr(), y.data_ptr(), tok, 0, parts, ws.data_ptr(), need, sp()), NAME)
             torch.cuda.synchronize()
             same = bool(torch.equal(got.view(torch.int16), y.view(torch.int16))) and bool(((got[0].double() - ref).abs() <= bound).all())
             t_new, first = [], t_par is None

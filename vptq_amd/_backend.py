@@ -183,6 +183,12 @@ EXPORTS = {
     "vptq_quant_gemm_gather12c_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
     "vptq_quant_gemm_gather12c": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gather12c_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 17 - 48 tokens of the same layers as 2 / 3 token blocks over the column-parts walk (gemm_gather12w.hip):
+    # `parts` as above, and 1 = no split
+    "vptq_quant_gemm_gather12w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12w_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather12w_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     # (added within ABI 12) 17 - 64 tokens of the canonical format in one launch (gemm_k256w_kernel, gemm_k256.hip)
     "vptq_quant_gemm_k256w_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int]),
     "vptq_quant_gemm_k256w": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, C.c_int, C.c_int, _vp]),

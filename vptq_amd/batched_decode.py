@@ -8,7 +8,8 @@ record in the table, a route function and a knob.  Behind the first table stands
 17 - 48 tokens of gemm_gatherx's formats - and behind that `BATCHED_DECODE_V12_ROUTES` (`batched_decode_v12_routes`): `gemm_gather12_route`,
 5 - 16 tokens of the vector-length-12 formats, which no record of the first two tables owns.  IN FRONT OF that third table a caller walks
 `BATCHED_DECODE_V12_COLUMN_ROUTES` (`batched_decode_v12_column_routes`): `gemm_gather12c_route`, the column-parts form of the same
-kernel for v = 12 layers with few outputs.
+kernel for v = 12 layers with few outputs.  BEHIND all four stands `BATCHED_DECODE_V12_WIDE_ROUTES` (`batched_decode_v12_wide_routes`):
+`gemm_gather12w_route`, 17 - 48 tokens of the v = 12 formats (token blocks over the column-parts walk), a window no other record has.
 """
 from __future__ import annotations
 
@@ -356,6 +357,49 @@ def gemm_gather12c_route(vector_len: int, num_centroids: int, num_res_centroids:
                for k, kr, p, min_el, max_el, min_tok, max_tok in _GEMM_GATHER12C_CELLS)
 
 
+# WHICH v = 12 layers take `vptq_quant_gemm_gather12w` (gemm_gather12w.hip: 2 / 3 blocks of 16 tokens over gemm_gather12c's walk of (row
+# group, column part) items; one part: the kernel writes y itself, else a second small kernel adds the parts' fp32 sums in a fixed
+# order; a layer with a column permutation: x[perm] written once into the stream's workspace in front) for 17 - 48 tokens, in place of
+# the dense route (vptq_dequant + F.linear) they have at the knob's "0".  A cell is `_GEMM_GATHER12C_CELLS`' (main centroids, residual
+# centroids, has a permutation, least index elements, most index elements, least tokens, most tokens); none lies under 1 M index
+# elements; routed by the rule above `_GEMM_GATHER_CELLS` (beats the dense route by more than the larger of 5 % and three times the
+# larger run-to-run spread, in every measured cell of the region, in both dtypes; the routed token counts of a layer are one interval);
+# tools/gemm_gather12c_bench.py --wide writes the table.  VPTQ_GEMM_GATHER12W=1 / 0 (with VPTQ_TUNING=1): every layer
+# `vptq_quant_gemm_gather12w_supported` accepts from 17 to 48 tokens / none.
+#
+# profiles/r39/table.md, profiles/r39/README.md (one MI355X, v12-k65536-4096 / -256 / -0, fp16 and bf16, with and without a permutation, 4096 x
+# 4096, 14336 x 4096, 4096 x 1024, 4096 x 14336, 8192 x 8192 and 8192 x 28672 (columns x outputs), tokens 17 / 24 / 32 / 33 / 40 / 48, parts = 0;
+# 432 cells, the entry's bits checked in every one, 370 win; spreads over 3 % in 20 cells, the largest 6.5 %):
+#   17 - 32 tokens (two token blocks): 0.39 - 0.93 of the dense route; every cell wins except v12-k65536-4096 bf16 WITHOUT a permutation on
+#     8192 x 8192 and 14336 x 4096 (0.96 - 0.99) and on 4096 x 14336 at 32 tokens (0.95), and one fp16 cell of v12-k65536-0 on 4096 x 4096
+#     (0.82, by its spread)
+#   33 - 48 tokens (three): v12-k65536-0 wins everywhere from 4.7 M index elements (0.46 - 0.82); with a residual table the kernel runs at
+#     ONE workgroup per CU there: without a permutation 0.89 - 1.21 on the layers up to 5.3 M (bf16 loses in every such cell) and 0.72 - 1.01 at
+#     8192 x 28672; 4096 x 4096 0.93 - 1.18 with or without one; with a permutation it wins from 4.7 M up (0.53 - 0.93; one bf16 cell at 48
+#     tokens 0.96)
+# NO CELL IS SHIPPED YET: the regions that win in every measured cell are listed in profiles/r39/README.md, but the suite was not run
+# with them in place, so the entry is reached by the knob (and `ops.quant_gemm_gather12w`) alone.
+_GEMM_GATHER12W_CELLS = ()
+GEMM_GATHER12W_MIN_TOKENS, GEMM_GATHER12W_MAX_TOKENS = 17, 48
+_GEMM_GATHER12W_MODE = (B.tune_env("VPTQ_GEMM_GATHER12W", "auto") or "auto").strip().lower()
+
+
+def gemm_gather12w_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features: int, in_features: int, tokens: int,
+                         has_perm: Optional[bool] = None) -> bool:
+    """does a layer of this format and shape take `vptq_quant_gemm_gather12w` (parts = 0: the library's rule) for `tokens` tokens?
+    has_perm as in `gemm_gather12_route`.  Pure: no device, no library (whether the library serves the layer is
+    `vptq_quant_gemm_gather12w_supported`'s answer)."""
+    if _GEMM_GATHER12W_MODE in ("0", "off") or not GEMM_GATHER12W_MIN_TOKENS <= tokens <= GEMM_GATHER12W_MAX_TOKENS or in_features % 8 or \
+            not _v12_owns(vector_len, num_centroids, num_res_centroids):
+        return False
+    if _GEMM_GATHER12W_MODE in ("1", "on"):
+        return True
+    n_el = ((out_features + vector_len - 1) // vector_len) * in_features
+    return any((k, kr) == (num_centroids, num_res_centroids) and (has_perm is None or bool(p) == bool(has_perm)) and
+               max(min_el, 1 << 20) <= n_el <= max_el and min_tok <= tokens <= max_tok
+               for k, kr, p, min_el, max_el, min_tok, max_tok in _GEMM_GATHER12W_CELLS)
+
+
 class BatchedDecodeRoute(NamedTuple):
     """what differs between the batched-decode routes; everything else is one code path in both callers"""
     entry: str                    # the library entry (`entry + "_supported"`: does the library serve this descriptor?)
@@ -404,7 +448,8 @@ BATCHED_DECODE_WIDE_ROUTES = (
 )
 # A third table, walked after the two above: the formats of vector length 12, which no record above owns (`_batched_decode_entry`
 # answers None for them), so no call is taken from a route above.  A permuted layer and a plain one take the same entry (perm=None),
-# which gathers x[perm] into the workspace itself.  17 - 48 tokens, sibling groups and v = 6 have no record: they keep their routes.
+# which gathers x[perm] into the workspace itself.  17 - 48 tokens are the fifth table's; sibling groups and v = 6 have no record: they keep
+# their routes.
 BATCHED_DECODE_V12_ROUTES = (
     BatchedDecodeRoute("vptq_quant_gemm_gather12", GEMM_GATHER12_MIN_TOKENS, GEMM_GATHER12_MAX_TOKENS, _v12_owns, gemm_gather12_route,
                        "_GEMM_GATHER12_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True),
@@ -415,6 +460,12 @@ BATCHED_DECODE_V12_ROUTES = (
 BATCHED_DECODE_V12_COLUMN_ROUTES = (
     BatchedDecodeRoute("vptq_quant_gemm_gather12c", GEMM_GATHER12_MIN_TOKENS, GEMM_GATHER12_MAX_TOKENS, _v12_owns, gemm_gather12c_route,
                        "_GEMM_GATHER12C_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True, extra=(0,)),
+)
+# A fifth table, walked BEHIND the four above: the v = 12 formats from the 17th token on, a window no record above has, so no call is
+# taken from a route above and with its knob at "0" every answer is what it was.  extra = (0,): `parts` = the library's rule.
+BATCHED_DECODE_V12_WIDE_ROUTES = (
+    BatchedDecodeRoute("vptq_quant_gemm_gather12w", GEMM_GATHER12W_MIN_TOKENS, GEMM_GATHER12W_MAX_TOKENS, _v12_owns, gemm_gather12w_route,
+                       "_GEMM_GATHER12W_MODE", None, B.GEMV_FORCE_GENERIC, workspace=True, perm_cells=True, extra=(0,)),
 )
 BATCHED_DECODE_MIN_TOKENS = min(r.min_tokens for r in BATCHED_DECODE_ROUTES)   # the union of the windows: what a caller guards with
 BATCHED_DECODE_MAX_TOKENS = max(r.max_tokens for r in BATCHED_DECODE_ROUTES)
@@ -446,6 +497,14 @@ def batched_decode_v12_column_routes(vector_len: int, num_centroids: int, num_re
     """`batched_decode_routes` over `BATCHED_DECODE_V12_COLUMN_ROUTES`: the same static filters; a caller walks these in front of
     `batched_decode_v12_routes`'."""
     return _static_routes(BATCHED_DECODE_V12_COLUMN_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm,
+                          has_perm)
+
+
+def batched_decode_v12_wide_routes(vector_len: int, num_centroids: int, num_res_centroids: int, num_codebooks: int, outliers: bool,
+                                   norm: bool, has_perm: bool) -> tuple:
+    """`batched_decode_routes` over `BATCHED_DECODE_V12_WIDE_ROUTES`: the same static filters; a caller walks these behind the four
+    other tables'."""
+    return _static_routes(BATCHED_DECODE_V12_WIDE_ROUTES, vector_len, num_centroids, num_res_centroids, num_codebooks, outliers, norm,
                           has_perm)
 
 

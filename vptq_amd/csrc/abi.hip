@@ -1522,6 +1522,71 @@ int vptq_quant_gemm_gather12c_instance(const VptqLayerDesc* d, int tokens, int, 
   return instance_done(t);
 }
 
+// ---- gemm_gather12w.hip (added within ABI 12): 17 - 48 tokens of vptq_quant_gemm_gather12's layers as 2 / 3 blocks of 16 tokens over
+// gemm_gather12c's (row group, column part) items.  One part: gemm_gather12w_kernel writes y itself; S >= 2: it stores raw fp32 sums
+// into the partials region and gemm_gather12w_sum_kernel adds them in a fixed order.  The workspace is [x[perm], only with a
+// permutation][partials, only when S >= 2]; both regions start 256-byte aligned.
+static int gather12w_validate(const VptqLayerDesc* d, int tokens, int parts) {
+  if (tokens < 17 || tokens > 48) return fail(VPTQ_E_TOKENS, "tokens %d outside [17, 48]", tokens);
+  if (!vptq::gemm_gather12w_decide(*d, tokens, parts).serves)
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gather12w serves the layers of gemm_gather12 (v = 12, 16384 ... 65536 main centroids, ...) in column parts of "
+                "whole 512-column tiles (parts >= 0; parts = %d)", parts);
+  return VPTQ_OK;
+}
+
+int vptq_quant_gemm_gather12w_supported(const VptqLayerDesc* d, int tokens, int parts) {
+  return validate_layer(d) == VPTQ_OK && tokens >= 17 && tokens <= 48 && vptq::gemm_gather12w_decide(*d, tokens, parts).serves ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gather12w_workspace_bytes(const VptqLayerDesc* d, int tokens, int parts) {
+  if (!vptq_quant_gemm_gather12w_supported(d, tokens, parts)) return 0;
+  return vptq::gemm_gather_px_workspace_bytes(*d, tokens) + vptq::gemm_gather12w_decide(*d, tokens, parts).partial_bytes;
+}
+
+int vptq_quant_gemm_gather12w(const VptqLayerDesc* d, const void* x, void* y, int tokens, int flags, int parts, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (const int rc = validate_layer(d)) return rc;
+  if (!x || !y) return fail(VPTQ_E_NULL, "x / y is NULL");
+  if (const int rc = gather12w_validate(d, tokens, parts)) return rc;
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12w: x must be 16-byte aligned");
+  const size_t xp_bytes = vptq::gemm_gather_px_workspace_bytes(*d, tokens);
+  const size_t need = xp_bytes + vptq::gemm_gather12w_decide(*d, tokens, parts).partial_bytes;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool out_f32 = (flags & VPTQ_GEMV_OUT_F32) != 0;
+  if (need == 0) {   // no permutation, one part: the kernel alone, the workspace is not touched
+    const hipError_t e = vptq::launch_gemm_gather12w(*d, x, y, tokens, out_f32, parts, nullptr, st);
+    return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12w launch");
+  }
+  if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gather12w: workspace of %zu bytes needed", need);
+  if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12w: the workspace must be 16-byte aligned");
+  void* const partials = need > xp_bytes ? (char*)workspace + xp_bytes : nullptr;
+  if (xp_bytes == 0) {   // no permutation
+    const hipError_t e = vptq::launch_gemm_gather12w(*d, x, y, tokens, out_f32, parts, partials, st);
+    return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12w launch");
+  }
+  hipError_t e = vptq::launch_permute_x_tokens(*d, x, workspace, tokens, st);
+  if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  e = vptq::launch_gemm_gather12w(vptq::gemm_gather_px_plain(*d), workspace, y, tokens, out_f32, parts, partials, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12w launch");
+}
+
+int vptq_quant_gemm_gather12w_instance(const VptqLayerDesc* d, int tokens, int, int parts, char* buf, size_t bytes) {
+  if (!d || !buf || bytes < 1) return fail(VPTQ_E_NULL, "desc / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = validate_layer(d)) return rc;
+  if (const int rc = gather12w_validate(d, tokens, parts)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const vptq::GemmGatherPxDecision X = vptq::gemm_gather_px_decide(*d, tokens);
+  if (X.perm) t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d | ", X.g, X.tok, X.grid_x, X.grid_y, X.tpt);
+  const vptq::GemmGather12wDecision D = vptq::gemm_gather12w_decide(vptq::gemm_gather_px_plain(*d), tokens, parts);
+  t.add("gemm_gather12w dt=%s ib=%d rb=%d res=%s tok=%d tb=%d tiles=%d parts=%d tpp=%d wgcu=%d rgs=%d", dt_text(D.base.f16), D.base.ib, D.base.rb,
+        D.base.res == 0 ? "none" : D.base.res == 1 ? "lds" : "l2", D.base.tok, D.tb, D.base.tiles, D.parts, D.tpp, D.base.wgcu, D.rgs);
+  if (D.parts >= 2) t.add(" | gemm_gather12w_sum dt=%s parts=%d grid=%dx%d", dt_text(D.base.f16), D.parts, D.sum_grid_x, D.sum_grid_y);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // ---- gemm_gather.hip's grouped launch (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gather, 1 - 16 tokens, in ONE
 // launch of gemm_gather_grouped_kernel, behind one permute launch per DISTINCT perm pointer of the members.
 // What a grouped call IS, decided once for the workspace query, the launcher and the `_instance`: which xp block a member reads (-1:

@@ -40,8 +40,8 @@
 // (vptq_quant_gemm_gather12 runs permute_x_tokens in front, as vptq_quant_gemm_gatherxw does).
 // LDS: 48 KiB + the table.  Registers: g12_min_wg workgroups per CU; no instantiation has scratch (profiles/r37/listings.md).  No
 // atomics, no scratch, plain vector stores.
-// NOT HERE: 17 - 48 tokens (token blocks), sibling groups, v = 6 (8 vector-rows per 48 outputs), the folded / selective arithmetics.
-// gemm_gather12c.hip holds a COPY of the row-group body (the column-parts form): A CHANGE TO THE BODY HERE BELONGS THERE TOO.
+// NOT HERE: 17 - 48 tokens (gemm_gather12w.hip), sibling groups, v = 6 (8 vector-rows per 48 outputs), the folded / selective arithmetics.
+// gemm_gather12c.hip (column parts) and gemm_gather12w.hip (token blocks) hold COPIES of the row-group body: A CHANGE HERE BELONGS THERE TOO.
 #include "gemm_gather_tile.h"
 #include "launch.h"
 

@@ -312,6 +312,23 @@ GemmGather12cDecision gemm_gather12c_decide(const VptqLayerDesc& d, int tokens, 
 hipError_t launch_gemm_gather12c(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, int parts, void* partials,
                                  hipStream_t st);
 
+// gemm_gather12w.hip - gemm_gather12's layers, 17 - 48 tokens in one launch: tb = 2 / 3 blocks of 16 tokens over gemm_gather12c's walk of
+// (row group, column part) items; gemm_gather12w_kernel<DT, RES, TB> finishes y itself where parts == 1 and stores raw fp32 sums into
+// partials [S][tokens][n_groups x 48] otherwise, which gemm_gather12w_sum_kernel<DT> adds in ascending part order; plain form only.
+// parts == 1: no split; parts >= 2: a request, gemm_gather12c's formula; parts == 0: the library's rule.  base: gemm_gather12_decide's
+// format decision with tok, wgcu (the smaller of the LDS bound and the kernel's register bound), grid and rgs of THIS launch;
+// partial_bytes 0 where parts == 1; serves: the parent's eligibility, 17 - 48 tokens and parts >= 0
+bool gemm_gather12w_eligible(const VptqLayerDesc& d, int tokens);
+struct GemmGather12wDecision {
+  GemmGather12Decision base;
+  int tb, parts, tpp, items, grid, rgs, op, sum_grid_x, sum_grid_y;
+  size_t partial_bytes;
+  bool serves;
+};
+GemmGather12wDecision gemm_gather12w_decide(const VptqLayerDesc& d, int tokens, int parts);
+hipError_t launch_gemm_gather12w(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, int parts, void* partials,
+                                 hipStream_t st);
+
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)
 // - scale_permuted / bias_permuted as scale / bias, no permutation - with x = xp: the bits of the layer's own entry

@@ -38,8 +38,8 @@ from vptq_amd import ops
 from vptq_amd.batched_decode import (  # noqa: F401
     BATCHED_DECODE_MAX_TOKENS, BATCHED_DECODE_MIN_TOKENS, GEMM_GATHER_MAX_TOKENS, GEMM_GATHER_PX_MAX_TOKENS, GEMM_GATHER_PX_MIN_TOKENS,
     GEMM_GATHERW_MAX_TOKENS, GEMM_GATHERW_MIN_TOKENS, GEMM_GATHERXW_MAX_TOKENS, GEMM_GATHERXW_MIN_TOKENS, GEMM_K256W_MAX_TOKENS,
-    GEMM_K256W_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_wide_routes, gemm_gather12_route,
-    gemm_gather12c_route, gemm_gather_px_route,
+    GEMM_K256W_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_v12_wide_routes, batched_decode_wide_routes, gemm_gather12_route,
+    gemm_gather12c_route, gemm_gather12w_route, gemm_gather_px_route,
     gemm_gather_route, gemm_gatherw_route, gemm_gatherx_route, gemm_gatherxw_route, gemm_k256w_route)
 # the batched-decode rules of a GROUP of siblings live in vptq_amd/grouped_decode.py: `GROUPED_DECODE_ROUTES`, one record per group
 # route (the knobs and cells are read there, at call time); the guard's window is the union of the routes' windows
@@ -991,7 +991,7 @@ class VQuantLinear(nn.Module):
 
     def _batched_decode_routes(self) -> tuple:
         """the batched-decode routes that can ever serve this layer (`batched_decode_routes` of its static configuration, then
-        `batched_decode_wide_routes`, then `batched_decode_v12_column_routes` in front of `batched_decode_v12_routes`) and whose entry this process's library has: decided once per layer, so that every other layer
+        `batched_decode_wide_routes`, then `batched_decode_v12_column_routes` in front of `batched_decode_v12_routes`, then `batched_decode_v12_wide_routes`) and whose entry this process's library has: decided once per layer, so that every other layer
         pays one dict look-up per call"""
         routes = self.__dict__.get("_bd_routes")
         if routes is None:
@@ -999,7 +999,8 @@ class VQuantLinear(nn.Module):
             static = (self.vector_len, self.num_centroids, _res_centroids(self), self.num_codebooks, self.enable_outlier, self.enable_norm,
                       bool(self.enable_perm))
             routes = tuple(r for r in batched_decode_routes(*static) + batched_decode_wide_routes(*static) +
-                           batched_decode_v12_column_routes(*static) + batched_decode_v12_routes(*static)
+                           batched_decode_v12_column_routes(*static) + batched_decode_v12_routes(*static) +
+                           batched_decode_v12_wide_routes(*static)
                            if getattr(lib, r.entry, None) is not None)
             self.__dict__["_bd_routes"] = routes
         return routes
@@ -1047,7 +1048,7 @@ class VQuantLinear(nn.Module):
 
     def _gemm_gather_px_workspace_bytes(self) -> int:
         """bytes of stream workspace the largest call any workspace route of this layer (`vptq_quant_gemm_gather_px`,
-        `vptq_quant_gemm_gatherxw`, `vptq_quant_gemm_gather12`, `vptq_quant_gemm_gather12c`) can take needs (`prepare_model` grows the stream's buffer to it): the maximum over the routes, each
+        `vptq_quant_gemm_gatherxw`, `vptq_quant_gemm_gather12`, `vptq_quant_gemm_gather12c`, `vptq_quant_gemm_gather12w`) can take needs (`prepare_model` grows the stream's buffer to it): the maximum over the routes, each
         at the most tokens its route function gives it; 0: the layer never takes such a route"""
         if "_compact" not in self.__dict__ and not self._parameters["indices"].is_cuda:
             return 0

@@ -19,9 +19,9 @@ import torch
 from torch.nn import functional as F
 
 from vptq_amd import _backend as B
-from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_wide_routes
+from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_v12_wide_routes, batched_decode_wide_routes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12c", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12c", "quant_gemm_gather12w", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -210,7 +210,7 @@ def quant_gemm(
         kr = num_res_centroids if enable_residual else 0
         static = (vector_len, num_centroids, kr, num_codebooks, enable_outlier, weight_scale is not None and weight_bias is not None,
                   perm is not None)
-        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) + batched_decode_v12_column_routes(*static) + batched_decode_v12_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
+        routes = batched_decode_routes(*static) + batched_decode_wide_routes(*static) + batched_decode_v12_column_routes(*static) + batched_decode_v12_routes(*static) + batched_decode_v12_wide_routes(*static) if tokens >= BATCHED_DECODE_MIN_TOKENS else ()
         for r in routes:
             if not batched_decode_takes(r, vector_len, num_centroids, kr, out_features, in_features, tokens, _FLAGS, perm is not None) or \
                     x.data_ptr() % 16 or not getattr(B.lib(), r.entry + "_supported")(gdesc, tokens, *r.extra):
@@ -381,6 +381,25 @@ def quant_gemm_gather12c(x: torch.Tensor, desc, out_features: int, parts: int = 
                                   extra=(int(parts),))
     if y is None:
         raise RuntimeError("quant_gemm_gather12c: the stream's workspace is too small and cannot grow during a capture "
+                           "(call it once, or vptq_amd.prepare_model, before capturing)")
+    return y
+
+
+def quant_gemm_gather12w(x: torch.Tensor, desc, out_features: int, parts: int = 0, out_f32: bool = False) -> torch.Tensor:
+    """y = x @ W^T + bias for 17 - 48 tokens of a layer `quant_gemm_gather12` serves (vector length 12, 16384 ... 65536 main centroids, any
+    residual codebook), with or without a column permutation (`vptq_quant_gemm_gather12w`, gemm_gather12w.hip): 2 / 3 blocks of 16 tokens
+    share one pass over the index windows, gathers and rebuilt tiles, the work split over (row group of 48 outputs, column part) as in
+    `quant_gemm_gather12c`; replaces dequant + F.linear.  The reference's roundings; no atomics: two calls give the same bits, and a
+    token's bits are those of `quant_gemm_gather12` (one part) / `quant_gemm_gather12c` (the same parts) in a call of <= 16 tokens.
+    parts: 1 = no split (the kernel writes y itself, one launch), >= 2 the column parts asked for (whole 512-column tiles, at most 16), 0:
+    the library's rule.  x[:, perm] of a layer with a permutation and the partial sums of a split go through this stream's workspace
+    (`B.gemv_workspace`).  `desc` = a LayerDesc of a layer `vptq_quant_gemm_gather12w_supported(desc, tokens, parts)` accepts; out_f32:
+    the un-rounded fp32 sums.  Raises where a stream capture is in progress and the workspace is too small (`prepare_model` sizes it
+    beforehand)."""
+    y = quant_gemm_batched_launch("vptq_quant_gemm_gather12w", desc, x, out_features, _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0), workspace=True,
+                                  extra=(int(parts),))
+    if y is None:
+        raise RuntimeError("quant_gemm_gather12w: the stream's workspace is too small and cannot grow during a capture "
                            "(call it once, or vptq_amd.prepare_model, before capturing)")
     return y
 
