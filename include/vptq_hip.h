@@ -1077,6 +1077,61 @@ VPTQ_API int vptq_quant_gemm_gatherxw_grouped(const VptqLayerDesc* descs, int n,
                                               void* workspace, size_t workspace_bytes, void* stream);
 VPTQ_API int vptq_quant_gemm_gatherxw_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, char* buf, size_t bytes);
 
+/* Batched decode of SIBLING layers of the large-codebook formats of VECTOR LENGTH 12 (vptq_quant_gemm_gather12's: v12-k65536-4096 / -256 /
+ * -0, ...) for 1 - 16 tokens in one launch (gemm_gather12_grouped_kernel and gemm_gather12_grouped_sum_kernel in
+ * gemm_gather12_grouped.hip; added within ABI 12; present when the symbols are).  descs[0 .. n) are 2 - 4 layers
+ * vptq_quant_gemm_gather12 serves, of one dtype, one group_size and one format (vector_len, num_centroids, num_res_centroids, hence
+ * index widths); they may differ in out_features, in every tensor, and in whether they have a column permutation.
+ * gemm_gather12_grouped_kernel<DT, RES> (RES: no residual table / table in LDS / table gathered from L2) walks ONE list of items: an
+ * item is (member, row group of 4 vector-rows = 48 outputs, column part of whole 512-column tiles); the members share group_size, so
+ * one split - S parts of tpp tiles - holds for the group; member m owns groups[m] * S consecutive items, inside a member item i is row
+ * group i / S, part i % S (vptq_quant_gemm_gather12c's order).  A workgroup that moves on to the next member reloads its pointers, scale
+ * and bias and (table in LDS) stages its residual table.  S == 1: the kernel adds the output bias in fp32, rounds once and stores
+ * y[m].  S >= 2: it stores raw fp32 sums into the member's partials [S][tokens][groups[m] * 48] in the workspace, and ONE launch of
+ * gemm_gather12_grouped_sum_kernel<DT> over the output blocks of 256 of every member adds the parts in ascending order, then the
+ * bias, and rounds once.  No atomics, no counters.
+ * BIT CONTRACT: an item depends neither on the grid nor on the workgroup that runs it.  For S >= 2, y[m] is BIT-IDENTICAL to
+ * vptq_quant_gemm_gather12c(&descs[m], ..., parts = S); for S == 1, to vptq_quant_gemm_gather12(&descs[m], ...) - at the same token
+ * count and x - and carries their guarantees.  The entry has the reference's roundings only.  Members with a permutation are read in
+ * the form without one (scale_permuted, bias_permuted) over xp = x[perm] in the workspace, written by one permute_x_tokens launch per
+ * DISTINCT perm pointer: members whose `perm` pointers are equal share one xp.  All launches go to `stream`; nothing is allocated:
+ * graph-capturable.
+ *   x [tokens][in_features] (one x for every member), y[m] [tokens][descs[m].out_features], the members' dtype; flags:
+ *   VPTQ_GEMV_OUT_F32 stores the fp32 sums (every y[m] is float32); every other flag is accepted and changes nothing.
+ *   parts > 0: a request - tpp = ceil(tiles / min(parts, tiles, 16)), S = ceil(tiles / tpp), tiles = ceil(group_size / 512):
+ *   vptq_quant_gemm_gather12c's split for the same request, with S == 1 allowed.  parts == 0: the library's rule - the rule of
+ *   vptq_quant_gemm_gather12w (the v = 12 rule that allows one part) over the group's TOTAL row groups and the CUs * wgcu resident
+ *   workgroups; no rule of its own has been measured.  parts < 0: not served.
+ * vptq_quant_gemm_gather12_grouped_supported: 1 where 2 <= n <= 4, 1 <= tokens <= 16, parts >= 0, vptq_quant_gemm_gather12_supported
+ *   answers 1 for every member and the members share dtype, group_size, vector_len, num_centroids and num_res_centroids (and index
+ *   widths), else 0; host logic.
+ * vptq_quant_gemm_gather12_grouped_workspace_bytes: k blocks of tokens * group_size * 2 rounded up to 256, k the number of distinct
+ *   non-NULL perm pointers among the members; then, for S >= 2, every member's S * tokens * groups[m] * 48 * 4 bytes, each rounded up
+ *   to 256, in member order; 0 where `_supported` answers 0.
+ * vptq_quant_gemm_gather12_grouped: NULL descs / x / y VPTQ_E_NULL; tokens outside [1, 16] VPTQ_E_TOKENS; n outside [2, 4], parts < 0
+ *   or a group it does not serve VPTQ_E_UNSUPPORTED (vptq_last_error names the first member that rules it out and why); a NULL y[m]
+ *   VPTQ_E_NULL; an x that is not 16-byte aligned VPTQ_E_UNSUPPORTED; then, where the query answers more than 0, a NULL workspace or
+ *   fewer workspace_bytes than it answers VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned VPTQ_E_ALIGN; nothing is
+ *   launched then.
+ * vptq_quant_gemm_gather12_grouped_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   permute_x_tokens g=N tok=N grid=XxY tpt=4 perms=K | <inner>      K distinct permutations: K such launches
+ *   none | <inner>                                                  no member has a permutation
+ *   <inner> = gemm_gather12_grouped dt=f16|bf16 ib=N rb=N res=none|lds|l2 tok=N n=N groups=A+B[+C[+D]] tiles=N parts=S tpp=N wgcu=N
+ *             items=N grid=N rgs=N[ | gemm_gather12_grouped_sum dt=f16|bf16 parts=S grid=XxY]
+ *       ib / rb the main / residual index widths, groups the row groups (48 outputs) of every member, tiles the column tiles (512
+ *       columns), S the column parts of tpp tiles, wgcu the resident workgroups per CU (vptq_quant_gemm_gather12_instance's), items =
+ *       total row groups * S, grid = min(items, CUs * wgcu) the workgroups, rgs the most items one workgroup walks; the sum launch
+ *       (S >= 2 only) has X = the members' blocks of 256 outputs, summed, and Y = tokens.  Returns as vptq_quant_gemm_gather_instance does.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: every member as vptq_quant_gemm_gather12 takes it (part of "supported"); x 16 bytes (VPTQ_E_UNSUPPORTED); the workspace 16
+ * bytes (VPTQ_E_ALIGN); every y[m] and bias element-aligned. */
+VPTQ_API int vptq_quant_gemm_gather12_grouped_supported(const VptqLayerDesc* descs, int n, int tokens, int parts);
+VPTQ_API size_t vptq_quant_gemm_gather12_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens, int parts);
+VPTQ_API int vptq_quant_gemm_gather12_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags,
+                                              int parts, void* workspace, size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gather12_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, int parts, char* buf,
+                                                       size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits.
  * Alignment: indices and codebooks 4 bytes; everything else - W included - element-aligned.  16-byte aligned W, weight_scale /
  * weight_bias and indices let the kernel store, read the norm tensors and read the index stream in 16-byte pieces (store= / norm= / idx=

@@ -234,6 +234,12 @@ EXPORTS = {
     "vptq_quant_gemm_gatherxw_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int]),
     "vptq_quant_gemm_gatherxw_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gatherxw_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 1 - 16 tokens of 2 - 4 sibling layers of vptq_quant_gemm_gather12 in one launch over (row group, column part)
+    # items, one x gather per distinct permutation (gemm_gather12_grouped.hip): `parts` behind the tokens / the flags (0: the library's rule)
+    "vptq_quant_gemm_gather12_grouped_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather12_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

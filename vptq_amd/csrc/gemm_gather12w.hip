@@ -15,7 +15,7 @@
 //    from L2, the reference's three roundings, the 48 KiB tile [N block][chunk][16 outputs][16 bytes] with the slot XOR-ed by chunk & 7,
 //    the gathers of tile t + 1 in flight during the MFMAs of tile t, prefetches clamped to the part's last tile).  A copy for the
 //    reason given there: as a shared function such bodies have twice cost 3 - 8 % and changed the parents' listings (profiles/r17,
-//    profiles/r31).  A CHANGE TO THE BODY HERE BELONGS IN gemm_gather12.hip AND gemm_gather12c.hip TOO, AND THE OTHER WAY ROUND.
+//    profiles/r31).  A CHANGE TO THE BODY HERE BELONGS IN gemm_gather12.hip, gemm_gather12c.hip AND gemm_gather12_grouped.hip TOO, AND THE OTHER WAY ROUND.
 //  * TOKEN BLOCKS.  Lane (token mj, k group mkg) of block b reads row 16 b + mj of x, clamped to the last token and masked past it
 //    (gt_load_a1: the uniform base + a 32-bit lane offset, one address register per load).  Per K-step a wave reads the three N
 //    blocks' B operands ONCE (three ds_read_b128) and every read feeds all TB token blocks before the next one: 3 x TB
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(kG12wSumThreads) void gemm_gather12w_sum_kernel(con
 // best split.  The items of a row group are short and the walk it += gridDim.x deals them out evenly whatever the residency, so the
 // rule counts slots = CUs x the LDS bound's 2 for EVERY instantiation; the grid is still CUs x wgcu.  So corrected, its choice is within
 // 3.1 % of the fastest measured split in all 120 cells.
-static int g12w_rule_parts(int tiles, int groups, int slots) {
+int gemm_gather12w_rule_parts(int tiles, int groups, int slots) {   // (kernels.h: gemm_gather12_grouped.hip reads it too)
   if (4LL * groups > 5LL * slots) return 1;
   for (int pass = 0; pass < 2; ++pass)
     for (int tpp = 1; tpp <= tiles; ++tpp) {
@@ -370,7 +370,7 @@ GemmGather12wDecision gemm_gather12w_decide(const VptqLayerDesc& d, int tokens, 
   if (D.base.wgcu > by_regs) D.base.wgcu = by_regs;
   const int tiles = D.base.tiles, slots = device_cus() * D.base.wgcu, groups = D.base.n_groups;
   int want = parts;
-  if (parts == 0) want = g12w_rule_parts(tiles, groups, device_cus() * by_lds);
+  if (parts == 0) want = gemm_gather12w_rule_parts(tiles, groups, device_cus() * by_lds);
   if (want > kG12wMaxParts) want = kG12wMaxParts;
   if (want > tiles) want = tiles;
   if (want < 1) want = 1;

@@ -328,6 +328,25 @@ struct GemmGather12wDecision {
 GemmGather12wDecision gemm_gather12w_decide(const VptqLayerDesc& d, int tokens, int parts);
 hipError_t launch_gemm_gather12w(const VptqLayerDesc& d, const void* x, void* y, int tokens, bool out_f32, int parts, void* partials,
                                  hipStream_t st);
+// its parts == 0 rule - the v = 12 rule that allows ONE part: the parts for `groups` row groups of `tiles` tiles on `slots` resident slots
+int gemm_gather12w_rule_parts(int tiles, int groups, int slots);
+
+// gemm_gather12_grouped.hip - 2 - 4 sibling layers of gemm_gather12 (one dtype, width and format), 1 - 16 tokens, in ONE launch of
+// gemm_gather12_grouped_kernel<DT, RES>: gemm_gather12c's (row group, column part) items of every member as one list, member m owning
+// [first_item[m], first_item[m + 1]); S == 1: the kernel finishes every y[m] itself (gemm_gather12's epilogue); S >= 2: raw fp32 sums go
+// to each member's partials [S][tokens][op[m]] and ONE launch of gemm_gather12_grouped_sum_kernel<DT> over the members' output blocks of
+// 256, concatenated (first_block), adds them in ascending part order; plain form only - the caller hands a member with a permutation
+// over as its descriptor without one, with x[perm] for its x.  base: gemm_gather12_decide's of the first member with grid and rgs of
+// THIS launch; parts > 0: a request, gemm_gather12c's formula with S == 1 allowed; parts == 0: gemm_gather12w_rule_parts over the total
+// row groups and CUs x wgcu; partial_bytes[m]: rounded up to 256, 0 where S == 1
+struct GemmGather12GroupedDecision {
+  GemmGather12Decision base;
+  int n, parts, tpp, items, grid, rgs, sum_grid_x, sum_grid_y, groups[4], first_item[5], op[4], first_block[5];
+  size_t partial_bytes[4];
+};
+GemmGather12GroupedDecision gemm_gather12_grouped_decide(const VptqLayerDesc* descs, int n, int tokens, int parts);
+hipError_t launch_gemm_gather12_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                        int parts, void* partials, hipStream_t st);
 
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)

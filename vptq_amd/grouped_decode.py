@@ -8,7 +8,8 @@ Pure rules - no device, no tensors, in the style of vptq_amd/batched_decode.py: 
 measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group routes (`GROUPED_DECODE_WIDE_ROUTES`: a format's routes
 beyond its first window; `GROUPED_DECODE_X_ROUTES`: the routes of formats the first table has no owner for; `sibling_decode_routes`
 reads all three; `GROUPED_DECODE_X_WIDE_ROUTES`: those formats' routes beyond their first window, read behind the others by
-`sibling_group_routes`).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
+`sibling_group_routes`; `GROUPED_DECODE_V12_ROUTES`: the v = 12 formats' `vptq_quant_gemm_gather12_grouped`, 5 - 16 tokens, read behind
+all of them by `sibling_group_v12_routes`).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
 is not routed here leaves every member on the routes it had.  `SiblingGroup.forward_batched` (vptq_amd/layers/vqlinear.py) and
 `prepare_model` decide through it.
 """
@@ -17,7 +18,7 @@ from __future__ import annotations
 from typing import Callable, NamedTuple, Optional, Sequence
 
 from vptq_amd import _backend as B
-from vptq_amd.batched_decode import _batched_decode_entry
+from vptq_amd.batched_decode import _batched_decode_entry, _v12_owns
 
 # WHICH groups take the grouped launch.  The kernel is gemm_gather's (v = 8, 65536 main centroids, 0 / 256 / 65536 residual
 # centroids), 5 - 16 tokens (1 - 4 tokens are `SiblingGroup.forward` / `forward_sliced`'s).  A cell is (residual centroids, has_perm,
@@ -352,6 +353,67 @@ def gemm_gatherxw_grouped_tokens(vector_len: int, num_centroids: int, num_res_ce
                  if gemm_gatherxw_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
 
 
+# WHICH groups of the large-codebook formats of VECTOR LENGTH 12 (`vptq_quant_gemm_gather12`'s: v12-k65536-4096 / -256 / -0, `_v12_owns` of
+# vptq_amd/batched_decode.py) take `vptq_quant_gemm_gather12_grouped` (gemm_gather12_grouped.hip: gemm_gather12c's (row group, column
+# part) items of every member as one list, one sum launch for the group where the columns are split), 5 - 16 tokens (1 - 4 tokens are
+# `SiblingGroup.forward` / `forward_sliced`'s; 17 - 48 have no group route).  Without it every member goes out alone: gemm_gather12,
+# gemm_gather12c, two gemv_gatherx launches or vptq_dequant + a dense GEMM, whichever `BATCHED_DECODE_V12_ROUTES` /
+# `BATCHED_DECODE_V12_COLUMN_ROUTES` give a layer of its format and size, each behind an x gather of its own when permuted.  A cell has
+# `_GEMM_GATHERXW_GROUPED_CELLS`' format without the vector length: (main centroids, residual centroids, has_perm, member count, least
+# TOTAL index elements of the group, most total index elements or None, least tokens, most tokens).  Routed by the rule of the tables
+# above: the grouped launch beats the SUM of what the members take without it by more than the larger of 5 % and three times the
+# larger run-to-run spread, in every measured cell of the region, in both dtypes; no cell lies under
+# GEMM_GATHER12_GROUPED_MIN_ELEMENTS (1 M total index elements: gemm_gather12c's floor).  tools/gemm_gather12_grouped_bench.py writes the
+# table.  VPTQ_GEMM_GATHER12_GROUPED=1 / 0 (with VPTQ_TUNING=1): every group of the kernel's formats from 5 to 16 tokens / none.
+#
+# profiles/r40/table.md, profiles/r40/README.md (one MI355X, fp16 and bf16, v12-k65536-4096 / -256 / -0, q / k / v and gate / up of the 8B and
+# 70B shapes = 2.0 M, 6.7 M, 9.3 M and 37.3 M total index elements, tokens 5 / 8 / 16, parts = 0, with one shared permutation and without; 144
+# cells, every member has the bits of its own entry in every one, ALL win by the rule; run-to-run spreads at most 2 %):
+#   q / k / v        8B shapes (1040 items of one tile; the parent: gemm_gather12c for q, two gemv_gatherx launches each for k / v up to 8
+#                    tokens and two dense routes from 9) 0.35 - 0.61 of the parent - v12-k65536-4096 fp16 with a permutation, 5 / 8 / 16
+#                    tokens: 42.2 / 42.5 / 43.2 us against 92.2 / 100.5 / 77.8; 70B shapes (4 parts of 4 tiles) 0.41 - 0.90, the closest at 16
+#                    tokens without a permutation (v12-k65536-4096: 0.90)
+#   gate / up        8B shapes (two gemm_gather12c calls: four launches; here 2 parts, two launches) 0.86 - 0.95; 70B shapes (two
+#                    gemm_gather12 launches; here one part, one launch) 0.84 - 0.91
+# A region reaches from its smallest to its largest MEASURED group of its member count and no further: a group of four, a group of
+# which only some members have a permutation, v12-k32768-1024 and q / k / v groups above 7 M elements are behind the knob.
+_GEMM_GATHER12_GROUPED_CELLS = tuple((65536, kr, perm, members, min_el, max_el, 5, 16) for kr in (0, 256, 4096) for perm in (True, False)
+                                     for members, min_el, max_el in ((3, 2 << 20, 7 << 20), (2, 9 << 20, 38 << 20)))
+GEMM_GATHER12_GROUPED_MIN_TOKENS, GEMM_GATHER12_GROUPED_MAX_TOKENS = 5, 16
+GEMM_GATHER12_GROUPED_MIN_ELEMENTS = 1 << 20
+GEMM_GATHER12_GROUPED_MAX_MEMBERS = 4
+_GEMM_GATHER12_GROUPED_MODE = (B.tune_env("VPTQ_GEMM_GATHER12_GROUPED", "auto") or "auto").strip().lower()
+
+
+def gemm_gather12_grouped_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                in_features: int, tokens: int, has_perm: Optional[bool]) -> bool:
+    """does a group of sibling layers of this format (shared by its members) with these output widths take
+    `vptq_quant_gemm_gather12_grouped` (parts = 0: the library's rule) for `tokens` tokens?  has_perm: True - every member has a
+    column permutation, False - none, None - some.  Pure: no device, no library (whether the library serves the group is
+    `vptq_quant_gemm_gather12_grouped_supported`'s answer).  Only for the v = 12 formats, which no other group route owns."""
+    if _GEMM_GATHER12_GROUPED_MODE in ("0", "off") or not GEMM_GATHER12_GROUPED_MIN_TOKENS <= tokens <= GEMM_GATHER12_GROUPED_MAX_TOKENS:
+        return False
+    n = len(out_features_tuple)
+    if not 2 <= n <= GEMM_GATHER12_GROUPED_MAX_MEMBERS or in_features % 8 or not _v12_owns(vector_len, num_centroids, num_res_centroids):
+        return False
+    if _GEMM_GATHER12_GROUPED_MODE in ("1", "on"):
+        return True
+    if has_perm is None:
+        return False
+    n_el = sum((o + vector_len - 1) // vector_len for o in out_features_tuple) * in_features
+    return any((k, kr) == (num_centroids, num_res_centroids) and perm == has_perm and members == n and
+               n_el >= max(min_el, GEMM_GATHER12_GROUPED_MIN_ELEMENTS) and (max_el is None or n_el <= max_el) and
+               min_tok <= tokens <= max_tok for k, kr, perm, members, min_el, max_el, min_tok, max_tok in _GEMM_GATHER12_GROUPED_CELLS)
+
+
+def gemm_gather12_grouped_tokens(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                 in_features: int, has_perm: Optional[bool]) -> tuple:
+    """the token counts the route function gives to the grouped launch for this group, ascending (possibly none): `prepare_model`
+    sizes the stream's workspace to the largest"""
+    return tuple(t for t in range(GEMM_GATHER12_GROUPED_MIN_TOKENS, GEMM_GATHER12_GROUPED_MAX_TOKENS + 1)
+                 if gemm_gather12_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
+
+
 class GroupedDecodeRoute(NamedTuple):
     """what differs between the group routes; everything else is one code path in `SiblingGroup` (a third route is a record and a
     route function).  `route` and `tokens` take the group's static configuration as `SiblingGroup._batched_static` states it:
@@ -364,6 +426,7 @@ class GroupedDecodeRoute(NamedTuple):
     max_tokens: int
     off_flags: int                            # launch flags that switch the route off
     exact_only: bool = False                  # the kernel has the reference's roundings only: every member's arithmetic must be GEMV_EXACT
+    extra: tuple = ()                         # integer arguments the entry takes behind the tokens (`_supported`, `_workspace_bytes`) / the output widths (the op)
 
 
 # (the formats are disjoint: a group has at most one route, and the order changes no answer)
@@ -446,3 +509,22 @@ def sibling_group_routes(vector_len: int, num_centroids: int, num_res_centroids:
     knob is read."""
     return sibling_decode_routes(vector_len, num_centroids, num_res_centroids) + \
         tuple(r for r in GROUPED_DECODE_X_WIDE_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))
+
+
+# the routes of the v = 12 formats, which none of the four tables above has an owner for: `vptq_quant_gemm_gather12_grouped`, 5 - 16
+# tokens.  (Once more a table and a reader of its own: the four tables above and their four readers keep every answer they gave
+# before.)  extra = (0,): `parts` = the library's rule.  The window lies inside GROUPED_DECODE_MIN_TOKENS ... GROUPED_DECODE_MAX_TOKENS.
+GROUPED_DECODE_V12_ROUTES = (
+    GroupedDecodeRoute("vptq_quant_gemm_gather12_grouped", _v12_owns,
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_gather12_grouped_route(v, k, kr, outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_gather12_grouped_tokens(v, k, kr, outs, width, has_perm),
+                       GEMM_GATHER12_GROUPED_MIN_TOKENS, GEMM_GATHER12_GROUPED_MAX_TOKENS, B.GEMV_FORCE_GENERIC, extra=(0,)),
+)
+
+
+def sibling_group_v12_routes(vector_len: int, num_centroids: int, num_res_centroids: int) -> tuple:
+    """every group route a `SiblingGroup` of this format can take, in window order: `sibling_group_routes`' answer, then the records of
+    `GROUPED_DECODE_V12_ROUTES` that own the format (none for any format but the v = 12 ones, for which the first part is empty).
+    What `SiblingGroup` reads.  No knob is read."""
+    return sibling_group_routes(vector_len, num_centroids, num_res_centroids) + \
+        tuple(r for r in GROUPED_DECODE_V12_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))

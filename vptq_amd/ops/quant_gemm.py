@@ -21,7 +21,7 @@ from torch.nn import functional as F
 from vptq_amd import _backend as B
 from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_v12_wide_routes, batched_decode_wide_routes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12c", "quant_gemm_gather12w", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12_grouped", "quant_gemm_gather12c", "quant_gemm_gather12w", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -431,9 +431,10 @@ def quant_gemm_gather_grouped(x: torch.Tensor, descs, out_features_list, out_f32
     return _grouped_launch("vptq_quant_gemm_gather_grouped", x, descs, out_features_list, out_f32)
 
 
-def _grouped_launch(entry: str, x: torch.Tensor, descs, out_features_list, out_f32: bool):
+def _grouped_launch(entry: str, x: torch.Tensor, descs, out_features_list, out_f32: bool, extra: tuple = ()):
     """the plumbing of the grouped entries (`entry`, `entry`_workspace_bytes): the descriptor array, this stream's workspace, one
-    output per member; None under a capture whose workspace is too small"""
+    output per member; None under a capture whose workspace is too small.  extra: integer arguments the entry takes behind the
+    tokens of its workspace query and behind the flags of the launch (gemm_gather12_grouped: parts)"""
     import ctypes as C
     n = len(out_features_list)
     if not isinstance(descs, C.Array):
@@ -446,13 +447,13 @@ def _grouped_launch(entry: str, x: torch.Tensor, descs, out_features_list, out_f
     flags = _FLAGS | (B.GEMV_OUT_F32 if out_f32 else 0)
     with torch.cuda.device(dev):
         sp = B.current_stream_ptr(dev)
-        need = getattr(lib, entry + "_workspace_bytes")(descs, n, tokens)
+        need = getattr(lib, entry + "_workspace_bytes")(descs, n, tokens, *extra)
         ws, wsb = B.gemv_workspace(dev.index if dev.index is not None else torch.cuda.current_device(), sp, need)
         if need and ws is None:
             return None
         ys = [torch.empty(shape[:-1] + (o,), dtype=torch.float32 if out_f32 else x.dtype, device=dev) for o in out_features_list]
         yp = (C.c_void_p * n)(*[y.data_ptr() for y in ys])
-        rc = getattr(lib, entry)(descs, n, x.data_ptr(), yp, tokens, flags, ws, wsb, sp)
+        rc = getattr(lib, entry)(descs, n, x.data_ptr(), yp, tokens, flags, *extra, ws, wsb, sp)
     if rc:
         B.check(rc, entry)
     return ys
@@ -510,6 +511,28 @@ def quant_gemm_gatherxw_grouped(x: torch.Tensor, descs, out_features_list, out_f
     where a stream capture is in progress and the workspace is too small (nothing is allocated or launched then; `prepare_model`
     sizes it beforehand)."""
     return _grouped_launch("vptq_quant_gemm_gatherxw_grouped", x, descs, out_features_list, out_f32)
+
+
+def quant_gemm_gather12_grouped(x: torch.Tensor, descs, out_features, parts: int = 0, out_f32: bool = False):
+    """[y_m = x @ W_m^T + bias_m] for 1 - 16 tokens of 2 - 4 sibling layers `quant_gemm_gather12` serves (vector length 12; one dtype,
+    input width and format: main and residual codebook size; with or without a column permutation) in ONE launch
+    (`vptq_quant_gemm_gather12_grouped`, gemm_gather12_grouped.hip: the members' (row group of 48 outputs, column part) items as one
+    list) - plus, where the columns are split, one small launch that adds every member's parts in ascending order - behind one
+    x[:, perm] gather per DISTINCT `perm` pointer of the members.  x[:, perm] and the partial sums go through this stream's workspace
+    (`B.gemv_workspace`).  parts: the column parts asked for (whole 512-column tiles, at most 16; 1 = no split), 0: the library's
+    rule.  With S parts cut, every y_m has the bits of `quant_gemm_gather12c(x, descs[m], ..., parts=S)`, at S = 1 of
+    `quant_gemm_gather12(x, descs[m], ...)`.  `descs` = a ctypes array (or a sequence) of LayerDesc of a group
+    `vptq_quant_gemm_gather12_grouped_supported(descs, n, tokens, parts)` accepts; `out_features`: the members' output widths;
+    out_f32: the un-rounded fp32 sums.  Returns the list of outputs, or None where the library does not serve the group or where a
+    stream capture is in progress and the workspace is too small (nothing is allocated or launched then; `prepare_model` sizes it
+    beforehand)."""
+    import ctypes as C
+    n = len(out_features)
+    if not isinstance(descs, C.Array):
+        descs = (B.LayerDesc * n)(*descs)
+    if not B.lib().vptq_quant_gemm_gather12_grouped_supported(descs, n, x.numel() // x.shape[-1], int(parts)):
+        return None
+    return _grouped_launch("vptq_quant_gemm_gather12_grouped", x, descs, out_features, out_f32, extra=(int(parts),))
 
 
 def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
