@@ -1132,6 +1132,61 @@ VPTQ_API int vptq_quant_gemm_gather12_grouped(const VptqLayerDesc* descs, int n,
 VPTQ_API int vptq_quant_gemm_gather12_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, int parts, char* buf,
                                                        size_t bytes);
 
+/* 17 - 48 TOKENS of the groups of vptq_quant_gemm_gather12_grouped in one launch (gemm_gather12w_grouped_kernel and
+ * gemm_gather12w_grouped_sum_kernel in gemm_gather12w_grouped.hip; added within ABI 12; present when the symbols are): in place of one
+ * vptq_dequant + dense GEMM, or one vptq_quant_gemm_gather12w call, per member.  descs[0 .. n) are 2 - 4 layers
+ * vptq_quant_gemm_gather12 serves, of one dtype, one group_size and one format; they may differ in out_features, in every tensor, and
+ * in whether they have a column permutation.  gemm_gather12w_grouped_kernel<DT, RES, TB> (RES: no residual table / table in LDS / table
+ * gathered from L2; TB = 2 / 3 blocks of 16 tokens) walks vptq_quant_gemm_gather12_grouped's list of items - (member, row group of 48
+ * outputs, column part of whole 512-column tiles), member m owning groups[m] * S consecutive items, item i of a member being row group
+ * i / S, part i % S - and runs vptq_quant_gemm_gather12w's token-block pass on each: the B operands of a K-step are read from LDS once
+ * and feed every token block.  A workgroup that moves on to the next member reloads its pointers, scale and bias and (table in LDS)
+ * stages its residual table.  S == 1: the kernel adds the output bias in fp32, rounds once and stores y[m].  S >= 2: it stores raw
+ * fp32 sums into the member's partials [S][tokens][groups[m] * 48] in the workspace, and ONE launch of
+ * gemm_gather12w_grouped_sum_kernel<DT> over the output blocks of 256 of every member and every token adds the parts in ascending
+ * order, then the bias, and rounds once.  No atomics, no counters.
+ * BIT CONTRACT: an item depends neither on the grid nor on the workgroup that runs it.  y[m] is BIT-IDENTICAL to
+ * vptq_quant_gemm_gather12w(&descs[m], ..., tokens, parts = S) on the same x; hence a token's bits are those of
+ * vptq_quant_gemm_gather12 (S == 1) / vptq_quant_gemm_gather12c (S >= 2) for that token in a call of at most 16.  The entry has the
+ * reference's roundings only.  Members with a permutation are read in the form without one over xp = x[perm] in the workspace,
+ * written by one permute_x_tokens launch per DISTINCT perm pointer.  All launches go to `stream`; nothing is allocated:
+ * graph-capturable.
+ *   x [tokens][in_features] (one x for every member), y[m] [tokens][descs[m].out_features], the members' dtype; flags:
+ *   VPTQ_GEMV_OUT_F32 stores the fp32 sums (every y[m] is float32); every other flag is accepted and changes nothing.
+ *   parts > 0: a request - tpp = ceil(tiles / min(parts, tiles, 16)), S = ceil(tiles / tpp), tiles = ceil(group_size / 512):
+ *   vptq_quant_gemm_gather12w's split for the same request.  parts == 0: the library's rule - the rule of vptq_quant_gemm_gather12w
+ *   over the group's TOTAL row groups and the CUs * wgcu resident workgroups of the instantiation that runs; no rule of its own has
+ *   been measured.  parts < 0: not served.
+ * vptq_quant_gemm_gather12w_grouped_supported: 1 where 2 <= n <= 4, 17 <= tokens <= 48, parts >= 0,
+ *   vptq_quant_gemm_gather12_supported(desc, 16) answers 1 for every member and the members share dtype, group_size, vector_len,
+ *   num_centroids and num_res_centroids (and index widths), else 0; host logic.
+ * vptq_quant_gemm_gather12w_grouped_workspace_bytes: k blocks of tokens * group_size * 2 rounded up to 256, k the number of distinct
+ *   non-NULL perm pointers among the members; then, for S >= 2, every member's S * tokens * groups[m] * 48 * 4 bytes, each rounded up
+ *   to 256, in member order: exactly the bytes the entry touches; 0 where `_supported` answers 0.  With parts == 0 the answer is NOT
+ *   monotone in `tokens` (S can fall from 32 to 33 tokens, where wgcu does): size a shared workspace over every token count in use.
+ * vptq_quant_gemm_gather12w_grouped: NULL descs / x / y VPTQ_E_NULL; tokens outside [17, 48] VPTQ_E_TOKENS; n outside [2, 4], parts < 0
+ *   or a group it does not serve VPTQ_E_UNSUPPORTED (vptq_last_error names the first member that rules it out and why); a NULL y[m]
+ *   VPTQ_E_NULL; an x that is not 16-byte aligned VPTQ_E_UNSUPPORTED; then, where the query answers more than 0, a NULL workspace or
+ *   fewer workspace_bytes than it answers VPTQ_E_WORKSPACE and a workspace that is not 16-byte aligned VPTQ_E_ALIGN; nothing is
+ *   launched then.
+ * vptq_quant_gemm_gather12w_grouped_instance: the launches as one line (host logic, without a device the CU count is taken as 256):
+ *   permute_x_tokens g=N tok=N grid=XxY tpt=4 perms=K | <inner>      K distinct permutations: K such launches
+ *   none | <inner>                                                  no member has a permutation
+ *   <inner> = gemm_gather12w_grouped dt=f16|bf16 ib=N rb=N res=none|lds|l2 tok=N tb=2|3 n=N groups=A+B[+C[+D]] tiles=N parts=S tpp=N
+ *             wgcu=N items=N grid=N rgs=N[ | gemm_gather12w_grouped_sum dt=f16|bf16 parts=S grid=XxY]
+ *       as vptq_quant_gemm_gather12_grouped_instance's, with tb the token blocks and wgcu the resident workgroups per CU of THIS
+ *       instantiation: 2, and 1 with a residual table and three token blocks (vptq_quant_gemm_gather12w_instance's); grid =
+ *       min(items, CUs * wgcu).  Returns as vptq_quant_gemm_gather_instance does.
+ * Workspace: contents do not matter before a call and are undefined after it; calls on one stream may share it.
+ * Alignment: every member as vptq_quant_gemm_gather12 takes it (part of "supported"); x 16 bytes (VPTQ_E_UNSUPPORTED); the workspace 16
+ * bytes (VPTQ_E_ALIGN); every y[m] and bias element-aligned. */
+VPTQ_API int vptq_quant_gemm_gather12w_grouped_supported(const VptqLayerDesc* descs, int n, int tokens, int parts);
+VPTQ_API size_t vptq_quant_gemm_gather12w_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens, int parts);
+VPTQ_API int vptq_quant_gemm_gather12w_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags,
+                                               int parts, void* workspace, size_t workspace_bytes, void* stream);
+VPTQ_API int vptq_quant_gemm_gather12w_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int flags, int parts, char* buf,
+                                                        size_t bytes);
+
 /* W[O, I] dense, row-major, desc->dtype: the reference CPU path's bits.
  * Alignment: indices and codebooks 4 bytes; everything else - W included - element-aligned.  16-byte aligned W, weight_scale /
  * weight_bias and indices let the kernel store, read the norm tensors and read the index stream in 16-byte pieces (store= / norm= / idx=

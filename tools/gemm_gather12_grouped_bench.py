@@ -12,7 +12,12 @@ second launch over a refilled workspace gives the same bits, and every member ha
 (vptq_quant_gemm_gather12c, at one part vptq_quant_gemm_gather12; first group of the ring).  With a permutation the members of a group
 share one.  One JSON line per row; --md appends a markdown table row per measured row; --budget-s: no new group is started after that
 many seconds (the cells not reached are printed as "not measured").
-    python tools/gemm_gather12_grouped_bench.py --md profiles/r40/table.md"""
+--wide: 17 - 48 tokens (17 / 24 / 32 / 33 / 40 / 48 unless --tokens says otherwise) through vptq_quant_gemm_gather12w_grouped
+(gemm_gather12w_grouped.hip); the parent is every member's own route with the knob `_GEMM_GATHER12W_GROUPED_MODE` at 0 (the dense route,
+or vptq_quant_gemm_gather12w where its knob or cells route the member), and `bits` compares every member with
+vptq_quant_gemm_gather12w at the same split.
+    python tools/gemm_gather12_grouped_bench.py --md profiles/r40/table.md
+    python tools/gemm_gather12_grouped_bench.py --wide --md profiles/r41/table.md"""
 import argparse, ctypes, json, os, statistics, sys, time, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -27,7 +32,8 @@ ap.add_argument("--formats", default="65536,4096;65536,256;65536,0", help="k,kr;
 ap.add_argument("--groups", default="4096:4096,1024,1024;4096:14336,14336;8192:8192,1024,1024;8192:28672,28672",
                 help="I:O,O[,O[,O]];... (input columns: the members' outputs) - q / k / v and gate / up of the 8B and 70B shapes")
 ap.add_argument("--dtypes", default="f16,bf16")
-ap.add_argument("--tokens", default="5,8,16")
+ap.add_argument("--tokens", default="")
+ap.add_argument("--wide", action="store_true", help="17 - 48 tokens: vptq_quant_gemm_gather12w_grouped")
 ap.add_argument("--perms", default="0,1")
 ap.add_argument("--parts", default="0")
 ap.add_argument("--reps", type=int, default=3)
@@ -36,12 +42,13 @@ ap.add_argument("--ring-bytes", type=int, default=512 << 20)
 ap.add_argument("--budget-s", type=float, default=0.0)
 ap.add_argument("--md", default="")
 a = ap.parse_args()
-NAME, V = "vptq_quant_gemm_gather12_grouped", 12
+NAME, V = "vptq_quant_gemm_gather12w_grouped" if a.wide else "vptq_quant_gemm_gather12_grouped", 12
+a.tokens = a.tokens or ("17,24,32,33,40,48" if a.wide else "5,8,16")
 t_start = time.time()
 dev = torch.device("cuda", 0); g = torch.Generator(device=dev).manual_seed(0); lib = B.lib()
 box = f"{torch.cuda.get_device_name(0)}, {torch.cuda.get_device_properties(0).multi_processor_count} CUs"
 print(json.dumps(dict(box=box)), flush=True)
-gd._GEMM_GATHER12_GROUPED_MODE = "0"   # the parent is every member's own route
+gd._GEMM_GATHER12_GROUPED_MODE = gd._GEMM_GATHER12W_GROUPED_MODE = "0"   # the parent is every member's own route
 rows, skipped = [], []
 
 
@@ -91,6 +98,8 @@ def write_md(r):
 
 
 def parent_name(k, kr, O, I, tok, perm):
+    if a.wide:
+        return "12w" if bd.gemm_gather12w_route(V, k, kr, O, I, tok, perm) else "dense"
     if bd.gemm_gather12c_route(V, k, kr, O, I, tok, perm):
         return "12c"
     return "12" if bd.gemm_gather12_route(V, k, kr, O, I, tok, perm) else "2 x gemv_gatherx" if tok <= 8 else "dense"
@@ -149,6 +158,8 @@ for I, outs, k, kr, perm, dname in cells:
             same = all(torch.equal(p.view(torch.int16), q.view(torch.int16)) for p, q in zip(got, ys))
             for d, O, want in zip(ds0, outs, got):
                 own, y1 = ("vptq_quant_gemm_gather12c", (S,)) if S >= 2 else ("vptq_quant_gemm_gather12", ()), torch.empty(1, tok, O, device=dev, dtype=dt)
+                if a.wide:
+                    own = ("vptq_quant_gemm_gather12w", (S,))
                 need1 = getattr(lib, own[0] + "_workspace_bytes")(d, tok, *own[1])
                 ws1 = torch.empty(max(need1, 16), dtype=torch.uint8, device=dev)
                 B.check(getattr(lib, own[0])(d, x.data_ptr(), y1.data_ptr(), tok, 0, *own[1], ws1.data_ptr(), need1, sp()), own[0])

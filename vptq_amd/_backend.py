@@ -240,6 +240,12 @@ EXPORTS = {
     "vptq_quant_gemm_gather12_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
     "vptq_quant_gemm_gather12_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
     "vptq_quant_gemm_gather12_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    # (added within ABI 12) 17 - 48 tokens of the same groups as 2 / 3 token blocks over the same items (gemm_gather12w_grouped.hip): the
+    # same four shapes
+    "vptq_quant_gemm_gather12w_grouped_supported": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12w_grouped_workspace_bytes": (C.c_size_t, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int]),
+    "vptq_quant_gemm_gather12w_grouped": (C.c_int, [C.POINTER(LayerDesc), C.c_int, _vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, _vp]),
+    "vptq_quant_gemm_gather12w_grouped_instance": (C.c_int, [C.POINTER(LayerDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

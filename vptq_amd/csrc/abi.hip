@@ -2129,6 +2129,88 @@ int vptq_quant_gemm_gather12_grouped_instance(const VptqLayerDesc* descs, int n,
   return instance_done(t);
 }
 
+// ---- gemm_gather12w_grouped.hip (added within ABI 12): 2 - 4 sibling layers of vptq_quant_gemm_gather12, 17 - 48 tokens, in ONE launch
+// of gemm_gather12w_grouped_kernel over the members' (row group, column part) items - and, where the columns are split (S >= 2), one
+// launch of gemm_gather12w_grouped_sum_kernel over every member and token - behind one permute launch per DISTINCT perm pointer of the
+// members.  The plan is the gather group's (grouped_gather_decide), the member rule is gemm_gather12_grouped's at 16 tokens (what
+// vptq_quant_gemm_gather12w serves).  The workspace is [one x[perm] block per distinct permutation][member 0's partials][member 1's]
+// ..., every region 256-byte aligned.
+constexpr int kGemmGather12wGroupedTokLo = 17, kGemmGather12wGroupedTokHi = 48;   // TB = 2 / 3 blocks of 16 tokens
+static int grouped_gather12w_validate(const VptqLayerDesc* descs, int n, int tokens, int parts) {
+  if (tokens < kGemmGather12wGroupedTokLo || tokens > kGemmGather12wGroupedTokHi)
+    return fail(VPTQ_E_TOKENS, "tokens %d outside [%d, %d]", tokens, kGemmGather12wGroupedTokLo, kGemmGather12wGroupedTokHi);
+  int member = 0;
+  if (const char* why = grouped_gather12_refusal(descs, n, 16, parts, &member))
+    return fail(VPTQ_E_UNSUPPORTED, "gemm_gather12w_grouped (n = %d, parts = %d): member %d: %s", n, parts, member, why);
+  return VPTQ_OK;
+}
+static size_t grouped_gather12w_partial_bytes(const vptq::GemmGather12wGroupedDecision& D) {
+  size_t bytes = 0;
+  for (int m = 0; m < D.n; ++m) bytes += D.partial_bytes[m];
+  return bytes;
+}
+
+int vptq_quant_gemm_gather12w_grouped_supported(const VptqLayerDesc* descs, int n, int tokens, int parts) {
+  int member = 0;
+  return descs && tokens >= kGemmGather12wGroupedTokLo && tokens <= kGemmGather12wGroupedTokHi &&
+                 !grouped_gather12_refusal(descs, n, 16, parts, &member) ? 1 : 0;
+}
+
+size_t vptq_quant_gemm_gather12w_grouped_workspace_bytes(const VptqLayerDesc* descs, int n, int tokens, int parts) {
+  if (!vptq_quant_gemm_gather12w_grouped_supported(descs, n, tokens, parts)) return 0;
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  return G.block_bytes * (size_t)G.n_perms + grouped_gather12w_partial_bytes(vptq::gemm_gather12w_grouped_decide(G.plain, n, tokens, parts));
+}
+
+int vptq_quant_gemm_gather12w_grouped(const VptqLayerDesc* descs, int n, const void* x, void* const* y, int tokens, int flags, int parts,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  // (VPTQ_GEMV_FAST_MATH / _SELECTIVE / _EXACT: the kernel has the reference's roundings only)
+  if (!descs || !x || !y) return fail(VPTQ_E_NULL, "descs / x / y is NULL");
+  if (const int rc = grouped_gather12w_validate(descs, n, tokens, parts)) return rc;
+  for (int m = 0; m < n; ++m)
+    if (!y[m]) return fail(VPTQ_E_NULL, "y[%d] is NULL", m);
+  if ((((uintptr_t)x) & 15) != 0) return fail(VPTQ_E_UNSUPPORTED, "gemm_gather12w_grouped: x must be 16-byte aligned");
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  const size_t xp_bytes = G.block_bytes * (size_t)G.n_perms;   // (block_bytes is a multiple of 256)
+  const size_t need = xp_bytes + grouped_gather12w_partial_bytes(vptq::gemm_gather12w_grouped_decide(G.plain, n, tokens, parts));
+  if (need > 0) {
+    if (!workspace || workspace_bytes < need) return fail(VPTQ_E_WORKSPACE, "gemm_gather12w_grouped: workspace of %zu bytes needed", need);
+    if ((((uintptr_t)workspace) & 15) != 0) return fail(VPTQ_E_ALIGN, "gemm_gather12w_grouped: the workspace must be 16-byte aligned");
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  for (int j = 0; j < G.n_perms; ++j) {   // one x gather per distinct permutation
+    const hipError_t e = vptq::launch_permute_x_tokens(descs[G.owner[j]], x, (char*)workspace + (size_t)j * G.block_bytes, tokens, st);
+    if (e != hipSuccess) return hip_fail(e, "permute_x_tokens launch");
+  }
+  const void* xs[4] = {};
+  for (int m = 0; m < n; ++m) xs[m] = G.slot[m] < 0 ? x : (const char*)workspace + (size_t)G.slot[m] * G.block_bytes;
+  void* const partials = need > xp_bytes ? (char*)workspace + xp_bytes : nullptr;
+  const hipError_t e = vptq::launch_gemm_gather12w_grouped(G.plain, n, xs, y, tokens, (flags & VPTQ_GEMV_OUT_F32) != 0, parts, partials, st);   // (stream order is the dependency)
+  return e == hipSuccess ? VPTQ_OK : hip_fail(e, "gemm_gather12w_grouped launch");
+}
+
+int vptq_quant_gemm_gather12w_grouped_instance(const VptqLayerDesc* descs, int n, int tokens, int, int parts, char* buf, size_t bytes) {
+  if (!descs || !buf || bytes < 1) return fail(VPTQ_E_NULL, "descs / buf is NULL");
+  buf[0] = 0;
+  if (const int rc = grouped_gather12w_validate(descs, n, tokens, parts)) return rc;
+  Text t = {buf, bytes, 0, true};
+  const GroupedGatherPlan G = grouped_gather_decide(descs, n, tokens);
+  if (G.n_perms > 0) {
+    const vptq::GemmGatherPxDecision D = vptq::gemm_gather_px_decide(descs[G.owner[0]], tokens);
+    t.add("permute_x_tokens g=%d tok=%d grid=%dx%d tpt=%d perms=%d | ", D.g, D.tok, D.grid_x, D.grid_y, D.tpt, G.n_perms);
+  } else {
+    t.add("none | ");
+  }
+  const vptq::GemmGather12wGroupedDecision D = vptq::gemm_gather12w_grouped_decide(G.plain, n, tokens, parts);
+  t.add("gemm_gather12w_grouped dt=%s ib=%d rb=%d res=%s tok=%d tb=%d n=%d groups=", dt_text(D.base.f16), D.base.ib, D.base.rb,
+        D.base.res == 0 ? "none" : D.base.res == 1 ? "lds" : "l2", D.base.tok, D.tb, D.n);
+  for (int m = 0; m < D.n; ++m) t.add(m ? "+%d" : "%d", D.groups[m]);
+  t.add(" tiles=%d parts=%d tpp=%d wgcu=%d items=%d grid=%d rgs=%d", D.base.tiles, D.parts, D.tpp, D.base.wgcu, D.items, D.grid, D.rgs);
+  if (D.parts >= 2) t.add(" | gemm_gather12w_grouped_sum dt=%s parts=%d grid=%dx%d", dt_text(D.base.f16), D.parts, D.sum_grid_x, D.sum_grid_y);
+  if (!t.fits) buf[0] = 0;
+  return instance_done(t);
+}
+
 // the checks of vptq_dequant and vptq_dequant_instance
 static int validate_dequant(const VptqLayerDesc* d, const void* W) {
   int rc = validate_layer(d);

@@ -41,7 +41,7 @@
 // LDS: 48 KiB + the table.  Registers: g12_min_wg workgroups per CU; no instantiation has scratch (profiles/r37/listings.md).  No
 // atomics, no scratch, plain vector stores.
 // NOT HERE: 17 - 48 tokens (gemm_gather12w.hip), sibling groups, v = 6 (8 vector-rows per 48 outputs), the folded / selective arithmetics.
-// gemm_gather12c.hip (column parts), gemm_gather12w.hip (token blocks) and gemm_gather12_grouped.hip (sibling groups) hold COPIES of the row-group body: A CHANGE HERE BELONGS THERE TOO.
+// gemm_gather12c.hip (column parts), gemm_gather12w.hip (token blocks), gemm_gather12_grouped.hip (sibling groups) and gemm_gather12w_grouped.hip (sibling groups, token blocks) hold COPIES of the row-group body: A CHANGE HERE BELONGS THERE TOO.
 #include "gemm_gather_tile.h"
 #include "launch.h"
 

@@ -19,7 +19,7 @@
 //    [N block][chunk][16 outputs][16 bytes] with the slot XOR-ed by chunk & 7, four K-steps per wave x three mfma16x16x32<DT>, the
 //    gathers of tile t + 1 in flight during the MFMAs of tile t).  A copy for the reason given there: as a shared function such bodies
 //    have twice cost 3 - 8 % and changed the parents' listings (profiles/r17, profiles/r31).  A CHANGE TO THE BODY HERE BELONGS IN
-//    gemm_gather12.hip, gemm_gather12c.hip AND gemm_gather12w.hip TOO, AND THE OTHER WAY ROUND.
+//    gemm_gather12.hip, gemm_gather12c.hip, gemm_gather12w.hip AND gemm_gather12w_grouped.hip TOO, AND THE OTHER WAY ROUND.
 //  * EPILOGUE: the 4 waves' three partial D meet in LDS and are added in wave order.  S == 1: the output bias is added in fp32, the sum
 //    rounded once and stored into y[m] (VPTQ_GEMV_OUT_F32: the fp32 sum) - gemm_gather12's epilogue.  S >= 2: the raw fp32 sums of all 48
 //    outputs go to partials_m[part][token][rg x 48 + 0 ... 47] in the workspace (plain vector stores; no atomics, no counters, no
@@ -32,7 +32,7 @@
 // BIT CONTRACT: an item depends neither on the grid nor on the workgroup that runs it.  For S >= 2, y[m] is bit-identical to
 // vptq_quant_gemm_gather12c(descs[m], parts = S); for S == 1 to vptq_quant_gemm_gather12(descs[m]) - at the same token count and x.
 // LDS 48 KiB + the table; 2 workgroups per CU as the parents; no instantiation has scratch (profiles/r40/listings.md).
-// NOT HERE: 17 - 48 tokens of v = 12 groups (gemm_gather12w's token-block pass behind this walk), groups of mixed format, v = 6, the
+// NOT HERE: 17 - 48 tokens of v = 12 groups (gemm_gather12w_grouped.hip: gemm_gather12w's token-block pass behind this walk), groups of mixed format, v = 6, the
 // folded / selective arithmetics.
 #include "gemm_gather_tile.h"
 #include "launch.h"

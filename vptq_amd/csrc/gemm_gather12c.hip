@@ -10,7 +10,7 @@
 //    three roundings, the 48 KiB tile [N block][chunk][16 outputs][16 bytes] with the slot XOR-ed by chunk & 7, four K-steps per wave x
 //    three v_mfma_f32_16x16x32, the gathers of tile t + 1 in flight during the MFMAs of tile t).  A copy for the reason given there:
 //    as a shared function such bodies have twice cost 3 - 8 % and changed the parents' listings (profiles/r17, profiles/r31).  A CHANGE
-//    TO THE BODY HERE BELONGS IN gemm_gather12.hip, gemm_gather12w.hip (its third copy) AND gemm_gather12_grouped.hip (its fourth) TOO, AND THE OTHER WAY ROUND.
+//    TO THE BODY HERE BELONGS IN gemm_gather12.hip, gemm_gather12w.hip (its third copy), gemm_gather12_grouped.hip (its fourth) AND gemm_gather12w_grouped.hip (its fifth) TOO, AND THE OTHER WAY ROUND.
 //  * WHAT DIFFERS: the tile loop runs over [t0, t1) of the part; the index window, g12c_dcol, the scale / bias prefetch and the x
 //    columns start at tile t0.  The prefetch of "the tile after next" (index window, scale / bias) and the preamble's second window are
 //    clamped to the PART's last tile, t1 - 1 (ptile), and then by g12c_dcol inside the row as in the parent: the address is one the

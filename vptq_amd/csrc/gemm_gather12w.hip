@@ -15,7 +15,7 @@
 //    from L2, the reference's three roundings, the 48 KiB tile [N block][chunk][16 outputs][16 bytes] with the slot XOR-ed by chunk & 7,
 //    the gathers of tile t + 1 in flight during the MFMAs of tile t, prefetches clamped to the part's last tile).  A copy for the
 //    reason given there: as a shared function such bodies have twice cost 3 - 8 % and changed the parents' listings (profiles/r17,
-//    profiles/r31).  A CHANGE TO THE BODY HERE BELONGS IN gemm_gather12.hip, gemm_gather12c.hip AND gemm_gather12_grouped.hip TOO, AND THE OTHER WAY ROUND.
+//    profiles/r31).  A CHANGE TO THE BODY HERE BELONGS IN gemm_gather12.hip, gemm_gather12c.hip, gemm_gather12_grouped.hip AND gemm_gather12w_grouped.hip TOO, AND THE OTHER WAY ROUND.
 //  * TOKEN BLOCKS.  Lane (token mj, k group mkg) of block b reads row 16 b + mj of x, clamped to the last token and masked past it
 //    (gt_load_a1: the uniform base + a 32-bit lane offset, one address register per load).  Per K-step a wave reads the three N
 //    blocks' B operands ONCE (three ds_read_b128) and every read feeds all TB token blocks before the next one: 3 x TB
@@ -40,7 +40,7 @@
 // token, at S >= 2 what vptq_quant_gemm_gather12c gives it with the same (S, tpp), in a call of <= 16 tokens.
 // There is no form with a permutation (permute_x_tokens in front, vptq_quant_gemm_gather12w).  LDS 48 KiB + the table.  No atomics, no
 // scratch in any of the 12 instantiations (profiles/r39/listings.md), plain vector stores only.
-// NOT HERE: a fourth token block (49 - 64 tokens), sibling groups, v = 6, the folded / selective arithmetics.
+// NOT HERE: a fourth token block (49 - 64 tokens), sibling groups (gemm_gather12w_grouped.hip), v = 6, the folded / selective arithmetics.
 #include "gemm_gather_tile.h"
 #include "launch.h"
 

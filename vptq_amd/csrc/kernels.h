@@ -348,6 +348,22 @@ GemmGather12GroupedDecision gemm_gather12_grouped_decide(const VptqLayerDesc* de
 hipError_t launch_gemm_gather12_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
                                         int parts, void* partials, hipStream_t st);
 
+// gemm_gather12w_grouped.hip - the same groups, 17 - 48 tokens, in ONE launch of gemm_gather12w_grouped_kernel<DT, RES, TB>: gemm_gather12w's
+// token-block pass (tb = 2 / 3 blocks of 16 tokens) over gemm_gather12_grouped's item list and member walk; S == 1: the kernel finishes
+// every y[m] itself; S >= 2: raw fp32 sums go to each member's partials [S][tokens][op[m]] and ONE launch of
+// gemm_gather12w_grouped_sum_kernel<DT> adds them in ascending part order; plain form only.  base: gemm_gather12_decide's of the first
+// member with tok, wgcu (the smaller of the LDS bound and the kernel's register bound), grid and rgs of THIS launch; parts > 0: a
+// request, gemm_gather12w's formula; parts == 0: gemm_gather12w_rule_parts over the total row groups and CUs x wgcu;
+// partial_bytes[m]: rounded up to 256, 0 where S == 1
+struct GemmGather12wGroupedDecision {
+  GemmGather12Decision base;
+  int tb, n, parts, tpp, items, grid, rgs, sum_grid_x, sum_grid_y, groups[4], first_item[5], op[4], first_block[5];
+  size_t partial_bytes[4];
+};
+GemmGather12wGroupedDecision gemm_gather12w_grouped_decide(const VptqLayerDesc* descs, int n, int tokens, int parts);
+hipError_t launch_gemm_gather12w_grouped(const VptqLayerDesc* descs, int n, const void* const* x, void* const* y, int tokens, bool out_f32,
+                                         int parts, void* partials, hipStream_t st);
+
 // gemm_gather_px.hip - a layer with a column permutation through the three kernels above in their forms WITHOUT one: xp[t][c] =
 // x[t][perm[c]] written once per call into a workspace (permute_x_tokens_kernel), then the layer's kernel over gemm_gather_px_plain(d)
 // - scale_permuted / bias_permuted as scale / bias, no permutation - with x = xp: the bits of the layer's own entry

@@ -9,7 +9,8 @@ measured cells, and `GROUPED_DECODE_ROUTES`, the ordered record of the group rou
 beyond its first window; `GROUPED_DECODE_X_ROUTES`: the routes of formats the first table has no owner for; `sibling_decode_routes`
 reads all three; `GROUPED_DECODE_X_WIDE_ROUTES`: those formats' routes beyond their first window, read behind the others by
 `sibling_group_routes`; `GROUPED_DECODE_V12_ROUTES`: the v = 12 formats' `vptq_quant_gemm_gather12_grouped`, 5 - 16 tokens, read behind
-all of them by `sibling_group_v12_routes`).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
+all of them by `sibling_group_v12_routes`; `GROUPED_DECODE_V12_WIDE_ROUTES`: their `vptq_quant_gemm_gather12w_grouped`, 17 - 48 tokens, read
+behind that by `sibling_group_v12_wide_routes`).  These routes are a group's, not a layer's: `BATCHED_DECODE_ROUTES` and the layers' cell tables do not know it, and a group that
 is not routed here leaves every member on the routes it had.  `SiblingGroup.forward_batched` (vptq_amd/layers/vqlinear.py) and
 `prepare_model` decide through it.
 """
@@ -356,7 +357,7 @@ def gemm_gatherxw_grouped_tokens(vector_len: int, num_centroids: int, num_res_ce
 # WHICH groups of the large-codebook formats of VECTOR LENGTH 12 (`vptq_quant_gemm_gather12`'s: v12-k65536-4096 / -256 / -0, `_v12_owns` of
 # vptq_amd/batched_decode.py) take `vptq_quant_gemm_gather12_grouped` (gemm_gather12_grouped.hip: gemm_gather12c's (row group, column
 # part) items of every member as one list, one sum launch for the group where the columns are split), 5 - 16 tokens (1 - 4 tokens are
-# `SiblingGroup.forward` / `forward_sliced`'s; 17 - 48 have no group route).  Without it every member goes out alone: gemm_gather12,
+# `SiblingGroup.forward` / `forward_sliced`'s; 17 - 48 tokens are `vptq_quant_gemm_gather12w_grouped`'s, below).  Without it every member goes out alone: gemm_gather12,
 # gemm_gather12c, two gemv_gatherx launches or vptq_dequant + a dense GEMM, whichever `BATCHED_DECODE_V12_ROUTES` /
 # `BATCHED_DECODE_V12_COLUMN_ROUTES` give a layer of its format and size, each behind an x gather of its own when permuted.  A cell has
 # `_GEMM_GATHERXW_GROUPED_CELLS`' format without the vector length: (main centroids, residual centroids, has_perm, member count, least
@@ -412,6 +413,65 @@ def gemm_gather12_grouped_tokens(vector_len: int, num_centroids: int, num_res_ce
     sizes the stream's workspace to the largest"""
     return tuple(t for t in range(GEMM_GATHER12_GROUPED_MIN_TOKENS, GEMM_GATHER12_GROUPED_MAX_TOKENS + 1)
                  if gemm_gather12_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
+
+
+# WHICH groups of the v = 12 formats take `vptq_quant_gemm_gather12w_grouped` (gemm_gather12w_grouped.hip: gemm_gather12w's token-block
+# pass behind gemm_gather12_grouped's member walk), 17 - 48 tokens - the window beyond `vptq_quant_gemm_gather12_grouped`'s.  Without it
+# every member goes out alone from the 17th token on: vptq_dequant + a dense GEMM or, behind its knob, gemm_gather12w (one to two
+# launches and an x gather per member), whichever `BATCHED_DECODE_V12_WIDE_ROUTES` gives a layer of its format and size.  A cell has
+# `_GEMM_GATHER12_GROUPED_CELLS`' format: (main centroids, residual centroids, has_perm, member count, least TOTAL index elements of the
+# group, most total index elements or None, least tokens, most tokens).  Routed by the rule of the tables above: the grouped launch
+# beats the SUM of what the members take without it by more than the larger of 5 % and three times the larger run-to-run spread, in
+# every measured cell of the region, in both dtypes; a region reaches from its smallest to its largest measured group of its member
+# count and no further; no cell lies under GEMM_GATHER12W_GROUPED_MIN_ELEMENTS (1 M total index elements).
+# tools/gemm_gather12_grouped_bench.py --wide writes the table.  VPTQ_GEMM_GATHER12W_GROUPED=1 / 0 (with VPTQ_TUNING=1): every group of
+# the kernel's formats from 17 to 48 tokens / none.
+#
+# profiles/r41/table.md, profiles/r41/README.md (one MI355X, fp16 and bf16, v12-k65536-4096 / -256 / -0, q / k / v and gate / up of the 8B and
+# 70B shapes = 2.0 M, 6.7 M, 9.3 M and 37.3 M total index elements, tokens 17 / 24 / 32 / 33 / 40 / 48, parts = 0, with one shared permutation
+# and without; 288 cells, every member has the bits of its own entry in every one, 266 win; run-to-run spreads at most 2.4 %; the
+# parent is the members' dense routes):
+#   17 - 32 tokens   all 144 cells win: 8B q / k / v 0.41 - 0.61 of the parent, 70B q / k / v 0.48 - 0.87, 8B gate / up 0.52 - 0.89, 70B gate / up
+#                    0.37 - 0.78
+#   33 - 48 tokens   v12-k65536-0 wins everywhere (0.41 - 0.77); with a residual table the kernel runs at ONE workgroup per CU: with a
+#                    permutation 0.48 - 0.86 except the 8B gate / up pair of -4096 in bf16 (0.96 - 1.00); without one the 8B gate / up pair
+#                    is level or slower (0.95 - 1.27) and bf16 does not win on the 70B q / k / v (0.96 - 1.15)
+# NO CELL IS SHIPPED YET: the regions that win in every measured cell are listed in profiles/r41/README.md, but the suites were not run
+# with them in place, so the tuple is empty and the entry is reached by the knob (and `ops.quant_gemm_gather12w_grouped`) alone.
+_GEMM_GATHER12W_GROUPED_CELLS = ()
+GEMM_GATHER12W_GROUPED_MIN_TOKENS, GEMM_GATHER12W_GROUPED_MAX_TOKENS = 17, 48
+GEMM_GATHER12W_GROUPED_MIN_ELEMENTS = 1 << 20
+GEMM_GATHER12W_GROUPED_MAX_MEMBERS = 4
+_GEMM_GATHER12W_GROUPED_MODE = (B.tune_env("VPTQ_GEMM_GATHER12W_GROUPED", "auto") or "auto").strip().lower()
+
+
+def gemm_gather12w_grouped_route(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                 in_features: int, tokens: int, has_perm: Optional[bool]) -> bool:
+    """does a group of sibling layers of this format (shared by its members) with these output widths take
+    `vptq_quant_gemm_gather12w_grouped` (parts = 0: the library's rule) for `tokens` tokens?  has_perm: True - every member has a
+    column permutation, False - none, None - some.  Pure: no device, no library (whether the library serves the group is
+    `vptq_quant_gemm_gather12w_grouped_supported`'s answer).  Only for the v = 12 formats: a group has one route per window."""
+    if _GEMM_GATHER12W_GROUPED_MODE in ("0", "off") or not GEMM_GATHER12W_GROUPED_MIN_TOKENS <= tokens <= GEMM_GATHER12W_GROUPED_MAX_TOKENS:
+        return False
+    n = len(out_features_tuple)
+    if not 2 <= n <= GEMM_GATHER12W_GROUPED_MAX_MEMBERS or in_features % 8 or not _v12_owns(vector_len, num_centroids, num_res_centroids):
+        return False
+    if _GEMM_GATHER12W_GROUPED_MODE in ("1", "on"):
+        return True
+    if has_perm is None:
+        return False
+    n_el = sum((o + vector_len - 1) // vector_len for o in out_features_tuple) * in_features
+    return any((k, kr) == (num_centroids, num_res_centroids) and perm == has_perm and members == n and
+               n_el >= max(min_el, GEMM_GATHER12W_GROUPED_MIN_ELEMENTS) and (max_el is None or n_el <= max_el) and
+               min_tok <= tokens <= max_tok for k, kr, perm, members, min_el, max_el, min_tok, max_tok in _GEMM_GATHER12W_GROUPED_CELLS)
+
+
+def gemm_gather12w_grouped_tokens(vector_len: int, num_centroids: int, num_res_centroids: int, out_features_tuple: Sequence[int],
+                                  in_features: int, has_perm: Optional[bool]) -> tuple:
+    """the token counts the route function gives to the grouped launch for this group, ascending (possibly none): `prepare_model`
+    sizes the stream's workspace to the largest"""
+    return tuple(t for t in range(GEMM_GATHER12W_GROUPED_MIN_TOKENS, GEMM_GATHER12W_GROUPED_MAX_TOKENS + 1)
+                 if gemm_gather12w_grouped_route(vector_len, num_centroids, num_res_centroids, out_features_tuple, in_features, t, has_perm))
 
 
 class GroupedDecodeRoute(NamedTuple):
@@ -528,3 +588,23 @@ def sibling_group_v12_routes(vector_len: int, num_centroids: int, num_res_centro
     What `SiblingGroup` reads.  No knob is read."""
     return sibling_group_routes(vector_len, num_centroids, num_res_centroids) + \
         tuple(r for r in GROUPED_DECODE_V12_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))
+
+
+# the v = 12 formats' route BEYOND their first window: `vptq_quant_gemm_gather12w_grouped`, 17 - 48 tokens behind
+# `vptq_quant_gemm_gather12_grouped`'s 5 - 16.  (A table and a reader of its own: the five tables above and their five readers keep every
+# answer they gave before.)  extra = (0,): `parts` = the library's rule.  The window lies inside GROUPED_DECODE_MIN_TOKENS ...
+# GROUPED_DECODE_MAX_TOKENS.
+GROUPED_DECODE_V12_WIDE_ROUTES = (
+    GroupedDecodeRoute("vptq_quant_gemm_gather12w_grouped", _v12_owns,
+                       lambda v, k, kr, outs, width, tokens, has_perm: gemm_gather12w_grouped_route(v, k, kr, outs, width, tokens, has_perm),
+                       lambda v, k, kr, outs, width, has_perm: gemm_gather12w_grouped_tokens(v, k, kr, outs, width, has_perm),
+                       GEMM_GATHER12W_GROUPED_MIN_TOKENS, GEMM_GATHER12W_GROUPED_MAX_TOKENS, B.GEMV_FORCE_GENERIC, extra=(0,)),
+)
+
+
+def sibling_group_v12_wide_routes(vector_len: int, num_centroids: int, num_res_centroids: int) -> tuple:
+    """every group route a `SiblingGroup` of this format can take, in window order: `sibling_group_v12_routes`' answer, then the records
+    of `GROUPED_DECODE_V12_WIDE_ROUTES` that own the format (none for any format but the v = 12 ones).  What `SiblingGroup` reads.  No
+    knob is read."""
+    return sibling_group_v12_routes(vector_len, num_centroids, num_res_centroids) + \
+        tuple(r for r in GROUPED_DECODE_V12_WIDE_ROUTES if r.owns(vector_len, num_centroids, num_res_centroids))

@@ -44,8 +44,8 @@ from vptq_amd.batched_decode import (  # noqa: F401
 # the batched-decode rules of a GROUP of siblings live in vptq_amd/grouped_decode.py: `GROUPED_DECODE_ROUTES`, one record per group
 # route (the knobs and cells are read there, at call time); the guard's window is the union of the routes' windows
 from vptq_amd.grouped_decode import (  # noqa: F401
-    GROUPED_DECODE_MAX_TOKENS, GROUPED_DECODE_MIN_TOKENS, GROUPED_DECODE_V12_ROUTES, GROUPED_DECODE_X_WIDE_ROUTES, gemm_gather_grouped_route, gemm_gather_grouped_tokens, gemm_k256_grouped_route,
-    gemm_k256_grouped_tokens, grouped_decode_route, grouped_decode_routes, sibling_decode_routes, sibling_group_routes, sibling_group_v12_routes)
+    GROUPED_DECODE_MAX_TOKENS, GROUPED_DECODE_MIN_TOKENS, GROUPED_DECODE_V12_ROUTES, GROUPED_DECODE_V12_WIDE_ROUTES, GROUPED_DECODE_X_WIDE_ROUTES, gemm_gather_grouped_route, gemm_gather_grouped_tokens, gemm_k256_grouped_route,
+    gemm_k256_grouped_tokens, grouped_decode_route, grouped_decode_routes, sibling_decode_routes, sibling_group_routes, sibling_group_v12_routes, sibling_group_v12_wide_routes)
 # the sliced-layout rules (1 - 4 tokens) live in vptq_amd/sliced_routes.py and are read through the module (`R.exact_route_is_large`:
 # one monkeypatch changes every reader); only import-time constants that nothing assigns to are imported by name, for the hot guard
 from vptq_amd import sliced_routes as R
@@ -140,8 +140,8 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
     `stream` - so a first one-token step captured on `stream` takes the sliced kernels.  The stream's `B.gemv_workspace` is grown to
     the largest x[perm] copy (`vptq_quant_gemm_gather_px_workspace_bytes` at 48 tokens) of the permuted layers `gemm_gather_px_route`
     routes, and to the x[perm] copies `vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_gatherw_grouped` / `vptq_quant_gemm_gatherx_grouped` /
-    `vptq_quant_gemm_gatherxw_grouped` / `vptq_quant_gemm_gather12_grouped` (x[perm] copies and the partial sums of its column parts) / `vptq_quant_gemm_k256_grouped` need for the linked sibling groups their routes (`gemm_gather_grouped_route` /
-    `gemm_gatherw_grouped_route` / `gemm_gatherx_grouped_route` / `gemm_gatherxw_grouped_route` / `gemm_gather12_grouped_route` / `gemm_k256_grouped_route`) route (the largest need over a format's records, each at its largest routed token count), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
+    `vptq_quant_gemm_gatherxw_grouped` / `vptq_quant_gemm_gather12_grouped` / `vptq_quant_gemm_gather12w_grouped` (x[perm] copies and the partial sums of their column parts) / `vptq_quant_gemm_k256_grouped` need for the linked sibling groups their routes (`gemm_gather_grouped_route` /
+    `gemm_gatherw_grouped_route` / `gemm_gatherx_grouped_route` / `gemm_gatherxw_grouped_route` / `gemm_gather12_grouped_route` / `gemm_gather12w_grouped_route` / `gemm_k256_grouped_route`) route (the largest need over a format's records and over every routed token count of each), so a 5 - 48 token step captured afterwards keeps those routes.  Returns {"layers": {name: {"built", "bytes", "seconds"}},
     "built": layers with a layout, "bytes", "seconds"}."""
     rep = {"layers": {}, "built": 0, "bytes": 0, "seconds": 0.0}
     px = {}   # device index -> (device, most workspace bytes of its routed permuted layers)
@@ -159,7 +159,7 @@ def prepare_model(model: nn.Module, stream=None) -> dict:
             px[cache.device_index] = (cache.device, max(need, px.get(cache.device_index, (None, 0))[1]))
     if not torch.cuda.is_available() or torch.cuda.is_current_stream_capturing():
         return rep
-    # ... and to the x[perm] copies of the sibling groups their batched-decode route takes, at the largest routed token count
+    # ... and to the x[perm] copies of the sibling groups their batched-decode route takes, the largest need over the routed token counts
     groups = {id(g): g for g in (m.__dict__.get("_siblings") for m in model.modules() if isinstance(m, VQuantLinear)) if g is not None}
     for g in groups.values():
         if all(m._parameters["indices"].is_cuda for m in g.members if "_compact" not in m.__dict__):
@@ -241,7 +241,7 @@ class SiblingGroup:
         None - some), or None where the members do not share format and width or are not one-codebook layers with scale and bias.
         `_batched_route` is the first record of the format's group routes (`sibling_group_routes`, vptq_amd/grouped_decode.py: the
         owner in `GROUPED_DECODE_ROUTES`, then its wide routes; for gemm_gatherx's formats the record of `GROUPED_DECODE_X_ROUTES`, then
-        that of `GROUPED_DECODE_X_WIDE_ROUTES` where it routes the group at all; for the v = 12 formats the record of `GROUPED_DECODE_V12_ROUTES`, read through `sibling_group_v12_routes`, where it routes the group at all), or None; with a token count, the record of the format whose window holds it."""
+        that of `GROUPED_DECODE_X_WIDE_ROUTES` where it routes the group at all; for the v = 12 formats the record of `GROUPED_DECODE_V12_ROUTES`, then that of `GROUPED_DECODE_V12_WIDE_ROUTES`, read through `sibling_group_v12_wide_routes`, each where it routes the group at all), or None; with a token count, the record of the format whose window holds it."""
         st = self.__dict__.get("_bstatic")
         if st is None:
             ms = self.members
@@ -253,10 +253,10 @@ class SiblingGroup:
                 v, k, kr, width = next(iter(fmt))
                 st = ((v, k, kr, tuple(m.out_features for m in ms), width, perms.pop() if len(perms) == 1 else None),)
             self._bstatic = st
-            # (a record of `GROUPED_DECODE_X_WIDE_ROUTES` / `GROUPED_DECODE_V12_ROUTES` only where its knob and cells, read once here, route
+            # (a record of `GROUPED_DECODE_X_WIDE_ROUTES` / `GROUPED_DECODE_V12_ROUTES` / `GROUPED_DECODE_V12_WIDE_ROUTES` only where its knob and cells, read once here, route
             # some token count of THIS group: a group it never routes answers None for that window, as before the record existed)
-            routes = sibling_group_v12_routes(*st[0][:3]) if st[0] is not None else ()
-            self._broutes = tuple(r for r in routes if r not in GROUPED_DECODE_X_WIDE_ROUTES + GROUPED_DECODE_V12_ROUTES or r.tokens(*st[0]))
+            routes = sibling_group_v12_wide_routes(*st[0][:3]) if st[0] is not None else ()
+            self._broutes = tuple(r for r in routes if r not in GROUPED_DECODE_X_WIDE_ROUTES + GROUPED_DECODE_V12_ROUTES + GROUPED_DECODE_V12_WIDE_ROUTES or r.tokens(*st[0]))
             self._broute = self._broutes[0] if self._broutes else None
         return st[0]
 
@@ -272,7 +272,7 @@ class SiblingGroup:
 
     def _batched_plan(self, r=None):
         """the descriptor array the group route's entry (`vptq_quant_gemm_gather_grouped` / `vptq_quant_gemm_gatherw_grouped` / `vptq_quant_gemm_gatherx_grouped` /
-        `vptq_quant_gemm_gatherxw_grouped` / `vptq_quant_gemm_gather12_grouped` / `vptq_quant_gemm_k256_grouped`) is called
+        `vptq_quant_gemm_gatherxw_grouped` / `vptq_quant_gemm_gather12_grouped` / `vptq_quant_gemm_gather12w_grouped` / `vptq_quant_gemm_k256_grouped`) is called
         with, (descs, caches), decided once per entry (r: a record of the format, default its first) and per set of descriptor generations - or None: no route has the format, a compacted member, a library without the entry, members on several devices or of
         several dtypes, a group the library does not serve.  Members whose `perm` tensors are `torch.equal` get ONE perm pointer in
         their descriptor copies (the first such member's): the entry then gathers x once for them.  Not decided inside a stream
@@ -311,8 +311,10 @@ class SiblingGroup:
 
     def _batched_workspace_bytes(self):
         """(device, device index, bytes) of stream workspace the largest call the group's batched-decode route can take needs
-        (`prepare_model` grows the stream's buffer to it) - the largest need over the format's records, each at its largest routed
-        token count - or None: the group never takes such a route"""
+        (`prepare_model` grows the stream's buffer to it) - the largest need over the format's records and over every routed token
+        count of each (the need does not always rise with the tokens: `vptq_quant_gemm_gather12w_grouped` cuts fewer column parts
+        where its third token block runs at one workgroup per CU, so a 32-token call can need more than a 48-token one) - or None:
+        the group never takes such a route"""
         st = self._batched_static()
         if self._batched_route() is None:
             return None
@@ -325,7 +327,8 @@ class SiblingGroup:
             descs, caches = plan
             if r.exact_only and not all(c.arithmetic_flags & B.GEMV_EXACT for c in caches):
                 continue
-            need = int(getattr(B.lib(), r.entry + "_workspace_bytes")(descs, len(caches), routed[-1], *r.extra))
+            query = getattr(B.lib(), r.entry + "_workspace_bytes")
+            need = max(int(query(descs, len(caches), t, *r.extra)) for t in routed)
             if best is None or need > best[2]:
                 best = (caches[0].device, caches[0].device_index, need)
         return best
@@ -333,7 +336,7 @@ class SiblingGroup:
     def forward_batched(self, layer, x, tokens):
         """5 - 48 tokens of large-codebook and of canonical-format siblings: ONE launch for the group (the entry of the group's record
         whose window holds the token count: `vptq_quant_gemm_gather_grouped` up to 16 tokens / `vptq_quant_gemm_gatherw_grouped` from 17 /
-        `vptq_quant_gemm_gatherx_grouped` (gemm_gatherx's formats, up to 16 tokens) / `vptq_quant_gemm_gatherxw_grouped` (the same, from 17) / `vptq_quant_gemm_gather12_grouped` (the v = 12 formats, up to 16 tokens) / `vptq_quant_gemm_k256_grouped`, one x gather per distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
+        `vptq_quant_gemm_gatherx_grouped` (gemm_gatherx's formats, up to 16 tokens) / `vptq_quant_gemm_gatherxw_grouped` (the same, from 17) / `vptq_quant_gemm_gather12_grouped` (the v = 12 formats, up to 16 tokens) / `vptq_quant_gemm_gather12w_grouped` (the same, from 17) / `vptq_quant_gemm_k256_grouped`, one x gather per distinct permutation) where the group's route (vptq_amd/grouped_decode.py) takes the call; same protocol as `forward` -
         the first member called launches, the others pick their output up when they are called with the very same tensor at the
         same version.  None = not this group's route (no route has the format, the route function says no, a compacted member,
         mixed formats or dtypes, a group the library does not serve, a member whose arithmetic is not the reference's roundings where

@@ -21,7 +21,7 @@ from torch.nn import functional as F
 from vptq_amd import _backend as B
 from vptq_amd.batched_decode import BATCHED_DECODE_MIN_TOKENS, batched_decode_routes, batched_decode_takes, batched_decode_v12_column_routes, batched_decode_v12_routes, batched_decode_v12_wide_routes, batched_decode_wide_routes
 
-__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12_grouped", "quant_gemm_gather12c", "quant_gemm_gather12w", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
+__all__ = ["dequant", "quant_gemm", "quant_gemm_gather", "quant_gemm_gather12", "quant_gemm_gather12_grouped", "quant_gemm_gather12c", "quant_gemm_gather12w", "quant_gemm_gather12w_grouped", "quant_gemm_gather_grouped", "quant_gemm_gather_px", "quant_gemm_gatherw", "quant_gemm_gatherw_grouped", "quant_gemm_gatherx", "quant_gemm_gatherx_grouped", "quant_gemm_gatherxw", "quant_gemm_gatherxw_grouped", "quant_gemm_k256_grouped", "quant_gemm_k256w",
            "quant_gemv_v2"]
 
 # env knob: VPTQ_EXACT=1 forces the reference CPU path's three 16-bit roundings per weight whatever the arithmetic mode
@@ -533,6 +533,28 @@ def quant_gemm_gather12_grouped(x: torch.Tensor, descs, out_features, parts: int
     if not B.lib().vptq_quant_gemm_gather12_grouped_supported(descs, n, x.numel() // x.shape[-1], int(parts)):
         return None
     return _grouped_launch("vptq_quant_gemm_gather12_grouped", x, descs, out_features, out_f32, extra=(int(parts),))
+
+
+def quant_gemm_gather12w_grouped(x: torch.Tensor, descs, out_features, parts: int = 0, out_f32: bool = False):
+    """[y_m = x @ W_m^T + bias_m] for 17 - 48 tokens of 2 - 4 sibling layers `quant_gemm_gather12w` serves (vector length 12; one dtype,
+    input width and format: main and residual codebook size; with or without a column permutation) in ONE launch
+    (`vptq_quant_gemm_gather12w_grouped`, gemm_gather12w_grouped.hip: 2 / 3 blocks of 16 tokens over the members' (row group of 48
+    outputs, column part) items as one list) - plus, where the columns are split, one small launch that adds every member's parts in
+    ascending order - behind one x[:, perm] gather per DISTINCT `perm` pointer of the members.  x[:, perm] and the partial sums go
+    through this stream's workspace (`B.gemv_workspace`).  parts: the column parts asked for (whole 512-column tiles, at most 16; 1 =
+    no split), 0: the library's rule.  With S parts cut, every y_m has the bits of `quant_gemm_gather12w(x, descs[m], ..., parts=S)`.
+    `descs` = a ctypes array (or a sequence) of LayerDesc of a group `vptq_quant_gemm_gather12w_grouped_supported(descs, n, tokens,
+    parts)` accepts; `out_features`: the members' output widths; out_f32: the un-rounded fp32 sums.  Returns the list of outputs, or
+    None where the library does not serve the group or where a stream capture is in progress and the workspace is too small (nothing
+    is allocated or launched then; `prepare_model` sizes it beforehand for the linked groups the route function routes, at parts = 0,
+    to the largest need over the routed token counts - the need can FALL from 32 to 33 tokens, where the rule cuts fewer parts)."""
+    import ctypes as C
+    n = len(out_features)
+    if not isinstance(descs, C.Array):
+        descs = (B.LayerDesc * n)(*descs)
+    if not B.lib().vptq_quant_gemm_gather12w_grouped_supported(descs, n, x.numel() // x.shape[-1], int(parts)):
+        return None
+    return _grouped_launch("vptq_quant_gemm_gather12w_grouped", x, descs, out_features, out_f32, extra=(int(parts),))
 
 
 def quant_gemm_k256w(x: torch.Tensor, desc, out_features: int, out_f32: bool = False) -> torch.Tensor:
